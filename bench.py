@@ -17,7 +17,14 @@ WORLD_SIZE is not set — bench.py starts the N ranks itself.
 --config C1: configs[0], the reference's own CPU-runnable case: the bonsai stand-in through createSortWorker under Node,
 the reference's WASM sorter on the host beside the HIP sorter, outputs compared bit for bit.
 
-Prints ONE JSON line on rank 0 (see the task contract) with `roofline`, `blend`, `frame` and `cpu_baseline` objects.
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, warm-up, the N timed steps and ONE JSON
+line on rank 0 (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  `--full` adds everything else the
+line used to carry: the hipEvent-bracketed median, per-stage times, `roofline`, `blend`, `frame`, the pipelined / fork-join
+contexts, the secondary columns and scenes, the one-GPU references of a multi-GPU run and `cpu_baseline`.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step - the frame and (one GPU) the
+sorted index list - as DIR/<name>.npy (float32; see dump_outputs).  The scenes are seeded, so the same arguments give the
+same inputs in every run.
 """
 import argparse
 import glob
@@ -250,24 +257,63 @@ class Watchdog:
         return False
 
 
+# Outputs of the timed path (--dump-outputs): float32 values, at most this many bytes in all
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array of `arrays` (name -> array) as out_dir/<name>.npy in float32 (float64 when an integer array
+    holds values float32 cannot represent exactly).  The arrays share DUMP_BUDGET_BYTES, smallest first: each may use the
+    budget left divided by the arrays still to come; one that does not fit is replaced by a fixed, seeded sample of its
+    flattened values (the same positions for the same size in every run, ascending).  Returns {name: [shape written, shape
+    computed]}."""
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: np.asarray(arrays[k]).size)):
+        a = np.asarray(arrays[name])
+        exact32 = a.dtype.kind not in "iu" or a.size == 0 or (int(a.max()) < (1 << 24) and int(a.min()) > -(1 << 24))
+        dt = np.dtype(np.float32 if exact32 else np.float64)
+        cap = max((left // (len(arrays) - i) - 4096) // dt.itemsize, 0)       # (4 KiB for the .npy header)
+        shape = a.shape
+        if a.size > cap:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, size=cap))]
+        a = a.astype(dt)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 4096
+        written[name] = [list(a.shape), list(shape)]
+    return written
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (frames); ms_per_step = their time / steps")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: median, stage times, roofline / blend / frame objects, secondary "
+                         "contexts, columns and scenes, one-GPU references of a multi-GPU run, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--config", default=None, choices=["C1", "C2", "C3", "C4", "C5", "C3T", "C3S"],
                     help="default: C3 (BASELINE.json's metric configuration) at every N; with --gpus N > 1 a second object `c5` "
                          "(BASELINE.json configs[4]: the 8-GPU configuration, garden at 7680x4320) on the same ranks")
     ap.add_argument("--splats", type=int, default=0, help="override the splat count (debug only; invalid as a result)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-cull", action="store_true",
-                    help="skip the secondary columns (orbit, octree cull, fused frustum cull, translucent / capture-like scenes)")
+                    help="--full without the secondary columns (orbit, octree cull, fused frustum cull, translucent / capture-like "
+                         "scenes)")
     ap.add_argument("--only-headline", action="store_true",
-                    help="probe + warm-up + the timed frames and nothing else (profiler runs: every frame is a headline frame)")
+                    help="probe + warm-up + the timed frames (+ the median's frames with --full) and nothing else (profiler runs: "
+                         "every frame is a headline frame)")
     ap.add_argument("--median-frames", type=int, default=50,
-                    help="frames of the hipEvent-bracketed median (SURVEY.md 8d: >= 50); 0 = skip")
-    return ap.parse_args()
+                    help="--full: frames of the hipEvent-bracketed median (SURVEY.md 8d: >= 50); 0 = skip")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config == "C1":
+        ap.error("--dump-outputs: the C1 sort runs under Node and hands nothing back to this process")
+    return args
 
 
 class Rig:
@@ -394,12 +440,17 @@ class Env:
 
 
 SETTLE_FRAMES = 64
+# what a plain run (no --full) prints: the headline figure, the run's shape and the workload it was measured on
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "settle_frames", "fps",
+              "host_enqueue_ms_per_frame", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+              "frames_drawn_before_timing_ended", "scene_gen_s")
 
 
-def measure(env, cfg_name, steps, warmup, world, rank, stages=True, median_frames=50, dump=None):
+def measure(env, cfg_name, steps, warmup, world, rank, stages=True, median_frames=50, dump=None, dump_dir=None):
     """One workload (a BASELINE.json configuration = viewport + pose of the scene the rig holds) on `world` ranks: probe,
     strips, warm-up, the timed region (barrier + synchronize on both sides, MAX over ranks), the hipEvent-bracketed median,
-    the k_project clock and (stages) the per-stage times.  world = 1 on a multi-rank job = rank 0 alone, the others wait."""
+    the k_project clock and (stages) the per-stage times.  world = 1 on a multi-rank job = rank 0 alone, the others wait.
+    dump: path of an .npy for the uint8 frame of the last timed step (tests); dump_dir: --dump-outputs."""
     torch, dist, rig, stream, device = env.torch, env.dist, env.rig, env.stream, env.device
     from gaussiansplats3d_amd import camera, scenes
     from gaussiansplats3d_amd import dist as gdist
@@ -509,10 +560,17 @@ def measure(env, cfg_name, steps, warmup, world, rank, stages=True, median_frame
             t = torch.tensor([elapsed], dtype=torch.float64, device=device if env.backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        if dump and rank == 0:                                # tests: the frame the timed steps left on rank 0
+        if (dump or dump_dir) and rank == 0:                  # the frame the timed steps left on rank 0
             torch.cuda.synchronize()
             last_full = fulls_buf[(turn["k"] - 1) % nbuf] if world > 1 else full
-            np.save(dump, last_full.cpu().numpy())
+            frame = last_full.cpu().numpy()
+            if dump:
+                np.save(dump, frame)
+            if dump_dir:
+                outs = {"frame": frame}
+                if world == 1:                                # (a rank's list holds only its strip's splats)
+                    outs["sorted_indexes"] = worker.debug_read(2, rig.N)
+                m["dumped"] = dump_outputs(dump_dir, outs)
         m["proj_ms_sum"], m["proj_launches"] = mesh.kernel_time(0, reset=True)    # HIP events on the kernel's own stream
         st_timed = mesh.last_stats()                          # the list-bin size the timed frames used, and their entries
         m["list_px"], m["D32"] = int(st_timed.list_bin_px), int(st_timed.tile_entries)
@@ -657,7 +715,7 @@ def main():
     cam = camera.demo_camera(cfg["pose"], W, H)
     N = scene.count
     t_gen = time.perf_counter() - t_gen
-    extras = world == 1 and not args.no_cull and not args.only_headline
+    extras = world == 1 and args.full and not args.no_cull and not args.only_headline
 
     env = Env()
     env.torch, env.dist, env.device, env.backend, env.group = torch, dist, device, backend, None
@@ -678,9 +736,10 @@ def main():
             env.group.close()
             env.group = None
 
-    detailed = not args.only_headline
-    M = measure(env, headline, args.steps, args.warmup, world, rank, stages=detailed, median_frames=args.median_frames,
-                dump=os.environ.get("GS_BENCH_DUMP"))
+    detailed = args.full and not args.only_headline
+    M = measure(env, headline, args.steps, args.warmup, world, rank, stages=detailed,
+                median_frames=args.median_frames if args.full else 0, dump=os.environ.get("GS_BENCH_DUMP"),
+                dump_dir=args.dump_outputs)
     st_probe, strips, strip = M["st_probe"], M["strips"], M["strip_tensor"]
     frames_headline = rig.frames
     second, solo, c5_one = None, None, None
@@ -1211,8 +1270,12 @@ def main():
             "frames_drawn_before_timing_ended": frames_headline,
             "scene_gen_s": round(t_gen, 1),
         }
-        if world == 1 and not args.no_cpu and not args.only_headline:
+        if world == 1 and args.full and not args.no_cpu and not args.only_headline:
             out["cpu_baseline"] = cpu_baseline(scene, mvp, args.cpu_seconds)
+        if not args.full:
+            out = {k: v for k, v in out.items() if k in PLAIN_KEYS}
+        if args.dump_outputs:
+            out["dumped_outputs"] = M.get("dumped")
         print(json.dumps(out), flush=True)
     if env.group is not None:
         env.group.close()

@@ -41,6 +41,10 @@ def build(force=False):
     ref_wasm = os.path.join(_HERE, "_ref", "sorter_no_simd_non_shared.wasm")
     if (force or not os.path.exists(ref_so) or not os.path.exists(ref_wasm)) and os.path.exists("/root/reference/src/worker/sorter_no_simd.cpp"):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    # tests/test_node_seam.py's bundle (the Viewer's caller text + loader modules); the target keeps a prebuilt one (or none)
+    # where the reference or node is missing
+    if force or not os.path.exists(os.path.join(_HERE, "_ref", "seam", "viewer_cut.json")):
+        subprocess.check_call(["make", "-C", _HERE, "seam"], stdout=subprocess.DEVNULL)
 
 
 def _lib():

@@ -118,3 +118,24 @@ def test_gather_floor_is_the_largest_peer_strip_over_one_link(monkeypatch):
     monkeypatch.setenv("GS_LINK_GBPS", "38.4")
     assert abs(bench.gather_floor(strips, 7680, 4320, 8, None)["gather_floor_ms"] - 2 * g["gather_floor_ms"]) < 2e-4
     assert bench.gather_floor(strips, 7680, 4320, 1, 1.0) is None and bench.gather_floor(None, 7680, 4320, 8, 1.0) is None
+
+
+def test_dump_outputs_float32_within_the_budget_and_a_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 (.npy), whole arrays while they fit, smallest first; a larger one becomes the same seeded sample
+    in every run, and the files stay within DUMP_BUDGET_BYTES."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1_000_000)
+    small = np.arange(1000, dtype=np.uint32)[::-1].copy()
+    big = np.random.default_rng(3).integers(0, 256, (600, 500, 4), dtype=np.uint8)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"frame": big, "sorted_indexes": small})
+    a_small, a_big = np.load(tmp_path / "a" / "sorted_indexes.npy"), np.load(tmp_path / "a" / "frame.npy")
+    assert a_small.dtype == a_big.dtype == np.float32
+    np.testing.assert_array_equal(a_small, small.astype(np.float32))
+    assert w["frame"][1] == [600, 500, 4] and 0 < a_big.size < big.size
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 1_000_000
+    bench.dump_outputs(str(tmp_path / "b"), {"frame": big, "sorted_indexes": small})
+    np.testing.assert_array_equal(a_big, np.load(tmp_path / "b" / "frame.npy"))
+    assert np.isin(a_big, big).all()
+    # integers float32 cannot hold exactly go out as float64
+    bench.dump_outputs(str(tmp_path / "c"), {"ids": np.array([0, (1 << 24) + 1], dtype=np.uint32)})
+    ids = np.load(tmp_path / "c" / "ids.npy")
+    assert ids.dtype == np.float64 and ids[1] == (1 << 24) + 1

@@ -17,7 +17,7 @@ def _run(tmp_path, gpus, config="C3"):
     env = dict(os.environ, GS_BENCH_DUMP=dump)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3",
-                                   "--warmup", "1", "--no-cpu", "--no-cull", "--splats", "300000", "--median-frames", "5"] +
+                                   "--warmup", "1", "--full", "--no-cpu", "--no-cull", "--splats", "300000", "--median-frames", "5"] +
                                   (["--config", config] if config else []), env=env, text=True, timeout=600)
     line = [l for l in out.splitlines() if l.startswith('{"metric"')]
     assert len(line) == 1, out
@@ -54,3 +54,29 @@ def test_a_multi_gpu_run_keeps_the_metric_configuration_and_adds_the_8k_one(tmp_
     assert two8["config"]["width"] == 7680 and two8["c5"] is None
     assert frame8_1.shape == frame8_2.shape == (4320, 7680, 4) and frame8_1.any()
     np.testing.assert_array_equal(frame8_1, frame8_2)
+
+
+def test_a_plain_run_prints_the_headline_and_dumps_what_it_drew(tmp_path):
+    """No --full: the headline keys only, --steps timed steps, and --dump-outputs writes the last timed frame (the frame
+    GS_BENCH_DUMP saves) and the sorted list, as float32; a second run with the same arguments dumps the same arrays."""
+    def run(tag):
+        dump, out_dir = str(tmp_path / f"frame_{tag}.npy"), tmp_path / f"out_{tag}"
+        env = dict(os.environ, GS_BENCH_DUMP=dump)
+        env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                                       "--splats", "300000", "--dump-outputs", str(out_dir)], env=env, text=True, timeout=600)
+        line = [l for l in out.splitlines() if l.startswith('{"metric"')]
+        assert len(line) == 1, out
+        return json.loads(line[0]), np.load(dump), np.load(out_dir / "frame.npy"), np.load(out_dir / "sorted_indexes.npy")
+
+    d, frame_u8, frame, order = run("a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert "roofline" not in d and "cpu_baseline" not in d and "median_ms_per_step" not in d
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4) and frame.any()
+    np.testing.assert_array_equal(frame, frame_u8.astype(np.float32))
+    assert order.dtype == np.float32 and np.array_equal(np.sort(order), np.arange(300000, dtype=np.float32))
+    _, _, frame2, order2 = run("b")
+    np.testing.assert_array_equal(frame, frame2)
+    np.testing.assert_array_equal(order, order2)

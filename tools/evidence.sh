@@ -6,6 +6,7 @@
 # dry run.  Everything lands under gpurun_out/<tag>/; copy what should be judged into profiles/.   usage: tools/evidence.sh <tag>
 TAG=${1:-rXX}
 cd /root/repo; mkdir -p gpurun_out/$TAG
+EV=$_                     # this tag's output directory (the last argument of the mkdir above)
 (timeout 900 python -m pytest tests -q -m gpu 2>&1 | tail -6) > gpurun_out/$TAG/pytest_gpu.txt
 cp gpurun_out/crops_C*.json gpurun_out/whole_frame_*.json gpurun_out/$TAG/ 2>/dev/null    # (before tools/probes/rop8_arith_ab.sh redraws three of them with variant builds)
 bash tools/pmc.sh $TAG hbm > /dev/null 2>&1
@@ -18,8 +19,8 @@ bash tools/prof.sh ${TAG}_kstats > gpurun_out/$TAG/kstats.txt 2>&1
 cp gpurun_out/${TAG}_kstats/kernel_stats.csv gpurun_out/$TAG/kernel_stats.csv
 cp gpurun_out/${TAG}_kstats/bench_under_rocprof.json gpurun_out/$TAG/bench_under_rocprof.json
 cp gpurun_out/${TAG}_kstats/kstats.json gpurun_out/$TAG/kstats.json; cp gpurun_out/$TAG/kstats.json profiles/${TAG}_kstats.json   # (the line's per-kernel sort times)
-(timeout 700 python bench.py 2>gpurun_out/$TAG/bench.err | tail -1) > gpurun_out/$TAG/bench.json
-for C in C2 C4 C5; do (timeout 300 python bench.py --config $C --no-cpu --no-cull --steps 30 2>/dev/null | tail -1) > gpurun_out/$TAG/bench_$C.json; done
+(timeout 700 python bench.py --full 2>$EV/bench.err | tail -1) > $EV/bench.json
+for C in C2 C4 C5; do (timeout 300 python bench.py --full --config $C --no-cpu --no-cull --steps 30 2>/dev/null | tail -1) > $EV/bench_$C.json; done
 (timeout 200 python bench.py --config C1 --steps 30 2>/dev/null | tail -1) > gpurun_out/$TAG/bench_C1.json
 # C4: the configuration where the binner and the entry sort weigh most
 bash tools/prof.sh ${TAG}_C4_kstats --config C4 > gpurun_out/$TAG/kstats_C4.txt 2>&1
@@ -67,7 +68,7 @@ bash tools/rank_prof.sh $TAG C3 1:0 > gpurun_out/$TAG/vis_cull_n1_kstats.txt 2>&
 (python tools/strip_scaling.py C3 20; python tools/strip_scaling.py C5 15) 2>&1 | grep -v amdgpu.ids > gpurun_out/$TAG/strip_scaling.txt
 # the same rank frames on the default context (streams of its own + two sets of vertex-stage outputs: what bench.py --gpus N runs)
 (GS_STRIP_STREAMS=1 python tools/strip_scaling.py C3 20; GS_STRIP_STREAMS=1 python tools/strip_scaling.py C5 15) 2>&1 | grep -v amdgpu.ids > gpurun_out/$TAG/strip_scaling_streams.txt
-(timeout 400 python bench.py --gpus 2 --steps 10 --no-cpu --no-cull 2>/dev/null | tail -1) > gpurun_out/$TAG/bench_2ranks_dry_run.json
+(timeout 400 python bench.py --gpus 2 --steps 10 --full --no-cpu --no-cull 2>/dev/null | tail -1) > $EV/bench_2ranks_dry_run.json
 # forced list-bin sizes against the per-mesh rule
 [ -z "$GS_EVIDENCE_LIGHT" ] && (timeout 500 python tools/list_shift_ab.py "C3 C2 C3T C5" "1 3 4 5 auto" 2>&1 | grep -v amdgpu.ids) > gpurun_out/$TAG/list_shift_ab.txt
 # FILE -> native reader -> sort -> draw at BASELINE size: a 5.8 M-splat INRIA .ply staged on the box (synthetic content, real format)
