@@ -23,6 +23,7 @@ GS_CTX_SINGLE_STREAM, GS_CTX_STAGE_TIMING, GS_CTX_FORK_JOIN = 1, 2, 4
 GS_TILE = 16
 GS_BIN = 32          # blend workgroups are per 32-px bin (2x2 tiles); entry lists per list bin (RenderStats.list_bin_px)
 GS_MAX_SCENES = 32
+GS_PRECOMPUTED_DEVICE = 1   # gs_sorter_sort's `precomputed`: the distances gs_mesh_compute_distances left in the sorter
 
 
 class GsError(RuntimeError):
@@ -105,6 +106,7 @@ SYMBOLS = {
     "gs_sorter_sort": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.POINTER(SortStats)]),
     "gs_sorter_sort_gathered": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, C.POINTER(SortStats)]),
     "gs_sorter_bind_mesh": (C.c_int, [_VP, _VP]),
+    "gs_sorter_set_uploaded_count": (C.c_int, [_VP, C.c_uint32]),
     "gs_sorter_set_frustum_cull": (C.c_int, [_VP, C.c_int]),
     "gs_sorter_set_visibility_cull": (C.c_int, [_VP, C.c_int]),
     "gs_sorter_debug_read": (C.c_int, [_VP, C.c_int, _VP, C.c_uint32]),
@@ -135,6 +137,7 @@ SYMBOLS = {
     "gs_group_render_gather": (C.c_int, [_VP, _VP, C.POINTER(Camera), _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, _VP]),
     "gs_mesh_render": (C.c_int, [_VP, C.POINTER(Camera), _VP, _VP, C.c_uint32, _VP, _VP, C.POINTER(RenderStats)]),
     "gs_mesh_debug_read": (C.c_int, [_VP, C.c_int, _VP, C.c_uint32]),
+    "gs_mesh_compute_distances": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "gs_mesh_debug_rop8": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "gs_mesh_set_deep_pass": (C.c_int, [_VP, C.c_int]),
     "gs_mesh_set_draw_mode": (C.c_int, [_VP, C.c_uint32]),

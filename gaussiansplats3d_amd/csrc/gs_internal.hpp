@@ -312,6 +312,11 @@ struct gs_sorter {
     bool key_sync_used = false;
     DevBuf mask_copy;                  // the bound mesh's visibility mask as the last visibility-culled sort consumed it
     bool last_vis_culled = false;
+    // distances a gs_mesh_compute_distances(..., dst = this sorter) left in `precomputed` (sorts with GS_PRECOMPUTED_DEVICE)
+    bool dev_distances = false;        // cleared when a sort copies host distances over them
+    uint32_t dev_distances_count = 0;  // the mesh's uploaded splat count when they were computed
+    bool dev_distances_integer = false;
+    hipEvent_t ev_handover = nullptr;  // orders that hand-over between the context's stream and this sorter's
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -409,6 +414,7 @@ struct gs_mesh {
     bool has_scenes = false;
     uint32_t scene_count = 1;
     DevBuf staging;
+    DevBuf distances;          // uint32 [n]: gs_mesh_compute_distances's result when no sorter receives it (distances.hip)
     // per-draw
     DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
     DevBuf zrec;               // float [n]     the survivor's window-space centre depth, same slots (only while a destination

@@ -1247,7 +1247,8 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     A(s->frame, 2 * sizeof(SortFrame));
     if (st == GS_OK) st = s->radix.init();
     if (st == GS_OK && (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess ||
-                        hipEventCreateWithFlags(&s->ev_consumed, hipEventDisableTiming) != hipSuccess)) {
+                        hipEventCreateWithFlags(&s->ev_consumed, hipEventDisableTiming) != hipSuccess ||
+                        hipEventCreateWithFlags(&s->ev_handover, hipEventDisableTiming) != hipSuccess)) {
         gs_set_error("hipEventCreate failed");
         st = GS_ERR_HIP;
     }
@@ -1290,6 +1291,7 @@ void gs_sorter_destroy(gs_sorter* s) {
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->ev_consumed) (void)hipEventDestroy(s->ev_consumed);
+    if (s->ev_handover) (void)hipEventDestroy(s->ev_handover);
     if (s->own_stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -1315,6 +1317,24 @@ int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     if (from + count > s->uploaded) s->uploaded = from + count;   // uploadedSplatCount, SortWorker.js:97
     s->centers_version++;
     sorter_tell_mesh(s);                                   // (more centres than the bound mesh holds: no position map, no derived mask)
+    return GS_OK;
+}
+
+int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
+    GS_REQUIRE(s != nullptr, "sorter == NULL");
+    GS_REQUIRE(count <= s->max_count, "count exceeds max_splat_count");
+    if (count <= s->uploaded) return GS_OK;
+    ScopedDevice sd(s->ctx->device);
+    hipStream_t st = s->stream;
+    const size_t from = s->uploaded, n = count - s->uploaded;
+    GS_HIP(hipMemsetAsync(s->caos.as<uint4>() + from, 0, n * 16, st));
+    DevBuf* planes[] = {&s->cx, &s->cy, &s->cz, &s->cw, &s->scene_idx};
+    for (DevBuf* b : planes)
+        if (b->p) GS_HIP(hipMemsetAsync(b->as<uint32_t>() + from, 0, n * 4, st));
+    GS_HIP(hipStreamSynchronize(st));
+    s->uploaded = count;
+    s->centers_version++;
+    sorter_tell_mesh(s);
     return GS_OK;
 }
 
@@ -1353,6 +1373,13 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
                             uint32_t sort_count, uint32_t render_count, const void* precomputed, const float* transforms,
                             uint32_t* sorted_out, gs_sort_stats* stats, const uint32_t* list_count_dev = nullptr) {
     GS_REQUIRE(s && mvp, "sorter / mvp == NULL");
+    const bool pre_device = precomputed == GS_PRECOMPUTED_DEVICE;
+    if (pre_device) {
+        GS_REQUIRE(s->dev_distances, "GS_PRECOMPUTED_DEVICE: no gs_mesh_compute_distances has handed distances to this sorter");
+        GS_REQUIRE(s->dev_distances_count >= s->uploaded, "GS_PRECOMPUTED_DEVICE: fewer distances than the sorter's uploaded splats");
+        GS_REQUIRE(s->dev_distances_integer == ((s->flags & GS_SORT_INTEGER) != 0),
+                   "GS_PRECOMPUTED_DEVICE: the distances were computed for the other GS_SORT_INTEGER setting");
+    }
     // SortWorker.js:100-101 clamps both counts to the uploaded splat count
     if (render_count > s->uploaded) render_count = s->uploaded;
     if (sort_count > s->uploaded) sort_count = s->uploaded;
@@ -1430,7 +1457,10 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
     kp.mode = ((s->flags & GS_SORT_INTEGER) ? MODE_INT : 0) | (dynamic ? MODE_DYNAMIC : 0) | (precomputed ? MODE_PRECOMPUTED : 0);
     if (precomputed) {
         GS_TRY(s->precomputed.ensure((size_t)s->max_count * 4));
-        GS_HIP(hipMemcpyAsync(s->precomputed.p, precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
+        if (!pre_device) {                     // (the device hand-over: gs_mesh_compute_distances wrote the buffer in place)
+            GS_HIP(hipMemcpyAsync(s->precomputed.p, precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
+            s->dev_distances = false;
+        }
         kp.precomputed = s->precomputed.as<uint32_t>();
     }
     if (dynamic && !precomputed) {

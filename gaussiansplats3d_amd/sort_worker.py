@@ -82,7 +82,9 @@ class SortWorker:
             if idx.size < render:                    # the C side copies splatRenderCount entries
                 raise ValueError(f"indexesToSort holds {idx.size} entries, splatRenderCount is {render}")
         pre = None
-        if s.get("usePrecomputedDistances"):
+        if s.get("usePrecomputedDistances") and s.get("precomputedOnDevice"):
+            pre = L.GS_PRECOMPUTED_DEVICE       # what SplatMesh.compute_distances_on_gpu(..., sort_worker=self) left on the device
+        elif s.get("usePrecomputedDistances"):
             pre = np.ascontiguousarray(s["precomputedDistances"],
                                        dtype=np.int32 if self.integer_based_sort else np.float32)
             if pre.size < self.uploaded_splat_count:  # one distance per uploaded splat (SortWorker.js:125-178)
@@ -97,7 +99,7 @@ class SortWorker:
         stats = L.SortStats()
         st = L.check(self.lib.gs_sorter_sort(
             self.handle, mvp.ctypes.data, idx.ctypes.data if idx is not None else None, sort, render,
-            pre.ctypes.data if pre is not None else None, tr.ctypes.data if tr is not None else None,
+            pre if isinstance(pre, int) else pre.ctypes.data if pre is not None else None, tr.ctypes.data if tr is not None else None,
             out.ctypes.data if out is not None else None, None if keep else C.byref(stats)))
         reply = {"sortDone": True, "splatSortCount": sort, "splatRenderCount": render,
                  "sortTime": float(stats.device_ms), "status": st}
@@ -115,16 +117,18 @@ class SortWorker:
                               "indexesToSort": indexes, "transforms": np.tile(np.eye(4, dtype=np.float32).reshape(16), 32)},
                              keep_on_device=True)
 
-    def sort_gathered(self, mvp, sort_count=None, keep_on_device=False):
+    def sort_gathered(self, mvp, sort_count=None, keep_on_device=False, precomputed_on_device=False):
         """Sort the device-resident indexesToSort list (and splatRenderCount) the last
-        ``SplatTree.gather_scene_nodes_for_sort(..., sort_worker=self)`` produced."""
+        ``SplatTree.gather_scene_nodes_for_sort(..., sort_worker=self)`` produced.  precomputed_on_device: key it by the
+        distances ``SplatMesh.compute_distances_on_gpu(..., sort_worker=self)`` left on the device."""
         mvp = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).astype(np.float32))
         tr = np.tile(np.eye(4, dtype=np.float32).reshape(16), L.GS_MAX_SCENES) if self.dynamic_mode else None
         stats = L.SortStats()
         # render count is held by the library; ask for the sorted list only when the caller wants it on the host
         out = None if keep_on_device else np.empty(self.gathered_count, dtype=np.uint32)
         sc = 0xFFFFFFFF if sort_count is None else int(sort_count)
-        st = L.check(self.lib.gs_sorter_sort_gathered(self.handle, mvp.ctypes.data, sc, None,
+        pre = L.GS_PRECOMPUTED_DEVICE if precomputed_on_device else None
+        st = L.check(self.lib.gs_sorter_sort_gathered(self.handle, mvp.ctypes.data, sc, pre,
                                                       tr.ctypes.data if tr is not None else None,
                                                       out.ctypes.data if out is not None else None,
                                                       None if keep_on_device else C.byref(stats)))
@@ -132,6 +136,12 @@ class SortWorker:
             out = out[:stats.result_count]
         return {"sortDone": True, "status": st, "sortTime": float(stats.device_ms), "sortedIndexes": out, "stats": stats,
                 "splatRenderCount": self.gathered_count}
+
+    def set_uploaded_count(self, count):
+        """uploadedSplatCount without a `centers` message (gs_sorter_set_uploaded_count): a Viewer with gpuAcceleratedSort
+        posts only precomputed distances.  Splats that never received centres get zero ones."""
+        L.check(self.lib.gs_sorter_set_uploaded_count(self.handle, int(count)))
+        self.uploaded_splat_count = max(self.uploaded_splat_count, int(count))
 
     def set_frustum_cull(self, enable=True):
         """Fuse a per-splat frustum cull into full sorts (gs_sorter_set_frustum_cull): the result is the reference's

@@ -12,14 +12,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .util import to_half_three
+from .util import distance_uniforms, to_half_three
 
 
 class SplatMesh:
     def __init__(self, context, max_splat_count, spherical_harmonics_degree=0, half_precision_covariances=False,
                  antialiased=False, kernel_2d_size=0.3, max_screen_space_splat_size=1024.0, splat_scale=1.0,
                  point_cloud_mode=False, spherical_harmonics_8bit=False, dynamic_mode=False,
-                 enable_optional_effects=False):
+                 enable_optional_effects=False, keep_order=False):
         self.ctx = context
         self.lib = context.lib
         self.max_splat_count = int(max_splat_count)
@@ -34,6 +34,8 @@ class SplatMesh:
         self.dynamic_mode = bool(dynamic_mode)
         self.enable_optional_effects = bool(enable_optional_effects)
         self.fade_in = None                                    # (sceneCenter, visibleRegionFadeStartRadius) or None
+        self.keep_order = bool(keep_order)                     # GS_MESH_KEEP_ORDER: device storage in upload order (no Morton)
+        self.scene_transforms = None                           # fp64 column-major 16-vectors of set_scenes (dynamic distance pass)
         self.splat_count = 0
         self.render_count = 0
         self._indexes = None          # host indexes from updateRenderIndexes
@@ -43,7 +45,8 @@ class SplatMesh:
         self.handle = C.c_void_p()
         L.check(self.lib.gs_mesh_create(context.handle, self.max_splat_count, self.sh_degree,
                                         (L.GS_MESH_COV_HALF if self.half_cov else 0) |
-                                        (L.GS_MESH_SH_U8 if self.sh_8bit else 0), C.byref(self.handle)))
+                                        (L.GS_MESH_SH_U8 if self.sh_8bit else 0) |
+                                        (L.GS_MESH_KEEP_ORDER if self.keep_order else 0), C.byref(self.handle)))
         context._adopt(self)
 
     # -- build / data upload ------------------------------------------------------------------------
@@ -83,6 +86,8 @@ class SplatMesh:
         (enableOptionalEffects), sphericalHarmonics8BitCompressionRangeMin/Max.  transforms: column-major 16-vectors;
         inverse(transform) * cameraPosition (the dynamic-mode SH view origin) is evaluated here in fp64."""
         n = max(len(x) for x in (transforms, opacity, visible, sh8_range) if x is not None)
+        if transforms is not None:
+            self.scene_transforms = [np.asarray(t, np.float64).reshape(16) for t in transforms]
         sp = L.SceneParams()
         sp.scene_count = n
         for s_ in range(n):
@@ -97,6 +102,31 @@ class SplatMesh:
                 sp.sh8_min[s_], sp.sh8_max[s_] = float(sh8_range[s_][0]), float(sh8_range[s_][1])
         L.check(self.lib.gs_mesh_set_scenes(self.handle, C.byref(sp)))
         return self
+
+    def compute_distances_on_gpu(self, model_view_proj, out=None, sort_worker=None, integer=None, dynamic=None,
+                                 scene_transforms=None):
+        """SplatMesh.computeDistancesOnGPU(modelViewProjMatrix, outComputedDistances) (SplatMesh.js:1701-1814): the distance
+        pass of gpuAcceleratedSort over every uploaded splat (gs_mesh_compute_distances).  The uniforms are computed here with
+        the reference's fp64 arithmetic (getIntegerMatrixArray, per-scene mvp * transform in dynamic mode).
+          out          int32 / float32 array of >= uploaded splats, filled by original splat index; None = no host copy
+          sort_worker  a SortWorker that receives the distances on the device: sort them with
+                       ``post_message({"sort": {..., "usePrecomputedDistances": True, "precomputedOnDevice": True}})``
+          integer      integerBasedDistancesComputation (default: the worker's integer_based_sort, else True)
+          dynamic      dynamicMode (default: this mesh's); scene_transforms default to those of set_scenes
+        Returns `out` (or None)."""
+        if integer is None:
+            integer = sort_worker.integer_based_sort if sort_worker is not None else True
+        dynamic = self.dynamic_mode if dynamic is None else bool(dynamic)
+        uniforms, scenes = distance_uniforms(model_view_proj, integer, dynamic,
+                                             self.scene_transforms if scene_transforms is None else scene_transforms)
+        if out is not None:
+            if out.dtype != (np.int32 if integer else np.float32) or not out.flags.c_contiguous or out.size < self.splat_count:
+                raise ValueError(f"out must be a contiguous {'int32' if integer else 'float32'} array of >= {self.splat_count} values")
+        flags = (L.GS_SORT_INTEGER if integer else 0) | (L.GS_SORT_DYNAMIC if dynamic else 0)
+        L.check(self.lib.gs_mesh_compute_distances(self.handle, flags, uniforms.ctypes.data, scenes,
+                                                   out.ctypes.data if out is not None else None,
+                                                   sort_worker.handle if sort_worker is not None else None))
+        return out
 
     def set_fade_in(self, scene_center=None, visible_region_fade_start_radius=0.0):
         """fadeInComplete == 0 with these uniforms (SplatMesh.updateVisibleRegionFadeDistance); None = complete."""

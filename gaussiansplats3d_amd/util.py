@@ -1,4 +1,6 @@
 """Host-side numeric helpers that mirror what the reference's JS layer does before data reaches the GPU."""
+import math
+
 import numpy as np
 
 
@@ -39,3 +41,64 @@ def float_centers(centers3):
     """SplatMesh.getFloatCenters(padFour=true), SplatMesh.js:1935-1948: w = 1.0."""
     c = np.ascontiguousarray(centers3, dtype=np.float32).reshape(-1, 3)
     return np.concatenate([c, np.ones((c.shape[0], 1), np.float32)], axis=1)
+
+
+# -- gpuAcceleratedSort: the uniforms of the distance pass (SplatMesh.computeDistancesOnGPU, SplatMesh.js:1701-1814) ------------
+def js_math_round(x):
+    """JS Math.round of an fp64 value: the nearest integer, halves towards +Infinity (Python's round() sends halves to even).
+    Returned as a float, like the JS number (NaN and infinities pass through)."""
+    x = float(x)
+    if x != x or x in (math.inf, -math.inf):
+        return x
+    r = math.floor(x)
+    return float(r + 1) if x - r >= 0.5 else float(r)
+
+
+def js_to_int32(x):
+    """ECMAScript ToInt32 / WebIDL `long` (what gl.uniform*i and an Int32Array store make of a JS number): NaN and infinities
+    -> 0, otherwise the integer part modulo 2^32 as a signed value."""
+    x = float(x)
+    if x != x or x in (math.inf, -math.inf):
+        return 0
+    v = int(x) & 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+def get_integer_matrix_array(elements):
+    """SplatMesh.getIntegerMatrixArray (SplatMesh.js:2057-2064): Math.round(m * 1000.0) per element, fp64 (JS numbers)."""
+    return [js_math_round(float(e) * 1000.0) for e in np.asarray(elements, dtype=np.float64).reshape(16)]
+
+
+def premultiply(a, b):
+    """THREE.Matrix4: b.clone().premultiply(a) = multiplyMatrices(a, b), fp64, each element summed left to right as three does
+    (numpy's matmul may reorder or fuse).  a, b, result: column-major 16-vectors."""
+    a = [float(v) for v in np.asarray(a, dtype=np.float64).reshape(16)]
+    b = [float(v) for v in np.asarray(b, dtype=np.float64).reshape(16)]
+    out = [0.0] * 16
+    for col in range(4):
+        for row in range(4):
+            out[4 * col + row] = a[row] * b[4 * col] + a[4 + row] * b[4 * col + 1] + a[8 + row] * b[4 * col + 2] + a[12 + row] * b[4 * col + 3]
+    return out
+
+
+def distance_uniforms(model_view_proj, integer, dynamic, scene_transforms=None):
+    """What computeDistancesOnGPU uploads (SplatMesh.js:1719-1743), in the layout gs_mesh_compute_distances takes:
+    static integer int32[3], static float float32[3], dynamic integer int32[4 * scenes], dynamic float float32[16 * scenes]
+    (per scene mvp * transform).  Returns (array, scene_count)."""
+    mvp = [float(v) for v in np.asarray(model_view_proj, dtype=np.float64).reshape(16)]
+    if not dynamic:
+        if integer:
+            im = get_integer_matrix_array(mvp)
+            return np.array([js_to_int32(im[k]) for k in (2, 6, 10)], dtype=np.int32), 1
+        return np.array([mvp[2], mvp[6], mvp[10]], dtype=np.float64).astype(np.float32), 1
+    transforms = [np.eye(4).reshape(16)] if scene_transforms is None or len(scene_transforms) == 0 else scene_transforms
+    rows = []
+    for t in transforms:
+        m = premultiply(mvp, t)
+        if integer:
+            im = get_integer_matrix_array(m)
+            rows += [js_to_int32(im[k]) for k in (2, 6, 10, 14)]
+        else:
+            rows += m
+    out = np.array(rows, dtype=np.int32) if integer else np.array(rows, dtype=np.float64).astype(np.float32)
+    return out, len(transforms)

@@ -126,6 +126,11 @@ int gs_sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_so
 int gs_sorter_sort_gathered(gs_sorter* s, const float* mvp, uint32_t sort_count, const void* precomputed,
                             const float* transforms, uint32_t* sorted_out, gs_sort_stats* stats);
 
+/* uploadedSplatCount without centres: a Viewer with gpuAcceleratedSort never posts the `centers` message (src/Viewer.js:1124-1136)
+ * and sorts only precomputed distances.  Raises the sorter's uploaded splat count to `count` (<= max_splat_count); splats
+ * that never received centres get zero ones, what the reference's zero-filled WASM memory holds.  A smaller count is a no-op. */
+int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count);
+
 /* Optional coupling of the two seams: a sorter bound to a mesh leaves its device-resident result as positions in
  * that mesh's internal storage order, so gs_mesh_render(m, ..., sorter = s, ...) needs no per-frame index translation.
  * Host-visible results (sorted_out, gs_sorter_debug_read) are always the caller's splat indexes.  m = NULL unbinds. */
@@ -394,6 +399,37 @@ int gs_mesh_set_destination(gs_mesh* m, const gs_destination* dest);
  * gs_mesh_render with an identical gs_camera consumes them instead of projecting again (once: the vertex stage runs exactly
  * one time per frame either way); any other camera simply projects afresh.  Needed before a visibility-culled sort. */
 int gs_mesh_project(gs_mesh* m, const gs_camera* cam);
+
+/* The distance pass of gpuAcceleratedSort: SplatMesh.computeDistancesOnGPU (SplatMesh.js:1701-1814) with the transform-feedback
+ * vertex shader of :1449-1490, over every uploaded splat, one value per ORIGINAL splat index.
+ *   flags     GS_SORT_INTEGER (integerBasedDistancesComputation) | GS_SORT_DYNAMIC (dynamicMode)
+ *   uniforms  exactly what the reference uploads:
+ *               static integer   int32[3]               getIntegerMatrixArray(mvp)[2, 6, 10]
+ *               static float     float[3]               mvp.elements[2, 6, 10]
+ *               dynamic integer  int32[4 * scene_count] getIntegerMatrixArray(mvp * scene.transform)[2, 6, 10, 14] per scene
+ *               dynamic float    float[16 * scene_count] (mvp * scene.transform).elements per scene, column-major
+ *             (getIntegerMatrixArray = Math.round(m * 1000) per element, SplatMesh.js:2057-2064, then WebGL's int32 conversion)
+ *   scene_count  1..GS_MAX_SCENES (static: 1); scenes beyond it read zero rows, like unset GL uniforms
+ *   out_host  int32 / float[uploaded splats] by original index (waits for it), or NULL
+ *   dst       a sorter of the same context whose device-side precomputed-distance buffer receives the result (no PCIe; the
+ *             next gs_sorter_sort / _gathered with precomputed = GS_PRECOMPUTED_DEVICE sorts it), or NULL.  Its max_splat_count
+ *             must cover the mesh's uploaded splats.  The hand-over is ordered with an event on a multi-stream context.
+ * Arithmetic per splat at storage position p (centres as gs_mesh_upload received them, in fp32):
+ *   integer   x, y, z = ToInt32(Math.round((double)c * 1000)) (getIntegerCenters(padFour), SplatMesh.js:1912-1926: NaN and
+ *             infinities -> 0, everything else wraps modulo 2^32), w = 1000; products and sums wrap modulo 2^32 (GLSL ES 3.00)
+ *               static   x*u.x + y*u.y + z*u.z                      dynamic  x*t.x + y*t.y + z*t.z + t.w*1000
+ *   float     fp32, every product and sum rounded on its own (no fused multiply-add), left to right
+ *               static   ((x*u.x + y*u.y) + z*u.z)                  dynamic  (((T[2]*x + T[6]*y) + T[10]*z) + T[14])
+ *             (a GL driver may contract these, so the reference itself is defined to within an ulp here)
+ * GS_ERR_INVALID for unknown flags, scene_count 0 or > GS_MAX_SCENES, a dynamic pass over several scenes on a mesh without scene
+ * indexes, or a dst smaller than the mesh's uploaded splat count. */
+int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, uint32_t scene_count, void* out_host,
+                              gs_sorter* dst);
+/* `precomputed` argument of gs_sorter_sort / gs_sorter_sort_gathered: sort the distances the last gs_mesh_compute_distances(...,
+ * dst = this sorter) left on the device (nothing crosses PCIe).  GS_ERR_INVALID when the sorter never received any, received fewer
+ * than its uploaded splat count, or received them for the other GS_SORT_INTEGER setting.  A sort with host distances overwrites
+ * them. */
+#define GS_PRECOMPUTED_DEVICE ((const void*)(uintptr_t)1)
 
 /* Intermediates of the last draw (tests, strip load-balancing).  what: 0 = per splat (storage order) the
  * 32-byte vertex-stage record {cx, cy, ax, ay, bx, by, r|g<<16, b|a<<16 (unorm16)}; 1 = per splat the tile

@@ -11,8 +11,9 @@
 // Integration = two imports (INTEGRATION.md):
 //     import { SplatMesh } from '<this repo>/node/SplatMesh.mjs';          // was './splatmesh/SplatMesh.js'
 //     import { createSortWorker } from '<this repo>/node/SortWorker.mjs';  // was './worker/SortWorker.js'
-// plus the Viewer option `gpuAcceleratedSort: false` (the WebGL transform-feedback distance pass, SplatMesh.js:1701-1814, is
-// subsumed by the device sort's own keying).
+// The Viewer option `gpuAcceleratedSort: true` works too: computeDistancesOnGPU runs the reference's transform-feedback distance
+// pass (SplatMesh.js:1701-1814, shader :1449-1490) as a HIP kernel over the device mesh and copies the distances into the array
+// the Viewer hands it (the worker's SharedArrayBuffer view or its own typed array), as getBufferSubData does there.
 //
 // `three` is the same peer dependency the reference imports (in this repo's tests it resolves to oracle/three_min.mjs).
 // The frame lands in `this.frame` = {data: Uint8Array RGBA8 (row 0 = bottom, like gl.readPixels), width, height}; a host
@@ -60,7 +61,6 @@ export class SplatMesh {
     const defaults = [SplatRenderMode.ThreeD, false, false, false, 1, true, false, false, 1024, 0, 0, 1.0, 0.3];
     names.forEach((name, k) => { this[name] = args[k] === undefined ? defaults[k] : args[k]; });
     if (this.splatRenderMode !== SplatRenderMode.ThreeD) throw new Error('SplatMesh (HIP): only SplatRenderMode.ThreeD is implemented');
-    this.enableDistancesComputationOnGPU = false;           // the device sort keys the splats itself (see the header)
     Object.assign(this, {
       renderer: undefined, scenes: [], sceneOptions: undefined, minSphericalHarmonicsDegree: 0,
       splatTree: null, baseSplatTree: null, onSplatTreeReadyCallback: null, splatDataTextures: {},
@@ -289,7 +289,35 @@ export class SplatMesh {
   setRenderer(renderer) { this.renderer = renderer; }
   freeIntermediateSplatData() {}                            // nothing is kept on the host
   updateVisibleRegionFadeDistance() {}                      // SceneRevealMode.Instant semantics: fadeInComplete = 1 (:1201-1226)
-  computeDistancesOnGPU() { return Promise.resolve(true); } // subsumed by the device sort (gpuAcceleratedSort must be false)
+
+  // :1701-1814.  Uniforms as the reference uploads them: the clip-z row of mvp (static) or of mvp * the scene's transform (dynamic,
+  // one per scene), as Math.round(x * 1000) integers or as fp32.  The pass runs synchronously, so the Promise resolves with
+  // `outComputedDistances` already filled (by original splat index).
+  computeDistancesOnGPU(modelViewProjMatrix, outComputedDistances) {
+    if (!this.core || this.core.splatCount <= 0) return Promise.resolve();
+    const integer = !!this.integerBasedDistancesComputation;
+    const zRow = (mat, w) => {                                // elements 2, 6, 10 (, 14) of the integer matrix: its clip-z row
+      const im = SplatMesh.getIntegerMatrixArray(mat);
+      return [2, 6, 10, 14].slice(0, w).map((k) => im[k]);
+    };
+    let uniforms, sceneCount = 1;
+    if (this.dynamicMode) {
+      sceneCount = this.scenes.length;
+      uniforms = integer ? new Int32Array(4 * sceneCount) : new Float32Array(16 * sceneCount);
+      this.scenes.forEach((scene, k) => {
+        const sceneMvp = new THREE.Matrix4().multiplyMatrices(modelViewProjMatrix, scene.transform);
+        if (integer) uniforms.set(zRow(sceneMvp, 4), 4 * k);               // Int32Array stores ToInt32, as gl.uniform4i does
+        else uniforms.set(sceneMvp.elements, 16 * k);                      // Float32Array rounds to fp32, as gl.uniformMatrix4fv does
+      });
+    } else {
+      uniforms = integer ? new Int32Array(zRow(modelViewProjMatrix, 3))
+                         : Float32Array.from([2, 6, 10], (k) => modelViewProjMatrix.elements[k]);
+    }
+    this.core.computeDistances((integer ? 1 : 0) | (this.dynamicMode ? 2 : 0), uniforms, sceneCount, outComputedDistances);
+    return Promise.resolve();
+  }
+  // :2057-2064: every element of a THREE.Matrix4 times 1000, rounded by Math.round (JS numbers, not yet int32)
+  static getIntegerMatrixArray(matrix) { return Array.from(matrix.elements, (e) => Math.round(e * 1000.0)); }
 
   // ---- per-sort / per-frame ------------------------------------------------------------------------------------------
   updateRenderIndexes(globalIndexes, renderSplatCount) {    // :1228-1235

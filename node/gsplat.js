@@ -31,6 +31,7 @@ class HipSortWorker {
     this.integerBasedSort = !!integerBasedSort;
     this.dynamicMode = !!dynamicMode;
     this.uploadedSplatCount = 0;
+    this.centersReceived = false;
     this._busy = false;
     this._queue = [];
     this._terminated = false;
@@ -76,9 +77,23 @@ class HipSortWorker {
       const centers = this.integerBasedSort ? new Int32Array(msg.centers) : new Float32Array(msg.centers);
       const scene = this.dynamicMode ? new Uint32Array(msg.sceneIndexes) : null;
       addon.sorterUploadCenters(this.handle, msg.range.from, count, centers, scene);
+      this.centersReceived = true;
       this.uploadedSplatCount = Math.max(this.uploadedSplatCount, msg.range.from + count);
     } else if (msg.sort) {                                                // SortWorker.js:99-115, 31-81
       const s = msg.sort;
+      if (s.usePrecomputedDistances && !this.centersReceived) {
+        // gpuAcceleratedSort: the Viewer posts no `centers` message (src/Viewer.js:1124-1136), only distances.  The reference's
+        // worker keeps uploadedSplatCount at 0 (SortWorker.js:123) and so sorts and draws nothing in this mode.  Deliberately
+        // unlike it, a worker that never received centres counts every splat its distance array covers (maxSplatCount entries,
+        // Viewer.js:1274-1281): indexesToSort names ORIGINAL splat indexes, which an octree gather leaves anywhere below the
+        // splat count even when splatRenderCount is smaller.
+        const distances = this.useSharedMemory ? this.maxSplatCount : (s.precomputedDistances ? s.precomputedDistances.length : 0);
+        const n = Math.min(distances, this.maxSplatCount);
+        if (n > this.uploadedSplatCount) {
+          addon.sorterSetUploadedCount(this.handle, n);
+          this.uploadedSplatCount = n;
+        }
+      }
       const renderCount = Math.min(s.splatRenderCount || 0, this.uploadedSplatCount);
       const sortCount = Math.min(s.splatSortCount || 0, this.uploadedSplatCount);
       const mvp = new Float32Array(s.modelViewProj);                      // fp64 -> fp32 like SortWorker.js:54
@@ -212,6 +227,11 @@ class SplatMeshHIP {
   // sceneIndexes texture (SplatMesh.js:881-897) and the per-scene uniforms of updateUniforms (:1263-1276):
   // {sceneCount, transforms F32(16n), invCamPos F32(4n) = inverse(transform) * cameraPosition, opacity F32(n), visible U32(n),
   //  sh8Min F32(n), sh8Max F32(n)}
+  // SplatMesh.computeDistancesOnGPU's pass: `uniforms` as the reference uploads them (include/gsplat_hip.h), the distances of the
+  // uploaded splats into `out` (Int32Array / Float32Array by original index) and / or a sort worker's device buffer
+  computeDistances(flags, uniforms, sceneCount, out, sortWorker) {
+    addon.meshComputeDistances(this.handle, flags, uniforms, sceneCount, out || null, this.splatCount, sortWorker ? sortWorker.handle : null);
+  }
   setSceneIndexes(sceneIndexes, start = 0) { addon.meshUploadSceneIndexes(this.handle, start, sceneIndexes.length, sceneIndexes); }
   setScenes(params) { addon.meshSetScenes(this.handle, params); this.hasScenes = true; }
   // the fade-in of SplatMesh.updateVisibleRegionFadeDistance: visibleRegionFadeStartRadius + sceneCenter; null switches it off

@@ -302,6 +302,42 @@ static napi_value SorterSortAsync(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* sorterSetUploadedCount(sorter, count): uploadedSplatCount without centres (gpuAcceleratedSort posts none) */
+static napi_value SorterSetUploadedCount(napi_env env, napi_callback_info info) {
+    ARGS(2)
+    int st;
+
+    LOCKED(st = gs_sorter_set_uploaded_count((gs_sorter*)get_external(env, argv[0]), get_u32(env, argv[1])));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+
+/* meshComputeDistances(mesh, flags, uniforms Int32Array|Float32Array, sceneCount, out Int32Array|Float32Array|null, count,
+ *                      sorter|null): SplatMesh.computeDistancesOnGPU's pass (gs_mesh_compute_distances).  `count` = the mesh's
+ * uploaded splat count (what the pass writes into `out`).  Synchronous under the addon's lock, like every other call here: it
+ * returns once `out` holds the distances (the reference's getBufferSubData after its fence, SplatMesh.js:1771-1803). */
+static napi_value MeshComputeDistances(napi_env env, napi_callback_info info) {
+    ARGS(7)
+    void *u, *out;
+    size_t ub, ob;
+    if (!get_bytes(env, argv[2], &u, &ub) || !u || !get_bytes(env, argv[4], &out, &ob)) {
+        napi_throw_type_error(env, NULL, "meshComputeDistances: uniforms / out");
+        return NULL;
+    }
+    const uint32_t flags = get_u32(env, argv[1]), scenes = get_u32(env, argv[3]), count = get_u32(env, argv[5]);
+    const size_t need_u = (flags & GS_SORT_DYNAMIC) ? (size_t)scenes * ((flags & GS_SORT_INTEGER) ? 16 : 64) : 12;
+    if (ub < need_u || (out && ob < (size_t)count * 4)) {
+        napi_throw_range_error(env, NULL, "meshComputeDistances: uniforms shorter than the scenes need / out shorter than count");
+        return NULL;
+    }
+    int st;
+
+    LOCKED(st = gs_mesh_compute_distances((gs_mesh*)get_external(env, argv[0]), flags, u, scenes, out,
+                                          (gs_sorter*)get_external(env, argv[6])));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+
 /* meshCreate(ctx, maxSplatCount, shDegree, flags) */
 static napi_value MeshCreate(napi_env env, napi_callback_info info) {
     ARGS(4)
@@ -807,6 +843,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"treeCreate", TreeCreate},         {"treeDestroy", TreeDestroy},     {"treeInfo", TreeInfo},
         {"treeGather", TreeGather},         {"treeRead", TreeRead},         {"assetLoad", AssetLoad},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
+        {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
