@@ -361,7 +361,7 @@ def _set_destination(depth, depth_unorm24, W, H):
         _lib().gro_set_destination_depth(None, 0)
         return None
     d = np.ascontiguousarray(depth, dtype=np.float32).reshape(H, W)
-    _lib().gro_set_destination_depth(d.ctypes.data_as(_f32p), int(bool(depth_unorm24)))
+    _lib().gro_set_destination_depth(d.ctypes.data_as(_f32p), int(depth_unorm24))   # 2: llvmpipe's fp32 conversion
     return d
 
 

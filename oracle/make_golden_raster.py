@@ -73,8 +73,8 @@ class Uniforms(C.Structure):
                 ("sh8_min", C.c_float * 32), ("sh8_max", C.c_float * 32), ("scene_visibility", C.c_int32 * 32)]
 
 
-def run_vertex(lib, case):
-    """case: what tests/raster_cases.py builds.  Returns float32 [n, 4 corners, 10]."""
+def harness_inputs(case):
+    """case: what tests/raster_cases.py builds -> (Scene, Uniforms, arrays to keep alive); oracle/gl_ref.c takes the same."""
     sc, u = Scene(), Uniforms()
     keep = []
 
@@ -107,6 +107,13 @@ def run_vertex(lib, case):
         u.scene_opacity[s_] = un["scene_opacity"][s_] if s_ < len(un["scene_opacity"]) else 1.0
         u.scene_visibility[s_] = un["scene_visibility"][s_] if s_ < len(un["scene_visibility"]) else 1
         u.sh8_min[s_], u.sh8_max[s_] = un["sh8_range"]
+    return sc, u, keep
+
+
+def run_vertex(lib, case):
+    """case: what tests/raster_cases.py builds.  Returns float32 [n, 4 corners, 10]."""
+    sc, u, _keep = harness_inputs(case)
+    n = case["centers"].shape[0]
     out = np.zeros((n, 4, 10), dtype=np.float32)
     lib.harness_run_vertex(C.byref(sc), C.byref(u), out.ctypes.data_as(C.c_void_p))
     return out

@@ -252,7 +252,13 @@ static int g_dst_unorm24 = 0;
 void gro_set_destination_depth(const float* depth, int unorm24) { g_dst_depth = depth; g_dst_unorm24 = unorm24; }
 /* (the conversion in fp64: round to nearest exactly - in fp32 the product already sits at 1-LSB granularity above z = 0.5; the
  * result is an integer < 2^24, exact as a float) */
-static float depth_cmp_value(float z) { return g_dst_unorm24 ? (float)floor((double)z * 16777215.0 + 0.5) : z; }
+/* unorm24 == 2: the product evaluated in fp32 and then rounded to nearest even, as Mesa's llvmpipe converts (measured against it,
+ * tests/test_gl_ref.py): the fp32 product may round across a level below z = 0.5, so the two rules keep
+ * different splats there.  Test infrastructure only: the engine and mode 1 keep the exact rule. */
+static float depth_cmp_value(float z) {
+    if (g_dst_unorm24 == 2) return rintf(z * 16777215.0f);
+    return g_dst_unorm24 ? (float)floor((double)z * 16777215.0 + 0.5) : z;
+}
 
 /* How far an RGBA8 render target can drift from the exact composite (row a14): every blend into the target rounds each channel
  * to 8 bits (an error of at most half a step), and every later splat scales what has accumulated by (1 - alpha):
@@ -317,7 +323,9 @@ static uint64_t blend_one(const gro_splat2d* s, int W, int H, int wx0, int wy0, 
 /*
  * Full frame.  fb = float RGBA [H][W][4], row 0 = bottom, must be zeroed by the caller (clear colour
  * (0,0,0,0), Viewer.js:358-359).  rop8 != 0 emulates the RGBA8 render target by rounding dst to unorm8
- * after every splat (what the reference's ROP really does); rop8 == 0 keeps fp32 (the parity target).
+ * after every splat (one model of an RGBA8 target: Mesa's llvmpipe instead rounds the fragment colour to unorm8 before it blends
+ * and sits further from this rule than the fp32 composite rounded once - DESIGN.md section 2); rop8 == 0 keeps fp32 (the parity
+ * target).
  * ambig (nullable, [H][W] bytes): set to 1 where some splat's A fell within 8 +- amb_eps, i.e. where
  * the discontinuous `A > 8 -> discard` may legitimately flip under different fp32 evaluation orders.
  * Returns the number of (pixel, splat) fragments that survived the discard.

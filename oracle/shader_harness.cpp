@@ -1,8 +1,8 @@
 // oracle/shader_harness.cpp — TEST INFRASTRUCTURE.  Runs the reference's OWN vertex / fragment shader text on the CPU.
 // SHADER_VERT / SHADER_FRAG are files produced by oracle/make_golden_raster.py from the strings the reference's
 // SplatMaterial3D.build() returned (token rewrites only, see there); they compile here against oracle/glsl_shim.hpp.  This
-// file supplies what a WebGL2 draw call supplies around them: the data textures laid out as
-// /root/reference/src/splatmesh/SplatMesh.js:637-898 lays them out, the uniforms of SplatMesh.updateUniforms (:1248-1280)
+// file supplies what a WebGL2 draw call supplies around them: the data textures packed as
+// /root/reference/src/splatmesh/SplatMesh.js:637-898 packs them (oracle/texel_pack.h), the uniforms of SplatMesh.updateUniforms (:1248-1280)
 // and three.js' built-ins (modelViewMatrix, projectionMatrix, viewMatrix, cameraPosition, the quad attribute `position`,
 // SplatGeometry.js:14-23), and collects gl_Position / varyings per (splat, quad corner) and gl_FragColor / discard per
 // fragment.  Built by make_golden_raster.py into oracle/_ref/ (never committed: it embeds reference text).
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "glsl_shim.hpp"
+#include "texel_pack.h"
 
 #define discard do { gs_discarded = true; return; } while (0)
 
@@ -67,43 +68,37 @@ void harness_run_vertex(const HarnessScene* sc, const HarnessUniforms* u, float*
     using namespace glsl;
     const uint32_t n = sc->count;
     const uint32_t ncoef = sc->sh_degree_stored == 0 ? 0 : (sc->sh_degree_stored == 1 ? 9 : 24);
-    // data textures (SplatMesh.js:637-898): power-of-two sizes keep index -> uv -> texel exact
+    // data textures (SplatMesh.js:637-898), packed by oracle/texel_pack.h; laid out 64 wide with power-of-two heights here,
+    // which keeps index -> uv -> texel exact in the shim's sampler (oracle/gl_ref.c uses the reference's own sizes)
     const int W = 64;
     auto height = [&](size_t texels) { return pow2_at_least((texels + W - 1) / W); };
-    std::vector<uint32_t> cc(4 * (size_t)W * height(n), 0u);             // RGBA32UI: {rgba8 packed, bits(x), bits(y), bits(z)}
-    for (uint32_t i = 0; i < n; i++) {
-        const uint8_t* c = sc->rgba + 4 * i;
-        cc[4 * i] = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);      // Util.js:53-55
-        memcpy(&cc[4 * i + 1], sc->centers + 3 * i, 12);
-    }
+    std::vector<uint32_t> cc(4 * (size_t)W * height(n));                  // RGBA32UI: {rgba8 packed, bits(x), bits(y), bits(z)}
+    tp_pack_centers_colors(n, sc->centers, sc->rgba, W, height(n), cc.data());
     VS::centersColorsTexture.data = cc.data(); VS::centersColorsTexture.w = W; VS::centersColorsTexture.h = height(n);
     VS::centersColorsTexture.channels = 4;
     VS::centersColorsTextureSize = vec2((float)W, (float)height(n));
     std::vector<float> covf;                                               // RGBA32F, 6 floats per splat, 1.5 texels (:741)
     std::vector<uint32_t> covh;                                            // RGBA32UI, one texel per splat: 3 packed half pairs (:735-739)
     if (sc->cov_half) {
-        covh.assign(4 * (size_t)W * height(n), 0u);
-        for (uint32_t i = 0; i < n; i++)
-            for (int k = 0; k < 3; k++)
-                covh[4 * i + k] = (uint32_t)sc->cov16[6 * i + 2 * k] | ((uint32_t)sc->cov16[6 * i + 2 * k + 1] << 16);
+        covh.resize(4 * (size_t)W * height(n));
+        tp_pack_covariances_half(n, sc->cov16, W, height(n), covh.data());
         VS::covariancesTextureHalfFloat.data = covh.data(); VS::covariancesTextureHalfFloat.w = W;
         VS::covariancesTextureHalfFloat.h = height(n); VS::covariancesTextureHalfFloat.channels = 4;
         VS::covariancesTextureSize = vec2((float)W, (float)height(n));
         VS::covariancesAreHalfFloat = 1;
     } else {
         const size_t texels = ((size_t)n * 6 + 3) / 4 + 2;
-        covf.assign(4 * (size_t)W * height(texels), 0.0f);
-        memcpy(covf.data(), sc->cov, sizeof(float) * 6 * n);
+        covf.resize(4 * (size_t)W * height(texels));
+        tp_pack_covariances(n, sc->cov, W, height(texels), covf.data());
         VS::covariancesTexture.data = covf.data(); VS::covariancesTexture.w = W; VS::covariancesTexture.h = height(texels);
         VS::covariancesTextureSize = vec2((float)W, (float)height(texels));
         VS::covariancesAreHalfFloat = 0;
     }
     std::vector<float> shf;                                                // single texture: 9 -> 10 / 24 -> 24 padded components (:797-867)
     if (ncoef) {
-        const uint32_t stride = ncoef == 9 ? 10 : 24;
-        const size_t texels = ((size_t)n * stride + 3) / 4 + 2;
-        shf.assign(4 * (size_t)W * height(texels), 0.0f);
-        for (uint32_t i = 0; i < n; i++) memcpy(&shf[(size_t)i * stride], sc->sh + (size_t)i * ncoef, sizeof(float) * ncoef);
+        const size_t texels = ((size_t)n * tp_sh_stride(ncoef) + 3) / 4 + 2;
+        shf.resize(4 * (size_t)W * height(texels));
+        tp_pack_sh(n, ncoef, sc->sh, W, height(texels), shf.data());
         VS::sphericalHarmonicsTexture.data = shf.data(); VS::sphericalHarmonicsTexture.w = W;
         VS::sphericalHarmonicsTexture.h = height(texels);
         VS::sphericalHarmonicsTextureSize = vec2((float)W, (float)height(texels));
@@ -111,8 +106,8 @@ void harness_run_vertex(const HarnessScene* sc, const HarnessUniforms* u, float*
     VS::sphericalHarmonicsMultiTextureMode = 0;
     std::vector<uint32_t> sidx(1, 0u);
     if (sc->scene_idx) {                                                   // R32UI (:881-897)
-        sidx.assign((size_t)W * height(n), 0u);
-        memcpy(sidx.data(), sc->scene_idx, 4 * (size_t)n);
+        sidx.resize((size_t)W * height(n));
+        tp_pack_scene_indexes(n, sc->scene_idx, W, height(n), sidx.data());
         VS::sceneIndexesTexture.data = sidx.data(); VS::sceneIndexesTexture.w = W; VS::sceneIndexesTexture.h = height(n);
         VS::sceneIndexesTexture.channels = 1;
         VS::sceneIndexesTextureSize = vec2((float)W, (float)height(n));

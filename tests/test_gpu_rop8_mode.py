@@ -1,6 +1,8 @@
-"""-m gpu: GS_DRAW_ROP8 - the reference's blend state as a GPU executes it (SplatMaterial3D.js:65-75: NormalBlending into an RGBA8
-target, every channel rounded to 8 bits after EVERY splat, back to front) as a draw mode of the render seam, against the
-ROP-emulating oracle (raster_oracle.c, rop8) and against the engine's own verification kernel (gs_mesh_debug_rop8)."""
+"""-m gpu: GS_DRAW_ROP8 - the reference's blend state into an RGBA8 target as modelled by the oracle's rop8 rule
+(SplatMaterial3D.js:65-75: NormalBlending, every channel rounded to 8 bits after EVERY splat, back to front) as a draw mode of the
+render seam, against the ROP-emulating oracle (raster_oracle.c, rop8) and against the engine's own verification kernel
+(gs_mesh_debug_rop8).  The rule is one model of a ROP, not a measured one: Mesa's llvmpipe sits further from it than from the fp32
+composite rounded once (tests/test_gl_ref.py)."""
 import numpy as np
 import pytest
 

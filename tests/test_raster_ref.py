@@ -112,14 +112,11 @@ def ctx():
     c.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", raster_cases.CASES)
-def test_hip_vertex_stage_matches_the_reference_shader(ctx, name):
+def engine_mesh(ctx, case):
+    """A SplatMesh holding a raster case's scene with its shader build's options, uniforms and camera set (GPU tier)."""
     from gaussiansplats3d_amd import SplatMesh
-    case = raster_cases.make_case(name)
-    u, cam, sc = case["uniforms"], case["camera"], case["scene"]
-    n = sc.count
-    mesh = SplatMesh(ctx, n, sc.sh_degree, half_precision_covariances=case["cov_half"], antialiased=case["antialiased"],
+    u, sc = case["uniforms"], case["scene"]
+    mesh = SplatMesh(ctx, sc.count, sc.sh_degree, half_precision_covariances=case["cov_half"], antialiased=case["antialiased"],
                      kernel_2d_size=case["kernel2d"], max_screen_space_splat_size=case["max_splat_px"], splat_scale=u["splat_scale"],
                      point_cloud_mode=bool(u["point_cloud"]), spherical_harmonics_8bit=case["sh8"],
                      dynamic_mode=case["build"] == "dynamic2", enable_optional_effects=case["build"] == "effects1")
@@ -132,11 +129,14 @@ def test_hip_vertex_stage_matches_the_reference_shader(ctx, name):
                         sh8_range=[u["sh8_range"]] * k)
     if not u["fade_in_complete"]:
         mesh.set_fade_in(u["scene_center"], u["fade_start_radius"])
-    mesh.set_camera(cam, focal_adjustment=1.0 / u["inverse_focal_adjustment"], spherical_harmonics_degree=u["sh_degree"])
-    mesh.update_render_indexes(np.arange(n, dtype=np.uint32), n)
-    mesh.render()
-    recs, rects, on_screen = mesh.debug_records()
-    drawn, centre, b1, b2, colour = _from_shader(G["vs_" + name], u["viewport"])
+    mesh.set_camera(case["camera"], focal_adjustment=1.0 / u["inverse_focal_adjustment"], spherical_harmonics_degree=u["sh_degree"])
+    return mesh
+
+
+def check_engine_records(case, res, recs, on_screen):
+    """The engine's vertex-stage records (debug_records) against a shader's outputs `res` ([n, 4, 10]) of the same splats."""
+    u = case["uniforms"]
+    drawn, centre, b1, b2, colour = _from_shader(res, u["viewport"])
     # the engine additionally drops splats whose footprint reaches no pixel centre of the viewport: a subset of `drawn`
     assert not (on_screen & ~drawn).any(), "the engine draws a splat the reference's shader rejects"
     k = on_screen
@@ -150,7 +150,7 @@ def test_hip_vertex_stage_matches_the_reference_shader(ctx, name):
         want = K * b[k] / nrm[:, None]
         err = np.abs(f[k, col:col + 2] - want).max(axis=1)     # relative to the vector's length (a component may be ~0)
         assert (err <= 5e-4 * np.sqrt((want ** 2).sum(axis=1)) + 1e-6).all(), float((err / np.sqrt((want ** 2).sum(axis=1))).max())
-    tol = 2e-4 if name == "dynamic" else 2e-5                 # unorm16 storage of the record's colour
+    tol = 2e-4 if case["build"] == "dynamic2" else 2e-5       # unorm16 storage of the record's colour
     got = np.stack([(recs[k, 6] & 0xFFFF), (recs[k, 6] >> 16), (recs[k, 7] & 0xFFFF), (recs[k, 7] >> 16)], axis=1) / 65535.0
     np.testing.assert_allclose(got, np.clip(colour[k], 0, 1), rtol=0, atol=tol)
     # every splat the shader draws and the engine drops must be one whose ellipse misses all pixel centres of the frame
@@ -160,4 +160,16 @@ def test_hip_vertex_stage_matches_the_reference_shader(ctx, name):
     inside = (centre[:, 0] + ext_x > 0.5) & (centre[:, 0] - ext_x < W - 0.5) & (centre[:, 1] + ext_y > 0.5) & (centre[:, 1] - ext_y < H - 0.5)
     thin = np.minimum(ext_x, ext_y) < 0.5 + 1e-3              # its box can slip between two rows / columns of pixel centres
     assert (thin | ~inside)[dropped].all(), "a dropped splat must miss every pixel centre of the frame"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", raster_cases.CASES)
+def test_hip_vertex_stage_matches_the_reference_shader(ctx, name):
+    case = raster_cases.make_case(name)
+    n = case["scene"].count
+    mesh = engine_mesh(ctx, case)
+    mesh.update_render_indexes(np.arange(n, dtype=np.uint32), n)
+    mesh.render()
+    recs, rects, on_screen = mesh.debug_records()
+    check_engine_records(case, G["vs_" + name], recs, on_screen)
     mesh.dispose()
