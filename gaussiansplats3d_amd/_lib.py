@@ -21,6 +21,7 @@ GS_MESH_COV_HALF, GS_MESH_SH_U8, GS_MESH_KEEP_ORDER = 1, 2, 4
 GS_CAM_ANTIALIASED, GS_CAM_POINT_CLOUD, GS_CAM_ORTHOGRAPHIC, GS_CAM_FADE_IN, GS_CAM_SCENE_EFFECTS, GS_CAM_DYNAMIC = 1, 2, 4, 8, 16, 32
 GS_CTX_SINGLE_STREAM, GS_CTX_STAGE_TIMING, GS_CTX_FORK_JOIN = 1, 2, 4
 GS_TILE = 16
+GS_SCHEDULE_WORDS = 10  # gs_mesh_debug_read(what = 7): header words before the blend order
 GS_BIN = 32          # blend workgroups are per 32-px bin (2x2 tiles); entry lists per list bin (RenderStats.list_bin_px)
 GS_MAX_SCENES = 32
 GS_PRECOMPUTED_DEVICE = 1   # gs_sorter_sort's `precomputed`: the distances gs_mesh_compute_distances left in the sorter

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <new>
 #include <utility>
@@ -54,9 +55,24 @@ struct DevBuf {
             return GS_ERR_NOMEM;
         }
         bytes = n;
+        // $GSPLAT_POISON_ALLOC=<byte> (tests): every new allocation holds that byte instead of whatever the allocator left -
+        // usually zeros, which hide reads of memory nobody wrote.  Read on every call, so a test can switch it per object.
+        if (const char* poison = getenv("GSPLAT_POISON_ALLOC")) {
+            const int byte = (int)(strtol(poison, nullptr, 0) & 0xFF);
+            e = hipMemset(p, byte, n);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) {
+                gs_set_error("poisoning an allocation of %zu bytes failed: %s", n, hipGetErrorString(e));
+                return GS_ERR_HIP;
+            }
+        }
         return GS_OK;
     }
-    int ensure(size_t n) { return n <= bytes ? GS_OK : alloc(n); }
+    // grows the buffer to >= n bytes; *fresh (if given) says whether it was (re)allocated - and so holds nothing written yet
+    int ensure(size_t n, bool* fresh = nullptr) {
+        if (fresh) *fresh = n > bytes;
+        return n <= bytes ? GS_OK : alloc(n);
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -454,6 +470,11 @@ struct gs_mesh {
     bool deep_pass = false;    // this draw runs the deep pass (decided in gs_launch_binning)
     DevBuf blend_order;        // uint32 [blend bins]: this draw's bins by descending cost in the previous draw (k_bin_emit)
     bool blend_order_valid = false;
+    struct ScheduleArgs {      // what the last draw's schedule job was given (gs_mesh_debug_read(what = 7); tests)
+        uint32_t ran, blend_bins;
+        int32_t sx, sy;
+        uint32_t deep, deep_min, deep_factor, fused;
+    } sched = {};
     RadixScratch radix;
     uint32_t entry_capacity = 0;
     uint32_t sorted_buf = 0;   // ping-pong buffer index holding the tile-sorted entries of the last draw
@@ -474,7 +495,7 @@ struct gs_mesh {
     struct ProjSet {
         DevBuf recs, zrec, rects, vis_mask, block_any, vis32, prect, vis_orig;
         hipEvent_t ev_done = nullptr;
-        bool drawn = false, vis_orig_dirty = true, vis_orig_lazy = false;
+        bool drawn = false, vis_orig_dirty = true, vis_orig_lazy = false, vis_orig_tail_zero = false;
         uint32_t vis_orig_count = 0;
     } alt;
     bool two_sets = false;                         // alt is allocated and in use
@@ -494,6 +515,7 @@ struct gs_mesh {
                                           // k_mask_derive_count): full-frame gs_mesh_project calls skip the per-survivor atomics
     bool vis_orig_lazy = false;           // ... and the pending projection did: vis_orig holds nothing yet
     bool vis_orig_dirty = true;           // vis_orig may hold bits (cleared by the sort that consumes it, see k_mask_compact)
+    bool vis_orig_tail_zero = false;      // (lazy projection) the words its sorter does not write were zero: the sort leaves all zero
     uint32_t vis_orig_count = 0;          // splats the last gs_mesh_project looked at
     bool timed_project = false;           // the last vertex stage was bracketed with ev_p0 / ev_p1
     bool timed_draw = false;              // the last draw recorded its stage events (see gs_context::stage_events)
@@ -521,7 +543,10 @@ const uint32_t* gs_mesh_payload_unmap(gs_mesh* m);
 // (ev_before / ev_after, nullable, recorded on ctx->aux: around the whole vertex stage - block test, mask memset, k_project - when
 // whole_stage (a timed draw's project_ms), else right around k_project itself, so that gs_mesh_kernel_time, the bench's live
 // roofline clock over the untimed frames of its timed region, times that one kernel)
-int gs_launch_project(gs_mesh* m, const ProjectParams& pp, bool orig_mask, hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,
+// orig_mask: what becomes of the by-original-index mask (gs_mesh::vis_orig): nothing, set by the vertex stage, or left to the
+// bound sorter (its buffer is only prepared)
+constexpr int GS_ORIG_MASK_NONE = 0, GS_ORIG_MASK_WRITE = 1, GS_ORIG_MASK_DERIVED = 2;
+int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,
                       bool whole_stage = false);
 int gs_launch_binning(gs_mesh* m, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
 int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev);

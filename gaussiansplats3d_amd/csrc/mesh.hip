@@ -667,9 +667,10 @@ static void mesh_swap_sets(gs_mesh* m) {
     swap_buf(m->vis32, o.vis32); swap_buf(m->prect, o.prect); swap_buf(m->vis_orig, o.vis_orig);
     std::swap(m->ev_done, o.ev_done); std::swap(m->set_drawn, o.drawn);
     std::swap(m->vis_orig_dirty, o.vis_orig_dirty); std::swap(m->vis_orig_count, o.vis_orig_count); std::swap(m->vis_orig_lazy, o.vis_orig_lazy);
+    std::swap(m->vis_orig_tail_zero, o.vis_orig_tail_zero);
 }
 
-static int mesh_project(gs_mesh* m, const ProjectParams& pp, bool orig_mask, bool timed) {
+static int mesh_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, bool timed) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream, aux = ctx->aux;
     if (timed) GS_HIP(hipEventRecord(m->ev[0], st));
@@ -707,7 +708,7 @@ static int mesh_draw_once(gs_mesh* m, const ProjectParams& pp, const uint32_t* o
     m->timed_draw = timed;
     const uint32_t tiles = pp.lists_x * (pp.list_row_end - pp.list_row_begin);  // one entry list per list bin
     GS_TRY(m->tile_ranges.ensure((size_t)tiles * 8 + 16));
-    if (!projected) GS_TRY(mesh_project(m, pp, false, timed));   // else gs_mesh_project already ran it for this camera
+    if (!projected) GS_TRY(mesh_project(m, pp, GS_ORIG_MASK_NONE, timed));   // else gs_mesh_project already ran it for this camera
     else if (timed) GS_HIP(hipEventRecord(m->ev[0], st));
     // join: projection and (if a sorter feeds this draw) the sort result
     if (aux != st) GS_HIP(hipStreamWaitEvent(st, m->ev_p1, 0));
@@ -861,13 +862,8 @@ int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
     // consumer is a bound sorter that holds the mesh's position map, left to that sorter (k_mask_derive_count: 25 us of a C3 frame)
     static const bool no_lazy = getenv("GSPLAT_NO_LAZY_MASK") != nullptr;      // (A/B and tests)
     const bool lazy = m->derive_orig_mask && m->reorder && !no_lazy && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
-    GS_TRY(mesh_project(m, pp, !lazy, m->ctx->stage_events));
+    GS_TRY(mesh_project(m, pp, lazy ? GS_ORIG_MASK_DERIVED : GS_ORIG_MASK_WRITE, m->ctx->stage_events));
     m->vis_orig_lazy = lazy;
-    if (lazy) {
-        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64));
-        m->vis_orig_dirty = true;                              // (whatever it holds beyond the words the sorter will write)
-        m->vis_orig_count = pp.count;
-    }
     m->projection_pending = true;
     m->projected_cam = *cam;
     m->projected_depth_mode = pp.depth_mode;
@@ -1049,6 +1045,20 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         uint32_t* w = static_cast<uint32_t*>(dst);
         w[0] = m->measured_visible; w[1] = m->measured_count; w[2] = m->last_project_mode;
         return GS_OK;
+    } else if (what == 7) {   // the last draw's blend schedule (tile_bin.hip blend_schedule_job): GS_SCHEDULE_WORDS words, then
+                              // blend_order [0, count - GS_SCHEDULE_WORDS); count = GS_SCHEDULE_WORDS .. + blend bins
+        GS_REQUIRE(count >= GS_SCHEDULE_WORDS && count - GS_SCHEDULE_WORDS <= m->sched.blend_bins &&
+                   (count == GS_SCHEDULE_WORDS || (m->sched.ran && (size_t)(count - GS_SCHEDULE_WORDS) * 4 <= m->blend_order.bytes)),
+                   "count outside GS_SCHEDULE_WORDS .. + the blend bins of a draw that ran the schedule");
+        GS_HIP(hipStreamSynchronize(st));
+        volatile uint32_t* mir = (volatile uint32_t*)m->mirror_host;
+        const gs_mesh::ScheduleArgs& a = m->sched;
+        const uint32_t head[GS_SCHEDULE_WORDS] = {a.ran, a.blend_bins, (uint32_t)a.sx, (uint32_t)a.sy, a.deep, a.deep_min, a.deep_factor, a.fused,
+                                                  mir ? mir[4] : 0u, mir ? mir[5] : 0u};
+        memcpy(dst, head, sizeof(head));
+        if (count > GS_SCHEDULE_WORDS)
+            GS_HIP(hipMemcpyAsync(static_cast<uint32_t*>(dst) + GS_SCHEDULE_WORDS, m->blend_order.p, (size_t)(count - GS_SCHEDULE_WORDS) * 4,
+                                  hipMemcpyDeviceToHost, st));
     } else GS_REQUIRE(false, "unknown debug selector");
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;

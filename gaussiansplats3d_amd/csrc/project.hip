@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_pr
     }
 }
 
-int gs_launch_project(gs_mesh* m, const ProjectParams& pp, bool orig_mask, hipEvent_t ev_before, hipEvent_t ev_after, bool whole_stage) {
+int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEvent_t ev_before, hipEvent_t ev_after, bool whole_stage) {
     MeshPlanes mp;
     mp.px = m->px.as<float>(); mp.py = m->py.as<float>(); mp.pz = m->pz.as<float>();
     mp.covA = m->covA.p; mp.covB = m->covB.p;
@@ -599,6 +599,17 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, bool orig_mask, hipEv
     mp.sh0 = m->sh0.as<uint4>(); mp.sh1 = m->sh1.p; mp.sh2 = m->sh2.as<uint4>();
     mp.scene_idx = m->scene_idx.as<uint32_t>();
     mp.scenes = m->scene_dev.as<gs_scene_params>();
+    if (orig_mask == GS_ORIG_MASK_DERIVED) {
+        // The bound sorter derives the mask: it writes (and, consuming it, clears) the words of the positions it sorts, and leaves
+        // every word beyond them as it was.  A fresh buffer is zeroed here, on the stream the sorter waits for, so that a later
+        // projection that skips the clear (vis_orig_dirty false) never ORs bits into garbage.
+        bool fresh = false;
+        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
+        if (fresh) GS_HIP(hipMemsetAsync(m->vis_orig.p, 0, m->vis_orig.bytes, m->ctx->aux));
+        m->vis_orig_tail_zero = fresh || !m->vis_orig_dirty;  // every word the sorter will not write is zero
+        m->vis_orig_dirty = true;
+        m->vis_orig_count = pp.count;
+    }
     if (pp.count == 0) {
         if (ev_before) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));
         if (ev_after) GS_HIP(hipEventRecord(ev_after, m->ctx->aux));
@@ -625,9 +636,9 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, bool orig_mask, hipEv
                            m->vis_mask.as<unsigned long long>(), m->vis32.as<uint2>(), m->block_any.as<uint8_t>());
     if (pp.depth_mode) GS_TRY(m->zrec.ensure((size_t)m->max_count * 4 + 16));
     uint32_t* vis_orig = nullptr;
-    if (orig_mask) {
-        const bool fresh = m->vis_orig.p == nullptr;
-        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 31) / 32 * 4 + 64));
+    if (orig_mask == GS_ORIG_MASK_WRITE) {
+        bool fresh = false;                             // (allocated just now: it holds nothing anybody wrote)
+        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
         // the visibility-culled sort that consumes the mask leaves it zeroed (k_mask_compact); only a mask nobody consumed
         // (two gs_mesh_project in a row, a sort over fewer splats) is cleared here
         if (fresh || m->vis_orig_dirty)

@@ -1620,8 +1620,9 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
                 hipLaunchKernelGGL(k_mask_compact, dim3(grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(),
                                    s->chunk_counts.as<uint32_t>(), R, chunk_len, s->idx_in.as<uint32_t>(), kp.frame);
             }
-            // the mask is all zero again if this sort covered every splat the vertex stage looked at
-            if (R >= s->bound_mesh->vis_orig_count) s->bound_mesh->vis_orig_dirty = false;
+            // the mask is all zero again if this sort covered every splat the vertex stage looked at - and, where it derived the
+            // mask itself, if the words beyond the ones it wrote were zero already (gs_mesh_project)
+            if (R >= s->bound_mesh->vis_orig_count && (!lazy || s->bound_mesh->vis_orig_tail_zero)) s->bound_mesh->vis_orig_dirty = false;
             idx_dev = s->idx_in.as<uint32_t>();
             kp.idx_in = idx_dev;
             kp.count_dev = &kp.frame->kept;

@@ -300,8 +300,10 @@ struct StatShift {
     uint32_t bins_x;
 };
 // The blend's schedule and the deep pass's members, one workgroup of BIN_THREADS (see where it is called: k_bin_emit / k_bin_fused)
-__device__ __forceinline__ void blend_schedule_job(const uint2* __restrict__ prev_blend_stats, uint32_t blend_bins, uint32_t* __restrict__ blend_order,
-                                                   uint32_t deep, uint32_t* __restrict__ deep_flags, uint32_t* __restrict__ blend_stats_w,
+// (prev_blend_stats and blend_stats_w are the same buffer - the previous draw's statistics, read, then the members' zeroed: no
+// __restrict__ on either)
+__device__ __forceinline__ void blend_schedule_job(const uint2* prev_blend_stats, uint32_t blend_bins, uint32_t* __restrict__ blend_order,
+                                                   uint32_t deep, uint32_t* __restrict__ deep_flags, uint32_t* blend_stats_w,
                                                    uint32_t deep_min, uint32_t deep_factor, volatile uint32_t* __restrict__ mirror, StatShift sh) {
     __shared__ uint32_t s_cost[RADIX_BINS], s_tmp2[4];
     // the chunked composite's per-draw words: no deep bins yet, an empty partial pool (k_bin_count resets them as well; in the fused
@@ -369,7 +371,16 @@ __device__ __forceinline__ void blend_schedule_job(const uint2* __restrict__ pre
     if (threadIdx.x == 0) { s_deep_n = 0u; s_deep_cost = 0u; }
     __threadfence_block();
     __syncthreads();                                   // blend_order complete (and visible to this workgroup)
-    for (uint32_t p = threadIdx.x; p < min(blend_bins, GS_DEEP_MAX_BINS); p += BIN_THREADS) {
+    // Two phases: every member is decided before any statistics are zeroed.  blend_stats_w IS prev_blend_stats, and with a
+    // StatShift a bin's cost is read from ANOTHER bin (a neighbour, which may be a member): zeroing in the same loop made later
+    // readers - other threads, and this thread's second head position - see 0 and drop bins from the pass.
+    constexpr uint32_t HEAD_PER_T = (GS_DEEP_MAX_BINS + BIN_THREADS - 1u) / BIN_THREADS;
+    uint32_t member[HEAD_PER_T];
+#pragma unroll
+    for (uint32_t q = 0; q < HEAD_PER_T; q++) {
+        const uint32_t p = threadIdx.x + q * BIN_THREADS;
+        member[q] = GS_DEEP_NONE;
+        if (p >= min(blend_bins, GS_DEEP_MAX_BINS)) continue;
         const uint32_t i = __hip_atomic_load(&blend_order[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const uint32_t cost = i < blend_bins ? cost_of(i) : 0u;
         if (cost >= deep_trigger) s_trigger = 1u;
@@ -379,11 +390,16 @@ __device__ __forceinline__ void blend_schedule_job(const uint2* __restrict__ pre
             if (deep) {
                 deep_flags[GS_FLAG_LIST + k] = i;
                 deep_flags[GS_FLAG_OF + i] = k;
-                blend_stats_w[2u * i] = 0u; blend_stats_w[2u * i + 1u] = 0u; blend_stats_w[2u * blend_bins + i] = 0u;
+                member[q] = i;
             }
         }
     }
-    __syncthreads();
+    __syncthreads();                                   // every cost_of() of the head has been read
+#pragma unroll
+    for (uint32_t q = 0; q < HEAD_PER_T; q++) {
+        const uint32_t i = member[q];
+        if (i != GS_DEEP_NONE) { blend_stats_w[2u * i] = 0u; blend_stats_w[2u * i + 1u] = 0u; blend_stats_w[2u * blend_bins + i] = 0u; }
+    }
     if (threadIdx.x == 0) {
         // (a draw whose tail no longer reaches the trigger still runs the pass it was launched with - on the bins of the
         // membership rule - and tells the next one to stop)
@@ -417,9 +433,9 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
                                                           uint32_t row_begin /* first list-bin row */, KeyT* __restrict__ keys_out,
                                                           uint32_t* __restrict__ vals_out, uint32_t list_shift,
                                                           volatile uint32_t* __restrict__ mirror, uint32_t serial,
-                                                          const uint2* __restrict__ prev_blend_stats, uint32_t blend_bins,
+                                                          const uint2* prev_blend_stats, uint32_t blend_bins,
                                                           uint32_t* __restrict__ blend_order, uint32_t deep,
-                                                          uint32_t* __restrict__ deep_flags, uint32_t* __restrict__ blend_stats_w,
+                                                          uint32_t* __restrict__ deep_flags, uint32_t* blend_stats_w,
                                                           uint32_t deep_min, uint32_t deep_factor, StatShift sh) {
     __shared__ __attribute__((aligned(16))) uint32_t s_eoff[BIN_MAX_BLOCKS];   // entries of the binning workgroups before b (saturating)
     __shared__ __attribute__((aligned(16))) uint32_t s_cnt[BIN_MAX_BLOCKS];    // compacted splats of binning workgroup b
@@ -602,7 +618,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     // (k_bin_emit's)
     RenderFrame* __restrict__ frame, uint32_t capacity, uint32_t tiles_x /* list bins per row */, uint32_t row_begin /* first list-bin row */,
     KeyT* __restrict__ keys_out, uint32_t* __restrict__ vals_out, volatile uint32_t* __restrict__ mirror, uint32_t serial,
-    const uint2* __restrict__ prev_blend_stats, uint32_t* __restrict__ blend_order, uint32_t deep, uint32_t* __restrict__ blend_stats_w,
+    const uint2* prev_blend_stats, uint32_t* __restrict__ blend_order, uint32_t deep, uint32_t* blend_stats_w,
     uint32_t deep_min, uint32_t deep_factor, BinScan scan, StatShift sh) {
     __shared__ unsigned long long s_w[4];
     __shared__ uint32_t s_any[ANY_WORDS];
@@ -830,6 +846,8 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
     // (that workgroup also raises the deep pass's trigger, so under a camera that keeps moving it still runs when the pass is on,
     // for scenes of tiny splats - the ones that grow deep bins - and every 8th draw otherwise)
     const bool order_wg = order_ok && (same_view || stale_order || m->deep_pass || pp.list_shift == GS_LIST_SHIFT_SMALL || (m->draw_serial & 7u) == 7u);
+    // (what the schedule job of this draw is given: gs_mesh_debug_read(what = 7))
+    m->sched = {order_wg ? 1u : 0u, blend_bins, stat_shift.sx, stat_shift.sy, m->deep_pass ? 1u : 0u, deep_min, deep_factor, fused ? 1u : 0u};
     ++m->draw_serial;
     if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the scan's granules are tagged with the serial: 0 is "never written")
     if (fused) {

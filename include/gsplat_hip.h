@@ -440,7 +440,12 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * real cost, used to balance multi-GPU strips; 5 = the deep pass of the last draw: {bins it composited, bins over its threshold,
  * chunk partials the per-bin kernel closed itself, 1 if that pool ran out}, then the bin numbers (count = 4 .. 4 + 512 words);
  * 6 = host state (count = 3 words): {visible splats, splats projected} of the last full-frame draw whose verdict has reached the
- * host, and where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all).
+ * host, and where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all);
+ * 7 = the blend schedule of the last draw (the one workgroup that orders the blend's bins by the previous draw's per-bin statistics,
+ * what = 4, and names the deep pass's members), GS_SCHEDULE_WORDS words: {1 if it ran, blend bins, shift x, shift y (int32: this
+ * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, 1 if
+ * the fused binner ran, the bins it put over the deep pass's trigger (0 when none reached it), the members' share of the walk in
+ * 1/1024}, then the bin order itself (count = GS_SCHEDULE_WORDS .. + blend bins; the order only after a draw that ran it).
  *
  * The composite (csrc/tile_blend.hip).  Per 16x16-px quadrant, the ordered list entries whose ellipse reaches the quadrant are
  * cut into chunks of 1024; a chunk is the plain front-to-back composite from T = 1, and the chunks are merged near -> far
@@ -448,6 +453,7 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * configurations - that is exactly the single front-to-back composite; beyond, it differs from it by fp32 rounding, and it lets
  * many waves composite one very deep quadrant at once (the "deep pass", chosen per bin from the previous draw's statistics).
  * The frame does not depend on that choice, on list batching or on how a multi-GPU draw cuts its strips. */
+#define GS_SCHEDULE_WORDS 10
 int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count);
 
 /* VERIFICATION of the blend state (SplatMaterial3D.js:65-75): the reference composites back to front into an RGBA8 target,
