@@ -243,9 +243,13 @@ struct ScopedDevice {
 // sorter object (sorter.hip)
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t SORT_SHARDS = 32;   // min / max words per sort: workgroup b reduces into shard b % 32
+// Where the reference starts its running min / max of the keys (not INT32_MAX / INT32_MIN): what a sort over nothing reports,
+// and the neutral element of every min / max accumulator here.
+constexpr int32_t KEY_MIN_INIT = 2147483640;    // sorter.cpp:25  int minDistance
+constexpr int32_t KEY_MAX_INIT = -2147483640;   // sorter.cpp:24  int maxDistance
 struct SortFrame {            // device-resident per-sort scalars
-    int32_t key_min[SORT_SHARDS];   // atomicMin targets, initialised to +2147483640 (sorter.cpp:25)
-    int32_t key_max[SORT_SHARDS];   // atomicMax targets, initialised to -2147483640 (sorter.cpp:24)
+    int32_t key_min[SORT_SHARDS];   // atomicMin targets, initialised to KEY_MIN_INIT
+    int32_t key_max[SORT_SHARDS];   // atomicMax targets, initialised to KEY_MAX_INIT
     __host__ __device__ int32_t lo() const {
         int32_t v = key_min[0];
         for (uint32_t k = 1; k < SORT_SHARDS; k++) v = key_min[k] < v ? key_min[k] : v;

@@ -72,6 +72,50 @@ __global__ __launch_bounds__(256) void k_aos4_to_soa(const uint4* __restrict__ a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The rules every front-end kernel shares, each said once: the static key, the centre as the frustum test sees it, the
+// housekeeping of a sort's first kernel, the min / max accumulator.
+// ---------------------------------------------------------------------------------------------------
+// The static key of one centre (three words of its plane / AoS entry), integer mode: int32 wrap-around.  sorter.cpp:63-75
+__device__ __forceinline__ int32_t static_key_int(const KeyParams& p, uint32_t x, uint32_t y, uint32_t z) {
+    return (int32_t)(x * (uint32_t)p.im0 + y * (uint32_t)p.im1 + z * (uint32_t)p.im2);
+}
+// ... float mode: fp32 left to right, no contraction, then x4096 in double and WASM's truncation.  sorter.cpp:128-138
+__device__ __forceinline__ int32_t static_key_float(const KeyParams& p, uint32_t xb, uint32_t yb, uint32_t zb) {
+    float s = __fmul_rn(p.fm0, __uint_as_float(xb));
+    s = __fadd_rn(s, __fmul_rn(p.fm1, __uint_as_float(yb)));
+    s = __fadd_rn(s, __fmul_rn(p.fm2, __uint_as_float(zb)));
+    return trunc_f64_i32((double)s * 4096.0);
+}
+__device__ __forceinline__ int32_t static_key(const KeyParams& p, uint32_t x, uint32_t y, uint32_t z) {
+    return (p.mode & MODE_INT) ? static_key_int(p, x, y, z) : static_key_float(p, x, y, z);
+}
+// ... of position i of the SoA planes (the loads inside the mode branch)
+__device__ __forceinline__ int32_t static_key_planes(const KeyParams& p, uint32_t i) {
+    if (p.mode & MODE_INT) return static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
+    return static_key_float(p, p.cx[i], p.cy[i], p.cz[i]);
+}
+// four consecutive splats, one 16-byte vector per plane (integer mode)
+__device__ __forceinline__ int4 static_key_int4(const KeyParams& p, const uint4& x, const uint4& y, const uint4& z) {
+    return make_int4(static_key_int(p, x.x, y.x, z.x), static_key_int(p, x.y, y.y, z.y), static_key_int(p, x.z, y.z, z.z),
+                     static_key_int(p, x.w, y.w, z.w));
+}
+
+// The centre as the frustum test (frustum_keep_one) sees it: the sorter's own centre words as floats.
+__device__ __forceinline__ float3 centre_int_as_float(uint32_t x, uint32_t y, uint32_t z) {
+    return make_float3(__fmul_rn((float)(int32_t)x, 0.001f), __fmul_rn((float)(int32_t)y, 0.001f), __fmul_rn((float)(int32_t)z, 0.001f));
+}
+// ... and the static key with it, in ONE mode branch (c: a gathered centre)
+__device__ __forceinline__ int32_t static_key_centre(const KeyParams& p, const uint4& c, float3& centre) {
+    if (p.mode & MODE_INT) {
+        centre = centre_int_as_float(c.x, c.y, c.z);
+        return static_key_int(p, c.x, c.y, c.z);
+    }
+    centre = make_float3(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z));
+    return static_key_float(p, c.x, c.y, c.z);
+}
+
+// Every mode, for the splat a list entry names: precomputed and dynamic keys, else the static key of its gathered centre.
 __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g) {
     if (p.mode & MODE_PRECOMPUTED) {
         const uint32_t raw = p.precomputed[g];
@@ -79,37 +123,103 @@ __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g)
         return trunc_f64_i32((double)__uint_as_float(raw) * 4096.0);                       // :79-86
     }
     const uint4 c = p.aos[g];                                                              // gathered by list index
-    if (p.mode & MODE_INT) {
-        const uint32_t x = c.x, y = c.y, z = c.z;                                          // wrap-around int32
-        if (p.mode & MODE_DYNAMIC) {                                                       // :41-62
-            const int32_t* r = p.rows->im[p.scene_idx[g]];
-            return (int32_t)(x * (uint32_t)r[0] + y * (uint32_t)r[1] + z * (uint32_t)r[2] + c.w * (uint32_t)r[3]);
-        }
-        return (int32_t)(x * (uint32_t)p.im0 + y * (uint32_t)p.im1 + z * (uint32_t)p.im2); // :63-75, w lane unused
+    if (!(p.mode & MODE_DYNAMIC)) return static_key(p, c.x, c.y, c.z);                     // (w lane unused)
+    if (p.mode & MODE_INT) {                                                               // :41-62, wrap-around int32
+        const int32_t* r = p.rows->im[p.scene_idx[g]];
+        return (int32_t)(c.x * (uint32_t)r[0] + c.y * (uint32_t)r[1] + c.z * (uint32_t)r[2] + c.w * (uint32_t)r[3]);
     }
-    const float x = __uint_as_float(c.x), y = __uint_as_float(c.y), z = __uint_as_float(c.z);
-    float s;
-    if (p.mode & MODE_DYNAMIC) {                                                           // :110-126
-        const float* r = p.rows->fm[p.scene_idx[g]];
-        s = __fmul_rn(r[0], x);
-        s = __fadd_rn(s, __fmul_rn(r[1], y));
-        s = __fadd_rn(s, __fmul_rn(r[2], z));
-        s = __fadd_rn(s, __fmul_rn(r[3], __uint_as_float(c.w)));
-    } else {                                                                               // :128-138
-        s = __fmul_rn(p.fm0, x);
-        s = __fadd_rn(s, __fmul_rn(p.fm1, y));
-        s = __fadd_rn(s, __fmul_rn(p.fm2, z));
-    }
+    const float* r = p.rows->fm[p.scene_idx[g]];                                           // :110-126
+    float s = __fmul_rn(r[0], __uint_as_float(c.x));
+    s = __fadd_rn(s, __fmul_rn(r[1], __uint_as_float(c.y)));
+    s = __fadd_rn(s, __fmul_rn(r[2], __uint_as_float(c.z)));
+    s = __fadd_rn(s, __fmul_rn(r[3], __uint_as_float(c.w)));
     return trunc_f64_i32((double)s * 4096.0);
 }
+
+// The housekeeping folded into the first kernel of a sort (two launches and their boundaries saved per sort): the radix digit
+// totals are zeroed before any histogram adds to them, and the OTHER SortFrame is reset for the next sort.  t / stride: the
+// thread's index in the grid / the grid's size.
+// AGENT (k_depth_key_hist): pass 0's group rows - the first RADIX_MAX_GROUPS x RADIX_BINS words - are added to inside the same
+// launch, behind its barrier, by workgroups of other XCDs: zeroed with agent-scope stores, which go through to the memory side - a
+// plain store would sit dirty in this XCD's L2 until a release wrote the whole L2 back, and 472 such releases made that kernel
+// 80 us long.  The later passes' rows are read by later kernels and take plain stores.
+template <bool AGENT = false>
+__device__ __forceinline__ void sort_begin(const KeyParams& p, uint32_t t, uint32_t stride) {
+    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) {
+        if (AGENT && w < (uint32_t)(RADIX_MAX_GROUPS * RADIX_BINS)) __hip_atomic_store(&p.digit_total[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else p.digit_total[w] = 0u;
+    }
+    if (t < SORT_SHARDS) {
+        p.next_frame->key_min[t] = KEY_MIN_INIT;
+        p.next_frame->key_max[t] = KEY_MAX_INIT;
+    }
+    if (t == 0) {
+        p.next_frame->clamped = 0;
+        p.next_frame->kept = 0;
+    }
+}
+
+// Min / max of the keys a thread has seen, and their way into the sort's SortFrame.
+// No guard for a wave or workgroup that saw nothing: it publishes the two initial values, and an atomicMin with KEY_MIN_INIT
+// (atomicMax with KEY_MAX_INIT) cannot change a word that started there - the same SortFrame with or without the test, and the
+// streaming kernels do without the compare and branch.
+struct MinMax {
+    int32_t lo = KEY_MIN_INIT, hi = KEY_MAX_INIT;
+    __device__ __forceinline__ void take(int32_t k) {
+        lo = min(lo, k);
+        hi = max(hi, k);
+    }
+    __device__ __forceinline__ void take(const int4& k) {
+        lo = min(min(lo, k.x), min(min(k.y, k.z), k.w));
+        hi = max(max(hi, k.x), max(max(k.y, k.z), k.w));
+    }
+    __device__ __forceinline__ void reduce_wave() {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = min(lo, __shfl_xor(lo, o, 64));
+            hi = max(hi, __shfl_xor(hi, o, 64));
+        }
+    }
+    // one device-scope word retires ~88 atomics per microsecond: 2 x 512 workgroups on one pair of words were ~10 us of
+    // k_depth_key's tail.  SORT_SHARDS pairs, reduced by whoever reads them (SortFrame::lo() / hi()).
+    __device__ __forceinline__ void publish(SortFrame* f, uint32_t shard) const {
+        atomicMin(&f->key_min[shard % SORT_SHARDS], lo);
+        atomicMax(&f->key_max[shard % SORT_SHARDS], hi);
+    }
+    // per wave (the whole wave calls)
+    __device__ __forceinline__ void publish_wave(SortFrame* f, uint32_t shard) {
+        reduce_wave();
+        if ((threadIdx.x & 63u) == 0u) publish(f, shard);
+    }
+    // per workgroup of WAVES waves, through LDS (the whole workgroup calls).  Holds the workgroup's ONE barrier: what the kernel
+    // staged in LDS before the call may be read after it.
+    template <int WAVES>
+    __device__ __forceinline__ void publish_block(SortFrame* f) {
+        __shared__ int32_t s_lo[WAVES], s_hi[WAVES];
+        reduce_wave();
+        if ((threadIdx.x & 63u) == 0u) {
+            s_lo[threadIdx.x >> 6] = lo;
+            s_hi[threadIdx.x >> 6] = hi;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            lo = s_lo[0];
+            hi = s_hi[0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) {
+                lo = min(lo, s_lo[w]);
+                hi = max(hi, s_hi[w]);
+            }
+            publish(f, blockIdx.x);
+        }
+    }
+};
 
 // Phase A: keys for list positions [sort_start, render_count) + device-wide min / max.
 // VEC4: identity index list + static integer mode (the Viewer's default, cull off): each lane reads 4 consecutive
 // splats per plane as one 16-byte load and writes 4 keys as one 16-byte store.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void k_depth_key(KeyParams p) {
-    __shared__ int32_t s_lo[4], s_hi[4];
-    int32_t lo = 2147483640, hi = -2147483640;
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (p.ext_minmax) {
@@ -119,16 +229,15 @@ __global__ __launch_bounds__(256) void k_depth_key(KeyParams p) {
         for (uint32_t i = t; i < R; i += stride) p.keys_out[i] = depth_key_one(p, min(p.idx_in[i], p.last_splat));
         return;
     }
-    // housekeeping folded into the first kernel of a sort (two launches and their boundaries saved per sort)
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;   // sorter.cpp:25
-        p.next_frame->key_max[t] = -2147483640;  // sorter.cpp:24
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
+    sort_begin(p, t, stride);
+    MinMax mm;
+    auto scalars = [&](uint32_t begin, uint32_t end) {     // identity-list positions [begin, end), one at a time
+        for (uint32_t i = begin + t; i < end; i += stride) {
+            const int32_t k = depth_key_one(p, i);
+            p.keys_out[i] = k;
+            mm.take(k);
+        }
+    };
     if (VEC4) {
         // positions [a4*4, b4*4) are handled as vectors, the ragged head/tail as scalars by the first lanes
         const uint32_t a4 = (p.sort_start + 3u) / 4u, b4 = p.render_count / 4u;
@@ -136,33 +245,17 @@ __global__ __launch_bounds__(256) void k_depth_key(KeyParams p) {
         const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
         const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
         int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-        const uint32_t m0 = (uint32_t)p.im0, m1 = (uint32_t)p.im1, m2 = (uint32_t)p.im2;
         for (uint32_t v = a4 + t; v < b4; v += stride) {
-            const uint4 x = x4[v], y = y4[v], z = z4[v];
-            int4 k;
-            k.x = (int32_t)(x.x * m0 + y.x * m1 + z.x * m2);
-            k.y = (int32_t)(x.y * m0 + y.y * m1 + z.y * m2);
-            k.z = (int32_t)(x.z * m0 + y.z * m1 + z.z * m2);
-            k.w = (int32_t)(x.w * m0 + y.w * m1 + z.w * m2);
+            const int4 k = static_key_int4(p, x4[v], y4[v], z4[v]);
             o4[v] = k;
-            lo = min(min(lo, k.x), min(min(k.y, k.z), k.w));
-            hi = max(max(hi, k.x), max(max(k.y, k.z), k.w));
+            mm.take(k);
         }
         if (a4 <= b4) {
             const uint32_t head_end = min(a4 * 4u, p.render_count), tail_begin = max(b4 * 4u, head_end);
-            for (uint32_t i = p.sort_start + t; i < head_end; i += stride) {
-                const int32_t k = depth_key_one(p, i);
-                p.keys_out[i] = k; lo = min(lo, k); hi = max(hi, k);
-            }
-            for (uint32_t i = tail_begin + t; i < p.render_count; i += stride) {
-                const int32_t k = depth_key_one(p, i);
-                p.keys_out[i] = k; lo = min(lo, k); hi = max(hi, k);
-            }
+            scalars(p.sort_start, head_end);
+            scalars(tail_begin, p.render_count);
         } else {                                           // fewer than one aligned vector: all scalar
-            for (uint32_t i = p.sort_start + t; i < p.render_count; i += stride) {
-                const int32_t k = depth_key_one(p, i);
-                p.keys_out[i] = k; lo = min(lo, k); hi = max(hi, k);
-            }
+            scalars(p.sort_start, p.render_count);
         }
     } else {
         // the list's length may live on the device (an asynchronous gs_tree_gather): the sorted result then has that length,
@@ -173,29 +266,10 @@ __global__ __launch_bounds__(256) void k_depth_key(KeyParams p) {
             const uint32_t g = p.idx_in ? min(p.idx_in[i], p.last_splat) : i;
             const int32_t k = depth_key_one(p, g);
             p.keys_out[i] = k;
-            lo = min(lo, k);
-            hi = max(hi, k);
+            mm.take(k);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-    }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_lo[wave] = lo;
-        s_hi[wave] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
-        hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-        // one device-scope word retires ~88 atomics per microsecond: 2 x 512 workgroups on one pair of words were ~10 us of
-        // this kernel's tail.  SORT_SHARDS pairs, reduced by whoever reads them (SortFrame::lo() / hi()).
-        atomicMin(&p.frame->key_min[blockIdx.x % SORT_SHARDS], lo);
-        atomicMax(&p.frame->key_max[blockIdx.x % SORT_SHARDS], hi);
-    }
+    mm.publish_block<4>(p.frame);
 }
 
 // Phase A with the per-splat frustum cull (gs_sorter_set_frustum_cull).  Same keys, same min / max over EVERY list
@@ -206,19 +280,18 @@ __global__ __launch_bounds__(256) void k_depth_key(KeyParams p) {
 // splat on |clip.xy| > 1.2 w, clip.z < -1.2 w or ndc.z outside [-1, 1] (SplatMaterial.js:160-164 and the GL clip of a
 // quad that sits at its centre's depth), so for the same camera the kept set is a superset of what can reach the
 // frame, and the frame is bit-identical to the one the full sort produces.  Restated in oracle.frustum_keep.
-__device__ __forceinline__ bool frustum_keep_one(const float* m, float x, float y, float z) {
+__device__ __forceinline__ bool frustum_keep_one(const float* m, const float3 c) {
     float q[4];
 #pragma unroll
     for (int r = 0; r < 4; r++)
-        q[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[r], x), __fmul_rn(m[4 + r], y)), __fmul_rn(m[8 + r], z)), m[12 + r]);
+        q[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[r], c.x), __fmul_rn(m[4 + r], c.y)), __fmul_rn(m[8 + r], c.z)), m[12 + r]);
     const float lim_xy = __fadd_rn(__fmul_rn(1.25f, q[3]), 0.01f);
     const float lim_z = __fadd_rn(__fmul_rn(1.01f, q[3]), 0.01f);
     return !(fabsf(q[0]) > lim_xy || fabsf(q[1]) > lim_xy || q[2] < -lim_z || q[2] > lim_z);
 }
 
 __device__ __forceinline__ bool frustum_keep_int(const float* m, uint32_t x, uint32_t y, uint32_t z) {
-    return frustum_keep_one(m, __fmul_rn((float)(int32_t)x, 0.001f), __fmul_rn((float)(int32_t)y, 0.001f),
-                            __fmul_rn((float)(int32_t)z, 0.001f));
+    return frustum_keep_one(m, centre_int_as_float(x, y, z));
 }
 
 // VEC4 (identity list, static integer mode): lane l of a wave owns positions 4*(v0 + l) .. +3 of a 256-position window,
@@ -227,22 +300,11 @@ __device__ __forceinline__ bool frustum_keep_int(const float* m, uint32_t x, uin
 // every ballot is one mask word.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void k_depth_key_cull(KeyParams p) {
-    __shared__ int32_t s_lo[4], s_hi[4];
-    __shared__ uint32_t s_kept[4];
-    int32_t lo = 2147483640, hi = -2147483640;
-    uint32_t kept = 0;
     const uint32_t stride = gridDim.x * blockDim.x;               // a multiple of 64
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;
-        p.next_frame->key_max[t] = -2147483640;
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sort_begin(p, t, stride);
+    MinMax mm;
+    const uint32_t lane = threadIdx.x & 63;
     // sort_start == 0 in this variant; the length of a gathered list may live on the device (asynchronous gs_tree_gather)
     const uint32_t R = (!VEC4 && p.count_dev) ? min(*p.count_dev, p.render_count) : p.render_count;
     if (VEC4) {
@@ -251,19 +313,13 @@ __global__ __launch_bounds__(256) void k_depth_key_cull(KeyParams p) {
         const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
         const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
         int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-        const uint32_t m0 = (uint32_t)p.im0, m1 = (uint32_t)p.im1, m2 = (uint32_t)p.im2;
         for (uint32_t v = t; v < padded; v += stride) {
             uint32_t nib = 0;
             if (v < full) {
                 const uint4 x = x4[v], y = y4[v], z = z4[v];
-                int4 k;
-                k.x = (int32_t)(x.x * m0 + y.x * m1 + z.x * m2);
-                k.y = (int32_t)(x.y * m0 + y.y * m1 + z.y * m2);
-                k.z = (int32_t)(x.z * m0 + y.z * m1 + z.z * m2);
-                k.w = (int32_t)(x.w * m0 + y.w * m1 + z.w * m2);
+                const int4 k = static_key_int4(p, x, y, z);
                 o4[v] = k;
-                lo = min(min(lo, k.x), min(min(k.y, k.z), k.w));
-                hi = max(max(hi, k.x), max(max(k.y, k.z), k.w));
+                mm.take(k);
                 nib = (frustum_keep_int(p.mvp, x.x, y.x, z.x) ? 1u : 0u) | (frustum_keep_int(p.mvp, x.y, y.y, z.y) ? 2u : 0u) |
                       (frustum_keep_int(p.mvp, x.z, y.z, z.z) ? 4u : 0u) | (frustum_keep_int(p.mvp, x.w, y.w, z.w) ? 8u : 0u);
             } else if (v < nvec) {                                 // the ragged last vector
@@ -271,13 +327,13 @@ __global__ __launch_bounds__(256) void k_depth_key_cull(KeyParams p) {
                     const uint32_t i = 4u * v + c;
                     if (i < R) {
                         const uint32_t x = p.cx[i], y = p.cy[i], z = p.cz[i];
-                        const int32_t k = (int32_t)(x * m0 + y * m1 + z * m2);
-                        p.keys_out[i] = k; lo = min(lo, k); hi = max(hi, k);
+                        const int32_t k = static_key_int(p, x, y, z);
+                        p.keys_out[i] = k;
+                        mm.take(k);
                         nib |= frustum_keep_int(p.mvp, x, y, z) ? (1u << c) : 0u;
                     }
                 }
             }
-            kept += (uint32_t)__popc(nib);
             unsigned long long word = (unsigned long long)nib << (4u * (lane & 15u));
 #pragma unroll
             for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
@@ -302,55 +358,23 @@ __global__ __launch_bounds__(256) void k_depth_key_cull(KeyParams p) {
                 keep[k] = false;
                 if (in[k]) {
                     const uint32_t i = base + 64u * k + lane;
-                    int32_t key;
-                    float x, y, z;
-                    if (p.mode & MODE_INT) {
-                        key = (int32_t)(c[k].x * (uint32_t)p.im0 + c[k].y * (uint32_t)p.im1 + c[k].z * (uint32_t)p.im2);
-                        x = __fmul_rn((float)(int32_t)c[k].x, 0.001f); y = __fmul_rn((float)(int32_t)c[k].y, 0.001f);
-                        z = __fmul_rn((float)(int32_t)c[k].z, 0.001f);
-                    } else {
-                        x = __uint_as_float(c[k].x); y = __uint_as_float(c[k].y); z = __uint_as_float(c[k].z);
-                        float s = __fmul_rn(p.fm0, x);
-                        s = __fadd_rn(s, __fmul_rn(p.fm1, y));
-                        s = __fadd_rn(s, __fmul_rn(p.fm2, z));
-                        key = trunc_f64_i32((double)s * 4096.0);
-                    }
+                    float3 centre;
+                    const int32_t key = static_key_centre(p, c[k], centre);
                     p.keys_out[i] = key;
-                    lo = min(lo, key);
-                    hi = max(hi, key);
-                    keep[k] = frustum_keep_one(p.mvp, x, y, z);
+                    mm.take(key);
+                    keep[k] = frustum_keep_one(p.mvp, centre);
                 }
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const unsigned long long word = __ballot(keep[k]);
-                if (lane == 0 && base + 64u * k < padded) {
-                    p.keep[(base >> 6) + k] = word;
-                    kept += (uint32_t)__popcll(word);
-                }
+                if (lane == 0 && base + 64u * k < padded) p.keep[(base >> 6) + k] = word;
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-        kept += __shfl_xor(kept, o, 64);
-    }
-    if (lane == 0) {
-        s_lo[wave] = lo;
-        s_hi[wave] = hi;
-        s_kept[wave] = kept;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
-        hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-        atomicMin(&p.frame->key_min[blockIdx.x % SORT_SHARDS], lo);
-        atomicMax(&p.frame->key_max[blockIdx.x % SORT_SHARDS], hi);
-        // (the number of kept positions is published by pass 0 of the radix sort - the sum of its digit totals - instead of by
-        // one atomicAdd per workgroup on a single word here: radix.hpp, count_out)
-    }
+    // (the number of kept positions is published by pass 0 of the radix sort - the sum of its digit totals - instead of by
+    // one atomicAdd per workgroup on a single word here: radix.hpp, count_out)
+    mm.publish_block<4>(p.frame);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -382,23 +406,11 @@ __global__ __launch_bounds__(256) void k_tree_leaf_cache(const uint32_t* __restr
 
 template <bool CULL>
 __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyParams p) {
-    __shared__ int32_t s_lo[4], s_hi[4];
-    __shared__ uint32_t s_kept[4];
     const uint32_t stride = gridDim.x * blockDim.x, gt = blockIdx.x * blockDim.x + threadIdx.x;
-    // the housekeeping of a sort's first kernel (see k_depth_key)
-    for (uint32_t w = gt; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
-    if (gt < SORT_SHARDS) {
-        p.next_frame->key_min[gt] = 2147483640;
-        p.next_frame->key_max[gt] = -2147483640;
-    }
-    if (gt == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-        if (!CULL) p.frame->kept = c.v.totals[0];            // the list's length, where the consumers of a culled sort look for it
-    }
+    sort_begin(p, gt, stride);
+    if (!CULL && gt == 0) p.frame->kept = c.v.totals[0];     // the list's length, where the consumers of a culled sort look for it
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    int32_t lo = 2147483640, hi = -2147483640;
-    uint32_t kept = 0;
+    MinMax mm;
     // A wave's work is a sequence of ROUNDS: 256 consecutive entries (four 64-splat slices, twelve loads that leave together) of
     // one kept leaf's list - a leaf holds ~200 splats, so most leaves are one round.  Round 6: the loads of round k + 1 are issued
     // BEFORE round k is keyed and stored (two register sets, no copies: the loop is unrolled by two), also across leaves; before,
@@ -441,30 +453,15 @@ __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyPar
         for (int k = 0; k < 4; k++) {
             const uint32_t t = t0 + 64u * k + lane;
             const bool in = t < n;
-            int32_t key;
-            float x, y, z;
-            if (p.mode & MODE_INT) {
-                key = (int32_t)(L.ce[k].x * (uint32_t)p.im0 + L.ce[k].y * (uint32_t)p.im1 + L.ce[k].z * (uint32_t)p.im2);
-                x = __fmul_rn((float)(int32_t)L.ce[k].x, 0.001f); y = __fmul_rn((float)(int32_t)L.ce[k].y, 0.001f);
-                z = __fmul_rn((float)(int32_t)L.ce[k].z, 0.001f);
-            } else {
-                x = __uint_as_float(L.ce[k].x); y = __uint_as_float(L.ce[k].y); z = __uint_as_float(L.ce[k].z);
-                float s = __fmul_rn(p.fm0, x);
-                s = __fadd_rn(s, __fmul_rn(p.fm1, y));
-                s = __fadd_rn(s, __fmul_rn(p.fm2, z));
-                key = trunc_f64_i32((double)s * 4096.0);
-            }
+            float3 centre;
+            const int32_t key = static_key_centre(p, L.ce[k], centre);
             if (in) {
                 c.idx_out[off + t] = L.idx[k];
                 c.pay_out[off + t] = L.pos[k];
                 p.keys_out[off + t] = key;
-                lo = min(lo, key);
-                hi = max(hi, key);
+                mm.take(key);
             }
-            if (CULL) {
-                bits[k] = __ballot(in && frustum_keep_one(p.mvp, x, y, z));
-                kept += (uint32_t)__popcll(bits[k]);         // (the same value in every lane)
-            }
+            if (CULL) bits[k] = __ballot(in && frustum_keep_one(p.mvp, centre));
         }
         if (CULL && lane == 0u) {
             // The round's 256 list positions start at `first`: four words of the (zeroed) keep mask and a carry into the
@@ -499,26 +496,7 @@ __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyPar
         load(ra, A);
         process(rb, B);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0) {
-        s_lo[wave] = lo;
-        s_hi[wave] = hi;
-        s_kept[wave] = kept;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lo = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
-        hi = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-        if (lo <= hi) {
-            atomicMin(&p.frame->key_min[blockIdx.x % SORT_SHARDS], lo);
-            atomicMax(&p.frame->key_max[blockIdx.x % SORT_SHARDS], hi);
-        }
-        // (CULL: the kept count is published by pass 0 of the radix sort, radix.hpp count_out)
-    }
+    mm.publish_block<4>(p.frame);                            // (CULL: the kept count is published by pass 0 of the radix sort, radix.hpp count_out)
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -534,48 +512,21 @@ __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyPar
 // A rank of a multi-GPU draw therefore streams 12 bytes per splat and radix-sorts only what its strip draws.
 constexpr uint32_t VC_THREADS = 256, VC_SPAN = 1024;       // positions per workgroup iteration (4 per lane; 32 mask words)
 
-__device__ __forceinline__ int32_t depth_key_planes(const KeyParams& p, uint32_t i) {
-    if (p.mode & MODE_INT) return (int32_t)(p.cx[i] * (uint32_t)p.im0 + p.cy[i] * (uint32_t)p.im1 + p.cz[i] * (uint32_t)p.im2);
-    float s = __fmul_rn(p.fm0, __uint_as_float(p.cx[i]));
-    s = __fadd_rn(s, __fmul_rn(p.fm1, __uint_as_float(p.cy[i])));
-    s = __fadd_rn(s, __fmul_rn(p.fm2, __uint_as_float(p.cz[i])));
-    return trunc_f64_i32((double)s * 4096.0);
-}
-
 __global__ __launch_bounds__(VC_THREADS) void k_minmax_count(KeyParams p, const uint32_t* __restrict__ mask, uint32_t chunk_len,
                                                              uint32_t* __restrict__ chunk_counts) {
-    __shared__ int32_t s_lo[4], s_hi[4];
     __shared__ uint32_t s_cnt[4];
-    const uint32_t stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;
-        p.next_frame->key_max[t] = -2147483640;
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
+    sort_begin(p, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     const uint32_t N = p.render_count;
     const uint32_t begin = min(blockIdx.x * chunk_len, N), end = min(begin + chunk_len, N);     // chunk_len % VC_SPAN == 0
-    int32_t lo = 2147483640, hi = -2147483640;
+    MinMax mm;
     uint32_t cnt = 0;
-    const uint32_t m0 = (uint32_t)p.im0, m1 = (uint32_t)p.im1, m2 = (uint32_t)p.im2;
     for (uint32_t base = begin; base < end; base += VC_SPAN) {
         const uint32_t i0 = base + 4u * threadIdx.x;
         if ((p.mode & MODE_INT) && i0 + 4u <= end) {               // 16-byte plane loads
-            const uint4 x = reinterpret_cast<const uint4*>(p.cx)[i0 >> 2], y = reinterpret_cast<const uint4*>(p.cy)[i0 >> 2],
-                        z = reinterpret_cast<const uint4*>(p.cz)[i0 >> 2];
-            const int32_t k0 = (int32_t)(x.x * m0 + y.x * m1 + z.x * m2), k1 = (int32_t)(x.y * m0 + y.y * m1 + z.y * m2);
-            const int32_t k2 = (int32_t)(x.z * m0 + y.z * m1 + z.z * m2), k3 = (int32_t)(x.w * m0 + y.w * m1 + z.w * m2);
-            lo = min(min(lo, k0), min(min(k1, k2), k3));
-            hi = max(max(hi, k0), max(max(k1, k2), k3));
+            mm.take(static_key_int4(p, reinterpret_cast<const uint4*>(p.cx)[i0 >> 2], reinterpret_cast<const uint4*>(p.cy)[i0 >> 2],
+                                    reinterpret_cast<const uint4*>(p.cz)[i0 >> 2]));
         } else {
-            for (uint32_t i = i0; i < min(i0 + 4u, end); i++) {
-                const int32_t k = depth_key_planes(p, i);
-                lo = min(lo, k);
-                hi = max(hi, k);
-            }
+            for (uint32_t i = i0; i < min(i0 + 4u, end); i++) mm.take(static_key_planes(p, i));
         }
         const uint32_t w = (base >> 5) + threadIdx.x;              // the 32 mask words of this span
         // (a sort over fewer splats than the vertex stage looked at leaves set bits beyond `end` in the last word)
@@ -583,19 +534,10 @@ __global__ __launch_bounds__(VC_THREADS) void k_minmax_count(KeyParams p, const 
             cnt += (uint32_t)__popc(mask[w] & (end - (w << 5) >= 32u ? 0xFFFFFFFFu : (1u << (end - (w << 5))) - 1u));
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-        cnt += __shfl_xor(cnt, o, 64);
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) { s_lo[wave] = lo; s_hi[wave] = hi; s_cnt[wave] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMin(&p.frame->key_min[blockIdx.x % SORT_SHARDS], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
-        atomicMax(&p.frame->key_max[blockIdx.x % SORT_SHARDS], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
-        chunk_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63u) == 0u) s_cnt[threadIdx.x >> 6] = cnt;
+    mm.publish_block<4>(p.frame);                                  // (and its barrier: s_cnt is complete)
+    if (threadIdx.x == 0) chunk_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
 // The mask is CONSUMED: every word is copied to the sorter's own buffer (gs_sorter_debug_read) and zeroed, which is the state the
@@ -666,16 +608,7 @@ constexpr uint32_t VC_TURN = VC_UNROLL * VC_WAVE_SPAN * (VC_THREADS / 64u);   //
 __global__ __launch_bounds__(VC_THREADS) void k_mask_count(KeyParams p, const uint32_t* __restrict__ mask, uint32_t chunk_len,
                                                            uint32_t* __restrict__ chunk_counts) {
     __shared__ uint32_t s_cnt[4];
-    const uint32_t stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;
-        p.next_frame->key_max[t] = -2147483640;
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
+    sort_begin(p, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     const uint32_t N = p.render_count;
     const uint32_t begin = min(blockIdx.x * chunk_len, N), end = min(begin + chunk_len, N);
     uint32_t cnt = 0;
@@ -708,16 +641,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_mask_derive_count(KeyParams p, c
                                                                   uint32_t* __restrict__ chunk_counts) {
     __shared__ uint32_t s_cnt[4];
     __shared__ uint32_t s_any[VC_ANY_WORDS];
-    const uint32_t stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;      // (the sort's housekeeping: k_mask_count's)
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;
-        p.next_frame->key_max[t] = -2147483640;
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
+    sort_begin(p, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     const bool coarse = blocks <= VC_ANY_WORDS * 32u;
     if (coarse) {
         for (uint32_t w = threadIdx.x; w < (blocks + 31u) / 32u; w += VC_THREADS) {
@@ -812,8 +736,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
     if (blockIdx.x == 0u && threadIdx.x == 0u) p.frame->kept = s_all[0] + s_all[1] + s_all[2] + s_all[3];
     const uint32_t N = p.render_count;
     const uint32_t begin = min(blockIdx.x * chunk_len, N), end = min(begin + chunk_len, N);       // chunk_len % VC_TURN == 0
-    int32_t lo = 2147483640, hi = -2147483640;
-    const uint32_t m0 = (uint32_t)p.im0, m1 = (uint32_t)p.im1, m2 = (uint32_t)p.im2;
+    MinMax mm;
     const uint4* __restrict__ x4 = reinterpret_cast<const uint4*>(p.cx);
     const uint4* __restrict__ y4 = reinterpret_cast<const uint4*>(p.cy);
     const uint4* __restrict__ z4 = reinterpret_cast<const uint4*>(p.cz);
@@ -855,18 +778,8 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
                                zs[4] = {cur.Z[u].x, cur.Z[u].y, cur.Z[u].z, cur.Z[u].w};
 #pragma unroll
                 for (uint32_t c = 0; c < 4u; c++) {
-                    if (p.mode & MODE_INT) {
-                        k[c] = (int32_t)(xs[c] * m0 + ys[c] * m1 + zs[c] * m2);
-                    } else {
-                        float sm = __fmul_rn(p.fm0, __uint_as_float(xs[c]));
-                        sm = __fadd_rn(sm, __fmul_rn(p.fm1, __uint_as_float(ys[c])));
-                        sm = __fadd_rn(sm, __fmul_rn(p.fm2, __uint_as_float(zs[c])));
-                        k[c] = trunc_f64_i32((double)sm * 4096.0);
-                    }
-                    if (i0 + c < end) {                                    // (min / max over the list's positions only)
-                        lo = min(lo, k[c]);
-                        hi = max(hi, k[c]);
-                    }
+                    k[c] = static_key(p, xs[c], ys[c], zs[c]);
+                    if (i0 + c < end) mm.take(k[c]);                       // (min / max over the list's positions only)
                 }
             }
             const uint32_t nib = (word >> (i0 & 31u)) & 15u, mine = (uint32_t)__popc(nib);
@@ -910,15 +823,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
         }
         cur = nxt;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0u && lo <= hi) {
-        atomicMin(&p.frame->key_min[(blockIdx.x * 4u + wave) % SORT_SHARDS], lo);
-        atomicMax(&p.frame->key_max[(blockIdx.x * 4u + wave) % SORT_SHARDS], hi);
-    }
+    mm.publish_wave(p.frame, blockIdx.x * 4u + wave);
 }
 
 // Phase B as a radix loader.  Logical element j <-> list position i = R-1-j (reverse traversal makes the
@@ -926,8 +831,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
 // IDX: the list is an index (or ready-made payload) array, not the identity - a compile-time switch: as a run-time `idx ? load : i`
 // every index load sat in a branch of its own with a full memory wait behind it, eight serialised round trips per tile in every
 // sort of a gathered / compacted list (r05k ISA of the pass-0 scatter).
-template <bool CULL, bool IDX>
-struct DepthLoaderT {
+struct DepthLoaderArgs {                   // what every (CULL, IDX) variant is built from; the kernel-argument layout of all of them
     const int32_t* __restrict__ keys;
     const unsigned long long* __restrict__ keep;   // CULL: 1 bit per list position (k_depth_key_cull)
     const uint32_t* __restrict__ idx;      // nullable: identity
@@ -939,14 +843,19 @@ struct DepthLoaderT {
     uint32_t count_clamps;                 // only the histogram launch counts, so each element counts once
     int32_t lo;
     float range_map;
-
+};
+template <bool CULL, bool IDX>
+struct DepthLoaderT : DepthLoaderArgs {
     __device__ __forceinline__ void prepare() {
         if (n_dev) render_count = *n_dev;                       // sort_start is 0 in that variant
         // the sort's min / max live in SORT_SHARDS words each: lane l reads shard l, five xor-shuffles reduce them
         // (every thread reading all 64 words cost the histogram kernel 5 us)
         const uint32_t l = threadIdx.x & (SORT_SHARDS - 1u);
-        lo = frame->key_min[l];
-        int32_t hi = frame->key_max[l];
+        set_range(frame->key_min[l], frame->key_max[l]);
+    }
+    // lo / hi: shard (lane % SORT_SHARDS) of the sort's min / max, as this lane read it
+    __device__ __forceinline__ void set_range(int32_t lo_shard, int32_t hi) {
+        lo = lo_shard;
 #pragma unroll
         for (int o = SORT_SHARDS / 2; o > 0; o >>= 1) {
             lo = min(lo, __shfl_xor(lo, o, 64));
@@ -1063,26 +972,8 @@ struct KeyHistSync {
 __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, DepthLoader ld, int shift, uint32_t* __restrict__ block_hist,
                                                                   uint32_t* __restrict__ digit_total, KeyHistSync sync) {
     __shared__ uint32_t s_hist[4][RADIX_BINS];
-    __shared__ int32_t s_lo[HIST_THREADS / 64], s_hi[HIST_THREADS / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + tid;
-    // (k_depth_key's housekeeping.  The group rows are added to BEHIND the barrier by workgroups of other XCDs: zeroed with
-    // agent-scope stores, which go through to the memory side - a plain store would sit dirty in this XCD's L2 until a release
-    // wrote the whole L2 back, and 472 such releases made this kernel 80 us long)
-    // (only pass 0's rows - the first RADIX_MAX_GROUPS x RADIX_BINS words - are touched inside this launch; the later passes' rows are
-    // read by later kernels and take plain stores)
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) {
-        if (w < (uint32_t)(RADIX_MAX_GROUPS * RADIX_BINS)) __hip_atomic_store(&p.digit_total[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else p.digit_total[w] = 0u;
-    }
-    if (t < SORT_SHARDS) {
-        p.next_frame->key_min[t] = 2147483640;
-        p.next_frame->key_max[t] = -2147483640;
-    }
-    if (t == 0) {
-        p.next_frame->clamped = 0;
-        p.next_frame->kept = 0;
-    }
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    sort_begin<true>(p, blockIdx.x * blockDim.x + tid, gridDim.x * blockDim.x);   // (pass 0's rows are added to behind the barrier below)
     for (uint32_t k = tid; k < 4u * RADIX_BINS; k += HIST_THREADS) (&s_hist[0][0])[k] = 0;
     const uint32_t R = p.render_count;
     const RadixChunk ch = radix_chunk(R);
@@ -1095,9 +986,8 @@ __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, De
     const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
     const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
     int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-    const uint32_t m0 = (uint32_t)p.im0, m1 = (uint32_t)p.im1, m2 = (uint32_t)p.im2;
     int4 key[KV];
-    int32_t lo = 2147483640, hi = -2147483640;
+    MinMax mm;
     uint4 x[KV], y[KV], z[KV];
 #pragma unroll
     for (uint32_t k = 0; k < KV; k++) {
@@ -1107,29 +997,14 @@ __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, De
 #pragma unroll
     for (uint32_t k = 0; k < KV; k++) {
         const uint32_t v = v0 + k * HIST_THREADS + tid;
-        key[k].x = (int32_t)(x[k].x * m0 + y[k].x * m1 + z[k].x * m2);
-        key[k].y = (int32_t)(x[k].y * m0 + y[k].y * m1 + z[k].y * m2);
-        key[k].z = (int32_t)(x[k].z * m0 + y[k].z * m1 + z[k].z * m2);
-        key[k].w = (int32_t)(x[k].w * m0 + y[k].w * m1 + z[k].w * m2);
+        key[k] = static_key_int4(p, x[k], y[k], z[k]);
         if (v < v1) {
             o4[v] = key[k];
-            lo = min(min(lo, key[k].x), min(min(key[k].y, key[k].z), key[k].w));
-            hi = max(max(hi, key[k].x), max(max(key[k].y, key[k].z), key[k].w));
+            mm.take(key[k]);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o, 64));
-        hi = max(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0) { s_lo[wave] = lo; s_hi[wave] = hi; }
-    __syncthreads();
+    mm.publish_block<HIST_THREADS / 64>(p.frame);
     if (tid == 0) {
-        for (uint32_t w = 1; w < HIST_THREADS / 64; w++) { lo = min(lo, s_lo[w]); hi = max(hi, s_hi[w]); }
-        if (v1 > v0) {
-            atomicMin(&p.frame->key_min[blockIdx.x % SORT_SHARDS], lo);
-            atomicMax(&p.frame->key_max[blockIdx.x % SORT_SHARDS], hi);
-        }
         // The barrier across the grid.  What the other workgroups need from this one are agent-scope atomics and stores (min / max,
         // the zeroed group rows): performed at the memory side, so "complete" is "visible" - the arrival only has to be issued after
         // they are complete (a workgroup-scope release = s_waitcnt), not after an L2 write-back.  The keys and the histogram rows are
@@ -1146,19 +1021,8 @@ __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, De
     }
     __syncthreads();
     // phase 2: the final range (fresh loads: the words were written by other workgroups' atomics)
-    {
-        const uint32_t l = tid & (SORT_SHARDS - 1u);
-        int32_t glo = __hip_atomic_load(&ld.frame->key_min[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int32_t ghi = __hip_atomic_load(&ld.frame->key_max[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int o = SORT_SHARDS / 2; o > 0; o >>= 1) {
-            glo = min(glo, __shfl_xor(glo, o, 64));
-            ghi = max(ghi, __shfl_xor(ghi, o, 64));
-        }
-        ld.range_map = __fdiv_rn((float)(ld.range - 1), __fsub_rn((float)ghi, (float)glo));
-        ld.lo = __builtin_amdgcn_readfirstlane(glo);
-        ld.range_map = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ld.range_map)));
-    }
+    ld.set_range(__hip_atomic_load(&ld.frame->key_min[tid & (SORT_SHARDS - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                 __hip_atomic_load(&ld.frame->key_max[tid & (SORT_SHARDS - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     uint32_t* hist = s_hist[wave & 3u];
 #pragma unroll
     for (uint32_t k = 0; k < KV; k++) {
@@ -1185,8 +1049,7 @@ __global__ void k_debug_buckets(DepthLoader ld, int32_t* out) {
 
 // Pass 0 of a depth sort for one (CULL, IDX) combination of the loader: packed + chunk-staged, packed, or key + value output.
 struct Pass0Args {
-    DepthLoader base;                   // the fields every variant shares (copied member by member below)
-    const unsigned long long* keep;
+    DepthLoaderArgs ld;
     uint32_t Rs, val_bits;
     int shift;
     bool pack, chunked, wide;
@@ -1198,9 +1061,7 @@ struct Pass0Args {
 template <bool CULL, bool IDX>
 static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
     typedef DepthLoaderT<CULL, IDX> L;
-    L d = {};
-    d.keys = a.base.keys; d.keep = a.keep; d.idx = a.base.idx; d.map = a.base.map; d.frame = a.base.frame; d.n_dev = a.base.n_dev;
-    d.sort_start = a.base.sort_start; d.render_count = a.base.render_count; d.range = a.base.range; d.last_splat = a.base.last_splat;
+    const L d = {a.ld};
     L h = d;                            // only the histogram launch counts clamped buckets (once per element)
     h.count_clamps = 1;
     if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, a.vo, a.val_bits, a.kept_out, a.skip_hist);
@@ -1255,7 +1116,7 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     if (st == GS_OK) {
         SortFrame init[2];
         for (SortFrame& f : init) {
-            for (uint32_t k = 0; k < SORT_SHARDS; k++) { f.key_min[k] = 2147483640; f.key_max[k] = -2147483640; }
+            for (uint32_t k = 0; k < SORT_SHARDS; k++) { f.key_min[k] = KEY_MIN_INIT; f.key_max[k] = KEY_MAX_INIT; }
             f.clamped = f.kept = 0;
         }
         if (hipMemcpy(s->frame.p, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1356,8 +1217,8 @@ static int sorter_collect_stats(gs_sorter* s, gs_sort_stats* stats) {
     if (s->timed_sort) GS_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     int32_t key_lo = f.lo(), key_hi = f.hi();
     if (s->last_sort == 0) {                       // nothing was keyed: the frame belongs to an earlier sort
-        key_lo = 2147483640;
-        key_hi = -2147483640;
+        key_lo = KEY_MIN_INIT;
+        key_hi = KEY_MAX_INIT;
         f.clamped = 0;
     }
     stats->device_ms = ms;
@@ -1369,12 +1230,76 @@ static int sorter_collect_stats(gs_sorter* s, gs_sort_stats* stats) {
     return f.clamped ? GS_WARN_KEY_CLAMPED : GS_OK;
 }
 
-static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_sort, bool device_list,
-                            uint32_t sort_count, uint32_t render_count, const void* precomputed, const float* transforms,
-                            uint32_t* sorted_out, gs_sort_stats* stats, const uint32_t* list_count_dev = nullptr) {
-    GS_REQUIRE(s && mvp, "sorter / mvp == NULL");
-    const bool pre_device = precomputed == GS_PRECOMPUTED_DEVICE;
-    if (pre_device) {
+// ---------------------------------------------------------------------------------------------------
+// One sort, in steps: sort_check -> sort_stage_inputs -> launch_front_end -> run_radix_passes -> sort_finish.
+// ---------------------------------------------------------------------------------------------------
+// The switches of this file (A/B runs and tests), read here and nowhere else.
+struct SortSwitches {
+    // read once per process, at its first sort (the tests and the soaks start a child process per setting):
+    bool tree_no_fuse;         // $GSPLAT_TREE_NO_FUSE: a planned gather is copied by tree.hip, never by the key kernel
+    const char* vis_front;     // $GSPLAT_VIS_FRONT = stream | compact: forces one front end of the visibility cull
+    bool no_pack;              // $GSPLAT_NO_SORT_PACK: the unpacked radix passes
+    bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
+    // read on every sort (tests and the soaks set it inside a running process):
+    bool key_hist_fused;       // $GSPLAT_KEY_HIST_FUSED, unless one of the two above is set in the environment NOW
+};
+static SortSwitches sort_switches() {
+    static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
+    static const char* vis_front = getenv("GSPLAT_VIS_FRONT");
+    static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
+    static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
+    return {tree_no_fuse, vis_front, no_pack, no_chunk,
+            getenv("GSPLAT_KEY_HIST_FUSED") && !getenv("GSPLAT_NO_SORT_PACK") && !getenv("GSPLAT_NO_SORT_CHUNK")};
+}
+
+static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
+    for (const gs_mesh* l : ctx->live_meshes)
+        if (l == m) return m != nullptr;
+    return false;
+}
+
+// The cut of R > 0 positions for a streaming front end: a workgroup owns a contiguous run of whole units, at most two
+// workgroups per CU.
+struct ChunkGrid { uint32_t grid, len; };
+static ChunkGrid chunk_grid(const gs_context* ctx, uint32_t R, uint32_t unit) {
+    const uint32_t units = (R + unit - 1u) / unit;
+    const uint32_t grid = units < (uint32_t)ctx->cu_count * 2u ? units : (uint32_t)ctx->cu_count * 2u;
+    return {grid, ((units + grid - 1u) / grid) * unit};
+}
+
+struct SortPlan {
+    // the call
+    const float* mvp;
+    const uint32_t* indexes_to_sort;
+    bool device_list;                  // the list is what gs_tree_gather left (or planned) in idx_in
+    const void* precomputed;
+    const float* transforms;
+    const uint32_t* list_count_dev;    // the list's real length lives on the device (asynchronous gs_tree_gather); R bounds it
+    // sort_check
+    uint32_t R, Rs, sort_start;        // render count, sort count (both clamped), R - Rs
+    bool pre_device, dynamic;
+    bool vis_cull;                     // compact by the bound mesh's visibility mask, then sort the survivors
+    bool cull;                         // the frustum cull's keep-mask path; the visibility cull compacts instead
+    const uint32_t *map, *unmap;       // a bound mesh stores its splats in its own (Morton) order: hand it positions in that order
+    uint32_t last_splat;               // uploaded - 1: list entries are clamped to it
+    // The payload's range, not the list's: with a bound mesh a payload is perm[o], a position inside the mesh's slotted range,
+    // which reaches mesh.uploaded - 1 even when fewer centres have reached this sorter (gs_mesh_payload_map allows
+    // sorter.uploaded <= mesh.uploaded).  Sized from last_splat alone, the payload's top bits OR-ed into the key.
+    uint32_t max_payload, val_bits;
+    SortSwitches sw;
+    // sort_stage_inputs
+    const uint32_t* idx_dev;           // the index list on the device (nullptr: identity)
+    bool fused_tree;                   // the gathered list is still to be copied, and this sort does it itself
+    // launch_front_end
+    bool vec4;                         // identity list + static integer mode
+    bool key_hist_fused;               // k_depth_key_hist left pass 0's histogram
+    bool vis_front;                    // the visibility cull's front end wrote keys and payloads of the survivors itself
+};
+
+// 1. argument checks and count clamps; what the flags and the bound mesh make of the call
+static int sort_check(gs_sorter* s, uint32_t sort_count, uint32_t render_count, SortPlan& pl) {
+    pl.pre_device = pl.precomputed == GS_PRECOMPUTED_DEVICE;
+    if (pl.pre_device) {
         GS_REQUIRE(s->dev_distances, "GS_PRECOMPUTED_DEVICE: no gs_mesh_compute_distances has handed distances to this sorter");
         GS_REQUIRE(s->dev_distances_count >= s->uploaded, "GS_PRECOMPUTED_DEVICE: fewer distances than the sorter's uploaded splats");
         GS_REQUIRE(s->dev_distances_integer == ((s->flags & GS_SORT_INTEGER) != 0),
@@ -1384,34 +1309,60 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
     if (render_count > s->uploaded) render_count = s->uploaded;
     if (sort_count > s->uploaded) sort_count = s->uploaded;
     GS_REQUIRE(sort_count <= render_count, "splatSortCount > splatRenderCount");
-    const bool dynamic = (s->flags & GS_SORT_DYNAMIC) != 0;
-    GS_REQUIRE(!dynamic || transforms, "dynamic sorter needs transforms");
-    const bool vis_cull = s->visibility_cull && !list_count_dev;   // (sorts the identity list: not combinable with a gathered one)
-    const bool cull = s->frustum_cull && !vis_cull;        // the frustum cull's keep-mask path; the visibility cull compacts instead
-    // list_count_dev: the list's real length lives on the device (asynchronous gs_tree_gather); render_count bounds it
-    GS_REQUIRE(!list_count_dev || (device_list && sort_count == render_count && !dynamic && !precomputed),
+    pl.dynamic = (s->flags & GS_SORT_DYNAMIC) != 0;
+    GS_REQUIRE(!pl.dynamic || pl.transforms, "dynamic sorter needs transforms");
+    pl.vis_cull = s->visibility_cull && !pl.list_count_dev;   // (sorts the identity list: not combinable with a gathered one)
+    pl.cull = s->frustum_cull && !pl.vis_cull;
+    GS_REQUIRE(!pl.list_count_dev || (pl.device_list && sort_count == render_count && !pl.dynamic && !pl.precomputed),
                "a gathered list whose length lives on the device needs a full sort of a static scene without precomputed distances");
-    GS_REQUIRE(!(cull || vis_cull) || (sort_count == render_count && !dynamic && !precomputed),
+    GS_REQUIRE(!(pl.cull || pl.vis_cull) || (sort_count == render_count && !pl.dynamic && !pl.precomputed),
                "a per-splat cull needs a full sort (splatSortCount == splatRenderCount) of a static scene without precomputed distances");
-    gs_context* ctx = s->ctx;
-    ScopedDevice sd(ctx->device);
-    hipStream_t st = s->stream;
-    const uint32_t R = render_count, Rs = sort_count, sort_start = R - Rs;
-    const RadixExec ex = {st, &s->radix, ctx->lds_atomic_lane_order};
-    // a bound mesh stores its splats in its own (Morton) order: hand it positions in that order
-    if (s->bound_mesh) {                           // the mesh may have been destroyed since the bind
-        bool alive = false;
-        for (gs_mesh* m : ctx->live_meshes) alive = alive || (m == s->bound_mesh);
-        if (!alive) s->bound_mesh = nullptr;
-    }
-    const uint32_t* map = s->bound_mesh ? gs_mesh_payload_map(s->bound_mesh, s->uploaded) : nullptr;
-    if (vis_cull) {
+    pl.R = render_count;
+    pl.Rs = sort_count;
+    pl.sort_start = render_count - sort_count;
+    if (!sorter_mesh_alive(s->ctx, s->bound_mesh)) s->bound_mesh = nullptr;   // the mesh may have been destroyed since the bind
+    pl.map = s->bound_mesh ? gs_mesh_payload_map(s->bound_mesh, s->uploaded) : nullptr;
+    if (pl.vis_cull) {
         GS_REQUIRE(s->bound_mesh && s->bound_mesh->projection_pending && s->bound_mesh->uploaded >= s->uploaded,
                    "the visibility cull needs gs_sorter_bind_mesh and a gs_mesh_project of this frame's camera before the sort");
-        GS_REQUIRE(!indexes_to_sort && !device_list, "the visibility cull sorts the identity list (pass indexes_to_sort = NULL)");
-        if (s->bound_mesh->ev_p1 && ctx->aux != st) GS_HIP(hipStreamWaitEvent(st, s->bound_mesh->ev_p1, 0));   // the mask it reads
+        GS_REQUIRE(!pl.indexes_to_sort && !pl.device_list, "the visibility cull sorts the identity list (pass indexes_to_sort = NULL)");
     }
-    const uint32_t* unmap = map ? gs_mesh_payload_unmap(s->bound_mesh) : nullptr;
+    pl.unmap = pl.map ? gs_mesh_payload_unmap(s->bound_mesh) : nullptr;
+    pl.last_splat = s->uploaded ? s->uploaded - 1u : 0u;
+    pl.max_payload = pl.last_splat;
+    if (pl.map && s->bound_mesh->uploaded && s->bound_mesh->uploaded - 1u > pl.max_payload) pl.max_payload = s->bound_mesh->uploaded - 1u;
+    pl.val_bits = 1;
+    while (pl.val_bits < 32u && (pl.max_payload >> pl.val_bits)) pl.val_bits++;
+    pl.sw = sort_switches();
+    return GS_OK;
+}
+
+// The per-scene key rows of a dynamic sort: computeMatMul4x4ThirdRow (sorter.cpp:11-15), fp32, left-to-right, no contraction;
+// then x1000 in double
+static int store_scene_rows(gs_sorter* s, const float* mvp, const float* transforms) {
+    SceneRows rows;
+    for (uint32_t sc = 0; sc < GS_MAX_SCENES; sc++) {
+        const float* b = transforms + 16 * sc;
+        for (int c = 0; c < 4; c++) {
+            volatile float acc = mvp[2] * b[4 * c + 0];
+            acc = acc + mvp[6] * b[4 * c + 1];
+            acc = acc + mvp[10] * b[4 * c + 2];
+            acc = acc + mvp[14] * b[4 * c + 3];
+            rows.fm[sc][c] = acc;
+            rows.im[sc][c] = trunc_f64_i32((double)rows.fm[sc][c] * 1000.0);
+        }
+    }
+    k_store_scene_rows<<<1, 256, 0, s->stream>>>(rows, s->scene_rows.as<SceneRows>());
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// 2. stream ordering and input staging: what the sort waits for, the index list, the distances, the scene rows, KeyParams
+static int sort_stage_inputs(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
+    gs_context* ctx = s->ctx;
+    hipStream_t st = s->stream;
+    const float* mvp = pl.mvp;
+    if (pl.vis_cull && s->bound_mesh->ev_p1 && ctx->aux != st) GS_HIP(hipStreamWaitEvent(st, s->bound_mesh->ev_p1, 0));   // the mask it reads
     if (ctx->fork_join && st != ctx->stream) {
         // serial frames on a multi-stream context: this sort starts when everything the context's stream holds now (the previous
         // frame's draw) has finished, then runs beside this frame's vertex stage
@@ -1423,15 +1374,12 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
         s->consumer_pending = false;
     }
 
-    const uint32_t* idx_dev = nullptr;
-    bool fused_tree = false;                               // the gathered list is still to be copied, and this sort does it itself
-    bool vis_front = false;                                // the visibility cull's front end wrote keys and payloads of the survivors itself
-    if (device_list) {
-        idx_dev = s->idx_in.as<uint32_t>();                // written by gs_tree_gather on this stream ...
+    if (pl.device_list) {
+        pl.idx_dev = s->idx_in.as<uint32_t>();             // written by gs_tree_gather on this stream ...
         if (s->pending_tree) {                             // ... or only planned by it (tree.hip): the copy is ours
-            static const bool no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
-            fused_tree = !no_fuse && Rs == R && Rs > 0 && !dynamic && !precomputed && !vis_cull && (!cull || s->pending_keep_zeroed);
-            if (!fused_tree) {
+            pl.fused_tree = !pl.sw.tree_no_fuse && pl.Rs == pl.R && pl.Rs > 0 && !pl.dynamic && !pl.precomputed && !pl.vis_cull &&
+                            (!pl.cull || s->pending_keep_zeroed);
+            if (!pl.fused_tree) {
                 GS_TRY(gs_tree_copy_plain(s->pending_tree, s->idx_in.as<uint32_t>(), st));
                 gs_tree_forget_sorter(s->pending_tree, s);
             }
@@ -1440,305 +1388,300 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
         // A sort that does not consume the gathered list may destroy what a gather left for a later gs_sorter_sort_gathered
         // (ADVICE r04): a planned gather's fused copy ORs its keep bits into a mask the GATHER zeroed - a frustum-culled sort in
         // between rewrites that mask, so the copy falls back to the plain one + the ordinary key kernel; a list that was already
-        // copied into idx_in is gone once a host list or a compaction overwrites it (the compaction: below, where the front end
-        // of a visibility-culled sort is chosen - ADVICE r05: the streaming one writes pay_in and leaves idx_in alone).
+        // copied into idx_in is gone once a host list or a compaction overwrites it (the compaction: launch_vis_cull_front, where
+        // the front end of a visibility-culled sort is chosen - ADVICE r05: the streaming one writes pay_in and leaves idx_in alone).
         if (s->pending_tree) {
-            if (cull) s->pending_keep_zeroed = false;
-        } else if (indexes_to_sort) {
+            if (pl.cull) s->pending_keep_zeroed = false;
+        } else if (pl.indexes_to_sort) {
             s->has_gathered = false;
         }
+        if (pl.indexes_to_sort) {
+            GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
+            if (pl.R) GS_HIP(hipMemcpyAsync(s->idx_in.p, pl.indexes_to_sort, (size_t)pl.R * 4, hipMemcpyHostToDevice, st));
+            pl.idx_dev = s->idx_in.as<uint32_t>();
+        }
     }
-    if (!device_list && indexes_to_sort) {
-        GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
-        if (R) GS_HIP(hipMemcpyAsync(s->idx_in.p, indexes_to_sort, (size_t)R * 4, hipMemcpyHostToDevice, st));
-        idx_dev = s->idx_in.as<uint32_t>();
-    }
-    KeyParams kp = {};
-    kp.mode = ((s->flags & GS_SORT_INTEGER) ? MODE_INT : 0) | (dynamic ? MODE_DYNAMIC : 0) | (precomputed ? MODE_PRECOMPUTED : 0);
-    if (precomputed) {
+    kp.mode = ((s->flags & GS_SORT_INTEGER) ? MODE_INT : 0) | (pl.dynamic ? MODE_DYNAMIC : 0) | (pl.precomputed ? MODE_PRECOMPUTED : 0);
+    if (pl.precomputed) {
         GS_TRY(s->precomputed.ensure((size_t)s->max_count * 4));
-        if (!pre_device) {                     // (the device hand-over: gs_mesh_compute_distances wrote the buffer in place)
-            GS_HIP(hipMemcpyAsync(s->precomputed.p, precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
+        if (!pl.pre_device) {                  // (the device hand-over: gs_mesh_compute_distances wrote the buffer in place)
+            GS_HIP(hipMemcpyAsync(s->precomputed.p, pl.precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
             s->dev_distances = false;
         }
         kp.precomputed = s->precomputed.as<uint32_t>();
     }
-    if (dynamic && !precomputed) {
-        // computeMatMul4x4ThirdRow (sorter.cpp:11-15), fp32, left-to-right, no contraction; then x1000 in double
-        SceneRows rows;
-        for (uint32_t sc = 0; sc < GS_MAX_SCENES; sc++) {
-            const float* b = transforms + 16 * sc;
-            for (int c = 0; c < 4; c++) {
-                volatile float acc = mvp[2] * b[4 * c + 0];
-                acc = acc + mvp[6] * b[4 * c + 1];
-                acc = acc + mvp[10] * b[4 * c + 2];
-                acc = acc + mvp[14] * b[4 * c + 3];
-                rows.fm[sc][c] = acc;
-                rows.im[sc][c] = trunc_f64_i32((double)rows.fm[sc][c] * 1000.0);
-            }
-        }
-        k_store_scene_rows<<<1, 256, 0, st>>>(rows, s->scene_rows.as<SceneRows>());
-        GS_HIP(hipGetLastError());
+    if (pl.dynamic && !pl.precomputed) {
+        GS_TRY(store_scene_rows(s, mvp, pl.transforms));
         kp.rows = s->scene_rows.as<SceneRows>();
     }
     kp.cx = s->cx.as<uint32_t>(); kp.cy = s->cy.as<uint32_t>(); kp.cz = s->cz.as<uint32_t>();
     kp.cw = s->cw.as<uint32_t>(); kp.scene_idx = s->scene_idx.as<uint32_t>();
     kp.aos = s->caos.as<uint4>();
-    kp.idx_in = idx_dev;
+    kp.idx_in = pl.idx_dev;
     kp.keys_out = s->keys.as<int32_t>();
-    if (Rs > 0) s->frame_index ^= 1u;          // this sort's frame was reset by the previous sort's k_depth_key (or at create)
+    if (pl.Rs > 0) s->frame_index ^= 1u;       // this sort's frame was reset by the previous sort's first kernel (or at create)
     kp.frame = s->frame.as<SortFrame>() + s->frame_index;
     kp.next_frame = s->frame.as<SortFrame>() + (s->frame_index ^ 1u);
     kp.digit_total = s->radix.digit_total.as<uint32_t>();
-    kp.sort_start = sort_start;
-    kp.render_count = R;
-    kp.last_splat = s->uploaded ? s->uploaded - 1u : 0u;
+    kp.sort_start = pl.sort_start;
+    kp.render_count = pl.R;
+    kp.last_splat = pl.last_splat;
     kp.im0 = trunc_f64_i32((double)mvp[2] * 1000.0);     // sorter.cpp:64
     kp.im1 = trunc_f64_i32((double)mvp[6] * 1000.0);
     kp.im2 = trunc_f64_i32((double)mvp[10] * 1000.0);
     kp.fm0 = mvp[2]; kp.fm1 = mvp[6]; kp.fm2 = mvp[10];
-
-    if (cull) {
+    if (pl.cull) {
         GS_TRY(s->keep_mask.ensure((((size_t)s->max_count + 63) / 64 + 8) * 8));   // the key kernel writes whole 256-position windows
         kp.keep = s->keep_mask.as<unsigned long long>();
         memcpy(kp.mvp, mvp, sizeof(kp.mvp));
     }
-    if (list_count_dev) kp.count_dev = list_count_dev;
+    kp.count_dev = pl.list_count_dev;
+    return GS_OK;
+}
 
-    s->timed_sort = stats != nullptr || ctx->stage_events;
-    if (s->timed_sort) GS_HIP(hipEventRecord(s->ev0, st));
-    uint32_t passes = 0;
-    if (Rs > 0) {
-        const bool vec4 = (kp.mode == MODE_INT) && !idx_dev;
-        // $GSPLAT_KEY_HIST_FUSED=1: keys + pass 0's histogram in one launch behind a barrier across the grid (k_depth_key_hist) - only for
-        // the plain full sort of the identity list whose pass 0 is the packed, chunk-staged one, and only when the whole grid is
-        // resident at once (<= 2 workgroups of 1024 threads per CU)
-        uint32_t kh_grid = 0;
-        bool key_hist_fused = false;
-        if (getenv("GSPLAT_KEY_HIST_FUSED") && vec4 && !fused_tree && !vis_cull && !cull && sort_start == 0u && Rs == R && (R & 3u) == 0u &&
-            !list_count_dev && !getenv("GSPLAT_NO_SORT_PACK") && !getenv("GSPLAT_NO_SORT_CHUNK") && s->precision > 8u) {
-            uint32_t mp = kp.last_splat;
-            if (map && s->bound_mesh->uploaded && s->bound_mesh->uploaded - 1u > mp) mp = s->bound_mesh->uploaded - 1u;
-            uint32_t vb = 1;
-            while (vb < 32u && (mp >> vb)) vb++;
-            kh_grid = radix_chunk_grid_for(Rs);
-            key_hist_fused = vb <= 24u && (s->precision - 8u) + vb <= 32u && kh_grid != 0u && kh_grid <= 2u * (uint32_t)ctx->cu_count;
-            if (key_hist_fused) {
-                if (!s->key_sync.p) {
-                    GS_TRY(s->key_sync.alloc(64));
-                    GS_HIP(hipMemsetAsync(s->key_sync.p, 0, 64, st));
-                    s->key_sync_base = 0u;
-                }
-            }
-        }
-        if (fused_tree) {
-            // copy + keys (+ keep bits) of the planned gather in one kernel over leaf-major copies of the centres and payloads
-            TreeCopyParams cp;
-            gs_tree_view(s->pending_tree, &cp.v);
-            const void* mesh_key = map ? (const void*)s->bound_mesh : nullptr;
-            const uint32_t layout = map ? s->bound_mesh->layout_version : 0u;
-            GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
-            if (s->leaf_cache_tree != cp.v.tree_uid || s->leaf_cache_centers != s->centers_version || s->leaf_cache_mesh != mesh_key ||
-                s->leaf_cache_layout != layout || s->leaf_cache_uploaded != s->uploaded || !s->leaf_centers.p) {
-                GS_TRY(s->leaf_centers.ensure((size_t)cp.v.tree_splats * 16 + 16));
-                GS_TRY(s->leaf_pos.ensure((size_t)cp.v.tree_splats * 4 + 16));
-                if (cp.v.tree_splats)
-                    hipLaunchKernelGGL(k_tree_leaf_cache, dim3(grid_for(cp.v.tree_splats, 1024, 4096)), dim3(256), 0, st, cp.v.leaf_indexes,
-                                       cp.v.tree_splats, s->caos.as<uint4>(), map, kp.last_splat, s->leaf_centers.as<uint4>(),
-                                       s->leaf_pos.as<uint32_t>());
-                s->leaf_cache_tree = cp.v.tree_uid; s->leaf_cache_centers = s->centers_version; s->leaf_cache_mesh = mesh_key;
-                s->leaf_cache_layout = layout; s->leaf_cache_uploaded = s->uploaded;
-            }
-            cp.leaf_centers = s->leaf_centers.as<uint4>();
-            cp.leaf_pos = s->leaf_pos.as<uint32_t>();
-            cp.idx_out = s->idx_in.as<uint32_t>();
-            cp.pay_out = s->pay_in.as<uint32_t>();
-            // (a workgroup ends with one atomic on the sort's kept counter, and same-address atomics retire at ~12 ns each:
-            // 6.5 k workgroups queue ~80 us of them behind 30 us of memory traffic - eight workgroups per CU walk the leaves)
-            uint32_t cgrid = (cp.v.leaves + 3u) / 4u;
-            cgrid = cgrid < 1u ? 1u : (cgrid > (uint32_t)ctx->cu_count * 8u ? (uint32_t)ctx->cu_count * 8u : cgrid);
-            if (cull) hipLaunchKernelGGL(k_tree_copy_keys<true>, dim3(cgrid), dim3(256), 0, st, cp, kp);
-            else hipLaunchKernelGGL(k_tree_copy_keys<false>, dim3(cgrid), dim3(256), 0, st, cp, kp);
-            gs_tree_forget_sorter(s->pending_tree, s);
-        } else if (vis_cull) {
-            // compact, then sort the survivors (see k_minmax_count): the list is what the bound mesh's vertex stage kept
-            const uint32_t spans = (R + VC_SPAN - 1u) / VC_SPAN;
-            const uint32_t grid = spans < (uint32_t)ctx->cu_count * 2u ? spans : (uint32_t)ctx->cu_count * 2u;
-            const uint32_t chunk_len = ((spans + grid - 1u) / grid) * VC_SPAN;
-            GS_TRY(s->chunk_counts.ensure((size_t)grid * 4));
-            GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
-            GS_TRY(s->mask_copy.ensure(((size_t)s->max_count + 31) / 32 * 4 + 64));
-            uint32_t* mask = s->bound_mesh->vis_orig.as<uint32_t>();
-            // The projection left the by-original-index mask to us (gs_mesh_project of a full frame for a mesh whose bound sorter
-            // culls by visibility): k_mask_derive_count builds it from the storage-order mask through the payload map.
-            const bool lazy = s->bound_mesh->vis_orig_lazy;
-            GS_REQUIRE(!lazy || map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
-            const uint32_t mblocks = (s->bound_mesh->uploaded + 255u) >> 8;
-            constexpr uint32_t DERIVE_SUBS = 4;
-            auto derive = [&](uint32_t dgrid, uint32_t dlen) {
-                hipLaunchKernelGGL(k_mask_derive_count, dim3(dgrid * DERIVE_SUBS), dim3(VC_THREADS), 0, st, kp, map,
-                                   s->bound_mesh->vis_mask.as<unsigned long long>(), s->bound_mesh->block_any.as<uint8_t>(), mblocks, dlen,
-                                   DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), s->chunk_counts.as<uint32_t>());
-            };
-            // Two front ends, chosen by what the vertex stage drew.  A full frame keeps a large part of the scene (C3: a quarter):
-            // the streaming front end keys the survivors on the way (N = 1 frame 0.285 -> 0.270 ms, r05k).  A rank's strip keeps
-            // a few per cent: round 4's chain - a 12-byte-per-splat min / max pass, a compaction of the mask, and centre gathers
-            // for the few survivors - is the cheaper one there (C3 rank 4 of 8: 0.116 vs 0.126 ms, same box), because the streaming
-            // kernel also reads the payload table (+4 bytes per splat) and runs at 2.8 TB/s where the pure reduction reaches 4.
-            // $GSPLAT_VIS_FRONT = stream | compact forces one (A/B and tests).
-            static const char* force = getenv("GSPLAT_VIS_FRONT");
-            // (projected_cam is the camera of the gs_mesh_project this sort consumes: the entry checks refused the call unless
-            // the bound mesh's projection_pending is set)
-            const gs_camera& pc = s->bound_mesh->projected_cam;
-            const uint32_t rows_total = (pc.height + GS_TILE - 1u) / GS_TILE;
-            const bool strip = !(pc.tile_row_begin == 0u && (pc.tile_row_end == 0u || pc.tile_row_end >= rows_total));
-            vis_front = force ? force[0] == 's' : !strip;
-            if (vis_front) {
-                // one contiguous run of positions per workgroup, walked in turns of 4096 (two workgroups per CU)
-                // (a chunk is a whole number of turns; with the mask derived here, of DERIVE_SUBS x turns: one piece per sub-workgroup)
-                const uint32_t tlen = lazy ? VC_TURN * DERIVE_SUBS : VC_TURN;
-                const uint32_t turns = (R + tlen - 1u) / tlen;
-                const uint32_t wgrid = turns < (uint32_t)ctx->cu_count * 2u ? turns : (uint32_t)ctx->cu_count * 2u;
-                const uint32_t wlen = ((turns + wgrid - 1u) / wgrid) * tlen;
-                GS_TRY(s->chunk_counts.ensure((size_t)wgrid * DERIVE_SUBS * 4));
-                GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
-                if (lazy) derive(wgrid, wlen);
-                else hipLaunchKernelGGL(k_mask_count, dim3(wgrid), dim3(VC_THREADS), 0, st, kp, mask, wlen, s->chunk_counts.as<uint32_t>());
-                if (map) hipLaunchKernelGGL(k_cull_front<true>, dim3(wgrid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                            s->chunk_counts.as<uint32_t>(), wlen, map, s->pay_in.as<uint32_t>(), lazy ? DERIVE_SUBS : 1u);
-                else hipLaunchKernelGGL(k_cull_front<false>, dim3(wgrid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                        s->chunk_counts.as<uint32_t>(), wlen, map, s->pay_in.as<uint32_t>(), 1u);
-            } else {
-                if (!s->pending_tree) s->has_gathered = false;     // k_mask_compact overwrites a gathered list that was already copied into idx_in
-                if (lazy) {                                        // (a forced compact front end: the mask first, its counts are redone below)
-                    const uint32_t tlen = VC_TURN * DERIVE_SUBS, turns = (R + tlen - 1u) / tlen;
-                    const uint32_t dgrid = turns < (uint32_t)ctx->cu_count * 2u ? turns : (uint32_t)ctx->cu_count * 2u;
-                    GS_TRY(s->chunk_counts.ensure((size_t)std::max(dgrid * DERIVE_SUBS, grid) * 4));
-                    derive(dgrid, ((turns + dgrid - 1u) / dgrid) * tlen);
-                }
-                hipLaunchKernelGGL(k_minmax_count, dim3(grid), dim3(VC_THREADS), 0, st, kp, mask, chunk_len, s->chunk_counts.as<uint32_t>());
-                hipLaunchKernelGGL(k_mask_compact, dim3(grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(),
-                                   s->chunk_counts.as<uint32_t>(), R, chunk_len, s->idx_in.as<uint32_t>(), kp.frame);
-            }
-            // the mask is all zero again if this sort covered every splat the vertex stage looked at - and, where it derived the
-            // mask itself, if the words beyond the ones it wrote were zero already (gs_mesh_project)
-            if (R >= s->bound_mesh->vis_orig_count && (!lazy || s->bound_mesh->vis_orig_tail_zero)) s->bound_mesh->vis_orig_dirty = false;
-            idx_dev = s->idx_in.as<uint32_t>();
-            kp.idx_in = idx_dev;
-            kp.count_dev = &kp.frame->kept;
-            kp.ext_minmax = 1u;
-            if (!vis_front) hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(Rs, 256 * 4, (uint32_t)ctx->cu_count * 2)), dim3(256), 0, st, kp);
-        } else if (cull && vec4)
-            hipLaunchKernelGGL(k_depth_key_cull<true>, dim3(grid_for(Rs, 256 * 16, (uint32_t)ctx->cu_count * 2)), dim3(256), 0, st, kp);
-        else if (cull)
-            hipLaunchKernelGGL(k_depth_key_cull<false>, dim3(grid_for(Rs, 256 * 4, (uint32_t)ctx->cu_count * 4)), dim3(256), 0, st, kp);
-        else if (vec4 && key_hist_fused) {
-            DepthLoader hl = {};
-            hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = R; hl.range = 1u << s->precision;
-            hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
-            KeyHistSync sync = {s->key_sync.as<uint32_t>(), s->key_sync.as<uint32_t>() + 1, s->key_sync_base};
-            s->key_sync_base += kh_grid;
-            s->key_sync_used = true;
-            hipLaunchKernelGGL(k_depth_key_hist, dim3(kh_grid), dim3(HIST_THREADS), 0, st, kp, hl, 0, s->radix.block_hist.as<uint32_t>(),
-                               s->radix.digit_total.as<uint32_t>(), sync);
-        } else if (vec4)
-            hipLaunchKernelGGL(k_depth_key<true>, dim3(grid_for(Rs, 256 * 16, (uint32_t)ctx->cu_count * GS_KEY_GRID_MULT)), dim3(256), 0, st, kp);
-        else
-            hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(Rs, 256 * 4, (uint32_t)ctx->cu_count * 2)), dim3(256), 0, st, kp);
-        GS_HIP(hipGetLastError());
-        DepthLoader dl = {};
-        dl.keys = s->keys.as<int32_t>();
-        dl.idx = (fused_tree || vis_front) ? s->pay_in.as<uint32_t>() : idx_dev;     // (the fused copy / the cull's front end wrote the payloads themselves)
-        dl.map = (fused_tree || vis_front) ? nullptr : map;
-        dl.frame = kp.frame;
-        dl.sort_start = sort_start;
-        dl.render_count = R;
-        dl.range = 1u << s->precision;
-        // The payload's range, not the list's: with a bound mesh a payload is perm[o], a position inside the mesh's slotted range,
-        // which reaches mesh.uploaded - 1 even when fewer centres have reached this sorter (gs_mesh_payload_map allows
-        // sorter.uploaded <= mesh.uploaded).  Sized from last_splat alone, the payload's top bits OR-ed into the key.
-        uint32_t max_payload = kp.last_splat;
-        if (map && s->bound_mesh->uploaded && s->bound_mesh->uploaded - 1u > max_payload) max_payload = s->bound_mesh->uploaded - 1u;
-        // (the loader clamps what it reads from `idx`: splat indexes normally, ready-made payloads after a fused copy / front end)
-        dl.last_splat = (fused_tree || vis_front) ? max_payload : kp.last_splat;
-        dl.n_dev = vis_cull ? &kp.frame->kept : list_count_dev;
-        passes = (s->precision + 7) / 8;
-        uint32_t* out_tail = s->sorted.as<uint32_t>() + sort_start;
-        void* kbuf[2] = {s->keyA.p, s->keyB.p};
-        uint32_t* vbuf[2] = {s->valA.as<uint32_t>(), s->valB.as<uint32_t>()};
-        // What travels between the passes: after pass p the key still holds precision - 8 (p + 1) bits.  When those fit above the
-        // payload in one 32-bit word (payloads are splat positions < uploaded: 23 bits at 5.8 M splats, 24 at 16 M, so the default
-        // 16-bit buckets always do below 2^24 splats) the pass writes that word instead of a key array and a value array
-        // (radix.hpp PACK_OUT); otherwise 16- or 32-bit keys + values as before, and a later pass packs as soon as it can.
-        uint32_t val_bits = 1;
-        while (val_bits < 32u && (max_payload >> val_bits)) val_bits++;
-        static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;       // A/B and tests: the unpacked path
-        static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;     // ... the tile-at-a-time scatter for packed passes
-        // packed passes stage a whole chunk in LDS (radix.hpp) when the list is short enough for <= CHUNK_TILES tiles per
-        // workgroup and the payload leaves 8 bits for the digit beside it in the last pass's staging word
-        const bool chunked = !no_chunk && val_bits <= 24u && radix_chunk_grid_for(Rs) != 0u;
-        const bool wide = s->precision > 16;
-        bool in_packed = false;                                                       // the previous pass packed
-        for (uint32_t p = 0; p < passes; p++) {
-            const bool last = (p + 1 == passes);
-            const int left = (int)s->precision - 8 * (int)(p + 1);                    // key bits after this pass
-            const bool pack = !last && !no_pack && (uint32_t)left + val_bits <= 32u;
-            const int shift = in_packed ? 0 : 8 * (int)p;
-            uint32_t* vo = last ? out_tail : vbuf[p & 1];
-            // after a culling pass 0 the element count is the device-resident kept count
-            const uint32_t* n_dev = (cull || vis_cull || list_count_dev) ? &kp.frame->kept : nullptr;
-            if (p == 0) {
-                Pass0Args a = {};
-                a.base = dl; a.keep = cull ? kp.keep : nullptr; a.Rs = Rs; a.val_bits = val_bits; a.shift = shift;
-                a.pack = pack; a.chunked = chunked; a.wide = wide; a.kbuf0 = kbuf[0]; a.vo = vo;
-                a.kept_out = cull ? &kp.frame->kept : nullptr;         // a culling pass 0 compacts: it publishes the result's length
-                a.skip_hist = key_hist_fused;
-                const bool has_idx = dl.idx != nullptr;
-                if (cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
-                else if (cull) GS_TRY((depth_pass0<true, false>(ex, a)));
-                else if (has_idx) GS_TRY((depth_pass0<false, true>(ex, a)));
-                else GS_TRY((depth_pass0<false, false>(ex, a)));
-            } else if (in_packed) {
-                PackedLoader pl = {vbuf[(p - 1) & 1], n_dev, Rs, val_bits};
-                ArrayLoader<uint32_t> ph = {vbuf[(p - 1) & 1], nullptr, n_dev, Rs};
-                if (chunked && last) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, false>(ex, ph, (int)val_bits, pl, Rs, 0, (int)p, vo, 0u)));
-                else if (chunked) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, true>(ex, ph, (int)val_bits, pl, Rs, 0, (int)p, vo, val_bits)));
-                else if (last) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, false>(ex, ph, (int)val_bits, pl, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, 0u)));
-                else GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, true>(ex, ph, (int)val_bits, pl, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
-            } else if (wide) {
-                ArrayLoader<uint32_t> al = {(const uint32_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
-                if (last) GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, false>(ex, al, al, Rs, shift, (int)p, (uint32_t*)nullptr, vo)));
-                else if (pack) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, ArrayLoader<uint32_t>, uint8_t, false, false, true>(ex, al, shift, al, Rs, shift, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
-                else GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, true>(ex, al, al, Rs, shift, (int)p, (uint32_t*)kbuf[p & 1], vo)));
-            } else {
-                ArrayLoader<uint16_t> al = {(const uint16_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
-                if (last) GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, false>(ex, al, al, Rs, shift, (int)p, (uint16_t*)nullptr, vo)));
-                else GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, true>(ex, al, al, Rs, shift, (int)p, (uint16_t*)kbuf[p & 1], vo)));
-            }
-            in_packed = in_packed || pack;
-        }
+// 3a. copy + keys (+ keep bits) of a planned gather in one kernel over leaf-major copies of the centres and payloads
+static int launch_tree_front(gs_sorter* s, const SortPlan& pl, const KeyParams& kp) {
+    gs_context* ctx = s->ctx;
+    hipStream_t st = s->stream;
+    TreeCopyParams cp;
+    gs_tree_view(s->pending_tree, &cp.v);
+    const void* mesh_key = pl.map ? (const void*)s->bound_mesh : nullptr;
+    const uint32_t layout = pl.map ? s->bound_mesh->layout_version : 0u;
+    GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
+    if (s->leaf_cache_tree != cp.v.tree_uid || s->leaf_cache_centers != s->centers_version || s->leaf_cache_mesh != mesh_key ||
+        s->leaf_cache_layout != layout || s->leaf_cache_uploaded != s->uploaded || !s->leaf_centers.p) {
+        GS_TRY(s->leaf_centers.ensure((size_t)cp.v.tree_splats * 16 + 16));
+        GS_TRY(s->leaf_pos.ensure((size_t)cp.v.tree_splats * 4 + 16));
+        if (cp.v.tree_splats)
+            hipLaunchKernelGGL(k_tree_leaf_cache, dim3(grid_for(cp.v.tree_splats, 1024, 4096)), dim3(256), 0, st, cp.v.leaf_indexes,
+                               cp.v.tree_splats, s->caos.as<uint4>(), pl.map, kp.last_splat, s->leaf_centers.as<uint4>(),
+                               s->leaf_pos.as<uint32_t>());
+        s->leaf_cache_tree = cp.v.tree_uid; s->leaf_cache_centers = s->centers_version; s->leaf_cache_mesh = mesh_key;
+        s->leaf_cache_layout = layout; s->leaf_cache_uploaded = s->uploaded;
     }
-    if (sort_start > 0) {
-        hipLaunchKernelGGL(k_copy_head, dim3(grid_for(sort_start, 1024, 2048)), dim3(256), 0, st, idx_dev, map,
-                           s->sorted.as<uint32_t>(), sort_start, s->uploaded - 1u);
+    cp.leaf_centers = s->leaf_centers.as<uint4>();
+    cp.leaf_pos = s->leaf_pos.as<uint32_t>();
+    cp.idx_out = s->idx_in.as<uint32_t>();
+    cp.pay_out = s->pay_in.as<uint32_t>();
+    // (a workgroup ends with one atomic on the sort's kept counter, and same-address atomics retire at ~12 ns each:
+    // 6.5 k workgroups queue ~80 us of them behind 30 us of memory traffic - eight workgroups per CU walk the leaves)
+    const uint32_t cgrid = grid_for(cp.v.leaves, 4, (uint32_t)ctx->cu_count * 8u);
+    if (pl.cull) hipLaunchKernelGGL(k_tree_copy_keys<true>, dim3(cgrid), dim3(256), 0, st, cp, kp);
+    else hipLaunchKernelGGL(k_tree_copy_keys<false>, dim3(cgrid), dim3(256), 0, st, cp, kp);
+    gs_tree_forget_sorter(s->pending_tree, s);
+    return GS_OK;
+}
+
+// 3b. the visibility cull: compact, then sort the survivors (see k_minmax_count) - the list is what the bound mesh's vertex
+// stage kept.  Leaves the list's length on the device (kp.count_dev) and min / max in the frame (kp.ext_minmax).
+static int launch_vis_cull_front(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
+    gs_context* ctx = s->ctx;
+    hipStream_t st = s->stream;
+    gs_mesh* mesh = s->bound_mesh;
+    const uint32_t R = pl.R;
+    GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
+    GS_TRY(s->mask_copy.ensure(((size_t)s->max_count + 31) / 32 * 4 + 64));
+    uint32_t* mask = mesh->vis_orig.as<uint32_t>();
+    uint32_t* counts = nullptr;                            // (set once chunk_counts has its size)
+    // The projection left the by-original-index mask to us (gs_mesh_project of a full frame for a mesh whose bound sorter
+    // culls by visibility): k_mask_derive_count builds it from the storage-order mask through the payload map.
+    const bool lazy = mesh->vis_orig_lazy;
+    GS_REQUIRE(!lazy || pl.map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
+    constexpr uint32_t DERIVE_SUBS = 4;
+    // (a chunk of the derived mask is a whole number of DERIVE_SUBS x turns: one piece per sub-workgroup)
+    const ChunkGrid dg = chunk_grid(ctx, R, VC_TURN * DERIVE_SUBS);
+    auto derive = [&]() {
+        hipLaunchKernelGGL(k_mask_derive_count, dim3(dg.grid * DERIVE_SUBS), dim3(VC_THREADS), 0, st, kp, pl.map,
+                           mesh->vis_mask.as<unsigned long long>(), mesh->block_any.as<uint8_t>(), (mesh->uploaded + 255u) >> 8, dg.len,
+                           DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), counts);
+    };
+    // Two front ends, chosen by what the vertex stage drew.  A full frame keeps a large part of the scene (C3: a quarter):
+    // the streaming front end keys the survivors on the way (N = 1 frame 0.285 -> 0.270 ms, r05k).  A rank's strip keeps
+    // a few per cent: round 4's chain - a 12-byte-per-splat min / max pass, a compaction of the mask, and centre gathers
+    // for the few survivors - is the cheaper one there (C3 rank 4 of 8: 0.116 vs 0.126 ms, same box), because the streaming
+    // kernel also reads the payload table (+4 bytes per splat) and runs at 2.8 TB/s where the pure reduction reaches 4.
+    // $GSPLAT_VIS_FRONT = stream | compact forces one (A/B and tests).
+    // (projected_cam is the camera of the gs_mesh_project this sort consumes: the entry checks refused the call unless
+    // the bound mesh's projection_pending is set)
+    const gs_camera& pc = mesh->projected_cam;
+    const uint32_t rows_total = (pc.height + GS_TILE - 1u) / GS_TILE;
+    const bool strip = !(pc.tile_row_begin == 0u && (pc.tile_row_end == 0u || pc.tile_row_end >= rows_total));
+    pl.vis_front = pl.sw.vis_front ? pl.sw.vis_front[0] == 's' : !strip;
+    if (pl.vis_front) {
+        // one contiguous run of positions per workgroup, walked in turns of 4096 (two workgroups per CU)
+        const ChunkGrid wg = lazy ? dg : chunk_grid(ctx, R, VC_TURN);
+        GS_TRY(s->chunk_counts.ensure((size_t)wg.grid * DERIVE_SUBS * 4));
+        GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
+        counts = s->chunk_counts.as<uint32_t>();
+        if (lazy) derive();
+        else hipLaunchKernelGGL(k_mask_count, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, wg.len, counts);
+        if (pl.map) hipLaunchKernelGGL(k_cull_front<true>, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
+                                       counts, wg.len, pl.map, s->pay_in.as<uint32_t>(), lazy ? DERIVE_SUBS : 1u);
+        else hipLaunchKernelGGL(k_cull_front<false>, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
+                                counts, wg.len, pl.map, s->pay_in.as<uint32_t>(), 1u);
+    } else {
+        const ChunkGrid cg = chunk_grid(ctx, R, VC_SPAN);
+        if (!s->pending_tree) s->has_gathered = false;     // k_mask_compact overwrites a gathered list that was already copied into idx_in
+        GS_TRY(s->chunk_counts.ensure((size_t)std::max(lazy ? dg.grid * DERIVE_SUBS : 0u, cg.grid) * 4));
+        counts = s->chunk_counts.as<uint32_t>();
+        if (lazy) derive();                                // (a forced compact front end: the mask first, its counts are redone below)
+        hipLaunchKernelGGL(k_minmax_count, dim3(cg.grid), dim3(VC_THREADS), 0, st, kp, mask, cg.len, counts);
+        hipLaunchKernelGGL(k_mask_compact, dim3(cg.grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(), counts, R, cg.len,
+                           s->idx_in.as<uint32_t>(), kp.frame);
+    }
+    // the mask is all zero again if this sort covered every splat the vertex stage looked at - and, where it derived the
+    // mask itself, if the words beyond the ones it wrote were zero already (gs_mesh_project)
+    if (R >= mesh->vis_orig_count && (!lazy || mesh->vis_orig_tail_zero)) mesh->vis_orig_dirty = false;
+    pl.idx_dev = s->idx_in.as<uint32_t>();
+    kp.idx_in = pl.idx_dev;
+    kp.count_dev = &kp.frame->kept;
+    kp.ext_minmax = 1u;
+    if (!pl.vis_front) hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(pl.Rs, 256 * 4, (uint32_t)ctx->cu_count * 2)), dim3(256), 0, st, kp);
+    return GS_OK;
+}
+
+// $GSPLAT_KEY_HIST_FUSED=1: keys + pass 0's histogram in one launch behind a barrier across the grid (k_depth_key_hist) - only for
+// the plain full sort of the identity list whose pass 0 is the packed, chunk-staged one, and only when the whole grid is
+// resident at once (<= 2 workgroups of 1024 threads per CU).  Returns the grid, 0 = not this sort.
+static uint32_t key_hist_grid(const gs_sorter* s, const SortPlan& pl) {
+    if (!pl.sw.key_hist_fused || !pl.vec4 || pl.fused_tree || pl.vis_cull || pl.cull || pl.sort_start != 0u || (pl.R & 3u) != 0u ||
+        pl.list_count_dev || s->precision <= 8u)
+        return 0u;
+    const uint32_t grid = radix_chunk_grid_for(pl.Rs);
+    return (pl.val_bits <= 24u && (s->precision - 8u) + pl.val_bits <= 32u && grid <= 2u * (uint32_t)s->ctx->cu_count) ? grid : 0u;
+}
+
+// 3. the first kernel(s) of the sort: keys, min / max, the housekeeping (sort_begin) - one branch per kernel family
+static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
+    gs_context* ctx = s->ctx;
+    hipStream_t st = s->stream;
+    const uint32_t cus = (uint32_t)ctx->cu_count;
+    pl.vec4 = (kp.mode == MODE_INT) && !pl.idx_dev;
+    const uint32_t kh_grid = key_hist_grid(s, pl);
+    pl.key_hist_fused = kh_grid != 0u;
+    if (pl.fused_tree) {
+        GS_TRY(launch_tree_front(s, pl, kp));
+    } else if (pl.vis_cull) {
+        GS_TRY(launch_vis_cull_front(s, pl, kp));
+    } else if (pl.cull) {
+        if (pl.vec4) hipLaunchKernelGGL(k_depth_key_cull<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * 2)), dim3(256), 0, st, kp);
+        else hipLaunchKernelGGL(k_depth_key_cull<false>, dim3(grid_for(pl.Rs, 256 * 4, cus * 4)), dim3(256), 0, st, kp);
+    } else if (pl.key_hist_fused) {
+        if (!s->key_sync.p) {
+            GS_TRY(s->key_sync.alloc(64));
+            GS_HIP(hipMemsetAsync(s->key_sync.p, 0, 64, st));
+            s->key_sync_base = 0u;
+        }
+        DepthLoaderArgs hl = {};
+        hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
+        hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
+        KeyHistSync sync = {s->key_sync.as<uint32_t>(), s->key_sync.as<uint32_t>() + 1, s->key_sync_base};
+        s->key_sync_base += kh_grid;
+        s->key_sync_used = true;
+        hipLaunchKernelGGL(k_depth_key_hist, dim3(kh_grid), dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, 0, s->radix.block_hist.as<uint32_t>(),
+                           s->radix.digit_total.as<uint32_t>(), sync);
+    } else if (pl.vec4) {
+        hipLaunchKernelGGL(k_depth_key<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * GS_KEY_GRID_MULT)), dim3(256), 0, st, kp);
+    } else {
+        hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(pl.Rs, 256 * 4, cus * 2)), dim3(256), 0, st, kp);
     }
     GS_HIP(hipGetLastError());
-    if (s->timed_sort || st != ctx->stream) GS_HIP(hipEventRecord(s->ev1, st));   // a draw on another stream waits for it
-    s->last_render = R;
-    s->last_sort = Rs;
+    return GS_OK;
+}
+
+// 4. the radix passes over key' = range - 1 - bucket of the reversed list: pass 0 reads the keys through a DepthLoader
+static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& kp) {
+    const RadixExec ex = {s->stream, &s->radix, s->ctx->lds_atomic_lane_order};
+    const uint32_t Rs = pl.Rs, val_bits = pl.val_bits;
+    const bool own_payloads = pl.fused_tree || pl.vis_front;    // the fused copy / the cull's front end wrote the payloads themselves
+    DepthLoaderArgs dl = {};
+    dl.keys = s->keys.as<int32_t>();
+    dl.keep = pl.cull ? kp.keep : nullptr;
+    dl.idx = own_payloads ? s->pay_in.as<uint32_t>() : pl.idx_dev;
+    dl.map = own_payloads ? nullptr : pl.map;
+    dl.frame = kp.frame;
+    dl.sort_start = pl.sort_start;
+    dl.render_count = pl.R;
+    dl.range = 1u << s->precision;
+    // (the loader clamps what it reads from `idx`: splat indexes normally, ready-made payloads after a fused copy / front end)
+    dl.last_splat = own_payloads ? pl.max_payload : kp.last_splat;
+    dl.n_dev = pl.vis_cull ? &kp.frame->kept : pl.list_count_dev;
+    const uint32_t passes = (s->precision + 7) / 8;
+    uint32_t* out_tail = s->sorted.as<uint32_t>() + pl.sort_start;
+    void* kbuf[2] = {s->keyA.p, s->keyB.p};
+    uint32_t* vbuf[2] = {s->valA.as<uint32_t>(), s->valB.as<uint32_t>()};
+    // What travels between the passes: after pass p the key still holds precision - 8 (p + 1) bits.  When those fit above the
+    // payload in one 32-bit word (payloads are splat positions < uploaded: 23 bits at 5.8 M splats, 24 at 16 M, so the default
+    // 16-bit buckets always do below 2^24 splats) the pass writes that word instead of a key array and a value array
+    // (radix.hpp PACK_OUT); otherwise 16- or 32-bit keys + values as before, and a later pass packs as soon as it can.
+    // Packed passes stage a whole chunk in LDS (radix.hpp) when the list is short enough for <= CHUNK_TILES tiles per
+    // workgroup and the payload leaves 8 bits for the digit beside it in the last pass's staging word.
+    const bool chunked = !pl.sw.no_chunk && val_bits <= 24u && radix_chunk_grid_for(Rs) != 0u;
+    const bool wide = s->precision > 16;
+    // after a culling pass 0 the element count is the device-resident kept count
+    const uint32_t* n_dev = (pl.cull || pl.vis_cull || pl.list_count_dev) ? &kp.frame->kept : nullptr;
+    bool in_packed = false;                                                       // the previous pass packed
+    for (uint32_t p = 0; p < passes; p++) {
+        const bool last = (p + 1 == passes);
+        const int left = (int)s->precision - 8 * (int)(p + 1);                    // key bits after this pass
+        const bool pack = !last && !pl.sw.no_pack && (uint32_t)left + val_bits <= 32u;
+        const int shift = in_packed ? 0 : 8 * (int)p;
+        uint32_t* vo = last ? out_tail : vbuf[p & 1];
+        if (p == 0) {
+            Pass0Args a = {};
+            a.ld = dl; a.Rs = Rs; a.val_bits = val_bits; a.shift = shift;
+            a.pack = pack; a.chunked = chunked; a.wide = wide; a.kbuf0 = kbuf[0]; a.vo = vo;
+            a.kept_out = pl.cull ? &kp.frame->kept : nullptr;      // a culling pass 0 compacts: it publishes the result's length
+            a.skip_hist = pl.key_hist_fused;
+            const bool has_idx = dl.idx != nullptr;
+            if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
+            else if (pl.cull) GS_TRY((depth_pass0<true, false>(ex, a)));
+            else if (has_idx) GS_TRY((depth_pass0<false, true>(ex, a)));
+            else GS_TRY((depth_pass0<false, false>(ex, a)));
+        } else if (in_packed) {
+            PackedLoader pk = {vbuf[(p - 1) & 1], n_dev, Rs, val_bits};
+            ArrayLoader<uint32_t> ph = {vbuf[(p - 1) & 1], nullptr, n_dev, Rs};
+            if (chunked && last) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, false>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, vo, 0u)));
+            else if (chunked) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, true>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, vo, val_bits)));
+            else if (last) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, false>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, 0u)));
+            else GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, true>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
+        } else if (wide) {
+            ArrayLoader<uint32_t> al = {(const uint32_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
+            if (last) GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, false>(ex, al, al, Rs, shift, (int)p, (uint32_t*)nullptr, vo)));
+            else if (pack) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, ArrayLoader<uint32_t>, uint8_t, false, false, true>(ex, al, shift, al, Rs, shift, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
+            else GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, true>(ex, al, al, Rs, shift, (int)p, (uint32_t*)kbuf[p & 1], vo)));
+        } else {
+            ArrayLoader<uint16_t> al = {(const uint16_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
+            if (last) GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, false>(ex, al, al, Rs, shift, (int)p, (uint16_t*)nullptr, vo)));
+            else GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, true>(ex, al, al, Rs, shift, (int)p, (uint16_t*)kbuf[p & 1], vo)));
+        }
+        in_packed = in_packed || pack;
+    }
+    return GS_OK;
+}
+
+// 5. the unsorted head, the result's bookkeeping, the optional host copy and statistics
+static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, uint32_t passes, uint32_t* sorted_out, gs_sort_stats* stats) {
+    hipStream_t st = s->stream;
+    if (pl.sort_start > 0) {
+        hipLaunchKernelGGL(k_copy_head, dim3(grid_for(pl.sort_start, 1024, 2048)), dim3(256), 0, st, pl.idx_dev, pl.map,
+                           s->sorted.as<uint32_t>(), pl.sort_start, s->uploaded - 1u);
+    }
+    GS_HIP(hipGetLastError());
+    if (s->timed_sort || st != s->ctx->stream) GS_HIP(hipEventRecord(s->ev1, st));   // a draw on another stream waits for it
+    s->last_render = pl.R;
+    s->last_sort = pl.Rs;
     s->last_passes = passes;
-    s->last_identity = (idx_dev == nullptr);
-    s->last_culled = (cull || vis_cull || list_count_dev) && Rs > 0;   // the result's length lives in result_frame->kept
-    s->last_vis_culled = vis_cull && Rs > 0;
+    s->last_identity = (pl.idx_dev == nullptr);
+    s->last_culled = (pl.cull || pl.vis_cull || pl.list_count_dev) && pl.Rs > 0;   // the result's length lives in result_frame->kept
+    s->last_vis_culled = pl.vis_cull && pl.Rs > 0;
     s->result_frame = kp.frame;
-    s->result_mesh = map ? s->bound_mesh : nullptr;
-    s->result_unmap = unmap;
-    // (the clamp of the host-visible un-mapping: payloads of a bound mesh are positions in ITS storage, < mesh.uploaded)
-    s->result_payload_max = (map && s->bound_mesh->uploaded && s->bound_mesh->uploaded - 1u > kp.last_splat) ? s->bound_mesh->uploaded - 1u : kp.last_splat;
+    s->result_mesh = pl.map ? s->bound_mesh : nullptr;
+    s->result_unmap = pl.unmap;
+    s->result_payload_max = pl.max_payload;    // (the clamp of the host-visible un-mapping: payloads of a bound mesh are positions in ITS storage)
     s->has_result = true;
 
-    int status = GS_OK;
-    uint32_t out_count = R;
+    uint32_t out_count = pl.R;
     if (sorted_out && s->last_culled) {            // the result's length is only known on the device
         SortFrame f;
         GS_HIP(hipMemcpyAsync(&f, kp.frame, sizeof(f), hipMemcpyDeviceToHost, st));
@@ -1747,9 +1690,9 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
     }
     if (sorted_out && out_count) {
         const void* src = s->sorted.p;
-        if (unmap) {                               // the host always sees the caller's splat indexes
+        if (pl.unmap) {                            // the host always sees the caller's splat indexes
             GS_TRY(s->debug.ensure((size_t)s->max_count * 4));
-            hipLaunchKernelGGL(k_unmap, dim3(grid_for(out_count, 1024, 2048)), dim3(256), 0, st, s->sorted.as<uint32_t>(), unmap,
+            hipLaunchKernelGGL(k_unmap, dim3(grid_for(out_count, 1024, 2048)), dim3(256), 0, st, s->sorted.as<uint32_t>(), pl.unmap,
                                s->debug.as<uint32_t>(), out_count, s->result_payload_max);
             GS_HIP(hipGetLastError());
             src = s->debug.p;
@@ -1757,14 +1700,35 @@ static int sorter_sort_impl(gs_sorter* s, const float* mvp, const uint32_t* inde
         GS_HIP(hipMemcpyAsync(sorted_out, src, (size_t)out_count * 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
     }
-    if (stats) status = sorter_collect_stats(s, stats);
-    return status;
+    return stats ? sorter_collect_stats(s, stats) : GS_OK;
+}
+
+static int sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_sort, bool device_list, uint32_t sort_count,
+                       uint32_t render_count, const void* precomputed, const float* transforms, uint32_t* sorted_out,
+                       gs_sort_stats* stats, const uint32_t* list_count_dev = nullptr) {
+    GS_REQUIRE(s && mvp, "sorter / mvp == NULL");
+    SortPlan pl = {};
+    pl.mvp = mvp; pl.indexes_to_sort = indexes_to_sort; pl.device_list = device_list; pl.precomputed = precomputed;
+    pl.transforms = transforms; pl.list_count_dev = list_count_dev;
+    KeyParams kp = {};
+    GS_TRY(sort_check(s, sort_count, render_count, pl));
+    ScopedDevice sd(s->ctx->device);
+    GS_TRY(sort_stage_inputs(s, pl, kp));
+    s->timed_sort = stats != nullptr || s->ctx->stage_events;
+    if (s->timed_sort) GS_HIP(hipEventRecord(s->ev0, s->stream));
+    uint32_t passes = 0;
+    if (pl.Rs > 0) {
+        GS_TRY(launch_front_end(s, pl, kp));
+        GS_TRY(run_radix_passes(s, pl, kp));
+        passes = (s->precision + 7) / 8;
+    }
+    return sort_finish(s, pl, kp, passes, sorted_out, stats);
 }
 
 int gs_sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_sort, uint32_t sort_count,
                    uint32_t render_count, const void* precomputed, const float* transforms, uint32_t* sorted_out,
                    gs_sort_stats* stats) {
-    return sorter_sort_impl(s, mvp, indexes_to_sort, false, sort_count, render_count, precomputed, transforms, sorted_out,
+    return sorter_sort(s, mvp, indexes_to_sort, false, sort_count, render_count, precomputed, transforms, sorted_out,
                             stats);
 }
 
@@ -1775,29 +1739,24 @@ int gs_sorter_sort_gathered(gs_sorter* s, const float* mvp, uint32_t sort_count,
     if (s->gathered_on_device) {                                  // s->gathered = the tree's splat count, an upper bound
         GS_REQUIRE(sort_count >= s->gathered, "after an asynchronous gs_tree_gather only the whole list can be sorted: the "
                                               "partial-sort schedule needs splatRenderCount on the host (pass render_count)");
-        return sorter_sort_impl(s, mvp, nullptr, true, s->gathered, s->gathered, precomputed, transforms, sorted_out, stats,
+        return sorter_sort(s, mvp, nullptr, true, s->gathered, s->gathered, precomputed, transforms, sorted_out, stats,
                                 s->gathered_dev.as<uint32_t>());
     }
     if (sort_count > s->gathered) sort_count = s->gathered;       // Math.min(queuedSorts.shift(), splatRenderCount)
-    return sorter_sort_impl(s, mvp, nullptr, true, sort_count, s->gathered, precomputed, transforms, sorted_out, stats);
+    return sorter_sort(s, mvp, nullptr, true, sort_count, s->gathered, precomputed, transforms, sorted_out, stats);
 }
 
 // A bound sorter that culls by visibility and holds the mesh's position map derives the by-original-index mask itself
 // (k_mask_derive_count): the mesh's next full-frame gs_mesh_project may then skip its per-survivor atomics.
 static void sorter_tell_mesh(gs_sorter* s) {
     gs_mesh* m = s->bound_mesh;
-    if (!m) return;
-    bool alive = false;
-    for (gs_mesh* l : s->ctx->live_meshes) alive = alive || l == m;
-    if (alive) m->derive_orig_mask = s->visibility_cull && gs_mesh_payload_map(m, s->uploaded) != nullptr;
+    if (sorter_mesh_alive(s->ctx, m)) m->derive_orig_mask = s->visibility_cull && gs_mesh_payload_map(m, s->uploaded) != nullptr;
 }
 
 int gs_sorter_bind_mesh(gs_sorter* s, gs_mesh* m) {
     GS_REQUIRE(s != nullptr, "sorter == NULL");
     GS_REQUIRE(!m || m->ctx == s->ctx, "mesh lives on another context");
-    if (s->bound_mesh && s->bound_mesh != m) {
-        for (gs_mesh* l : s->ctx->live_meshes) if (l == s->bound_mesh) l->derive_orig_mask = false;
-    }
+    if (s->bound_mesh != m && sorter_mesh_alive(s->ctx, s->bound_mesh)) s->bound_mesh->derive_orig_mask = false;
     s->bound_mesh = m;
     sorter_tell_mesh(s);
     return GS_OK;
@@ -1835,9 +1794,7 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     if (what == 0) src = s->keys.p;
     else if (what == 2) {
         src = s->sorted.p;
-        bool alive = false;
-        for (gs_mesh* m : s->ctx->live_meshes) alive = alive || (m == s->result_mesh);
-        if (alive && s->result_unmap && count) {
+        if (sorter_mesh_alive(s->ctx, s->result_mesh) && s->result_unmap && count) {
             GS_TRY(s->debug.ensure((size_t)s->max_count * 4));
             hipLaunchKernelGGL(k_unmap, dim3(grid_for(count, 1024, 2048)), dim3(256), 0, st, s->sorted.as<uint32_t>(),
                                s->result_unmap, s->debug.as<uint32_t>(), count, s->result_payload_max);
@@ -1847,7 +1804,7 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     }
     else if (what == 1) {
         GS_TRY(s->debug.ensure((size_t)s->max_count * 4));
-        DepthLoader dl = {};
+        DepthLoaderArgs dl = {};
         dl.keys = s->keys.as<int32_t>();
         dl.frame = s->frame.as<SortFrame>() + s->frame_index;
         dl.sort_start = s->last_render - s->last_sort;
@@ -1855,7 +1812,7 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
         dl.range = 1u << s->precision;
         GS_HIP(hipMemsetAsync(s->debug.p, 0, (size_t)s->last_render * 4, st));
         if (s->last_sort)
-            hipLaunchKernelGGL(k_debug_buckets, dim3(grid_for(s->last_sort, 1024, 2048)), dim3(256), 0, st, dl, s->debug.as<int32_t>());
+            hipLaunchKernelGGL(k_debug_buckets, dim3(grid_for(s->last_sort, 1024, 2048)), dim3(256), 0, st, DepthLoader{dl}, s->debug.as<int32_t>());
         GS_HIP(hipGetLastError());
         src = s->debug.p;
     } else if (what == 3) {
