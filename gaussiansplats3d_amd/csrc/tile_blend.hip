@@ -72,9 +72,6 @@ __device__ __forceinline__ uint32_t quadrant_mask(uint2 r16, uint32_t bx, uint32
 // only 3 % / 12 % / 13 % of the halves were skippable, and the branches cost more than they saved: blend ms with whole-quadrant
 // masks / half masks + skip: C3 0.070 / 0.076-0.083, C3T 0.477 / 0.507-0.585, C2 0.190 / 0.203-0.226, C3S 4.38 / 4.30;
 // profiles/r03b_blend_lanes.txt, r03b_ab_blend_half_skip.txt.)
-#ifndef GS_BLEND_EXACT
-#define GS_BLEND_EXACT 1
-#endif
 __device__ __forceinline__ uint32_t exact_quadrants(uint32_t qm, const uint4 lo, const uint4 hi, uint32_t bx, uint32_t by) {
 #pragma clang fp contract(off)
     const float cx = __uint_as_float(lo.x), cy = __uint_as_float(lo.y);
@@ -108,50 +105,12 @@ __device__ __forceinline__ uint32_t exact_quadrants(uint32_t qm, const uint4 lo,
     return qm & out;
 }
 
-// Which of the sixteen 8x8-pixel blocks of the 32-px bin (bx, by) the splat can reach: bit 4 q + b, q = the quadrant (as above),
-// b = (block column & 1) + 2 (block row & 1) inside it.  CONSERVATIVE (a clear bit proves that every pixel of the block fails
-// `A <= 8`; a set bit promises nothing), by four separating axes between the block of pixel centres (half-extent 3.5) and the
-// ellipse u^2 + w^2 <= 4 log2(e): the ellipse's own two axes (|u| and |w| at the block's centre against the block's reach along
-// that axis plus the radius - for a thin splat the only test that matters) and the pixel axes (the ellipse's bounding box).
-// A splat skipped on a block would have composited alpha = 0 there - C and T unchanged, bit for bit - so nothing that decides a
-// pixel depends on this mask: it only says where evaluating the splat is a waste of lanes.
-// Margins: the blend evaluates u = fma(ay, y, fma(ax, x, cu)) relative to the bin's origin, this test ax X + ay Y relative to
-// the splat's centre; both round at the scale of |ax| |cx - origin| + |ay| |cy - origin| (a long thin splat whose centre is far
-// from the bin), which `slack` bounds with a factor of 8 to spare.
-__device__ __forceinline__ uint32_t block_mask16(const uint4 lo, const uint4 hi, uint32_t bx, uint32_t by) {
-#pragma clang fp contract(off)
-    const float cx = __uint_as_float(lo.x), cy = __uint_as_float(lo.y);
-    const float ax = __uint_as_float(lo.z), ay = __uint_as_float(lo.w), ex = __uint_as_float(hi.x), ey = __uint_as_float(hi.y);
-    constexpr float R = 2.4022448f * 1.0005f;                                // sqrt(4 log2(e)), and the limit's own margin
-    const float X0 = (float)(bx * GS_BIN) + 4.0f - cx, Y0 = (float)(by * GS_BIN) + 4.0f - cy;   // centre of block (0, 0) from the splat's
-    const float far = fabsf(X0) + fabsf(Y0) + 64.0f;
-    const float su = 3.5f * (fabsf(ax) + fabsf(ay)) + R + 1e-6f * far * (fabsf(ax) + fabsf(ay));
-    const float sw = 3.5f * (fabsf(ex) + fabsf(ey)) + R + 1e-6f * far * (fabsf(ex) + fabsf(ey));
-    const float det = ax * ey - ay * ex;
-    const float idet2 = __builtin_amdgcn_rcpf(det * det);                    // inf for a degenerate basis: every block kept
-    const float sx = 3.5f + R * 1.001f * __builtin_sqrtf((ay * ay + ey * ey) * idet2) + 1e-3f;
-    const float sy = 3.5f + R * 1.001f * __builtin_sqrtf((ax * ax + ex * ex) * idet2) + 1e-3f;
-    uint32_t out = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < 4u; r++) {
-        const float Y = Y0 + 8.0f * (float)r;
-        const bool row_ok = !(fabsf(Y) > sy);                                // (NaN keeps)
-#pragma unroll
-        for (uint32_t c = 0; c < 4u; c++) {
-            const float X = X0 + 8.0f * (float)c;
-            const float u = ax * X + ay * Y, w = ex * X + ey * Y;
-            const bool ok = row_ok && !(fabsf(X) > sx) && !(fabsf(u) > su) && !(fabsf(w) > sw);
-            if (ok) out |= 1u << (4u * ((c >> 1) + 2u * (r >> 1)) + (c & 1u) + 2u * (r & 1u));
-        }
-    }
-    return out;
-}
-
-// expands one record, relative to the origin of the bin that stages it
-__device__ __forceinline__ void stage_entry(LdsSplat* dst, const uint4 lo, const uint4 hi, float bin_x0, float bin_y0, float z = 0.0f) {
+// expands one record, relative to the origin of the bin (bx, by) that stages it (z: the splat's window depth, draws with a
+// destination depth only)
+__device__ __forceinline__ void stage_entry(LdsSplat* dst, const uint4 lo, const uint4 hi, uint32_t bx, uint32_t by, float z) {
 #pragma clang fp contract(off)
     LdsSplat s;
-    const float cx = __uint_as_float(lo.x) - bin_x0, cy = __uint_as_float(lo.y) - bin_y0;
+    const float cx = __uint_as_float(lo.x) - (float)(bx * GS_BIN), cy = __uint_as_float(lo.y) - (float)(by * GS_BIN);
     s.ax = __uint_as_float(lo.z); s.ay = __uint_as_float(lo.w);
     s.bx = __uint_as_float(hi.x); s.by = __uint_as_float(hi.y);
     s.cu = -__builtin_fmaf(s.ax, cx, s.ay * cy);
@@ -163,191 +122,6 @@ __device__ __forceinline__ void stage_entry(LdsSplat* dst, const uint4 lo, const
     s.a = (float)(hi.w >> 16) * (1.0f / 65535.0f);
     *dst = s;
 }
-
-#ifdef GS_BLEND_PROFILE
-// tools/blend_profile.py: per bin {start, end} of s_memrealtime (100 MHz), list length, batches, survivors walked by wave 0..3
-// ... and [8] lane evaluations (256 per walked splat), [9] lanes that passed `keep` (A <= 8), [10] lanes that passed it on a
-// pixel still accumulating (T > 1e-4), [11] half quadrants evaluated: what fraction of the blend's pixel work can hit anything;
-// [12] iterations of a walk by 8x8 blocks (see the walk), [13] (splat, 8x8 block) pairs that walk would evaluate
-constexpr unsigned BLEND_PROF_BINS = 40960, BLEND_PROF_WORDS = 14;
-__device__ unsigned long long g_blend_prof[BLEND_PROF_WORDS * BLEND_PROF_BINS];
-// per deep-pass unit: {start, end, windows scanned, survivors composited}
-__device__ unsigned long long g_deep_prof[4 * GS_DEEP_UNITS];
-extern "C" int gs_debug_deep_prof(void* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_deep_prof), sizeof(unsigned long long) * 4 * GS_DEEP_UNITS, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int gs_debug_blend_prof(void* dst, unsigned bins) {
-    if (bins > BLEND_PROF_BINS) bins = BLEND_PROF_BINS;
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_blend_prof), (size_t)bins * BLEND_PROF_WORDS * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
-
-// 6 workgroups per CU: the kernel wants 80 VGPRs.  In r02 8 per CU (64 VGPRs) spilled 50 registers (132 MB of HBM traffic
-// per launch instead of 34).  Re-measured on the r03 kernel, which spills only 8 / 16 dwords at 7 / 8 per CU and none of them in
-// the inner loop (profiles/r03zz_ab_blend_occupancy.txt, blend ms at 6 / 7 / 8): C3 0.057 / 0.061 / 0.067, C3T 0.396 / 0.465 /
-// 0.626, C2 0.156 / 0.184 / 0.231, C5 0.579 / 0.584 / 0.600 - all 2040 bins of a 1080p frame resident at once does not pay for
-// the scratch traffic of the staging code.  With 6, a quarter of the workgroups start late, into whatever CU frees up first.
-#ifndef BLEND_OCC
-#define BLEND_OCC 6
-#endif
-#ifndef GS_BLEND_PAIRS
-#define GS_BLEND_PAIRS 0              // 1: the per-bin kernel composites two survivors per iteration where it can (A/B)
-#endif
-#ifndef GS_BLEND_CHECK
-#define GS_BLEND_CHECK 8u             // a wave tests its quadrant for saturation after every 8th splat it composites (4 / 8 / 16 measured:
-                                      // C3 blend 0.0587 / 0.0575 / 0.0613 ms, C2 0.159 / 0.153 / 0.151, C3S 0.90 / 0.88 / 0.88; profiles/r04y_ab_project.txt)
-#endif
-static_assert(256u % GS_BLEND_CHECK == 0, "every chunk ends on a saturation test");
-
-// the 4 pixels of a lane (x = lane & 15, y = (lane >> 4) + 4g) as two packed pairs: [h].x = strip 2h, [h].y = strip 2h + 1
-struct Px {
-    v2f T[2], Cr[2], Cg[2], Cb[2];
-    __device__ __forceinline__ void reset() {
-#pragma unroll
-        for (int h = 0; h < 2; h++) { T[h] = v2f{1.0f, 1.0f}; Cr[h] = v2f{0, 0}; Cg[h] = v2f{0, 0}; Cb[h] = v2f{0, 0}; }
-    }
-    __device__ __forceinline__ float4 get(int g) const { return make_float4(Cr[g >> 1][g & 1], Cg[g >> 1][g & 1], Cb[g >> 1][g & 1], T[g >> 1][g & 1]); }
-    __device__ __forceinline__ bool open() const {            // wave-uniform: some pixel of the quadrant still has T > 1e-4
-        const float tmax = fmaxf(fmaxf(T[0].x, T[0].y), fmaxf(T[1].x, T[1].y));
-        return __ballot(tmax > GS_T_EPS) != 0ull;
-    }
-};
-
-__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-
-// One splat over the 4 pixels of every lane: the fragment shader + one step of the front-to-back composite.  Every operation is
-// spelled out (no contraction left to the compiler): the per-bin kernel and the deep pass must produce the same bits.
-// `if (A > 8.0) discard` is a saturated multiply-add instead of a compare + select (which does not pack and stalls on VCC):
-// keep = sat((CUT - pw) * 2^100) is exactly 1 for pw < CUT and 0 for pw >= CUT - fp32 cannot represent a positive difference
-// below 2^-100 here.  The two pairs are independent chains the scheduler interleaves.
-// DEPTH (a draw with a destination depth, gs_mesh_set_destination): the reference's `depthTest: true, depthWrite: false`
-// (SplatMaterial3D.js:72-73) - a fragment whose depth (the splat centre's: the quad is flat, :206-210) fails LEQUAL against the
-// pixel's stored depth dz contributes nothing: alpha = 0 there, exactly like a discarded fragment.  A per-(splat, pixel) select
-// on the alpha, so the order of the list and who executes the composite stay irrelevant.
-struct Alpha { v2f a[2]; float r, g, b; };
-template <bool DEPTH>
-__device__ __forceinline__ void alpha_of(const LdsSplat* sp, float fx, const v2f (&fy)[2], const v2f (&dz)[2], const Px& px, Alpha& out, uint32_t& p_kept, uint32_t& p_useful) {
-#pragma clang fp contract(off)
-    const float4 q0 = *reinterpret_cast<const float4*>(&sp->ax);     // three wave-uniform ds_read_b128 broadcasts
-    const float4 q1 = *reinterpret_cast<const float4*>(&sp->bx);
-    const float4 q2 = *reinterpret_cast<const float4*>(&sp->r);
-    const float ux = __builtin_fmaf(q0.x, fx, q0.z), wx = __builtin_fmaf(q1.x, fx, q1.z);
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const v2f u = fma2(v2f{q0.y, q0.y}, fy[h], v2f{ux, ux});
-        const v2f w = fma2(v2f{q1.y, q1.y}, fy[h], v2f{wx, wx});
-        const v2f pw = fma2(u, u, w * w);
-        v2f e;
-        e.x = __builtin_amdgcn_exp2f(-pw.x);
-        e.y = __builtin_amdgcn_exp2f(-pw.y);
-        const v2f keep = pk_fma_sat(pw, v2f{-GS_HUGE, -GS_HUGE}, v2f{GS_POWER_CUT * GS_HUGE, GS_POWER_CUT * GS_HUGE});
-#ifdef GS_BLEND_PROFILE
-        p_kept += (uint32_t)__popcll(__ballot(keep.x > 0.0f)) + (uint32_t)__popcll(__ballot(keep.y > 0.0f));
-        p_useful += (uint32_t)__popcll(__ballot(keep.x > 0.0f && px.T[h].x > GS_T_EPS)) +
-                    (uint32_t)__popcll(__ballot(keep.y > 0.0f && px.T[h].y > GS_T_EPS));
-#endif
-        out.a[h] = e * (v2f{q1.w, q1.w} * keep);
-        if (DEPTH) {
-            out.a[h].x = q0.w <= dz[h].x ? out.a[h].x : 0.0f;
-            out.a[h].y = q0.w <= dz[h].y ? out.a[h].y : 0.0f;
-        }
-    }
-    out.r = q2.x; out.g = q2.y; out.b = q2.z;
-    (void)px; (void)p_kept; (void)p_useful; (void)dz;
-}
-__device__ __forceinline__ void apply_alpha(Px& px, const Alpha& al) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const v2f wgt = px.T[h] * al.a[h];
-        px.Cr[h] = fma2(wgt, v2f{al.r, al.r}, px.Cr[h]);
-        px.Cg[h] = fma2(wgt, v2f{al.g, al.g}, px.Cg[h]);
-        px.Cb[h] = fma2(wgt, v2f{al.b, al.b}, px.Cb[h]);
-        px.T[h] = fma2(-px.T[h], al.a[h], px.T[h]);                  // T * (1 - alpha) without waiting for wgt
-    }
-}
-template <bool DEPTH>
-__device__ __forceinline__ void composite_one(const LdsSplat* sp, float fx, const v2f (&fy)[2], const v2f (&dz)[2], Px& px, uint32_t& p_kept, uint32_t& p_useful) {
-    Alpha al;
-    alpha_of<DEPTH>(sp, fx, fy, dz, px, al, p_kept, p_useful);
-    apply_alpha(px, al);
-}
-// Two consecutive splats: both alphas first (they do not depend on the pixel's state), then the two composite steps in order -
-// the same operations on the same operands as two composite_one calls, with the second splat's LDS reads and exponentials in
-// the shadow of the first's.  For waves that walk alone (the deep pass's units): they are bound by the latency of one splat's
-// dependent chain (~400 cycles per splat against 132 of VALU issue), not by issue slots.
-template <bool DEPTH>
-__device__ __forceinline__ void composite_two(const LdsSplat* sp, const LdsSplat* sp1, float fx, const v2f (&fy)[2], const v2f (&dz)[2], Px& px, uint32_t& p_kept, uint32_t& p_useful) {
-    Alpha a0, a1;
-    alpha_of<DEPTH>(sp, fx, fy, dz, px, a0, p_kept, p_useful);
-    alpha_of<DEPTH>(sp1, fx, fy, dz, px, a1, p_kept, p_useful);
-    apply_alpha(px, a0);
-    apply_alpha(px, a1);
-}
-
-// The second level of the chunked composite: chunk partials {C_c, T_c} merged near -> far.  The fold of a single chunk is exact
-// (fma(1, C, 0) = C, 1 * T = T).  It stops after the first chunk that leaves no pixel of the quadrant with T > 1e-4.
-struct Folded {
-    float C[4][3], T[4];
-    __device__ __forceinline__ void reset() {
-#pragma unroll
-        for (int g = 0; g < 4; g++) { T[g] = 1.0f; C[g][0] = 0.0f; C[g][1] = 0.0f; C[g][2] = 0.0f; }
-    }
-    __device__ __forceinline__ void merge(int g, const float4 p) {
-        C[g][0] = __builtin_fmaf(T[g], p.x, C[g][0]);
-        C[g][1] = __builtin_fmaf(T[g], p.y, C[g][1]);
-        C[g][2] = __builtin_fmaf(T[g], p.z, C[g][2]);
-        T[g] = __fmul_rn(T[g], p.w);
-    }
-    __device__ __forceinline__ void merge_cum(int g, const float4 p) {   // p.w = the product INCLUDING this chunk (bin_body's pool)
-        C[g][0] = __builtin_fmaf(T[g], p.x, C[g][0]);
-        C[g][1] = __builtin_fmaf(T[g], p.y, C[g][1]);
-        C[g][2] = __builtin_fmaf(T[g], p.z, C[g][2]);
-        T[g] = p.w;
-    }
-    __device__ __forceinline__ bool open() const {
-        const float tmax = fmaxf(fmaxf(T[0], T[1]), fmaxf(T[2], T[3]));
-        return __ballot(tmax > GS_T_EPS) != 0ull;
-    }
-};
-
-// dst_rgba (nullable): the colour the splats are blended over (gs_mesh_set_destination), the WHOLE frame's RGBA8 rows.  Back to
-// front NormalBlending over dst leaves rgb = C + T * dst.rgb, alpha = (1 - T) + T * dst.a (C, T = the splats' own composite).
-__device__ __forceinline__ void write_pixels(uint32_t* __restrict__ out, uint32_t width, uint32_t y0, uint32_t y1, uint32_t px, uint32_t py0,
-                                             const Folded& f, const uint32_t* __restrict__ dst_rgba = nullptr) {
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const uint32_t py = py0 + 4u * g;
-        if (px < width && py >= y0 && py < y1) {
-            float a = 1.0f - f.T[g];
-            float cr = f.C[g][0], cg = f.C[g][1], cb = f.C[g][2];
-            if (dst_rgba) {
-                const uint32_t d = dst_rgba[(size_t)py * width + px];
-                cr = __builtin_fmaf(f.T[g], (float)(d & 255u) * (1.0f / 255.0f), cr);
-                cg = __builtin_fmaf(f.T[g], (float)((d >> 8) & 255u) * (1.0f / 255.0f), cg);
-                cb = __builtin_fmaf(f.T[g], (float)((d >> 16) & 255u) * (1.0f / 255.0f), cb);
-                a = __builtin_fmaf(f.T[g], (float)(d >> 24) * (1.0f / 255.0f), a);
-            }
-            const uint32_t r8 = (uint32_t)(fminf(fmaxf(cr, 0.0f), 1.0f) * 255.0f + 0.5f);
-            const uint32_t g8 = (uint32_t)(fminf(fmaxf(cg, 0.0f), 1.0f) * 255.0f + 0.5f);
-            const uint32_t b8 = (uint32_t)(fminf(fmaxf(cb, 0.0f), 1.0f) * 255.0f + 0.5f);
-            const uint32_t a8 = (uint32_t)(fminf(fmaxf(a, 0.0f), 1.0f) * 255.0f + 0.5f);
-            out[(size_t)(py - y0) * width + px] = r8 | (g8 << 8) | (b8 << 16) | (a8 << 24);
-        }
-    }
-}
-
-struct DeepArgs {
-    uint32_t* flags;            // gs_mesh::deep_flags (GS_FLAG_*)
-    uint32_t* ent;              // [GS_DEEP_MAX_BINS][GS_DEEP_LIST_CAP]
-    uint32_t* cnt;              // [GS_DEEP_MAX_BINS][GS_DEEP_RANGES][4]
-    float4* partial;            // [GS_DEEP_UNITS][256]
-    uint32_t* work;             // [GS_DEEP_UNITS]: d << 7 | c << 2 | q of the units that exist (k_deep_plan)
-    float4* pool;               // [pool_slots][256]
-    uint32_t pool_slots;        // GS_POOL_SLOTS (tests shrink it: $GSPLAT_POOL_SLOTS)
-    uint32_t unit_wgs;          // workgroups of (bin, quadrant, chunk) units behind the per-bin workgroups (0: no deep pass)
-    uint32_t unit_at;           // ... sit at blockIdx [unit_at, unit_at + unit_wgs): behind the unit_at costliest bins' workgroups
-};
 
 struct FrameArgs {
     const uint2* __restrict__ ranges;
@@ -367,21 +141,6 @@ struct FrameArgs {
     uint32_t depth_mode, height;
 };
 
-// the stored depth of this lane's four pixels (x = px, y = py0 + 4 g), as the blend compares it; outside the frame: passes
-__device__ __forceinline__ void load_dst_depth(const FrameArgs& fa, uint32_t px, uint32_t py0, v2f (&dz)[2]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const uint32_t py = py0 + 4u * g;
-        float d = GS_HUGE;
-        if (px < fa.width && py < fa.height) {
-            d = fa.dst_depth[(size_t)py * fa.width + px];
-            if (fa.depth_mode == 2u) d = (float)floor((double)d * 16777215.0 + 0.5);
-        }
-        dz[g >> 1][g & 1] = d;
-    }
-}
-
 struct BinGeom {
     uint32_t bx, by, begin, n;
     __device__ __forceinline__ BinGeom(const FrameArgs& fa, uint32_t bin) {
@@ -398,6 +157,272 @@ struct BinGeom {
     }
 };
 
+// A lane's place in quadrant q of a bin: its 4 pixels (x = px, y = py0 + 4 g), their centres relative to the bin's origin (what the
+// staged splats are expressed in) as two packed pairs - [h].x = strip 2h, [h].y = strip 2h + 1 - and (DEPTH) the stored depth of
+// each as the blend compares it; outside the frame: passes.
+template <bool DEPTH>
+struct QuadLane {
+    uint32_t px, py0;
+    float fx;
+    v2f fy[2], dz[2];
+    __device__ __forceinline__ QuadLane(const FrameArgs& fa, const BinGeom& bg, uint32_t q, uint32_t lane) {
+        px = bg.bx * GS_BIN + (q & 1u) * GS_TILE + (lane & 15u);
+        py0 = bg.by * GS_BIN + (q >> 1) * GS_TILE + (lane >> 4);
+        fx = (float)((q & 1u) * GS_TILE + (lane & 15u)) + 0.5f;
+        const float fy0 = (float)((q >> 1) * GS_TILE + (lane >> 4)) + 0.5f;
+        fy[0] = v2f{fy0, fy0 + 4.0f}; fy[1] = v2f{fy0 + 8.0f, fy0 + 12.0f};
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const uint32_t py = py0 + 4u * g;
+            float d = GS_HUGE;
+            if (DEPTH && px < fa.width && py < fa.height) {
+#pragma clang fp contract(off)
+                d = fa.dst_depth[(size_t)py * fa.width + px];
+                if (fa.depth_mode == 2u) d = (float)floor((double)d * 16777215.0 + 0.5);
+            }
+            dz[g >> 1][g & 1] = d;
+        }
+    }
+};
+
+// 6 workgroups per CU: the kernel wants 80 VGPRs.  In r02 8 per CU (64 VGPRs) spilled 50 registers (132 MB of HBM traffic
+// per launch instead of 34).  Re-measured on the r03 kernel, which spills only 8 / 16 dwords at 7 / 8 per CU and none of them in
+// the inner loop (profiles/r03zz_ab_blend_occupancy.txt, blend ms at 6 / 7 / 8): C3 0.057 / 0.061 / 0.067, C3T 0.396 / 0.465 /
+// 0.626, C2 0.156 / 0.184 / 0.231, C5 0.579 / 0.584 / 0.600 - all 2040 bins of a 1080p frame resident at once does not pay for
+// the scratch traffic of the staging code.  With 6, a quarter of the workgroups start late, into whatever CU frees up first.
+constexpr int BLEND_OCC = 6;
+// a wave tests its quadrant for saturation after every 8th splat it composites (4 / 8 / 16 measured: C3 blend 0.0587 / 0.0575 /
+// 0.0613 ms, C2 0.159 / 0.153 / 0.151, C3S 0.90 / 0.88 / 0.88; profiles/r04y_ab_project.txt)
+constexpr uint32_t GS_BLEND_CHECK = 8u;
+static_assert(256u % GS_BLEND_CHECK == 0, "every chunk ends on a saturation test");
+
+// the 4 pixels of a lane (x = lane & 15, y = (lane >> 4) + 4g) as two packed pairs: [h].x = strip 2h, [h].y = strip 2h + 1
+struct Px {
+    v2f T[2], Cr[2], Cg[2], Cb[2];
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int h = 0; h < 2; h++) { T[h] = v2f{1.0f, 1.0f}; Cr[h] = v2f{0, 0}; Cg[h] = v2f{0, 0}; Cb[h] = v2f{0, 0}; }
+    }
+    __device__ __forceinline__ float4 get(int g) const { return make_float4(Cr[g >> 1][g & 1], Cg[g >> 1][g & 1], Cb[g >> 1][g & 1], T[g >> 1][g & 1]); }
+    __device__ __forceinline__ bool open() const {            // wave-uniform: some pixel of the quadrant still has T > 1e-4
+        const float tmax = fmaxf(fmaxf(T[0].x, T[0].y), fmaxf(T[1].x, T[1].y));
+        return __ballot(tmax > GS_T_EPS) != 0ull;
+    }
+};
+
+__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+
+// The -DGS_BLEND_PROFILE build's counters (`make blendprof`); in the default build an empty object whose methods do nothing, so
+// that the composite has one signature.  A default-constructed one (the ROP8 draw's) counts nothing in either build.
+#ifdef GS_BLEND_PROFILE
+// tools/blend_profile.py: per bin {start, end} of s_memrealtime (100 MHz), list length, batches, survivors walked by wave 0..3
+// ... and [8] lane evaluations (256 per walked splat), [9] lanes that passed `keep` (A <= 8), [10] lanes that passed it on a
+// pixel still accumulating (T > 1e-4), [11] half quadrants evaluated: what fraction of the blend's pixel work can hit anything
+constexpr unsigned BLEND_PROF_BINS = 40960, BLEND_PROF_WORDS = 12;
+__device__ unsigned long long g_blend_prof[BLEND_PROF_WORDS * BLEND_PROF_BINS];
+// per deep-pass unit: {start, end, windows scanned, survivors composited}
+__device__ unsigned long long g_deep_prof[4 * GS_DEEP_UNITS];
+extern "C" int gs_debug_deep_prof(void* dst) {
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_deep_prof), sizeof(unsigned long long) * 4 * GS_DEEP_UNITS, 0, hipMemcpyDeviceToHost);
+}
+extern "C" int gs_debug_blend_prof(void* dst, unsigned bins) {
+    if (bins > BLEND_PROF_BINS) bins = BLEND_PROF_BINS;
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_blend_prof), (size_t)bins * BLEND_PROF_WORDS * 8, 0, hipMemcpyDeviceToHost);
+}
+struct BlendProf {
+    const Px* px = nullptr;                                 // the pixels the composite accumulates into (null: count nothing)
+    unsigned long long t_start = 0;
+    uint32_t batches = 0, kept = 0, useful = 0;
+    __device__ __forceinline__ BlendProf() {}
+    __device__ __forceinline__ explicit BlendProf(const Px& acc) : px(&acc), t_start(wall_clock64()) {}
+    __device__ __forceinline__ void batch() { batches++; }
+    __device__ __forceinline__ void lanes(int h, v2f keep) {
+        if (!px) return;
+        kept += (uint32_t)__popcll(__ballot(keep.x > 0.0f)) + (uint32_t)__popcll(__ballot(keep.y > 0.0f));
+        useful += (uint32_t)__popcll(__ballot(keep.x > 0.0f && px->T[h].x > GS_T_EPS)) +
+                  (uint32_t)__popcll(__ballot(keep.y > 0.0f && px->T[h].y > GS_T_EPS));
+    }
+    // the end of bin_body (every thread of the workgroup): this bin's words
+    __device__ __forceinline__ void bin_done(uint32_t bin, uint32_t n, uint32_t wave, uint32_t walked) {
+        __shared__ unsigned int s_prof[3];
+        const uint32_t tid = threadIdx.x, lane = tid & 63u;
+        if (tid < 3u) s_prof[tid] = 0u;
+        __syncthreads();
+        if (lane == 0u) {
+            atomicAdd(&s_prof[0], kept);
+            atomicAdd(&s_prof[1], useful);
+            atomicAdd(&s_prof[2], 2u * walked);
+        }
+        if (bin < BLEND_PROF_BINS && lane == 0u) {
+            if (wave == 0u) {
+                g_blend_prof[BLEND_PROF_WORDS * bin + 0] = t_start;
+                g_blend_prof[BLEND_PROF_WORDS * bin + 2] = n;
+                g_blend_prof[BLEND_PROF_WORDS * bin + 3] = batches;
+            }
+            g_blend_prof[BLEND_PROF_WORDS * bin + 4 + wave] = walked;
+        }
+        __syncthreads();
+        if (bin < BLEND_PROF_BINS && tid == 0u) {
+            g_blend_prof[BLEND_PROF_WORDS * bin + 1] = wall_clock64();
+            g_blend_prof[BLEND_PROF_WORDS * bin + 8] = 128ull * s_prof[2];
+            g_blend_prof[BLEND_PROF_WORDS * bin + 9] = s_prof[0];
+            g_blend_prof[BLEND_PROF_WORDS * bin + 10] = s_prof[1];
+            g_blend_prof[BLEND_PROF_WORDS * bin + 11] = s_prof[2];
+        }
+    }
+};
+#else
+struct BlendProf {
+    __device__ __forceinline__ BlendProf() {}
+    __device__ __forceinline__ explicit BlendProf(const Px&) {}
+    __device__ __forceinline__ void batch() {}
+    __device__ __forceinline__ void lanes(int, v2f) {}
+    __device__ __forceinline__ void bin_done(uint32_t, uint32_t, uint32_t, uint32_t) {}
+};
+#endif
+
+// The per-bin kernel's stop rule as a step of a walk that does nothing else at a test (the deep pass's units): `n` more splats
+// composited - one, or a pair, which never straddles a test; false once a test finds the quadrant saturated.
+__device__ __forceinline__ bool still_open(const Px& acc, uint32_t& since_check, uint32_t n) {
+    since_check += n;
+    if (since_check != GS_BLEND_CHECK) return true;
+    since_check = 0;
+    return acc.open();
+}
+
+// One splat over the 4 pixels of every lane: the fragment shader + one step of the front-to-back composite.  Every operation is
+// spelled out (no contraction left to the compiler): the per-bin kernel and the deep pass must produce the same bits.
+// `if (A > 8.0) discard` is a saturated multiply-add instead of a compare + select (which does not pack and stalls on VCC):
+// keep = sat((CUT - pw) * 2^100) is exactly 1 for pw < CUT and 0 for pw >= CUT - fp32 cannot represent a positive difference
+// below 2^-100 here.  The two pairs are independent chains the scheduler interleaves.
+// DEPTH (a draw with a destination depth, gs_mesh_set_destination): the reference's `depthTest: true, depthWrite: false`
+// (SplatMaterial3D.js:72-73) - a fragment whose depth (the splat centre's: the quad is flat, :206-210) fails LEQUAL against the
+// pixel's stored depth dz contributes nothing: alpha = 0 there, exactly like a discarded fragment.  A per-(splat, pixel) select
+// on the alpha, so the order of the list and who executes the composite stay irrelevant.
+struct Alpha { v2f a[2]; float r, g, b; };
+template <bool DEPTH>
+__device__ __forceinline__ void alpha_of(const LdsSplat* sp, const QuadLane<DEPTH>& ql, Alpha& out, BlendProf& prof) {
+#pragma clang fp contract(off)
+    const float4 q0 = *reinterpret_cast<const float4*>(&sp->ax);     // three wave-uniform ds_read_b128 broadcasts
+    const float4 q1 = *reinterpret_cast<const float4*>(&sp->bx);
+    const float4 q2 = *reinterpret_cast<const float4*>(&sp->r);
+    const float ux = __builtin_fmaf(q0.x, ql.fx, q0.z), wx = __builtin_fmaf(q1.x, ql.fx, q1.z);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const v2f u = fma2(v2f{q0.y, q0.y}, ql.fy[h], v2f{ux, ux});
+        const v2f w = fma2(v2f{q1.y, q1.y}, ql.fy[h], v2f{wx, wx});
+        const v2f pw = fma2(u, u, w * w);
+        v2f e;
+        e.x = __builtin_amdgcn_exp2f(-pw.x);
+        e.y = __builtin_amdgcn_exp2f(-pw.y);
+        const v2f keep = pk_fma_sat(pw, v2f{-GS_HUGE, -GS_HUGE}, v2f{GS_POWER_CUT * GS_HUGE, GS_POWER_CUT * GS_HUGE});
+        prof.lanes(h, keep);
+        out.a[h] = e * (v2f{q1.w, q1.w} * keep);
+        if (DEPTH) {
+            out.a[h].x = q0.w <= ql.dz[h].x ? out.a[h].x : 0.0f;
+            out.a[h].y = q0.w <= ql.dz[h].y ? out.a[h].y : 0.0f;
+        }
+    }
+    out.r = q2.x; out.g = q2.y; out.b = q2.z;
+}
+__device__ __forceinline__ void apply_alpha(Px& px, const Alpha& al) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const v2f wgt = px.T[h] * al.a[h];
+        px.Cr[h] = fma2(wgt, v2f{al.r, al.r}, px.Cr[h]);
+        px.Cg[h] = fma2(wgt, v2f{al.g, al.g}, px.Cg[h]);
+        px.Cb[h] = fma2(wgt, v2f{al.b, al.b}, px.Cb[h]);
+        px.T[h] = fma2(-px.T[h], al.a[h], px.T[h]);                  // T * (1 - alpha) without waiting for wgt
+    }
+}
+template <bool DEPTH>
+__device__ __forceinline__ void composite_one(const LdsSplat* sp, const QuadLane<DEPTH>& ql, Px& px, BlendProf& prof) {
+    Alpha al;
+    alpha_of(sp, ql, al, prof);
+    apply_alpha(px, al);
+}
+// Two consecutive splats: both alphas first (they do not depend on the pixel's state), then the two composite steps in order -
+// the same operations on the same operands as two composite_one calls, with the second splat's LDS reads and exponentials in
+// the shadow of the first's.  For waves that walk alone (the deep pass's units): they are bound by the latency of one splat's
+// dependent chain (~400 cycles per splat against 132 of VALU issue), not by issue slots.
+template <bool DEPTH>
+__device__ __forceinline__ void composite_two(const LdsSplat* sp, const LdsSplat* sp1, const QuadLane<DEPTH>& ql, Px& px, BlendProf& prof) {
+    Alpha a0, a1;
+    alpha_of(sp, ql, a0, prof);
+    alpha_of(sp1, ql, a1, prof);
+    apply_alpha(px, a0);
+    apply_alpha(px, a1);
+}
+
+// The second level of the chunked composite: chunk partials {C_c, T_c} merged near -> far.  The fold of a single chunk is exact
+// (fma(1, C, 0) = C, 1 * T = T).  It stops after the first chunk that leaves no pixel of the quadrant with T > 1e-4.
+struct Folded {
+    float C[4][3], T[4];
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int g = 0; g < 4; g++) { T[g] = 1.0f; C[g][0] = 0.0f; C[g][1] = 0.0f; C[g][2] = 0.0f; }
+    }
+    __device__ __forceinline__ void add_rgb(int g, const float4 p) {
+        C[g][0] = __builtin_fmaf(T[g], p.x, C[g][0]);
+        C[g][1] = __builtin_fmaf(T[g], p.y, C[g][1]);
+        C[g][2] = __builtin_fmaf(T[g], p.z, C[g][2]);
+    }
+    __device__ __forceinline__ void merge(int g, const float4 p) { add_rgb(g, p); T[g] = __fmul_rn(T[g], p.w); }
+    // p.w = the product INCLUDING this chunk (bin_body's pool)
+    __device__ __forceinline__ void merge_cum(int g, const float4 p) { add_rgb(g, p); T[g] = p.w; }
+    __device__ __forceinline__ bool open() const {
+        const float tmax = fmaxf(fmaxf(T[0], T[1]), fmaxf(T[2], T[3]));
+        return __ballot(tmax > GS_T_EPS) != 0ull;
+    }
+};
+
+// an RGBA8 word (r in the low byte) as channel values k / 255
+__device__ __forceinline__ float4 unpack_rgba8(uint32_t d) {
+    return make_float4((float)(d & 255u) * (1.0f / 255.0f), (float)((d >> 8) & 255u) * (1.0f / 255.0f),
+                       (float)((d >> 16) & 255u) * (1.0f / 255.0f), (float)(d >> 24) * (1.0f / 255.0f));
+}
+// ... and back, as the draws round a frame: clamp, then x 255 + 0.5 as ONE fma (no pragma here: both callers always contracted it).
+// k_rop8_window keeps the oracle's unfused mul, add under its own pragma, so it does not share this.
+__device__ __forceinline__ uint32_t pack_rgba8(float r, float g, float b, float a) {
+    auto u8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
+    return u8(r) | (u8(g) << 8) | (u8(b) << 16) | (u8(a) << 24);
+}
+
+// dst_rgba (nullable): the colour the splats are blended over (gs_mesh_set_destination), the WHOLE frame's RGBA8 rows.  Back to
+// front NormalBlending over dst leaves rgb = C + T * dst.rgb, alpha = (1 - T) + T * dst.a (C, T = the splats' own composite).
+__device__ __forceinline__ void write_pixels(uint32_t* __restrict__ out, uint32_t width, uint32_t y0, uint32_t y1, uint32_t px, uint32_t py0,
+                                             const Folded& f, const uint32_t* __restrict__ dst_rgba = nullptr) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const uint32_t py = py0 + 4u * g;
+        if (px < width && py >= y0 && py < y1) {
+            float a = 1.0f - f.T[g];
+            float cr = f.C[g][0], cg = f.C[g][1], cb = f.C[g][2];
+            if (dst_rgba) {
+                const float4 d = unpack_rgba8(dst_rgba[(size_t)py * width + px]);
+                cr = __builtin_fmaf(f.T[g], d.x, cr);
+                cg = __builtin_fmaf(f.T[g], d.y, cg);
+                cb = __builtin_fmaf(f.T[g], d.z, cb);
+                a = __builtin_fmaf(f.T[g], d.w, a);
+            }
+            out[(size_t)(py - y0) * width + px] = pack_rgba8(cr, cg, cb, a);
+        }
+    }
+}
+
+struct DeepArgs {
+    uint32_t* flags;            // gs_mesh::deep_flags (GS_FLAG_*)
+    uint32_t* ent;              // [GS_DEEP_MAX_BINS][GS_DEEP_LIST_CAP]
+    uint32_t* cnt;              // [GS_DEEP_MAX_BINS][GS_DEEP_RANGES][4]
+    float4* partial;            // [GS_DEEP_UNITS][256]
+    uint32_t* work;             // [GS_DEEP_UNITS]: d << 7 | c << 2 | q of the units that exist (k_deep_plan)
+    float4* pool;               // [pool_slots][256]
+    uint32_t pool_slots;        // GS_POOL_SLOTS (tests shrink it: $GSPLAT_POOL_SLOTS)
+    uint32_t unit_wgs;          // workgroups of (bin, quadrant, chunk) units behind the per-bin workgroups (0: no deep pass)
+    uint32_t unit_at;           // ... sit at blockIdx [unit_at, unit_at + unit_wgs): behind the unit_at costliest bins' workgroups
+};
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // one workgroup per bin
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -411,33 +436,18 @@ __device__ __forceinline__ void bin_body(const FrameArgs& fa, const DeepArgs& da
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));     // wave-uniform, and known to be
     const uint32_t bx = bg.bx, by = bg.by, begin = bg.begin, n = bg.n;
-    const uint32_t px = bx * GS_BIN + (wave & 1u) * GS_TILE + (lane & 15u);
-    const uint32_t py0 = by * GS_BIN + (wave >> 1) * GS_TILE + (lane >> 4);
-    // pixel centres relative to the bin's origin (what the staged splats are expressed in)
-    const float bin_x0 = (float)(bx * GS_BIN), bin_y0 = (float)(by * GS_BIN);
-    const float fx = (float)((wave & 1u) * GS_TILE + (lane & 15u)) + 0.5f;
-    const float fy0 = (float)((wave >> 1) * GS_TILE + (lane >> 4)) + 0.5f;
-    const v2f fy[2] = {{fy0, fy0 + 4.0f}, {fy0 + 8.0f, fy0 + 12.0f}};
-    v2f dz[2] = {{GS_HUGE, GS_HUGE}, {GS_HUGE, GS_HUGE}};
-    if (DEPTH) load_dst_depth(fa, px, py0, dz);
+    const QuadLane<DEPTH> ql(fa, bg, wave, lane);
 
-#ifdef GS_BLEND_PROFILE
-    const unsigned long long t_start = wall_clock64();
-    uint32_t batches = 0;
-#endif
     uint32_t walked = 0, scanned = 0;                  // statistics: wave-uniform, kept in scalar registers
     uint32_t since_check = 0;                          // splats composited since the last saturation test (never reset by a batch
                                                        // or group boundary - see the test)
     uint32_t in_chunk = 0, closed = 0;                 // composited in the open chunk (counted at the tests); chunks closed
     bool can_close = true;                             // (false once the partial pool ran out)
     uint32_t my_slot = 0;                              // lane c: the pool slot of closed chunk c
-    uint32_t p_kept = 0, p_useful = 0;
-#ifdef GS_BLEND_PROFILE
-    uint32_t p_blk[4] = {0u, 0u, 0u, 0u}, p_iters = 0, p_blocks = 0;
-#endif
     bool live_wave = bg.live(fa, wave);
     Px acc;
     acc.reset();
+    BlendProf prof(acc);
 
     // entry payload = record slot (k_bin_emit); the slot also names the splat's tile rect, which says whether and where the
     // splat touches THIS bin - most entries of a 128-px list do not, and only the others are expanded into LDS.
@@ -463,19 +473,15 @@ __device__ __forceinline__ void bin_body(const FrameArgs& fa, const DeepArgs& da
     }
     for (uint32_t base = 0; base < n; base += BLEND_THREADS) {
         const uint32_t cnt = min((uint32_t)BLEND_THREADS, n - base);
-#ifdef GS_BLEND_PROFILE
-        batches++;
-#endif
+        prof.batch();
         scanned += cnt;
         __syncthreads();                               // previous batch fully consumed, s_live read by everyone
+        // (rect mask, exact test, expansion: k_deep_scan and the ROP8 draw spell the same three calls out.  One helper for the three
+        // sites was built and cost instructions here - 5 to 13 per kernel - or loaded the ROP8 draw's records twice: not kept.)
         uint32_t qm = tid < cnt ? quadrant_mask(rect, bx, by) : 0u;
-        if (GS_BLEND_EXACT && qm) qm = exact_quadrants(qm, lo, hi, bx, by);
-#ifdef GS_BLEND_PROFILE
-        s_qmask[tid] = qm ? qm | (block_mask16(lo, hi, bx, by) << 8) : 0u;
-#else
+        if (qm) qm = exact_quadrants(qm, lo, hi, bx, by);
         s_qmask[tid] = qm;
-#endif
-        if (qm) stage_entry(&s_batch[tid], lo, hi, bin_x0, bin_y0, zs);
+        if (qm) stage_entry(&s_batch[tid], lo, hi, bx, by, zs);
         if (tid == 0) *s_live = 0u;
         // prefetch while this batch is blended
         rect = fa.rects[v_next];
@@ -492,29 +498,7 @@ __device__ __forceinline__ void bin_body(const FrameArgs& fa, const DeepArgs& da
                     const uint32_t j = g0 + (uint32_t)__builtin_ctzll(m);
                     m &= m - 1ull;
                     walked++;
-#ifdef GS_BLEND_PROFILE
-                    {   // what a walk by 8x8 blocks would cost: the four 16-lane groups of the wave each walk the survivors of their
-                        // own block, in step between two saturation tests -> iterations = the longest of the four lists per interval
-                        const uint32_t bm = ((uint32_t)__builtin_amdgcn_readfirstlane((int)s_qmask[j]) >> (8u + 4u * wave)) & 15u;
-                        p_blk[0] += bm & 1u; p_blk[1] += (bm >> 1) & 1u; p_blk[2] += (bm >> 2) & 1u; p_blk[3] += (bm >> 3) & 1u;
-                        p_blocks += (uint32_t)__popc(bm);
-                        if (((since_check + 1u) % GS_BLEND_CHECK) == 0u) {
-                            p_iters += max(max(p_blk[0], p_blk[1]), max(p_blk[2], p_blk[3]));
-                            p_blk[0] = p_blk[1] = p_blk[2] = p_blk[3] = 0u;
-                        }
-                    }
-#endif
-#if GS_BLEND_PAIRS
-                    // (two splats in flight when the next survivor of the group does not straddle a saturation test: A/B knob)
-                    if (m && !(since_check & 1u)) {
-                        const uint32_t j1 = g0 + (uint32_t)__builtin_ctzll(m);
-                        m &= m - 1ull;
-                        walked++;
-                        since_check++;
-                        composite_two<DEPTH>(&s_batch[j], &s_batch[j1], fx, fy, dz, acc, p_kept, p_useful);
-                    } else
-#endif
-                    composite_one<DEPTH>(&s_batch[j], fx, fy, dz, acc, p_kept, p_useful);
+                    composite_one(&s_batch[j], ql, acc, prof);
                     // Retire the wave when the open chunk has saturated its whole quadrant (every T <= 1e-4; everything behind is
                     // then multiplied by <= 1e-4).  Tested after every GS_BLEND_CHECK-th splat of the chunk and nowhere else, so a
                     // chunk composites exactly the first K of its own ordered survivors (K = the first multiple of GS_BLEND_CHECK at
@@ -580,36 +564,7 @@ __device__ __forceinline__ void bin_body(const FrameArgs& fa, const DeepArgs& da
         // turns every counter of these loops into a VGPR and every branch into exec-mask bookkeeping)
         if (__builtin_amdgcn_readfirstlane((int)*s_live) == 0) break;   // every quadrant saturated (or clipped): skip the rest of the list
     }
-#ifdef GS_BLEND_PROFILE
-    __shared__ unsigned int s_prof[5];
-    if (tid < 5u) s_prof[tid] = 0u;
-    __syncthreads();
-    if (lane == 0u) {
-        atomicAdd(&s_prof[0], p_kept);
-        atomicAdd(&s_prof[1], p_useful);
-        atomicAdd(&s_prof[2], 2u * walked);
-        atomicAdd(&s_prof[3], p_iters + max(max(p_blk[0], p_blk[1]), max(p_blk[2], p_blk[3])));
-        atomicAdd(&s_prof[4], p_blocks);
-    }
-    if (bin < BLEND_PROF_BINS && lane == 0u) {
-        if (wave == 0u) {
-            g_blend_prof[BLEND_PROF_WORDS * bin + 0] = t_start;
-            g_blend_prof[BLEND_PROF_WORDS * bin + 2] = n;
-            g_blend_prof[BLEND_PROF_WORDS * bin + 3] = batches;
-        }
-        g_blend_prof[BLEND_PROF_WORDS * bin + 4 + wave] = walked;
-    }
-    __syncthreads();
-    if (bin < BLEND_PROF_BINS && tid == 0u) {
-        g_blend_prof[BLEND_PROF_WORDS * bin + 1] = wall_clock64();
-        g_blend_prof[BLEND_PROF_WORDS * bin + 8] = 128ull * s_prof[2];
-        g_blend_prof[BLEND_PROF_WORDS * bin + 9] = s_prof[0];
-        g_blend_prof[BLEND_PROF_WORDS * bin + 10] = s_prof[1];
-        g_blend_prof[BLEND_PROF_WORDS * bin + 11] = s_prof[2];
-        g_blend_prof[BLEND_PROF_WORDS * bin + 12] = s_prof[3];
-        g_blend_prof[BLEND_PROF_WORDS * bin + 13] = s_prof[4];
-    }
-#endif
+    prof.bin_done(bin, n, wave, walked);
     // statistics: one plain 8-byte store per workgroup, summed by the host when somebody asks (8160 same-address atomics
     // at the end of the kernel cost 60 us: a device-scope counter retires ~88 atomics per microsecond)
     // {entries scanned, half quadrants evaluated (2 per pair)} per bin (the blend's cost: what orders the next draw's workgroups,
@@ -641,7 +596,7 @@ __device__ __forceinline__ void bin_body(const FrameArgs& fa, const DeepArgs& da
             for (int g = 0; g < 4; g++) f.merge(g, acc.get(g));
         }
     }
-    write_pixels(fa.out, fa.width, fa.y0, fa.y1, px, py0, f, fa.dst_rgba);
+    write_pixels(fa.out, fa.width, fa.y0, fa.y1, ql.px, ql.py0, f, fa.dst_rgba);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -689,7 +644,7 @@ __global__ __launch_bounds__(256) void k_deep_scan(FrameArgs fa, DeepArgs da) {
             if (pos < bg.n) {
                 const uint32_t slot = fa.vals[bg.begin + pos];
                 qm = quadrant_mask(fa.rects[slot], bg.bx, bg.by);
-                if (GS_BLEND_EXACT && qm) qm = exact_quadrants(qm, fa.recs[2 * (size_t)slot], fa.recs[2 * (size_t)slot + 1], bg.bx, bg.by);
+                if (qm) qm = exact_quadrants(qm, fa.recs[2 * (size_t)slot], fa.recs[2 * (size_t)slot + 1], bg.bx, bg.by);
                 da.ent[(size_t)d * GS_DEEP_LIST_CAP + pos] = slot | (qm << 28);
             }
 #pragma unroll
@@ -812,18 +767,14 @@ __device__ __forceinline__ void deep_unit_one(const FrameArgs& fa, const DeepArg
     uint32_t skip = first - before;                                         // survivors of that range in front of the chunk
     const uint32_t limit = c == GS_CHUNKS_MAX - 1u ? 0xFFFFFFFFu : gs_chunk_size(c);   // the last chunk takes the rest
 
-    const float bin_x0 = (float)(bg.bx * GS_BIN), bin_y0 = (float)(bg.by * GS_BIN);
-    const float fx = (float)((q & 1u) * GS_TILE + (lane & 15u)) + 0.5f;
-    const float fy0 = (float)((q >> 1) * GS_TILE + (lane >> 4)) + 0.5f;
-    const v2f fy[2] = {{fy0, fy0 + 4.0f}, {fy0 + 8.0f, fy0 + 12.0f}};
-    v2f dz[2] = {{GS_HUGE, GS_HUGE}, {GS_HUGE, GS_HUGE}};
-    if (DEPTH) load_dst_depth(fa, bg.bx * GS_BIN + (q & 1u) * GS_TILE + (lane & 15u), bg.by * GS_BIN + (q >> 1) * GS_TILE + (lane >> 4), dz);
+    const QuadLane<DEPTH> ql(fa, bg, q, lane);
     LdsSplat* mine = s_batch + 64u * wave;                                  // this wave's quarter of the batch buffer
     uint32_t* qs = s_queue + 128u * wave;                                   // slots of survivors found but not yet composited
     const uint32_t* ent = da.ent + (size_t)d * GS_DEEP_LIST_CAP;
     Px acc;
     acc.reset();
-    uint32_t done = 0, since_check = 0, p_kept = 0, p_useful = 0;
+    BlendProf prof(acc);
+    uint32_t done = 0, since_check = 0;
     uint32_t pend = 0, queued = 0;                                          // in the queue; found so far (<= limit)
     bool open = true;
     // The scan reads GS_SCAN_AHEAD windows of 64 entry words at a time and asks for the next group before it looks at this one: a
@@ -874,7 +825,7 @@ __device__ __forceinline__ void deep_unit_one(const FrameArgs& fa, const DeepArg
         __builtin_amdgcn_wave_barrier();
         if (lane < k) {
             const uint32_t slot = qs[lane];
-            stage_entry(&mine[lane], fa.recs[2 * (size_t)slot], fa.recs[2 * (size_t)slot + 1], bin_x0, bin_y0, DEPTH ? fa.zrec[slot] : 0.0f);
+            stage_entry(&mine[lane], fa.recs[2 * (size_t)slot], fa.recs[2 * (size_t)slot + 1], bg.bx, bg.by, DEPTH ? fa.zrec[slot] : 0.0f);
         }
         const uint32_t carry = lane < rem ? qs[64u + lane] : 0u;           // what is left moves to the front of the queue
         __builtin_amdgcn_wave_barrier();
@@ -884,23 +835,19 @@ __device__ __forceinline__ void deep_unit_one(const FrameArgs& fa, const DeepArg
         __builtin_amdgcn_wave_barrier();
         uint32_t jj = 0;
         if ((since_check & 1u) && k) {                                      // (pairs never straddle a saturation test)
-            composite_one<DEPTH>(&mine[0], fx, fy, dz, acc, p_kept, p_useful);
+            composite_one(&mine[0], ql, acc, prof);
             jj = 1; done++;
-            if (++since_check == GS_BLEND_CHECK) { since_check = 0; if (!acc.open()) open = false; }
+            open = still_open(acc, since_check, 1u);
         }
         for (; jj + 1u < k && open; jj += 2u) {
-            composite_two<DEPTH>(&mine[jj], &mine[jj + 1u], fx, fy, dz, acc, p_kept, p_useful);
+            composite_two(&mine[jj], &mine[jj + 1u], ql, acc, prof);
             done += 2u;
-            since_check += 2u;
-            if (since_check == GS_BLEND_CHECK) {                            // the per-bin kernel's stop rule
-                since_check = 0;
-                if (!acc.open()) open = false;
-            }
+            open = still_open(acc, since_check, 2u);
         }
         if (jj < k && open) {
-            composite_one<DEPTH>(&mine[jj], fx, fy, dz, acc, p_kept, p_useful);
+            composite_one(&mine[jj], ql, acc, prof);
             done++;
-            if (++since_check == GS_BLEND_CHECK) { since_check = 0; if (!acc.open()) open = false; }
+            open = still_open(acc, since_check, 1u);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -929,17 +876,12 @@ __global__ __launch_bounds__(BLEND_THREADS, BLEND_OCC) void k_tile_blend(FrameAr
     __shared__ uint32_t s_live;
     __shared__ uint32_t s_walked[4];
     __shared__ uint32_t s_queue[512];                  // (deep units: 128 pending survivor slots per wave)
-#ifdef GS_AB_NO_DEEP_UNIT            // (A/B: the per-bin kernel alone)
-    if (blockIdx.x < bins) bin_body<DEPTH>(fa, da, blockIdx.x, s_batch, s_qmask, &s_live, s_walked);
-    (void)s_queue;
-#else
     const uint32_t b = blockIdx.x, at = min(da.unit_at, bins);
     if (b >= at && b < at + da.unit_wgs) {
         deep_unit<DEPTH>(fa, da, s_batch, s_queue);
     } else {
         bin_body<DEPTH>(fa, da, b < at ? b : b - da.unit_wgs, s_batch, s_qmask, &s_live, s_walked);
     }
-#endif
 }
 
 __global__ __launch_bounds__(BLEND_THREADS) void k_deep_fold(FrameArgs fa, DeepArgs da) {
@@ -962,7 +904,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_deep_fold(FrameArgs fa, DeepA
         for (int g = 0; g < 4; g++) f.merge(g, part[64 * g]);
         open = f.open();
     }
-    write_pixels(fa.out, fa.width, fa.y0, fa.y1, bg.bx * GS_BIN + (q & 1u) * GS_TILE + (lane & 15u), bg.by * GS_BIN + (q >> 1) * GS_TILE + (lane >> 4), f, fa.dst_rgba);
+    const QuadLane<false> ql(fa, bg, q, lane);                              // (its pixels only: nothing here reads a depth)
+    write_pixels(fa.out, fa.width, fa.y0, fa.y1, ql.px, ql.py0, f, fa.dst_rgba);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -976,23 +919,21 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_deep_fold(FrameArgs fa, DeepA
 //     rgb = a * src + (1 - a) * rgb ;  alpha = a + (1 - a) * alpha ;  every channel -> floor(clamp01(v) * 255 + 0.5) / 255
 // after every splat - oracle/raster_oracle.c's rop8 mode.  A verification path (gs_mesh_debug_rop8), not a draw mode: a thread
 // walks its whole list.
-__global__ __launch_bounds__(256) void k_rop8_window(FrameArgs fa, uint32_t wx0, uint32_t wy0, uint32_t ww, uint32_t wh, uint32_t height,
-                                                      uint32_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_rop8_window(FrameArgs fa, uint32_t wx0, uint32_t wy0, uint32_t ww, uint32_t wh, uint32_t* __restrict__ out) {
 #pragma clang fp contract(off)
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= ww * wh) return;
     const uint32_t px = wx0 + t % ww, py = wy0 + t / ww;
     float r = 0.0f, g = 0.0f, b = 0.0f, al = 0.0f;
-    if (px < fa.width && py < height && py >= fa.y0 && py < fa.y1) {
+    if (px < fa.width && py < fa.height && py >= fa.y0 && py < fa.y1) {
         float dzp = GS_HUGE;                                  // the destination (gs_mesh_set_destination): stored depth and colour
         if (fa.dst_depth) {
             dzp = fa.dst_depth[(size_t)py * fa.width + px];
             if (fa.depth_mode == 2u) dzp = (float)floor((double)dzp * 16777215.0 + 0.5);
         }
         if (fa.dst_rgba) {
-            const uint32_t d = fa.dst_rgba[(size_t)py * fa.width + px];
-            r = (float)(d & 255u) * (1.0f / 255.0f); g = (float)((d >> 8) & 255u) * (1.0f / 255.0f);
-            b = (float)((d >> 16) & 255u) * (1.0f / 255.0f); al = (float)(d >> 24) * (1.0f / 255.0f);
+            const float4 d = unpack_rgba8(fa.dst_rgba[(size_t)py * fa.width + px]);
+            r = d.x; g = d.y; b = d.z; al = d.w;
         }
         const uint32_t tx = px / GS_TILE, ty = py / GS_TILE;
         const uint32_t lx = tx >> fa.list_shift, ly = (ty >> fa.list_shift) - fa.list_row_begin;
@@ -1023,7 +964,7 @@ __global__ __launch_bounds__(256) void k_rop8_window(FrameArgs fa, uint32_t wx0,
             }
         }
     }
-    auto u8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
+    auto u8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };   // (not pack_rgba8: unfused here, as q8)
     out[t] = u8(r) | (u8(g) << 8) | (u8(b) << 16) | (u8(al) << 24);
 }
 
@@ -1044,25 +985,17 @@ __global__ __launch_bounds__(256) void k_rop8_window(FrameArgs fa, uint32_t wx0,
 struct Rop8Px {                                  // a lane's 4 pixels, channel values k / 255 held as floats (packed pairs as in Px)
     v2f r[2], g[2], b[2], a[2];
 };
-__device__ __forceinline__ v2f q8_pair(v2f v) {
-#pragma clang fp contract(off)
-    const v2f c = __builtin_elementwise_min(__builtin_elementwise_max(v, v2f{0.0f, 0.0f}), v2f{1.0f, 1.0f});
-    const v2f t = c * v2f{255.0f, 255.0f} + v2f{0.5f, 0.5f};
-    return v2f{floorf(t.x), floorf(t.y)} * v2f{1.0f / 255.0f, 1.0f / 255.0f};
-}
-// How the update is evaluated (GS_ROP8_FUSED; same box, tests/test_gpu_crops.py's `rop8_mode` numbers, profiles/r06z_rop8_arith_ab.txt):
-//   0  the oracle's operation order, no contraction: mul, mul, add, max, min, mul, add, 2 x floor, mul = 10 VALU slots per channel
+// How the update is evaluated (same box, tests/test_gpu_crops.py's `rop8_mode` numbers, profiles/r06z_rop8_arith_ab.txt).  Three forms
+// were built behind a build option (last in 5fc96ee), and only this one is left:
+//   -  the oracle's operation order, no contraction: mul, mul, add, max, min, mul, add, 2 x floor, mul = 10 VALU slots per channel
 //      and pixel pair;
-//   1  (default) fused multiply-adds: (1 - a) c + (a src) rounded once with the clamp as the instruction's modifier, x 255 + 0.5 as
-//      one more fma = 6 slots.  Equal to the ROP-emulating oracle exactly as often as 0 (C3 full walk 0.99847 of the channel values
-//      at the worst window / 0.99920 in the mean, both ways; C2 0.99994, C3T 0.99890 / 0.99936 vs 0.99937), never more than 1 apart
-//      - the differences to the oracle come from the alphas (v_exp_f32 against expf), not from this rounding - and C3 bounded
+//   -  (this one) fused multiply-adds: (1 - a) c + (a src) rounded once with the clamp as the instruction's modifier, x 255 + 0.5 as
+//      one more fma = 6 slots.  Equal to the ROP-emulating oracle exactly as often as the first (C3 full walk 0.99847 of the channel
+//      values at the worst window / 0.99920 in the mean, both ways; C2 0.99994, C3T 0.99890 / 0.99936 vs 0.99937), never more than 1
+//      apart - the differences to the oracle come from the alphas (v_exp_f32 against expf), not from this rounding - and C3 bounded
 //      0.422 -> 0.375 ms per frame, the full walk 3.50 -> 2.62, C2 0.80 -> 0.69 / 2.14 -> 1.60;
-//   2  channel values held as 0 .. 255 (no clamp, no final scaling: 5 slots): another 2 % (bounded) / 6 % (full), equality 0.99854 /
+//   -  channel values held as 0 .. 255 (no clamp, no final scaling: 5 slots): another 2 % (bounded) / 6 % (full), equality 0.99854 /
 //      0.99982 / 0.99878 at C3 / C2 / C3T - not the same population of differing values, so not taken.
-#ifndef GS_ROP8_FUSED
-#define GS_ROP8_FUSED 1
-#endif
 __device__ __forceinline__ v2f q8_pair_fused(v2f c01) {
     const v2f t = fma2(c01, v2f{255.0f, 255.0f}, v2f{0.5f, 0.5f});
     return v2f{floorf(t.x), floorf(t.y)} * v2f{1.0f / 255.0f, 1.0f / 255.0f};
@@ -1073,39 +1006,18 @@ __device__ __forceinline__ v2f pk_fma_sat_vvv(v2f a, v2f b, v2f c) {
     return d;
 }
 template <bool DEPTH>
-__device__ __forceinline__ void composite_rop8(const LdsSplat* sp, float fx, const v2f (&fy)[2], const v2f (&dz)[2], Rop8Px& px) {
+__device__ __forceinline__ void composite_rop8(const LdsSplat* sp, const QuadLane<DEPTH>& ql, Rop8Px& px) {
 #pragma clang fp contract(off)
     Alpha al;
-    uint32_t dummy0 = 0, dummy1 = 0;
-    Px unused;                                   // (alpha_of reads the pixel state only in the profile build)
-    unused.reset();
-    alpha_of<DEPTH>(sp, fx, fy, dz, unused, al, dummy0, dummy1);
+    BlendProf none;
+    alpha_of(sp, ql, al, none);
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const v2f a = al.a[h], om = v2f{1.0f, 1.0f} - a;
-#if GS_ROP8_FUSED == 2
-        // channel values held as k (0 .. 255), the splat's colour x 255: k' = floor((1 - a) k + a s255 + 0.5); a convex combination
-        // of values in [0, 255] needs no clamp
-        const v2f half = {0.5f, 0.5f};
-        auto q = [&](v2f c, float s255) {
-            const v2f t = fma2(om, c, a * v2f{s255, s255}) + half;
-            return v2f{floorf(t.x), floorf(t.y)};
-        };
-        px.r[h] = q(px.r[h], al.r * 255.0f);
-        px.g[h] = q(px.g[h], al.g * 255.0f);
-        px.b[h] = q(px.b[h], al.b * 255.0f);
-        px.a[h] = q(px.a[h], 255.0f);
-#elif GS_ROP8_FUSED
         px.r[h] = q8_pair_fused(pk_fma_sat_vvv(om, px.r[h], a * v2f{al.r, al.r}));
         px.g[h] = q8_pair_fused(pk_fma_sat_vvv(om, px.g[h], a * v2f{al.g, al.g}));
         px.b[h] = q8_pair_fused(pk_fma_sat_vvv(om, px.b[h], a * v2f{al.b, al.b}));
         px.a[h] = q8_pair_fused(pk_fma_sat_vvv(om, px.a[h], a));
-#else
-        px.r[h] = q8_pair(a * v2f{al.r, al.r} + om * px.r[h]);
-        px.g[h] = q8_pair(a * v2f{al.g, al.g} + om * px.g[h]);
-        px.b[h] = q8_pair(a * v2f{al.b, al.b} + om * px.b[h]);
-        px.a[h] = q8_pair(a + om * px.a[h]);
-#endif
     }
 }
 // GS_DRAW_ROP8 is BOUNDED (the default of the mode): back to front over the splats IN FRONT OF THE QUADRANT'S SATURATION DEPTH only.
@@ -1130,13 +1042,7 @@ __device__ __forceinline__ void composite_rop8(const LdsSplat* sp, float fx, con
 // 95.4 % of C3T's channel values equal, two steps apart at worst; C3 and C2 passed).  Pass 1 counts a fragment only from alpha >=
 // 1 / 64 on - where a (s - c) spans several steps and a difference between two backgrounds survives the rounding with probability
 // ~(1 - a) - so translucent content is simply walked whole.
-#ifndef GS_ROP8_T_EPS_CFG
-#define GS_ROP8_T_EPS_CFG 1e-6f
-#endif
-#ifndef GS_ROP8_A_MIN_CFG
-#define GS_ROP8_A_MIN_CFG (1.0f / 64.0f)
-#endif
-constexpr float GS_ROP8_T_EPS = GS_ROP8_T_EPS_CFG, GS_ROP8_A_MIN = GS_ROP8_A_MIN_CFG;
+constexpr float GS_ROP8_T_EPS = 1e-6f, GS_ROP8_A_MIN = 1.0f / 64.0f;
 // (7 / 8 workgroups per CU instead of 6 - 72 / 64 VGPRs, a handful of spilled dwords - were measured: C2 bounded 0.80 -> 0.81 / 0.82 ms)
 template <bool DEPTH, bool BOUNDED>
 __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa, uint32_t bins) {
@@ -1149,14 +1055,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t bx = bg.bx, by = bg.by, begin = bg.begin, n = bg.n;
-    const uint32_t px = bx * GS_BIN + (wave & 1u) * GS_TILE + (lane & 15u);
-    const uint32_t py0 = by * GS_BIN + (wave >> 1) * GS_TILE + (lane >> 4);
-    const float bin_x0 = (float)(bx * GS_BIN), bin_y0 = (float)(by * GS_BIN);
-    const float fx = (float)((wave & 1u) * GS_TILE + (lane & 15u)) + 0.5f;
-    const float fy0 = (float)((wave >> 1) * GS_TILE + (lane >> 4)) + 0.5f;
-    const v2f fy[2] = {{fy0, fy0 + 4.0f}, {fy0 + 8.0f, fy0 + 12.0f}};
-    v2f dz[2] = {{GS_HUGE, GS_HUGE}, {GS_HUGE, GS_HUGE}};
-    if (DEPTH) load_dst_depth(fa, px, py0, dz);
+    const QuadLane<DEPTH> ql(fa, bg, wave, lane);
+    const uint32_t px = ql.px, py0 = ql.py0;
     const bool live_wave = bg.live(fa, wave);
     const uint32_t batches = (n + BLEND_THREADS - 1u) / BLEND_THREADS;
     // one batch of <= 256 entries -> LDS, exactly as the fp32 draw stages it (between two barriers of the caller)
@@ -1165,12 +1065,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
         uint32_t qm = 0;
         if (tid < cnt) {
             const uint32_t slot = fa.vals[begin + base + tid];
-            const uint2 rect = fa.rects[slot];
-            qm = quadrant_mask(rect, bx, by);
+            qm = quadrant_mask(fa.rects[slot], bx, by);
             if (qm) {
                 const uint4 lo = fa.recs[2 * (size_t)slot], hi = fa.recs[2 * (size_t)slot + 1];
-                if (GS_BLEND_EXACT) qm = exact_quadrants(qm, lo, hi, bx, by);
-                if (qm) stage_entry(&s_batch[tid], lo, hi, bin_x0, bin_y0, DEPTH ? fa.zrec[slot] : 0.0f);
+                qm = exact_quadrants(qm, lo, hi, bx, by);
+                if (qm) stage_entry(&s_batch[tid], lo, hi, bx, by, DEPTH ? fa.zrec[slot] : 0.0f);
             }
         }
         s_qmask[tid] = qm;
@@ -1199,10 +1098,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
                         m &= m - 1ull;
                         taken++;
                         Alpha al;
-                        uint32_t d0 = 0, d1 = 0;
-                        Px unused;
-                        unused.reset();
-                        alpha_of<DEPTH>(&s_batch[g0 + jl], fx, fy, dz, unused, al, d0, d1);
+                        BlendProf none;
+                        alpha_of(&s_batch[g0 + jl], ql, al, none);
 #pragma unroll
                         for (int h = 0; h < 2; h++) {                      // (a faint fragment hides nothing from an 8-bit target: see above)
                             const v2f a = {al.a[h].x >= GS_ROP8_A_MIN ? al.a[h].x : 0.0f, al.a[h].y >= GS_ROP8_A_MIN ? al.a[h].y : 0.0f};
@@ -1232,11 +1129,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
         const uint32_t py = py0 + 4u * g;
         uint32_t d = 0u;
         if (fa.dst_rgba && px < fa.width && py < fa.height) d = fa.dst_rgba[(size_t)py * fa.width + px];
-        constexpr float unit = GS_ROP8_FUSED == 2 ? 1.0f : 1.0f / 255.0f;
-        acc.r[g >> 1][g & 1] = (float)(d & 255u) * unit;
-        acc.g[g >> 1][g & 1] = (float)((d >> 8) & 255u) * unit;
-        acc.b[g >> 1][g & 1] = (float)((d >> 16) & 255u) * unit;
-        acc.a[g >> 1][g & 1] = (float)(d >> 24) * unit;
+        const float4 c = unpack_rgba8(d);
+        acc.r[g >> 1][g & 1] = c.x; acc.g[g >> 1][g & 1] = c.y; acc.b[g >> 1][g & 1] = c.z; acc.a[g >> 1][g & 1] = c.w;
     }
     uint32_t walked = 0;
     // pass 2 (the only pass of the full walk): back to front, every channel rounded after every splat
@@ -1269,7 +1163,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
                 const uint32_t jl = 63u - (uint32_t)__builtin_clzll(m);           // the farthest survivor left
                 m &= ~(1ull << jl);
                 walked++;
-                composite_rop8<DEPTH>(&s_batch[64u * k + jl], fx, fy, dz, acc);
+                composite_rop8(&s_batch[64u * k + jl], ql, acc);
             }
         }
     }
@@ -1284,34 +1178,32 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
     for (int g = 0; g < 4; g++) {
         const uint32_t py = py0 + 4u * g;
         if (px < fa.width && py >= fa.y0 && py < fa.y1) {
-            auto u8 = [](float v) { return GS_ROP8_FUSED == 2 ? (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f) : (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-            fa.out[(size_t)(py - fa.y0) * fa.width + px] = u8(acc.r[g >> 1][g & 1]) | (u8(acc.g[g >> 1][g & 1]) << 8) |
-                                                           (u8(acc.b[g >> 1][g & 1]) << 16) | (u8(acc.a[g >> 1][g & 1]) << 24);
+            fa.out[(size_t)(py - fa.y0) * fa.width + px] = pack_rgba8(acc.r[g >> 1][g & 1], acc.g[g >> 1][g & 1], acc.b[g >> 1][g & 1], acc.a[g >> 1][g & 1]);
         }
     }
 }
 
-// the destination of a draw as the kernels see it (pp.depth_mode was derived from the same fields: mesh_params)
-static void frame_destination(FrameArgs& fa, const gs_mesh* m, const ProjectParams& pp) {
-    fa.depth_mode = pp.depth_mode;
-    fa.height = (uint32_t)pp.height;
-    fa.zrec = pp.depth_mode ? m->zrec.as<float>() : nullptr;
-    fa.dst_depth = pp.depth_mode ? m->dest_depth : nullptr;
-    fa.dst_rgba = m->dest_rgba;
-}
-
-int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev) {
+// what every kernel here reads of a draw: the lists and records of the last binning, the frame's and the strip's geometry, and the
+// destination as the kernels see it (pp.depth_mode was derived from the same fields: mesh_params)
+static FrameArgs frame_args(const gs_mesh* m, const ProjectParams& pp) {
     FrameArgs fa = {};
-    frame_destination(fa, m, pp);
     fa.ranges = m->tile_ranges.as<uint2>();
     fa.vals = (m->sorted_buf ? m->evalB : m->evalA).as<uint32_t>();
     fa.recs = m->recs.as<uint4>();
     fa.rects = m->rects.as<uint2>();
-    fa.width = (uint32_t)pp.width; fa.y0 = pp.y0; fa.y1 = pp.y1;
+    fa.width = (uint32_t)pp.width; fa.height = (uint32_t)pp.height; fa.y0 = pp.y0; fa.y1 = pp.y1;
     fa.bins_x = pp.bins_x; fa.bin_row_begin = pp.bin_row_begin;
-    fa.lists_x = pp.lists_x; fa.list_row_begin = pp.list_row_begin; fa.list_shift = pp.list_shift - 0u;
-    // (list_shift here counts 16-px tiles per list bin edge, as in the binner: a list bin is (16 << list_shift) px)
-    hipLaunchKernelGGL(k_rop8_window, dim3((w * h + 255u) / 256u), dim3(256), 0, m->ctx->stream, fa, x0, y0, w, h, (uint32_t)pp.height, out_dev);
+    // (list_shift counts 16-px tiles per list bin edge, as in the binner: a list bin is (16 << list_shift) px)
+    fa.lists_x = pp.lists_x; fa.list_row_begin = pp.list_row_begin; fa.list_shift = pp.list_shift;
+    fa.depth_mode = pp.depth_mode;
+    fa.zrec = pp.depth_mode ? m->zrec.as<float>() : nullptr;
+    fa.dst_depth = pp.depth_mode ? m->dest_depth : nullptr;
+    fa.dst_rgba = m->dest_rgba;
+    return fa;
+}
+
+int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev) {
+    hipLaunchKernelGGL(k_rop8_window, dim3((w * h + 255u) / 256u), dim3(256), 0, m->ctx->stream, frame_args(m, pp), x0, y0, w, h, out_dev);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -1322,19 +1214,11 @@ int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev) {
     GS_TRY(m->blend_stats.ensure((size_t)bins * 12));     // uint2 [bins] {scanned, halves} | uint32 [bins] pairs
     m->blend_bins = bins;
     hipStream_t st = m->ctx->stream;
-    FrameArgs fa;
-    fa.ranges = m->tile_ranges.as<uint2>();
-    fa.vals = (m->sorted_buf ? m->evalB : m->evalA).as<uint32_t>();
-    fa.recs = m->recs.as<uint4>();
-    fa.rects = m->rects.as<uint2>();
+    FrameArgs fa = frame_args(m, pp);
     fa.out = reinterpret_cast<uint32_t*>(out_dev);
-    fa.width = (uint32_t)pp.width; fa.y0 = pp.y0; fa.y1 = pp.y1;
-    fa.bins_x = pp.bins_x; fa.bin_row_begin = pp.bin_row_begin;
-    fa.lists_x = pp.lists_x; fa.list_row_begin = pp.list_row_begin; fa.list_shift = pp.list_shift;
     fa.bin_stats = m->blend_stats.as<uint2>();
     fa.bin_pairs = m->blend_stats.as<uint32_t>() + 2 * (size_t)bins;
     fa.bin_order = m->blend_order_valid ? m->blend_order.as<uint32_t>() : nullptr;
-    frame_destination(fa, m, pp);
     // (the buffers were sized and the flag words reset by the binner's launches: gs_launch_binning)
     DeepArgs da;
     da.flags = m->deep_flags.as<uint32_t>();
@@ -1372,11 +1256,9 @@ int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev) {
     if (getenv("GSPLAT_DEEP_UNIT_WGS") && m->deep_pass)
         da.unit_wgs = std::max(1u, std::min<uint32_t>((uint32_t)atoi(getenv("GSPLAT_DEEP_UNIT_WGS")), (uint32_t)m->ctx->cu_count * BLEND_OCC));
     if (m->draw_mode != GS_DRAW_FP32) {                    // the reference's RGBA8 target, splat by splat (no deep pass: nothing to schedule)
-        const bool full = m->draw_mode == GS_DRAW_ROP8_FULL;
-        if (fa.depth_mode && full) hipLaunchKernelGGL((k_tile_blend_rop8<true, false>), dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
-        else if (fa.depth_mode) hipLaunchKernelGGL((k_tile_blend_rop8<true, true>), dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
-        else if (full) hipLaunchKernelGGL((k_tile_blend_rop8<false, false>), dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
-        else hipLaunchKernelGGL((k_tile_blend_rop8<false, true>), dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
+        static void (*const rop8[2][2])(FrameArgs, uint32_t) = {                // [DEPTH][BOUNDED]
+            {k_tile_blend_rop8<false, false>, k_tile_blend_rop8<false, true>}, {k_tile_blend_rop8<true, false>, k_tile_blend_rop8<true, true>}};
+        hipLaunchKernelGGL(rop8[fa.depth_mode != 0u][m->draw_mode != GS_DRAW_ROP8_FULL], dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
         m->blend_stats_mode = m->draw_mode;                // (a later fp32 draw neither orders its bins nor picks deep bins from these)
         m->blend_row_begin = pp.bin_row_begin;
         m->blend_width = (uint32_t)pp.width;

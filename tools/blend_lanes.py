@@ -14,7 +14,7 @@ import numpy as np
 
 from gaussiansplats3d_amd import Context, SplatMesh, _lib, camera, create_sort_worker, scenes, util
 
-WORDS, MAX_BINS = 14, 40960
+WORDS, MAX_BINS = 12, 40960
 
 
 def measure(ctx, lib, name, scene=None):
@@ -43,10 +43,6 @@ def measure(ctx, lib, name, scene=None):
            "lanes_kept_frac": round(kept / max(ev, 1), 4), "lanes_useful_frac": round(useful / max(ev, 1), 4),
            # what the same draw evaluated before halves could be skipped: 256 lanes per (splat, quadrant) pair
            "lanes_kept_frac_of_whole_quadrants": round(kept / max(256 * pairs, 1), 4),
-           # a walk by 8x8 blocks (four 16-lane groups of a wave on their own block's survivors, in step between two saturation
-           # tests): iterations it would take per (splat, quadrant) pair walked today, and blocks a pair reaches (of 4)
-           "block_walk_iterations": int(buf[:, 12].sum()), "block_walk_iterations_per_pair": round(int(buf[:, 12].sum()) / max(pairs, 1), 4),
-           "blocks_per_pair": round(int(buf[:, 13].sum()) / max(pairs, 1), 4),
            "bins_sampled": bins, "entries_scanned": int(st.entries_scanned)}
     w.terminate()
     mesh.dispose()
