@@ -47,6 +47,27 @@ class SplatAsset:
         out.update(cov=cov32, cov_f16=cov16, sh_f16=sh16, sh_u8=sh8, scales=sc, rotations=ro)
         return out
 
+    def upload_to(self, mesh, frm=0, first=0, count=None, minimum_alpha=1):
+        """Decode splats [first, first + count) on the device into splats [frm, frm + count) of ``mesh``
+        (gs_mesh_upload_asset): what ``fill()`` + ``SplatMesh.build`` / ``update_data`` of the range leave, without the
+        decoded arrays ever existing on the host."""
+        count = self.info.splat_count - first if count is None else count
+        L.check(self.lib.gs_mesh_upload_asset(mesh.handle, int(frm), self.handle, int(first), int(count), int(minimum_alpha)))
+        mesh.splat_count = max(mesh.splat_count, int(frm) + int(count))
+
+    def upload_centers_to(self, sorter, frm=0, first=0, count=None, scene_indexes=None):
+        """The sort worker's ``centers`` message for the same range, derived on the device
+        (gs_sorter_upload_asset_centers): integer or float centres as the worker was created."""
+        count = self.info.splat_count - first if count is None else count
+        scene = None
+        if sorter.dynamic_mode:
+            scene = np.ascontiguousarray(scene_indexes, dtype=np.uint32).reshape(-1)
+            if scene.size != count:
+                raise ValueError("scene_indexes must hold one index per splat of the range")
+        L.check(self.lib.gs_sorter_upload_asset_centers(sorter.handle, int(frm), self.handle, int(first), int(count),
+                                                        scene.ctypes.data if scene is not None else None))
+        sorter.uploaded_splat_count = max(sorter.uploaded_splat_count, int(frm) + int(count))
+
     def close(self):
         if self.handle:
             self.lib.gs_asset_close(self.handle)
@@ -113,51 +134,62 @@ def write_ksplat(centers, scales, rotations_wxyz, rgba, sh_rows=None, sh_degree=
     partial_lengths = []
     bucket_centers = np.zeros((0, 3), np.float32)
     scale_range = 32767
-    if lvl >= 1:
-        mn = c64.min(axis=0) if n else np.zeros(3)
-        dims = (c64.max(axis=0) - mn) if n else np.zeros(3)
+    if lvl >= 1 and n:
+        mn = c64.min(axis=0)
+        dims = c64.max(axis=0) - mn
         yb, zb = int(np.ceil(dims[1] / block_size)), int(np.ceil(dims[2] / block_size))
         blk = np.floor((c64 - mn) / block_size).astype(np.int64)
         ids = blk[:, 0] * (yb * zb) + blk[:, 1] * zb + blk[:, 2]
-        open_b, fulls, centers_of = {}, [], {}
-        for i in range(n):
-            b = open_b.setdefault(int(ids[i]), [])
-            if not b:
-                centers_of[id(b)] = blk[i] * block_size + mn + block_size / 2.0
-            b.append(i)
-            if len(b) >= bucket_size:
-                fulls.append(b)
-                del open_b[int(ids[i])]
-        # for (bucketId in obj): integer-like keys enumerate in ascending numeric order
-        partial = [open_b[k] for k in sorted(open_b)]
-        blist = fulls + partial
-        full, partial_lengths, n_buckets = len(fulls), [len(b) for b in partial], len(blist)
-        order = np.array([i for b in blist for i in b], dtype=np.int64)
-        bucket_centers = np.array([centers_of[id(b)] for b in blist], np.float64).reshape(-1, 3)
-        bucket_of = np.repeat(np.arange(n_buckets), [len(b) for b in blist])
+        # A block's splats fill its open bucket in input order; a bucket that reaches bucket_size is closed.  Full buckets are
+        # listed in the order they closed, then the open ones by block id (`for (bucketId in obj)`: ascending integer keys).
+        by_block = np.argsort(ids, kind="stable")
+        sid = ids[by_block]
+        starts = np.flatnonzero(np.r_[True, sid[1:] != sid[:-1]])
+        counts = np.diff(np.r_[starts, n])
+        rank = np.arange(n) - np.repeat(starts, counts)                     # position of a splat inside its block
+        chunk = rank // bucket_size
+        is_full = (chunk + 1) * bucket_size <= np.repeat(counts, counts)
+        first_of = np.flatnonzero(rank % bucket_size == 0)                  # (in by_block order) first splat of every bucket
+        lengths = np.diff(np.r_[first_of, n])
+        full_b = is_full[first_of]
+        closed_at = by_block[first_of + lengths - 1]                        # input index of the splat that closed the bucket
+        key = np.where(full_b, closed_at, n + sid[first_of])               # fulls by closing time, then partials by block id
+        blist = np.argsort(key, kind="stable")
+        full, n_buckets = int(full_b.sum()), len(first_of)
+        partial_lengths = lengths[blist][full:].tolist()
+        pos = np.repeat(first_of[blist], lengths[blist]) + (np.arange(n) - np.repeat(np.cumsum(lengths[blist]) - lengths[blist],
+                                                                                    lengths[blist]))
+        order = by_block[pos].astype(np.int64)
+        bucket_centers = blk[by_block[first_of[blist]]] * block_size + mn + block_size / 2.0
+        bucket_of = np.repeat(np.arange(n_buckets), lengths[blist])
         buckets_meta = np.array(partial_lengths, np.uint32).tobytes() + bucket_centers.astype(np.float32).tobytes()
-    rows = bytearray()
     q = rotations_wxyz.astype(np.float64)
     q = q / np.linalg.norm(q, axis=1, keepdims=True)                       # tempRot.normalize()
     sf = scale_range / (block_size * 0.5)
-    for k, i in enumerate(order):
+    table = np.zeros((n, bps), np.uint8)
+    put = lambda col, a: table.__setitem__((slice(None), slice(col, col + a.shape[1] * a.itemsize)),              # noqa: E731
+                                           np.ascontiguousarray(a).view(np.uint8).reshape(n, -1)) if n else None
+    if lvl == 0:
+        put(0, c64[order].astype(np.float32))
+        put(12, np.asarray(scales, np.float64)[order].astype(np.float32))
+        put(24, q[order].astype(np.float32))
+    elif n:
+        d = c64[order] - bucket_centers[bucket_of]                                              # bucketCenterDelta (doubles)
+        put(0, np.clip(np.floor(d * sf + 0.5) + scale_range, 0, scale_range * 2 + 1).astype(np.uint16))   # Math.round
+        put(6, to_half_three(np.asarray(scales)[order]))
+        put(12, to_half_three(q[order]))
+    col = [40, 20, 20][lvl]
+    put(col, np.asarray(rgba, np.uint8).reshape(n, 4)[order])
+    if ncomp:
+        s = np.asarray(sh_rows, np.float64).reshape(n, ncomp)[order]
         if lvl == 0:
-            rows += np.asarray(c64[i], np.float32).tobytes() + np.asarray(scales[i], np.float32).tobytes()
-            rows += np.asarray(q[i], np.float32).tobytes()
+            put(col + 4, s.astype(np.float32))
+        elif lvl == 1:
+            put(col + 4, to_half_three(s))
         else:
-            d = c64[i] - bucket_centers[bucket_of[k]]                                          # bucketCenterDelta (doubles)
-            v = np.clip(np.floor(d * sf + 0.5) + scale_range, 0, scale_range * 2 + 1)       # Math.round
-            rows += v.astype(np.uint16).tobytes() + to_half_three(scales[i]).tobytes() + to_half_three(q[i]).tobytes()
-        rows += np.asarray(rgba[i], np.uint8).tobytes()
-        if ncomp:
-            s = np.asarray(sh_rows[i], np.float64)
-            if lvl == 0:
-                rows += s.astype(np.float32).tobytes()
-            elif lvl == 1:
-                rows += to_half_three(s).tobytes()
-            else:
-                lo, hi = sh_range
-                rows += np.clip(np.floor((np.clip(s, lo, hi) - lo) / (hi - lo) * 255), 0, 255).astype(np.uint8).tobytes()
+            lo, hi = sh_range
+            put(col + 4, np.clip(np.floor((np.clip(s, lo, hi) - lo) / (hi - lo) * 255), 0, 255).astype(np.uint8))
+    rows = table.tobytes()
     header = bytearray(4096)
     header[0:2] = bytes([0, 1])
     struct.pack_into("<IIII", header, 4, 1, 1, n, n)

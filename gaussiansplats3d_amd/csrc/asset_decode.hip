@@ -1,0 +1,289 @@
+// asset_decode.hip — the per-splat decode of an opened .ksplat / PLY image on the device: file rows -> the staging layout a
+// mesh upload commits (gs_mesh_upload_asset) and the sorter's `centers` message (gs_sorter_upload_asset_centers).
+// The arithmetic is gs_asset_fill's (assets.hip), expression for expression, in fp64 and unfused (this file is built with
+// -ffp-contract=off): only multiplies, adds and double -> float conversions are involved, so the planes are bit-equal to what
+// gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.  Restates, never copies:
+//   bucket of a splat / centre   /root/reference/src/loaders/SplatBuffer.js:199-246
+//   covariance                   SplatBuffer.js:440-486, 517-549 (three.js Matrix3/4 arithmetic in double)
+//   colour, SH order             SplatBuffer.js:551-575, 577-734 (no scene transform)
+//   integer centres              /root/reference/src/splatmesh/SplatMesh.js:1912-1948
+// Header and section parsing stay host code (assets.hip); the device sees a section table and searches it per splat.
+#include <algorithm>
+
+#include "asset_internal.hpp"
+
+namespace {
+
+struct DevSection {
+    long long data_off;        // byte offset of the section's row 0 in the device image (negative when the range starts inside the
+                               // section: rows before the range are not uploaded)
+    long long buckets_off;     // ... of its bucket centres
+    uint32_t count_offset, count;
+    uint32_t bytes_per_splat, bucket_size, full_buckets, bucket_count, bucket_storage, scale_range;
+    uint32_t partial_begin, partial_count;   // its slice of the cumulative partial_end list behind the sections
+    double scale_factor;
+};
+
+struct AssetView {             // kernel argument: the staged image
+    const uint8_t* image;
+    const DevSection* sections;
+    const uint32_t* partial_end;
+    uint32_t section_count, level, sh_degree, ncomp;
+};
+
+template <class T>
+__device__ __forceinline__ T ld(const uint8_t* p) {            // rows have no alignment (33 bytes per splat at level 2, SH 1)
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+
+// dataViewFloatForCompressionLevel for scale / rotation (never the 8-bit SH rule)
+__device__ __forceinline__ double comp(uint32_t level, const uint8_t* row, uint32_t index) {
+    if (level == 0) return (double)ld<float>(row + 4 * index);
+    return from_half(ld<uint16_t>(row + 2 * index));
+}
+
+// the section of splat i: the last one that begins at or before it (the table holds the non-empty sections of the range in order)
+__device__ __forceinline__ const DevSection& section_of(const AssetView& v, uint32_t i) {
+    uint32_t lo = 0, hi = v.section_count;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (v.sections[mid].count_offset <= i) lo = mid;
+        else hi = mid;
+    }
+    return v.sections[lo];
+}
+
+// SplatBuffer.js:199-219: full buckets first, then the partial ones by their stored lengths (std::upper_bound of the host)
+__device__ __forceinline__ uint32_t bucket_index(const AssetView& v, const DevSection& sec, uint32_t local) {
+    const uint32_t full_span = sec.full_buckets * sec.bucket_size;
+    if (local < full_span) return local / sec.bucket_size;
+    const uint32_t* pe = v.partial_end + sec.partial_begin;
+    uint32_t lo = 0, hi = sec.partial_count;                    // first partial bucket whose end is > local
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pe[mid] <= local) lo = mid + 1;
+        else hi = mid;
+    }
+    const uint32_t b = sec.full_buckets + lo;
+    return b < sec.bucket_count ? b : sec.bucket_count - 1u;    // never past the table
+}
+
+// getSplatCenter (SplatBuffer.js:221-246), narrowed to float as fillSplatCenterArray stores it
+__device__ __forceinline__ void decode_centre(const AssetView& v, const DevSection& sec, uint32_t local, const uint8_t* row, float c[3]) {
+    if (v.level == 0) {
+        for (int k = 0; k < 3; k++) c[k] = ld<float>(row + 4 * k);
+        return;
+    }
+    const uint8_t* bucket = v.image + sec.buckets_off + (size_t)sec.bucket_storage * bucket_index(v, sec, local);
+    for (int k = 0; k < 3; k++) {
+        const double x = ld<uint16_t>(row + 2 * k);
+        const double bc = ld<float>(bucket + 4 * k);
+        c[k] = (float)((x - (double)sec.scale_range) * sec.scale_factor + bc);
+    }
+}
+
+// One thread per splat: asset splat first + i -> element i of the staging arrays (MeshStaging).
+__global__ __launch_bounds__(256) void k_asset_decode(AssetView v, uint32_t first, uint32_t count, uint32_t min_alpha, float* __restrict__ centers,
+                                                      float* __restrict__ cov_f32, uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
+                                                      uint16_t* __restrict__ sh_f16, uint8_t* __restrict__ sh_u8) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const DevSection& sec = section_of(v, first + i);
+    const uint32_t local = first + i - sec.count_offset;
+    const uint8_t* row = v.image + sec.data_off + (long long)sec.bytes_per_splat * local;
+    float c[3];
+    decode_centre(v, sec, local, row, c);
+    for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = c[k];
+
+    const uint8_t* srow = row + asset_center_bytes(v.level);
+    {
+        const double sx = comp(v.level, srow, 0), sy = comp(v.level, srow, 1), sz = comp(v.level, srow, 2);
+        // rotation.set(x = f4, y = f5, z = f6, w = f3): NOT normalised (SplatBuffer.js:539-542)
+        const double w = comp(v.level, srow, 3), x = comp(v.level, srow, 4), y = comp(v.level, srow, 5), z = comp(v.level, srow, 6);
+        // Matrix4.makeRotationFromQuaternion = compose(zero, q, one) (three r160)
+        const double x2 = x + x, y2 = y + y, z2 = z + z;
+        const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
+        const double wx = w * x2, wy = w * y2, wz = w * z2;
+        const double R[3][3] = {{(1 - (yy + zz)) * 1, (xy - wz) * 1, (xz + wy) * 1},
+                                {(xy + wz) * 1, (1 - (xx + zz)) * 1, (yz - wx) * 1},
+                                {(xz - wy) * 1, (yz + wx) * 1, (1 - (xx + yy)) * 1}};
+        // covarianceMatrix = R * S (Matrix3.multiplyMatrices: a_i1*b_1j + a_i2*b_2j + a_i3*b_3j)
+        const double S[3][3] = {{sx, 0, 0}, {0, sy, 0}, {0, 0, sz}};
+        double M[3][3], Cm[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) M[r][q] = R[r][0] * S[0][q] + R[r][1] * S[1][q] + R[r][2] * S[2][q];
+        // transformedCovariance = M * M^T
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) Cm[r][q] = M[r][0] * M[q][0] + M[r][1] * M[q][1] + M[r][2] * M[q][2];
+        const double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            if (cov_f32) cov_f32[6 * (size_t)i + k] = (float)e[k];
+            else cov_f16[6 * (size_t)i + k] = to_half_three(e[k]);
+        }
+    }
+    const uint8_t* crow = srow + asset_center_bytes(v.level) + asset_rotation_bytes(v.level);
+    {   // fillSplatColorArray (SplatBuffer.js:551-575)
+        const uint32_t alpha = crow[3];
+        rgba[i] = (uint32_t)crow[0] | ((uint32_t)crow[1] << 8) | ((uint32_t)crow[2] << 16) | ((alpha >= min_alpha ? alpha : 0u) << 24);
+    }
+    if (v.ncomp) {   // fillSphericalHarmonicsArray, no transform: level 0 through the half rule, level 1 bits, level 2 bytes
+        const uint8_t* hrow = crow + 4;
+        auto emit = [&](uint32_t dst, uint32_t src) {
+            if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = hrow[src];
+            else sh_f16[(size_t)v.ncomp * i + dst] = v.level == 0 ? to_half_three((double)ld<float>(hrow + 4 * src)) : ld<uint16_t>(hrow + 2 * src);
+        };
+        for (uint32_t q = 0; q < 3; q++)                                               // set3FromArray(stride 3, base c)
+            for (uint32_t ch = 0; ch < 3; ch++) emit(3 * q + ch, q + 3 * ch);
+        if (v.sh_degree >= 2)
+            for (uint32_t q = 0; q < 5; q++)                                           // set3FromArray(stride 5, base 9 + c)
+                for (uint32_t ch = 0; ch < 3; ch++) emit(9 + 3 * q + ch, 9 + q + 5 * ch);
+    }
+}
+
+// The sorter's `centers` message of asset splats [first, first + count): padFour AoS, written where a copy from the host would
+// have put it.  integer: Math.round(fp32 centre * 1000.0) as util.integer_centers pins it - floor(v + 0.5) in double - with
+// w = 1000; a NaN or a value outside int32 becomes INT32_MIN (what the host's double -> int32 conversion stores).  Else the float
+// centre with w = 1.0.
+__global__ __launch_bounds__(256) void k_asset_centers(AssetView v, uint32_t first, uint32_t count, int integer, uint4* __restrict__ aos) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const DevSection& sec = section_of(v, first + i);
+    const uint32_t local = first + i - sec.count_offset;
+    float c[3];
+    decode_centre(v, sec, local, v.image + sec.data_off + (long long)sec.bytes_per_splat * local, c);
+    uint32_t o[3];
+    for (int k = 0; k < 3; k++) {
+        if (integer) {
+            const double r = floor((double)c[k] * 1000.0 + 0.5);
+            o[k] = (r >= -2147483648.0 && r < 2147483648.0) ? (uint32_t)(int32_t)r : 0x80000000u;
+        } else {
+            o[k] = __builtin_bit_cast(uint32_t, c[k]);
+        }
+    }
+    aos[i] = make_uint4(o[0], o[1], o[2], integer ? 1000u : __builtin_bit_cast(uint32_t, 1.0f));
+}
+
+// Uploads what the kernels read of splats [first, first + count), count > 0, in range: their rows (one contiguous piece of the
+// file), the bucket tables of their sections and the section table.  Synchronises `st`: the host table is a local.
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, AssetView* view) {
+    const uint32_t last = first + count - 1u;
+    std::vector<DevSection> table;
+    std::vector<uint32_t> partial;
+    std::vector<const AssetSection*> used;
+    for (const AssetSection& sec : a->sections) {
+        if (sec.max_splat_count == 0 || sec.count_offset > last || sec.count_offset + sec.max_splat_count <= first) continue;
+        used.push_back(&sec);
+    }
+    GS_REQUIRE(!used.empty(), "the asset has no section for the range");
+    const AssetSection &sa = *used.front(), &sb = *used.back();
+    const size_t lo = sa.data_base + (size_t)sa.bytes_per_splat * (first - sa.count_offset);
+    const size_t hi = sb.data_base + (size_t)sb.bytes_per_splat * (last - sb.count_offset + 1u);
+    size_t bytes = (hi - lo + 15) & ~(size_t)15;
+    for (const AssetSection* sec : used) {
+        DevSection d = {};
+        d.data_off = (long long)sec->data_base - (long long)lo;
+        d.count_offset = sec->count_offset;
+        d.count = sec->max_splat_count;
+        d.bytes_per_splat = sec->bytes_per_splat;
+        d.bucket_size = sec->bucket_size;
+        d.full_buckets = sec->full_buckets;
+        d.bucket_count = sec->bucket_count;
+        d.bucket_storage = sec->bucket_storage;
+        d.scale_range = sec->scale_range;
+        d.scale_factor = sec->scale_factor;
+        d.partial_begin = (uint32_t)partial.size();
+        d.partial_count = (uint32_t)sec->partial_end.size();
+        partial.insert(partial.end(), sec->partial_end.begin(), sec->partial_end.end());
+        if (a->level > 0) {                                  // bucket tables are only read for compressed centres
+            d.buckets_off = (long long)bytes;
+            bytes += ((size_t)sec->bucket_storage * sec->bucket_count + 15) & ~(size_t)15;
+        }
+        table.push_back(d);
+    }
+    const size_t table_bytes = table.size() * sizeof(DevSection), partial_bytes = partial.size() * 4;
+    GS_TRY(dev.bytes.ensure(bytes));
+    GS_TRY(dev.table.ensure(table_bytes + partial_bytes + 16));
+    uint8_t* image = dev.bytes.as<uint8_t>();
+    GS_HIP(hipMemcpyAsync(image, a->buf.data() + lo, hi - lo, hipMemcpyHostToDevice, st));
+    if (a->level > 0)
+        for (size_t k = 0; k < used.size(); k++)
+            if (used[k]->bucket_count)
+                GS_HIP(hipMemcpyAsync(image + table[k].buckets_off, a->buf.data() + used[k]->buckets_base,
+                                      (size_t)used[k]->bucket_storage * used[k]->bucket_count, hipMemcpyHostToDevice, st));
+    GS_HIP(hipMemcpyAsync(dev.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, st));
+    if (partial_bytes) GS_HIP(hipMemcpyAsync(dev.table.as<char>() + table_bytes, partial.data(), partial_bytes, hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st));
+    view->image = image;
+    view->sections = dev.table.as<DevSection>();
+    view->partial_end = reinterpret_cast<const uint32_t*>(dev.table.as<char>() + table_bytes);
+    view->section_count = (uint32_t)table.size();
+    view->level = a->level;
+    view->sh_degree = a->sh_degree;
+    view->ncomp = sh_components(a->sh_degree);
+    return GS_OK;
+}
+
+// gs_mesh_upload_asset's source: a segment of the staging is filled by k_asset_decode
+struct AssetRows : MeshUploadSource {
+    AssetView view;
+    uint32_t first, min_alpha;
+    int fill(gs_mesh* m, uint32_t o, uint32_t count, const MeshStaging& s, hipStream_t st) override {
+        const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
+        hipLaunchKernelGGL(k_asset_decode, dim3((count + 255u) / 256u), dim3(256), 0, st, view, first + o, count, min_alpha, (float*)s.base,
+                           half ? nullptr : (float*)(s.base + s.off_cov), half ? (uint16_t*)(s.base + s.off_cov) : nullptr,
+                           (uint32_t*)(s.base + s.off_rgba), s.sh_u8 ? nullptr : (uint16_t*)(s.base + s.off_sh),
+                           s.sh_u8 ? (uint8_t*)(s.base + s.off_sh) : nullptr);
+        GS_HIP(hipGetLastError());
+        return GS_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first, uint32_t count, uint32_t min_alpha) {
+    GS_REQUIRE(m && a, "mesh / asset == NULL");
+    GS_REQUIRE((uint64_t)from + count <= m->max_count, "range exceeds max_splat_count");
+    GS_REQUIRE((uint64_t)first + count <= a->splat_count, "range exceeds the asset's splat count");
+    GS_REQUIRE(m->sh_degree == a->sh_degree, "the mesh's SH degree differs from the asset's (gs_asset_info.sh_degree)");
+    const bool mesh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    GS_REQUIRE(m->sh_degree == 0 || mesh_u8 == (a->level == 2),
+               "GS_MESH_SH_U8 must be set exactly for a file whose SH are uint8 (gs_asset_info.sh_level == 2)");
+    if (count == 0) return GS_OK;
+    ScopedDevice sd(m->ctx->device);
+    // (an earlier call's decode kernels have finished: every upload synchronises before it returns)
+    AssetRows src;
+    GS_TRY(asset_stage(a, first, count, m->asset_dev, m->ctx->stream, &src.view));
+    src.first = first;
+    src.min_alpha = min_alpha;
+    src.stages_sh_u8 = mesh_u8;
+    return gs_mesh_upload_from(m, from, count, src);
+}
+
+int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uint32_t first, uint32_t count,
+                                   const uint32_t* scene_indexes) {
+    GS_REQUIRE(s && a, "sorter / asset == NULL");
+    GS_REQUIRE((uint64_t)from + count <= s->max_count, "range exceeds max_splat_count");
+    GS_REQUIRE((uint64_t)first + count <= a->splat_count, "range exceeds the asset's splat count");
+    GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || scene_indexes, "dynamic sorter needs scene_indexes");
+    if (count == 0) return GS_OK;
+    ScopedDevice sd(s->ctx->device);
+    AssetView view;
+    GS_TRY(asset_stage(a, first, count, s->asset_dev, s->stream, &view));
+    hipLaunchKernelGGL(k_asset_centers, dim3((count + 255u) / 256u), dim3(256), 0, s->stream, view, first, count,
+                       (s->flags & GS_SORT_INTEGER) ? 1 : 0, s->caos.as<uint4>() + from);
+    GS_HIP(hipGetLastError());
+    return gs_sorter_commit_centers(s, from, count, scene_indexes);
+}
+
+}  // extern "C"

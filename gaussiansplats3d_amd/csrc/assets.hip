@@ -1,4 +1,4 @@
-// assets.hip — native asset readers (host code only): INRIA-v1 .ply and .ksplat -> the arrays the render / sort seams
+// assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device): INRIA-v1 .ply and .ksplat -> the arrays the render / sort seams
 // consume.  Restates, never copies:
 //   PLY header        /root/reference/src/loaders/ply/PlyParserUtils.js:31-165 (decodeSectionHeader, SH field mapping),
 //                     INRIAV1PlyParser.js:20-47 (fields read)
@@ -16,37 +16,9 @@
 #include <math.h>
 #include <string>
 
-#include "gs_internal.hpp"
+#include "asset_internal.hpp"
 
 namespace {
-
-// THREE.DataUtils.toHalfFloat (three r160): clamp to +-65504, then the base/shift tables: the mantissa is TRUNCATED
-uint16_t to_half_three(double value) {
-    float v = (float)value;
-    if (v > 65504.0f) v = 65504.0f;
-    if (v < -65504.0f) v = -65504.0f;
-    uint32_t f;
-    memcpy(&f, &v, 4);
-    const uint32_t sign = (f >> 16) & 0x8000u;
-    const int e = (int)((f >> 23) & 0xFFu) - 127;
-    const uint32_t m = f & 0x007FFFFFu;
-    uint32_t out;
-    if (e < -24) out = 0;
-    else if (e < -14) out = (0x0400u >> (-e - 14)) + (m >> (-e - 1));
-    else if (e <= 15) out = ((uint32_t)(e + 15) << 10) + (m >> 13);
-    else if (e < 128) out = 0x7C00u;
-    else out = 0x7C00u + (m >> 13);
-    return (uint16_t)(out | sign);
-}
-
-double from_half(uint16_t h) {                         // exact
-    const uint32_t sign = h & 0x8000u, e = (h >> 10) & 31u, m = h & 1023u;
-    double v;
-    if (e == 0) v = ldexp((double)m, -24);
-    else if (e == 31) v = m ? NAN : INFINITY;
-    else v = ldexp((double)(m | 1024u), (int)e - 25);
-    return sign ? -v : v;
-}
 
 // Util.js clamp = Math.max(Math.min(v, hi), lo): JS min / max PROPAGATE NaN (C's fmin / fmax drop it)
 double clampd(double v, double lo, double hi) {
@@ -67,39 +39,10 @@ uint8_t clamped_u8(double v) {                         // Uint8ClampedArray stor
     return (uint8_t)nearbyint(v);
 }
 
-struct Section {
-    uint32_t splat_count, max_splat_count, bucket_size, bucket_count, full_buckets, partial_buckets, sh_degree;
-    uint32_t bytes_per_splat, scale_range;
-    double half_block, scale_factor;
-    size_t base, buckets_base, data_base;
-    uint32_t count_offset;
-    uint32_t bucket_storage;
-    std::vector<uint32_t> partial_end;     // cumulative end (in section-local splats) of every partial bucket
-};
-
+using Section = AssetSection;
 constexpr size_t KS_HEADER = 4096, KS_SECTION_HEADER = 1024;
-const uint32_t CENTER_BYTES[3] = {12, 6, 6}, SCALE_BYTES[3] = {12, 6, 6}, ROT_BYTES[3] = {16, 8, 8}, SH_BYTES_PER[3] = {4, 2, 1};
-uint32_t sh_components(uint32_t degree) { return degree == 0 ? 0u : (degree == 1 ? 9u : 24u); }
-
-}  // namespace
-
-struct gs_asset {
-    std::vector<uint8_t> buf;              // a .ksplat image (for a PLY: the level-0 section built from it)
-    uint32_t level = 0, splat_count = 0, sh_degree = 0;
-    float scene_center[3] = {0, 0, 0};
-    double sh_min = -1.5, sh_max = 1.5;
-    std::vector<Section> sections;
-    std::vector<uint32_t> section_of;      // per splat
-
-    template <class T>
-    T rd(size_t off) const {
-        T v;
-        memcpy(&v, buf.data() + off, sizeof(T));
-        return v;
-    }
-};
-
-namespace {
+constexpr auto &CENTER_BYTES = ASSET_CENTER_BYTES, &SCALE_BYTES = ASSET_SCALE_BYTES, &ROT_BYTES = ASSET_ROT_BYTES,
+               &SH_BYTES_PER = ASSET_SH_BYTES_PER;
 
 int parse_ksplat(gs_asset* a) {
     const size_t n = a->buf.size();

@@ -276,8 +276,15 @@ void gs_tree_view(gs_tree* t, TreeGatherView* v);
 int gs_tree_copy_plain(gs_tree* t, uint32_t* out_dev, hipStream_t st);   // the kept leaves' index lists -> indexesToSort
 void gs_tree_forget_sorter(gs_tree* t, gs_sorter* s);                    // the sorter consumed (or dropped) the pending gather
 
+// An opened asset's bytes as the device decode reads them (asset_decode.hip): the rows of the range being uploaded, the bucket
+// tables of its sections and the section table.  Owned by whatever receives the splats; rewritten by every call.
+struct AssetDeviceImage {
+    DevBuf bytes, table;
+};
+
 struct gs_sorter {
     gs_context* ctx = nullptr;
+    AssetDeviceImage asset_dev;
     uint32_t max_count = 0, flags = 0, precision = 16, uploaded = 0;
     // SoA planes of the AoS x4 centres the worker receives (int32 or float bit patterns)
     DevBuf cx, cy, cz, cw, scene_idx;
@@ -434,6 +441,8 @@ struct gs_mesh {
     bool has_scenes = false;
     uint32_t scene_count = 1;
     DevBuf staging;
+    DevBuf upload_partials;    // CentrePartial per workgroup: bounds and sums of a segment decoded on the device (mesh.hip)
+    AssetDeviceImage asset_dev;
     DevBuf distances;          // uint32 [n]: gs_mesh_compute_distances's result when no sorter receives it (distances.hip)
     // per-draw
     DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
@@ -542,6 +551,26 @@ int gs_selftest_lds_atomic_order(gs_context* ctx, bool* ok);
 // payload maps of a mesh for a bound sorter (nullptr when the mesh keeps upload order or covers fewer splats)
 const uint32_t* gs_mesh_payload_map(gs_mesh* m, uint32_t splats);
 const uint32_t* gs_mesh_payload_unmap(gs_mesh* m);
+
+// One upload into a mesh = per segment "fill the staging" (the source's half) + "commit the staging" (mesh.hip's half: Morton
+// keys, radix passes, permutation, the split kernels, the block boxes).  gs_mesh_upload fills by hipMemcpy from host arrays,
+// gs_mesh_upload_asset (asset_decode.hip) with a decode kernel; everything else of an upload is gs_mesh_upload_from's.
+struct MeshStaging {                       // where a segment's arrays sit in gs_mesh::staging
+    char* base;                            // centres: float [3n]
+    size_t off_cov, off_sh, off_rgba;      // covariance float [6n] or half bits [6n] | SH half bits or uint8 [ncoef n] | rgba uint8 [4n]
+    uint32_t ncoef;                        // SH values per splat the source stages (0: none)
+    bool sh_u8;                            // ... as uint8 (a GS_MESH_SH_U8 mesh whose source stages them), else half bits
+};
+struct MeshUploadSource {
+    const float* host_centers = nullptr;   // the range's centres in host memory; NULL: bounds and scene sums are reduced on the device
+    bool stages_sh_u8 = false;             // fill() also stages the uint8 SH of a GS_MESH_SH_U8 mesh
+    // stage splats [offset, offset + count) of the range on `st`
+    virtual int fill(gs_mesh* m, uint32_t offset, uint32_t count, const MeshStaging& stg, hipStream_t st) = 0;
+    virtual ~MeshUploadSource() = default;
+};
+int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSource& src);
+// what follows the AoS x4 centres of [from, from + count) landing in gs_sorter::caos, on the sorter's stream (sorter.hip)
+int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const uint32_t* scene_indexes);
 
 // kernels' host launchers ---------------------------------------------------------------------------
 // (ev_before / ev_after, nullable, recorded on ctx->aux: around the whole vertex stage - block test, mask memset, k_project - when

@@ -376,35 +376,120 @@ static bool mesh_range_slotted(const gs_mesh* m, uint32_t from, uint32_t count) 
     return false;
 }
 
-// One segment of an upload.  fresh: these splats have no storage slots yet - they get the Morton order of the segment;
-// otherwise they keep the slots an earlier upload gave them (perm stays a bijection, planes uploaded through the other
-// entry points and a bound sorter's resident result stay valid).
-static int mesh_upload_segment(gs_mesh* m, uint32_t from, uint32_t count, const float* centers, const float* cov_f32,
-                               const uint16_t* cov_f16, const uint8_t* rgba, const uint16_t* sh_f16, bool fresh) {
+}  // extern "C"
+
+// Where a segment's arrays sit in gs_mesh::staging (MeshStaging, gs_internal.hpp).  sh_u8: the source stages the uint8 SH of a
+// GS_MESH_SH_U8 mesh too (the host path hands those to gs_mesh_upload_sh_u8 instead).
+static int mesh_staging_layout(gs_mesh* m, uint32_t count, bool sh_u8, MeshStaging* s) {
     const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
-    const bool sh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    const bool mesh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    s->ncoef = (m->sh_degree == 0 || (mesh_u8 && !sh_u8)) ? 0 : (m->sh_degree == 1 ? 9 : 24);
+    s->sh_u8 = mesh_u8 && s->ncoef != 0;
+    const size_t b_c = (size_t)count * 12, b_cov = (size_t)count * (half ? 12 : 24), b_sh = (size_t)count * s->ncoef * (s->sh_u8 ? 1 : 2);
+    s->off_cov = (b_c + 255) & ~(size_t)255;
+    s->off_sh = (s->off_cov + b_cov + 255) & ~(size_t)255;
+    s->off_rgba = (s->off_sh + b_sh + 255) & ~(size_t)255;
+    GS_TRY(m->staging.ensure(s->off_sh + b_sh + 512 + (size_t)count * 4));
+    s->base = m->staging.as<char>();
+    return GS_OK;
+}
+
+// Bounds and sums of a segment's staged centres, for a source that has no host copy of them: one CentrePartial per workgroup.
+// The bounds skip NaN exactly as the host's `v < mn` / `v > mx` tests do and are exact in any order.  The sums are fp64 per
+// thread in index order, then a fixed tree: deterministic, but NOT bit-equal to the host path's serial sum - they feed
+// heuristics only (centre_sum / centre_sq / centre_n: how far a camera moved, in scene radii).
+struct CentrePartial {
+    float mn[3], mx[3];
+    uint32_t n, pad;
+    double s[4];                       // x, y, z, x*x + y*y + z*z
+};
+constexpr uint32_t CENTRE_REDUCE_BLOCKS = 512;
+
+__global__ __launch_bounds__(256) void k_centre_reduce(const float* __restrict__ c3, uint32_t count, CentrePartial* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ CentrePartial s_part[4];
+    CentrePartial p;
+    for (int k = 0; k < 3; k++) { p.mn[k] = INFINITY; p.mx[k] = -INFINITY; }
+    p.n = 0; p.pad = 0;
+    p.s[0] = p.s[1] = p.s[2] = p.s[3] = 0.0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const float c[3] = {c3[3 * (size_t)i], c3[3 * (size_t)i + 1], c3[3 * (size_t)i + 2]};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if (c[k] < p.mn[k]) p.mn[k] = c[k];
+            if (c[k] > p.mx[k]) p.mx[k] = c[k];
+        }
+        const float r2 = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+        if (!(r2 < 1e30f)) continue;                          // NaN / infinite centres draw nothing
+        p.s[0] += c[0]; p.s[1] += c[1]; p.s[2] += c[2]; p.s[3] += r2; p.n++;
+    }
+    auto join = [](CentrePartial& a, const CentrePartial& b) {
+        for (int k = 0; k < 3; k++) {
+            if (b.mn[k] < a.mn[k]) a.mn[k] = b.mn[k];
+            if (b.mx[k] > a.mx[k]) a.mx[k] = b.mx[k];
+        }
+        for (int k = 0; k < 4; k++) a.s[k] += b.s[k];
+        a.n += b.n;
+    };
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        CentrePartial q;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { q.mn[k] = __shfl_xor(p.mn[k], o, 64); q.mx[k] = __shfl_xor(p.mx[k], o, 64); }
+#pragma unroll
+        for (int k = 0; k < 4; k++) q.s[k] = __shfl_xor(p.s[k], o, 64);
+        q.n = __shfl_xor(p.n, o, 64);
+        join(p, q);
+    }
+    if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = p;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (int w = 1; w < 4; w++) join(p, s_part[w]);
+        out[blockIdx.x] = p;
+    }
+}
+
+// The commit half of an upload: what the source's fill left in the staging -> the mesh's planes.  fresh: these splats have no
+// storage slots yet - they get the Morton order of the segment; otherwise they keep the slots an earlier upload gave them (perm
+// stays a bijection, planes uploaded through the other entry points and a bound sorter's resident result stay valid).
+// host_centers: the segment's centres on the host (the Morton bounds are taken from them), or NULL: bounds and the scene's
+// centre sums are reduced on the device.
+static int mesh_commit_segment(gs_mesh* m, uint32_t from, uint32_t count, const MeshStaging& s, const float* host_centers, bool fresh) {
+    const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
     hipStream_t st = m->ctx->stream;
-    const uint32_t ncoef = (m->sh_degree == 0 || sh_u8) ? 0 : (m->sh_degree == 1 ? 9 : 24);
-    const size_t b_c = (size_t)count * 12, b_cov = (size_t)count * (half ? 12 : 24), b_sh = (size_t)count * ncoef * 2;
-    size_t off_cov = (b_c + 255) & ~(size_t)255, off_sh = (off_cov + b_cov + 255) & ~(size_t)255;
-    GS_TRY(m->staging.ensure(off_sh + b_sh + 512 + (size_t)count * 4));
-    char* stg = m->staging.as<char>();
-    GS_HIP(hipMemcpyAsync(stg, centers, b_c, hipMemcpyHostToDevice, st));
-    GS_HIP(hipMemcpyAsync(stg + off_cov, half ? (const void*)cov_f16 : (const void*)cov_f32, b_cov, hipMemcpyHostToDevice, st));
-    if (ncoef) GS_HIP(hipMemcpyAsync(stg + off_sh, sh_f16, b_sh, hipMemcpyHostToDevice, st));
+    char* stg = s.base;
     const dim3 g(up_grid(count)), b(256);
     const uint32_t* perm = m->reorder ? m->perm.as<uint32_t>() : nullptr;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (!host_centers) {
+        const uint32_t blocks = std::min((count + 255u) / 256u, CENTRE_REDUCE_BLOCKS);
+        GS_TRY(m->upload_partials.ensure(sizeof(CentrePartial) * CENTRE_REDUCE_BLOCKS));
+        hipLaunchKernelGGL(k_centre_reduce, dim3(blocks), b, 0, st, (const float*)stg, count, m->upload_partials.as<CentrePartial>());
+        GS_HIP(hipGetLastError());
+        std::vector<CentrePartial> part(blocks);
+        GS_HIP(hipMemcpyAsync(part.data(), m->upload_partials.p, sizeof(CentrePartial) * blocks, hipMemcpyDeviceToHost, st));
+        GS_HIP(hipStreamSynchronize(st));
+        for (const CentrePartial& p : part) {                 // in workgroup order
+            for (int k = 0; k < 3; k++) {
+                if (p.mn[k] < mn[k]) mn[k] = p.mn[k];
+                if (p.mx[k] > mx[k]) mx[k] = p.mx[k];
+                m->centre_sum[k] += p.s[k];
+            }
+            m->centre_sq += p.s[3];
+            m->centre_n += p.n;
+        }
+    }
     if (fresh) m->layout_version++;
     if (m->reorder && fresh) {
-        // Morton order of this segment: bounds on the host (the centres are host memory anyway), 30-bit codes, 4 stable
+        // Morton order of this segment: bounds (on the host when the centres are host memory anyway), 30-bit codes, 4 stable
         // radix passes with the entry ping-pong buffers as scratch, then perm[original] = internal
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < count; i++)
-            for (int k = 0; k < 3; k++) {
-                const float v = centers[3 * (size_t)i + k];
-                if (v < mn[k]) mn[k] = v;
-                if (v > mx[k]) mx[k] = v;
-            }
+        if (host_centers)
+            for (uint32_t i = 0; i < count; i++)
+                for (int k = 0; k < 3; k++) {
+                    const float v = host_centers[3 * (size_t)i + k];
+                    if (v < mn[k]) mn[k] = v;
+                    if (v > mx[k]) mx[k] = v;
+                }
         float3 lo = make_float3(mn[0], mn[1], mn[2]), inv;
         inv.x = mx[0] > mn[0] ? 1.0f / (mx[0] - mn[0]) : 0.0f;
         inv.y = mx[1] > mn[1] ? 1.0f / (mx[1] - mn[1]) : 0.0f;
@@ -422,19 +507,20 @@ static int mesh_upload_segment(gs_mesh* m, uint32_t from, uint32_t count, const 
         }
         hipLaunchKernelGGL(k_perm_from_sorted, g, b, 0, st, vbuf[0], count, from, m->perm.as<uint32_t>(), m->inv_perm.as<uint32_t>());
     }
-    const size_t off_rgba = (off_sh + b_sh + 255) & ~(size_t)255;
-    GS_HIP(hipMemcpyAsync(stg + off_rgba, rgba, (size_t)count * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_scatter_u32, g, b, 0, st, (const uint32_t*)(stg + off_rgba), count, from, perm, m->rgba.as<uint32_t>());
+    hipLaunchKernelGGL(k_scatter_u32, g, b, 0, st, (const uint32_t*)(stg + s.off_rgba), count, from, perm, m->rgba.as<uint32_t>());
     hipLaunchKernelGGL(k_split_centers, g, b, 0, st, (const float*)stg, count, from, perm, m->px.as<float>(), m->py.as<float>(),
                        m->pz.as<float>());
     if (half)
-        hipLaunchKernelGGL(k_split_cov_f16, g, b, 0, st, (const uint16_t*)(stg + off_cov), count, from, perm, m->covA.as<uint2>(),
+        hipLaunchKernelGGL(k_split_cov_f16, g, b, 0, st, (const uint16_t*)(stg + s.off_cov), count, from, perm, m->covA.as<uint2>(),
                            m->covB.as<uint32_t>(), m->cov_bound.as<float>());
     else
-        hipLaunchKernelGGL(k_split_cov_f32, g, b, 0, st, (const float*)(stg + off_cov), count, from, perm, m->covA.as<float4>(),
+        hipLaunchKernelGGL(k_split_cov_f32, g, b, 0, st, (const float*)(stg + s.off_cov), count, from, perm, m->covA.as<float4>(),
                            m->covB.as<float2>(), m->cov_bound.as<float>());
-    if (ncoef)
-        hipLaunchKernelGGL(k_split_sh, g, b, 0, st, (const uint16_t*)(stg + off_sh), count, from, perm, ncoef, m->sh0.as<uint4>(),
+    if (s.ncoef && s.sh_u8)
+        hipLaunchKernelGGL(k_split_sh_u8, g, b, 0, st, (const uint8_t*)(stg + s.off_sh), count, from, perm, s.ncoef, m->sh0.as<uint4>(),
+                           m->sh1.as<uint2>());
+    else if (s.ncoef)
+        hipLaunchKernelGGL(k_split_sh, g, b, 0, st, (const uint16_t*)(stg + s.off_sh), count, from, perm, s.ncoef, m->sh0.as<uint4>(),
                            m->sh1.p, m->sh2.as<uint4>());
     {   // The boxes of the storage blocks this segment touches.  A fresh segment owns the slots [from, from + count); splats
         // uploaded before keep THEIR slots, scattered over the Morton run(s) of the earlier upload(s) - anywhere inside the merged
@@ -457,24 +543,18 @@ static int mesh_upload_segment(gs_mesh* m, uint32_t from, uint32_t count, const 
 // SplatMesh.updateDataTexturesFromBaseData(fromSplat, toSplat) accepts any range, any number of times
 // (/root/reference/src/splatmesh/SplatMesh.js:900-1062).  Splats seen for the first time are stored along the Morton curve
 // of their own contiguous run; splats uploaded before keep their slots and only have their data replaced.
-int gs_mesh_upload(gs_mesh* m, uint32_t from, uint32_t count, const float* centers, const float* cov_f32,
-                   const uint16_t* cov_f16, const uint8_t* rgba, const uint16_t* sh_f16) {
-    GS_REQUIRE(m && centers && rgba, "mesh / centers / rgba == NULL");
-    GS_REQUIRE((uint64_t)from + count <= m->max_count, "range exceeds max_splat_count");
-    const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
-    GS_REQUIRE(half ? (cov_f16 && !cov_f32) : (cov_f32 && !cov_f16), "covariance format does not match the mesh (GS_MESH_COV_HALF)");
-    const bool sh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
-    GS_REQUIRE(m->sh_degree == 0 || sh_u8 || sh_f16, "mesh stores spherical harmonics but sh_f16 == NULL");
-    GS_REQUIRE(!(sh_u8 && sh_f16), "GS_MESH_SH_U8 mesh: upload SH with gs_mesh_upload_sh_u8");
+// One upload, whatever fills the staging (MeshUploadSource): the stream discipline, the fresh / non-fresh segment cuts and the
+// slotted-range bookkeeping are said here once for gs_mesh_upload and gs_mesh_upload_asset.
+int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSource& src) {
     if (count == 0) return GS_OK;
     m->projection_pending = false;                        // the scene changed under a pending gs_mesh_project
     ScopedDevice sd(m->ctx->device);
     // earlier draws may still read the planes / the permutation on either stream
     GS_HIP(hipStreamSynchronize(m->ctx->stream));
     if (m->ctx->aux != m->ctx->stream) GS_HIP(hipStreamSynchronize(m->ctx->aux));
-    const uint32_t ncoef = (m->sh_degree == 0 || sh_u8) ? 0 : (m->sh_degree == 1 ? 9 : 24);
     const uint32_t end = from + count;
-    {   // where the scene is and how large (mean and RMS radius of the centres; a heuristic's inputs: re-uploads count twice)
+    if (const float* centers = src.host_centers) {
+        // where the scene is and how large (mean and RMS radius of the centres; a heuristic's inputs: re-uploads count twice)
         double sx = 0.0, sy = 0.0, sz = 0.0, sq = 0.0;
         uint64_t n = 0;
         for (uint32_t i = 0; i < count; i++) {
@@ -499,9 +579,11 @@ int gs_mesh_upload(gs_mesh* m, uint32_t from, uint32_t count, const float* cente
     if (pos < end) cuts.push_back({pos, true});
     for (size_t k = 0; k < cuts.size(); k++) {
         const uint32_t b = cuts[k].first, e = k + 1 < cuts.size() ? cuts[k + 1].first : end, o = b - from;
-        GS_TRY(mesh_upload_segment(m, b, e - b, centers + 3 * (size_t)o, cov_f32 ? cov_f32 + 6 * (size_t)o : nullptr,
-                                   cov_f16 ? cov_f16 + 6 * (size_t)o : nullptr, rgba + 4 * (size_t)o,
-                                   sh_f16 ? sh_f16 + (size_t)ncoef * o : nullptr, cuts[k].second || !m->reorder));
+        MeshStaging stg;
+        GS_TRY(mesh_staging_layout(m, e - b, src.stages_sh_u8, &stg));
+        GS_TRY(src.fill(m, o, e - b, stg, m->ctx->stream));
+        GS_TRY(mesh_commit_segment(m, b, e - b, stg, src.host_centers ? src.host_centers + 3 * (size_t)o : nullptr,
+                                   cuts[k].second || !m->reorder));
     }
     // merge [from, end) into the slotted ranges
     std::vector<std::pair<uint32_t, uint32_t>> merged;
@@ -515,6 +597,42 @@ int gs_mesh_upload(gs_mesh* m, uint32_t from, uint32_t count, const float* cente
     m->slotted.swap(merged);
     if (end > m->uploaded) m->uploaded = end;
     return GS_OK;
+}
+
+namespace {
+// gs_mesh_upload's source: the arrays fillSplatDataArrays emitted, copied from host memory
+struct HostArrays : MeshUploadSource {
+    const float* cov_f32;
+    const uint16_t* cov_f16;
+    const uint8_t* rgba;
+    const uint16_t* sh_f16;
+    int fill(gs_mesh*, uint32_t o, uint32_t count, const MeshStaging& s, hipStream_t st) override {
+        GS_HIP(hipMemcpyAsync(s.base, host_centers + 3 * (size_t)o, (size_t)count * 12, hipMemcpyHostToDevice, st));
+        if (cov_f16) GS_HIP(hipMemcpyAsync(s.base + s.off_cov, cov_f16 + 6 * (size_t)o, (size_t)count * 12, hipMemcpyHostToDevice, st));
+        else GS_HIP(hipMemcpyAsync(s.base + s.off_cov, cov_f32 + 6 * (size_t)o, (size_t)count * 24, hipMemcpyHostToDevice, st));
+        if (s.ncoef)
+            GS_HIP(hipMemcpyAsync(s.base + s.off_sh, sh_f16 + (size_t)s.ncoef * o, (size_t)count * s.ncoef * 2, hipMemcpyHostToDevice, st));
+        GS_HIP(hipMemcpyAsync(s.base + s.off_rgba, rgba + 4 * (size_t)o, (size_t)count * 4, hipMemcpyHostToDevice, st));
+        return GS_OK;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int gs_mesh_upload(gs_mesh* m, uint32_t from, uint32_t count, const float* centers, const float* cov_f32,
+                   const uint16_t* cov_f16, const uint8_t* rgba, const uint16_t* sh_f16) {
+    GS_REQUIRE(m && centers && rgba, "mesh / centers / rgba == NULL");
+    GS_REQUIRE((uint64_t)from + count <= m->max_count, "range exceeds max_splat_count");
+    const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
+    GS_REQUIRE(half ? (cov_f16 && !cov_f32) : (cov_f32 && !cov_f16), "covariance format does not match the mesh (GS_MESH_COV_HALF)");
+    const bool sh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    GS_REQUIRE(m->sh_degree == 0 || sh_u8 || sh_f16, "mesh stores spherical harmonics but sh_f16 == NULL");
+    GS_REQUIRE(!(sh_u8 && sh_f16), "GS_MESH_SH_U8 mesh: upload SH with gs_mesh_upload_sh_u8");
+    HostArrays src;
+    src.host_centers = centers;
+    src.cov_f32 = cov_f32; src.cov_f16 = cov_f16; src.rgba = rgba; src.sh_f16 = sh_f16;
+    return gs_mesh_upload_from(m, from, count, src);
 }
 
 int gs_mesh_upload_sh_u8(gs_mesh* m, uint32_t from, uint32_t count, const uint8_t* sh_u8) {

@@ -1165,9 +1165,17 @@ int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || scene_indexes, "dynamic sorter needs scene_indexes");
     if (count == 0) return GS_OK;
     ScopedDevice sd(s->ctx->device);
+    GS_HIP(hipMemcpyAsync(s->caos.as<uint4>() + from, centers_aos4, (size_t)count * 16, hipMemcpyHostToDevice, s->stream));
+    return gs_sorter_commit_centers(s, from, count, scene_indexes);
+}
+
+}  // extern "C"
+
+// The AoS x4 centres of [from, from + count) are in `caos` (enqueued on the sorter's stream by a copy from the host or by
+// asset_decode.hip's k_asset_centers): the SoA planes, the scene indexes and the bookkeeping of a `centers` message.
+int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const uint32_t* scene_indexes) {
     hipStream_t st = s->stream;
     uint4* aos = s->caos.as<uint4>() + from;               // kept: index-list sorts gather 16 bytes per splat from it
-    GS_HIP(hipMemcpyAsync(aos, centers_aos4, (size_t)count * 16, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_aos4_to_soa, dim3(grid_for(count, 256, 4096)), dim3(256), 0, st, aos, count,
                        from, s->cx.as<uint32_t>(), s->cy.as<uint32_t>(), s->cz.as<uint32_t>(),
                        (s->flags & GS_SORT_DYNAMIC) ? s->cw.as<uint32_t>() : nullptr);
@@ -1180,6 +1188,8 @@ int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     sorter_tell_mesh(s);                                   // (more centres than the bound mesh holds: no position map, no derived mask)
     return GS_OK;
 }
+
+extern "C" {
 
 int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
     GS_REQUIRE(s != nullptr, "sorter == NULL");

@@ -272,6 +272,25 @@ int gs_mesh_upload(gs_mesh* m, uint32_t from, uint32_t count, const float* cente
  * gs_mesh_upload for such a mesh and call this for the same range). */
 int gs_mesh_upload_sh_u8(gs_mesh* m, uint32_t from, uint32_t count, const uint8_t* sh_u8);
 
+/* Decode splats [first, first+count) of an opened asset on the device and store them as splats
+ * [from, from+count) of the mesh: the result is what gs_asset_fill(a, min_alpha, ...) followed by
+ * gs_mesh_upload (+ gs_mesh_upload_sh_u8 for a level-2 file) of the same range leaves, plane for plane. Replaces
+ * SplatBuffer.fillSplatCenterArray / fillSplatCovarianceArray / fillSplatColorArray / fillSphericalHarmonicsArray
+ * (SplatBuffer.js:440-486, 517-734) + SplatMesh.updateDataTexturesFromBaseData (SplatMesh.js:900-1062) in one call:
+ * the file's rows cross to the device, not the decoded arrays.  GS_ERR_INVALID, and nothing changes, when a range is
+ * out of bounds, the mesh's SH degree differs from gs_asset_info.sh_degree, or GS_MESH_SH_U8 disagrees with
+ * sh_level == 2 for a degree > 0.  GS_MESH_COV_HALF is the mesh's choice; the device narrows with
+ * THREE.DataUtils.toHalfFloat's truncating rule (SplatBuffer.js:469-474). */
+int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first, uint32_t count, uint32_t min_alpha);
+
+/* The `centers` message for the same range, derived on the device: int32 centres x1000 rounded as
+ * SplatMesh.getIntegerCenters does (GS_SORT_INTEGER; SplatMesh.js:1912-1926), or the float centres
+ * (getFloatCenters, :1935-1948), padFour.  scene_indexes as in gs_sorter_upload_centers.  Replaces
+ * SplatBuffer.fillSplatCenterArray + getIntegerCenters / getFloatCenters + the worker's copy
+ * (src/worker/SortWorker.js:84-98).  GS_ERR_INVALID, and nothing changes, when a range is out of bounds. */
+int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uint32_t first, uint32_t count,
+                                   const uint32_t* scene_indexes);
+
 /* Per-splat scene index (sceneIndexesTexture, SplatMesh.js:881-897): needed when more than one scene is loaded. */
 int gs_mesh_upload_scene_indexes(gs_mesh* m, uint32_t from, uint32_t count, const uint32_t* scene_indexes);
 

@@ -136,6 +136,16 @@ class HipSortWorker {
     }
   }
 
+  // HIP-engine extra: the `centers` message of a file's splats, derived on the device from its bytes
+  // (gs_sorter_upload_asset_centers).  Like a `centers` message it must not be posted while a sort is in flight.
+  uploadAssetCenters(bytes, format, maxShDegree, from = 0, first = 0, count = 0xFFFFFFFF, sceneIndexes = null) {
+    if (this._busy) throw new Error('uploadAssetCenters: a sort is in flight');
+    const n = addon.sorterUploadAssetCenters(this.handle, from, bytes, format, maxShDegree, first, count, sceneIndexes);
+    this.centersReceived = true;
+    this.uploadedSplatCount = Math.max(this.uploadedSplatCount, from + n);
+    return n;
+  }
+
   // HIP-engine extras (no counterpart in the reference).  bindMesh: results stay on the device as positions in the mesh's
   // storage order; setVisibilityCull: full sorts keep only what mesh.project() of this frame's camera (and strip) draws
   bindMesh(mesh) { addon.sorterBindMesh(this.handle, mesh ? mesh.handle : null); }
@@ -223,6 +233,13 @@ class SplatMeshHIP {
     addon.meshUpload(this.handle, start, n, centers, cov16 ? null : covariances, cov16, colors, sh16);
     if (this.shDegree && this.sphericalHarmonics8Bit) addon.meshUploadShU8(this.handle, start, n, sphericalHarmonics);   // Uint8Array
     this.splatCount = Math.max(this.splatCount, start + n);
+  }
+  // The same upload straight from a file's bytes, decoded per splat on the device (gs_mesh_upload_asset): format 1 = .ply,
+  // 2 = .ksplat; the mesh's sphericalHarmonicsDegree / sphericalHarmonics8Bit must be the file's.  Returns the splats uploaded.
+  buildFromAsset(bytes, format, start = 0, first = 0, count = 0xFFFFFFFF, minimumAlpha = 1) {
+    const n = addon.meshUploadAsset(this.handle, start, bytes, format, this.shDegree, first, count, minimumAlpha);
+    this.splatCount = Math.max(this.splatCount, start + n);
+    return n;
   }
   // sceneIndexes texture (SplatMesh.js:881-897) and the per-scene uniforms of updateUniforms (:1263-1276):
   // {sceneCount, transforms F32(16n), invCamPos F32(4n) = inverse(transform) * cameraPosition, opacity F32(n), visible U32(n),

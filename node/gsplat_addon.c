@@ -798,6 +798,39 @@ static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* meshUploadAsset(mesh, from, bytes ArrayBuffer|Uint8Array, format 1=ply 2=ksplat, maxShDegree, first, count, minAlpha) -> splats uploaded
+ * sorterUploadAssetCenters(sorter, from, bytes, format, maxShDegree, first, count, sceneIndexes|null) -> splats uploaded
+ * The per-splat decode on the device (gs_mesh_upload_asset / gs_sorter_upload_asset_centers): the file's rows cross to the card, not
+ * the arrays assetLoad returns.  count 0xFFFFFFFF: every splat from `first` on. */
+static napi_value upload_asset(napi_env env, napi_callback_info info, int to_sorter) {
+    ARGS(8)
+    void *data, *sc = NULL;
+    size_t nb, sb = 0;
+    if (!get_bytes(env, argv[2], &data, &nb) || !data) { napi_throw_type_error(env, NULL, "asset bytes"); return NULL; }
+    if (to_sorter && !get_bytes(env, argv[7], &sc, &sb)) { napi_throw_type_error(env, NULL, "sceneIndexes"); return NULL; }
+    gs_asset* a = NULL;
+    int st;
+    LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[3]), get_u32(env, argv[4]), &a));
+    if (st < 0) return throw_gs(env, st);
+    gs_asset_info ai;
+    gs_asset_get_info(a, &ai);
+    const uint32_t from = get_u32(env, argv[1]), first = get_u32(env, argv[5]);
+    uint32_t count = get_u32(env, argv[6]);
+    if (count == 0xFFFFFFFFu) count = first <= ai.splat_count ? ai.splat_count - first : 0;
+    if (sc && sb < (size_t)count * 4) {
+        LOCKED(gs_asset_close(a));
+        napi_throw_range_error(env, NULL, "sceneIndexes shorter than count");
+        return NULL;
+    }
+    if (to_sorter) { LOCKED(st = gs_sorter_upload_asset_centers((gs_sorter*)get_external(env, argv[0]), from, a, first, count, (const uint32_t*)sc)); }
+    else { LOCKED(st = gs_mesh_upload_asset((gs_mesh*)get_external(env, argv[0]), from, a, first, count, get_u32(env, argv[7]))); }
+    LOCKED(gs_asset_close(a));
+    if (st < 0) return throw_gs(env, st);
+    return num(env, count);
+}
+static napi_value MeshUploadAsset(napi_env env, napi_callback_info info) { return upload_asset(env, info, 0); }
+static napi_value SorterUploadAssetCenters(napi_env env, napi_callback_info info) { return upload_asset(env, info, 1); }
+
 /* meshSetDestination(mesh, depth Float32Array(W*H)|null, rgba Uint8Array(4*W*H)|null, width, height, flags): what the following
  * draws are depth-tested against and blended over (gs_mesh_set_destination; SplatMaterial3D.js:72-73, src/Viewer.js:1610-1616,
  * src/DropInViewer.js:34-42).  Both null: back to a cleared target without a depth test. */
@@ -847,6 +880,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
+        {"meshUploadAsset", MeshUploadAsset}, {"sorterUploadAssetCenters", SorterUploadAssetCenters},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -1,0 +1,98 @@
+"""Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
+    python tools/load_time.py [--n 5800000] [--file NAME] [--repeats 5] [--out profiles/<tag>_load_time.txt]
+  host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
+  device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
+The file: $GS_DATA_DIR/<--file> when given, else a seeded level-2 SH-2 .ksplat of --n splats from assets.write_ksplat (the C3
+count by default).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
+alternate.  Prints median and spread (max - min) of both and the bytes each sends over PCIe; the device path passes when its
+median is below the host path's by more than the larger spread."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gaussiansplats3d_amd import Context, SplatMesh, assets, create_sort_worker, util
+from gaussiansplats3d_amd import _lib as L
+
+
+def seeded_file(n):
+    rng = np.random.default_rng(20260921)
+    centers = rng.normal(size=(n, 3)) * 4.0
+    scales = np.exp(rng.normal(-3.6, 0.5, size=(n, 3)))
+    rot = rng.normal(size=(n, 4))
+    rgba = rng.integers(0, 256, size=(n, 4), dtype=np.uint8)
+    sh = rng.normal(0.0, 0.4, size=(n, 24)).astype(np.float32)
+    return assets.write_ksplat(centers, scales, rot, rgba, sh, 2, 2, block_size=5.0, bucket_size=256)[0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=5_800_000)
+    ap.add_argument("--file", default=None)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.file:
+        path = os.path.join(os.environ.get("GS_DATA_DIR", "."), args.file)
+        data, source = open(path, "rb").read(), args.file
+    else:
+        data, source = seeded_file(args.n), f"seeded level-2 SH-2 .ksplat, {args.n} splats"
+    asset = assets.SplatAsset(data, None, 2)
+    info = asset.info
+    n, deg, sh8 = info.splat_count, info.sh_degree, info.sh_level == 2 and info.sh_degree > 0
+    ncoef = {0: 0, 1: 9, 2: 24}[deg]
+    ctx = Context(0)
+
+    def fresh():
+        return SplatMesh(ctx, n, deg, spherical_harmonics_8bit=sh8), create_sort_worker(ctx, n)
+
+    def host(mesh, worker):
+        f = asset.fill(1, False)
+        p = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
+        L.check(mesh.lib.gs_mesh_upload(mesh.handle, 0, n, p(f["centers"]), p(f["cov"]), None, p(f["rgba"]), p(f["sh_f16"])))
+        if f["sh_u8"] is not None:
+            L.check(mesh.lib.gs_mesh_upload_sh_u8(mesh.handle, 0, n, p(f["sh_u8"])))
+        ci = util.integer_centers(f["centers"])
+        L.check(worker.lib.gs_sorter_upload_centers(worker.handle, 0, n, ci.ctypes.data, None))
+
+    def device(mesh, worker):
+        asset.upload_to(mesh)
+        asset.upload_centers_to(worker)
+
+    times = {"host": [], "device": []}
+    for _ in range(args.repeats):
+        for name, path in (("host", host), ("device", device)):
+            mesh, worker = fresh()
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            path(mesh, worker)
+            ctx.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+            worker.terminate()
+            mesh.dispose()
+    rows_bytes = len(data) - 4096 - 1024 * int(np.frombuffer(data[4:8], np.uint32)[0])      # rows + bucket tables of every section
+    pcie = {"host": n * (12 + 24 + 4 + ncoef * (1 if sh8 else 2)) + n * 16, "device": 2 * rows_bytes}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    spread = {k: float(max(v) - min(v)) for k, v in times.items()}
+    lines = [f"load_time: {source}; file {len(data)} bytes, {n} splats, SH degree {deg}, compression level {info.compression_level}; "
+             f"{args.repeats} repeats per path, alternating, fresh mesh + sorter each"]
+    for k in ("host", "device"):
+        lines.append(f"{k:6s} median {med[k]:10.2f} ms  spread {spread[k]:8.2f} ms  PCIe {pcie[k]:12d} bytes ({pcie[k] / n:.1f} B/splat)  "
+                     f"runs " + " ".join(f"{t:.2f}" for t in times[k]))
+    gap, need = med["host"] - med["device"], max(spread.values())
+    lines.append(f"gap {gap:.2f} ms (x{med['host'] / med['device']:.1f}), larger spread {need:.2f} ms: " + ("PASS" if gap > need else "FAIL"))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+    asset.close()
+    ctx.close()
+    return 0 if gap > need else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
