@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256) void k_split_sh(const uint16_t* __restrict__ s
 __global__ __launch_bounds__(256) void k_debug_expand(const unsigned long long* __restrict__ vis_mask, const uint2* __restrict__ vis32, uint32_t count,
                                                       const uint32_t* __restrict__ perm, const uint4* __restrict__ recs,
                                                       const uint2* __restrict__ rects, uint4* __restrict__ out_recs,
-                                                      uint2* __restrict__ out_rects, unsigned long long* __restrict__ out_mask) {
+                                                      uint2* __restrict__ out_rects, unsigned long long* __restrict__ out_mask,
+                                                      uint32_t* __restrict__ out_slots) {
     const uint32_t orig = blockIdx.x * 256u + threadIdx.x;
     const uint32_t i = orig < count ? (perm ? perm[orig] : orig) : 0u;     // internal position of this original splat
     const unsigned long long* mw = vis_mask + ((i >> 8) << 2);
@@ -145,6 +146,7 @@ __global__ __launch_bounds__(256) void k_debug_expand(const unsigned long long* 
         out_recs[2 * (size_t)orig + 1] = vis ? recs[2 * (size_t)slot + 1] : z;
     }
     if (out_rects) out_rects[orig] = vis ? rects[slot] : make_uint2(0xFFFFu, 0u);
+    if (out_slots) out_slots[orig] = vis ? slot : 0xFFFFFFFFu;              // the slot the entry lists name the splat by
 }
 
 // 8-bit SH: 9 or 24 bytes per splat -> one 16-byte plane (+ one 8-byte plane for degree 2)
@@ -263,6 +265,7 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     m->reorder = !(flags & GS_MESH_KEEP_ORDER) && !getenv("GSPLAT_NO_REORDER");
     m->no_block_cull = getenv("GSPLAT_NO_BLOCK_CULL") != nullptr;
     m->no_block_list = getenv("GSPLAT_NO_BLOCK_LIST") != nullptr;
+    m->no_coarse_vis = getenv("GSPLAT_NO_COARSE_VIS") != nullptr;
     m->block_test_always = getenv("GSPLAT_BLOCK_TEST_ALWAYS") != nullptr;
     m->no_deep = getenv("GSPLAT_NO_DEEP") != nullptr;
     if (const char* ls = getenv("GSPLAT_LIST_SHIFT"))
@@ -1128,20 +1131,20 @@ int gs_mesh_set_deep_pass(gs_mesh* m, int enabled) {
 
 int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
     GS_REQUIRE(m && dst, "mesh / dst == NULL");
-    GS_REQUIRE(m->has_draw && (what >= 2 || count <= m->last_count), "no draw / count too large");
+    GS_REQUIRE(m->has_draw && ((what >= 2 && what != 9) || count <= m->last_count), "no draw / count too large");
     ScopedDevice sd(m->ctx->device);
     hipStream_t st = m->ctx->stream;
-    if (what == 0 || what == 1 || what == 3) {
+    if (what == 0 || what == 1 || what == 3 || what == 9) {
         if (count == 0) return GS_OK;
         const uint32_t splats = what == 3 ? (count * 64u < m->last_count ? count * 64u : m->last_count) : count;
-        const size_t bytes = what == 3 ? (size_t)count * 8 : (size_t)count * (what == 0 ? sizeof(SplatRec) : 8);
+        const size_t bytes = what == 3 ? (size_t)count * 8 : (size_t)count * (what == 0 ? sizeof(SplatRec) : what == 9 ? 4 : 8);
         GS_REQUIRE(what != 3 || (size_t)count * 8 <= m->vis_mask.bytes, "count exceeds the mask length");
         GS_TRY(m->staging.ensure(bytes + 64));
         if (what == 3) GS_HIP(hipMemsetAsync(m->staging.p, 0, bytes, st));
         hipLaunchKernelGGL(k_debug_expand, dim3((splats + 255u) / 256u), dim3(256), 0, st, m->vis_mask.as<unsigned long long>(), m->vis32.as<uint2>(), splats,
                            m->reorder ? m->perm.as<uint32_t>() : nullptr, m->recs.as<uint4>(), m->rects.as<uint2>(),
                            what == 0 ? m->staging.as<uint4>() : nullptr, what == 1 ? m->staging.as<uint2>() : nullptr,
-                           what == 3 ? m->staging.as<unsigned long long>() : nullptr);
+                           what == 3 ? m->staging.as<unsigned long long>() : nullptr, what == 9 ? m->staging.as<uint32_t>() : nullptr);
         GS_HIP(hipGetLastError());
         GS_HIP(hipMemcpyAsync(dst, m->staging.p, bytes, hipMemcpyDeviceToHost, st));
     } else if (what == 2) {   // [begin,end) of every tile of the last draw's strip; count = number of tiles
@@ -1177,6 +1180,14 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         if (count > GS_SCHEDULE_WORDS)
             GS_HIP(hipMemcpyAsync(static_cast<uint32_t*>(dst) + GS_SCHEDULE_WORDS, m->blend_order.p, (size_t)(count - GS_SCHEDULE_WORDS) * 4,
                                   hipMemcpyDeviceToHost, st));
+    } else if (what == 8) {   // the entry values of the last draw in list order: the record slots the what = 2 ranges index
+        // (as gs_mesh_debug_rop8: a pending gs_mesh_project has swapped the record sets, the slots would name the other set's records)
+        GS_REQUIRE(!m->projection_pending, "a gs_mesh_project is pending: the entries of the last draw refer to the other record set (draw first)");
+        RenderFrame f;
+        GS_HIP(hipMemcpyAsync(&f, m->frame.p, sizeof(f), hipMemcpyDeviceToHost, st));
+        GS_HIP(hipStreamSynchronize(st));
+        GS_REQUIRE(count <= f.entry_count && count <= m->entry_capacity, "count exceeds the entries of the last draw");
+        if (count) GS_HIP(hipMemcpyAsync(dst, (m->sorted_buf ? m->evalB : m->evalA).p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     } else GS_REQUIRE(false, "unknown debug selector");
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;

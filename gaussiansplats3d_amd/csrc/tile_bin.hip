@@ -186,7 +186,8 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
                                                            uint32_t* __restrict__ digit_total,
                                                            uint2* __restrict__ tile_ranges, uint32_t tiles, uint32_t list_shift,
                                                            uint32_t splat_count, const uint8_t* __restrict__ block_any,
-                                                           uint32_t* __restrict__ deep_flags, uint32_t blend_bins) {
+                                                           uint32_t* __restrict__ deep_flags, uint32_t blend_bins,
+                                                           uint32_t lds_bitmap /* 0: $GSPLAT_NO_COARSE_VIS, the flag bytes themselves */) {
     __shared__ unsigned long long s_w[4];
     // Coarse visibility, one bit per 256-splat storage block, in LDS.  75 % of a scene's splats draw nothing and, stored along
     // a Morton curve, mostly whole blocks of them; an LDS bit test spares those list positions the 8-byte L2 gather of their
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     __shared__ uint32_t s_any[ANY_WORDS];
     BIN_PROF(0, 0, wall_clock64());
     const uint32_t blocks = (splat_count + 255u) >> 8;
-    const bool coarse = block_any != nullptr && blocks <= ANY_WORDS * 32u;
+    const bool coarse = block_any != nullptr && blocks <= ANY_WORDS * 32u && lds_bitmap != 0u;
     if (coarse) {
         for (uint32_t w = threadIdx.x; w < (blocks + 31u) / 32u; w += BIN_THREADS) {
             const uint4* src = reinterpret_cast<const uint4*>(block_any + 32u * w);      // the buffer is padded to 64 bytes
@@ -619,7 +620,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     RenderFrame* __restrict__ frame, uint32_t capacity, uint32_t tiles_x /* list bins per row */, uint32_t row_begin /* first list-bin row */,
     KeyT* __restrict__ keys_out, uint32_t* __restrict__ vals_out, volatile uint32_t* __restrict__ mirror, uint32_t serial,
     const uint2* prev_blend_stats, uint32_t* __restrict__ blend_order, uint32_t deep, uint32_t* blend_stats_w,
-    uint32_t deep_min, uint32_t deep_factor, BinScan scan, StatShift sh) {
+    uint32_t deep_min, uint32_t deep_factor, BinScan scan, StatShift sh, uint32_t lds_bitmap) {
     __shared__ unsigned long long s_w[4];
     __shared__ uint32_t s_any[ANY_WORDS];
     __shared__ uint32_t s_base;
@@ -631,7 +632,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     }
     const uint32_t wg = blockIdx.x - first_wg, G = gridDim.x - first_wg;
     const uint32_t blocks = (splat_count + 255u) >> 8;
-    const bool coarse = block_any != nullptr && blocks <= ANY_WORDS * 32u;
+    const bool coarse = block_any != nullptr && blocks <= ANY_WORDS * 32u && lds_bitmap != 0u;
     if (coarse) {                                                          // (k_bin_count's LDS bitmap of live storage blocks)
         for (uint32_t w = threadIdx.x; w < (blocks + 31u) / 32u; w += BIN_THREADS) {
             const uint4* src = reinterpret_cast<const uint4*>(block_any + 32u * w);
@@ -867,13 +868,14 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
                            m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, frame, cap, pp.lists_x, pp.list_row_begin,
                            m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), m->mirror_dev, m->draw_serial,
                            order_wg ? m->blend_stats.as<uint2>() : nullptr, order_wg ? m->blend_order.as<uint32_t>() : nullptr,
-                           m->deep_pass ? 1u : 0u, m->blend_stats.as<uint32_t>(), deep_min, deep_factor, scan, stat_shift);
+                           m->deep_pass ? 1u : 0u, m->blend_stats.as<uint32_t>(), deep_min, deep_factor, scan, stat_shift,
+                           m->no_coarse_vis ? 0u : 1u);
     } else {
         hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
                            m->translate ? m->perm.as<uint32_t>() : nullptr, m->prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
                            m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
                            m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
-                           m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins);
+                           m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
         hipLaunchKernelGGL((k_bin_emit<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, frame, cap, m->cidx.as<uint32_t>(),
                            m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
                            m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,

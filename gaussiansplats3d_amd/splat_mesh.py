@@ -319,6 +319,32 @@ class SplatMesh:
         cnt = np.where(rng[:, 1] > rng[:, 0], rng[:, 1] - rng[:, 0], 0).astype(np.uint32)   # untouched: (~0, 0)
         return cnt.reshape(b1 - b0, bins_x)
 
+    def bin_lists(self, tile_rows=None, list_bin_px=None):
+        """The entry lists of the last draw (`tile_rows`: the strip it drew): (ranges uint32 [lists, 2] - [begin, end) per list bin,
+        row-major from the strip's first list-bin row, (~0, 0) = untouched; entries uint32 [D] - the record slots the ranges index,
+        every list near -> far; slot_of_splat uint32 [n] - the record slot the vertex stage gave each splat, in the caller's
+        numbering, 0xFFFFFFFF = not visible).  list_bin_px: the draw's list-bin edge when asking ``last_stats`` for it is not
+        wanted (after an asynchronous draw that overflowed, ``last_stats`` regrows the entry buffers)."""
+        cam = self._cam
+        LB = int(self.last_stats().list_bin_px) if list_bin_px is None else int(list_bin_px)
+        bins_x = (cam.width + LB - 1) // LB
+        rows_total = (cam.height + L.GS_TILE - 1) // L.GS_TILE
+        r0, r1 = (0, rows_total) if tile_rows is None else tile_rows
+        y0, y1 = r0 * L.GS_TILE, min(r1 * L.GS_TILE, cam.height)
+        b0, b1 = y0 // LB, (y1 + LB - 1) // LB if y1 > y0 else y0 // LB
+        rng = np.empty(((b1 - b0) * bins_x, 2), dtype=np.uint32)
+        if rng.shape[0]:
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 2, rng.ctypes.data, rng.shape[0]))
+        touched = rng[:, 1] > rng[:, 0]
+        D = int(rng[touched, 1].max()) if touched.any() else 0            # the lists tile [0, D)
+        entries = np.empty(D, dtype=np.uint32)
+        if D:
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 8, entries.ctypes.data, D))
+        slots = np.empty(self.splat_count, dtype=np.uint32)
+        if self.splat_count:
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 9, slots.ctypes.data, self.splat_count))
+        return rng, entries, slots
+
     def blend_bin_stats(self):
         """Per 32-px blend bin of the last FULL-frame draw: (entries scanned, 2 x (splat, quadrant) pairs composited),
         [bin_rows, bins_x, 2]."""

@@ -464,7 +464,12 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * what = 4, and names the deep pass's members), GS_SCHEDULE_WORDS words: {1 if it ran, blend bins, shift x, shift y (int32: this
  * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, 1 if
  * the fused binner ran, the bins it put over the deep pass's trigger (0 when none reached it), the members' share of the walk in
- * 1/1024}, then the bin order itself (count = GS_SCHEDULE_WORDS .. + blend bins; the order only after a draw that ran it).
+ * 1/1024}, then the bin order itself (count = GS_SCHEDULE_WORDS .. + blend bins; the order only after a draw that ran it);
+ * 8 = the entry values of the last draw in list order: `count` uint32 record slots (count <= min(tile_entries, entry_capacity) of
+ * that draw), the array the [begin,end) ranges of what = 2 index, each list near -> far; refused while a gs_mesh_project is pending
+ * (the slots then refer to the other record set, as for gs_mesh_debug_rop8);
+ * 9 = per splat, in the caller's numbering, the record slot the last vertex stage gave it (uint32, 0xFFFFFFFF = not visible): what
+ * the entries of what = 8 name a splat by.
  *
  * The composite (csrc/tile_blend.hip).  Per 16x16-px quadrant, the ordered list entries whose ellipse reaches the quadrant are
  * cut into chunks of 1024; a chunk is the plain front-to-back composite from T = 1, and the chunks are merged near -> far

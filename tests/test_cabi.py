@@ -73,8 +73,10 @@ def test_graft_entry_checks_the_header_abi_version():
 
 
 def test_debug_read_constants_match_the_header():
-    """gs_mesh_debug_read(what = 7) is a debug selector, not an export: the ABI version stays, the header word count is mirrored."""
+    """gs_mesh_debug_read(what = 7 / 8 / 9) are debug selectors, not exports: the ABI version stays, the header word count is mirrored."""
     header = open(os.path.join(ROOT, "include", "gsplat_hip.h")).read()
     assert int(re.search(r"#define GS_SCHEDULE_WORDS (\d+)", header).group(1)) == _lib.GS_SCHEDULE_WORDS
     assert int(re.search(r"#define GS_ABI_VERSION (\d+)", header).group(1)) == 5
     assert "7 = the blend schedule of the last draw" in header
+    assert "8 = the entry values of the last draw in list order" in header
+    assert "9 = per splat, in the caller's numbering, the record slot the last vertex stage gave it" in header
