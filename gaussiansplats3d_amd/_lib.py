@@ -114,6 +114,7 @@ SYMBOLS = {
     "gs_asset_open": (C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "gs_asset_close": (None, [_VP]),
     "gs_asset_get_info": (C.c_int, [_VP, C.POINTER(AssetInfo)]),
+    "gs_asset_set_transform": (C.c_int, [_VP, _VP]),
     "gs_asset_fill": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gs_mesh_upload_asset": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gs_sorter_upload_asset_centers": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),

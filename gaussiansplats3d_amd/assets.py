@@ -2,7 +2,8 @@
 
 Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFileData`` -> ``SplatBuffer``
 (/root/reference/src/loaders/ply/PlyLoader.js, src/loaders/ksplat/KSplatLoader.js) followed by
-``SplatMesh.fillSplatDataArrays`` (src/splatmesh/SplatMesh.js:1853-1902).  ``load`` returns the arrays
+``SplatMesh.fillSplatDataArrays`` (src/splatmesh/SplatMesh.js:1853-1902), with the scene's static transform when
+``SplatAsset.set_transform`` gave one.  ``load`` returns the arrays
 ``SplatMesh.build`` / the sort worker take.  The two ``write_*`` helpers produce the same file formats (used by the
 tests and to stage synthetic scenes as real files); they are not part of the reference's API surface.
 """
@@ -29,6 +30,19 @@ class SplatAsset:
                                        int(spherical_harmonics_degree), C.byref(self.handle)))
         self.info = L.AssetInfo()
         L.check(self.lib.gs_asset_get_info(self.handle, C.byref(self.info)))
+
+    def set_transform(self, matrix):
+        """The static-mode scene transform (gs_asset_set_transform): 16 numbers, column-major like
+        ``THREE.Matrix4.elements`` (a 4x4 array is read as elements[4 * column + row]), or None to remove it.  ``fill``,
+        ``upload_to`` and ``upload_centers_to`` then return what the reference's fills return with that transform; an
+        identity matrix is not the same as None for the SH of a level-2 file."""
+        if matrix is None:
+            L.check(self.lib.gs_asset_set_transform(self.handle, None))
+            return
+        m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64).reshape(-1))
+        if m.size != 16:
+            raise ValueError("a scene transform has 16 elements")
+        L.check(self.lib.gs_asset_set_transform(self.handle, m.ctypes.data))
 
     def fill(self, minimum_alpha=1, half_precision_covariances=False, want_scale_rotation=False):
         n, deg = self.info.splat_count, self.info.sh_degree

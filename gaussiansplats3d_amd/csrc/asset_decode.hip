@@ -5,7 +5,9 @@
 // gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.  Restates, never copies:
 //   bucket of a splat / centre   /root/reference/src/loaders/SplatBuffer.js:199-246
 //   covariance                   SplatBuffer.js:440-486, 517-549 (three.js Matrix3/4 arithmetic in double)
-//   colour, SH order             SplatBuffer.js:551-575, 577-734 (no scene transform)
+//   colour, SH order             SplatBuffer.js:551-575, 577-734
+//   static scene transform       SplatBuffer.js:340-342, 461-466, 684-688, 707-715, 736-770 (the XF instantiations: an asset
+//                                with gs_asset_set_transform; asset_internal.hpp says the arithmetic once for both sides)
 //   integer centres              /root/reference/src/splatmesh/SplatMesh.js:1912-1948
 // Header and section parsing stay host code (assets.hip); the device sees a section table and searches it per splat.
 #include <algorithm>
@@ -70,32 +72,49 @@ __device__ __forceinline__ uint32_t bucket_index(const AssetView& v, const DevSe
     return b < sec.bucket_count ? b : sec.bucket_count - 1u;    // never past the table
 }
 
-// getSplatCenter (SplatBuffer.js:221-246), narrowed to float as fillSplatCenterArray stores it
-__device__ __forceinline__ void decode_centre(const AssetView& v, const DevSection& sec, uint32_t local, const uint8_t* row, float c[3]) {
+// getSplatCenter (SplatBuffer.js:221-246), narrowed to float as fillSplatCenterArray stores it; XF: through the scene
+// transform first (the double centre, SplatBuffer.js:332-342)
+template <bool XF>
+__device__ __forceinline__ void decode_centre(const AssetView& v, const AssetTransform& t, const DevSection& sec, uint32_t local,
+                                              const uint8_t* row, float c[3]) {
+    double d[3];
     if (v.level == 0) {
-        for (int k = 0; k < 3; k++) c[k] = ld<float>(row + 4 * k);
-        return;
+        for (int k = 0; k < 3; k++) d[k] = ld<float>(row + 4 * k);
+    } else {
+        const uint8_t* bucket = v.image + sec.buckets_off + (size_t)sec.bucket_storage * bucket_index(v, sec, local);
+        for (int k = 0; k < 3; k++) {
+            const double x = ld<uint16_t>(row + 2 * k);
+            const double bc = ld<float>(bucket + 4 * k);
+            d[k] = (x - (double)sec.scale_range) * sec.scale_factor + bc;
+        }
     }
-    const uint8_t* bucket = v.image + sec.buckets_off + (size_t)sec.bucket_storage * bucket_index(v, sec, local);
-    for (int k = 0; k < 3; k++) {
-        const double x = ld<uint16_t>(row + 2 * k);
-        const double bc = ld<float>(bucket + 4 * k);
-        c[k] = (float)((x - (double)sec.scale_range) * sec.scale_factor + bc);
-    }
+    if constexpr (XF) xf_centre(t, d, c);
+    else for (int k = 0; k < 3; k++) c[k] = (float)d[k];
 }
 
+struct NoTransform { uint32_t none; };   // the untransformed instantiations carry no matrix in their kernel argument
+struct DevTransform {          // the transformed ones: 16 + 9 + 25 doubles and the file's 8-bit SH range, by value
+    AssetTransform t;
+    double sh_min, sh_max;
+};
+__device__ __forceinline__ const AssetTransform& transform_of(const DevTransform& x) { return x.t; }
+__device__ __forceinline__ AssetTransform transform_of(const NoTransform&) { return AssetTransform(); }   // never read
+
 // One thread per splat: asset splat first + i -> element i of the staging arrays (MeshStaging).
-__global__ __launch_bounds__(256) void k_asset_decode(AssetView v, uint32_t first, uint32_t count, uint32_t min_alpha, float* __restrict__ centers,
-                                                      float* __restrict__ cov_f32, uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
+template <bool XF, class Transform>
+__global__ __launch_bounds__(256) void k_asset_decode(AssetView v, Transform xf, uint32_t first, uint32_t count, uint32_t min_alpha,
+                                                      float* __restrict__ centers, float* __restrict__ cov_f32,
+                                                      uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
                                                       uint16_t* __restrict__ sh_f16, uint8_t* __restrict__ sh_u8) {
 #pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
+    const AssetTransform& t = transform_of(xf);
     const DevSection& sec = section_of(v, first + i);
     const uint32_t local = first + i - sec.count_offset;
     const uint8_t* row = v.image + sec.data_off + (long long)sec.bytes_per_splat * local;
     float c[3];
-    decode_centre(v, sec, local, row, c);
+    decode_centre<XF>(v, t, sec, local, row, c);
     for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = c[k];
 
     const uint8_t* srow = row + asset_center_bytes(v.level);
@@ -122,11 +141,12 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, uint32_t firs
         for (int r = 0; r < 3; r++)
 #pragma unroll
             for (int q = 0; q < 3; q++) Cm[r][q] = M[r][0] * M[q][0] + M[r][1] * M[q][1] + M[r][2] * M[q][2];
-        const double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+        double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+        if constexpr (XF) xf_covariance(t, Cm, e);                                     // T3 * C * T3^T (SplatBuffer.js:461-466)
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-            if (cov_f32) cov_f32[6 * (size_t)i + k] = (float)e[k];
-            else cov_f16[6 * (size_t)i + k] = to_half_three(e[k]);
+            if (cov_f32) cov_f32[6 * (size_t)i + k] = XF ? xf_f32(e[k]) : (float)e[k];
+            else cov_f16[6 * (size_t)i + k] = XF ? xf_f16(e[k]) : to_half_three(e[k]);
         }
     }
     const uint8_t* crow = srow + asset_center_bytes(v.level) + asset_rotation_bytes(v.level);
@@ -134,7 +154,13 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, uint32_t firs
         const uint32_t alpha = crow[3];
         rgba[i] = (uint32_t)crow[0] | ((uint32_t)crow[1] << 8) | ((uint32_t)crow[2] << 16) | ((alpha >= min_alpha ? alpha : 0u) << 24);
     }
-    if (v.ncomp) {   // fillSphericalHarmonicsArray, no transform: level 0 through the half rule, level 1 bits, level 2 bytes
+    if constexpr (XF) {   // fillSphericalHarmonicsArray with a transform: widened, rotated, converted from level 0
+        if (v.ncomp)
+            xf_sh(t, v.level, v.sh_degree, xf.sh_min, xf.sh_max, crow + 4, [&](uint32_t dst, double val) {
+                if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = to_uint8_range(val, xf.sh_min, xf.sh_max);
+                else sh_f16[(size_t)v.ncomp * i + dst] = xf_f16(val);
+            });
+    } else if (v.ncomp) {   // ... without one: level 0 through the half rule, level 1 bits, level 2 bytes
         const uint8_t* hrow = crow + 4;
         auto emit = [&](uint32_t dst, uint32_t src) {
             if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = hrow[src];
@@ -152,14 +178,16 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, uint32_t firs
 // have put it.  integer: Math.round(fp32 centre * 1000.0) as util.integer_centers pins it - floor(v + 0.5) in double - with
 // w = 1000; a NaN or a value outside int32 becomes INT32_MIN (what the host's double -> int32 conversion stores).  Else the float
 // centre with w = 1.0.
-__global__ __launch_bounds__(256) void k_asset_centers(AssetView v, uint32_t first, uint32_t count, int integer, uint4* __restrict__ aos) {
+template <bool XF, class Transform>
+__global__ __launch_bounds__(256) void k_asset_centers(AssetView v, Transform xf, uint32_t first, uint32_t count, int integer,
+                                                       uint4* __restrict__ aos) {
 #pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
     const DevSection& sec = section_of(v, first + i);
     const uint32_t local = first + i - sec.count_offset;
     float c[3];
-    decode_centre(v, sec, local, v.image + sec.data_off + (long long)sec.bytes_per_splat * local, c);
+    decode_centre<XF>(v, transform_of(xf), sec, local, v.image + sec.data_off + (long long)sec.bytes_per_splat * local, c);
     uint32_t o[3];
     for (int k = 0; k < 3; k++) {
         if (integer) {
@@ -233,15 +261,25 @@ int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceIm
 }
 
 // gs_mesh_upload_asset's source: a segment of the staging is filled by k_asset_decode
+DevTransform dev_transform(const gs_asset* a) { return DevTransform{a->xf, a->sh_min, a->sh_max}; }
+
 struct AssetRows : MeshUploadSource {
     AssetView view;
+    const gs_asset* asset;
     uint32_t first, min_alpha;
     int fill(gs_mesh* m, uint32_t o, uint32_t count, const MeshStaging& s, hipStream_t st) override {
         const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
-        hipLaunchKernelGGL(k_asset_decode, dim3((count + 255u) / 256u), dim3(256), 0, st, view, first + o, count, min_alpha, (float*)s.base,
-                           half ? nullptr : (float*)(s.base + s.off_cov), half ? (uint16_t*)(s.base + s.off_cov) : nullptr,
-                           (uint32_t*)(s.base + s.off_rgba), s.sh_u8 ? nullptr : (uint16_t*)(s.base + s.off_sh),
-                           s.sh_u8 ? (uint8_t*)(s.base + s.off_sh) : nullptr);
+        const dim3 grid((count + 255u) / 256u), block(256);
+        float* cov32 = half ? nullptr : (float*)(s.base + s.off_cov);
+        uint16_t* cov16 = half ? (uint16_t*)(s.base + s.off_cov) : nullptr;
+        uint16_t* sh16 = s.sh_u8 ? nullptr : (uint16_t*)(s.base + s.off_sh);
+        uint8_t* sh8 = s.sh_u8 ? (uint8_t*)(s.base + s.off_sh) : nullptr;
+        if (asset->has_transform)
+            hipLaunchKernelGGL((k_asset_decode<true, DevTransform>), grid, block, 0, st, view, dev_transform(asset), first + o, count,
+                               min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
+        else
+            hipLaunchKernelGGL((k_asset_decode<false, NoTransform>), grid, block, 0, st, view, NoTransform{0u}, first + o, count,
+                               min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
         GS_HIP(hipGetLastError());
         return GS_OK;
     }
@@ -264,6 +302,7 @@ int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first,
     // (an earlier call's decode kernels have finished: every upload synchronises before it returns)
     AssetRows src;
     GS_TRY(asset_stage(a, first, count, m->asset_dev, m->ctx->stream, &src.view));
+    src.asset = a;
     src.first = first;
     src.min_alpha = min_alpha;
     src.stages_sh_u8 = mesh_u8;
@@ -276,12 +315,20 @@ int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uin
     GS_REQUIRE((uint64_t)from + count <= s->max_count, "range exceeds max_splat_count");
     GS_REQUIRE((uint64_t)first + count <= a->splat_count, "range exceeds the asset's splat count");
     GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || scene_indexes, "dynamic sorter needs scene_indexes");
+    GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || !a->has_transform,
+               "a dynamic sorter takes untransformed centres: dynamic mode applies scene transforms per frame and never bakes them");
     if (count == 0) return GS_OK;
     ScopedDevice sd(s->ctx->device);
     AssetView view;
     GS_TRY(asset_stage(a, first, count, s->asset_dev, s->stream, &view));
-    hipLaunchKernelGGL(k_asset_centers, dim3((count + 255u) / 256u), dim3(256), 0, s->stream, view, first, count,
-                       (s->flags & GS_SORT_INTEGER) ? 1 : 0, s->caos.as<uint4>() + from);
+    const dim3 grid((count + 255u) / 256u), block(256);
+    const int integer = (s->flags & GS_SORT_INTEGER) ? 1 : 0;
+    if (a->has_transform)
+        hipLaunchKernelGGL((k_asset_centers<true, DevTransform>), grid, block, 0, s->stream, view, dev_transform(a), first, count, integer,
+                           s->caos.as<uint4>() + from);
+    else
+        hipLaunchKernelGGL((k_asset_centers<false, NoTransform>), grid, block, 0, s->stream, view, NoTransform{0u}, first, count, integer,
+                           s->caos.as<uint4>() + from);
     GS_HIP(hipGetLastError());
     return gs_sorter_commit_centers(s, from, count, scene_indexes);
 }

@@ -8,8 +8,10 @@
 //                     :199-219 (bucket of a splat), :221-246 (centre decode)
 //   arrays            SplatBuffer.fillSplatCenterArray / fillSplatColorArray :551-575 / fillSplatCovarianceArray :517-549 +
 //                     computeCovariance :440-486 (three.js Matrix3/4 arithmetic in double) / fillSphericalHarmonicsArray
-//                     :577-734 WITHOUT a scene transform (identity scenes / dynamicMode), SH target level =
-//                     max(1, buffer level) (SplatMesh.js:1064-1066)
+//                     :577-734, SH target level = max(1, buffer level) (SplatMesh.js:1064-1066); WITHOUT a scene
+//                     transform (dynamicMode) until gs_asset_set_transform gives one (static mode, SplatMesh.js:1872-1899):
+//                     then Vector3.applyMatrix4 :340-342, T3*C*T3^T :461-466, rotated SH :628-637, 684-688, 707-715, 766-817
+//   scene transform   three r160 Matrix4.decompose / Quaternion.setFromRotationMatrix / normalize / makeRotationFromQuaternion
 // A PLY is first laid out as the level-0 section the reference would build from it (file order, i.e. the reference's
 // `optimizeSplatData: false`), so every fill routine reads one format.
 #include <algorithm>
@@ -19,18 +21,6 @@
 #include "asset_internal.hpp"
 
 namespace {
-
-// Util.js clamp = Math.max(Math.min(v, hi), lo): JS min / max PROPAGATE NaN (C's fmin / fmax drop it)
-double clampd(double v, double lo, double hi) {
-    if (v != v) return v;
-    return v > hi ? hi : (v < lo ? lo : v);
-}
-
-uint8_t to_uint8_range(double v, double lo, double hi) {                            // SplatBuffer.js:22-26
-    v = clampd(v, lo, hi);
-    const double r = clampd(floor((v - lo) / (hi - lo) * 255.0), 0.0, 255.0);
-    return r == r ? (uint8_t)r : (uint8_t)0;                                        // a NaN stored into a Uint8Array is 0
-}
 
 uint8_t clamped_u8(double v) {                         // Uint8ClampedArray store: NaN -> 0, round half to even
     if (!(v == v)) return 0;
@@ -389,22 +379,28 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
     GS_REQUIRE(!(sh_f16 && sh_u8), "pass sh_f16 (compression level <= 1) or sh_u8 (level 2), not both");
     GS_REQUIRE(!sh_u8 || a->level == 2, "sh_u8 output needs a compression level 2 file (SplatMesh.js:1064-1066)");
     GS_REQUIRE(!sh_f16 || a->level <= 1, "a level 2 file keeps its SH as uint8: ask for sh_u8");
+    GS_REQUIRE(!a->has_transform || !(scales || rotations),
+               "scales / rotations of a transformed asset are not provided (gs_asset_set_transform(a, NULL) removes the transform)");
     const uint32_t ncomp = sh_components(a->sh_degree);
+    const bool xf = a->has_transform;
     for (uint32_t i = 0; i < a->splat_count; i++) {
         const Section& sec = a->sections[a->section_of[i]];
         const uint32_t local = i - sec.count_offset;
         const size_t row = sec.data_base + (size_t)sec.bytes_per_splat * local;
         if (centers) {                                                                 // getSplatCenter :221-246
+            double c[3];
             if (a->level == 0) {
-                for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = a->rd<float>(row + 4 * k);
+                for (int k = 0; k < 3; k++) c[k] = a->rd<float>(row + 4 * k);
             } else {
                 const uint32_t b = bucket_index(a, sec, local);
                 for (int k = 0; k < 3; k++) {
                     const double x = a->rd<uint16_t>(row + 2 * k);
                     const double bc = a->rd<float>(sec.buckets_base + (size_t)sec.bucket_storage * b + 4 * k);
-                    centers[3 * (size_t)i + k] = (float)((x - (double)sec.scale_range) * sec.scale_factor + bc);
+                    c[k] = (x - (double)sec.scale_range) * sec.scale_factor + bc;
                 }
             }
+            if (xf) xf_centre(a->xf, c, centers + 3 * (size_t)i);
+            else for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = (float)c[k];
         }
         const size_t srow = row + CENTER_BYTES[a->level];
         if (cov_f32 || cov_f16 || scales || rotations) {
@@ -437,10 +433,11 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
                 // transformedCovariance = M * M^T
                 for (int r = 0; r < 3; r++)
                     for (int c = 0; c < 3; c++) Cm[r][c] = M[r][0] * M[c][0] + M[r][1] * M[c][1] + M[r][2] * M[c][2];
-                const double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+                double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+                if (xf) xf_covariance(a->xf, Cm, e);
                 for (int k = 0; k < 6; k++) {
-                    if (cov_f32) cov_f32[6 * (size_t)i + k] = (float)e[k];
-                    if (cov_f16) cov_f16[6 * (size_t)i + k] = to_half_three(e[k]);
+                    if (cov_f32) cov_f32[6 * (size_t)i + k] = xf ? xf_f32(e[k]) : (float)e[k];
+                    if (cov_f16) cov_f16[6 * (size_t)i + k] = xf ? xf_f16(e[k]) : to_half_three(e[k]);
                 }
             }
         }
@@ -450,7 +447,13 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
             const uint8_t alpha = a->buf[crow + 3];
             rgba[4 * (size_t)i + 3] = alpha >= min_alpha ? alpha : 0;
         }
-        if ((sh_f16 || sh_u8) && ncomp) {                                              // fillSphericalHarmonicsArray, no transform
+        if ((sh_f16 || sh_u8) && ncomp && xf) {                                        // fillSphericalHarmonicsArray with a transform
+            const size_t hrow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u;
+            xf_sh(a->xf, a->level, a->sh_degree, a->sh_min, a->sh_max, a->buf.data() + hrow, [&](uint32_t dst, double v) {
+                if (sh_u8) sh_u8[(size_t)ncomp * i + dst] = to_uint8_range(v, a->sh_min, a->sh_max);
+                else sh_f16[(size_t)ncomp * i + dst] = xf_f16(v);
+            });
+        } else if ((sh_f16 || sh_u8) && ncomp) {                                       // ... without one
             const size_t hrow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u;
             auto emit = [&](uint32_t dst, uint32_t src) {
                 if (sh_u8) { sh_u8[(size_t)ncomp * i + dst] = a->rd<uint8_t>(hrow + src); return; }
@@ -464,6 +467,109 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
                     for (uint32_t ch = 0; ch < 3; ch++) emit(9 + 3 * c + ch, 9 + c + 5 * ch);
         }
     }
+    return GS_OK;
+}
+
+// The per-call preamble of the transformed fills, done once (SplatBuffer.js:628-637 and the band-2 rows of
+// rotateSphericalHarmonics5 :775-815, which the reference recomputes per splat from the same inputs).
+int gs_asset_set_transform(gs_asset* a, const double* transform16) {
+    GS_REQUIRE(a != nullptr, "asset == NULL");
+    if (!transform16) {
+        a->has_transform = false;
+        return GS_OK;
+    }
+    const double* te = transform16;
+    for (int k = 0; k < 16; k++) GS_REQUIRE(isfinite(te[k]), "scene transform: an element is not finite");
+    GS_REQUIRE(te[3] == 0 && te[7] == 0 && te[11] == 0 && te[15] == 1, "scene transform: the bottom row is not (0, 0, 0, 1)");
+    // Matrix4.decompose (three r160)
+    double sx = sqrt(te[0] * te[0] + te[1] * te[1] + te[2] * te[2]);
+    const double sy = sqrt(te[4] * te[4] + te[5] * te[5] + te[6] * te[6]);
+    const double sz = sqrt(te[8] * te[8] + te[9] * te[9] + te[10] * te[10]);
+    GS_REQUIRE(sx != 0 && sy != 0 && sz != 0, "scene transform: a basis column has length 0 (Matrix4.decompose divides by it)");
+    {   // Matrix4.determinant
+        const double n11 = te[0], n12 = te[4], n13 = te[8], n14 = te[12], n21 = te[1], n22 = te[5], n23 = te[9], n24 = te[13];
+        const double n31 = te[2], n32 = te[6], n33 = te[10], n34 = te[14], n41 = te[3], n42 = te[7], n43 = te[11], n44 = te[15];
+        const double det =
+            n41 * (+n14 * n23 * n32 - n13 * n24 * n32 - n14 * n22 * n33 + n12 * n24 * n33 + n13 * n22 * n34 - n12 * n23 * n34) +
+            n42 * (+n11 * n23 * n34 - n11 * n24 * n33 + n14 * n21 * n33 - n13 * n21 * n34 + n13 * n24 * n31 - n14 * n23 * n31) +
+            n43 * (+n11 * n24 * n32 - n11 * n22 * n34 - n14 * n21 * n32 + n12 * n21 * n34 + n14 * n22 * n31 - n12 * n24 * n31) +
+            n44 * (-n13 * n22 * n31 - n11 * n23 * n32 + n11 * n22 * n33 + n13 * n21 * n32 - n12 * n21 * n33 + n12 * n23 * n31);
+        if (det < 0) sx = -sx;
+    }
+    const double invSX = 1 / sx, invSY = 1 / sy, invSZ = 1 / sz;
+    const double m11 = te[0] * invSX, m21 = te[1] * invSX, m31 = te[2] * invSX;
+    const double m12 = te[4] * invSY, m22 = te[5] * invSY, m32 = te[6] * invSY;
+    const double m13 = te[8] * invSZ, m23 = te[9] * invSZ, m33 = te[10] * invSZ;
+    // Quaternion.setFromRotationMatrix
+    double qx, qy, qz, qw;
+    const double trace = m11 + m22 + m33;
+    if (trace > 0) {
+        const double s = 0.5 / sqrt(trace + 1.0);
+        qw = 0.25 / s; qx = (m32 - m23) * s; qy = (m13 - m31) * s; qz = (m21 - m12) * s;
+    } else if (m11 > m22 && m11 > m33) {
+        const double s = 2.0 * sqrt(1.0 + m11 - m22 - m33);
+        qw = (m32 - m23) / s; qx = 0.25 * s; qy = (m12 + m21) / s; qz = (m13 + m31) / s;
+    } else if (m22 > m33) {
+        const double s = 2.0 * sqrt(1.0 + m22 - m11 - m33);
+        qw = (m13 - m31) / s; qx = (m12 + m21) / s; qy = 0.25 * s; qz = (m23 + m32) / s;
+    } else {
+        const double s = 2.0 * sqrt(1.0 + m33 - m11 - m22);
+        qw = (m21 - m12) / s; qx = (m13 + m31) / s; qy = (m23 + m32) / s; qz = 0.25 * s;
+    }
+    {   // tempRotation.normalize()
+        double l = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
+        if (l == 0) { qx = qy = qz = 0; qw = 1; }
+        else { l = 1 / l; qx = qx * l; qy = qy * l; qz = qz * l; qw = qw * l; }
+    }
+    // makeRotationFromQuaternion = compose(zero, q, one), then Matrix3.setFromMatrix4: E = Matrix3.elements (column-major)
+    double E[9];
+    {
+        const double x = qx, y = qy, z = qz, w = qw;
+        const double x2 = x + x, y2 = y + y, z2 = z + z;
+        const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
+        const double wx = w * x2, wy = w * y2, wz = w * z2;
+        E[0] = (1 - (yy + zz)) * 1; E[1] = (xy + wz) * 1; E[2] = (xz - wy) * 1;
+        E[3] = (xy - wz) * 1; E[4] = (1 - (xx + zz)) * 1; E[5] = (yz + wx) * 1;
+        E[6] = (xz + wy) * 1; E[7] = (yz - wx) * 1; E[8] = (1 - (xx + yy)) * 1;
+    }
+    AssetTransform t;
+    for (int k = 0; k < 16; k++) t.m[k] = te[k];
+    double(&sh11)[3] = t.sh1[0], (&sh12)[3] = t.sh1[1], (&sh13)[3] = t.sh1[2];
+    sh11[0] = E[4]; sh11[1] = -E[7]; sh11[2] = E[1];                                    // SplatBuffer.js:634-636
+    sh12[0] = -E[5]; sh12[1] = E[8]; sh12[2] = -E[2];
+    sh13[0] = E[3]; sh13[1] = -E[6]; sh13[2] = E[0];
+    const double kSqrt0104 = sqrt(1.0 / 4.0), kSqrt0304 = sqrt(3.0 / 4.0), kSqrt0103 = sqrt(1.0 / 3.0), kSqrt0403 = sqrt(4.0 / 3.0),
+                 kSqrt0112 = sqrt(1.0 / 12.0);
+    double(&sh21)[5] = t.sh2[0], (&sh22)[5] = t.sh2[1], (&sh23)[5] = t.sh2[2], (&sh24)[5] = t.sh2[3], (&sh25)[5] = t.sh2[4];
+    sh21[0] = kSqrt0104 * ((sh13[2] * sh11[0] + sh13[0] * sh11[2]) + (sh11[2] * sh13[0] + sh11[0] * sh13[2]));   // :781-815
+    sh21[1] = (sh13[1] * sh11[0] + sh11[1] * sh13[0]);
+    sh21[2] = kSqrt0304 * (sh13[1] * sh11[1] + sh11[1] * sh13[1]);
+    sh21[3] = (sh13[1] * sh11[2] + sh11[1] * sh13[2]);
+    sh21[4] = kSqrt0104 * ((sh13[2] * sh11[2] - sh13[0] * sh11[0]) + (sh11[2] * sh13[2] - sh11[0] * sh13[0]));
+    sh22[0] = kSqrt0104 * ((sh12[2] * sh11[0] + sh12[0] * sh11[2]) + (sh11[2] * sh12[0] + sh11[0] * sh12[2]));
+    sh22[1] = sh12[1] * sh11[0] + sh11[1] * sh12[0];
+    sh22[2] = kSqrt0304 * (sh12[1] * sh11[1] + sh11[1] * sh12[1]);
+    sh22[3] = sh12[1] * sh11[2] + sh11[1] * sh12[2];
+    sh22[4] = kSqrt0104 * ((sh12[2] * sh11[2] - sh12[0] * sh11[0]) + (sh11[2] * sh12[2] - sh11[0] * sh12[0]));
+    sh23[0] = kSqrt0103 * (sh12[2] * sh12[0] + sh12[0] * sh12[2]) +
+              -kSqrt0112 * ((sh13[2] * sh13[0] + sh13[0] * sh13[2]) + (sh11[2] * sh11[0] + sh11[0] * sh11[2]));
+    sh23[1] = kSqrt0403 * sh12[1] * sh12[0] + -kSqrt0103 * (sh13[1] * sh13[0] + sh11[1] * sh11[0]);
+    sh23[2] = sh12[1] * sh12[1] + -kSqrt0104 * (sh13[1] * sh13[1] + sh11[1] * sh11[1]);
+    sh23[3] = kSqrt0403 * sh12[1] * sh12[2] + -kSqrt0103 * (sh13[1] * sh13[2] + sh11[1] * sh11[2]);
+    sh23[4] = kSqrt0103 * (sh12[2] * sh12[2] - sh12[0] * sh12[0]) +
+              -kSqrt0112 * ((sh13[2] * sh13[2] - sh13[0] * sh13[0]) + (sh11[2] * sh11[2] - sh11[0] * sh11[0]));
+    sh24[0] = kSqrt0104 * ((sh12[2] * sh13[0] + sh12[0] * sh13[2]) + (sh13[2] * sh12[0] + sh13[0] * sh12[2]));
+    sh24[1] = sh12[1] * sh13[0] + sh13[1] * sh12[0];
+    sh24[2] = kSqrt0304 * (sh12[1] * sh13[1] + sh13[1] * sh12[1]);
+    sh24[3] = sh12[1] * sh13[2] + sh13[1] * sh12[2];
+    sh24[4] = kSqrt0104 * ((sh12[2] * sh13[2] - sh12[0] * sh13[0]) + (sh13[2] * sh12[2] - sh13[0] * sh12[0]));
+    sh25[0] = kSqrt0104 * ((sh13[2] * sh13[0] + sh13[0] * sh13[2]) - (sh11[2] * sh11[0] + sh11[0] * sh11[2]));
+    sh25[1] = (sh13[1] * sh13[0] - sh11[1] * sh11[0]);
+    sh25[2] = kSqrt0304 * (sh13[1] * sh13[1] - sh11[1] * sh11[1]);
+    sh25[3] = (sh13[1] * sh13[2] - sh11[1] * sh11[2]);
+    sh25[4] = kSqrt0104 * ((sh13[2] * sh13[2] - sh13[0] * sh13[0]) - (sh11[2] * sh11[2] - sh11[0] * sh11[0]));
+    a->xf = t;
+    a->has_transform = true;
     return GS_OK;
 }
 

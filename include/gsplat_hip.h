@@ -232,11 +232,27 @@ typedef struct gs_asset_info {
     float sh_min, sh_max;        /* min/maxSphericalHarmonicsCoeff of the file (8-bit SH range)                  */
 } gs_asset_info;
 int gs_asset_get_info(gs_asset* a, gs_asset_info* info);
-/* SplatMesh.fillSplatDataArrays (src/splatmesh/SplatMesh.js:1853-1902) without a scene transform; any pointer may
+/* The scene transform SplatMesh.fillSplatDataArrays hands to the SplatBuffer fills in static mode
+ * (SplatMesh.js:1872-1899, getSceneTransform :2019-2028): 16 doubles, column-major, THREE.Matrix4.elements.
+ * NULL removes it (the reference's `transform === undefined` path, the state of a freshly opened asset).  An identity
+ * matrix is NOT the same as NULL for SH: with a matrix the coefficients are widened, rotated in double and converted
+ * from level 0 again (SplatBuffer.js:663-673, 684-688), which moves uint8 values of a level-2 file.  From then on
+ * gs_asset_fill, gs_mesh_upload_asset and gs_sorter_upload_asset_centers return what the reference returns with that
+ * `transform` argument: centres through Vector3.applyMatrix4 (SplatBuffer.js:340-342), covariances as T3 C T3^T
+ * (:461-466), SH bands 1 and 2 rotated by the matrix's rotation (:628-637, 766-817); rgba is unaffected.  Replaces
+ * the `transform` parameter of SplatBuffer.fillSplatCenterArray / fillSplatCovarianceArray /
+ * fillSphericalHarmonicsArray and the decompose + band rows fillSphericalHarmonicsArray derives per call.
+ * GS_ERR_INVALID, and the asset keeps the transform it had, for a non-finite element, a bottom row other than
+ * (0, 0, 0, 1) (Matrix4.compose never makes another) or a basis column of length 0 (Matrix4.decompose divides by it). */
+int gs_asset_set_transform(gs_asset* a, const double* transform16);
+/* SplatMesh.fillSplatDataArrays (src/splatmesh/SplatMesh.js:1853-1902), with the scene transform of
+ * gs_asset_set_transform if one is set (static mode) and without one otherwise (dynamic mode); any pointer may
  * be NULL.  centers float[3n]; cov_f32 float[6n] / cov_f16 half bits[6n] (covariance compression level 0 / 1);
  * rgba uint8[4n] with alpha zeroed below min_alpha; sh_f16 half bits[ncoef*n] (sh_level 1) or sh_u8 uint8[ncoef*n]
  * (sh_level 2), coefficient-major RGB triples; scales float[3n], rotations float[4n] (x,y,z,w) normalised with
- * w >= 0, as fillSplatScaleRotationArray returns them (SplatBuffer.js:349-437). */
+ * w >= 0, as fillSplatScaleRotationArray returns them (SplatBuffer.js:349-437) - untransformed only: asking for them
+ * while a transform is set is GS_ERR_INVALID (the transformed fillSplatScaleRotationArray serves the raycaster and
+ * 2D mode). */
 int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba,
                   uint16_t* sh_f16, uint8_t* sh_u8, float* scales, float* rotations);
 
@@ -277,7 +293,8 @@ int gs_mesh_upload_sh_u8(gs_mesh* m, uint32_t from, uint32_t count, const uint8_
  * gs_mesh_upload (+ gs_mesh_upload_sh_u8 for a level-2 file) of the same range leaves, plane for plane. Replaces
  * SplatBuffer.fillSplatCenterArray / fillSplatCovarianceArray / fillSplatColorArray / fillSphericalHarmonicsArray
  * (SplatBuffer.js:440-486, 517-734) + SplatMesh.updateDataTexturesFromBaseData (SplatMesh.js:900-1062) in one call:
- * the file's rows cross to the device, not the decoded arrays.  GS_ERR_INVALID, and nothing changes, when a range is
+ * the file's rows cross to the device, not the decoded arrays; a scene transform (gs_asset_set_transform) is applied
+ * there too.  GS_ERR_INVALID, and nothing changes, when a range is
  * out of bounds, the mesh's SH degree differs from gs_asset_info.sh_degree, or GS_MESH_SH_U8 disagrees with
  * sh_level == 2 for a degree > 0.  GS_MESH_COV_HALF is the mesh's choice; the device narrows with
  * THREE.DataUtils.toHalfFloat's truncating rule (SplatBuffer.js:469-474). */
@@ -287,7 +304,9 @@ int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first,
  * SplatMesh.getIntegerCenters does (GS_SORT_INTEGER; SplatMesh.js:1912-1926), or the float centres
  * (getFloatCenters, :1935-1948), padFour.  scene_indexes as in gs_sorter_upload_centers.  Replaces
  * SplatBuffer.fillSplatCenterArray + getIntegerCenters / getFloatCenters + the worker's copy
- * (src/worker/SortWorker.js:84-98).  GS_ERR_INVALID, and nothing changes, when a range is out of bounds. */
+ * (src/worker/SortWorker.js:84-98).  An asset with a scene transform gives the centres of the transformed fill.
+ * GS_ERR_INVALID, and nothing changes, when a range is out of bounds or a GS_SORT_DYNAMIC sorter is handed an asset
+ * with a transform (dynamic mode applies transforms per frame and never bakes them). */
 int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uint32_t first, uint32_t count,
                                    const uint32_t* scene_indexes);
 

@@ -1,0 +1,39 @@
+// Loads a file with a static scene transform through the device decode of the JS shim and draws one frame (test driver).
+//   node asset_transform_via_js.js <file .ply|.ksplat> <in.bin> <out.bin>
+// in.bin: uint32 {width, height, shDegree, sphericalHarmonics8Bit}, modelView F32[16], proj F32[16], camPos F32[3], focal F32[2],
+// modelViewProj F32[16] (the sort's), transform F64[16] (Matrix4.elements).  out.bin: the sorted indexes U32[n], then the frame
+// U8[4 * width * height].
+'use strict';
+const fs = require('fs');
+const gs = require('./gsplat.js');
+const [filePath, inPath, outPath] = process.argv.slice(2);
+const bytes = new Uint8Array(fs.readFileSync(filePath));
+const format = bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? 1 : 2;      // "ply"
+const buf = fs.readFileSync(inPath);
+const ab = buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.byteLength);
+const [width, height, shDegree, sh8] = new Uint32Array(ab, 0, 4);
+let off = 16;
+const take = (count) => { const a = new Float32Array(ab.slice(off, off + count * 4)); off += count * 4; return a; };
+const modelView = take(16), proj = take(16), camPos = take(3), focal = take(2), mvp = take(16);
+const transform = Array.from(new Float64Array(ab.slice(off, off + 128)));
+const info = gs.addon.assetLoad(bytes, format, shDegree, 1, 0), n = info.splatCount;
+const mesh = new gs.SplatMeshHIP(n, { sphericalHarmonicsDegree: shDegree, sphericalHarmonics8Bit: !!sh8 });
+if (sh8) mesh.setScenes({ sceneCount: 1, sh8Min: new Float32Array([info.shMin]), sh8Max: new Float32Array([info.shMax]) });
+const uploaded = mesh.buildFromAsset(bytes, format, 0, 0, 0xFFFFFFFF, 1, transform);
+const worker = gs.createSortWorker(n, false, true, true, false);
+worker.synchronous = true;
+worker.uploadAssetCenters(bytes, format, shDegree, 0, 0, 0xFFFFFFFF, null, transform);
+worker.onmessage = (e) => {
+  if (!e.data.sortDone) return;
+  const order = e.data.sortedIndexes;
+  mesh.updateRenderIndexes(order, n);
+  mesh.updateUniforms({ x: width, y: height }, focal[0], focal[1], false, 1.0, 1.0);
+  mesh.setCameraMatrices(modelView, proj, camPos);
+  const { pixels } = mesh.render();
+  fs.writeFileSync(outPath, Buffer.concat([Buffer.from(order.buffer, order.byteOffset, order.byteLength),
+                                           Buffer.from(pixels.buffer, pixels.byteOffset, pixels.byteLength)]));
+  console.log(JSON.stringify({ splatCount: n, uploaded }));
+  worker.terminate();
+  mesh.dispose();
+};
+worker.postMessage({ sort: { modelViewProj: mvp, splatRenderCount: n, splatSortCount: n } });

@@ -138,9 +138,11 @@ class HipSortWorker {
 
   // HIP-engine extra: the `centers` message of a file's splats, derived on the device from its bytes
   // (gs_sorter_upload_asset_centers).  Like a `centers` message it must not be posted while a sort is in flight.
-  uploadAssetCenters(bytes, format, maxShDegree, from = 0, first = 0, count = 0xFFFFFFFF, sceneIndexes = null) {
+  // transform: the scene's static transform (Matrix4.elements, 16 numbers) baked into the centres as the reference's static
+  // mode does; a dynamic-mode worker refuses one.
+  uploadAssetCenters(bytes, format, maxShDegree, from = 0, first = 0, count = 0xFFFFFFFF, sceneIndexes = null, transform = null) {
     if (this._busy) throw new Error('uploadAssetCenters: a sort is in flight');
-    const n = addon.sorterUploadAssetCenters(this.handle, from, bytes, format, maxShDegree, first, count, sceneIndexes);
+    const n = addon.sorterUploadAssetCenters(this.handle, from, bytes, format, maxShDegree, first, count, sceneIndexes, transform);
     this.centersReceived = true;
     this.uploadedSplatCount = Math.max(this.uploadedSplatCount, from + n);
     return n;
@@ -236,8 +238,11 @@ class SplatMeshHIP {
   }
   // The same upload straight from a file's bytes, decoded per splat on the device (gs_mesh_upload_asset): format 1 = .ply,
   // 2 = .ksplat; the mesh's sphericalHarmonicsDegree / sphericalHarmonics8Bit must be the file's.  Returns the splats uploaded.
-  buildFromAsset(bytes, format, start = 0, first = 0, count = 0xFFFFFFFF, minimumAlpha = 1) {
-    const n = addon.meshUploadAsset(this.handle, start, bytes, format, this.shDegree, first, count, minimumAlpha);
+  // transform: the scene's static transform (Matrix4.elements, 16 numbers: what addSplatScene's position / rotation / scale
+  // compose to), baked into centres, covariances and SH as SplatMesh.fillSplatDataArrays does in static mode.  The static
+  // Viewer passes the identity when a scene has none, which is not the same as null for the SH of a level-2 file.
+  buildFromAsset(bytes, format, start = 0, first = 0, count = 0xFFFFFFFF, minimumAlpha = 1, transform = null) {
+    const n = addon.meshUploadAsset(this.handle, start, bytes, format, this.shDegree, first, count, minimumAlpha, transform);
     this.splatCount = Math.max(this.splatCount, start + n);
     return n;
   }

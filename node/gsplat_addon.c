@@ -798,12 +798,39 @@ static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     return r;
 }
 
-/* meshUploadAsset(mesh, from, bytes ArrayBuffer|Uint8Array, format 1=ply 2=ksplat, maxShDegree, first, count, minAlpha) -> splats uploaded
- * sorterUploadAssetCenters(sorter, from, bytes, format, maxShDegree, first, count, sceneIndexes|null) -> splats uploaded
+/* meshUploadAsset(mesh, from, bytes ArrayBuffer|Uint8Array, format 1=ply 2=ksplat, maxShDegree, first, count, minAlpha[, transform])
+ *   -> splats uploaded
+ * sorterUploadAssetCenters(sorter, from, bytes, format, maxShDegree, first, count, sceneIndexes|null[, transform]) -> splats uploaded
  * The per-splat decode on the device (gs_mesh_upload_asset / gs_sorter_upload_asset_centers): the file's rows cross to the card, not
- * the arrays assetLoad returns.  count 0xFFFFFFFF: every splat from `first` on. */
+ * the arrays assetLoad returns.  count 0xFFFFFFFF: every splat from `first` on.  transform: the scene's static transform, 16 numbers
+ * (THREE.Matrix4.elements), applied right after the asset is opened (gs_asset_set_transform); absent / null / undefined = none. */
 static napi_value upload_asset(napi_env env, napi_callback_info info, int to_sorter) {
-    ARGS(8)
+    size_t argc = 9;
+    napi_value argv[9];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 8) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+    double transform[16];
+    int have_transform = 0;
+    if (argc >= 9) {
+        napi_valuetype t = napi_undefined;
+        napi_typeof(env, argv[8], &t);
+        if (t != napi_undefined && t != napi_null) {
+            uint32_t len = 0;
+            napi_value len_v, el;
+            if (t != napi_object || napi_get_named_property(env, argv[8], "length", &len_v) != napi_ok ||
+                napi_get_value_uint32(env, len_v, &len) != napi_ok || len != 16) {
+                napi_throw_type_error(env, NULL, "transform: an array of 16 numbers");
+                return NULL;
+            }
+            for (uint32_t k = 0; k < 16; k++) {
+                if (napi_get_element(env, argv[8], k, &el) != napi_ok || napi_get_value_double(env, el, &transform[k]) != napi_ok) {
+                    napi_throw_type_error(env, NULL, "transform: an array of 16 numbers");
+                    return NULL;
+                }
+            }
+            have_transform = 1;
+        }
+    }
     void *data, *sc = NULL;
     size_t nb, sb = 0;
     if (!get_bytes(env, argv[2], &data, &nb) || !data) { napi_throw_type_error(env, NULL, "asset bytes"); return NULL; }
@@ -812,6 +839,13 @@ static napi_value upload_asset(napi_env env, napi_callback_info info, int to_sor
     int st;
     LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[3]), get_u32(env, argv[4]), &a));
     if (st < 0) return throw_gs(env, st);
+    if (have_transform) {
+        LOCKED(st = gs_asset_set_transform(a, transform));
+        if (st < 0) {
+            LOCKED(gs_asset_close(a));
+            return throw_gs(env, st);
+        }
+    }
     gs_asset_info ai;
     gs_asset_get_info(a, &ai);
     const uint32_t from = get_u32(env, argv[1]), first = get_u32(env, argv[5]);

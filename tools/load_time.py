@@ -1,9 +1,11 @@
 """Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
-    python tools/load_time.py [--n 5800000] [--file NAME] [--repeats 5] [--out profiles/<tag>_load_time.txt]
+    python tools/load_time.py [--n 5800000] [--file NAME] [--repeats 5] [--transform identity | 16 numbers]
+                              [--out profiles/<tag>_load_time.txt]
   host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
   device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
 The file: $GS_DATA_DIR/<--file> when given, else a seeded level-2 SH-2 .ksplat of --n splats from assets.write_ksplat (the C3
-count by default).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
+count by default).  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
+Viewer passes for a scene without one), set on the asset so both paths bake it (gs_asset_set_transform).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
 alternate.  Prints median and spread (max - min) of both and the bytes each sends over PCIe; the device path passes when its
 median is below the host path's by more than the larger spread."""
 import argparse
@@ -33,14 +35,21 @@ def main():
     ap.add_argument("--n", type=int, default=5_800_000)
     ap.add_argument("--file", default=None)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--transform", nargs="+", default=None, metavar="M", help="`identity` or the 16 elements, column-major")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    transform = None
+    if args.transform is not None:
+        transform = np.eye(4).reshape(16) if args.transform == ["identity"] else np.array([float(v) for v in args.transform])
+        if transform.size != 16:
+            ap.error("--transform takes `identity` or 16 numbers")
     if args.file:
         path = os.path.join(os.environ.get("GS_DATA_DIR", "."), args.file)
         data, source = open(path, "rb").read(), args.file
     else:
         data, source = seeded_file(args.n), f"seeded level-2 SH-2 .ksplat, {args.n} splats"
     asset = assets.SplatAsset(data, None, 2)
+    asset.set_transform(transform)
     info = asset.info
     n, deg, sh8 = info.splat_count, info.sh_degree, info.sh_level == 2 and info.sh_degree > 0
     ncoef = {0: 0, 1: 9, 2: 24}[deg]
@@ -78,7 +87,8 @@ def main():
     med = {k: float(np.median(v)) for k, v in times.items()}
     spread = {k: float(max(v) - min(v)) for k, v in times.items()}
     lines = [f"load_time: {source}; file {len(data)} bytes, {n} splats, SH degree {deg}, compression level {info.compression_level}; "
-             f"{args.repeats} repeats per path, alternating, fresh mesh + sorter each"]
+             f"{args.repeats} repeats per path, alternating, fresh mesh + sorter each; scene transform "
+             + ("none" if transform is None else " ".join(f"{v:g}" for v in transform))]
     for k in ("host", "device"):
         lines.append(f"{k:6s} median {med[k]:10.2f} ms  spread {spread[k]:8.2f} ms  PCIe {pcie[k]:12d} bytes ({pcie[k] / n:.1f} B/splat)  "
                      f"runs " + " ".join(f"{t:.2f}" for t in times[k]))
