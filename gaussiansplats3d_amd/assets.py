@@ -1,11 +1,14 @@
 """Host-side mirror of the reference's scene loaders, over the native readers of libgsplat_hip (csrc/assets.hip).
 
-Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFileData`` -> ``SplatBuffer``
-(/root/reference/src/loaders/ply/PlyLoader.js, src/loaders/ksplat/KSplatLoader.js) followed by
+Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFileData`` / ``SplatLoader`` -> ``SplatBuffer``
+(/root/reference/src/loaders/ply/PlyLoader.js, src/loaders/ksplat/KSplatLoader.js, src/loaders/splat/SplatLoader.js's
+progressive file-order path) followed by
 ``SplatMesh.fillSplatDataArrays`` (src/splatmesh/SplatMesh.js:1853-1902), with the scene's static transform when
 ``SplatAsset.set_transform`` gave one.  ``load`` returns the arrays
-``SplatMesh.build`` / the sort worker take.  The two ``write_*`` helpers produce the same file formats (used by the
-tests and to stage synthetic scenes as real files); they are not part of the reference's API surface.
+``SplatMesh.build`` / the sort worker take.  ``"ply"`` covers INRIA-v1 and the PlayCanvas / SuperSplat compressed PLY (decided
+from the header); ``"splat"`` has no magic number and is chosen by ``fmt`` or a file name's extension.  The ``write_*``
+helpers produce the same file formats (used by the tests and to stage synthetic scenes as real files); they are not part
+of the reference's API surface.
 """
 import ctypes as C
 import struct
@@ -17,7 +20,8 @@ from .util import to_half_three
 
 
 class SplatAsset:
-    """An opened .ply / .ksplat: ``info`` + ``fill()`` -> dict of arrays."""
+    """An opened .ply / .ksplat / .splat: ``info`` + ``fill()`` -> dict of arrays."""
+    FORMATS = {"ply": L.GS_ASSET_PLY, "ksplat": L.GS_ASSET_KSPLAT, "splat": L.GS_ASSET_SPLAT}
 
     def __init__(self, data, fmt=None, spherical_harmonics_degree=2):
         self.lib = L.load()
@@ -26,8 +30,9 @@ class SplatAsset:
             fmt = "ply" if data[:3] == b"ply" else "ksplat"
         self.handle = C.c_void_p()
         buf = (C.c_char * len(data)).from_buffer_copy(data)
-        L.check(self.lib.gs_asset_open(buf, len(data), L.GS_ASSET_PLY if fmt == "ply" else L.GS_ASSET_KSPLAT,
-                                       int(spherical_harmonics_degree), C.byref(self.handle)))
+        if fmt not in self.FORMATS:
+            raise ValueError(f"unknown asset format {fmt!r}: one of {sorted(self.FORMATS)}")
+        L.check(self.lib.gs_asset_open(buf, len(data), self.FORMATS[fmt], int(spherical_harmonics_degree), C.byref(self.handle)))
         self.info = L.AssetInfo()
         L.check(self.lib.gs_asset_get_info(self.handle, C.byref(self.info)))
 
@@ -95,8 +100,15 @@ class SplatAsset:
 
 
 def load(path_or_bytes, spherical_harmonics_degree=2, minimum_alpha=1, half_precision_covariances=False):
-    data = open(path_or_bytes, "rb").read() if isinstance(path_or_bytes, str) else path_or_bytes
-    a = SplatAsset(data, None, spherical_harmonics_degree)
+    fmt = None
+    if isinstance(path_or_bytes, str):
+        if path_or_bytes.lower().endswith(".splat"):          # .splat has no magic number: the extension decides
+            fmt = "splat"
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    else:
+        data = path_or_bytes
+    a = SplatAsset(data, fmt, spherical_harmonics_degree)
     try:
         return a.fill(minimum_alpha, half_precision_covariances)
     finally:
@@ -128,6 +140,100 @@ def write_ply(centers, log_scales, rotations_wxyz, f_dc, opacity_logit, f_rest=N
     rec = np.zeros(n, dtype=[("f", np.float32, body.shape[1]), ("u", np.uint8)])
     rec["f"], rec["u"] = body, extra_uchar
     return header.encode() + rec.tobytes()
+
+
+def write_splat(centers, scales, rotations_wxyz, rgba):
+    """.splat rows (src/loaders/splat/SplatParser.js:77-82): centre 3 x f32, scale 3 x f32 (linear), RGBA 4 x u8, rotation
+    4 x u8 as round(q / |q| * 128 + 128) clipped to 0..255, stored w, x, y, z."""
+    n = centers.shape[0]
+    q = np.asarray(rotations_wxyz, np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    rec = np.zeros(n, dtype=[("c", "<f4", 3), ("s", "<f4", 3), ("rgba", np.uint8, 4), ("rot", np.uint8, 4)])
+    rec["c"], rec["s"], rec["rgba"] = centers, scales, np.asarray(rgba, np.uint8).reshape(n, 4)
+    rec["rot"] = np.clip(np.floor(q * 128 + 128 + 0.5), 0, 255).astype(np.uint8)
+    return rec.tobytes()
+
+
+def pack_unit_quaternions(rotations_wxyz):
+    """The 2 + 10 + 10 + 10 rotation word of the compressed PLY: the largest component (by magnitude, made positive) is
+    dropped, its index goes to the top two bits, the other three follow in w, x, y, z order scaled by sqrt(2) / 2 into 10 bits."""
+    q = np.asarray(rotations_wxyz, np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    n = q.shape[0]
+    largest = np.argmax(np.abs(q), axis=1)
+    q = q * np.where(q[np.arange(n), largest] < 0, -1.0, 1.0)[:, None]
+    keep = np.array([[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]])[largest]
+    rest = np.take_along_axis(q, keep, axis=1)
+    u = np.clip(np.floor((rest * (np.sqrt(2) * 0.5) + 0.5) * 1023 + 0.5), 0, 1023).astype(np.uint32)
+    return (largest.astype(np.uint32) << 30) | (u[:, 0] << 20) | (u[:, 1] << 10) | u[:, 2]
+
+
+_PC_CHUNK = ["min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "min_scale_x", "min_scale_y", "min_scale_z",
+             "max_scale_x", "max_scale_y", "max_scale_z"]
+_PC_COLOR = ["min_r", "min_g", "min_b", "max_r", "max_g", "max_b"]
+
+
+def write_compressed_ply(centers, log_scales, rotations, rgba, sh=None, color_extremes=False, chunk_order=None, comment=None,
+                         rotation_words=None):
+    """PlayCanvas / SuperSplat compressed PLY (src/loaders/ply/PlayCanvasCompressedPlyParser.js): chunks of 256 splats with
+    fp32 extremes, 11/10/11-bit positions and log scales, 2+10+10+10 rotations of real unit quaternions (w, x, y, z), 8888
+    colours, and an `sh` element of one byte per coefficient.  rgba: floats in 0..1 [n, 4] (with color_extremes the colour
+    is lerped between per-chunk extremes, min_r .. max_b).  sh: float [n, 9|24|45] in the file's order (all R
+    coefficients, then G, then B), coded as round((v + 4) / 8 * 255).  chunk_order: a permutation of the chunk element's
+    property names; comment: a `comment` header line; rotation_words: {splat: uint32} overrides."""
+    n = centers.shape[0]
+    nchunk = (n + 255) // 256
+    chunk_of = np.arange(n) // 256
+    rgba = np.asarray(rgba, np.float64).reshape(n, 4)
+
+    def extremes(v):
+        starts = np.arange(0, n, 256)
+        return np.minimum.reduceat(v, starts, axis=0).astype(np.float32), np.maximum.reduceat(v, starts, axis=0).astype(np.float32)
+
+    def unorm(v, lo, hi, bits):
+        lo, hi = lo.astype(np.float64)[chunk_of], hi.astype(np.float64)[chunk_of]
+        span = np.where(hi > lo, hi - lo, 1.0)
+        t = np.clip((v - lo) / span, 0.0, 1.0)
+        return np.floor(t * ((1 << bits) - 1) + 0.5).astype(np.uint32)
+
+    def pack111011(v, lo, hi):
+        return (unorm(v[:, 0], lo[:, 0], hi[:, 0], 11) << 21) | (unorm(v[:, 1], lo[:, 1], hi[:, 1], 10) << 11) | \
+            unorm(v[:, 2], lo[:, 2], hi[:, 2], 11)
+
+    c64, s64 = np.asarray(centers, np.float64), np.asarray(log_scales, np.float64)
+    plo, phi = extremes(c64)
+    slo, shi = extremes(s64)
+    cols = {nm: a[:, k] for nm, a, k in zip(_PC_CHUNK, [plo] * 3 + [phi] * 3 + [slo] * 3 + [shi] * 3, [0, 1, 2] * 4)}
+    names = list(_PC_CHUNK)
+    if color_extremes:
+        clo, chi = extremes(rgba[:, :3])
+        cols.update({nm: a[:, k] for nm, a, k in zip(_PC_COLOR, [clo] * 3 + [chi] * 3, [0, 1, 2] * 2)})
+        names += _PC_COLOR
+        rgb = np.stack([unorm(rgba[:, k], clo[:, k], chi[:, k], 8) for k in range(3)], axis=1)
+    else:
+        rgb = np.floor(np.clip(rgba[:, :3], 0, 1) * 255 + 0.5).astype(np.uint32)
+    alpha = np.floor(np.clip(rgba[:, 3], 0, 1) * 255 + 0.5).astype(np.uint32)
+    if chunk_order is not None:
+        assert sorted(chunk_order) == sorted(names)
+        names = list(chunk_order)
+    vertex = np.zeros((n, 4), np.uint32)
+    vertex[:, 0] = pack111011(c64, plo, phi)
+    vertex[:, 1] = pack_unit_quaternions(rotations)
+    for i, word in (rotation_words or {}).items():
+        vertex[i, 1] = word
+    vertex[:, 2] = pack111011(s64, slo, shi)
+    vertex[:, 3] = (rgb[:, 0] << 24) | (rgb[:, 1] << 16) | (rgb[:, 2] << 8) | alpha
+    header = "ply\nformat binary_little_endian 1.0\n"
+    if comment:
+        header += f"comment {comment}\n"
+    header += f"element chunk {nchunk}\n" + "".join(f"property float {nm}\n" for nm in names)
+    header += f"element vertex {n}\n" + "".join(f"property uint packed_{nm}\n" for nm in ("position", "rotation", "scale", "color"))
+    body = np.stack([cols[nm] for nm in names], axis=1).astype("<f4").tobytes() + vertex.astype("<u4").tobytes()
+    if sh is not None:
+        sh = np.asarray(sh, np.float64).reshape(n, -1)
+        header += f"element sh {n}\n" + "".join(f"property uchar f_rest_{k}\n" for k in range(sh.shape[1]))
+        body += np.clip(np.floor((sh + 4.0) / 8.0 * 255.0 + 0.5), 0, 255).astype(np.uint8).tobytes()
+    return (header + "end_header\n").encode() + body
 
 
 def write_ksplat(centers, scales, rotations_wxyz, rgba, sh_rows=None, sh_degree=0, compression_level=0, block_size=5.0,

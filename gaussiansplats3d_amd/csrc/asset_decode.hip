@@ -1,5 +1,9 @@
-// asset_decode.hip — the per-splat decode of an opened .ksplat / PLY image on the device: file rows -> the staging layout a
+// asset_decode.hip — the per-splat decode of an opened asset on the device: file rows -> the staging layout a
 // mesh upload commits (gs_mesh_upload_asset) and the sorter's `centers` message (gs_sorter_upload_asset_centers).
+// The kernels take a ROW SOURCE (a template parameter, as XF is one): the .ksplat image (also an INRIA-v1 PLY's level-0
+// image), the 32-byte rows of a .splat, or the 16-byte vertex rows + chunk rows + SH bytes of a PlayCanvas compressed PLY.
+// The last two produce the level-0 tuple in registers through asset_internal.hpp's row arithmetic - the functions the host's
+// image builder calls - so only file rows cross the bus and the level-0 image is never built on this path.
 // The arithmetic is gs_asset_fill's (assets.hip), expression for expression, in fp64 and unfused (this file is built with
 // -ffp-contract=off): only multiplies, adds and double -> float conversions are involved, so the planes are bit-equal to what
 // gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.  Restates, never copies:
@@ -72,12 +76,8 @@ __device__ __forceinline__ uint32_t bucket_index(const AssetView& v, const DevSe
     return b < sec.bucket_count ? b : sec.bucket_count - 1u;    // never past the table
 }
 
-// getSplatCenter (SplatBuffer.js:221-246), narrowed to float as fillSplatCenterArray stores it; XF: through the scene
-// transform first (the double centre, SplatBuffer.js:332-342)
-template <bool XF>
-__device__ __forceinline__ void decode_centre(const AssetView& v, const AssetTransform& t, const DevSection& sec, uint32_t local,
-                                              const uint8_t* row, float c[3]) {
-    double d[3];
+// getSplatCenter (SplatBuffer.js:221-246) in double
+__device__ __forceinline__ void ksplat_centre(const AssetView& v, const DevSection& sec, uint32_t local, const uint8_t* row, double d[3]) {
     if (v.level == 0) {
         for (int k = 0; k < 3; k++) d[k] = ld<float>(row + 4 * k);
     } else {
@@ -88,9 +88,108 @@ __device__ __forceinline__ void decode_centre(const AssetView& v, const AssetTra
             d[k] = (x - (double)sec.scale_range) * sec.scale_factor + bc;
         }
     }
-    if constexpr (XF) xf_centre(t, d, c);
-    else for (int k = 0; k < 3; k++) c[k] = (float)d[k];
 }
+
+// ---- row sources ---------------------------------------------------------------------------------------------------------
+// A source is the kernel argument that says where splat i's values come from.  Its Row gives: the double centre, the doubles
+// of scale and rotation (w, x, y, z) as the fills read them, the colour bytes, and the SH of file index `src` in each of the
+// three forms the store needs (widened double for the rotated fill, half bits, the level-2 byte).
+struct KsplatSource : AssetView {
+    struct Row {
+        const AssetView& v;
+        const DevSection& sec;
+        uint32_t local;
+        const uint8_t* row;
+        __device__ __forceinline__ const uint8_t* srow() const { return row + asset_center_bytes(v.level); }
+        __device__ __forceinline__ const uint8_t* crow() const { return srow() + asset_center_bytes(v.level) + asset_rotation_bytes(v.level); }
+        __device__ __forceinline__ void centre(double d[3]) const { ksplat_centre(v, sec, local, row, d); }
+        __device__ __forceinline__ void scale_rotation(double s[3], double q[4]) const {
+            for (int k = 0; k < 3; k++) s[k] = comp(v.level, srow(), k);
+            for (int k = 0; k < 4; k++) q[k] = comp(v.level, srow(), 3 + k);
+        }
+        __device__ __forceinline__ uint32_t colour() const { return ld<uint32_t>(crow()); }
+        __device__ __forceinline__ double sh_wide(uint32_t src, double lo, double hi) const { return sh_widen(v.level, crow() + 4, src, lo, hi); }
+        __device__ __forceinline__ uint16_t sh_half(uint32_t src) const {      // level 0 through the half rule, level 1 bits
+            return v.level == 0 ? to_half_three((double)ld<float>(crow() + 4 + 4 * src)) : ld<uint16_t>(crow() + 4 + 2 * src);
+        }
+        __device__ __forceinline__ uint8_t sh_byte(uint32_t src) const { return crow()[4 + src]; }
+    };
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        const DevSection& sec = section_of(*this, splat);
+        const uint32_t local = splat - sec.count_offset;
+        return Row{*this, sec, local, image + sec.data_off + (long long)sec.bytes_per_splat * local};
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const { row(splat).centre(d); }
+};
+
+// the level-0 tuple in registers, as the two row formats produce it (fp32 values of a level-0 row, widened as the fills widen them)
+struct TupleRow {
+    Level0Tuple t;
+    const uint8_t* sh;             // compressed PLY: the splat's SH bytes (unaligned: 9 / 24 / 45 per splat)
+    uint32_t read_coeff;
+    __device__ __forceinline__ void centre(double d[3]) const { for (int k = 0; k < 3; k++) d[k] = t.c[k]; }
+    __device__ __forceinline__ void scale_rotation(double s[3], double q[4]) const {
+        for (int k = 0; k < 3; k++) s[k] = t.s[k];
+        for (int k = 0; k < 4; k++) q[k] = t.r[k];
+    }
+    __device__ __forceinline__ uint32_t colour() const {
+        return (uint32_t)t.rgba[0] | ((uint32_t)t.rgba[1] << 8) | ((uint32_t)t.rgba[2] << 16) | ((uint32_t)t.rgba[3] << 24);
+    }
+    __device__ __forceinline__ double sh_wide(uint32_t src, double, double) const { return (double)pc_row_sh(sh, read_coeff, src); }
+    __device__ __forceinline__ uint16_t sh_half(uint32_t src) const { return to_half_three((double)pc_row_sh(sh, read_coeff, src)); }
+    __device__ __forceinline__ uint8_t sh_byte(uint32_t) const { return 0; }       // sh_level is 1: never stored as bytes
+};
+
+// .splat: rows start at the allocation-aligned staging base, so a 32-byte row is two 16-byte loads
+struct SplatSource {
+    const uint4* rows;             // row 0 = asset splat `base`
+    uint32_t base;
+    uint32_t level, sh_degree, ncomp;   // 0, 0, 0
+    using Row = TupleRow;
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        const uint4 a = rows[2 * (size_t)(splat - base)], b = rows[2 * (size_t)(splat - base) + 1];
+        const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        Row r;
+        splat_row_tuple(w, r.t);
+        r.sh = nullptr;
+        r.read_coeff = 0;
+        return r;
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const {    // the first three floats of the row
+        const uint4 a = rows[2 * (size_t)(splat - base)];
+        d[0] = __builtin_bit_cast(float, a.x); d[1] = __builtin_bit_cast(float, a.y); d[2] = __builtin_bit_cast(float, a.z);
+    }
+};
+
+// compressed PLY: one 16-byte load per vertex row; the chunk of a splat is floor(i / 256) by ABSOLUTE splat index, so a
+// workgroup of 256 consecutive splats touches at most two chunk rows; the chunk rows keep their file stride and order
+struct CompressedSource {
+    const uint4* vertex;           // row 0 = asset splat `base`
+    const uint8_t* chunks;         // row 0 = chunk base / 256
+    const uint8_t* sh;             // row 0 = asset splat `base`
+    uint32_t base;
+    uint32_t level, sh_degree, ncomp;   // 0, the output degree, 0 / 9 / 24
+    PcLayout layout;
+    using Row = TupleRow;
+    __device__ __forceinline__ const uint8_t* chunk_of(uint32_t splat) const {
+        return chunks + (size_t)layout.chunk_stride * (splat / 256u - base / 256u);
+    }
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        const uint4 a = vertex[splat - base];
+        const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+        Row r;
+        pc_row_tuple(w, chunk_of(splat), layout, r.t);
+        r.sh = sh + (size_t)layout.sh_stride * (splat - base);
+        r.read_coeff = layout.read_coeff;
+        return r;
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const {    // the position word and six extremes only
+        const uint32_t* words = reinterpret_cast<const uint32_t*>(vertex + (splat - base));
+        float c[3];
+        pc_row_centre(words[layout.word[0]], chunk_of(splat), layout, c);
+        for (int k = 0; k < 3; k++) d[k] = c[k];
+    }
+};
 
 struct NoTransform { uint32_t none; };   // the untransformed instantiations carry no matrix in their kernel argument
 struct DevTransform {          // the transformed ones: 16 + 9 + 25 doubles and the file's 8-bit SH range, by value
@@ -99,10 +198,21 @@ struct DevTransform {          // the transformed ones: 16 + 9 + 25 doubles and 
 };
 __device__ __forceinline__ const AssetTransform& transform_of(const DevTransform& x) { return x.t; }
 __device__ __forceinline__ AssetTransform transform_of(const NoTransform&) { return AssetTransform(); }   // never read
+__device__ __forceinline__ double sh_lo(const DevTransform& x) { return x.sh_min; }
+__device__ __forceinline__ double sh_hi(const DevTransform& x) { return x.sh_max; }
+__device__ __forceinline__ double sh_lo(const NoTransform&) { return 0.0; }
+__device__ __forceinline__ double sh_hi(const NoTransform&) { return 0.0; }
+
+// the double centre through the scene transform (SplatBuffer.js:332-342) or narrowed to float as fillSplatCenterArray stores it
+template <bool XF>
+__device__ __forceinline__ void store_centre(const AssetTransform& t, const double d[3], float c[3]) {
+    if constexpr (XF) xf_centre(t, d, c);
+    else for (int k = 0; k < 3; k++) c[k] = (float)d[k];
+}
 
 // One thread per splat: asset splat first + i -> element i of the staging arrays (MeshStaging).
-template <bool XF, class Transform>
-__global__ __launch_bounds__(256) void k_asset_decode(AssetView v, Transform xf, uint32_t first, uint32_t count, uint32_t min_alpha,
+template <class Source, bool XF, class Transform>
+__global__ __launch_bounds__(256) void k_asset_decode(Source v, Transform xf, uint32_t first, uint32_t count, uint32_t min_alpha,
                                                       float* __restrict__ centers, float* __restrict__ cov_f32,
                                                       uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
                                                       uint16_t* __restrict__ sh_f16, uint8_t* __restrict__ sh_u8) {
@@ -110,18 +220,20 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, Transform xf,
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
     const AssetTransform& t = transform_of(xf);
-    const DevSection& sec = section_of(v, first + i);
-    const uint32_t local = first + i - sec.count_offset;
-    const uint8_t* row = v.image + sec.data_off + (long long)sec.bytes_per_splat * local;
-    float c[3];
-    decode_centre<XF>(v, t, sec, local, row, c);
-    for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = c[k];
-
-    const uint8_t* srow = row + asset_center_bytes(v.level);
+    const typename Source::Row row = v.row(first + i);
     {
-        const double sx = comp(v.level, srow, 0), sy = comp(v.level, srow, 1), sz = comp(v.level, srow, 2);
+        double d[3];
+        float c[3];
+        row.centre(d);
+        store_centre<XF>(t, d, c);
+        for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = c[k];
+    }
+    {
+        double s3[3], q4[4];
+        row.scale_rotation(s3, q4);
+        const double sx = s3[0], sy = s3[1], sz = s3[2];
         // rotation.set(x = f4, y = f5, z = f6, w = f3): NOT normalised (SplatBuffer.js:539-542)
-        const double w = comp(v.level, srow, 3), x = comp(v.level, srow, 4), y = comp(v.level, srow, 5), z = comp(v.level, srow, 6);
+        const double w = q4[0], x = q4[1], y = q4[2], z = q4[3];
         // Matrix4.makeRotationFromQuaternion = compose(zero, q, one) (three r160)
         const double x2 = x + x, y2 = y + y, z2 = z + z;
         const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
@@ -149,22 +261,20 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, Transform xf,
             else cov_f16[6 * (size_t)i + k] = XF ? xf_f16(e[k]) : to_half_three(e[k]);
         }
     }
-    const uint8_t* crow = srow + asset_center_bytes(v.level) + asset_rotation_bytes(v.level);
     {   // fillSplatColorArray (SplatBuffer.js:551-575)
-        const uint32_t alpha = crow[3];
-        rgba[i] = (uint32_t)crow[0] | ((uint32_t)crow[1] << 8) | ((uint32_t)crow[2] << 16) | ((alpha >= min_alpha ? alpha : 0u) << 24);
+        const uint32_t word = row.colour(), alpha = word >> 24;
+        rgba[i] = (word & 0x00FFFFFFu) | ((alpha >= min_alpha ? alpha : 0u) << 24);
     }
     if constexpr (XF) {   // fillSphericalHarmonicsArray with a transform: widened, rotated, converted from level 0
         if (v.ncomp)
-            xf_sh(t, v.level, v.sh_degree, xf.sh_min, xf.sh_max, crow + 4, [&](uint32_t dst, double val) {
-                if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = to_uint8_range(val, xf.sh_min, xf.sh_max);
+            xf_sh(t, v.sh_degree, [&](uint32_t src) { return row.sh_wide(src, sh_lo(xf), sh_hi(xf)); }, [&](uint32_t dst, double val) {
+                if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = to_uint8_range(val, sh_lo(xf), sh_hi(xf));
                 else sh_f16[(size_t)v.ncomp * i + dst] = xf_f16(val);
             });
     } else if (v.ncomp) {   // ... without one: level 0 through the half rule, level 1 bits, level 2 bytes
-        const uint8_t* hrow = crow + 4;
         auto emit = [&](uint32_t dst, uint32_t src) {
-            if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = hrow[src];
-            else sh_f16[(size_t)v.ncomp * i + dst] = v.level == 0 ? to_half_three((double)ld<float>(hrow + 4 * src)) : ld<uint16_t>(hrow + 2 * src);
+            if (sh_u8) sh_u8[(size_t)v.ncomp * i + dst] = row.sh_byte(src);
+            else sh_f16[(size_t)v.ncomp * i + dst] = row.sh_half(src);
         };
         for (uint32_t q = 0; q < 3; q++)                                               // set3FromArray(stride 3, base c)
             for (uint32_t ch = 0; ch < 3; ch++) emit(3 * q + ch, q + 3 * ch);
@@ -178,16 +288,16 @@ __global__ __launch_bounds__(256) void k_asset_decode(AssetView v, Transform xf,
 // have put it.  integer: Math.round(fp32 centre * 1000.0) as util.integer_centers pins it - floor(v + 0.5) in double - with
 // w = 1000; a NaN or a value outside int32 becomes INT32_MIN (what the host's double -> int32 conversion stores).  Else the float
 // centre with w = 1.0.
-template <bool XF, class Transform>
-__global__ __launch_bounds__(256) void k_asset_centers(AssetView v, Transform xf, uint32_t first, uint32_t count, int integer,
+template <class Source, bool XF, class Transform>
+__global__ __launch_bounds__(256) void k_asset_centers(Source v, Transform xf, uint32_t first, uint32_t count, int integer,
                                                        uint4* __restrict__ aos) {
 #pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
-    const DevSection& sec = section_of(v, first + i);
-    const uint32_t local = first + i - sec.count_offset;
+    double d[3];
     float c[3];
-    decode_centre<XF>(v, transform_of(xf), sec, local, v.image + sec.data_off + (long long)sec.bytes_per_splat * local, c);
+    v.centre(first + i, d);
+    store_centre<XF>(transform_of(xf), d, c);
     uint32_t o[3];
     for (int k = 0; k < 3; k++) {
         if (integer) {
@@ -202,7 +312,7 @@ __global__ __launch_bounds__(256) void k_asset_centers(AssetView v, Transform xf
 
 // Uploads what the kernels read of splats [first, first + count), count > 0, in range: their rows (one contiguous piece of the
 // file), the bucket tables of their sections and the section table.  Synchronises `st`: the host table is a local.
-int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, AssetView* view) {
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, KsplatSource* view, bool /*centres_only*/) {
     const uint32_t last = first + count - 1u;
     std::vector<DevSection> table;
     std::vector<uint32_t> partial;
@@ -260,11 +370,46 @@ int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceIm
     return GS_OK;
 }
 
+// .splat: rows [first, first + count) at the staging base
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, SplatSource* src, bool /*centres_only*/) {
+    const size_t bytes = 32 * (size_t)count;
+    GS_TRY(dev.bytes.ensure(bytes));
+    GS_HIP(hipMemcpyAsync(dev.bytes.p, a->file.data() + 32 * (size_t)first, bytes, hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st));
+    *src = SplatSource{dev.bytes.as<uint4>(), first, 0u, 0u, 0u};
+    return GS_OK;
+}
+
+// compressed PLY: the range's 16-byte vertex rows, the chunk rows first / 256 .. (first + count - 1) / 256 at their file stride,
+// and - unless only centres are wanted - the range's SH rows (one splat's bytes are contiguous in the file); each piece starts
+// 16-byte aligned.  gs_asset_open
+// proved that the file holds all three.
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, CompressedSource* src,
+                bool centres_only) {
+    const uint32_t chunk_lo = first / 256u, chunk_hi = (first + count - 1u) / 256u;
+    const uint32_t ncomp = sh_components(a->sh_degree);
+    const size_t vertex_bytes = 16 * (size_t)count, chunk_bytes = (size_t)a->pc.chunk_stride * (chunk_hi - chunk_lo + 1u),
+                 sh_bytes = ncomp && !centres_only ? (size_t)a->pc.sh_stride * count : 0;
+    const size_t chunk_off = vertex_bytes, sh_off = chunk_off + ((chunk_bytes + 15) & ~(size_t)15);
+    GS_TRY(dev.bytes.ensure(sh_off + ((sh_bytes + 15) & ~(size_t)15)));
+    uint8_t* image = dev.bytes.as<uint8_t>();
+    GS_HIP(hipMemcpyAsync(image, a->file.data() + a->pc_vertex_base + 16 * (size_t)first, vertex_bytes, hipMemcpyHostToDevice, st));
+    GS_HIP(hipMemcpyAsync(image + chunk_off, a->file.data() + a->pc_chunk_base + (size_t)a->pc.chunk_stride * chunk_lo, chunk_bytes,
+                          hipMemcpyHostToDevice, st));
+    if (sh_bytes)
+        GS_HIP(hipMemcpyAsync(image + sh_off, a->file.data() + a->pc_sh_base + (size_t)a->pc.sh_stride * first, sh_bytes,
+                              hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st));
+    *src = CompressedSource{reinterpret_cast<const uint4*>(image), image + chunk_off, image + sh_off, first, 0u, a->sh_degree, ncomp, a->pc};
+    return GS_OK;
+}
+
 // gs_mesh_upload_asset's source: a segment of the staging is filled by k_asset_decode
 DevTransform dev_transform(const gs_asset* a) { return DevTransform{a->xf, a->sh_min, a->sh_max}; }
 
+template <class Source>
 struct AssetRows : MeshUploadSource {
-    AssetView view;
+    Source view;
     const gs_asset* asset;
     uint32_t first, min_alpha;
     int fill(gs_mesh* m, uint32_t o, uint32_t count, const MeshStaging& s, hipStream_t st) override {
@@ -275,15 +420,42 @@ struct AssetRows : MeshUploadSource {
         uint16_t* sh16 = s.sh_u8 ? nullptr : (uint16_t*)(s.base + s.off_sh);
         uint8_t* sh8 = s.sh_u8 ? (uint8_t*)(s.base + s.off_sh) : nullptr;
         if (asset->has_transform)
-            hipLaunchKernelGGL((k_asset_decode<true, DevTransform>), grid, block, 0, st, view, dev_transform(asset), first + o, count,
+            hipLaunchKernelGGL((k_asset_decode<Source, true, DevTransform>), grid, block, 0, st, view, dev_transform(asset), first + o, count,
                                min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
         else
-            hipLaunchKernelGGL((k_asset_decode<false, NoTransform>), grid, block, 0, st, view, NoTransform{0u}, first + o, count,
+            hipLaunchKernelGGL((k_asset_decode<Source, false, NoTransform>), grid, block, 0, st, view, NoTransform{0u}, first + o, count,
                                min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
         GS_HIP(hipGetLastError());
         return GS_OK;
     }
 };
+
+template <class Source>
+int mesh_upload_rows(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first, uint32_t count, uint32_t min_alpha, bool mesh_u8) {
+    AssetRows<Source> src;
+    GS_TRY(asset_stage(a, first, count, m->asset_dev, m->ctx->stream, &src.view, false));
+    src.asset = a;
+    src.first = first;
+    src.min_alpha = min_alpha;
+    src.stages_sh_u8 = mesh_u8;
+    return gs_mesh_upload_from(m, from, count, src);
+}
+
+template <class Source>
+int sorter_upload_rows(gs_sorter* s, uint32_t from, gs_asset* a, uint32_t first, uint32_t count) {
+    Source view;
+    GS_TRY(asset_stage(a, first, count, s->asset_dev, s->stream, &view, true));
+    const dim3 grid((count + 255u) / 256u), block(256);
+    const int integer = (s->flags & GS_SORT_INTEGER) ? 1 : 0;
+    if (a->has_transform)
+        hipLaunchKernelGGL((k_asset_centers<Source, true, DevTransform>), grid, block, 0, s->stream, view, dev_transform(a), first, count,
+                           integer, s->caos.as<uint4>() + from);
+    else
+        hipLaunchKernelGGL((k_asset_centers<Source, false, NoTransform>), grid, block, 0, s->stream, view, NoTransform{0u}, first, count,
+                           integer, s->caos.as<uint4>() + from);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
 
 }  // namespace
 
@@ -300,13 +472,9 @@ int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first,
     if (count == 0) return GS_OK;
     ScopedDevice sd(m->ctx->device);
     // (an earlier call's decode kernels have finished: every upload synchronises before it returns)
-    AssetRows src;
-    GS_TRY(asset_stage(a, first, count, m->asset_dev, m->ctx->stream, &src.view));
-    src.asset = a;
-    src.first = first;
-    src.min_alpha = min_alpha;
-    src.stages_sh_u8 = mesh_u8;
-    return gs_mesh_upload_from(m, from, count, src);
+    if (a->rows == ASSET_ROWS_SPLAT) return mesh_upload_rows<SplatSource>(m, from, a, first, count, min_alpha, mesh_u8);
+    if (a->rows == ASSET_ROWS_COMPRESSED_PLY) return mesh_upload_rows<CompressedSource>(m, from, a, first, count, min_alpha, mesh_u8);
+    return mesh_upload_rows<KsplatSource>(m, from, a, first, count, min_alpha, mesh_u8);
 }
 
 int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uint32_t first, uint32_t count,
@@ -319,17 +487,9 @@ int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uin
                "a dynamic sorter takes untransformed centres: dynamic mode applies scene transforms per frame and never bakes them");
     if (count == 0) return GS_OK;
     ScopedDevice sd(s->ctx->device);
-    AssetView view;
-    GS_TRY(asset_stage(a, first, count, s->asset_dev, s->stream, &view));
-    const dim3 grid((count + 255u) / 256u), block(256);
-    const int integer = (s->flags & GS_SORT_INTEGER) ? 1 : 0;
-    if (a->has_transform)
-        hipLaunchKernelGGL((k_asset_centers<true, DevTransform>), grid, block, 0, s->stream, view, dev_transform(a), first, count, integer,
-                           s->caos.as<uint4>() + from);
-    else
-        hipLaunchKernelGGL((k_asset_centers<false, NoTransform>), grid, block, 0, s->stream, view, NoTransform{0u}, first, count, integer,
-                           s->caos.as<uint4>() + from);
-    GS_HIP(hipGetLastError());
+    if (a->rows == ASSET_ROWS_SPLAT) GS_TRY(sorter_upload_rows<SplatSource>(s, from, a, first, count));
+    else if (a->rows == ASSET_ROWS_COMPRESSED_PLY) GS_TRY(sorter_upload_rows<CompressedSource>(s, from, a, first, count));
+    else GS_TRY(sorter_upload_rows<KsplatSource>(s, from, a, first, count));
     return gs_sorter_commit_centers(s, from, count, scene_indexes);
 }
 

@@ -1,5 +1,6 @@
 // asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share: the parsed
-// .ksplat image and the two half-float rules, each said once for both sides.
+// .ksplat image, the two half-float rules, and the per-row arithmetic of the formats whose file rows are decoded on both
+// sides (.splat, PlayCanvas compressed PLY), each said once for both sides.
 #pragma once
 #include <math.h>
 
@@ -91,15 +92,14 @@ __host__ __device__ inline double sh_widen(uint32_t level, const uint8_t* p, uin
 }
 
 // fillSphericalHarmonicsArray with a transform (SplatBuffer.js:678-729): widen, rotateSphericalHarmonics3 / 5 (dot3 / dot5:
-// the accumulator starts at 0, the terms are added in order), convert FROM LEVEL 0 to the output level.  hrow: the splat's SH
-// in the file; out(dst, v) stores component dst of the splat.
-template <class Out>
-__host__ __device__ inline void xf_sh(const AssetTransform& t, uint32_t level, uint32_t degree, double sh_min, double sh_max,
-                                      const uint8_t* hrow, Out out) {
+// the accumulator starts at 0, the terms are added in order), convert FROM LEVEL 0 to the output level.  wide(src): the
+// widened value of the splat's SH with file index src; out(dst, v) stores component dst of the splat.
+template <class In, class Out>
+__host__ __device__ inline void xf_sh(const AssetTransform& t, uint32_t degree, In wide, Out out) {
 #pragma clang fp contract(off)
     for (uint32_t ch = 0; ch < 3; ch++) {                                              // set3FromArray(stride 3, base c)
         double in[3];
-        for (uint32_t q = 0; q < 3; q++) in[q] = sh_widen(level, hrow, q + 3 * ch, sh_min, sh_max);
+        for (uint32_t q = 0; q < 3; q++) in[q] = wide(q + 3 * ch);
         for (uint32_t j = 0; j < 3; j++) {
             double acc = 0.0;
             for (uint32_t q = 0; q < 3; q++) acc = acc + in[q] * t.sh1[j][q];
@@ -109,13 +109,195 @@ __host__ __device__ inline void xf_sh(const AssetTransform& t, uint32_t level, u
     if (degree < 2) return;
     for (uint32_t ch = 0; ch < 3; ch++) {                                              // set3FromArray(stride 5, base 9 + c)
         double in[5];
-        for (uint32_t q = 0; q < 5; q++) in[q] = sh_widen(level, hrow, 9 + q + 5 * ch, sh_min, sh_max);
+        for (uint32_t q = 0; q < 5; q++) in[q] = wide(9 + q + 5 * ch);
         for (uint32_t j = 0; j < 5; j++) {
             double acc = 0.0;
             for (uint32_t q = 0; q < 5; q++) acc = acc + in[q] * t.sh2[j][q];
             out(9 + 3 * j + ch, acc);
         }
     }
+}
+
+// ---- file rows decoded on both sides: .splat and PlayCanvas compressed PLY ---------------------------------------------------
+// file row (+ chunk row) -> the level-0 tuple the reference would store for it (SplatBuffer level 0: 3 centre floats, 3 scales,
+// 4 rotation floats in file slot order, 4 colour bytes) and the SH floats.  The host image builder (assets.hip) and the row
+// sources of the kernels (asset_decode.hip) both call these; every operation is IEEE-exact on both sides (+ - * / sqrt floor
+// ceil and conversions, unfused), and exp is row_exp below, one implementation compiled for both.  Restates, never copies:
+//   .splat row        src/loaders/splat/SplatParser.js:13-56
+//   compressed row    src/loaders/ply/PlayCanvasCompressedPlyParser.js:21-65 (unpack*, lerp), :379-432 (decompressBaseSplat),
+//                     :434-460 (decompressSphericalHarmonics) + SplatBuffer.writeSplatDataToSectionBuffer :1092-1124
+struct Level0Tuple {
+    float c[3], s[3], r[4];    // r: the level-0 row's four rotation floats in slot order (slot 0 is read back as w)
+    uint8_t rgba[4];
+};
+
+// A NaN this decode GENERATES (lerp over infinite extremes, sqrt of a negative) has one sign on the host and the other on the
+// device; a typed-array store keeps no particular NaN either.  Stored as the canonical quiet NaN on both sides (xf_f32's rule).
+__host__ __device__ inline float row_f32(double v) { return xf_f32(v); }
+
+// e^x in double for the compressed PLY's scales.  The argument reduction and the degree-5 remainder polynomial of the freely
+// distributable fdlibm e_exp (Sun Microsystems, 1993; the algorithm JavaScript engines ship as Math.exp), restated with
+// + - * / only, so the host and the device compute the same bits - libm here and the device library there would agree to 1 ulp
+// and then disagree after narrowing to fp32 about once in 2^29 values.
+__host__ __device__ inline double row_exp(double x) {
+#pragma clang fp contract(off)
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, inv_ln2 = 1.44269504088896338700e+00;
+    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
+                 P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+    const uint64_t bits = __builtin_bit_cast(uint64_t, x);
+    const uint32_t hx = (uint32_t)(bits >> 32) & 0x7FFFFFFFu;
+    const int neg = (int)(bits >> 63);
+    if (hx >= 0x40862E42u) {                                               // |x| >= 709.78: NaN, inf, overflow, underflow
+        if (hx >= 0x7FF00000u) {
+            if ((bits & 0x000FFFFFFFFFFFFFull) != 0) return x + x;        // NaN
+            return neg ? 0.0 : x;
+        }
+        if (x > 7.09782712893383973096e+02) return __builtin_bit_cast(double, 0x7FF0000000000000ull);
+        if (x < -7.45133219101941108420e+02) return 0.0;
+    }
+    double hi = 0.0, lo = 0.0;
+    int k = 0;
+    if (hx > 0x3FD62E42u) {                                                // |x| > 0.5 ln2
+        if (hx < 0x3FF0A2B2u) {                                            // and < 1.5 ln2
+            hi = neg ? x + ln2_hi : x - ln2_hi;
+            lo = neg ? -ln2_lo : ln2_lo;
+            k = neg ? -1 : 1;
+        } else {
+            k = (int)(inv_ln2 * x + (neg ? -0.5 : 0.5));
+            const double t = (double)k;
+            hi = x - t * ln2_hi;
+            lo = t * ln2_lo;
+        }
+        x = hi - lo;
+    } else if (hx < 0x3E300000u) {                                         // |x| < 2^-28
+        return 1.0 + x;
+    }
+    const double t = x * x;
+    const double c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    if (k == 0) return 1.0 - ((x * c) / (c - 2.0) - x);
+    const double y = 1.0 - ((lo - (x * c) / (2.0 - c)) - hi);
+    if (k >= -1021) {
+        if (k == 1024) return y * 2.0 * __builtin_bit_cast(double, 0x7FE0000000000000ull);
+        return y * __builtin_bit_cast(double, (uint64_t)(0x3FF + k) << 52);
+    }
+    return y * __builtin_bit_cast(double, (uint64_t)(0x3FF + k + 1000) << 52) * __builtin_bit_cast(double, 0x0170000000000000ull);   // 2^-1000
+}
+
+// Quaternion.normalize (three r160) on q = x, y, z, w
+__host__ __device__ inline void row_normalize(double q[4]) {
+#pragma clang fp contract(off)
+    double l = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (l == 0) { q[0] = q[1] = q[2] = 0; q[3] = 1; }
+    else { l = 1 / l; for (int k = 0; k < 4; k++) q[k] = q[k] * l; }
+}
+
+// .splat: the row's eight dwords (centre 3 x f32, scale 3 x f32, RGBA, rotation bytes).  Scales and colours are copied;
+// the quaternion is normalised once and stored w, x, y, z (SplatParser.js:28-49)
+__host__ __device__ inline void splat_row_tuple(const uint32_t w[8], Level0Tuple& t) {
+#pragma clang fp contract(off)
+    for (int k = 0; k < 3; k++) t.c[k] = __builtin_bit_cast(float, w[k]);
+    for (int k = 0; k < 3; k++) t.s[k] = __builtin_bit_cast(float, w[3 + k]);
+    for (int k = 0; k < 4; k++) t.rgba[k] = (uint8_t)(w[6] >> (8 * k));
+    const double b0 = (double)(w[7] & 255u), b1 = (double)((w[7] >> 8) & 255u), b2 = (double)((w[7] >> 16) & 255u), b3 = (double)(w[7] >> 24);
+    double q[4] = {(b1 - 128) / 128, (b2 - 128) / 128, (b3 - 128) / 128, (b0 - 128) / 128};
+    row_normalize(q);
+    t.r[0] = (float)q[3]; t.r[1] = (float)q[0]; t.r[2] = (float)q[1]; t.r[3] = (float)q[2];
+}
+
+// PlayCanvas compressed PLY: where a splat's values lie in its 16-byte vertex row and its chunk row, from the header
+enum { PC_MIN_POS = 0, PC_MAX_POS = 3, PC_MIN_SCALE = 6, PC_MAX_SCALE = 9, PC_MIN_COL = 12, PC_MAX_COL = 15 };
+struct PcLayout {
+    int32_t ext[18];           // byte offset in a chunk row of min_x/y/z, max_x/y/z, min_scale_x/y/z, max_scale_x/y/z, min_r/g/b,
+                               // max_r/g/b (float); the colour ones are -1 when the chunk element has none
+    uint32_t word[4];          // dword of packed_position, packed_rotation, packed_scale, packed_color in a vertex row
+    uint32_t chunk_stride;     // bytes per chunk row
+    uint32_t chunk_aligned;    // stride and every offset are multiples of 4: a chunk float is one aligned load
+    uint32_t sh_stride;        // SH properties (bytes) per splat: 9 / 24 / 45 for a well-formed file
+    uint32_t read_coeff;       // readSHCoeff 3 / 8 / 15: the stride of shArray[j * readSHCoeff + k]
+};
+
+__host__ __device__ inline double pc_chunk_f32(const uint8_t* chunk, const PcLayout& L, int which) {
+    float v;
+    const uint8_t* p = chunk + L.ext[which];
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (L.chunk_aligned) return (double)*reinterpret_cast<const float*>(p);   // the staged chunk rows start 16-byte aligned
+#endif
+    __builtin_memcpy(&v, p, 4);
+    return (double)v;
+}
+__host__ __device__ inline double pc_unorm(uint32_t value, uint32_t bits) {           // unpackUnorm: divides in double
+    const uint32_t t = (1u << bits) - 1u;
+    return (double)(value & t) / (double)t;
+}
+__host__ __device__ inline double pc_lerp(double a, double b, double t) {
+#pragma clang fp contract(off)
+    return a * (1 - t) + b * t;
+}
+__host__ __device__ inline void pc_unpack111011(uint32_t v, double out[3]) {
+    out[0] = pc_unorm(v >> 21, 11); out[1] = pc_unorm(v >> 11, 10); out[2] = pc_unorm(v, 11);
+}
+
+// the centre alone (what the sorter's message needs): the position word and the chunk's six position extremes
+__host__ __device__ inline void pc_row_centre(uint32_t position, const uint8_t* chunk, const PcLayout& L, float c[3]) {
+    double p[3];
+    pc_unpack111011(position, p);
+    for (int k = 0; k < 3; k++) c[k] = row_f32(pc_lerp(pc_chunk_f32(chunk, L, PC_MIN_POS + k), pc_chunk_f32(chunk, L, PC_MAX_POS + k), p[k]));
+}
+
+// JS Math.round: the nearest integer, ties towards +inf
+__host__ __device__ inline double js_round(double v) {
+    const double r = ceil(v);
+    return r - 0.5 > v ? r - 1.0 : r;
+}
+
+// decompressBaseSplat, then the level-0 store of writeSplatDataToSectionBuffer: normalise, `|| 0` on the scales and colours
+__host__ __device__ inline void pc_row_tuple(const uint32_t w[4], const uint8_t* chunk, const PcLayout& L, Level0Tuple& t) {
+#pragma clang fp contract(off)
+    pc_row_centre(w[L.word[0]], chunk, L, t.c);
+    {   // unpackRot: 2 + 10 + 10 + 10, the largest component dropped and rebuilt
+        const uint32_t v = w[L.word[1]];
+        const double norm = 1.0 / (1.4142135623730951 * 0.5);                          // 1.0 / (Math.sqrt(2) * 0.5)
+        const double a = (pc_unorm(v >> 20, 10) - 0.5) * norm, b = (pc_unorm(v >> 10, 10) - 0.5) * norm, c = (pc_unorm(v, 10) - 0.5) * norm;
+        const double m = sqrt(1.0 - (a * a + b * b + c * c));
+        double q[4];                                                                   // Quaternion.set(x, y, z, w)
+        switch (v >> 30) {
+            case 0: q[0] = m; q[1] = a; q[2] = b; q[3] = c; break;
+            case 1: q[0] = a; q[1] = m; q[2] = b; q[3] = c; break;
+            case 2: q[0] = a; q[1] = b; q[2] = m; q[3] = c; break;
+            default: q[0] = a; q[1] = b; q[2] = c; q[3] = m; break;
+        }
+        row_normalize(q);                                                              // tempRot.normalize() :1093-1094
+        for (int k = 0; k < 4; k++) t.r[k] = row_f32(q[k]);                            // rot.set([x, y, z, w]) :1112
+    }
+    {
+        double s[3];
+        pc_unpack111011(w[L.word[2]], s);
+        for (int k = 0; k < 3; k++) {
+            const double e = row_exp(pc_lerp(pc_chunk_f32(chunk, L, PC_MIN_SCALE + k), pc_chunk_f32(chunk, L, PC_MAX_SCALE + k), s[k]));
+            t.s[k] = (float)(e == e ? e : 0.0);                                        // `|| 0`
+        }
+    }
+    {   // unpack8888
+        const uint32_t v = w[L.word[3]];
+        for (int k = 0; k < 3; k++) {
+            const double c = pc_unorm(v >> (24 - 8 * k), 8);
+            double o;
+            if (L.ext[PC_MIN_COL + k] >= 0 && L.ext[PC_MAX_COL + k] >= 0)
+                o = clampd(js_round(pc_lerp(pc_chunk_f32(chunk, L, PC_MIN_COL + k), pc_chunk_f32(chunk, L, PC_MAX_COL + k), c) * 255), 0, 255);
+            else
+                o = clampd(floor(c * 255), 0, 255);
+            t.rgba[k] = o == o ? (uint8_t)o : (uint8_t)0;                              // `|| 0`; an integer in 0..255 otherwise
+        }
+        t.rgba[3] = (uint8_t)clampd(floor(pc_unorm(v, 8) * 255), 0, 255);
+    }
+}
+
+// SH float s (0..8 band 1, 9..23 band 2, the level-0 row's order) of a splat whose SH bytes start at sh: the inverse of the
+// reference's shIndexMap over shArray[j * readSHCoeff + k], value * (8 / 255) - 4, stored fp32
+__host__ __device__ inline float pc_row_sh(const uint8_t* sh, uint32_t read_coeff, uint32_t s) {
+#pragma clang fp contract(off)
+    const uint32_t j = s < 9u ? s / 3u : (s - 9u) / 5u, k = s < 9u ? s % 3u : 3u + (s - 9u) % 5u;
+    return (float)((double)sh[j * read_coeff + k] * (8.0 / 255.0) - 4);
 }
 
 struct AssetSection {
@@ -134,8 +316,16 @@ __host__ __device__ inline uint32_t asset_center_bytes(uint32_t level) { return 
 __host__ __device__ inline uint32_t asset_rotation_bytes(uint32_t level) { return level == 0 ? 16u : 8u; }
 __host__ __device__ inline uint32_t sh_components(uint32_t degree) { return degree == 0 ? 0u : (degree == 1 ? 9u : 24u); }
 
+enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2 };
+
 struct gs_asset {
-    std::vector<uint8_t> buf;              // a .ksplat image (for a PLY: the level-0 section built from it)
+    std::vector<uint8_t> buf;              // a .ksplat image (for an INRIA-v1 PLY: the level-0 section built from it; for the
+                                           // two row formats: built from `file` when a host fill first needs it)
+    uint32_t rows = ASSET_ROWS_KSPLAT;     // what the device decode reads: the image, or the file's own rows
+    std::vector<uint8_t> file;             // .splat / compressed PLY: the file as it was given
+    PcLayout pc = {};                      // compressed PLY: the header's layout
+    size_t pc_chunk_base = 0, pc_vertex_base = 0, pc_sh_base = 0;   // where the three elements start in `file`
+    uint32_t pc_chunk_count = 0;
     uint32_t level = 0, splat_count = 0, sh_degree = 0;
     float scene_center[3] = {0, 0, 0};
     double sh_min = -1.5, sh_max = 1.5;

@@ -1,5 +1,12 @@
-// assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device): INRIA-v1 .ply and .ksplat -> the arrays the render / sort seams
-// consume.  Restates, never copies:
+// assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device): INRIA-v1 .ply,
+// PlayCanvas compressed .ply, .splat and .ksplat -> the arrays the render / sort seams consume.  Restates, never copies:
+//   PLY flavour       src/loaders/ply/PlyParserUtils.js:257-271 (determineHeaderFormatFromHeaderText)
+//   compressed PLY    src/loaders/ply/PlayCanvasCompressedPlyParser.js:74-157 (decodeHeaderText), :159-242 (decodeHeader); the row
+//                     arithmetic (:379-460 + SplatBuffer.js:1092-1124) is in asset_internal.hpp, shared with the device
+//   .splat            src/loaders/splat/SplatParser.js:13-56 (parseToUncompressedSplatBufferSection): the reference's
+//                     progressive, FILE-ORDER path - every splat is kept, alpha is only zeroed at fill time by min_alpha.  The
+//                     `optimizeSplatData: false` array path (SplatLoader.js:12-22) drops splats below minimumAlpha and reorders
+//                     them bucket by bucket; that is not what "file order" means here and is not restated.
 //   PLY header        /root/reference/src/loaders/ply/PlyParserUtils.js:31-165 (decodeSectionHeader, SH field mapping),
 //                     INRIAV1PlyParser.js:20-47 (fields read)
 //   PLY row -> splat  INRIAV1PlyParser.js:114-209 (exp scale, sigmoid opacity, floor/clamp colours, quaternion normalise)
@@ -12,8 +19,11 @@
 //                     transform (dynamicMode) until gs_asset_set_transform gives one (static mode, SplatMesh.js:1872-1899):
 //                     then Vector3.applyMatrix4 :340-342, T3*C*T3^T :461-466, rotated SH :628-637, 684-688, 707-715, 766-817
 //   scene transform   three r160 Matrix4.decompose / Quaternion.setFromRotationMatrix / normalize / makeRotationFromQuaternion
-// A PLY is first laid out as the level-0 section the reference would build from it (file order, i.e. the reference's
-// `optimizeSplatData: false`), so every fill routine reads one format.
+// An INRIA-v1 PLY is first laid out as the level-0 section the reference would build from it (file order, i.e. the reference's
+// `optimizeSplatData: false`), so every fill routine reads one format.  A .splat / compressed PLY asset keeps the file's own
+// rows (what the device decode uploads) and builds that level-0 section when a host fill first needs it.
+// Reference quirk, documented and not reproduced: PlayCanvasCompressedPlyParser.readPly (:297-313) throws on a compressed PLY
+// without an `sh` element (TypeError: 'count' of undefined); the progressive path loads such files, and so does this reader.
 #include <algorithm>
 #include <math.h>
 #include <string>
@@ -310,6 +320,213 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
     return parse_ksplat(a);
 }
 
+// ---- level-0 image of a row format ---------------------------------------------------------------------
+// SplatBuffer.preallocateUncompressed (:1401-1433): header + one section header, rows of 44 + 4 * ncomp bytes
+void level0_header(std::vector<uint8_t>& buf, uint32_t count, uint32_t degree) {
+    const uint32_t bps = 44u + 4u * sh_components(degree);
+    buf.assign(KS_HEADER + KS_SECTION_HEADER + (size_t)bps * count, 0);
+    uint8_t* B = buf.data();
+    auto W32 = [&](size_t off, uint32_t v) { memcpy(B + off, &v, 4); };
+    auto W16 = [&](size_t off, uint16_t v) { memcpy(B + off, &v, 2); };
+    auto WF = [&](size_t off, float v) { memcpy(B + off, &v, 4); };
+    B[0] = 0; B[1] = 1;
+    W32(4, 1); W32(8, 1); W32(12, count); W32(16, count); W16(20, 0);
+    WF(36, -1.5f); WF(40, 1.5f);
+    W32(KS_HEADER + 0, count); W32(KS_HEADER + 4, count); W16(KS_HEADER + 40, (uint16_t)degree);
+}
+
+// What a host fill of a .splat / compressed PLY asset reads: every file row through the shared row arithmetic
+// (asset_internal.hpp) into the level-0 row the reference stores for it.  Built once, on the first fill.
+int build_level0_image(gs_asset* a) {
+    if (a->rows == ASSET_ROWS_KSPLAT || !a->buf.empty()) return GS_OK;
+    const uint32_t n = a->splat_count, degree = a->sh_degree, ncomp = sh_components(degree), bps = 44u + 4u * ncomp;
+    level0_header(a->buf, n, degree);
+    uint8_t* B = a->buf.data() + KS_HEADER + KS_SECTION_HEADER;
+    for (uint32_t i = 0; i < n; i++) {
+        Level0Tuple t;
+        uint8_t* o = B + (size_t)i * bps;
+        if (a->rows == ASSET_ROWS_SPLAT) {
+            uint32_t w[8];
+            memcpy(w, a->file.data() + 32 * (size_t)i, 32);
+            splat_row_tuple(w, t);
+        } else {
+            uint32_t w[4];
+            memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
+            pc_row_tuple(w, a->file.data() + a->pc_chunk_base + (size_t)a->pc.chunk_stride * (i / 256u), a->pc, t);
+            const uint8_t* sh = a->file.data() + a->pc_sh_base + (size_t)a->pc.sh_stride * i;
+            for (uint32_t s = 0; s < ncomp; s++) {
+                const float v = pc_row_sh(sh, a->pc.read_coeff, s);
+                memcpy(o + 44 + 4 * s, &v, 4);
+            }
+        }
+        memcpy(o, t.c, 12); memcpy(o + 12, t.s, 12); memcpy(o + 24, t.r, 16); memcpy(o + 40, t.rgba, 4);
+    }
+    a->sections.clear();
+    const int st = parse_ksplat(a);
+    if (st != GS_OK) a->buf.clear();
+    return st;
+}
+
+int parse_splat(gs_asset* a, const uint8_t* data, size_t bytes) {
+    GS_REQUIRE(bytes % 32 == 0, ".splat: the byte count is not a multiple of the 32-byte row");
+    GS_REQUIRE(bytes / 32 <= 0xFFFFFFFFull, ".splat: more than 2^32 - 1 rows");
+    a->file.assign(data, data + bytes);
+    a->rows = ASSET_ROWS_SPLAT;
+    a->splat_count = (uint32_t)(bytes / 32);
+    a->level = 0;
+    a->sh_degree = 0;
+    return GS_OK;
+}
+
+// PlyParserUtils.determineHeaderFormatFromHeaderText: every trimmed header line is looked at, the LAST match decides
+enum PlyFlavour { PLY_INRIA_V1, PLY_COMPRESSED, PLY_INRIA_V2 };
+PlyFlavour ply_flavour(const uint8_t* data, size_t bytes) {
+    const std::string head((const char*)data, bytes < (1u << 20) ? bytes : (1u << 20));
+    PlyFlavour f = PLY_INRIA_V1;
+    size_t pos = 0;
+    while (pos < head.size()) {
+        size_t nl = head.find('\n', pos);
+        if (nl == std::string::npos) nl = head.size();
+        const std::string line = trim(head.substr(pos, nl - pos));
+        pos = nl + 1;
+        if (line.rfind("element chunk", 0) == 0 || line.find("packed_") != std::string::npos) f = PLY_COMPRESSED;
+        else if (line.rfind("element codebook_centers", 0) == 0) f = PLY_INRIA_V2;
+        else if (line == "end_header") break;
+    }
+    return f;
+}
+
+// decodeHeader + decodeHeaderText.  The reference is memory-safe JavaScript and reads whatever the header describes; here
+// the layout the row decode relies on is proven at open: chunk, vertex[, sh] in that order (readPly reads them in that order
+// whatever the header says), sixteen-byte vertex rows of the four packed uints, float extremes, one uchar per SH property,
+// enough chunks, and every element inside the file.
+int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+    static const char end_token[] = "\nend_header\n";
+    GS_REQUIRE(bytes >= 4 && memcmp(data, "ply\n", 4) == 0, "compressed PLY: the file does not start with 'ply'");
+    const uint8_t* e = std::search(data, data + bytes, (const uint8_t*)end_token, (const uint8_t*)end_token + 12);
+    GS_REQUIRE(e != data + bytes, "compressed PLY: end of header not found");
+    const std::string text((const char*)data, (size_t)(e - data));
+    const size_t header_bytes = (size_t)(e - data) + 12;
+    struct Prop { std::string type, name; uint32_t size; };
+    struct Element { std::string name; uint64_t count; std::vector<Prop> props; uint64_t stride = 0; };
+    std::vector<Element> elements;
+    size_t pos = text.find('\n');                                                       // line 0 ("ply") is not looked at
+    pos = pos == std::string::npos ? text.size() : pos + 1;
+    while (pos < text.size()) {
+        size_t nl = text.find('\n', pos);
+        if (nl == std::string::npos) nl = text.size();
+        const std::string line = text.substr(pos, nl - pos);
+        pos = nl + 1;
+        if (line.rfind("comment ", 0) == 0) continue;
+        std::vector<std::string> words;                                                // String.split(' ')
+        for (size_t b = 0;;) {
+            const size_t sp = line.find(' ', b);
+            words.push_back(line.substr(b, sp == std::string::npos ? sp : sp - b));
+            if (sp == std::string::npos) break;
+            b = sp + 1;
+        }
+        while (words.size() < 3) words.push_back("");
+        if (words[0] == "format") {
+            GS_REQUIRE(words[1] == "binary_little_endian", "compressed PLY: the format is not binary_little_endian");
+        } else if (words[0] == "element") {
+            Element el;
+            el.name = words[1];
+            const std::string& c = words[2];                                           // parseInt(words[2], 10)
+            size_t d = 0;
+            uint64_t v = 0;
+            while (d < c.size() && c[d] >= '0' && c[d] <= '9' && v <= 0xFFFFFFFFull) v = v * 10 + (uint64_t)(c[d++] - '0');
+            GS_REQUIRE(d > 0 && v <= 0xFFFFFFFFull, "compressed PLY: an element count is not a number below 2^32");
+            el.count = v;
+            elements.push_back(el);
+        } else if (words[0] == "property") {
+            static const struct { const char* name; uint32_t size; } types[] = {{"char", 1}, {"uchar", 1}, {"short", 2}, {"ushort", 2},
+                                                                               {"int", 4}, {"uint", 4}, {"float", 4}, {"double", 8}};
+            uint32_t size = 0;
+            for (auto& t : types) if (words[1] == t.name) size = t.size;
+            GS_REQUIRE(size != 0, "compressed PLY: unrecognized property data type");
+            GS_REQUIRE(!elements.empty(), "compressed PLY: a property precedes every element");
+            elements.back().props.push_back({words[1], words[2], size});
+            elements.back().stride += size;
+        } else {
+            GS_REQUIRE(false, "compressed PLY: unrecognized header value (only format / element / property lines are read)");
+        }
+    }
+    GS_REQUIRE(elements.size() >= 2 && elements[0].name == "chunk" && elements[1].name == "vertex",
+               "compressed PLY: the elements must begin with chunk, vertex");
+    const Element &chunk = elements[0], &vertex = elements[1];
+    const Element* sh = elements.size() >= 3 && elements[2].name == "sh" ? &elements[2] : nullptr;
+    for (size_t k = 2; k < elements.size(); k++)
+        GS_REQUIRE(elements[k].name != "chunk" && elements[k].name != "vertex" && (elements[k].name != "sh" || k == 2),
+                   "compressed PLY: a chunk / vertex / sh element is repeated or out of order");
+    size_t off = header_bytes;
+    size_t base[3] = {0, 0, 0};
+    for (size_t k = 0; k < elements.size(); k++) {                                     // every element lies inside the file
+        if (k < 3) base[k] = off;
+        const uint64_t need = elements[k].stride * elements[k].count;                  // < 2^32 * (8 * lines of a 2^40 header): no overflow
+        GS_REQUIRE(elements[k].stride < (1ull << 24), "compressed PLY: an element row of 16 MiB or more");
+        GS_REQUIRE(need <= bytes - off, "compressed PLY: element data exceeds the file");
+        off += (size_t)need;
+    }
+    const uint64_t n = vertex.count;
+    GS_REQUIRE(chunk.count >= (n + 255) / 256, "compressed PLY: fewer chunks than ceil(vertex count / 256)");
+    PcLayout L = {};
+    {
+        static const char* packed[4] = {"packed_position", "packed_rotation", "packed_scale", "packed_color"};
+        GS_REQUIRE(vertex.props.size() == 4 && vertex.stride == 16, "compressed PLY: a vertex row is not the four packed uints");
+        for (int w = 0; w < 4; w++) {
+            int at = -1;
+            for (int k = 3; k >= 0; k--) if (vertex.props[k].name == packed[w]) at = k;
+            GS_REQUIRE(at >= 0 && vertex.props[at].type == "uint", "compressed PLY: a packed_* property is missing or not uint");
+            L.word[w] = (uint32_t)at;
+        }
+    }
+    {
+        static const char* names[18] = {"min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "min_scale_x", "min_scale_y", "min_scale_z",
+                                        "max_scale_x", "max_scale_y", "max_scale_z", "min_r", "min_g", "min_b", "max_r", "max_g", "max_b"};
+        bool aligned = chunk.stride % 4 == 0;
+        for (int w = 0; w < 18; w++) {
+            L.ext[w] = -1;
+            uint32_t o = 0;
+            for (const Prop& p : chunk.props) {                                        // Array.find: the first of that name
+                if (p.name == names[w]) {
+                    GS_REQUIRE(p.type == "float", "compressed PLY: a chunk extreme is not float");
+                    L.ext[w] = (int32_t)o;
+                    aligned = aligned && o % 4 == 0;
+                    break;
+                }
+                o += p.size;
+            }
+            GS_REQUIRE(w >= 12 || L.ext[w] >= 0, "compressed PLY: a position / scale extreme is missing from the chunk element");
+        }
+        L.chunk_stride = (uint32_t)chunk.stride;
+        L.chunk_aligned = aligned ? 1u : 0u;
+    }
+    uint32_t file_degree = 0;
+    if (sh) {
+        GS_REQUIRE(sh->count == n, "compressed PLY: the sh element's count differs from the vertex count");
+        const size_t P = sh->props.size();
+        for (size_t k = 0; k < P; k++)
+            GS_REQUIRE(sh->props[k].type == "uchar" && sh->props[k].name == "f_rest_" + std::to_string(k),
+                       "compressed PLY: the sh element is not f_rest_0 .. f_rest_N-1 as uchar");
+        file_degree = P >= 45 ? 3u : (P >= 24 ? 2u : (P >= 9 ? 1u : 0u));
+        L.sh_stride = (uint32_t)P;
+        L.read_coeff = file_degree == 3 ? 15u : (file_degree == 2 ? 8u : (file_degree == 1 ? 3u : 0u));
+    }
+    uint32_t degree = want_degree < file_degree ? want_degree : file_degree;            // Math.min(out, file)
+    if (degree > 2) degree = 2;                                                        // the level-0 row holds two bands
+    a->file.assign(data, data + bytes);
+    a->rows = ASSET_ROWS_COMPRESSED_PLY;
+    a->pc = L;
+    a->pc_chunk_base = base[0];
+    a->pc_vertex_base = base[1];
+    a->pc_sh_base = sh ? base[2] : 0;
+    a->pc_chunk_count = (uint32_t)chunk.count;
+    a->splat_count = (uint32_t)n;
+    a->level = 0;
+    a->sh_degree = degree;
+    return GS_OK;
+}
+
 // SplatBuffer.js:199-219: full buckets first, then the partial ones by their stored lengths.  parse_ksplat proved that the
 // tables cover every splat, so the result is always < bucket_count.
 uint32_t bucket_index(const gs_asset*, const Section& sec, uint32_t local) {
@@ -338,7 +555,17 @@ int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t ma
     int st;
     try {
         if (format == GS_ASSET_PLY) {
-            st = parse_ply(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
+            const PlyFlavour flavour = ply_flavour((const uint8_t*)data, (size_t)bytes);
+            if (flavour == PLY_INRIA_V2) {
+                gs_set_error("invalid argument: INRIA-v2 PLY (element codebook_centers) is not supported");
+                st = GS_ERR_INVALID;
+            } else if (flavour == PLY_COMPRESSED) {
+                st = parse_compressed_ply(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
+            } else {
+                st = parse_ply(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
+            }
+        } else if (format == GS_ASSET_SPLAT) {
+            st = parse_splat(a, (const uint8_t*)data, (size_t)bytes);
         } else if (format == GS_ASSET_KSPLAT) {
             a->buf.assign((const uint8_t*)data, (const uint8_t*)data + bytes);
             st = parse_ksplat(a);
@@ -381,6 +608,12 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
     GS_REQUIRE(!sh_f16 || a->level <= 1, "a level 2 file keeps its SH as uint8: ask for sh_u8");
     GS_REQUIRE(!a->has_transform || !(scales || rotations),
                "scales / rotations of a transformed asset are not provided (gs_asset_set_transform(a, NULL) removes the transform)");
+    try {
+        GS_TRY(build_level0_image(a));                       // .splat / compressed PLY: the first fill lays the level-0 rows out
+    } catch (const std::bad_alloc&) {
+        gs_set_error("out of host memory while decoding the asset");
+        return GS_ERR_NOMEM;
+    }
     const uint32_t ncomp = sh_components(a->sh_degree);
     const bool xf = a->has_transform;
     for (uint32_t i = 0; i < a->splat_count; i++) {
@@ -449,7 +682,8 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
         }
         if ((sh_f16 || sh_u8) && ncomp && xf) {                                        // fillSphericalHarmonicsArray with a transform
             const size_t hrow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u;
-            xf_sh(a->xf, a->level, a->sh_degree, a->sh_min, a->sh_max, a->buf.data() + hrow, [&](uint32_t dst, double v) {
+            const uint8_t* hp = a->buf.data() + hrow;
+            xf_sh(a->xf, a->sh_degree, [&](uint32_t src) { return sh_widen(a->level, hp, src, a->sh_min, a->sh_max); }, [&](uint32_t dst, double v) {
                 if (sh_u8) sh_u8[(size_t)ncomp * i + dst] = to_uint8_range(v, a->sh_min, a->sh_max);
                 else sh_f16[(size_t)ncomp * i + dst] = xf_f16(v);
             });

@@ -217,10 +217,19 @@ int gs_tree_gather(gs_tree* t, const gs_gather_params* params, gs_sorter* dst, u
  * ASSETS (host side, no GPU needed): the reference's file readers up to the arrays the seams consume
  * ------------------------------------------------------------------------------------------------ */
 typedef struct gs_asset gs_asset;
-#define GS_ASSET_PLY 1u      /* INRIA-v1 .ply, binary little endian: src/loaders/ply/INRIAV1PlyParser.js            */
+#define GS_ASSET_PLY 1u      /* .ply, binary little endian; the flavour is decided from the header as PlyParserUtils.js:257-271
+                              * does: `element chunk` / `packed_` = PlayCanvas (SuperSplat) compressed
+                              * (src/loaders/ply/PlayCanvasCompressedPlyParser.js), `element codebook_centers` = INRIA-v2
+                              * (refused), anything else INRIA-v1 (src/loaders/ply/INRIAV1PlyParser.js)                   */
 #define GS_ASSET_KSPLAT 2u   /* .ksplat, compression levels 0/1/2: src/loaders/SplatBuffer.js                        */
+#define GS_ASSET_SPLAT 3u    /* .splat, 32-byte rows (centre 3 x f32, scale 3 x f32, RGBA, rotation 4 x u8), SH degree 0:
+                              * src/loaders/splat/SplatParser.js:13-56, the progressive file-order path - every splat is
+                              * kept and alpha is only zeroed at fill time by min_alpha (the array path of SplatLoader.js:12-22
+                              * drops and reorders splats; that is not this interface's "file order")                 */
 /* Parses `data` (the bytes of the file).  max_sh_degree: outSphericalHarmonicsDegree (Viewer option
- * sphericalHarmonicsDegree); splats keep FILE order (the reference's optimizeSplatData:false). */
+ * sphericalHarmonicsDegree); splats keep FILE order (the reference's optimizeSplatData:false).  A .splat / compressed
+ * PLY asset keeps the file's own rows: gs_mesh_upload_asset / gs_sorter_upload_asset_centers send those to the device and
+ * decode them there, gs_asset_fill decodes them on the host the first time it is called (compression_level 0, sh_level 1). */
 int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t max_sh_degree, gs_asset** out);
 void gs_asset_close(gs_asset* a);
 typedef struct gs_asset_info {

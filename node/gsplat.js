@@ -236,8 +236,8 @@ class SplatMeshHIP {
     if (this.shDegree && this.sphericalHarmonics8Bit) addon.meshUploadShU8(this.handle, start, n, sphericalHarmonics);   // Uint8Array
     this.splatCount = Math.max(this.splatCount, start + n);
   }
-  // The same upload straight from a file's bytes, decoded per splat on the device (gs_mesh_upload_asset): format 1 = .ply,
-  // 2 = .ksplat; the mesh's sphericalHarmonicsDegree / sphericalHarmonics8Bit must be the file's.  Returns the splats uploaded.
+  // The same upload straight from a file's bytes, decoded per splat on the device (gs_mesh_upload_asset): format = AssetFormat.ply (INRIA-v1 or
+  // PlayCanvas compressed, decided from the header), .ksplat or .splat; the mesh's sphericalHarmonicsDegree / sphericalHarmonics8Bit must be the file's.  Returns the splats uploaded.
   // transform: the scene's static transform (Matrix4.elements, 16 numbers: what addSplatScene's position / rotation / scale
   // compose to), baked into centres, covariances and SH as SplatMesh.fillSplatDataArrays does in static mode.  The static
   // Viewer passes the identity when a scene has none, which is not the same as null for the SH of a level-2 file.
@@ -340,4 +340,10 @@ class StripGroup {
   dispose() { if (this.handle) { addon.groupDestroy(this.handle); this.handle = null; } }
 }
 
-module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, addon };
+// gs_asset_open's format argument (GS_ASSET_*), and the format of a file name: .splat has no magic number, so its extension decides
+const AssetFormat = { ply: 1, ksplat: 2, splat: 3 };
+const assetFormatOf = (fileName, bytes) => {
+  if (/\.splat$/i.test(fileName)) return AssetFormat.splat;
+  return bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? AssetFormat.ply : AssetFormat.ksplat;      // "ply"
+};
+module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon };

@@ -1,10 +1,12 @@
 """Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
-    python tools/load_time.py [--n 5800000] [--file NAME] [--repeats 5] [--transform identity | 16 numbers]
-                              [--out profiles/<tag>_load_time.txt]
+    python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply] [--sh-degree 0..3]
+                              [--repeats 5] [--transform identity | 16 numbers] [--out profiles/<tag>_load_time.txt]
   host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
   device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
-The file: $GS_DATA_DIR/<--file> when given, else a seeded level-2 SH-2 .ksplat of --n splats from assets.write_ksplat (the C3
-count by default).  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
+The file: $GS_DATA_DIR/<--file> when given (a name ending in .splat is one), else a seeded file of --n splats (the C3 count
+by default) in --format, from the writers of gaussiansplats3d_amd.assets: a level-2 SH-2 .ksplat (the default), an INRIA-v1
+PLY, a .splat, or a PlayCanvas compressed PLY with --sh-degree bands.  For .splat / compressed PLY the asset keeps the
+file's rows and the host decodes them on its first fill, so both paths open a fresh asset inside the timed region.  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
 Viewer passes for a scene without one), set on the asset so both paths bake it (gs_asset_set_transform).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
 alternate.  Prints median and spread (max - min) of both and the bytes each sends over PCIe; the device path passes when its
 median is below the host path's by more than the larger spread."""
@@ -30,8 +32,30 @@ def seeded_file(n):
     return assets.write_ksplat(centers, scales, rot, rgba, sh, 2, 2, block_size=5.0, bucket_size=256)[0]
 
 
+def seeded(fmt, n, sh_degree):
+    """(bytes, SplatAsset fmt, description) of the seeded file in --format."""
+    if fmt == "ksplat":
+        return seeded_file(n), "ksplat", f"seeded level-2 SH-2 .ksplat, {n} splats"
+    rng = np.random.default_rng(20260921)
+    centers = rng.normal(size=(n, 3)) * 4.0
+    log_scales = rng.normal(-3.6, 0.5, size=(n, 3))
+    rot = rng.normal(size=(n, 4))
+    ncoef = {0: 0, 1: 9, 2: 24, 3: 45}[sh_degree]
+    if fmt == "splat":
+        return assets.write_splat(centers, np.exp(log_scales), rot, rng.integers(0, 256, size=(n, 4), dtype=np.uint8)), "splat", \
+            f"seeded .splat, {n} splats"
+    sh = rng.normal(0.0, 0.4, size=(n, ncoef)).astype(np.float32) if ncoef else None
+    if fmt == "compressed-ply":
+        return assets.write_compressed_ply(centers, log_scales, rot, rng.random((n, 4)), sh), "ply", \
+            f"seeded PlayCanvas compressed PLY, {ncoef} SH properties, {n} splats"
+    return assets.write_ply(centers, log_scales, rot, rng.normal(size=(n, 3)), rng.normal(size=n), sh), "ply", \
+        f"seeded INRIA-v1 PLY, {ncoef} f_rest properties, {n} splats"
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", default="ksplat", choices=["ksplat", "ply", "splat", "compressed-ply"])
+    ap.add_argument("--sh-degree", type=int, default=2, choices=[0, 1, 2, 3], help="bands of a seeded ply / compressed-ply")
     ap.add_argument("--n", type=int, default=5_800_000)
     ap.add_argument("--file", default=None)
     ap.add_argument("--repeats", type=int, default=5)
@@ -46,11 +70,20 @@ def main():
     if args.file:
         path = os.path.join(os.environ.get("GS_DATA_DIR", "."), args.file)
         data, source = open(path, "rb").read(), args.file
+        fmt = "splat" if args.file.lower().endswith(".splat") else None
     else:
-        data, source = seeded_file(args.n), f"seeded level-2 SH-2 .ksplat, {args.n} splats"
-    asset = assets.SplatAsset(data, None, 2)
-    asset.set_transform(transform)
+        data, fmt, source = seeded(args.format, args.n, args.sh_degree)
+
+    def opened():
+        a = assets.SplatAsset(data, fmt, 2)
+        a.set_transform(transform)
+        return a
+
+    asset = opened()
     info = asset.info
+    header = data[:data.index(b"end_header\n") + 11] if data[:3] == b"ply" else b""
+    compressed = b"element chunk" in header
+    file_rows = fmt == "splat" or compressed                          # the asset keeps the file's rows
     n, deg, sh8 = info.splat_count, info.sh_degree, info.sh_level == 2 and info.sh_degree > 0
     ncoef = {0: 0, 1: 9, 2: 24}[deg]
     ctx = Context(0)
@@ -59,17 +92,23 @@ def main():
         return SplatMesh(ctx, n, deg, spherical_harmonics_8bit=sh8), create_sort_worker(ctx, n)
 
     def host(mesh, worker):
-        f = asset.fill(1, False)
+        a = opened() if file_rows else asset
+        f = a.fill(1, False)
         p = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
         L.check(mesh.lib.gs_mesh_upload(mesh.handle, 0, n, p(f["centers"]), p(f["cov"]), None, p(f["rgba"]), p(f["sh_f16"])))
         if f["sh_u8"] is not None:
             L.check(mesh.lib.gs_mesh_upload_sh_u8(mesh.handle, 0, n, p(f["sh_u8"])))
         ci = util.integer_centers(f["centers"])
         L.check(worker.lib.gs_sorter_upload_centers(worker.handle, 0, n, ci.ctypes.data, None))
+        if file_rows:
+            a.close()
 
     def device(mesh, worker):
-        asset.upload_to(mesh)
-        asset.upload_centers_to(worker)
+        a = opened() if file_rows else asset
+        a.upload_to(mesh)
+        a.upload_centers_to(worker)
+        if file_rows:
+            a.close()
 
     times = {"host": [], "device": []}
     for _ in range(args.repeats):
@@ -82,8 +121,16 @@ def main():
             times[name].append((time.perf_counter() - t0) * 1e3)
             worker.terminate()
             mesh.dispose()
-    rows_bytes = len(data) - 4096 - 1024 * int(np.frombuffer(data[4:8], np.uint32)[0])      # rows + bucket tables of every section
-    pcie = {"host": n * (12 + 24 + 4 + ncoef * (1 if sh8 else 2)) + n * 16, "device": 2 * rows_bytes}
+    if fmt == "splat":
+        device_bytes = 2 * len(data)                                  # the rows, once for the mesh and once for the sorter
+    elif compressed:                                                  # vertex rows + chunk rows twice, the SH bytes once
+        sh_file = n * header.count(b"property uchar f_rest_")
+        device_bytes = 2 * (len(data) - len(header) - sh_file) + (sh_file if ncoef else 0)
+    elif data[:3] == b"ply":
+        device_bytes = 2 * n * (44 + 4 * ncoef)                       # the level-0 image the host built from the PLY
+    else:
+        device_bytes = 2 * (len(data) - 4096 - 1024 * int(np.frombuffer(data[4:8], np.uint32)[0]))   # rows + bucket tables
+    pcie = {"host": n * (12 + 24 + 4 + ncoef * (1 if sh8 else 2)) + n * 16, "device": device_bytes}
     med = {k: float(np.median(v)) for k, v in times.items()}
     spread = {k: float(max(v) - min(v)) for k, v in times.items()}
     lines = [f"load_time: {source}; file {len(data)} bytes, {n} splats, SH degree {deg}, compression level {info.compression_level}; "
