@@ -149,6 +149,15 @@ __global__ __launch_bounds__(256) void k_debug_expand(const unsigned long long* 
     if (out_slots) out_slots[orig] = vis ? slot : 0xFFFFFFFFu;              // the slot the entry lists name the splat by
 }
 
+// test hook: a 4-byte storage-order plane (or, src == NULL, the storage position itself) by ORIGINAL splat index
+__global__ __launch_bounds__(256) void k_debug_by_original(const uint32_t* __restrict__ src, const uint32_t* __restrict__ perm, uint32_t count,
+                                                           uint32_t* __restrict__ out) {
+    const uint32_t orig = blockIdx.x * 256u + threadIdx.x;
+    if (orig >= count) return;
+    const uint32_t i = perm ? perm[orig] : orig;
+    out[orig] = src ? src[i] : i;
+}
+
 // 8-bit SH: 9 or 24 bytes per splat -> one 16-byte plane (+ one 8-byte plane for degree 2)
 __global__ __launch_bounds__(256) void k_split_sh_u8(const uint8_t* __restrict__ sh, uint32_t count, uint32_t from,
                                                      const uint32_t* __restrict__ perm, uint32_t ncoef, uint4* __restrict__ p0,
@@ -1131,9 +1140,26 @@ int gs_mesh_set_deep_pass(gs_mesh* m, int enabled) {
 
 int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
     GS_REQUIRE(m && dst, "mesh / dst == NULL");
-    GS_REQUIRE(m->has_draw && ((what >= 2 && what != 9) || count <= m->last_count), "no draw / count too large");
     ScopedDevice sd(m->ctx->device);
     hipStream_t st = m->ctx->stream;
+    if (what >= 10 && what <= 12) {   // the upload-time planes behind the strip and block culls (no draw needed)
+        if (count == 0) return GS_OK;
+        if (what == 11) {             // block_box rows: 8 floats per storage block
+            GS_REQUIRE(count <= (m->max_count + 255u) / 256u, "count exceeds the storage blocks of the mesh");
+            GS_HIP(hipMemcpyAsync(dst, m->block_box.p, (size_t)count * 32, hipMemcpyDeviceToHost, st));
+        } else {                      // 10: cov_bound, 12: the storage position - per ORIGINAL splat index
+            GS_REQUIRE(count <= m->uploaded, "count exceeds the uploaded splats");
+            GS_TRY(m->staging.ensure((size_t)count * 4 + 64));
+            hipLaunchKernelGGL(k_debug_by_original, dim3((count + 255u) / 256u), dim3(256), 0, st,
+                               what == 10 ? m->cov_bound.as<uint32_t>() : nullptr, m->reorder ? m->perm.as<uint32_t>() : nullptr, count,
+                               m->staging.as<uint32_t>());
+            GS_HIP(hipGetLastError());
+            GS_HIP(hipMemcpyAsync(dst, m->staging.p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+        }
+        GS_HIP(hipStreamSynchronize(st));
+        return GS_OK;
+    }
+    GS_REQUIRE(m->has_draw && ((what >= 2 && what != 9) || count <= m->last_count), "no draw / count too large");
     if (what == 0 || what == 1 || what == 3 || what == 9) {
         if (count == 0) return GS_OK;
         const uint32_t splats = what == 3 ? (count * 64u < m->last_count ? count * 64u : m->last_count) : count;

@@ -50,15 +50,23 @@ class SplatMesh:
         context._adopt(self)
 
     # -- build / data upload ------------------------------------------------------------------------
-    def build(self, centers, covariances, colors, spherical_harmonics=None, start=0, scene_indexes=None):
+    def build(self, centers, covariances, colors, spherical_harmonics=None, start=0, scene_indexes=None,
+              covariances_are_half_bits=False):
         """fillSplatDataArrays output -> device planes.  covariances: float32 [n,6]; narrowed with
         THREE.DataUtils.toHalfFloat semantics when half_precision_covariances (SplatBuffer.js:469-474).
+        covariances_are_half_bits=True (half_precision_covariances meshes only): covariances is uint16 [n,6], half bit patterns
+        the caller narrowed, stored as they are - the only way to store an inf or a NaN half, which toHalfFloat clamps away.
         spherical_harmonics: float16 (or uint16 bit patterns) [n, 9|24], coefficient-major RGB triples."""
         c = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 3)
         n = c.shape[0]
-        cov = np.ascontiguousarray(covariances, dtype=np.float32).reshape(n, 6)
+        if covariances_are_half_bits:
+            if not self.half_cov or np.asarray(covariances).dtype != np.uint16:
+                raise ValueError("covariances_are_half_bits needs a half_precision_covariances mesh and a uint16 array")
+            cov, cov16 = None, np.ascontiguousarray(covariances).reshape(n, 6)
+        else:
+            cov = np.ascontiguousarray(covariances, dtype=np.float32).reshape(n, 6)
+            cov16 = to_half_three(cov) if self.half_cov else None
         rgba = np.ascontiguousarray(colors, dtype=np.uint8).reshape(n, 4)
-        cov16 = to_half_three(cov) if self.half_cov else None
         sh = None
         sh8 = None
         ncoef = 9 if self.sh_degree == 1 else 24
@@ -303,6 +311,21 @@ class SplatMesh:
         L.check(self.lib.gs_mesh_debug_read(self.handle, 3, mask.ctypes.data, words))
         vis = np.unpackbits(mask.view(np.uint8), bitorder="little")[:n].astype(bool)
         return recs, rects, vis
+
+    def debug_cull_planes(self):
+        """The upload-time planes behind the strip and block culls (gs_mesh_debug_read what = 10 / 11 / 12): (cov_bound float32 [n]
+        by original splat index; block_box float32 [blocks, 8] per 256-splat storage block - min xyz, max xyz, largest member
+        cov_bound, unused; storage position uint32 [n] by original splat index).  Needs no draw."""
+        n = self.splat_count
+        blocks = (n + 255) // 256
+        bound = np.empty(n, dtype=np.float32)
+        boxes = np.empty((blocks, 8), dtype=np.float32)
+        pos = np.empty(n, dtype=np.uint32)
+        if n:
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 10, bound.ctypes.data, n))
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 11, boxes.ctypes.data, blocks))
+            L.check(self.lib.gs_mesh_debug_read(self.handle, 12, pos.ctypes.data, n))
+        return bound, boxes, pos
 
     def bin_entry_counts(self, tile_rows=None):
         """Entries per list bin of the last draw, shaped [list_rows, lists_x] (`tile_rows`: the strip it drew)."""

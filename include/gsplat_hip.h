@@ -497,7 +497,13 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * that draw), the array the [begin,end) ranges of what = 2 index, each list near -> far; refused while a gs_mesh_project is pending
  * (the slots then refer to the other record set, as for gs_mesh_debug_rop8);
  * 9 = per splat, in the caller's numbering, the record slot the last vertex stage gave it (uint32, 0xFFFFFFFF = not visible): what
- * the entries of what = 8 name a splat by.
+ * the entries of what = 8 name a splat by;
+ * 10 = per splat, in the caller's numbering, the bound of its covariance's spectral radius that the strip pre-tests read (float;
+ * count <= the uploaded splats); 11 = the boxes of the 256-splat storage blocks, 8 floats per block: {min xyz, max xyz of the
+ * members' centres (NaN left out), the largest member bound of what = 10 (NaN if any member's is), unused} (count = blocks <=
+ * ceil(max_splat_count / 256)); 12 = per splat, in the caller's numbering, its storage position (uint32; block = position / 256).
+ * 10 .. 12 read what the uploads left and need no draw.  Like the reads above, 10 and 12 go through the mesh's upload staging
+ * buffer: no debug read may run while another thread uploads to the same mesh.
  *
  * The composite (csrc/tile_blend.hip).  Per 16x16-px quadrant, the ordered list entries whose ellipse reaches the quadrant are
  * cut into chunks of 1024; a chunk is the plain front-to-back composite from T = 1, and the chunks are merged near -> far

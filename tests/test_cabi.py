@@ -80,3 +80,6 @@ def test_debug_read_constants_match_the_header():
     assert "7 = the blend schedule of the last draw" in header
     assert "8 = the entry values of the last draw in list order" in header
     assert "9 = per splat, in the caller's numbering, the record slot the last vertex stage gave it" in header
+    assert "10 = per splat, in the caller's numbering, the bound of its covariance's spectral radius" in header
+    assert "11 = the boxes of the 256-splat storage blocks, 8 floats per block" in header
+    assert "12 = per splat, in the caller's numbering, its storage position" in header
