@@ -87,7 +87,7 @@ class AssetInfo(C.Structure):
                 ("sh_level", C.c_uint32), ("scene_center", C.c_float * 3), ("sh_min", C.c_float), ("sh_max", C.c_float)]
 
 
-GS_ASSET_PLY, GS_ASSET_KSPLAT, GS_ASSET_SPLAT = 1, 2, 3
+GS_ASSET_PLY, GS_ASSET_KSPLAT, GS_ASSET_SPLAT, GS_ASSET_SPZ = 1, 2, 3, 4
 
 # every symbol include/gsplat_hip.h declares: (restype, argtypes)
 _VP = C.c_void_p

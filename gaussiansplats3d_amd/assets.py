@@ -1,16 +1,19 @@
 """Host-side mirror of the reference's scene loaders, over the native readers of libgsplat_hip (csrc/assets.hip).
 
-Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFileData`` / ``SplatLoader`` -> ``SplatBuffer``
+Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFileData`` / ``SplatLoader`` /
+``SpzLoader.loadFromFileData`` -> ``SplatBuffer``
 (/root/reference/src/loaders/ply/PlyLoader.js, src/loaders/ksplat/KSplatLoader.js, src/loaders/splat/SplatLoader.js's
-progressive file-order path) followed by
+progressive file-order path, src/loaders/spz/SpzLoader.js with ``optimizeSplatData: false``) followed by
 ``SplatMesh.fillSplatDataArrays`` (src/splatmesh/SplatMesh.js:1853-1902), with the scene's static transform when
 ``SplatAsset.set_transform`` gave one.  ``load`` returns the arrays
 ``SplatMesh.build`` / the sort worker take.  ``"ply"`` covers INRIA-v1 and the PlayCanvas / SuperSplat compressed PLY (decided
-from the header); ``"splat"`` has no magic number and is chosen by ``fmt`` or a file name's extension.  The ``write_*``
+from the header); ``"splat"`` has no magic number and is chosen by ``fmt`` or a file name's extension; ``"spz"`` is a gzip
+member (``1f 8b``), inflated by the library itself, and is chosen by ``fmt``, the extension or that magic.  The ``write_*``
 helpers produce the same file formats (used by the tests and to stage synthetic scenes as real files); they are not part
 of the reference's API surface.
 """
 import ctypes as C
+import gzip
 import struct
 
 import numpy as np
@@ -20,18 +23,20 @@ from .util import to_half_three
 
 
 class SplatAsset:
-    """An opened .ply / .ksplat / .splat: ``info`` + ``fill()`` -> dict of arrays."""
-    FORMATS = {"ply": L.GS_ASSET_PLY, "ksplat": L.GS_ASSET_KSPLAT, "splat": L.GS_ASSET_SPLAT}
+    """An opened .ply / .ksplat / .splat / .spz: ``info`` + ``fill()`` -> dict of arrays."""
+    FORMATS = {"ply": L.GS_ASSET_PLY, "ksplat": L.GS_ASSET_KSPLAT, "splat": L.GS_ASSET_SPLAT, "spz": L.GS_ASSET_SPZ}
 
     def __init__(self, data, fmt=None, spherical_harmonics_degree=2):
         self.lib = L.load()
         data = bytes(data)
         if fmt is None:
-            fmt = "ply" if data[:3] == b"ply" else "ksplat"
+            fmt = "ply" if data[:3] == b"ply" else ("spz" if data[:2] == b"\x1f\x8b" else "ksplat")
         self.handle = C.c_void_p()
         buf = (C.c_char * len(data)).from_buffer_copy(data)
         if fmt not in self.FORMATS:
             raise ValueError(f"unknown asset format {fmt!r}: one of {sorted(self.FORMATS)}")
+        if fmt == "spz" and data[:2] != b"\x1f\x8b":
+            raise ValueError("not an .spz file: the data does not start with the gzip magic 1f 8b")
         L.check(self.lib.gs_asset_open(buf, len(data), self.FORMATS[fmt], int(spherical_harmonics_degree), C.byref(self.handle)))
         self.info = L.AssetInfo()
         L.check(self.lib.gs_asset_get_info(self.handle, C.byref(self.info)))
@@ -104,6 +109,8 @@ def load(path_or_bytes, spherical_harmonics_degree=2, minimum_alpha=1, half_prec
     if isinstance(path_or_bytes, str):
         if path_or_bytes.lower().endswith(".splat"):          # .splat has no magic number: the extension decides
             fmt = "splat"
+        elif path_or_bytes.lower().endswith(".spz"):
+            fmt = "spz"
         with open(path_or_bytes, "rb") as f:
             data = f.read()
     else:
@@ -152,6 +159,44 @@ def write_splat(centers, scales, rotations_wxyz, rgba):
     rec["c"], rec["s"], rec["rgba"] = centers, scales, np.asarray(rgba, np.uint8).reshape(n, 4)
     rec["rot"] = np.clip(np.floor(q * 128 + 128 + 0.5), 0, 255).astype(np.uint8)
     return rec.tobytes()
+
+
+def spz_stream(centers, log_scales, rotations, rgba, sh=None, version=2, fractional_bits=12, sh_degree=None):
+    """The uncompressed .spz stream ``write_spz`` wraps in gzip: the 16-byte header and the six planes."""
+    n = centers.shape[0]
+    dims = {0: 0, 1: 3, 2: 8, 3: 15}
+    if sh_degree is None:
+        sh_degree = 0 if sh is None else {9: 1, 24: 2, 45: 3}[np.asarray(sh).reshape(n, -1).shape[1]]
+    dim = dims[sh_degree]
+    c = np.asarray(centers, np.float64)
+    if version == 2:
+        fixed = np.clip(np.floor(c * float(1 << fractional_bits) + 0.5), -(1 << 23), (1 << 23) - 1).astype(np.int64) & 0xFFFFFF
+        positions = np.stack([(fixed >> s) & 255 for s in (0, 8, 16)], axis=2).astype(np.uint8).tobytes()     # [n, 3 axes, 3 bytes]
+    else:
+        positions = c.astype("<f2").tobytes()
+    rgba = np.asarray(rgba, np.float64).reshape(n, 4)
+    u8 = lambda v: np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint8)                                   # noqa: E731
+    q = np.asarray(rotations, np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    q = q * np.where(q[:, :1] < 0, -1.0, 1.0)                       # w is rebuilt as a non-negative root
+    planes = [positions, u8(rgba[:, 3] * 255).tobytes(),
+              u8(((rgba[:, :3] - 0.5) / 0.28209479177387814 * 0.15 + 0.5) * 255).tobytes(),
+              u8((np.asarray(log_scales, np.float64) + 10.0) * 16.0).tobytes(), u8((q[:, 1:] + 1.0) * 127.5).tobytes()]
+    if dim:
+        s = np.asarray(sh, np.float64).reshape(n, 3, dim)           # [splat, channel, coefficient] -> coefficient-major on the wire
+        planes.append(u8(np.transpose(s, (0, 2, 1)) * 128.0 + 128.0).tobytes())
+    header = struct.pack("<IIIBBBB", 1347635022, version, n, sh_degree, fractional_bits, 0, 0)
+    return header + b"".join(planes)
+
+
+def write_spz(centers, log_scales, rotations, rgba, sh=None, version=2, fractional_bits=12, sh_degree=None):
+    """.spz (src/loaders/spz/SpzLoader.js:255-342), a quantising writer: a gzip member around the 16-byte header and the
+    planes positions (version 2: 24-bit fixed point with ``fractional_bits``; version 1: halves), alphas, colours
+    (``((c - 0.5) / SH_C0 * 0.15 + 0.5) * 255``: the inverse of the reader's rule), scales (``(log + 10) * 16``), rotations
+    (x, y, z of the unit quaternion with w >= 0 as ``(v + 1) * 127.5``) and SH (``v * 128 + 128``).  rotations: w, x, y, z;
+    rgba: floats in 0..1 [n, 4]; sh: float [n, 9|24|45] in the file order of the other writers (all R coefficients, then
+    G, then B); sh_degree defaults to what ``sh`` holds."""
+    return gzip.compress(spz_stream(centers, log_scales, rotations, rgba, sh, version, fractional_bits, sh_degree), 6, mtime=0)
 
 
 def pack_unit_quaternions(rotations_wxyz):

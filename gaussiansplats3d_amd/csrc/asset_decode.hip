@@ -1,9 +1,10 @@
 // asset_decode.hip — the per-splat decode of an opened asset on the device: file rows -> the staging layout a
 // mesh upload commits (gs_mesh_upload_asset) and the sorter's `centers` message (gs_sorter_upload_asset_centers).
 // The kernels take a ROW SOURCE (a template parameter, as XF is one): the .ksplat image (also an INRIA-v1 PLY's level-0
-// image), the 32-byte rows of a .splat, or the 16-byte vertex rows + chunk rows + SH bytes of a PlayCanvas compressed PLY.
-// The last two produce the level-0 tuple in registers through asset_internal.hpp's row arithmetic - the functions the host's
-// image builder calls - so only file rows cross the bus and the level-0 image is never built on this path.
+// image), the 32-byte rows of a .splat, the 16-byte vertex rows + chunk rows + SH bytes of a PlayCanvas compressed PLY, or
+// the six byte planes of an inflated .spz.  The last three produce the level-0 tuple in registers through asset_internal.hpp's
+// row arithmetic - the functions the host's image builder calls - so only file rows cross the bus and the level-0 image is
+// never built on this path.
 // The arithmetic is gs_asset_fill's (assets.hip), expression for expression, in fp64 and unfused (this file is built with
 // -ffp-contract=off): only multiplies, adds and double -> float conversions are involved, so the planes are bit-equal to what
 // gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.  Restates, never copies:
@@ -122,11 +123,9 @@ struct KsplatSource : AssetView {
     __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const { row(splat).centre(d); }
 };
 
-// the level-0 tuple in registers, as the two row formats produce it (fp32 values of a level-0 row, widened as the fills widen them)
-struct TupleRow {
+// the level-0 tuple in registers, as the row formats produce it (fp32 values of a level-0 row, widened as the fills widen them)
+struct TupleValues {
     Level0Tuple t;
-    const uint8_t* sh;             // compressed PLY: the splat's SH bytes (unaligned: 9 / 24 / 45 per splat)
-    uint32_t read_coeff;
     __device__ __forceinline__ void centre(double d[3]) const { for (int k = 0; k < 3; k++) d[k] = t.c[k]; }
     __device__ __forceinline__ void scale_rotation(double s[3], double q[4]) const {
         for (int k = 0; k < 3; k++) s[k] = t.s[k];
@@ -135,6 +134,10 @@ struct TupleRow {
     __device__ __forceinline__ uint32_t colour() const {
         return (uint32_t)t.rgba[0] | ((uint32_t)t.rgba[1] << 8) | ((uint32_t)t.rgba[2] << 16) | ((uint32_t)t.rgba[3] << 24);
     }
+};
+struct TupleRow : TupleValues {
+    const uint8_t* sh;             // compressed PLY: the splat's SH bytes (unaligned: 9 / 24 / 45 per splat)
+    uint32_t read_coeff;
     __device__ __forceinline__ double sh_wide(uint32_t src, double, double) const { return (double)pc_row_sh(sh, read_coeff, src); }
     __device__ __forceinline__ uint16_t sh_half(uint32_t src) const { return to_half_three((double)pc_row_sh(sh, read_coeff, src)); }
     __device__ __forceinline__ uint8_t sh_byte(uint32_t) const { return 0; }       // sh_level is 1: never stored as bytes
@@ -187,6 +190,62 @@ struct CompressedSource {
         const uint32_t* words = reinterpret_cast<const uint32_t*>(vertex + (splat - base));
         float c[3];
         pc_row_centre(words[layout.word[0]], chunk_of(splat), layout, c);
+        for (int k = 0; k < 3; k++) d[k] = c[k];
+    }
+};
+
+// .spz: six byte planes.  A staged plane slice begins 16-byte aligned at asset splat `base`, whatever `base` is, so splat
+// base + i has its bytes at stride * i - at any byte phase of a dword (strides 9 / 6 / 1 / 3 / 3 * dim).  There are no byte-wide
+// global loads: a value is cut with shifts out of the aligned dword(s) that hold it; neighbouring lanes meet in the same dwords
+// through the cache.  A second dword is loaded only when the value's own bytes reach into it, so the last lanes read at most
+// the slice's padding to 16 bytes, never past the allocation (and whatever the padding holds is masked away).
+__device__ __forceinline__ uint32_t spz_load1(const uint32_t* words, size_t b) { return (words[b >> 2] >> (8u * (uint32_t)(b & 3u))) & 255u; }
+__device__ __forceinline__ uint32_t spz_load2(const uint32_t* words, size_t b) {       // b is even: one dword holds both bytes
+    return (words[b >> 2] >> (8u * (uint32_t)(b & 3u))) & 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t spz_load3(const uint32_t* words, size_t b) {
+    const uint32_t shift = 8u * (uint32_t)(b & 3u);
+    uint32_t v = words[b >> 2] >> shift;
+    if (shift > 8u) v |= words[(b >> 2) + 1] << (32u - shift);                         // phases 2 and 3 continue in the next dword
+    return v & 0x00FFFFFFu;
+}
+
+struct SpzSource {
+    const uint32_t* plane[SPZ_PLANES];   // byte 0 of each slice = asset splat `base` (SH: staged whole, 3 * file_dim per splat)
+    uint32_t base;
+    uint32_t level, sh_degree, ncomp;    // 0, the output degree, 0 / 9 / 24
+    SpzLayout layout;
+    struct Row : TupleValues {
+        const uint32_t* sh;              // the SH slice
+        size_t sh_at;                    // byte offset of this splat's SH in it
+        __device__ __forceinline__ float value(uint32_t src) const { return spz_sh_value(spz_load1(sh, sh_at + spz_sh_index(src))); }
+        __device__ __forceinline__ double sh_wide(uint32_t src, double, double) const { return (double)value(src); }
+        __device__ __forceinline__ uint16_t sh_half(uint32_t src) const { return to_half_three((double)value(src)); }
+        __device__ __forceinline__ uint8_t sh_byte(uint32_t) const { return 0; }   // sh_level is 1: never stored as bytes
+    };
+    __device__ __forceinline__ void positions(size_t i, uint32_t pos[3]) const {
+        for (int k = 0; k < 3; k++)
+            pos[k] = layout.pos_stride == 9u ? spz_load3(plane[SPZ_POSITIONS], 9 * i + 3 * k) : spz_load2(plane[SPZ_POSITIONS], 6 * i + 2 * k);
+    }
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        const size_t i = splat - base;
+        SpzRowBytes b;
+        positions(i, b.pos);
+        b.alpha = spz_load1(plane[SPZ_ALPHAS], i);
+        b.colour = spz_load3(plane[SPZ_COLOURS], 3 * i);
+        b.scale = spz_load3(plane[SPZ_SCALES], 3 * i);
+        b.rotation = spz_load3(plane[SPZ_ROTATIONS], 3 * i);
+        Row r;
+        spz_row_tuple(layout, b, r.t);
+        r.sh = plane[SPZ_SH];
+        r.sh_at = 3 * (size_t)layout.file_dim * i;
+        return r;
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const {    // the position plane alone
+        uint32_t pos[3];
+        float c[3];
+        positions(splat - base, pos);
+        spz_row_centre(layout, pos, c);
         for (int k = 0; k < 3; k++) d[k] = c[k];
     }
 };
@@ -404,6 +463,37 @@ int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceIm
     return GS_OK;
 }
 
+// .spz: the slices [first, first + count) of the six planes (the position plane alone for the sorter's centres), each starting
+// 16-byte aligned and padded to 16 bytes; nothing else crosses the bus (19 + 3 * file_dim bytes per splat for version 2).  The SH
+// of a degree-3 file is staged whole and read up to the output degree.  spz_open proved that the stream holds every plane.
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, SpzSource* src, bool centres_only) {
+    const SpzLayout& L = a->spz;
+    const uint32_t ncomp = sh_components(a->sh_degree);
+    size_t at[SPZ_PLANES], bytes[SPZ_PLANES], total = 0;
+    for (int p = 0; p < SPZ_PLANES; p++) {
+        const bool wanted = p == SPZ_POSITIONS || (!centres_only && (p != SPZ_SH || ncomp));
+        at[p] = total;
+        bytes[p] = wanted ? (size_t)spz_plane_stride(L, p) * count : 0;
+        total += (bytes[p] + 15) & ~(size_t)15;
+    }
+    GS_TRY(dev.bytes.ensure(total));
+    uint8_t* image = dev.bytes.as<uint8_t>();
+    for (int p = 0; p < SPZ_PLANES; p++)
+        if (bytes[p])
+            GS_HIP(hipMemcpyAsync(image + at[p], a->file.data() + L.off[p] + (size_t)spz_plane_stride(L, p) * first, bytes[p],
+                                  hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st));
+    SpzSource v = {};
+    for (int p = 0; p < SPZ_PLANES; p++) v.plane[p] = reinterpret_cast<const uint32_t*>(image + at[p]);
+    v.base = first;
+    v.level = 0;
+    v.sh_degree = a->sh_degree;
+    v.ncomp = ncomp;
+    v.layout = L;
+    *src = v;
+    return GS_OK;
+}
+
 // gs_mesh_upload_asset's source: a segment of the staging is filled by k_asset_decode
 DevTransform dev_transform(const gs_asset* a) { return DevTransform{a->xf, a->sh_min, a->sh_max}; }
 
@@ -474,6 +564,7 @@ int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first,
     // (an earlier call's decode kernels have finished: every upload synchronises before it returns)
     if (a->rows == ASSET_ROWS_SPLAT) return mesh_upload_rows<SplatSource>(m, from, a, first, count, min_alpha, mesh_u8);
     if (a->rows == ASSET_ROWS_COMPRESSED_PLY) return mesh_upload_rows<CompressedSource>(m, from, a, first, count, min_alpha, mesh_u8);
+    if (a->rows == ASSET_ROWS_SPZ) return mesh_upload_rows<SpzSource>(m, from, a, first, count, min_alpha, mesh_u8);
     return mesh_upload_rows<KsplatSource>(m, from, a, first, count, min_alpha, mesh_u8);
 }
 
@@ -489,6 +580,7 @@ int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uin
     ScopedDevice sd(s->ctx->device);
     if (a->rows == ASSET_ROWS_SPLAT) GS_TRY(sorter_upload_rows<SplatSource>(s, from, a, first, count));
     else if (a->rows == ASSET_ROWS_COMPRESSED_PLY) GS_TRY(sorter_upload_rows<CompressedSource>(s, from, a, first, count));
+    else if (a->rows == ASSET_ROWS_SPZ) GS_TRY(sorter_upload_rows<SpzSource>(s, from, a, first, count));
     else GS_TRY(sorter_upload_rows<KsplatSource>(s, from, a, first, count));
     return gs_sorter_commit_centers(s, from, count, scene_indexes);
 }

@@ -1,10 +1,11 @@
 // asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share: the parsed
 // .ksplat image, the two half-float rules, and the per-row arithmetic of the formats whose file rows are decoded on both
-// sides (.splat, PlayCanvas compressed PLY), each said once for both sides.
+// sides (.splat, PlayCanvas compressed PLY, .spz), each said once for both sides.
 #pragma once
 #include <math.h>
 
 #include "gs_internal.hpp"
+#include "spz_container.hpp"
 
 // THREE.DataUtils.toHalfFloat (three r160): clamp to +-65504, then the base/shift tables: the mantissa is TRUNCATED
 __host__ __device__ inline uint16_t to_half_three(double value) {
@@ -300,6 +301,59 @@ __host__ __device__ inline float pc_row_sh(const uint8_t* sh, uint32_t read_coef
     return (float)((double)sh[j * read_coeff + k] * (8.0 / 255.0) - 4);
 }
 
+// ---- .spz: six byte planes -> the level-0 tuple --------------------------------------------------------------------------------
+// Restates, never copies: src/loaders/spz/SpzLoader.js:160-250 (unpackGaussians), :84-145 (unpackedSplatToUncompressedSplat), then
+// the level-0 store of SplatBuffer.writeSplatDataToSectionBuffer :1092-1124, 1168-1172.  A splat's bytes as both sides hand them over:
+struct SpzRowBytes {
+    uint32_t pos[3];           // version 2: three bytes little endian in bits 0..23; version 1: half bits
+    uint32_t alpha;            // the byte
+    uint32_t colour, scale, rotation;   // three bytes each, byte k in bits 8k .. 8k + 7
+};
+
+// the centre: 24-bit fixed point, sign-extended from bit 23, times the position scale (SpzLoader.js:196-204), or a half (:190-194:
+// halfToFloat is exact, as from_half is, for -0, inf and NaN too); stored fp32 (SplatBuffer.js:1114)
+__host__ __device__ inline void spz_row_centre(const SpzLayout& L, const uint32_t pos[3], float c[3]) {
+#pragma clang fp contract(off)
+    for (int k = 0; k < 3; k++) {
+        if (L.pos_stride == 9u) c[k] = (float)((double)((int32_t)(pos[k] << 8) >> 8) * L.pos_scale);
+        else c[k] = row_f32(from_half((uint16_t)pos[k]));
+    }
+}
+
+__host__ __device__ inline void spz_row_tuple(const SpzLayout& L, const SpzRowBytes& b, Level0Tuple& t) {
+#pragma clang fp contract(off)
+    spz_row_centre(L, b.pos, t.c);
+    for (int k = 0; k < 3; k++) t.s[k] = (float)row_exp((double)((b.scale >> (8 * k)) & 255u) / 16.0 - 10.0);   // :209; never 0 or NaN
+    {
+        const double x = (double)(b.rotation & 255u) / 127.5 - 1.0, y = (double)((b.rotation >> 8) & 255u) / 127.5 - 1.0,
+                     z = (double)((b.rotation >> 16) & 255u) / 127.5 - 1.0;
+        const double rest = 1.0 - (x * x + y * y + z * z);
+        // Quaternion.set(x = w, y = x, z = y, w = z) :132: row_normalize sums the squares in exactly that slot order.  Normalised
+        // there (:133) and AGAIN by writeSplatDataToSectionBuffer (SplatBuffer.js:1093-1094); one pass is not bit-equal to two.
+        double q[4] = {sqrt(rest > 0.0 ? rest : 0.0), x, y, z};
+        row_normalize(q);
+        row_normalize(q);
+        for (int k = 0; k < 4; k++) t.r[k] = (float)q[k];
+    }
+    for (int k = 0; k < 3; k++) {                                                      // :231, then clamp(floor(.)) :116-118
+        const double c = (double)((b.colour >> (8 * k)) & 255u);
+        t.rgba[k] = (uint8_t)clampd(floor(floor((((c / 255.0 - 0.5) / 0.15) * 0.28209479177387814 + 0.5) * 255)), 0, 255);
+    }
+    t.rgba[3] = (uint8_t)b.alpha;                                                      // min_alpha zeroes it at fill time only
+}
+
+// Level-0 SH slot s (0..8 band 1, 9..23 band 2) -> the byte's index within the splat's 3 * dim SH bytes: coefficient k of channel j
+// lies at 3 * k + j (:237), and slot s holds j = s / 3, k = s % 3 below 9, j = (s - 9) / 5, k = 3 + (s - 9) % 5 above (the inverse of
+// the reference's shIndexMap, as pc_row_sh states it).  The caller only asks for slots of a degree min(output, file) <= 2: k < dim.
+__host__ __device__ inline uint32_t spz_sh_index(uint32_t s) {
+    const uint32_t j = s < 9u ? s / 3u : (s - 9u) / 5u, k = s < 9u ? s % 3u : 3u + (s - 9u) % 5u;
+    return 3u * k + j;
+}
+__host__ __device__ inline float spz_sh_value(uint32_t byte) {                         // unquantizeSH :31-33, stored fp32
+#pragma clang fp contract(off)
+    return (float)(((double)byte - 128.0) / 128.0);
+}
+
 struct AssetSection {
     uint32_t splat_count, max_splat_count, bucket_size, bucket_count, full_buckets, partial_buckets, sh_degree;
     uint32_t bytes_per_splat, scale_range;
@@ -316,13 +370,14 @@ __host__ __device__ inline uint32_t asset_center_bytes(uint32_t level) { return 
 __host__ __device__ inline uint32_t asset_rotation_bytes(uint32_t level) { return level == 0 ? 16u : 8u; }
 __host__ __device__ inline uint32_t sh_components(uint32_t degree) { return degree == 0 ? 0u : (degree == 1 ? 9u : 24u); }
 
-enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2 };
+enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3 };
 
 struct gs_asset {
     std::vector<uint8_t> buf;              // a .ksplat image (for an INRIA-v1 PLY: the level-0 section built from it; for the
-                                           // two row formats: built from `file` when a host fill first needs it)
+                                           // row formats: built from `file` when a host fill first needs it)
     uint32_t rows = ASSET_ROWS_KSPLAT;     // what the device decode reads: the image, or the file's own rows
-    std::vector<uint8_t> file;             // .splat / compressed PLY: the file as it was given
+    std::vector<uint8_t> file;             // .splat / compressed PLY: the file as it was given; .spz: the INFLATED stream
+    SpzLayout spz = {};                    // .spz: where the planes lie in `file`
     PcLayout pc = {};                      // compressed PLY: the header's layout
     size_t pc_chunk_base = 0, pc_vertex_base = 0, pc_sh_base = 0;   // where the three elements start in `file`
     uint32_t pc_chunk_count = 0;

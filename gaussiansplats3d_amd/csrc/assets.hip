@@ -1,5 +1,8 @@
 // assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device): INRIA-v1 .ply,
-// PlayCanvas compressed .ply, .splat and .ksplat -> the arrays the render / sort seams consume.  Restates, never copies:
+// PlayCanvas compressed .ply, .splat, .spz and .ksplat -> the arrays the render / sort seams consume.  Restates, never copies:
+//   .spz              src/loaders/spz/SpzLoader.js:255-342 (container; the gzip reader and every refusal are in spz_container.hpp),
+//                     :366-388 with optimizeSplatData false (file order); the row arithmetic (:160-250, 84-145 + SplatBuffer.js
+//                     :1092-1124) is in asset_internal.hpp, shared with the device
 //   PLY flavour       src/loaders/ply/PlyParserUtils.js:257-271 (determineHeaderFormatFromHeaderText)
 //   compressed PLY    src/loaders/ply/PlayCanvasCompressedPlyParser.js:74-157 (decodeHeaderText), :159-242 (decodeHeader); the row
 //                     arithmetic (:379-460 + SplatBuffer.js:1092-1124) is in asset_internal.hpp, shared with the device
@@ -20,8 +23,9 @@
 //                     then Vector3.applyMatrix4 :340-342, T3*C*T3^T :461-466, rotated SH :628-637, 684-688, 707-715, 766-817
 //   scene transform   three r160 Matrix4.decompose / Quaternion.setFromRotationMatrix / normalize / makeRotationFromQuaternion
 // An INRIA-v1 PLY is first laid out as the level-0 section the reference would build from it (file order, i.e. the reference's
-// `optimizeSplatData: false`), so every fill routine reads one format.  A .splat / compressed PLY asset keeps the file's own
-// rows (what the device decode uploads) and builds that level-0 section when a host fill first needs it.
+// `optimizeSplatData: false`), so every fill routine reads one format.  A .splat / compressed PLY / .spz asset keeps the file's
+// own rows (for .spz: the inflated planes; what the device decode uploads) and builds that level-0 section when a host fill
+// first needs it.
 // Reference quirk, documented and not reproduced: PlayCanvasCompressedPlyParser.readPly (:297-313) throws on a compressed PLY
 // without an `sh` element (TypeError: 'count' of undefined); the progressive path loads such files, and so does this reader.
 #include <algorithm>
@@ -335,7 +339,7 @@ void level0_header(std::vector<uint8_t>& buf, uint32_t count, uint32_t degree) {
     W32(KS_HEADER + 0, count); W32(KS_HEADER + 4, count); W16(KS_HEADER + 40, (uint16_t)degree);
 }
 
-// What a host fill of a .splat / compressed PLY asset reads: every file row through the shared row arithmetic
+// What a host fill of a .splat / compressed PLY / .spz asset reads: every file row through the shared row arithmetic
 // (asset_internal.hpp) into the level-0 row the reference stores for it.  Built once, on the first fill.
 int build_level0_image(gs_asset* a) {
     if (a->rows == ASSET_ROWS_KSPLAT || !a->buf.empty()) return GS_OK;
@@ -349,6 +353,26 @@ int build_level0_image(gs_asset* a) {
             uint32_t w[8];
             memcpy(w, a->file.data() + 32 * (size_t)i, 32);
             splat_row_tuple(w, t);
+        } else if (a->rows == ASSET_ROWS_SPZ) {
+            const SpzLayout& L = a->spz;
+            const uint8_t* f = a->file.data();
+            auto three = [&](int plane) {
+                const uint8_t* p = f + L.off[plane] + 3 * (size_t)i;
+                return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+            };
+            SpzRowBytes b;
+            const uint8_t* pp = f + L.off[SPZ_POSITIONS] + (size_t)L.pos_stride * i;
+            for (int k = 0; k < 3; k++)
+                b.pos[k] = L.pos_stride == 9u ? ((uint32_t)pp[3 * k] | ((uint32_t)pp[3 * k + 1] << 8) | ((uint32_t)pp[3 * k + 2] << 16))
+                                              : ((uint32_t)pp[2 * k] | ((uint32_t)pp[2 * k + 1] << 8));
+            b.alpha = f[L.off[SPZ_ALPHAS] + i];
+            b.colour = three(SPZ_COLOURS); b.scale = three(SPZ_SCALES); b.rotation = three(SPZ_ROTATIONS);
+            spz_row_tuple(L, b, t);
+            const uint8_t* sh = f + L.off[SPZ_SH] + 3 * (size_t)L.file_dim * i;
+            for (uint32_t s = 0; s < ncomp; s++) {
+                const float v = spz_sh_value(sh[spz_sh_index(s)]);
+                memcpy(o + 44 + 4 * s, &v, 4);
+            }
         } else {
             uint32_t w[4];
             memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
@@ -375,6 +399,22 @@ int parse_splat(gs_asset* a, const uint8_t* data, size_t bytes) {
     a->splat_count = (uint32_t)(bytes / 32);
     a->level = 0;
     a->sh_degree = 0;
+    return GS_OK;
+}
+
+// .spz: the gzip member is inflated and checked at open (spz_container.hpp: the stream is exactly header + planes, so every
+// plane byte of every splat exists); the asset keeps the inflated stream, never the gzip.
+int parse_spz(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+    SpzHeader h;
+    const char* refusal = spz_open(data, bytes, a->file, h);
+    GS_REQUIRE(refusal == nullptr, refusal);
+    uint32_t degree = want_degree < h.sh_degree ? want_degree : h.sh_degree;           // Math.min(file, out) :370
+    if (degree > 2) degree = 2;                                                        // the level-0 row holds two bands
+    a->rows = ASSET_ROWS_SPZ;
+    a->spz = h.layout;
+    a->splat_count = h.count;
+    a->level = 0;
+    a->sh_degree = degree;
     return GS_OK;
 }
 
@@ -566,6 +606,8 @@ int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t ma
             }
         } else if (format == GS_ASSET_SPLAT) {
             st = parse_splat(a, (const uint8_t*)data, (size_t)bytes);
+        } else if (format == GS_ASSET_SPZ) {
+            st = parse_spz(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
         } else if (format == GS_ASSET_KSPLAT) {
             a->buf.assign((const uint8_t*)data, (const uint8_t*)data + bytes);
             st = parse_ksplat(a);
@@ -609,7 +651,7 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
     GS_REQUIRE(!a->has_transform || !(scales || rotations),
                "scales / rotations of a transformed asset are not provided (gs_asset_set_transform(a, NULL) removes the transform)");
     try {
-        GS_TRY(build_level0_image(a));                       // .splat / compressed PLY: the first fill lays the level-0 rows out
+        GS_TRY(build_level0_image(a));                       // .splat / compressed PLY / .spz: the first fill lays the level-0 rows out
     } catch (const std::bad_alloc&) {
         gs_set_error("out of host memory while decoding the asset");
         return GS_ERR_NOMEM;

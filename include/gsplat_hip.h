@@ -226,10 +226,16 @@ typedef struct gs_asset gs_asset;
                               * src/loaders/splat/SplatParser.js:13-56, the progressive file-order path - every splat is
                               * kept and alpha is only zeroed at fill time by min_alpha (the array path of SplatLoader.js:12-22
                               * drops and reorders splats; that is not this interface's "file order")                 */
+enum { GS_ASSET_SPZ = 4 };   /* .spz, versions 1 and 2: a gzip member around a 16-byte header and six byte planes (positions,
+                              * alphas, colours, scales, rotations, SH): src/loaders/spz/SpzLoader.js with optimizeSplatData
+                              * false.  Inflated by the library's own reader (no zlib); refused by name: a damaged gzip (CRC-32,
+                              * ISIZE, truncation, bytes behind the trailer), a wrong magic, a version outside 1..2, more than
+                              * 10 000 000 points, an SH degree above 3, a stream that is not exactly header + planes.  A
+                              * degree-3 file is read at degree 2.  An enum constant, unlike its siblings: same value space   */
 /* Parses `data` (the bytes of the file).  max_sh_degree: outSphericalHarmonicsDegree (Viewer option
  * sphericalHarmonicsDegree); splats keep FILE order (the reference's optimizeSplatData:false).  A .splat / compressed
- * PLY asset keeps the file's own rows: gs_mesh_upload_asset / gs_sorter_upload_asset_centers send those to the device and
- * decode them there, gs_asset_fill decodes them on the host the first time it is called (compression_level 0, sh_level 1). */
+ * PLY / .spz asset keeps the file's own rows (.spz: the inflated planes): gs_mesh_upload_asset /
+ * gs_sorter_upload_asset_centers send those to the device and decode them there, gs_asset_fill decodes them on the host the first time it is called (compression_level 0, sh_level 1). */
 int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t max_sh_degree, gs_asset** out);
 void gs_asset_close(gs_asset* a);
 typedef struct gs_asset_info {

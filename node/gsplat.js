@@ -340,10 +340,12 @@ class StripGroup {
   dispose() { if (this.handle) { addon.groupDestroy(this.handle); this.handle = null; } }
 }
 
-// gs_asset_open's format argument (GS_ASSET_*), and the format of a file name: .splat has no magic number, so its extension decides
-const AssetFormat = { ply: 1, ksplat: 2, splat: 3 };
+// gs_asset_open's format argument (GS_ASSET_*), and the format of a file name: .splat has no magic number, so its extension decides;
+// .spz is a gzip member: its extension or the gzip magic 1f 8b
+const AssetFormat = { ply: 1, ksplat: 2, splat: 3, spz: 4 };
 const assetFormatOf = (fileName, bytes) => {
   if (/\.splat$/i.test(fileName)) return AssetFormat.splat;
+  if (/\.spz$/i.test(fileName) || (bytes[0] === 0x1f && bytes[1] === 0x8b)) return AssetFormat.spz;
   return bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? AssetFormat.ply : AssetFormat.ksplat;      // "ply"
 };
 module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon };

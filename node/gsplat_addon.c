@@ -759,7 +759,7 @@ static napi_value TreeGather(napi_env env, napi_callback_info info) {
     return num(env, render_count);
 }
 
-/* assetLoad(bytes ArrayBuffer|Uint8Array, format 1=ply (INRIA-v1 or PlayCanvas compressed, by its header) 2=ksplat 3=splat, maxShDegree, minAlpha, halfCov)
+/* assetLoad(bytes ArrayBuffer|Uint8Array, format 1=ply (INRIA-v1 or PlayCanvas compressed, by its header) 2=ksplat 3=splat 4=spz, maxShDegree, minAlpha, halfCov)
  *   -> {splatCount, shDegree, compressionLevel, shLevel, shMin, shMax, centers F32, cov F32|U16, rgba U8, sh U16|U8|null} */
 static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     ARGS(5)
@@ -798,7 +798,7 @@ static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     return r;
 }
 
-/* meshUploadAsset(mesh, from, bytes ArrayBuffer|Uint8Array, format 1=ply (INRIA-v1 or PlayCanvas compressed, by its header) 2=ksplat 3=splat, maxShDegree, first, count, minAlpha[, transform])
+/* meshUploadAsset(mesh, from, bytes ArrayBuffer|Uint8Array, format 1=ply (INRIA-v1 or PlayCanvas compressed, by its header) 2=ksplat 3=splat 4=spz, maxShDegree, first, count, minAlpha[, transform])
  *   -> splats uploaded
  * sorterUploadAssetCenters(sorter, from, bytes, format, maxShDegree, first, count, sceneIndexes|null[, transform]) -> splats uploaded
  * The per-splat decode on the device (gs_mesh_upload_asset / gs_sorter_upload_asset_centers): the file's rows cross to the card, not

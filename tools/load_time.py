@@ -1,17 +1,20 @@
 """Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
-    python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply] [--sh-degree 0..3]
+    python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply|spz] [--sh-degree 0..3]
                               [--repeats 5] [--transform identity | 16 numbers] [--out profiles/<tag>_load_time.txt]
   host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
   device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
 The file: $GS_DATA_DIR/<--file> when given (a name ending in .splat is one), else a seeded file of --n splats (the C3 count
 by default) in --format, from the writers of gaussiansplats3d_amd.assets: a level-2 SH-2 .ksplat (the default), an INRIA-v1
-PLY, a .splat, or a PlayCanvas compressed PLY with --sh-degree bands.  For .splat / compressed PLY the asset keeps the
-file's rows and the host decodes them on its first fill, so both paths open a fresh asset inside the timed region.  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
+PLY, a .splat, a PlayCanvas compressed PLY or a version-2 .spz with --sh-degree bands.  For .splat / compressed PLY / .spz the
+asset keeps the file's rows and the host decodes them on its first fill, so both paths open a fresh asset inside the timed
+region (for .spz that includes the inflate, on both paths).  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
 Viewer passes for a scene without one), set on the asset so both paths bake it (gs_asset_set_transform).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
 alternate.  Prints median and spread (max - min) of both and the bytes each sends over PCIe; the device path passes when its
 median is below the host path's by more than the larger spread."""
 import argparse
+import gzip
 import os
+import struct
 import sys
 import time
 
@@ -45,6 +48,9 @@ def seeded(fmt, n, sh_degree):
         return assets.write_splat(centers, np.exp(log_scales), rot, rng.integers(0, 256, size=(n, 4), dtype=np.uint8)), "splat", \
             f"seeded .splat, {n} splats"
     sh = rng.normal(0.0, 0.4, size=(n, ncoef)).astype(np.float32) if ncoef else None
+    if fmt == "spz":
+        return assets.write_spz(centers, log_scales, rot, rng.random((n, 4)), sh), "spz", \
+            f"seeded version-2 .spz, file SH degree {sh_degree}, {n} splats"
     if fmt == "compressed-ply":
         return assets.write_compressed_ply(centers, log_scales, rot, rng.random((n, 4)), sh), "ply", \
             f"seeded PlayCanvas compressed PLY, {ncoef} SH properties, {n} splats"
@@ -54,8 +60,8 @@ def seeded(fmt, n, sh_degree):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", default="ksplat", choices=["ksplat", "ply", "splat", "compressed-ply"])
-    ap.add_argument("--sh-degree", type=int, default=2, choices=[0, 1, 2, 3], help="bands of a seeded ply / compressed-ply")
+    ap.add_argument("--format", default="ksplat", choices=["ksplat", "ply", "splat", "compressed-ply", "spz"])
+    ap.add_argument("--sh-degree", type=int, default=2, choices=[0, 1, 2, 3], help="bands of a seeded ply / compressed-ply / spz")
     ap.add_argument("--n", type=int, default=5_800_000)
     ap.add_argument("--file", default=None)
     ap.add_argument("--repeats", type=int, default=5)
@@ -70,7 +76,7 @@ def main():
     if args.file:
         path = os.path.join(os.environ.get("GS_DATA_DIR", "."), args.file)
         data, source = open(path, "rb").read(), args.file
-        fmt = "splat" if args.file.lower().endswith(".splat") else None
+        fmt = "splat" if args.file.lower().endswith(".splat") else ("spz" if args.file.lower().endswith(".spz") else None)
     else:
         data, fmt, source = seeded(args.format, args.n, args.sh_degree)
 
@@ -83,7 +89,8 @@ def main():
     info = asset.info
     header = data[:data.index(b"end_header\n") + 11] if data[:3] == b"ply" else b""
     compressed = b"element chunk" in header
-    file_rows = fmt == "splat" or compressed                          # the asset keeps the file's rows
+    spz = fmt == "spz" or data[:2] == b"\x1f\x8b"
+    file_rows = fmt == "splat" or compressed or spz                   # the asset keeps the file's rows
     n, deg, sh8 = info.splat_count, info.sh_degree, info.sh_level == 2 and info.sh_degree > 0
     ncoef = {0: 0, 1: 9, 2: 24}[deg]
     ctx = Context(0)
@@ -123,6 +130,9 @@ def main():
             mesh.dispose()
     if fmt == "splat":
         device_bytes = 2 * len(data)                                  # the rows, once for the mesh and once for the sorter
+    elif spz:                                     # the position plane twice, the other planes once; the SH plane whole when the mesh keeps a band
+        version, _, file_degree = struct.unpack_from("<IIB", gzip.decompress(data), 4)
+        device_bytes = n * (2 * (9 if version == 2 else 6) + 10 + (3 * (0, 3, 8, 15)[file_degree] if ncoef else 0))
     elif compressed:                                                  # vertex rows + chunk rows twice, the SH bytes once
         sh_file = n * header.count(b"property uchar f_rest_")
         device_bytes = 2 * (len(data) - len(header) - sh_file) + (sh_file if ncoef else 0)
