@@ -334,9 +334,6 @@ struct gs_sorter {
     const SortFrame* result_frame = nullptr;
     DevBuf keep_mask;                  // 1 bit per list position (frustum-cull variant)
     DevBuf chunk_counts;               // survivors per chunk of the identity list (visibility-cull variant)
-    DevBuf key_sync;                   // uint32 [2]: {arrivals, time-outs} of k_depth_key_hist's barrier across the grid ($GSPLAT_KEY_HIST_FUSED)
-    uint32_t key_sync_base = 0;        // arrivals before the next launch
-    bool key_sync_used = false;
     DevBuf mask_copy;                  // the bound mesh's visibility mask as the last visibility-culled sort consumed it
     bool last_vis_culled = false;
     // distances a gs_mesh_compute_distances(..., dst = this sorter) left in `precomputed` (sorts with GS_PRECOMPUTED_DEVICE)
@@ -403,6 +400,29 @@ struct ProjectParams {
     uint32_t depth_mode;           // destination depth test (gs_mesh_set_destination): 0 = off, 1 = fp32 compare, 2 = as a 24-bit buffer
 };
 
+// The switches of the draw path (A/B runs and tests): read by draw_switches() (mesh.hip) and nowhere else, fetched once per
+// gs_mesh_render / gs_mesh_project and handed down.  (What a mesh or a context reads when it is created lives on gs_mesh / gs_context.)
+struct DrawSwitches {
+    // read once per process, at its first draw (the tests and the soaks start a child process per setting):
+    uint32_t deep_min;             // $GSPLAT_DEEP_MIN: (splat, quadrant) pairs a bin's previous draw walked before the deep pass takes it (4 * GS_CHUNK)
+    uint32_t deep_factor;          // $GSPLAT_DEEP_FACTOR: ... and that many times the mean bin (3)
+    uint32_t pool_slots;           // $GSPLAT_POOL_SLOTS: chunk partials the per-bin kernel may close, at most GS_POOL_SLOTS
+    bool no_lazy_mask;             // $GSPLAT_NO_LAZY_MASK: gs_mesh_project writes the by-original-index mask itself, never the bound sorter
+    // read on every draw (tests, tools and the bench set them inside a running process):
+    bool no_blend_order;           // $GSPLAT_NO_BLEND_ORDER: no schedule job, the blend's bins in row-major order
+    float order_motion;            // $GSPLAT_ORDER_MOTION: parallax, in screen heights, up to which the previous draw's order is taken (0.045)
+    bool no_stat_shift;            // $GSPLAT_NO_STAT_SHIFT: the previous draw's statistics are read unshifted
+    bool blend_order_stale;        // $GSPLAT_BLEND_ORDER_STALE: order from whatever draw came before (rounds 2-5)
+    bool deep_row_major_on_motion; // $GSPLAT_DEEP_ROW_MAJOR_ON_MOTION: a deep-pass draw of a moved camera drops the order as well
+    bool no_async_list_bins;       // $GSPLAT_NO_ASYNC_LIST_BINS: the list-bin size follows statistics reads only, not the mapped words
+    bool deep_units_last;          // $GSPLAT_DEEP_UNITS_LAST: the deep pass's workgroups behind every bin, all of them
+    float deep_share_k;            // $GSPLAT_DEEP_SHARE_K: the pass's workgroups per share of the previous walk (0.6)
+    bool deep_unit_at_set, deep_unit_wgs_set;
+    uint32_t deep_unit_at;         // $GSPLAT_DEEP_UNIT_AT: where the pass's workgroups sit in the blend's launch (tools/probes)
+    uint32_t deep_unit_wgs;        // $GSPLAT_DEEP_UNIT_WGS: ... and how many (clamped to 1 .. what the device holds by gs_launch_blend)
+};
+DrawSwitches draw_switches();
+
 struct gs_mesh {
     gs_context* ctx = nullptr;
     uint32_t list_shift = GS_LIST_SHIFT_LARGE;     // list-bin size of the next draw (mesh_collect_stats re-evaluates it)
@@ -462,9 +482,6 @@ struct gs_mesh {
     DevBuf rect_q;             // uint2 [render_count] their rects, same layout as cidx
     DevBuf coff;               // uint32 [render_count] first entry slot of each, relative to its binning workgroup
     DevBuf bin_sums;           // uint32 [3][BIN_MAX_BLOCKS]: entries | visible splats | 16-px tiles per workgroup
-    DevBuf bin_scan;           // k_bin_fused's scan across the grid: uint64 granules {draw serial, value} [3][BIN_MAX_BLOCKS] per slice,
-                               // [3][BIN_MAX_BLOCKS / 32] per group of slices, then one uint32 `fail` word (tile_bin.hip)
-    bool bin_scan_ready = false;
     DevBuf ekeyA, ekeyB, evalA, evalB;   // tile entries ping-pong (key = tile id, val = splat index)
     DevBuf tile_ranges;        // uint2 [bins]
     DevBuf frame;              // RenderFrame
@@ -487,7 +504,7 @@ struct gs_mesh {
     struct ScheduleArgs {      // what the last draw's schedule job was given (gs_mesh_debug_read(what = 7); tests)
         uint32_t ran, blend_bins;
         int32_t sx, sy;
-        uint32_t deep, deep_min, deep_factor, fused;
+        uint32_t deep, deep_min, deep_factor;
     } sched = {};
     RadixScratch radix;
     uint32_t entry_capacity = 0;
@@ -582,6 +599,6 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
 constexpr int GS_ORIG_MASK_NONE = 0, GS_ORIG_MASK_WRITE = 1, GS_ORIG_MASK_DERIVED = 2;
 int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,
                       bool whole_stage = false);
-int gs_launch_binning(gs_mesh* m, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
-int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev);
+int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
+int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, uint8_t* out_dev);
 int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev);

@@ -238,6 +238,37 @@ static int mesh_alloc_entries(gs_mesh* m, uint32_t capacity) {
     return GS_OK;
 }
 
+// The draw path's switches (gs_internal.hpp: DrawSwitches), read here and nowhere else.  (gs_mesh_create below reads the switches
+// that hold for a mesh's lifetime.)
+DrawSwitches draw_switches() {
+    static const uint32_t deep_min = getenv("GSPLAT_DEEP_MIN") ? (uint32_t)atoi(getenv("GSPLAT_DEEP_MIN")) : 4u * GS_CHUNK;
+    static const uint32_t deep_factor = getenv("GSPLAT_DEEP_FACTOR") ? (uint32_t)atoi(getenv("GSPLAT_DEEP_FACTOR")) : 3u;
+    static const uint32_t pool_slots = getenv("GSPLAT_POOL_SLOTS") ? std::min<uint32_t>((uint32_t)atoi(getenv("GSPLAT_POOL_SLOTS")), GS_POOL_SLOTS) : GS_POOL_SLOTS;
+    static const bool no_lazy_mask = getenv("GSPLAT_NO_LAZY_MASK") != nullptr;
+    DrawSwitches sw = {};
+    sw.deep_min = deep_min;
+    sw.deep_factor = deep_factor;
+    sw.pool_slots = pool_slots;
+    sw.no_lazy_mask = no_lazy_mask;
+    sw.no_blend_order = getenv("GSPLAT_NO_BLEND_ORDER") != nullptr;
+    const char* motion = getenv("GSPLAT_ORDER_MOTION");
+    sw.order_motion = motion ? (float)atof(motion) : 0.045f;
+    sw.no_stat_shift = getenv("GSPLAT_NO_STAT_SHIFT") != nullptr;
+    sw.blend_order_stale = getenv("GSPLAT_BLEND_ORDER_STALE") != nullptr;
+    sw.deep_row_major_on_motion = getenv("GSPLAT_DEEP_ROW_MAJOR_ON_MOTION") != nullptr;
+    sw.no_async_list_bins = getenv("GSPLAT_NO_ASYNC_LIST_BINS") != nullptr;
+    sw.deep_units_last = getenv("GSPLAT_DEEP_UNITS_LAST") != nullptr;
+    const char* share_k = getenv("GSPLAT_DEEP_SHARE_K");
+    sw.deep_share_k = share_k ? (float)atof(share_k) : 0.6f;
+    const char* unit_at = getenv("GSPLAT_DEEP_UNIT_AT");
+    const char* unit_wgs = getenv("GSPLAT_DEEP_UNIT_WGS");
+    sw.deep_unit_at_set = unit_at != nullptr;
+    sw.deep_unit_wgs_set = unit_wgs != nullptr;
+    sw.deep_unit_at = unit_at ? (uint32_t)atoi(unit_at) : 0u;
+    sw.deep_unit_wgs = unit_wgs ? (uint32_t)atoi(unit_wgs) : 0u;
+    return sw;
+}
+
 extern "C" {
 
 int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree, uint32_t flags, gs_mesh** out) {
@@ -757,17 +788,6 @@ static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
         GS_HIP(hipStreamSynchronize(st));
         if (w[GS_FLAG_POOL_OVER]) m->last.flags |= GS_DRAW_POOL_EXHAUSTED;
     }
-    if (m->bin_scan_ready) {                               // k_bin_fused: a poll of the scan across its grid ran out of patience
-        uint32_t fail = 0;
-        GS_HIP(hipMemcpyAsync(&fail, (const char*)m->bin_scan.p + ((size_t)3 * 2048 + 3 * 64) * 8, 4, hipMemcpyDeviceToHost, st));
-        GS_HIP(hipStreamSynchronize(st));
-        if (fail) {
-            // (reported once: the word is cleared so that the draws that follow are judged on their own)
-            GS_HIP(hipMemsetAsync((char*)m->bin_scan.p + ((size_t)3 * 2048 + 3 * 64) * 8, 0, 4, st));
-            gs_set_error("the binner's cross-workgroup scan timed out (k_bin_fused): the frame is incomplete");
-            return GS_ERR_HIP;
-        }
-    }
     m->last.entries_scanned = 0;
     m->last.splats_walked = 0;
     m->last.halves_evaluated = 0;
@@ -830,8 +850,8 @@ static int mesh_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, bool
     return GS_OK;
 }
 
-static int mesh_draw_once(gs_mesh* m, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R,
-                          uint8_t* out_dev, bool projected, bool timed) {
+static int mesh_draw_once(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter,
+                          uint32_t R, uint8_t* out_dev, bool projected, bool timed) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream, aux = ctx->aux;
     timed = timed || ctx->stage_events;
@@ -846,9 +866,9 @@ static int mesh_draw_once(gs_mesh* m, const ProjectParams& pp, const uint32_t* o
     if (timed) GS_HIP(hipEventRecord(m->ev[1], st));
     // the index list is in the caller's splat numbering unless it comes from a sorter bound to this mesh
     m->translate = m->reorder && !(sorter && sorter->result_mesh == m);
-    GS_TRY(gs_launch_binning(m, pp, order_dev, sorter, R));   // records ev[2] between emit and the tile sort
+    GS_TRY(gs_launch_binning(m, sw, pp, order_dev, sorter, R));   // records ev[2] between emit and the tile sort
     if (timed) GS_HIP(hipEventRecord(m->ev[3], st));
-    GS_TRY(gs_launch_blend(m, pp, out_dev));
+    GS_TRY(gs_launch_blend(m, sw, pp, out_dev));
     m->stats_pp = pp;                                          // whose view the per-bin blend statistics now describe
     m->stats_pp_valid = true;
     m->drawn_dest_depth = m->dest_depth; m->drawn_dest_rgba = m->dest_rgba;      // the destination this draw saw (gs_mesh_debug_rop8)
@@ -935,7 +955,7 @@ static int mesh_params(gs_mesh* m, const gs_camera* cam, ProjectParams& pp) {
 // The share of the scene in view, from the last FULL-frame draw whose verdict has arrived (a 16-byte store of k_bin_emit's into the
 // mapped words: {serial, visible, 16-px tiles}), and the size of the list bins from the last draw of any kind; hints for the vertex
 // stage's launch shape (project.hip) and the binner's geometry: frames do not depend on either.
-static void mesh_read_view_share(gs_mesh* m) {
+static void mesh_read_view_share(gs_mesh* m, const DrawSwitches& sw) {
     volatile uint32_t* mir = m->mirror_host;
     const uint32_t vs = mir[8], vv = mir[9], t_lo = mir[10], t_hi = mir[11];
     if (vs == 0u || mir[8] != vs) return;                   // nothing yet / a newer draw is writing: look again next time
@@ -945,7 +965,7 @@ static void mesh_read_view_share(gs_mesh* m) {
     }
     if (vs != m->adapted_serial) {                          // (any draw, strips included: tiles per visible splat is a ratio)
         m->adapted_serial = vs;
-        if (!getenv("GSPLAT_NO_ASYNC_LIST_BINS")) {
+        if (!sw.no_async_list_bins) {
             const uint32_t before = m->list_shift;
             const uint64_t tiles16 = ((uint64_t)t_hi << 32) | t_lo;
             mesh_adapt_list_bins(m, tiles16, vv);
@@ -959,10 +979,10 @@ static void mesh_read_view_share(gs_mesh* m) {
     }
 }
 
-static int mesh_heal_overflow(gs_mesh* m, bool* healed) {
+static int mesh_heal_overflow(gs_mesh* m, const DrawSwitches& sw, bool* healed) {
     *healed = false;
     volatile uint32_t* mir = m->mirror_host;
-    mesh_read_view_share(m);
+    mesh_read_view_share(m, sw);
     if (m->grow_entries_to > m->entry_capacity) {           // the list bins just became smaller (mesh_read_view_share)
         GS_HIP(hipStreamSynchronize(m->ctx->stream));       // draws in flight still use the old buffers
         GS_TRY(mesh_alloc_entries(m, m->grow_entries_to));
@@ -990,8 +1010,7 @@ int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
     ScopedDevice sd(m->ctx->device);
     // + the per-splat mask a visibility-culled sort reads: written here by one atomic per survivor - or, for a full frame whose
     // consumer is a bound sorter that holds the mesh's position map, left to that sorter (k_mask_derive_count: 25 us of a C3 frame)
-    static const bool no_lazy = getenv("GSPLAT_NO_LAZY_MASK") != nullptr;      // (A/B and tests)
-    const bool lazy = m->derive_orig_mask && m->reorder && !no_lazy && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
+    const bool lazy = m->derive_orig_mask && m->reorder && !draw_switches().no_lazy_mask && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
     GS_TRY(mesh_project(m, pp, lazy ? GS_ORIG_MASK_DERIVED : GS_ORIG_MASK_WRITE, m->ctx->stage_events));
     m->vis_orig_lazy = lazy;
     m->projection_pending = true;
@@ -1013,8 +1032,9 @@ int gs_mesh_render(gs_mesh* m, const gs_camera* cam, const uint32_t* sorted_host
 
     ProjectParams pp;
     GS_TRY(mesh_params(m, cam, pp));
+    const DrawSwitches sw = draw_switches();
     bool healed = false;
-    GS_TRY(mesh_heal_overflow(m, &healed));
+    GS_TRY(mesh_heal_overflow(m, sw, &healed));
     // a gs_mesh_project of exactly this camera is consumed by exactly one draw (the vertex stage runs once per frame)
     bool projected = m->projection_pending && memcmp(cam, &m->projected_cam, sizeof(*cam)) == 0 && m->projected_depth_mode == pp.depth_mode;
     m->projection_pending = false;
@@ -1038,7 +1058,7 @@ int gs_mesh_render(gs_mesh* m, const gs_camera* cam, const uint32_t* sorted_host
     }
 
     m->last = gs_render_stats();
-    GS_TRY(mesh_draw_once(m, pp, order_dev, sorter, render_count, out_dev, projected, stats != nullptr));
+    GS_TRY(mesh_draw_once(m, sw, pp, order_dev, sorter, render_count, out_dev, projected, stats != nullptr));
     m->has_draw = true;
     m->last_count = pp.count;
 
@@ -1056,7 +1076,7 @@ int gs_mesh_render(gs_mesh* m, const gs_camera* cam, const uint32_t* sorted_host
                 return GS_ERR_CAPACITY;
             }
             GS_TRY(mesh_alloc_entries(m, (uint32_t)want));
-            GS_TRY(mesh_draw_once(m, pp, order_dev, sorter, render_count, out_dev, true, stats != nullptr));   // records still valid
+            GS_TRY(mesh_draw_once(m, sw, pp, order_dev, sorter, render_count, out_dev, true, stats != nullptr));   // records still valid
             ov = mesh_collect_stats(m, nullptr);
             if (ov < 0) return ov;
             m->last.overflowed = 1;
@@ -1188,7 +1208,7 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
                               // and where the last vertex stage ran its block test (1 separate kernel, 0 per workgroup, 2 nowhere)
         GS_REQUIRE(count == 3, "count == 3");
         GS_HIP(hipStreamSynchronize(st));
-        mesh_read_view_share(m);                           // (the mapped words the last draw left)
+        mesh_read_view_share(m, draw_switches());          // (the mapped words the last draw left)
         uint32_t* w = static_cast<uint32_t*>(dst);
         w[0] = m->measured_visible; w[1] = m->measured_count; w[2] = m->last_project_mode;
         return GS_OK;
@@ -1200,7 +1220,7 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_HIP(hipStreamSynchronize(st));
         volatile uint32_t* mir = (volatile uint32_t*)m->mirror_host;
         const gs_mesh::ScheduleArgs& a = m->sched;
-        const uint32_t head[GS_SCHEDULE_WORDS] = {a.ran, a.blend_bins, (uint32_t)a.sx, (uint32_t)a.sy, a.deep, a.deep_min, a.deep_factor, a.fused,
+        const uint32_t head[GS_SCHEDULE_WORDS] = {a.ran, a.blend_bins, (uint32_t)a.sx, (uint32_t)a.sy, a.deep, a.deep_min, a.deep_factor, 0u /* reserved */,
                                                   mir ? mir[4] : 0u, mir ? mir[5] : 0u};
         memcpy(dst, head, sizeof(head));
         if (count > GS_SCHEDULE_WORDS)

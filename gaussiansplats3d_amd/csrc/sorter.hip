@@ -139,16 +139,8 @@ __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g)
 // The housekeeping folded into the first kernel of a sort (two launches and their boundaries saved per sort): the radix digit
 // totals are zeroed before any histogram adds to them, and the OTHER SortFrame is reset for the next sort.  t / stride: the
 // thread's index in the grid / the grid's size.
-// AGENT (k_depth_key_hist): pass 0's group rows - the first RADIX_MAX_GROUPS x RADIX_BINS words - are added to inside the same
-// launch, behind its barrier, by workgroups of other XCDs: zeroed with agent-scope stores, which go through to the memory side - a
-// plain store would sit dirty in this XCD's L2 until a release wrote the whole L2 back, and 472 such releases made that kernel
-// 80 us long.  The later passes' rows are read by later kernels and take plain stores.
-template <bool AGENT = false>
 __device__ __forceinline__ void sort_begin(const KeyParams& p, uint32_t t, uint32_t stride) {
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) {
-        if (AGENT && w < (uint32_t)(RADIX_MAX_GROUPS * RADIX_BINS)) __hip_atomic_store(&p.digit_total[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else p.digit_total[w] = 0u;
-    }
+    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
     if (t < SORT_SHARDS) {
         p.next_frame->key_min[t] = KEY_MIN_INIT;
         p.next_frame->key_max[t] = KEY_MAX_INIT;
@@ -952,94 +944,6 @@ __global__ void k_unmap(const uint32_t* __restrict__ in, const uint32_t* __restr
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = unmap[min(in[i], last)];
 }
 
-// Phase A + the histogram of pass 0 in ONE launch ($GSPLAT_KEY_HIST_FUSED=1, opt-in).  A key's bucket needs the
-// exact min / max over ALL keys (sorter.cpp:142-146), which exist only when the last workgroup has keyed its splats - so the launch
-// is two phases around a barrier ACROSS THE GRID: one workgroup per chunk of the pass-0 scatter (radix.hpp: <= CHUNK_TILES tiles),
-// every thread keeps its <= 12 keys in registers, the grid meets on one counter (no reset: it only ever grows, every launch waits for
-// `base + gridDim.x`), then each workgroup reads the final min / max and histograms its own keys - the 24 MB re-read of the keys and
-// the kernel boundary of k_radix_hist are what this saves, the barrier is what it costs.  Needs the whole grid resident at once (the
-// host launches it only for <= 2 workgroups of 1024 threads per CU); the wait is bounded all the same: a workgroup that runs out of
-// patience raises `fail` (the sort reports GS_ERR_HIP at the next statistics read) instead of hanging the device.
-// Identity list, static integer mode, sort_start = 0, render_count a multiple of 4 (the 16-byte plane loads).
-#ifndef KEY_HIST_SLEEP
-#define KEY_HIST_SLEEP 4
-#endif
-struct KeyHistSync {
-    uint32_t* arrive;          // grows by gridDim.x per launch
-    uint32_t* fail;
-    uint32_t base;             // *arrive before this launch
-};
-__global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, DepthLoader ld, int shift, uint32_t* __restrict__ block_hist,
-                                                                  uint32_t* __restrict__ digit_total, KeyHistSync sync) {
-    __shared__ uint32_t s_hist[4][RADIX_BINS];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6;
-    sort_begin<true>(p, blockIdx.x * blockDim.x + tid, gridDim.x * blockDim.x);   // (pass 0's rows are added to behind the barrier below)
-    for (uint32_t k = tid; k < 4u * RADIX_BINS; k += HIST_THREADS) (&s_hist[0][0])[k] = 0;
-    const uint32_t R = p.render_count;
-    const RadixChunk ch = radix_chunk(R);
-    // logical element j of the radix passes is list position R - 1 - j: this chunk's elements [j0, j1) are positions (R - j1, R - j0]
-    const uint32_t j0 = min(ch.tile_begin * (uint32_t)RADIX_TILE, R), j1 = min(ch.tile_end * (uint32_t)RADIX_TILE, R);
-    const uint32_t v0 = (R - j1) / 4u, v1 = (R - j0) / 4u;                  // vectors of four positions (R, j0, j1 are multiples of 4)
-    constexpr uint32_t KV = (uint32_t)CHUNK_TILES * RADIX_TILE / (HIST_THREADS * 4u);
-    static_assert(KV * HIST_THREADS * 4u == (uint32_t)CHUNK_TILES * RADIX_TILE, "whole vectors per thread");
-    const uint4* x4 = reinterpret_cast<const uint4*>(p.cx);
-    const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
-    const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
-    int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-    int4 key[KV];
-    MinMax mm;
-    uint4 x[KV], y[KV], z[KV];
-#pragma unroll
-    for (uint32_t k = 0; k < KV; k++) {
-        const uint32_t v = min(v0 + k * HIST_THREADS + tid, v1 ? v1 - 1u : 0u);     // (unconditional loads, clamped)
-        x[k] = x4[v]; y[k] = y4[v]; z[k] = z4[v];
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < KV; k++) {
-        const uint32_t v = v0 + k * HIST_THREADS + tid;
-        key[k] = static_key_int4(p, x[k], y[k], z[k]);
-        if (v < v1) {
-            o4[v] = key[k];
-            mm.take(key[k]);
-        }
-    }
-    mm.publish_block<HIST_THREADS / 64>(p.frame);
-    if (tid == 0) {
-        // The barrier across the grid.  What the other workgroups need from this one are agent-scope atomics and stores (min / max,
-        // the zeroed group rows): performed at the memory side, so "complete" is "visible" - the arrival only has to be issued after
-        // they are complete (a workgroup-scope release = s_waitcnt), not after an L2 write-back.  The keys and the histogram rows are
-        // for the NEXT kernel.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __hip_atomic_fetch_add(sync.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t spins = 0;
-        // (relaxed polls: an acquiring load per poll invalidates the caches the workgroups that are still keying read through)
-        while (__hip_atomic_load(sync.arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - sync.base < gridDim.x) {
-            __builtin_amdgcn_s_sleep(KEY_HIST_SLEEP);
-            if (++spins > 4000000u) { atomicAdd(sync.fail, 1u); break; }            // (seconds: the grid was not resident at once)
-        }
-        // (what is read behind the barrier is read with agent-scope atomic loads and updated with agent-scope atomics: no acquire)
-    }
-    __syncthreads();
-    // phase 2: the final range (fresh loads: the words were written by other workgroups' atomics)
-    ld.set_range(__hip_atomic_load(&ld.frame->key_min[tid & (SORT_SHARDS - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                 __hip_atomic_load(&ld.frame->key_max[tid & (SORT_SHARDS - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    uint32_t* hist = s_hist[wave & 3u];
-#pragma unroll
-    for (uint32_t k = 0; k < KV; k++) {
-        if (v0 + k * HIST_THREADS + tid < v1) {
-            atomicAdd(&hist[(ld.hist_key(key[k].x) >> shift) & 255u], 1u);
-            atomicAdd(&hist[(ld.hist_key(key[k].y) >> shift) & 255u], 1u);
-            atomicAdd(&hist[(ld.hist_key(key[k].z) >> shift) & 255u], 1u);
-            atomicAdd(&hist[(ld.hist_key(key[k].w) >> shift) & 255u], 1u);
-        }
-    }
-    __syncthreads();
-    if (tid >= RADIX_BINS || ch.tile_begin >= ch.tile_end) return;
-    const uint32_t total = s_hist[0][tid] + s_hist[1][tid] + s_hist[2][tid] + s_hist[3][tid];
-    block_hist[ch.id * RADIX_BINS + tid] = total;
-    if (total) atomicAdd(&digit_total[(ch.id / RADIX_GROUP) * RADIX_BINS + tid], total);
-}
-
 __global__ void k_debug_buckets(DepthLoader ld, int32_t* out) {
     ld.prepare();
     for (uint32_t i = ld.sort_start + blockIdx.x * blockDim.x + threadIdx.x; i < ld.render_count;
@@ -1056,7 +960,6 @@ struct Pass0Args {
     void* kbuf0;
     uint32_t* vo;
     uint32_t* kept_out;
-    bool skip_hist;                     // k_depth_key_hist already left pass 0's histogram rows
 };
 template <bool CULL, bool IDX>
 static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
@@ -1064,7 +967,7 @@ static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
     const L d = {a.ld};
     L h = d;                            // only the histogram launch counts clamped buckets (once per element)
     h.count_clamps = 1;
-    if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, a.vo, a.val_bits, a.kept_out, a.skip_hist);
+    if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, a.vo, a.val_bits, a.kept_out);
     if (a.pack) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint8_t*)nullptr, a.vo, nullptr, 0u, a.val_bits, a.kept_out);
     if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out);
     return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint16_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out);
@@ -1213,16 +1116,6 @@ static int sorter_collect_stats(gs_sorter* s, gs_sort_stats* stats) {
     SortFrame f;
     GS_HIP(hipMemcpyAsync(&f, s->frame.as<SortFrame>() + s->frame_index, sizeof(f), hipMemcpyDeviceToHost, s->stream));
     GS_HIP(hipStreamSynchronize(s->stream));
-    if (s->key_sync_used) {                        // k_depth_key_hist: a workgroup gave up waiting for the rest of its grid
-        uint32_t w[2] = {0u, 0u};
-        GS_HIP(hipMemcpyAsync(w, s->key_sync.p, sizeof(w), hipMemcpyDeviceToHost, s->stream));
-        GS_HIP(hipStreamSynchronize(s->stream));
-        if (w[1]) {
-            GS_HIP(hipMemsetAsync((char*)s->key_sync.p + 4, 0, 4, s->stream));       // (reported once)
-            gs_set_error("the key kernel's barrier across its grid timed out (k_depth_key_hist): the sorted list is not valid");
-            return GS_ERR_HIP;
-        }
-    }
     float ms = 0.f;
     if (s->timed_sort) GS_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     int32_t key_lo = f.lo(), key_hi = f.hi();
@@ -1243,23 +1136,20 @@ static int sorter_collect_stats(gs_sorter* s, gs_sort_stats* stats) {
 // ---------------------------------------------------------------------------------------------------
 // One sort, in steps: sort_check -> sort_stage_inputs -> launch_front_end -> run_radix_passes -> sort_finish.
 // ---------------------------------------------------------------------------------------------------
-// The switches of this file (A/B runs and tests), read here and nowhere else.
+// The switches of this file (A/B runs and tests), read here and nowhere else: once per process, at its first sort (the tests and
+// the soaks start a child process per setting).
 struct SortSwitches {
-    // read once per process, at its first sort (the tests and the soaks start a child process per setting):
     bool tree_no_fuse;         // $GSPLAT_TREE_NO_FUSE: a planned gather is copied by tree.hip, never by the key kernel
     const char* vis_front;     // $GSPLAT_VIS_FRONT = stream | compact: forces one front end of the visibility cull
     bool no_pack;              // $GSPLAT_NO_SORT_PACK: the unpacked radix passes
     bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
-    // read on every sort (tests and the soaks set it inside a running process):
-    bool key_hist_fused;       // $GSPLAT_KEY_HIST_FUSED, unless one of the two above is set in the environment NOW
 };
 static SortSwitches sort_switches() {
     static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
     static const char* vis_front = getenv("GSPLAT_VIS_FRONT");
     static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
     static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
-    return {tree_no_fuse, vis_front, no_pack, no_chunk,
-            getenv("GSPLAT_KEY_HIST_FUSED") && !getenv("GSPLAT_NO_SORT_PACK") && !getenv("GSPLAT_NO_SORT_CHUNK")};
+    return {tree_no_fuse, vis_front, no_pack, no_chunk};
 }
 
 static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
@@ -1302,7 +1192,6 @@ struct SortPlan {
     bool fused_tree;                   // the gathered list is still to be copied, and this sort does it itself
     // launch_front_end
     bool vec4;                         // identity list + static integer mode
-    bool key_hist_fused;               // k_depth_key_hist left pass 0's histogram
     bool vis_front;                    // the visibility cull's front end wrote keys and payloads of the survivors itself
 };
 
@@ -1550,25 +1439,12 @@ static int launch_vis_cull_front(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     return GS_OK;
 }
 
-// $GSPLAT_KEY_HIST_FUSED=1: keys + pass 0's histogram in one launch behind a barrier across the grid (k_depth_key_hist) - only for
-// the plain full sort of the identity list whose pass 0 is the packed, chunk-staged one, and only when the whole grid is
-// resident at once (<= 2 workgroups of 1024 threads per CU).  Returns the grid, 0 = not this sort.
-static uint32_t key_hist_grid(const gs_sorter* s, const SortPlan& pl) {
-    if (!pl.sw.key_hist_fused || !pl.vec4 || pl.fused_tree || pl.vis_cull || pl.cull || pl.sort_start != 0u || (pl.R & 3u) != 0u ||
-        pl.list_count_dev || s->precision <= 8u)
-        return 0u;
-    const uint32_t grid = radix_chunk_grid_for(pl.Rs);
-    return (pl.val_bits <= 24u && (s->precision - 8u) + pl.val_bits <= 32u && grid <= 2u * (uint32_t)s->ctx->cu_count) ? grid : 0u;
-}
-
 // 3. the first kernel(s) of the sort: keys, min / max, the housekeeping (sort_begin) - one branch per kernel family
 static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     gs_context* ctx = s->ctx;
     hipStream_t st = s->stream;
     const uint32_t cus = (uint32_t)ctx->cu_count;
     pl.vec4 = (kp.mode == MODE_INT) && !pl.idx_dev;
-    const uint32_t kh_grid = key_hist_grid(s, pl);
-    pl.key_hist_fused = kh_grid != 0u;
     if (pl.fused_tree) {
         GS_TRY(launch_tree_front(s, pl, kp));
     } else if (pl.vis_cull) {
@@ -1576,20 +1452,6 @@ static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     } else if (pl.cull) {
         if (pl.vec4) hipLaunchKernelGGL(k_depth_key_cull<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * 2)), dim3(256), 0, st, kp);
         else hipLaunchKernelGGL(k_depth_key_cull<false>, dim3(grid_for(pl.Rs, 256 * 4, cus * 4)), dim3(256), 0, st, kp);
-    } else if (pl.key_hist_fused) {
-        if (!s->key_sync.p) {
-            GS_TRY(s->key_sync.alloc(64));
-            GS_HIP(hipMemsetAsync(s->key_sync.p, 0, 64, st));
-            s->key_sync_base = 0u;
-        }
-        DepthLoaderArgs hl = {};
-        hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
-        hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
-        KeyHistSync sync = {s->key_sync.as<uint32_t>(), s->key_sync.as<uint32_t>() + 1, s->key_sync_base};
-        s->key_sync_base += kh_grid;
-        s->key_sync_used = true;
-        hipLaunchKernelGGL(k_depth_key_hist, dim3(kh_grid), dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, 0, s->radix.block_hist.as<uint32_t>(),
-                           s->radix.digit_total.as<uint32_t>(), sync);
     } else if (pl.vec4) {
         hipLaunchKernelGGL(k_depth_key<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * GS_KEY_GRID_MULT)), dim3(256), 0, st, kp);
     } else {
@@ -1642,7 +1504,6 @@ static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& k
             a.ld = dl; a.Rs = Rs; a.val_bits = val_bits; a.shift = shift;
             a.pack = pack; a.chunked = chunked; a.wide = wide; a.kbuf0 = kbuf[0]; a.vo = vo;
             a.kept_out = pl.cull ? &kp.frame->kept : nullptr;      // a culling pass 0 compacts: it publishes the result's length
-            a.skip_hist = pl.key_hist_fused;
             const bool has_idx = dl.idx != nullptr;
             if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
             else if (pl.cull) GS_TRY((depth_pass0<true, false>(ex, a)));

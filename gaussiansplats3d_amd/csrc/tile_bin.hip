@@ -72,7 +72,7 @@ extern "C" int gs_debug_bin_prof(void* dst) {
 #endif
 
 // The count pass over one workgroup's slice [pos_begin, pos_end) of the near->far walk: filter, one gather per position of a live
-// block, compaction into the slice of (slot, rect, first entry) lists.  Shared by k_bin_count and k_bin_fused.
+// block, compaction into the slice of (slot, rect, first entry) lists (k_bin_count).
 struct SliceCount {
     uint32_t entries, splats, t16;       // entries emitted by the slice | compacted (visible) splats | this LANE's 16-px tiles (statistics)
 };
@@ -300,19 +300,14 @@ struct StatShift {
     int32_t sx, sy;            // this draw's bin (bx, by) shows what the previous draw's bin (bx - sx, by - sy) showed
     uint32_t bins_x;
 };
-// The blend's schedule and the deep pass's members, one workgroup of BIN_THREADS (see where it is called: k_bin_emit / k_bin_fused)
+// The blend's schedule and the deep pass's members, one workgroup of BIN_THREADS (see where it is called: k_bin_emit)
 // (prev_blend_stats and blend_stats_w are the same buffer - the previous draw's statistics, read, then the members' zeroed: no
 // __restrict__ on either)
 __device__ __forceinline__ void blend_schedule_job(const uint2* prev_blend_stats, uint32_t blend_bins, uint32_t* __restrict__ blend_order,
                                                    uint32_t deep, uint32_t* __restrict__ deep_flags, uint32_t* blend_stats_w,
                                                    uint32_t deep_min, uint32_t deep_factor, volatile uint32_t* __restrict__ mirror, StatShift sh) {
     __shared__ uint32_t s_cost[RADIX_BINS], s_tmp2[4];
-    // the chunked composite's per-draw words: no deep bins yet, an empty partial pool (k_bin_count resets them as well; in the fused
-    // launch this workgroup runs BESIDE the counting workgroups, so the reset has to be its own)
-    if (threadIdx.x < GS_FLAG_LIST) deep_flags[threadIdx.x] = 0u;
-    for (uint32_t w = threadIdx.x; w < blend_bins; w += BIN_THREADS) deep_flags[GS_FLAG_OF + w] = GS_DEEP_NONE;
-    __threadfence_block();
-    __syncthreads();
+    // (the chunked composite's per-draw words - no deep bins yet, an empty partial pool - were reset by k_bin_count, a kernel boundary ago)
     // three sweeps over the statistics, 8 loads in flight per lane (registers for all 8192 / 256 values would set the
     // whole kernel's VGPR allocation and cost every emitting workgroup its occupancy)
     constexpr uint32_t SWEEP = 8;
@@ -564,166 +559,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
     (void)emitted;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// k_bin_fused: count + emit in ONE launch (round 6).
-// k_bin_count fixes where every splat's entries go and k_bin_emit, a kernel boundary later, re-reads the compacted lists from a
-// grid that first scans all 2048 slice sums again.  Here the workgroup that counted a slice also emits it, as soon as it knows how
-// many entries the slices in front of it hold - a scan ACROSS the running grid:
-//   * every workgroup publishes {entries, visible splats, 16-px tiles} of its slice as 8-byte granules {tag, value} (one relaxed
-//     agent-scope store each: the value and its "ready" flag travel together, no fence; tag = the draw's serial, so the rows are
-//     never reset);
-//   * two levels: the last slice of a GROUP of 32 sums its group and publishes the group's row; a slice needs its <= 31
-//     predecessors inside the group and the <= 63 group rows in front = two rounds of polls by one wave (a flat look-back over
-//     2048 slices that all finish counting at the same moment would walk ~1000 granules per slice);
-//   * the LAST slice knows the frame's totals and writes the RenderFrame scalars and the host mirror.
-// Who waits for whom: slice c only ever waits for slices < c.  Slice ids are a function of blockIdx (xcd_chunk: monotone within
-// an XCD), every XCD starts its workgroups in blockIdx order, so the smallest unfinished slice is always running or the next one
-// its XCD starts: no cycle, whatever the residency (and all 2048 are resident at once on a whole MI355X: 8 per CU).  Every poll is
-// bounded all the same: a poll that runs out of patience raises `fail` (the draw reports GS_ERR_HIP on the next statistics read)
-// instead of hanging the device.
-struct BinScan {
-    unsigned long long* chunk_rows;     // [3][BIN_MAX_BLOCKS]
-    unsigned long long* group_rows;     // [3][BIN_MAX_BLOCKS / BIN_SCAN_GROUP]
-    uint32_t* fail;
-    uint32_t tag;
-};
-#ifndef BIN_SCAN_SLEEP
-#define BIN_SCAN_SLEEP 100              // units of 64 cycles between two polls of a wave (4 / 32 / 100: C3 bin stage 0.0642 / 0.0610 / 0.0598 ms)
-#endif
-constexpr uint32_t BIN_SCAN_GROUP = 32, BIN_SCAN_GROUPS = BIN_MAX_BLOCKS / BIN_SCAN_GROUP;
-static_assert(BIN_SCAN_GROUP <= 64 && BIN_SCAN_GROUPS <= 64, "one lane per predecessor / per group row");
-__device__ __forceinline__ void bin_scan_put(unsigned long long* p, uint32_t value, uint32_t tag) {
-    __hip_atomic_store(p, ((unsigned long long)tag << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t bin_scan_poll(const unsigned long long* p, uint32_t tag, uint32_t* fail) {
-    for (uint32_t spin = 0; spin < (1u << 21); spin++) {                  // ~ 1 s with the sleeps: a wrong frame, never a hung GPU
-        const unsigned long long g = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)(g >> 32) == tag) return (uint32_t)g;
-        __builtin_amdgcn_s_sleep(BIN_SCAN_SLEEP);
-    }
-    *fail = 1u;
-    return 0u;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <class KeyT>
-__global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bin_fused(
-    const uint32_t* __restrict__ order, uint32_t R_host, const uint32_t* __restrict__ R_dev /* nullable */, const uint32_t* __restrict__ perm,
-    const uint2* __restrict__ prect, uint32_t* __restrict__ cidx, uint2* __restrict__ crect, uint32_t* __restrict__ coff,
-    uint32_t* __restrict__ digit_total, uint2* __restrict__ tile_ranges, uint32_t tiles, uint32_t list_shift, uint32_t splat_count,
-    const uint8_t* __restrict__ block_any, uint32_t* __restrict__ deep_flags, uint32_t blend_bins,
-    // (k_bin_emit's)
-    RenderFrame* __restrict__ frame, uint32_t capacity, uint32_t tiles_x /* list bins per row */, uint32_t row_begin /* first list-bin row */,
-    KeyT* __restrict__ keys_out, uint32_t* __restrict__ vals_out, volatile uint32_t* __restrict__ mirror, uint32_t serial,
-    const uint2* prev_blend_stats, uint32_t* __restrict__ blend_order, uint32_t deep, uint32_t* blend_stats_w,
-    uint32_t deep_min, uint32_t deep_factor, BinScan scan, StatShift sh, uint32_t lds_bitmap) {
-    __shared__ unsigned long long s_w[4];
-    __shared__ uint32_t s_any[ANY_WORDS];
-    __shared__ uint32_t s_base;
-    // (+ one workgroup, the first to be dispatched, for the blend's schedule and the deep pass's members: k_bin_emit's)
-    const uint32_t first_wg = blend_order ? 1u : 0u;
-    if (blend_order && blockIdx.x == 0) {
-        blend_schedule_job(prev_blend_stats, blend_bins, blend_order, deep, deep_flags, blend_stats_w, deep_min, deep_factor, mirror, sh);
-        return;
-    }
-    const uint32_t wg = blockIdx.x - first_wg, G = gridDim.x - first_wg;
-    const uint32_t blocks = (splat_count + 255u) >> 8;
-    const bool coarse = block_any != nullptr && blocks <= ANY_WORDS * 32u && lds_bitmap != 0u;
-    if (coarse) {                                                          // (k_bin_count's LDS bitmap of live storage blocks)
-        for (uint32_t w = threadIdx.x; w < (blocks + 31u) / 32u; w += BIN_THREADS) {
-            const uint4* src = reinterpret_cast<const uint4*>(block_any + 32u * w);
-            const uint4 a = src[0], b = src[1];
-            const uint32_t v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                bits |= (((v[k] & 0xFFu) ? 1u : 0u) | ((v[k] & 0xFF00u) ? 2u : 0u) | ((v[k] & 0xFF0000u) ? 4u : 0u) |
-                         ((v[k] & 0xFF000000u) ? 8u : 0u)) << (4 * k);
-            s_any[w] = bits;
-        }
-        __syncthreads();
-    }
-    {   // the draw's housekeeping (k_bin_count's)
-        const uint32_t t = wg * BIN_THREADS + threadIdx.x, stride = G * BIN_THREADS;
-        for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) digit_total[w] = 0u;
-        for (uint32_t w = t; w < tiles; w += stride) tile_ranges[w] = make_uint2(0xFFFFFFFFu, 0u);
-        if (!first_wg) {                                                   // (a schedule workgroup resets - and then fills - these itself)
-            if (t < GS_FLAG_LIST) deep_flags[t] = 0u;
-            for (uint32_t w = t; w < blend_bins; w += stride) deep_flags[GS_FLAG_OF + w] = GS_DEEP_NONE;
-        }
-    }
-    const uint32_t R = R_dev ? min(*R_dev, R_host) : R_host;
-    const uint32_t batches = (R + BIN_THREADS - 1) / BIN_THREADS, per = (batches + G - 1) / G;
-    const uint32_t c = xcd_chunk(wg, G);
-    const uint32_t b0 = min(c * per, batches), b1 = min(b0 + per, batches);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t pos_begin = b0 * BIN_THREADS, pos_end = min(b1 * BIN_THREADS, R);
-    const SliceCount sc = bin_count_slice(order, R, perm, prect, cidx, crect, coff, list_shift, splat_count, block_any, coarse, s_any, s_w, pos_begin, pos_end);
-    uint32_t t16 = sc.t16;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t16 += __shfl_xor(t16, o, 64);
-    if (lane == 0) s_w[wave] = t16;
-    __syncthreads();
-    if (wave == 0u) {
-        const uint32_t E = sc.entries, V = sc.splats, T = (uint32_t)(s_w[0] + s_w[1] + s_w[2] + s_w[3]);
-        if (lane < 3u) bin_scan_put(scan.chunk_rows + (size_t)lane * BIN_MAX_BLOCKS + c, lane == 0u ? E : lane == 1u ? V : T, scan.tag);
-        const uint32_t g = c / BIN_SCAN_GROUP, j = c % BIN_SCAN_GROUP;
-        const bool closer = j == BIN_SCAN_GROUP - 1u || c == G - 1u;
-        // entries in front of this slice: the slices of its group before it + the groups before its group
-        const unsigned long long in_e = wave_sum64(lane < j ? bin_scan_poll(scan.chunk_rows + g * BIN_SCAN_GROUP + lane, scan.tag, scan.fail) : 0u);
-        if (closer) {
-            const unsigned long long ge = in_e + E;
-            if (lane == 0u) bin_scan_put(scan.group_rows + g, ge > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ge, scan.tag);
-        }
-        const unsigned long long front = in_e + wave_sum64(lane < g ? bin_scan_poll(scan.group_rows + lane, scan.tag, scan.fail) : 0u);
-        if (lane == 0u) s_base = front > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)front;
-        if (closer) {                                                      // the group's statistics rows; the last slice: the frame's totals
-            const unsigned long long gv = V + wave_sum64(lane < j ? bin_scan_poll(scan.chunk_rows + BIN_MAX_BLOCKS + g * BIN_SCAN_GROUP + lane, scan.tag, scan.fail) : 0u);
-            const unsigned long long gt = T + wave_sum64(lane < j ? bin_scan_poll(scan.chunk_rows + 2u * BIN_MAX_BLOCKS + g * BIN_SCAN_GROUP + lane, scan.tag, scan.fail) : 0u);
-            if (c != G - 1u) {
-                if (lane == 0u) {
-                    bin_scan_put(scan.group_rows + BIN_SCAN_GROUPS + g, (uint32_t)gv, scan.tag);
-                    bin_scan_put(scan.group_rows + 2u * BIN_SCAN_GROUPS + g, gt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)gt, scan.tag);
-                }
-            } else {
-                const unsigned long long vis64 = gv + wave_sum64(lane < g ? bin_scan_poll(scan.group_rows + BIN_SCAN_GROUPS + lane, scan.tag, scan.fail) : 0u);
-                const unsigned long long tsum = gt + wave_sum64(lane < g ? bin_scan_poll(scan.group_rows + 2u * BIN_SCAN_GROUPS + lane, scan.tag, scan.fail) : 0u);
-                const unsigned long long D64 = front + E;
-                if (lane == 0u) {
-                    const uint32_t vis = (uint32_t)vis64;
-                    frame->tiles16_lo = (uint32_t)tsum;
-                    frame->tiles16_hi = (uint32_t)(tsum >> 32);
-                    frame->visible = vis;
-                    frame->entries_lo = (uint32_t)D64;
-                    frame->entries_hi = (uint32_t)(D64 >> 32);
-                    frame->overflow = D64 > capacity ? 1u : 0u;
-                    frame->entry_count = D64 > capacity ? capacity : (uint32_t)D64;
-                    frame->pad = 0;
-                    if (mirror) {                                           // (see k_bin_emit: two 16-byte stores to mapped host memory)
-                        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                        const u32x4 v = {serial, D64 > capacity ? 1u : 0u, (uint32_t)D64, (uint32_t)(D64 >> 32)};
-                        *reinterpret_cast<volatile u32x4*>(mirror) = v;
-                        const u32x4 sv = {serial, vis, (uint32_t)tsum, (uint32_t)(tsum >> 32)};
-                        *reinterpret_cast<volatile u32x4*>(mirror + 8) = sv;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();                                                        // s_base; this workgroup's compacted lists (written above)
-    const uint32_t base = s_base;
-    if (base >= capacity) return;
-    for (uint32_t jb = 0; jb < sc.splats; jb += BIN_THREADS)
-        (void)bin_emit_batch<KeyT>(cidx, crect, coff, pos_begin + jb + threadIdx.x, jb + threadIdx.x < sc.splats, base, capacity, tiles_x, row_begin,
-                                   list_shift, keys_out, vals_out);
-}
-
-template <class KeyT>
-static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R, uint32_t tiles /* sort keys */) {
+static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R, uint32_t tiles /* sort keys */) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream;
     const RadixExec ex = {st, &m->radix, ctx->lds_atomic_lane_order};
@@ -748,12 +585,11 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
     // deep pass: a bin qualifies when its previous draw walked >= deep_min (splat, quadrant) pairs and >= deep_factor x the mean bin
     // (4096 pairs.  C3S frame ms at 2048 / 3072 / 4096 / 6144 / 8192: 1.336 / 1.338 / 1.309 / 1.296 / 1.500 - k_deep_scan costs
     // 0.17 ms for 512 bins and is bound by its gathers, so: fewer, deeper bins; profiles/r03zz_kstats_C3S.txt)
-    static const uint32_t deep_min_cfg = getenv("GSPLAT_DEEP_MIN") ? (uint32_t)atoi(getenv("GSPLAT_DEEP_MIN")) : 4u * GS_CHUNK;
-    static const uint32_t deep_factor = getenv("GSPLAT_DEEP_FACTOR") ? (uint32_t)atoi(getenv("GSPLAT_DEEP_FACTOR")) : 3u;
+    const uint32_t deep_factor = sw.deep_factor;
     // (a GS_DRAW_ROP8 draw has no deep pass - rounding after every splat does not split into chunks - and must not raise its trigger)
-    const uint32_t deep_min = m->draw_mode == GS_DRAW_FP32 ? deep_min_cfg : 0x7FFFFFFFu;
+    const uint32_t deep_min = m->draw_mode == GS_DRAW_FP32 ? sw.deep_min : 0x7FFFFFFFu;
     const bool order_ok = blend_bins > 0 && blend_bins <= 8192u && m->blend_bins == blend_bins && m->blend_row_begin == pp.bin_row_begin &&
-                          m->blend_width == (uint32_t)pp.width && m->blend_stats_mode == m->draw_mode && !getenv("GSPLAT_NO_BLEND_ORDER");
+                          m->blend_width == (uint32_t)pp.width && m->blend_stats_mode == m->draw_mode && !sw.no_blend_order;
     // (the same draw mode: a GS_DRAW_ROP8 draw walks its lists to the saturation depth twice or to their ends - its per-bin counters
     // say nothing about what an fp32 draw costs, and the other way round)
     if (order_ok) GS_TRY(m->blend_order.ensure((size_t)blend_bins * 4));
@@ -782,7 +618,7 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
     //    ($GSPLAT_ORDER_MOTION; 0 = the same view only).  Turning in place has none, at any speed.
     StatShift stat_shift = {0, 0, pp.bins_x};
     if (same_frame && !same_view && pp.block_cull && m->centre_n > 0) {
-        const float limit = getenv("GSPLAT_ORDER_MOTION") ? (float)atof(getenv("GSPLAT_ORDER_MOTION")) : 0.045f;
+        const float limit = sw.order_motion;
         const double inv_n = 1.0 / (double)m->centre_n;
         const float c[3] = {(float)(m->centre_sum[0] * inv_n), (float)(m->centre_sum[1] * inv_n), (float)(m->centre_sum[2] * inv_n)};
         auto window = [&](const ProjectParams& q, const float* p, float* xy) {       // (column-major matrices, window y up: project.hip)
@@ -797,7 +633,7 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
         float was[2], is[2];
         if (window(lp, c, was) && window(pp, c, is)) {
             const float dx = (is[0] - was[0]) / (float)GS_BIN, dy = (is[1] - was[1]) / (float)GS_BIN;
-            const bool shift_ok = fabsf(dx) < 4096.0f && fabsf(dy) < 4096.0f && !getenv("GSPLAT_NO_STAT_SHIFT");   // (false for NaN)
+            const bool shift_ok = fabsf(dx) < 4096.0f && fabsf(dy) < 4096.0f && !sw.no_stat_shift;   // (false for NaN)
             if (shift_ok) {
                 stat_shift.sx = (int32_t)lrintf(dx);
                 stat_shift.sy = (int32_t)lrintf(dy);
@@ -825,7 +661,7 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
             same_view = seen && moved <= limit;            // (NaN compares false)
         }
     }
-    const bool stale_order = getenv("GSPLAT_BLEND_ORDER_STALE") != nullptr;   // (A/B: rounds 2-5 - order from whatever draw came before)
+    const bool stale_order = sw.blend_order_stale;   // (A/B: rounds 2-5 - order from whatever draw came before)
     // The deep pass runs when the last draw whose verdict has arrived (mapped host word, no synchronisation) left bins over the
     // threshold - the decision only moves work between executors, the pixels do not depend on it (tile_blend.hip)
     m->deep_pass = order_ok && m->draw_mode == GS_DRAW_FP32 && !m->no_deep && m->mirror_host && ((volatile uint32_t*)m->mirror_host)[4] > 0u;
@@ -835,58 +671,29 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
         GS_TRY(m->deep_partial.ensure((size_t)GS_DEEP_UNITS * 256 * sizeof(float4)));
         GS_TRY(m->deep_work.ensure((size_t)GS_DEEP_UNITS * 4));
     }
-    // $GSPLAT_BIN_FUSED=1: count + emit in one launch behind a scan across the running grid (k_bin_fused).  Built, bit-identical,
-    // and SLOWER than the two kernels on every configuration, so it is not the default: bin stage C3 0.0513 -> 0.0598-0.0642 ms,
-    // C2 0.037 -> 0.047, C3S 0.084 -> 0.100, C4 0.419 -> 0.425-0.431 (profiles/r06i_ab_fused.txt, r06j_ab_fused_sleep.txt; longer
-    // back-off between polls recovers 4 of the 12 us).  Every slice's emit has to wait for the slowest slice's count - the scan
-    // is a grid-wide barrier in disguise - so the launch is count + barrier + emit like the two kernels, minus one kernel boundary,
-    // plus two hops of polling under the count's own memory traffic, and the emit loses k_bin_emit's round-robin deal of batches.
-    const char* fused_env = getenv("GSPLAT_BIN_FUSED");
-    const bool fused = fused_env && fused_env[0] == '1';
     // (+ one workgroup that orders the blend's bins and names the deep pass's members)
     // (that workgroup also raises the deep pass's trigger, so under a camera that keeps moving it still runs when the pass is on,
     // for scenes of tiny splats - the ones that grow deep bins - and every 8th draw otherwise)
     const bool order_wg = order_ok && (same_view || stale_order || m->deep_pass || pp.list_shift == GS_LIST_SHIFT_SMALL || (m->draw_serial & 7u) == 7u);
     // (what the schedule job of this draw is given: gs_mesh_debug_read(what = 7))
-    m->sched = {order_wg ? 1u : 0u, blend_bins, stat_shift.sx, stat_shift.sy, m->deep_pass ? 1u : 0u, deep_min, deep_factor, fused ? 1u : 0u};
+    m->sched = {order_wg ? 1u : 0u, blend_bins, stat_shift.sx, stat_shift.sy, m->deep_pass ? 1u : 0u, deep_min, deep_factor};
     ++m->draw_serial;
-    if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the scan's granules are tagged with the serial: 0 is "never written")
-    if (fused) {
-        GS_TRY(m->bin_scan.ensure(((size_t)3 * BIN_MAX_BLOCKS + 3 * BIN_SCAN_GROUPS) * 8 + 64));
-        if (!m->bin_scan_ready) {                        // once: no granule carries a tag
-            GS_HIP(hipMemsetAsync(m->bin_scan.p, 0, m->bin_scan.bytes, st));
-            m->bin_scan_ready = true;
-        }
-        BinScan scan;
-        scan.chunk_rows = m->bin_scan.as<unsigned long long>();
-        scan.group_rows = scan.chunk_rows + 3 * BIN_MAX_BLOCKS;
-        scan.fail = reinterpret_cast<uint32_t*>(scan.group_rows + 3 * BIN_SCAN_GROUPS);
-        scan.tag = m->draw_serial;
-        hipLaunchKernelGGL((k_bin_fused<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
-                           m->translate ? m->perm.as<uint32_t>() : nullptr, m->prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(),
-                           m->coff.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(), m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
-                           m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, frame, cap, pp.lists_x, pp.list_row_begin,
-                           m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), m->mirror_dev, m->draw_serial,
-                           order_wg ? m->blend_stats.as<uint2>() : nullptr, order_wg ? m->blend_order.as<uint32_t>() : nullptr,
-                           m->deep_pass ? 1u : 0u, m->blend_stats.as<uint32_t>(), deep_min, deep_factor, scan, stat_shift,
-                           m->no_coarse_vis ? 0u : 1u);
-    } else {
-        hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
-                           m->translate ? m->perm.as<uint32_t>() : nullptr, m->prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
-                           m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
-                           m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
-                           m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
-        hipLaunchKernelGGL((k_bin_emit<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, frame, cap, m->cidx.as<uint32_t>(),
-                           m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
-                           m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,
-                           order_wg ? m->blend_stats.as<uint2>() : nullptr, blend_bins, order_wg ? m->blend_order.as<uint32_t>() : nullptr,
-                           m->deep_pass ? 1u : 0u, m->deep_flags.as<uint32_t>(), m->blend_stats.as<uint32_t>(), deep_min, deep_factor, stat_shift);
-    }
+    if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the mapped words carry the serial: 0 is "no draw yet", mesh_read_view_share)
+    hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
+                       m->translate ? m->perm.as<uint32_t>() : nullptr, m->prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
+                       m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
+                       m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
+                       m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
+    hipLaunchKernelGGL((k_bin_emit<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, frame, cap, m->cidx.as<uint32_t>(),
+                       m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
+                       m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,
+                       order_wg ? m->blend_stats.as<uint2>() : nullptr, blend_bins, order_wg ? m->blend_order.as<uint32_t>() : nullptr,
+                       m->deep_pass ? 1u : 0u, m->deep_flags.as<uint32_t>(), m->blend_stats.as<uint32_t>(), deep_min, deep_factor, stat_shift);
     // ... and whenever the deep pass runs: its frames have the long tail that an order - even one from a view several degrees away -
     // and the pass's workgroups behind the costliest bins (tile_blend.hip) shorten.  Capture-like C3S, orbit at 3 / 6 / 12 degrees per
     // frame: 1.24 / 1.356 / 1.54 -> 1.18 / 1.31 / 1.51 ms, turning 4 degrees per frame 2.84 -> 2.77, never slower
     // (profiles/r06zz_deep_keeps_order_ab.txt; $GSPLAT_DEEP_ROW_MAJOR_ON_MOTION=1 is the earlier rule).
-    m->blend_order_valid = order_ok && (same_view || stale_order || (m->deep_pass && !getenv("GSPLAT_DEEP_ROW_MAJOR_ON_MOTION")));
+    m->blend_order_valid = order_ok && (same_view || stale_order || (m->deep_pass && !sw.deep_row_major_on_motion));
     GS_HIP(hipGetLastError());
     if (pp.row_begin == 0u && pp.row_end >= pp.tiles_y) {     // (a strip's visible count says nothing about the scene: mesh_heal_overflow)
         m->full_serial[m->draw_serial & 7u] = m->draw_serial;
@@ -915,8 +722,8 @@ static int binning_typed(gs_mesh* m, const ProjectParams& pp, const uint32_t* or
     return GS_OK;
 }
 
-int gs_launch_binning(gs_mesh* m, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count) {
+int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count) {
     const uint32_t tiles = pp.lists_x * (pp.list_row_end - pp.list_row_begin);   // one list per sort key
-    if (tiles <= 65536u && !m->ctx->wide_entry_keys) return binning_typed<uint16_t>(m, pp, order_dev, sorter, render_count, tiles);
-    return binning_typed<uint32_t>(m, pp, order_dev, sorter, render_count, tiles);
+    if (tiles <= 65536u && !m->ctx->wide_entry_keys) return binning_typed<uint16_t>(m, sw, pp, order_dev, sorter, render_count, tiles);
+    return binning_typed<uint32_t>(m, sw, pp, order_dev, sorter, render_count, tiles);
 }

@@ -1208,7 +1208,7 @@ int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint
     return GS_OK;
 }
 
-int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev) {
+int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, uint8_t* out_dev) {
     const uint32_t bins = pp.bins_x * (pp.bin_row_end - pp.bin_row_begin);
     if (bins == 0) return GS_OK;
     GS_TRY(m->blend_stats.ensure((size_t)bins * 12));     // uint2 [bins] {scanned, halves} | uint32 [bins] pairs
@@ -1226,8 +1226,7 @@ int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev) {
     da.cnt = m->deep_cnt.as<uint32_t>();
     da.partial = m->deep_partial.as<float4>();
     da.pool = m->chunk_pool.as<float4>();
-    static const uint32_t pool_slots = getenv("GSPLAT_POOL_SLOTS") ? std::min<uint32_t>((uint32_t)atoi(getenv("GSPLAT_POOL_SLOTS")), GS_POOL_SLOTS) : GS_POOL_SLOTS;
-    da.pool_slots = pool_slots;
+    da.pool_slots = sw.pool_slots;
     da.work = m->deep_work.as<uint32_t>();
     // (as many workgroups as the device holds at BLEND_OCC per CU: their waves loop over the unit list)
     da.unit_wgs = m->deep_pass ? (uint32_t)m->ctx->cu_count * BLEND_OCC : 0u;
@@ -1241,20 +1240,20 @@ int gs_launch_blend(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev) {
     //  * bins in row-major order (the camera moved on: no order): units are the fine-grained work that fills the end of the launch -
     //    in the middle they cost 13 % (moving camera 1.35 -> 1.52 ms) - so they stay last, all of them.
     da.unit_at = bins;
-    if (m->deep_pass && m->blend_order_valid && !getenv("GSPLAT_DEEP_UNITS_LAST")) {
+    if (m->deep_pass && m->blend_order_valid && !sw.deep_units_last) {
         const uint32_t cus = (uint32_t)m->ctx->cu_count;
         const uint32_t deep_hint = m->mirror_host ? ((volatile uint32_t*)m->mirror_host)[4] : 0u;      // bins the last verdict put in the pass
         // two per CU - or, when the pass's bins were most of the previous draw's walk, 0.6 of their share of the resident workgroups
         // (C3S: share 0.55, best at a third of the workgroups whatever AT is: 256 / 512 / 768 / 1536 -> 1.30 / 1.125 / 1.15 / 1.20 ms;
         // with exactly the share, 1.17)
         const float share = (float)std::min(m->mirror_host ? ((volatile uint32_t*)m->mirror_host)[5] : 0u, 1024u) * (1.0f / 1024.0f);
-        const float k = getenv("GSPLAT_DEEP_SHARE_K") ? (float)atof(getenv("GSPLAT_DEEP_SHARE_K")) : 0.6f;
+        const float k = sw.deep_share_k;
         da.unit_wgs = std::min(da.unit_wgs, std::max(2u * cus, (uint32_t)(k * share * (float)da.unit_wgs + 0.5f)));
         da.unit_at = std::min(bins, std::min(deep_hint, (uint32_t)GS_DEEP_MAX_BINS) + cus + cus / 2u);
     }
-    if (getenv("GSPLAT_DEEP_UNIT_AT") && m->deep_pass) da.unit_at = (uint32_t)atoi(getenv("GSPLAT_DEEP_UNIT_AT"));
-    if (getenv("GSPLAT_DEEP_UNIT_WGS") && m->deep_pass)
-        da.unit_wgs = std::max(1u, std::min<uint32_t>((uint32_t)atoi(getenv("GSPLAT_DEEP_UNIT_WGS")), (uint32_t)m->ctx->cu_count * BLEND_OCC));
+    if (sw.deep_unit_at_set && m->deep_pass) da.unit_at = sw.deep_unit_at;
+    if (sw.deep_unit_wgs_set && m->deep_pass)
+        da.unit_wgs = std::max(1u, std::min<uint32_t>(sw.deep_unit_wgs, (uint32_t)m->ctx->cu_count * BLEND_OCC));
     if (m->draw_mode != GS_DRAW_FP32) {                    // the reference's RGBA8 target, splat by splat (no deep pass: nothing to schedule)
         static void (*const rop8[2][2])(FrameArgs, uint32_t) = {                // [DEPTH][BOUNDED]
             {k_tile_blend_rop8<false, false>, k_tile_blend_rop8<false, true>}, {k_tile_blend_rop8<true, false>, k_tile_blend_rop8<true, true>}};

@@ -1,4 +1,4 @@
-"""Host model of the binner's entry lists (gaussiansplats3d_amd/csrc/tile_bin.hip: k_bin_count, k_bin_emit / k_bin_fused and the
+"""Host model of the binner's entry lists (gaussiansplats3d_amd/csrc/tile_bin.hip: k_bin_count, k_bin_emit and the
 entry sort): plain numpy integers, none of the kernels' slices, batches, offsets or radix passes.
 
 The contract it states:

@@ -85,7 +85,7 @@ class Rig:
         assert not bad, f"shift ({got['sx']}, {got['sy']}): {bad}"
         want = ref.head_outcome(sch, order)
         info = self.mesh.deep_pass_info()
-        tag = (f"{cam.width}x{cam.height} shift ({got['sx']}, {got['sy']}) deep={got['deep']} fused={got['fused']}: "
+        tag = (f"{cam.width}x{cam.height} shift ({got['sx']}, {got['sy']}) deep={got['deep']}: "
                f"total {sch.total}, thr {sch.thr}, trigger {sch.trigger}, {len(want['members'])} members")
         if got["deep"]:
             have = set(int(b) for b in info["bins"])
@@ -153,19 +153,6 @@ def test_schedule_without_the_deep_pass(ctx, c3s):
     rig.draw(rig.cam0)
     got = _still(rig)
     assert not got["deep"] and got["candidates"] > 0        # the trigger is still raised, nobody is named
-    rig.close()
-
-
-def test_schedule_of_the_fused_binner(ctx, monkeypatch):
-    rig = Rig(ctx, _pile(60000, 41), 640, 480)
-    monkeypatch.setenv("GSPLAT_BIN_FUSED", "1")             # (read at every draw)
-    rig.draw(rig.cam0)
-    got = _still(rig)
-    assert got["fused"] and got["deep"]
-    _turning(rig, need_deep=False)
-    monkeypatch.delenv("GSPLAT_BIN_FUSED")
-    rig.draw_and_check(rig.cam0)
-    assert not rig.mesh.blend_schedule()["fused"]
     rig.close()
 
 

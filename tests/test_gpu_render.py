@@ -830,10 +830,10 @@ def test_asynchronous_draws_learn_how_much_of_the_scene_is_in_view(ctx):
         ref_mesh.dispose(); mesh.dispose()
 
 
-def test_fused_binner_draws_the_same_frame_and_statistics(ctx, monkeypatch):
-    """$GSPLAT_BIN_FUSED=1 (k_bin_fused: count + emit in one launch behind a scan across the running grid; built in round 6,
-    slower than the two kernels, kept as an A/B switch) must produce the same entries: same frame, same counters - also when the
-    entry buffer overflows, for a strip, and for a list whose length lives on the device (a visibility-culled sort)."""
+def test_repeated_draws_give_the_same_frame_and_statistics(ctx):
+    """The binner (k_bin_count + k_bin_emit) leaves no state behind that changes the next draw's entries: the same frames and the same
+    counters the second time round - for a full frame, for a strip, and for a list whose length lives on the device (a
+    visibility-culled sort) - and also after a draw whose entry buffer overflowed."""
     scene = helpers.small_scene(150000, 1, seed=77)
     cam = camera.demo_camera("garden", 640, 360)
     n = scene.count
@@ -862,13 +862,11 @@ def test_fused_binner_draws_the_same_frame_and_statistics(ctx, monkeypatch):
         return out
 
     plain = frames()
-    monkeypatch.setenv("GSPLAT_BIN_FUSED", "1")
-    fused = frames()
+    again = frames()
     mesh.debug_set_entry_capacity(4096)                 # an overflowing draw is redone with a grown buffer
     w.sort_on_device(mvp, n)
     img, st = mesh.render()
-    monkeypatch.delenv("GSPLAT_BIN_FUSED")
-    for (a, *sa), (b, *sb) in zip(plain, fused):
+    for (a, *sa), (b, *sb) in zip(plain, again):
         np.testing.assert_array_equal(a, b)
         assert sa == sb
     np.testing.assert_array_equal(img, plain[0][0])

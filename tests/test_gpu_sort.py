@@ -130,10 +130,10 @@ def test_ballot_ranking_fallback_is_bit_exact(monkeypatch):
     c.close()
 
 
-def test_keys_and_pass_0_histogram_in_one_launch_is_bit_exact(monkeypatch):
-    """$GSPLAT_KEY_HIST_FUSED=1 (built as an opt-in): k_depth_key_hist keys the splats, meets its whole grid on one
-    counter for the exact min / max and histograms pass 0 from registers.  Same list as the two kernels at sizes that give one
-    chunk, several, ragged last tiles; sizes it does not take (not a multiple of 4) and partial sorts fall back silently."""
+def test_full_and_partial_sorts_match_the_oracle_across_chunk_shapes():
+    """The plain sort of the identity list (k_depth_key, then pass 0's histogram and the chunk-staged scatter) at sizes that give one
+    chunk, several, ragged last tiles and a count that is no multiple of 4: the full sort and a partial one (n // 2) are the
+    oracle's lists."""
     c = Context(0)
     rng = np.random.default_rng(99)
     cam = camera.demo_camera("garden", 640, 360)
@@ -147,13 +147,11 @@ def test_keys_and_pass_0_histogram_in_one_launch_is_bit_exact(monkeypatch):
             return w.post_message({"sort": {"modelViewProj": cam.sort_mvp(), "splatRenderCount": n, "splatSortCount": count,
                                             "usePrecomputedDistances": False, "indexesToSort": None, "transforms": None,
                                             "precomputedDistances": None}})["sortedIndexes"].copy()
-        monkeypatch.setenv("GSPLAT_KEY_HIST_FUSED", "1")
-        full = sort(n)
-        np.testing.assert_array_equal(full, oracle.sort_indexes(np.arange(n, dtype=np.uint32), ci, cam.sort_mvp()), err_msg=f"n {n}")
+        identity = np.arange(n, dtype=np.uint32)
+        np.testing.assert_array_equal(sort(n), oracle.sort_indexes(identity, ci, cam.sort_mvp()), err_msg=f"n {n}")
         assert w.last_stats()[0].result_count == n
-        part = sort(max(n // 2, 1))
-        monkeypatch.delenv("GSPLAT_KEY_HIST_FUSED")
-        np.testing.assert_array_equal(sort(n), full)
-        np.testing.assert_array_equal(sort(max(n // 2, 1)), part)
+        half = max(n // 2, 1)
+        np.testing.assert_array_equal(sort(half), oracle.sort_indexes(identity, ci, cam.sort_mvp(), sort_count=half, render_count=n),
+                                      err_msg=f"n {n}, sort count {half}")
         w.terminate()
     c.close()
