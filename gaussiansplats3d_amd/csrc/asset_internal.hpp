@@ -1,6 +1,7 @@
-// asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share: the parsed
-// .ksplat image, the two half-float rules, and the per-row arithmetic of the formats whose file rows are decoded on both
-// sides (.splat, PlayCanvas compressed PLY, .spz), each said once for both sides.
+// asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share, each said once as
+// __host__ __device__ code for both sides: the two half-float rules, the scene transform, the per-row arithmetic of the formats
+// whose file rows are decoded on both sides (.splat, PlayCanvas compressed PLY, .spz), the .ksplat row reader (KsplatSource)
+// and the per-splat fill (asset_fill_splat) that gs_asset_fill loops over and k_asset_decode runs one thread of.
 #pragma once
 #include <math.h>
 
@@ -94,9 +95,10 @@ __host__ __device__ inline double sh_widen(uint32_t level, const uint8_t* p, uin
 
 // fillSphericalHarmonicsArray with a transform (SplatBuffer.js:678-729): widen, rotateSphericalHarmonics3 / 5 (dot3 / dot5:
 // the accumulator starts at 0, the terms are added in order), convert FROM LEVEL 0 to the output level.  wide(src): the
-// widened value of the splat's SH with file index src; out(dst, v) stores component dst of the splat.
+// widened value of the splat's SH with file index src; out(dst, v) stores component dst of the splat.  Inlined into its one
+// caller, asset_fill_splat: out of line, the closures' captures would live in memory.
 template <class In, class Out>
-__host__ __device__ inline void xf_sh(const AssetTransform& t, uint32_t degree, In wide, Out out) {
+__host__ __device__ __forceinline__ void xf_sh(const AssetTransform& t, uint32_t degree, In wide, Out out) {
 #pragma clang fp contract(off)
     for (uint32_t ch = 0; ch < 3; ch++) {                                              // set3FromArray(stride 3, base c)
         double in[3];
@@ -354,21 +356,221 @@ __host__ __device__ inline float spz_sh_value(uint32_t byte) {                  
     return (float)(((double)byte - 128.0) / 128.0);
 }
 
-struct AssetSection {
-    uint32_t splat_count, max_splat_count, bucket_size, bucket_count, full_buckets, partial_buckets, sh_degree;
-    uint32_t bytes_per_splat, scale_range;
-    double half_block, scale_factor;
-    size_t base, buckets_base, data_base;
-    uint32_t count_offset;
-    uint32_t bucket_storage;
-    std::vector<uint32_t> partial_end;     // cumulative end (in section-local splats) of every partial bucket
+// ---- .ksplat rows: one reader for the host fill and the kernels ------------------------------------------------------------------
+// Restates, never copies: SplatBuffer.js:108-163 (rows per compression level), :199-219 (bucket of a splat), :221-246 (centre).
+// Bytes of a row's parts per compression level, in row order: centre, scale, rotation, RGBA (4), SH
+__host__ __device__ inline uint32_t asset_center_bytes(uint32_t level) { return level == 0 ? 12u : 6u; }
+__host__ __device__ inline uint32_t asset_scale_bytes(uint32_t level) { return level == 0 ? 12u : 6u; }
+__host__ __device__ inline uint32_t asset_rotation_bytes(uint32_t level) { return level == 0 ? 16u : 8u; }
+__host__ __device__ inline uint32_t asset_sh_value_bytes(uint32_t level) { return level == 0 ? 4u : (level == 1 ? 2u : 1u); }
+__host__ __device__ inline uint32_t sh_components(uint32_t degree) { return degree == 0 ? 0u : (degree == 1 ? 9u : 24u); }
+
+// What a row read needs of one section.  parse_ksplat (assets.hip) fills it with offsets into the file image and proves every
+// read through it in range; asset_stage (asset_decode.hip) copies the records of a range and rebases the offsets.
+struct KsplatSection {
+    long long data_off;        // byte offset of the section's row 0 in the image (negative in a staged range that starts inside the
+                               // section: rows before the range are not uploaded)
+    long long buckets_off;     // ... of its bucket centres
+    uint32_t count_offset, count;            // its first splat, its splats (maxSplatCount: secLoadedCountsToMax)
+    uint32_t bytes_per_splat, bucket_size, full_buckets, bucket_count, bucket_storage, scale_range;
+    uint32_t partial_begin, partial_count;   // its slice of the image's cumulative partial_end list
+    double scale_factor;
 };
 
-constexpr uint32_t ASSET_CENTER_BYTES[3] = {12, 6, 6}, ASSET_SCALE_BYTES[3] = {12, 6, 6}, ASSET_ROT_BYTES[3] = {16, 8, 8},
-                   ASSET_SH_BYTES_PER[3] = {4, 2, 1};
-__host__ __device__ inline uint32_t asset_center_bytes(uint32_t level) { return level == 0 ? 12u : 6u; }     // = scale bytes
-__host__ __device__ inline uint32_t asset_rotation_bytes(uint32_t level) { return level == 0 ? 16u : 8u; }
-__host__ __device__ inline uint32_t sh_components(uint32_t degree) { return degree == 0 ? 0u : (degree == 1 ? 9u : 24u); }
+struct KsplatView {            // an image: the host's file, or what a kernel argument says of the staged range
+    const uint8_t* image;
+    const KsplatSection* sections;           // the non-empty sections in order
+    const uint32_t* partial_end;             // cumulative end (in section-local splats) of every partial bucket
+    uint32_t section_count, level, sh_degree, ncomp;
+};
+
+template <class T>
+__host__ __device__ __forceinline__ T ld(const uint8_t* p) {   // rows have no alignment (33 bytes per splat at level 2, SH 1)
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+
+// dataViewFloatForCompressionLevel for scale / rotation (never the 8-bit SH rule: that is sh_widen)
+__host__ __device__ __forceinline__ double comp(uint32_t level, const uint8_t* row, uint32_t index) {
+    if (level == 0) return (double)ld<float>(row + 4 * index);
+    return from_half(ld<uint16_t>(row + 2 * index));
+}
+
+// the section of splat i: the last one that begins at or before it
+__host__ __device__ __forceinline__ const KsplatSection& section_of(const KsplatView& v, uint32_t i) {
+    uint32_t lo = 0, hi = v.section_count;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (v.sections[mid].count_offset <= i) lo = mid;
+        else hi = mid;
+    }
+    return v.sections[lo];
+}
+
+// SplatBuffer.js:199-219: full buckets first, then the partial ones by their stored lengths.  parse_ksplat proved that the
+// tables cover every splat, so the result is always < bucket_count; the clamp is never taken.
+__host__ __device__ __forceinline__ uint32_t bucket_index(const KsplatView& v, const KsplatSection& sec, uint32_t local) {
+    const uint32_t full_span = sec.full_buckets * sec.bucket_size;
+    if (local < full_span) return local / sec.bucket_size;
+    const uint32_t* pe = v.partial_end + sec.partial_begin;
+    uint32_t lo = 0, hi = sec.partial_count;                    // first partial bucket whose end is > local
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pe[mid] <= local) lo = mid + 1;
+        else hi = mid;
+    }
+    const uint32_t b = sec.full_buckets + lo;
+    return b < sec.bucket_count ? b : sec.bucket_count - 1u;    // never past the table
+}
+
+// getSplatCenter (SplatBuffer.js:221-246) in double
+__host__ __device__ __forceinline__ void ksplat_centre(const KsplatView& v, const KsplatSection& sec, uint32_t local, const uint8_t* row,
+                                                       double d[3]) {
+    if (v.level == 0) {
+        for (int k = 0; k < 3; k++) d[k] = ld<float>(row + 4 * k);
+    } else {
+        const uint8_t* bucket = v.image + sec.buckets_off + (size_t)sec.bucket_storage * bucket_index(v, sec, local);
+        for (int k = 0; k < 3; k++) {
+            const double x = ld<uint16_t>(row + 2 * k);
+            const double bc = ld<float>(bucket + 4 * k);
+            d[k] = (x - (double)sec.scale_range) * sec.scale_factor + bc;
+        }
+    }
+}
+
+// ---- row sources -----------------------------------------------------------------------------------------------------------------
+// A source says where splat i's values come from.  Its Row gives: the double centre, the doubles of scale and rotation
+// (w, x, y, z) as the fills read them, the colour bytes, and the SH of file index `src` in each of the three forms the store needs
+// (widened double for the rotated fill, half bits, the level-2 byte).  This one reads a .ksplat image on either side; the
+// kernels' sources over file rows of the other formats are in asset_decode.hip.
+struct KsplatSource : KsplatView {
+    struct Row {
+        const KsplatView& v;
+        const KsplatSection& sec;
+        uint32_t local;
+        const uint8_t* row;
+        __host__ __device__ __forceinline__ const uint8_t* srow() const { return row + asset_center_bytes(v.level); }
+        __host__ __device__ __forceinline__ const uint8_t* crow() const { return srow() + asset_scale_bytes(v.level) + asset_rotation_bytes(v.level); }
+        __host__ __device__ __forceinline__ void centre(double d[3]) const { ksplat_centre(v, sec, local, row, d); }
+        __host__ __device__ __forceinline__ void scale_rotation(double s[3], double q[4]) const {
+            for (int k = 0; k < 3; k++) s[k] = comp(v.level, srow(), k);
+            for (int k = 0; k < 4; k++) q[k] = comp(v.level, srow(), 3 + k);
+        }
+        __host__ __device__ __forceinline__ uint32_t colour() const { return ld<uint32_t>(crow()); }
+        __host__ __device__ __forceinline__ double sh_wide(uint32_t src, double lo, double hi) const { return sh_widen(v.level, crow() + 4, src, lo, hi); }
+        __host__ __device__ __forceinline__ uint16_t sh_half(uint32_t src) const {      // level 0 through the half rule, level 1 bits
+            return v.level == 0 ? to_half_three((double)ld<float>(crow() + 4 + 4 * src)) : ld<uint16_t>(crow() + 4 + 2 * src);
+        }
+        __host__ __device__ __forceinline__ uint8_t sh_byte(uint32_t src) const { return crow()[4 + src]; }
+    };
+    __host__ __device__ __forceinline__ Row row(uint32_t splat) const {
+        const KsplatSection& sec = section_of(*this, splat);
+        const uint32_t local = splat - sec.count_offset;
+        return Row{*this, sec, local, image + sec.data_off + (long long)sec.bytes_per_splat * local};
+    }
+    __host__ __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const { row(splat).centre(d); }
+};
+
+// ---- the per-splat fill: gs_asset_fill's loop body and k_asset_decode's thread -----------------------------------------------------
+// Restates, never copies: covariance SplatBuffer.js:440-486, 517-549 (three.js Matrix3/4 arithmetic in double); colour :551-575;
+// SH order :577-734; with a transform :340-342, 461-466, 684-688, 707-715, 736-770.  fp64 and unfused on both sides (the
+// pragma here, -ffp-contract=off on both translation units): only multiplies, adds and double -> float conversions, so what
+// gs_mesh_upload_asset leaves is bit-equal to gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8).
+// the double centre through the scene transform (SplatBuffer.js:332-342) or narrowed to float as fillSplatCenterArray stores it
+template <bool XF>
+__host__ __device__ __forceinline__ void store_centre(const AssetTransform& t, const double d[3], float c[3]) {
+    if constexpr (XF) xf_centre(t, d, c);
+    else for (int k = 0; k < 3; k++) c[k] = (float)d[k];
+}
+
+// splat `row` -> element i of the outputs.  XF: with the transform t (never read otherwise); sh_lo / sh_hi: the file's 8-bit SH range
+// (read with XF only); ncomp = sh_components(sh_degree) of the OUTPUT degree.
+// A kernel (HOST false) writes every plane of the staging layout (MeshStaging), one covariance width and one SH form: whichever
+// pointer of each pair is set; scales / rotations are never looked at.  The host fill (HOST true) may leave any output out, may
+// ask for both covariance widths, and has scales / rotations on top.  HOST settles that at compile time: the kernels carry none
+// of the host's checks.  Rgba: uint32_t on the device (one aligned word), uint8_t on the host (the C ABI asks for no alignment).
+template <bool XF, bool HOST, class Row, class Rgba>
+__host__ __device__ __forceinline__ void asset_fill_splat(const Row row, const AssetTransform& t, uint32_t sh_degree, uint32_t ncomp,
+                                                          double sh_lo, double sh_hi, uint32_t min_alpha, uint32_t i, float* centers,
+                                                          float* cov_f32, uint16_t* cov_f16, Rgba* rgba, uint16_t* sh_f16, uint8_t* sh_u8,
+                                                          float* scales, float* rotations) {
+#pragma clang fp contract(off)
+    if (!HOST || centers) {
+        double d[3];
+        float c[3];
+        row.centre(d);
+        store_centre<XF>(t, d, c);
+        for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = c[k];
+    }
+    if (!HOST || cov_f32 || cov_f16 || scales || rotations) {
+        double s3[3], q4[4];
+        row.scale_rotation(s3, q4);
+        const double sx = s3[0], sy = s3[1], sz = s3[2];
+        // rotation.set(x = f4, y = f5, z = f6, w = f3): NOT normalised (SplatBuffer.js:539-542)
+        const double w = q4[0], x = q4[1], y = q4[2], z = q4[3];
+        if constexpr (HOST) {
+            if (scales) for (int k = 0; k < 3; k++) scales[3 * (size_t)i + k] = (float)s3[k];
+            if (rotations) {   // fillSplatScaleRotationArray (SplatBuffer.js:407-424): Quaternion.normalize, then ensurePositiveW
+                double q[4] = {x, y, z, w};
+                row_normalize(q);
+                const double flip = q[3] < 0 ? -1 : 1;
+                for (int k = 0; k < 4; k++) rotations[4 * (size_t)i + k] = (float)(q[k] * flip);
+            }
+        }
+        if (!HOST || cov_f32 || cov_f16) {
+            // Matrix4.makeRotationFromQuaternion = compose(zero, q, one) (three r160)
+            const double x2 = x + x, y2 = y + y, z2 = z + z;
+            const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
+            const double wx = w * x2, wy = w * y2, wz = w * z2;
+            const double R[3][3] = {{(1 - (yy + zz)) * 1, (xy - wz) * 1, (xz + wy) * 1},
+                                    {(xy + wz) * 1, (1 - (xx + zz)) * 1, (yz - wx) * 1},
+                                    {(xz - wy) * 1, (yz + wx) * 1, (1 - (xx + yy)) * 1}};
+            // covarianceMatrix = R * S (Matrix3.multiplyMatrices: a_i1*b_1j + a_i2*b_2j + a_i3*b_3j)
+            const double S[3][3] = {{sx, 0, 0}, {0, sy, 0}, {0, 0, sz}};
+            double M[3][3], Cm[3][3];
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int q = 0; q < 3; q++) M[r][q] = R[r][0] * S[0][q] + R[r][1] * S[1][q] + R[r][2] * S[2][q];
+            // transformedCovariance = M * M^T
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int q = 0; q < 3; q++) Cm[r][q] = M[r][0] * M[q][0] + M[r][1] * M[q][1] + M[r][2] * M[q][2];
+            double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
+            if constexpr (XF) xf_covariance(t, Cm, e);                                     // T3 * C * T3^T (SplatBuffer.js:461-466)
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                if (cov_f32) cov_f32[6 * (size_t)i + k] = XF ? xf_f32(e[k]) : (float)e[k];
+                if (HOST ? cov_f16 != nullptr : !cov_f32) cov_f16[6 * (size_t)i + k] = XF ? xf_f16(e[k]) : to_half_three(e[k]);
+            }
+        }
+    }
+    if (!HOST || rgba) {   // fillSplatColorArray (SplatBuffer.js:551-575)
+        const uint32_t word = row.colour(), alpha = word >> 24;
+        const uint32_t out = (word & 0x00FFFFFFu) | ((alpha >= min_alpha ? alpha : 0u) << 24);
+        __builtin_memcpy(rgba + sizeof(out) / sizeof(Rgba) * (size_t)i, &out, sizeof(out));   // the bytes R, G, B, A
+    }
+    const bool sh = ncomp && (!HOST || sh_f16 || sh_u8);
+    if constexpr (XF) {   // fillSphericalHarmonicsArray with a transform: widened, rotated, converted from level 0
+        if (sh)
+            xf_sh(t, sh_degree, [&](uint32_t src) { return row.sh_wide(src, sh_lo, sh_hi); }, [&](uint32_t dst, double val) {
+                if (sh_u8) sh_u8[(size_t)ncomp * i + dst] = to_uint8_range(val, sh_lo, sh_hi);
+                else sh_f16[(size_t)ncomp * i + dst] = xf_f16(val);
+            });
+    } else if (sh) {   // ... without one: level 0 through the half rule, level 1 bits, level 2 bytes
+        auto emit = [&](uint32_t dst, uint32_t src) {
+            if (sh_u8) sh_u8[(size_t)ncomp * i + dst] = row.sh_byte(src);
+            else sh_f16[(size_t)ncomp * i + dst] = row.sh_half(src);
+        };
+        for (uint32_t q = 0; q < 3; q++)                                                   // set3FromArray(stride 3, base c)
+            for (uint32_t ch = 0; ch < 3; ch++) emit(3 * q + ch, q + 3 * ch);
+        if (sh_degree >= 2)
+            for (uint32_t q = 0; q < 5; q++)                                               // set3FromArray(stride 5, base 9 + c)
+                for (uint32_t ch = 0; ch < 3; ch++) emit(9 + 3 * q + ch, 9 + q + 5 * ch);
+    }
+}
 
 enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3 };
 
@@ -384,8 +586,8 @@ struct gs_asset {
     uint32_t level = 0, splat_count = 0, sh_degree = 0;
     float scene_center[3] = {0, 0, 0};
     double sh_min = -1.5, sh_max = 1.5;
-    std::vector<AssetSection> sections;
-    std::vector<uint32_t> section_of;      // per splat
+    std::vector<KsplatSection> sections;   // of `buf`: the non-empty ones, offsets from buf's byte 0
+    std::vector<uint32_t> partial_end;     // ... and the partial bucket ends of all of them
     bool has_transform = false;            // gs_asset_set_transform
     AssetTransform xf = {};
 
@@ -393,6 +595,17 @@ struct gs_asset {
     T rd(size_t off) const {
         T v;
         memcpy(&v, buf.data() + off, sizeof(T));
+        return v;
+    }
+    KsplatSource image() const {           // `buf` as a row source, at the asset's output SH degree
+        KsplatSource v;
+        v.image = buf.data();
+        v.sections = sections.data();
+        v.partial_end = partial_end.data();
+        v.section_count = (uint32_t)sections.size();
+        v.level = level;
+        v.sh_degree = sh_degree;
+        v.ncomp = sh_components(sh_degree);
         return v;
     }
 };

@@ -1,4 +1,5 @@
-// assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device): INRIA-v1 .ply,
+// assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device, through the
+// same .ksplat row reader and per-splat fill body: asset_internal.hpp says both once for the two sides): INRIA-v1 .ply,
 // PlayCanvas compressed .ply, .splat, .spz and .ksplat -> the arrays the render / sort seams consume.  Restates, never copies:
 //   .spz              src/loaders/spz/SpzLoader.js:255-342 (container; the gzip reader and every refusal are in spz_container.hpp),
 //                     :366-388 with optimizeSplatData false (file order); the row arithmetic (:160-250, 84-145 + SplatBuffer.js
@@ -10,15 +11,14 @@
 //                     progressive, FILE-ORDER path - every splat is kept, alpha is only zeroed at fill time by min_alpha.  The
 //                     `optimizeSplatData: false` array path (SplatLoader.js:12-22) drops splats below minimumAlpha and reorders
 //                     them bucket by bucket; that is not what "file order" means here and is not restated.
-//   PLY header        /root/reference/src/loaders/ply/PlyParserUtils.js:31-165 (decodeSectionHeader, SH field mapping),
+//   PLY header        src/loaders/ply/PlyParserUtils.js:31-165 (decodeSectionHeader, SH field mapping),
 //                     INRIAV1PlyParser.js:20-47 (fields read)
 //   PLY row -> splat  INRIAV1PlyParser.js:114-209 (exp scale, sigmoid opacity, floor/clamp colours, quaternion normalise)
 //                     + SplatBuffer.writeSplatDataToSectionBuffer :1056-1113 (level-0 row: second normalise, fp32 stores)
-//   .ksplat layout    SplatBuffer.js:108-163 (rows per compression level), :819-848 (header), :877-941 (section headers),
-//                     :199-219 (bucket of a splat), :221-246 (centre decode)
-//   arrays            SplatBuffer.fillSplatCenterArray / fillSplatColorArray :551-575 / fillSplatCovarianceArray :517-549 +
-//                     computeCovariance :440-486 (three.js Matrix3/4 arithmetic in double) / fillSphericalHarmonicsArray
-//                     :577-734, SH target level = max(1, buffer level) (SplatMesh.js:1064-1066); WITHOUT a scene
+//   .ksplat layout    SplatBuffer.js:819-848 (header), :877-941 (section headers); rows per compression level, the bucket of a
+//                     splat and the centre decode are in asset_internal.hpp
+//   arrays            asset_fill_splat (asset_internal.hpp) for every splat of the image; which outputs a call may ask for:
+//                     SH target level = max(1, buffer level) (SplatMesh.js:1064-1066); WITHOUT a scene
 //                     transform (dynamicMode) until gs_asset_set_transform gives one (static mode, SplatMesh.js:1872-1899):
 //                     then Vector3.applyMatrix4 :340-342, T3*C*T3^T :461-466, rotated SH :628-637, 684-688, 707-715, 766-817
 //   scene transform   three r160 Matrix4.decompose / Quaternion.setFromRotationMatrix / normalize / makeRotationFromQuaternion
@@ -43,10 +43,7 @@ uint8_t clamped_u8(double v) {                         // Uint8ClampedArray stor
     return (uint8_t)nearbyint(v);
 }
 
-using Section = AssetSection;
 constexpr size_t KS_HEADER = 4096, KS_SECTION_HEADER = 1024;
-constexpr auto &CENTER_BYTES = ASSET_CENTER_BYTES, &SCALE_BYTES = ASSET_SCALE_BYTES, &ROT_BYTES = ASSET_ROT_BYTES,
-               &SH_BYTES_PER = ASSET_SH_BYTES_PER;
 
 int parse_ksplat(gs_asset* a) {
     const size_t n = a->buf.size();
@@ -62,63 +59,77 @@ int parse_ksplat(gs_asset* a) {
     size_t base = KS_HEADER + (size_t)max_sections * KS_SECTION_HEADER;
     uint32_t count_offset = 0;
     uint32_t min_degree = 0;
+    a->sections.clear();
+    a->partial_end.clear();
     for (uint32_t s = 0; s < max_sections; s++) {
         const size_t h = KS_HEADER + (size_t)s * KS_SECTION_HEADER;
-        Section sec = {};
-        sec.max_splat_count = a->rd<uint32_t>(h + 4);
-        sec.splat_count = sec.max_splat_count;             // secLoadedCountsToMax
+        KsplatSection sec = {};
+        sec.count = a->rd<uint32_t>(h + 4);                // maxSplatCount: secLoadedCountsToMax
         sec.bucket_size = a->rd<uint32_t>(h + 8);
         sec.bucket_count = a->rd<uint32_t>(h + 12);
-        const float block = a->rd<float>(h + 16);
-        sec.half_block = (double)block / 2.0;
-        const uint32_t bucket_storage = a->rd<uint16_t>(h + 20);
-        sec.bucket_storage = bucket_storage;
+        const double half_block = (double)a->rd<float>(h + 16) / 2.0;
+        sec.bucket_storage = a->rd<uint16_t>(h + 20);
         const uint32_t range = a->rd<uint32_t>(h + 24);
         sec.scale_range = range ? range : (a->level == 0 ? 1u : 32767u);
-        sec.scale_factor = sec.half_block / (double)sec.scale_range;
+        sec.scale_factor = half_block / (double)sec.scale_range;
         sec.full_buckets = a->rd<uint32_t>(h + 32);
-        sec.partial_buckets = a->rd<uint32_t>(h + 36);
-        sec.sh_degree = a->rd<uint16_t>(h + 40);
-        GS_REQUIRE(sec.sh_degree <= 2, ".ksplat: spherical harmonics degree > 2");
-        sec.bytes_per_splat = CENTER_BYTES[a->level] + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u +
-                              SH_BYTES_PER[a->level] * sh_components(sec.sh_degree);
-        const size_t meta = (size_t)sec.partial_buckets * 4, buckets = (size_t)bucket_storage * sec.bucket_count + meta;
-        sec.base = base;
-        sec.buckets_base = base + meta;
-        sec.data_base = base + buckets;
+        const uint32_t partial_buckets = a->rd<uint32_t>(h + 36), sh_degree = a->rd<uint16_t>(h + 40);
+        GS_REQUIRE(sh_degree <= 2, ".ksplat: spherical harmonics degree > 2");
+        sec.bytes_per_splat = asset_center_bytes(a->level) + asset_scale_bytes(a->level) + asset_rotation_bytes(a->level) + 4u +
+                              asset_sh_value_bytes(a->level) * sh_components(sh_degree);
+        const size_t meta = (size_t)partial_buckets * 4, buckets = (size_t)sec.bucket_storage * sec.bucket_count + meta;
+        sec.buckets_off = (long long)(base + meta);
+        sec.data_off = (long long)(base + buckets);
         sec.count_offset = count_offset;
-        const size_t end = sec.data_base + (size_t)sec.bytes_per_splat * sec.max_splat_count;
+        const size_t end = base + buckets + (size_t)sec.bytes_per_splat * sec.count;
         GS_REQUIRE(end <= n, ".ksplat: section data exceeds the file");
-        if (a->level > 0 && sec.max_splat_count > 0) {
+        sec.partial_begin = (uint32_t)a->partial_end.size();
+        if (a->level > 0 && sec.count > 0) {
             // Bucket tables are only read for compressed centres (SplatBuffer.js:199-246).  The reference is memory-safe
-            // JavaScript; here every index into the tables is proven in range before gs_asset_fill reads through them.
-            GS_REQUIRE(bucket_storage >= 12, ".ksplat: bucket storage below the 12 bytes of a bucket centre");
+            // JavaScript; here every index into the tables is proven in range before a row read goes through them.
+            GS_REQUIRE(sec.bucket_storage >= 12, ".ksplat: bucket storage below the 12 bytes of a bucket centre");
             GS_REQUIRE(sec.bucket_size > 0, ".ksplat: bucket size 0 in a compressed section");
-            GS_REQUIRE((uint64_t)sec.full_buckets + sec.partial_buckets <= sec.bucket_count,
+            GS_REQUIRE((uint64_t)sec.full_buckets + partial_buckets <= sec.bucket_count,
                        ".ksplat: more full + partial buckets than the section stores");
             uint64_t covered = (uint64_t)sec.full_buckets * sec.bucket_size;
             GS_REQUIRE(covered <= 0xFFFFFFFFull, ".ksplat: full buckets x bucket size overflows 32 bits");   // bucket_index's span
-            sec.partial_end.reserve(sec.partial_buckets);
-            for (uint32_t p = 0; p < sec.partial_buckets; p++) {
-                covered += a->rd<uint32_t>(sec.base + 4 * (size_t)p);
+            for (uint32_t p = 0; p < partial_buckets; p++) {
+                covered += a->rd<uint32_t>(base + 4 * (size_t)p);
                 GS_REQUIRE(covered <= 0xFFFFFFFFull, ".ksplat: partial bucket lengths overflow");
-                sec.partial_end.push_back((uint32_t)covered);
+                a->partial_end.push_back((uint32_t)covered);
             }
-            GS_REQUIRE(covered >= sec.max_splat_count, ".ksplat: the buckets do not cover every splat of the section");
+            GS_REQUIRE(covered >= sec.count, ".ksplat: the buckets do not cover every splat of the section");
+            sec.partial_count = partial_buckets;
         }
         base = end;
-        count_offset += sec.max_splat_count;
-        if (s == 0 || sec.sh_degree < min_degree) min_degree = sec.sh_degree;   // getMinSphericalHarmonicsDegree
-        a->sections.push_back(sec);
+        count_offset += sec.count;
+        if (s == 0 || sh_degree < min_degree) min_degree = sh_degree;   // getMinSphericalHarmonicsDegree
+        if (sec.count > 0) a->sections.push_back(sec);      // section_of looks among the ones that hold splats
     }
     GS_REQUIRE(count_offset == max_splats || max_sections == 0 || count_offset >= max_splats, ".ksplat: splat counts disagree");
     a->splat_count = count_offset < max_splats ? count_offset : max_splats;
     a->sh_degree = min_degree;
-    a->section_of.resize(count_offset);
-    for (uint32_t s = 0; s < a->sections.size(); s++)
-        for (uint32_t j = 0; j < a->sections[s].max_splat_count; j++) a->section_of[a->sections[s].count_offset + j] = s;
     return GS_OK;
 }
+
+// ---- the level-0 image an INRIA-v1 PLY and the row formats are laid out as ------------------------------
+// SplatBuffer.preallocateUncompressed (:1401-1433): header + one section header, rows of 44 + 4 * ncomp bytes
+void level0_header(std::vector<uint8_t>& buf, uint32_t count, uint32_t degree) {
+    const uint32_t bps = 44u + 4u * sh_components(degree);
+    buf.assign(KS_HEADER + KS_SECTION_HEADER + (size_t)bps * count, 0);
+    uint8_t* B = buf.data();
+    auto W32 = [&](size_t off, uint32_t v) { memcpy(B + off, &v, 4); };
+    auto W16 = [&](size_t off, uint16_t v) { memcpy(B + off, &v, 2); };
+    auto WF = [&](size_t off, float v) { memcpy(B + off, &v, 4); };
+    B[0] = 0; B[1] = 1;
+    W32(4, 1); W32(8, 1); W32(12, count); W32(16, count); W16(20, 0);
+    WF(36, -1.5f); WF(40, 1.5f);
+    W32(KS_HEADER + 0, count); W32(KS_HEADER + 4, count); W16(KS_HEADER + 40, (uint16_t)degree);
+}
+void store_level0_row(uint8_t* o, const Level0Tuple& t) {
+    memcpy(o, t.c, 12); memcpy(o + 12, t.s, 12); memcpy(o + 24, t.r, 16); memcpy(o + 40, t.rgba, 4);
+}
+void store_level0_sh(uint8_t* o, uint32_t s, float v) { memcpy(o + 44 + 4 * s, &v, 4); }   // SH float s of the row
 
 // ---- PLY ------------------------------------------------------------------------------------------
 enum FieldType { T_DOUBLE, T_INT, T_UINT, T_FLOAT, T_SHORT, T_USHORT, T_UCHAR, T_UNKNOWN };
@@ -259,21 +270,14 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
         if (degree >= 2) for (int i = 0; i < 5; i++) F_d2[5 * rgb + i] = find(rest_name(i + cpc_d * rgb + 3));
     }
 
-    // level-0 .ksplat image with one section (SplatBuffer.preallocateUncompressed :1401-1433)
     const uint32_t ncomp = sh_components(out_degree), bps = 44u + 4u * ncomp;
-    a->buf.assign(KS_HEADER + KS_SECTION_HEADER + (size_t)bps * vertex_count, 0);
-    uint8_t* B = a->buf.data();
-    auto W32 = [&](size_t off, uint32_t v) { memcpy(B + off, &v, 4); };
-    auto W16 = [&](size_t off, uint16_t v) { memcpy(B + off, &v, 2); };
-    auto WF = [&](size_t off, float v) { memcpy(B + off, &v, 4); };
-    B[0] = 0; B[1] = 1;
-    W32(4, 1); W32(8, 1); W32(12, vertex_count); W32(16, vertex_count); W16(20, 0);
-    WF(36, -1.5f); WF(40, 1.5f);
-    W32(KS_HEADER + 0, vertex_count); W32(KS_HEADER + 4, vertex_count); W16(KS_HEADER + 40, (uint16_t)out_degree);
+    level0_header(a->buf, vertex_count, out_degree);
+    uint8_t* B = a->buf.data() + KS_HEADER + KS_SECTION_HEADER;
     const uint8_t* rows = data + header_bytes;
     for (uint32_t i = 0; i < vertex_count; i++) {
         const uint8_t* row = rows + (size_t)i * bytes_per_vertex;
-        const size_t o = KS_HEADER + KS_SECTION_HEADER + (size_t)i * bps;
+        uint8_t* o = B + (size_t)i * bps;
+        Level0Tuple t;
         double v, s3[3], r4[4] = {NAN, NAN, NAN, NAN}, c3[3] = {NAN, NAN, NAN}, col[3], op = 0.0;   // createSplat() starts every field at 0
         // INRIAV1PlyParser.js:148-156
         if (read_field(row, F_scale[0], &v)) {
@@ -295,48 +299,31 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
         op = clampd(floor(op), 0, 255);
         // :196-202 Quaternion.set(rot_0..3).normalize(), then the second normalize of writeSplatDataToSectionBuffer :1084-1086
         for (int k = 0; k < 4; k++) if (read_field(row, F_rot[k], &v)) r4[k] = v;
-        for (int pass = 0; pass < 2; pass++) {
-            double l = sqrt(r4[0] * r4[0] + r4[1] * r4[1] + r4[2] * r4[2] + r4[3] * r4[3]);   // x*x + y*y + z*z + w*w
-            if (l == 0) { r4[0] = r4[1] = r4[2] = 0; r4[3] = 1; }
-            else { l = 1 / l; for (int k = 0; k < 4; k++) r4[k] = r4[k] * l; }
-        }
+        row_normalize(r4);
+        row_normalize(r4);
         for (int k = 0; k < 3; k++) if (read_field(row, F_pos[k], &v)) c3[k] = v;
-        for (int k = 0; k < 3; k++) WF(o + 4 * k, (float)c3[k]);
-        for (int k = 0; k < 3; k++) WF(o + 12 + 4 * k, (float)(s3[k] == s3[k] ? s3[k] : 0.0));   // `|| 0`
-        for (int k = 0; k < 4; k++) WF(o + 24 + 4 * k, (float)r4[k]);
-        B[o + 40] = clamped_u8(col[0]); B[o + 41] = clamped_u8(col[1]); B[o + 42] = clamped_u8(col[2]);
-        B[o + 43] = clamped_u8(op);
+        for (int k = 0; k < 3; k++) t.c[k] = (float)c3[k];
+        for (int k = 0; k < 3; k++) t.s[k] = (float)(s3[k] == s3[k] ? s3[k] : 0.0);        // `|| 0`
+        for (int k = 0; k < 4; k++) t.r[k] = (float)r4[k];
+        for (int k = 0; k < 3; k++) t.rgba[k] = clamped_u8(col[k]);
+        t.rgba[3] = clamped_u8(op);
+        store_level0_row(o, t);
         if (out_degree >= 1) {                                                         // :183-194
             const bool have = read_field(row, F_rest0, &v);
             for (int s = 0; s < 9; s++) {
                 double c = 0;
                 if (have && read_field(row, F_d1[s], &v)) c = v;
-                WF(o + 44 + 4 * s, (float)c);
+                store_level0_sh(o, s, (float)c);
             }
             if (out_degree >= 2)
                 for (int s = 0; s < 15; s++) {
                     double c = 0;
                     if (have && read_field(row, F_d2[s], &v)) c = v;
-                    WF(o + 44 + 36 + 4 * s, (float)c);
+                    store_level0_sh(o, 9 + s, (float)c);
                 }
         }
     }
     return parse_ksplat(a);
-}
-
-// ---- level-0 image of a row format ---------------------------------------------------------------------
-// SplatBuffer.preallocateUncompressed (:1401-1433): header + one section header, rows of 44 + 4 * ncomp bytes
-void level0_header(std::vector<uint8_t>& buf, uint32_t count, uint32_t degree) {
-    const uint32_t bps = 44u + 4u * sh_components(degree);
-    buf.assign(KS_HEADER + KS_SECTION_HEADER + (size_t)bps * count, 0);
-    uint8_t* B = buf.data();
-    auto W32 = [&](size_t off, uint32_t v) { memcpy(B + off, &v, 4); };
-    auto W16 = [&](size_t off, uint16_t v) { memcpy(B + off, &v, 2); };
-    auto WF = [&](size_t off, float v) { memcpy(B + off, &v, 4); };
-    B[0] = 0; B[1] = 1;
-    W32(4, 1); W32(8, 1); W32(12, count); W32(16, count); W16(20, 0);
-    WF(36, -1.5f); WF(40, 1.5f);
-    W32(KS_HEADER + 0, count); W32(KS_HEADER + 4, count); W16(KS_HEADER + 40, (uint16_t)degree);
 }
 
 // What a host fill of a .splat / compressed PLY / .spz asset reads: every file row through the shared row arithmetic
@@ -369,23 +356,16 @@ int build_level0_image(gs_asset* a) {
             b.colour = three(SPZ_COLOURS); b.scale = three(SPZ_SCALES); b.rotation = three(SPZ_ROTATIONS);
             spz_row_tuple(L, b, t);
             const uint8_t* sh = f + L.off[SPZ_SH] + 3 * (size_t)L.file_dim * i;
-            for (uint32_t s = 0; s < ncomp; s++) {
-                const float v = spz_sh_value(sh[spz_sh_index(s)]);
-                memcpy(o + 44 + 4 * s, &v, 4);
-            }
+            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, spz_sh_value(sh[spz_sh_index(s)]));
         } else {
             uint32_t w[4];
             memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
             pc_row_tuple(w, a->file.data() + a->pc_chunk_base + (size_t)a->pc.chunk_stride * (i / 256u), a->pc, t);
             const uint8_t* sh = a->file.data() + a->pc_sh_base + (size_t)a->pc.sh_stride * i;
-            for (uint32_t s = 0; s < ncomp; s++) {
-                const float v = pc_row_sh(sh, a->pc.read_coeff, s);
-                memcpy(o + 44 + 4 * s, &v, 4);
-            }
+            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, pc_row_sh(sh, a->pc.read_coeff, s));
         }
-        memcpy(o, t.c, 12); memcpy(o + 12, t.s, 12); memcpy(o + 24, t.r, 16); memcpy(o + 40, t.rgba, 4);
+        store_level0_row(o, t);
     }
-    a->sections.clear();
     const int st = parse_ksplat(a);
     if (st != GS_OK) a->buf.clear();
     return st;
@@ -567,20 +547,16 @@ int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_
     return GS_OK;
 }
 
-// SplatBuffer.js:199-219: full buckets first, then the partial ones by their stored lengths.  parse_ksplat proved that the
-// tables cover every splat, so the result is always < bucket_count.
-uint32_t bucket_index(const gs_asset*, const Section& sec, uint32_t local) {
-    const uint32_t full_span = sec.full_buckets * sec.bucket_size;
-    if (local < full_span) return local / sec.bucket_size;
-    const auto it = std::upper_bound(sec.partial_end.begin(), sec.partial_end.end(), local);
-    const uint32_t b = sec.full_buckets + (uint32_t)(it - sec.partial_end.begin());
-    return b < sec.bucket_count ? b : sec.bucket_count - 1u;       // unreachable after parse_ksplat's checks; never past the table
-}
-
-double comp(const gs_asset* a, size_t row, uint32_t index, bool sh) {                   // dataViewFloatForCompressionLevel + toUncompressedFloat
-    if (a->level == 0) return a->rd<float>(row + 4 * (size_t)index);
-    if (a->level == 1 || !sh) return from_half(a->rd<uint16_t>(row + 2 * (size_t)index));
-    return (double)a->rd<uint8_t>(row + index) / 255 * (a->sh_max - a->sh_min) + a->sh_min;
+// gs_asset_fill's loop: every splat of the image through the shared per-splat body (asset_internal.hpp)
+template <bool XF>
+void fill_image(const gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba, uint16_t* sh_f16,
+                uint8_t* sh_u8, float* scales, float* rotations) {
+    const KsplatSource image = a->image();
+    const AssetTransform xf = a->xf;                       // a local: the byte stores of the loop cannot be taken to change it
+    const double sh_min = a->sh_min, sh_max = a->sh_max;
+    for (uint32_t i = 0, n = a->splat_count; i < n; i++)
+        asset_fill_splat<XF, true>(image.row(i), xf, image.sh_degree, image.ncomp, sh_min, sh_max, min_alpha, i, centers, cov_f32, cov_f16,
+                                   rgba, sh_f16, sh_u8, scales, rotations);
 }
 
 }  // namespace
@@ -656,93 +632,8 @@ int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f3
         gs_set_error("out of host memory while decoding the asset");
         return GS_ERR_NOMEM;
     }
-    const uint32_t ncomp = sh_components(a->sh_degree);
-    const bool xf = a->has_transform;
-    for (uint32_t i = 0; i < a->splat_count; i++) {
-        const Section& sec = a->sections[a->section_of[i]];
-        const uint32_t local = i - sec.count_offset;
-        const size_t row = sec.data_base + (size_t)sec.bytes_per_splat * local;
-        if (centers) {                                                                 // getSplatCenter :221-246
-            double c[3];
-            if (a->level == 0) {
-                for (int k = 0; k < 3; k++) c[k] = a->rd<float>(row + 4 * k);
-            } else {
-                const uint32_t b = bucket_index(a, sec, local);
-                for (int k = 0; k < 3; k++) {
-                    const double x = a->rd<uint16_t>(row + 2 * k);
-                    const double bc = a->rd<float>(sec.buckets_base + (size_t)sec.bucket_storage * b + 4 * k);
-                    c[k] = (x - (double)sec.scale_range) * sec.scale_factor + bc;
-                }
-            }
-            if (xf) xf_centre(a->xf, c, centers + 3 * (size_t)i);
-            else for (int k = 0; k < 3; k++) centers[3 * (size_t)i + k] = (float)c[k];
-        }
-        const size_t srow = row + CENTER_BYTES[a->level];
-        if (cov_f32 || cov_f16 || scales || rotations) {
-            const double sx = comp(a, srow, 0, false), sy = comp(a, srow, 1, false), sz = comp(a, srow, 2, false);
-            // rotation.set(x = f4, y = f5, z = f6, w = f3): NOT normalised (:539-542)
-            const double w = comp(a, srow, 3, false), x = comp(a, srow, 4, false), y = comp(a, srow, 5, false), z = comp(a, srow, 6, false);
-            if (scales) { scales[3 * (size_t)i] = (float)sx; scales[3 * (size_t)i + 1] = (float)sy; scales[3 * (size_t)i + 2] = (float)sz; }
-            if (rotations) {
-                // fillSplatScaleRotationArray (SplatBuffer.js:407-424): Quaternion.normalize, then ensurePositiveW
-                double q[4] = {x, y, z, w};
-                double l = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-                if (l == 0) { q[0] = q[1] = q[2] = 0; q[3] = 1; }
-                else { l = 1 / l; for (int k = 0; k < 4; k++) q[k] = q[k] * l; }
-                const double flip = q[3] < 0 ? -1 : 1;
-                for (int k = 0; k < 4; k++) rotations[4 * (size_t)i + k] = (float)(q[k] * flip);
-            }
-            if (cov_f32 || cov_f16) {
-                // Matrix4.makeRotationFromQuaternion = compose(zero, q, one) (three r160)
-                const double x2 = x + x, y2 = y + y, z2 = z + z;
-                const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
-                const double wx = w * x2, wy = w * y2, wz = w * z2;
-                const double R[3][3] = {{(1 - (yy + zz)) * 1, (xy - wz) * 1, (xz + wy) * 1},
-                                        {(xy + wz) * 1, (1 - (xx + zz)) * 1, (yz - wx) * 1},
-                                        {(xz - wy) * 1, (yz + wx) * 1, (1 - (xx + yy)) * 1}};
-                // covarianceMatrix = R * S (Matrix3.multiplyMatrices: a_i1*b_1j + a_i2*b_2j + a_i3*b_3j)
-                const double S[3][3] = {{sx, 0, 0}, {0, sy, 0}, {0, 0, sz}};
-                double M[3][3], Cm[3][3];
-                for (int r = 0; r < 3; r++)
-                    for (int c = 0; c < 3; c++) M[r][c] = R[r][0] * S[0][c] + R[r][1] * S[1][c] + R[r][2] * S[2][c];
-                // transformedCovariance = M * M^T
-                for (int r = 0; r < 3; r++)
-                    for (int c = 0; c < 3; c++) Cm[r][c] = M[r][0] * M[c][0] + M[r][1] * M[c][1] + M[r][2] * M[c][2];
-                double e[6] = {Cm[0][0], Cm[0][1], Cm[0][2], Cm[1][1], Cm[1][2], Cm[2][2]};   // elements 0,3,6,4,7,8
-                if (xf) xf_covariance(a->xf, Cm, e);
-                for (int k = 0; k < 6; k++) {
-                    if (cov_f32) cov_f32[6 * (size_t)i + k] = xf ? xf_f32(e[k]) : (float)e[k];
-                    if (cov_f16) cov_f16[6 * (size_t)i + k] = xf ? xf_f16(e[k]) : to_half_three(e[k]);
-                }
-            }
-        }
-        if (rgba) {                                                                    // fillSplatColorArray :551-575
-            const size_t crow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level];
-            for (int k = 0; k < 3; k++) rgba[4 * (size_t)i + k] = a->buf[crow + k];
-            const uint8_t alpha = a->buf[crow + 3];
-            rgba[4 * (size_t)i + 3] = alpha >= min_alpha ? alpha : 0;
-        }
-        if ((sh_f16 || sh_u8) && ncomp && xf) {                                        // fillSphericalHarmonicsArray with a transform
-            const size_t hrow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u;
-            const uint8_t* hp = a->buf.data() + hrow;
-            xf_sh(a->xf, a->sh_degree, [&](uint32_t src) { return sh_widen(a->level, hp, src, a->sh_min, a->sh_max); }, [&](uint32_t dst, double v) {
-                if (sh_u8) sh_u8[(size_t)ncomp * i + dst] = to_uint8_range(v, a->sh_min, a->sh_max);
-                else sh_f16[(size_t)ncomp * i + dst] = xf_f16(v);
-            });
-        } else if ((sh_f16 || sh_u8) && ncomp) {                                       // ... without one
-            const size_t hrow = srow + SCALE_BYTES[a->level] + ROT_BYTES[a->level] + 4u;
-            auto emit = [&](uint32_t dst, uint32_t src) {
-                if (sh_u8) { sh_u8[(size_t)ncomp * i + dst] = a->rd<uint8_t>(hrow + src); return; }
-                sh_f16[(size_t)ncomp * i + dst] = a->level == 0 ? to_half_three(a->rd<float>(hrow + 4 * (size_t)src))
-                                                                : a->rd<uint16_t>(hrow + 2 * (size_t)src);
-            };
-            for (uint32_t c = 0; c < 3; c++)                                           // set3FromArray(stride 3, base c)
-                for (uint32_t ch = 0; ch < 3; ch++) emit(3 * c + ch, c + 3 * ch);
-            if (a->sh_degree >= 2)
-                for (uint32_t c = 0; c < 5; c++)                                       // set3FromArray(stride 5, base 9 + c)
-                    for (uint32_t ch = 0; ch < 3; ch++) emit(9 + 3 * c + ch, 9 + c + 5 * ch);
-        }
-    }
+    if (a->has_transform) fill_image<true>(a, min_alpha, centers, cov_f32, cov_f16, rgba, sh_f16, sh_u8, scales, rotations);
+    else fill_image<false>(a, min_alpha, centers, cov_f32, cov_f16, rgba, sh_f16, sh_u8, scales, rotations);
     return GS_OK;
 }
 
@@ -792,15 +683,12 @@ int gs_asset_set_transform(gs_asset* a, const double* transform16) {
         const double s = 2.0 * sqrt(1.0 + m33 - m11 - m22);
         qw = (m21 - m12) / s; qx = (m13 + m31) / s; qy = (m23 + m32) / s; qz = 0.25 * s;
     }
-    {   // tempRotation.normalize()
-        double l = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-        if (l == 0) { qx = qy = qz = 0; qw = 1; }
-        else { l = 1 / l; qx = qx * l; qy = qy * l; qz = qz * l; qw = qw * l; }
-    }
+    double q[4] = {qx, qy, qz, qw};
+    row_normalize(q);                                                                  // tempRotation.normalize()
     // makeRotationFromQuaternion = compose(zero, q, one), then Matrix3.setFromMatrix4: E = Matrix3.elements (column-major)
     double E[9];
     {
-        const double x = qx, y = qy, z = qz, w = qw;
+        const double x = q[0], y = q[1], z = q[2], w = q[3];
         const double x2 = x + x, y2 = y + y, z2 = z + z;
         const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;
         const double wx = w * x2, wy = w * y2, wz = w * z2;

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import asset_cases
+import ksplat_sections
 from gaussiansplats3d_amd import assets, util
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ply_header_kat.json")))
@@ -260,3 +261,31 @@ def test_malformed_ksplat_bucket_tables_are_rejected_not_read_out_of_bounds():
     struct.pack_into("<I", blob, table + 4 * int(np.argmax(lengths)), 0)      # the largest partial bucket claims nothing
     with pytest.raises(GsError):
         assets.SplatAsset(bytes(blob), "ksplat", 0)
+
+
+@pytest.mark.parametrize("degrees", [(2, 2), (1, 2)])
+@pytest.mark.parametrize("level", [0, 1, 2])
+def test_ksplat_with_several_sections_against_oracle(level, degrees):
+    """Two sections of about 300 splats with an empty one between them (tests/ksplat_sections.py); in the second variant the last
+    section has the higher SH degree, so its rows are longer and the file's degree is the first one's.  gs_asset_fill against
+    oracle/asset_oracle.py's fill_from_ksplat, bit for bit."""
+    from oracle import asset_oracle
+    data = ksplat_sections.three_sections(level, degrees)
+    heads = ksplat_sections.section_headers(data)
+    assert [h["splats"] for h in heads] == [301, 0, 310] and [h["sh_degree"] for h in heads] == [degrees[0], degrees[0], degrees[1]]
+    if level > 0:
+        for h in (heads[0], heads[2]):                        # both bucket paths are taken in both sections
+            assert h["bucket_size"] == 64 and h["full"] >= 1 and h["partial"] >= 2 and h["buckets"] == h["full"] + h["partial"], h
+            assert h["full"] * 64 < h["splats"], "no splat lies in a partial bucket"
+    exp = asset_oracle.fill_from_ksplat(data, min_alpha=20)
+    a = assets.SplatAsset(data, "ksplat", 2)
+    assert (a.info.splat_count, a.info.sh_degree, a.info.compression_level) == (611, min(degrees), level)
+    assert exp["sh_degree"] == min(degrees)
+    got = a.fill(minimum_alpha=20)
+    a.close()
+    np.testing.assert_array_equal(got["centers"].view(np.uint32), exp["centers"].view(np.uint32))
+    np.testing.assert_array_equal(got["cov"].view(np.uint32), exp["cov"].view(np.uint32))
+    np.testing.assert_array_equal(got["rgba"], exp["rgba"])
+    sh = got["sh_u8"] if level == 2 else got["sh_f16"]
+    assert sh.dtype == exp["sh"].dtype and sh.shape == exp["sh"].shape == (611, {1: 9, 2: 24}[min(degrees)])
+    np.testing.assert_array_equal(sh, exp["sh"])

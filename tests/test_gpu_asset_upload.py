@@ -17,6 +17,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import asset_transform_cases
+import ksplat_sections
 from gaussiansplats3d_amd import Context, SplatMesh, assets, camera, create_sort_worker, scenes, util
 from gaussiansplats3d_amd import _lib as L
 
@@ -57,9 +59,9 @@ def host_centers(worker, filled, frm, first, count):
 class Pair:
     """One mesh + one sorter sized for the asset, and what a sort + draw of them shows."""
 
-    def __init__(self, ctx, asset, n, half, integer, keep_order, minimum_alpha):
+    def __init__(self, ctx, asset, n, half, integer, keep_order, minimum_alpha, cam=CAM):
         info = asset.info
-        self.asset, self.n, self.min_alpha, self.half = asset, n, minimum_alpha, half
+        self.asset, self.n, self.min_alpha, self.half, self.cam = asset, n, minimum_alpha, half, cam
         self.mesh = SplatMesh(ctx, n, info.sh_degree, half_precision_covariances=half,
                               spherical_harmonics_8bit=info.sh_level == 2 and info.sh_degree > 0, keep_order=keep_order)
         if self.mesh.sh_8bit:                                # the file's 8-bit SH range (a per-scene uniform)
@@ -85,14 +87,14 @@ class Pair:
 
     def observe(self):
         n = self.n
-        reply = self.worker.post_message({"sort": {"modelViewProj": CAM.sort_mvp(), "splatRenderCount": n, "splatSortCount": n}})
+        reply = self.worker.post_message({"sort": {"modelViewProj": self.cam.sort_mvp(), "splatRenderCount": n, "splatSortCount": n}})
         order = reply["sortedIndexes"].copy()
-        self.mesh.set_camera(CAM)
+        self.mesh.set_camera(self.cam)
         self.mesh.update_render_indexes(order, n)
         frame, _ = self.mesh.render()
         recs, rects, vis = self.mesh.debug_records(n)
         dist = np.empty(n, np.int32)
-        self.mesh.compute_distances_on_gpu(CAM.sort_mvp(), out=dist, integer=True)
+        self.mesh.compute_distances_on_gpu(self.cam.sort_mvp(), out=dist, integer=True)
         return {"order": order, "frame": frame, "records": recs, "rects": rects, "visible": vis, "distances": dist}
 
     def close(self):
@@ -238,6 +240,54 @@ def test_host_and_device_uploads_mix(ctx):
     ranges_case(ctx, [[("host", 0, 0, k), ("host", k, k, n - k)],
                       [("host", 0, 0, k), ("device", k, k, n - k)],
                       [("device", 0, 0, k), ("host", k, k, n - k)]], n=n)
+
+
+# ------------------------------------------------------------------------------------------------ several sections
+@pytest.mark.parametrize("transform", [None, "rigid"])
+@pytest.mark.parametrize("degrees", [(1, 1), (1, 2)])
+@pytest.mark.parametrize("level", [1, 2])
+def test_several_sections(ctx, level, degrees, transform):
+    """301 splats, an empty section, 310 splats (tests/ksplat_sections.py; with degrees (1, 2) the last section's rows are longer
+    than the first's): the whole file, a range from inside the first section's partial buckets to inside the last section (the
+    staged first section starts before the staged bytes, and the range crosses the empty section) and a range wholly in the
+    last section, decoded on the device among host uploads of the rest, against the all-host pair."""
+    data = ksplat_sections.three_sections(level, degrees)
+    heads = ksplat_sections.section_headers(data)
+    n_a, n_b = heads[0]["splats"], heads[2]["splats"]
+    assert (n_a, heads[1]["splats"], n_b) == (301, 0, 310)
+    for h in (heads[0], heads[2]):
+        assert h["full"] >= 1 and h["partial"] >= 2 and h["full"] * h["bucket_size"] < h["splats"], h
+    n = n_a + n_b
+    crossing = (heads[0]["full"] * heads[0]["bucket_size"] + 5, n_a + n_b // 2)      # [begin, end)
+    last = (n_a + 7, n - 13)
+    assert heads[0]["full"] * heads[0]["bucket_size"] < crossing[0] < n_a < crossing[1] < n and n_a < last[0] < last[1] < n
+
+    def around(begin, end):
+        return [("host", 0, 0, begin), ("device", begin, begin, end - begin), ("host", end, end, n - end)]
+
+    asset = assets.SplatAsset(data, "ksplat", 2)
+    pairs = []
+    try:
+        assert asset.info.sh_degree == 1
+        if transform:
+            asset.set_transform(asset_transform_cases.matrix(transform))
+        with np.errstate(all="ignore"):
+            cam = asset_transform_cases.cloud_camera(asset.fill()["centers"])
+        plans = [[("host", 0, 0, n)], [("device", 0, 0, n)], around(*crossing), around(*last)]
+        seen = []
+        for plan in plans:
+            pair = Pair(ctx, asset, n, level == 2, transform is None, False, 1, cam=cam)
+            pairs.append(pair)
+            for path, frm, first, count in plan:
+                (pair.host if path == "host" else pair.device)(frm, first, count)
+            seen.append(pair.observe())
+        assert seen[0]["frame"].any() and seen[0]["visible"].mean() >= 0.25, "the camera sees too little of the file"
+        for k in range(1, len(seen)):
+            assert_same(seen[0], seen[k], f"plan {k}")
+    finally:
+        for pair in pairs:
+            pair.close()
+        asset.close()
 
 
 # ------------------------------------------------------------------------------------------------ hostile rows
