@@ -143,6 +143,7 @@ SYMBOLS = {
     "gs_mesh_debug_read": (C.c_int, [_VP, C.c_int, _VP, C.c_uint32]),
     "gs_mesh_compute_distances": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "gs_mesh_debug_rop8": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
+    "gs_mesh_surface": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP]),
     "gs_mesh_set_deep_pass": (C.c_int, [_VP, C.c_int]),
     "gs_mesh_set_draw_mode": (C.c_int, [_VP, C.c_uint32]),
     "gs_mesh_last_stats": (C.c_int, [_VP, C.POINTER(RenderStats)]),

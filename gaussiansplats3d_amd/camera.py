@@ -79,6 +79,17 @@ def multiply(a16, b16):
     return _elements(_mat(a16) @ _mat(b16))
 
 
+def unproject(px, py, depth, width, height, projection, view):
+    """A window-space point -> world space, in fp64: (px, py) in pixels (GL window coordinates, row 0 = bottom; a pixel's centre
+    is at +0.5), depth = 0.5 * ndc.z + 0.5 as ``SplatMesh.surface`` reports it; projection / view: column-major 16-vectors
+    of the draw.  `view` is the camera's own view matrix (matrixWorldInverse), NOT the modelView: a mesh's model matrix is part of
+    what was drawn, and the point that comes back through inverse(projection * view) is in world space whatever that matrix is
+    (with the modelView instead it would be in the mesh's local space)."""
+    ndc = np.array([2.0 * float(px) / float(width) - 1.0, 2.0 * float(py) / float(height) - 1.0, 2.0 * float(depth) - 1.0, 1.0])
+    p = np.linalg.inv(_mat(projection) @ _mat(view)) @ ndc
+    return p[:3] / p[3]
+
+
 class PerspectiveCamera:
     """Minimal stand-in for the three.js camera the Viewer owns."""
 

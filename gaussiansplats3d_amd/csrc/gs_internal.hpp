@@ -602,3 +602,5 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
 int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
 int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, uint8_t* out_dev);
 int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev);
+int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float threshold,
+                      uint32_t* ids_dev, float* depth_dev);   // either output may be null

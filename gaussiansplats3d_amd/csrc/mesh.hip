@@ -1234,6 +1234,11 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_HIP(hipStreamSynchronize(st));
         GS_REQUIRE(count <= f.entry_count && count <= m->entry_capacity, "count exceeds the entries of the last draw");
         if (count) GS_HIP(hipMemcpyAsync(dst, (m->sorted_buf ? m->evalB : m->evalA).p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    } else if (what == 13) {  // the window depths the last draw's depth test compared, by record slot (what = 9 names a splat's slot)
+        GS_REQUIRE(!m->projection_pending, "a gs_mesh_project is pending: the depths of the last draw are no longer current (draw first)");
+        GS_REQUIRE(m->last_pp.depth_mode != 0u && (size_t)count * 4 <= m->zrec.bytes && count <= m->max_count,
+                   "the last draw had no destination depth (no depths were written) / count exceeds the mesh");
+        if (count) GS_HIP(hipMemcpyAsync(dst, m->zrec.p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     } else GS_REQUIRE(false, "unknown debug selector");
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;
@@ -1306,6 +1311,42 @@ int gs_mesh_debug_rop8(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uin
     GS_TRY(gs_launch_rop8_window(m, pp, x0, y0, width, height, m->staging.as<uint32_t>()));
     GS_HIP(hipMemcpyAsync(rgba_out_host, m->staging.p, bytes, hipMemcpyDeviceToHost, st));
     GS_HIP(hipStreamSynchronize(st));
+    return GS_OK;
+}
+
+int gs_mesh_surface(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float threshold, uint32_t* ids_out_host,
+                    float* depth_out_host, void* ids_out_dev, void* depth_out_dev) {
+    GS_REQUIRE(m, "mesh == NULL");
+    GS_REQUIRE(ids_out_host || depth_out_host || ids_out_dev || depth_out_dev, "gs_mesh_surface: all four outputs are NULL");
+    GS_REQUIRE(!(ids_out_host && ids_out_dev), "gs_mesh_surface: pass the id plane on the host OR on the device, not both");
+    GS_REQUIRE(!(depth_out_host && depth_out_dev), "gs_mesh_surface: pass the depth plane on the host OR on the device, not both");
+    GS_REQUIRE(threshold > 0.0f && threshold < 1.0f, "gs_mesh_surface: the threshold must lie in (0, 1)");
+    GS_REQUIRE(m->has_draw, "gs_mesh_surface: no draw yet");
+    // (as gs_mesh_debug_rop8: the lists of the last draw name records of the set a pending projection has swapped away)
+    GS_REQUIRE(!m->projection_pending, "gs_mesh_surface: a gs_mesh_project is pending: the records of the last draw are no longer current (draw first)");
+    const ProjectParams& pp = m->last_pp;
+    GS_REQUIRE(width > 0 && height > 0, "gs_mesh_surface: the window is empty");
+    GS_REQUIRE((uint64_t)x0 + width <= (uint64_t)pp.width && y0 >= pp.y0 && (uint64_t)y0 + height <= (uint64_t)pp.y1,
+               "gs_mesh_surface: the window leaves the rows the last draw covered");
+    GS_REQUIRE(m->drawn_dest_depth == m->dest_depth && m->drawn_dest_rgba == m->dest_rgba && m->drawn_dest_w == m->dest_w &&
+               m->drawn_dest_h == m->dest_h && m->drawn_dest_flags == m->dest_flags,
+               "the destination changed since the last draw (gs_mesh_set_destination): draw again before gs_mesh_surface");
+    ScopedDevice sd(m->ctx->device);
+    hipStream_t st = m->ctx->stream;
+    const size_t plane = (size_t)width * height * 4;
+    uint32_t* ids_dev = static_cast<uint32_t*>(ids_out_dev);
+    float* depth_dev = static_cast<float*>(depth_out_dev);
+    if (ids_out_host || depth_out_host) {              // host planes are produced in the staging buffer and copied back
+        GS_TRY(m->staging.ensure(2 * plane + 64));
+        if (ids_out_host) ids_dev = m->staging.as<uint32_t>();
+        if (depth_out_host) depth_dev = reinterpret_cast<float*>(m->staging.as<char>() + plane);
+    }
+    GS_TRY(gs_launch_surface(m, pp, x0, y0, width, height, threshold, ids_dev, depth_dev));
+    // (the pass reads the record set the last draw read: the next vertex stage into that set, on ctx->aux, waits for it as well)
+    if (m->ctx->aux != st) GS_HIP(hipEventRecord(m->ev_done, st));
+    if (ids_out_host) GS_HIP(hipMemcpyAsync(ids_out_host, ids_dev, plane, hipMemcpyDeviceToHost, st));
+    if (depth_out_host) GS_HIP(hipMemcpyAsync(depth_out_host, depth_dev, plane, hipMemcpyDeviceToHost, st));
+    if (ids_out_host || depth_out_host) GS_HIP(hipStreamSynchronize(st));
     return GS_OK;
 }
 

@@ -969,6 +969,170 @@ __global__ __launch_bounds__(256) void k_rop8_window(FrameArgs fa, uint32_t wx0,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// the surface pass: per pixel, the splat at which the front-to-back transmittance falls to a threshold (gs_mesh_surface)
+// ---------------------------------------------------------------------------------------------------------------------------
+// What a host scene that draws AFTER the splats needs to know of them (a cursor, depth of field, click-to-focus, transparent
+// objects): where the splat surface is.  The "median depth" of the 3DGS literature, read from the last draw's own lists like
+// k_rop8_window, on the blend's geometry: one workgroup per 32-px bin that intersects the window, one wave per 16x16 quadrant, four
+// pixels per lane; the parent list is scanned in batches of 256 entries staged exactly as the draws stage them (same rect and
+// exact reach tests, same expansion, the blend's own alpha_of - fragment rule and depth test included), and each wave walks its
+// survivors in ascending order carrying nothing but T (T <- fma(-T, a, T), the blend's step).  A pixel's answer is the FIRST entry
+// after which T <= threshold; an entry that contributes a = 0 (discarded, depth-culled, or never staged for the quadrant) leaves
+// T where it was - above the threshold for a pixel that has not crossed - so it can never be an answer.  A wave stops when every
+// pixel of its quadrant inside the window has crossed, the workgroup when its four waves have or the list ends.  No chunks, no
+// deep pass, no statistics: T is sequential and the walk is a few splats long wherever the frame is opaque; translucent content
+// that never crosses is walked to the end of its list by one wave per quadrant (the cost of the full ROP8 walk's scan).
+// After the walk every lane resolves its <= 4 crossing record slots: slot -> storage position (k_project compacts survivors inside
+// their 256-splat block: the (slot - block base)-th set bit of the block's four mask words) -> the caller's index (inv_perm), and
+// the window depth of that centre recomputed in the vertex stage's operation order, unquantised.  (Not through zrec: that plane
+// exists only under a destination depth and holds the 24-bit value in that mode.)
+constexpr uint32_t GS_SURFACE_NONE = 0xFFFFFFFFu;
+struct SurfaceArgs {
+    const unsigned long long* __restrict__ vis_mask;
+    const uint32_t* __restrict__ inv_perm;          // storage position -> the caller's index (null: the mesh keeps upload order)
+    const float* __restrict__ cx;
+    const float* __restrict__ cy;
+    const float* __restrict__ cz;
+    const uint32_t* __restrict__ scene_idx;
+    const gs_scene_params* __restrict__ scenes;
+    float view[16], proj[16], view_matrix[16];      // the last draw's (ProjectParams)
+    uint32_t dynamic, scene_count, count;
+    uint32_t wx0, wy0, ww, wh;                      // the window, in pixels
+    uint32_t bx0, by0, nbx;                         // its first 32-px bin and bins per row: workgroup b -> bin (bx0 + b % nbx, by0 + b / nbx)
+    float threshold;
+    uint32_t* __restrict__ ids;                     // [wh][ww] each, row-major from wy0 upwards; either may be null
+    float* __restrict__ depth;
+};
+// the storage position of record slot `slot`: the (slot - block base)-th visible splat of its 256-splat block (project.hip)
+__device__ __forceinline__ uint32_t surface_position(const unsigned long long* __restrict__ vis_mask, uint32_t slot) {
+    const uint32_t blk = slot >> 8;
+    uint32_t r = slot & 255u;
+    for (uint32_t w = 0; w < 4u; w++) {
+        unsigned long long word = vis_mask[4u * (size_t)blk + w];
+        const uint32_t c = (uint32_t)__popcll(word);
+        if (r < c) {
+            for (; r; r--) word &= word - 1ull;
+            return blk * 256u + w * 64u + (uint32_t)__builtin_ctzll(word);
+        }
+        r -= c;
+    }
+    return GS_SURFACE_NONE;                         // (a slot the mask does not hold: no such record was written)
+}
+// window depth of the centre at storage position i, in k_project's expression order (project.hip: v = MV c, q = P v, q.z / q.w)
+__device__ __forceinline__ float surface_depth(const SurfaceArgs& sa, uint32_t i) {
+#pragma clang fp contract(off)
+    const float c0 = sa.cx[i], c1 = sa.cy[i], c2 = sa.cz[i];
+    const float* MV = sa.view;
+    const float* P = sa.proj;
+    float MVd[16];
+    if (sa.dynamic) {                               // viewMatrix * transforms[scene]
+        const uint32_t scene = sa.scene_count > 1u ? min(sa.scene_idx[i], GS_MAX_SCENES - 1u) : 0u;
+        const float* A = sa.view_matrix;
+        const float* B = sa.scenes->transforms[scene];
+#pragma unroll
+        for (int col = 0; col < 4; col++)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                MVd[4 * col + r] = A[r] * B[4 * col] + A[4 + r] * B[4 * col + 1] + A[8 + r] * B[4 * col + 2] + A[12 + r] * B[4 * col + 3];
+        MV = MVd;
+    }
+    float v[4], q[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) v[r] = MV[r] * c0 + MV[4 + r] * c1 + MV[8 + r] * c2 + MV[12 + r];
+#pragma unroll
+    for (int r = 0; r < 4; r++) q[r] = P[r] * v[0] + P[4 + r] * v[1] + P[8 + r] * v[2] + P[12 + r] * v[3];
+    const float ndcz = q[2] / q[3];
+    return ndcz * 0.5f + 0.5f;
+}
+template <bool DEPTH>
+__global__ __launch_bounds__(BLEND_THREADS) void k_surface(FrameArgs fa, SurfaceArgs sa) {
+    __shared__ LdsSplat s_batch[BLEND_THREADS];
+    __shared__ uint32_t s_qmask[BLEND_THREADS];
+    __shared__ uint32_t s_slot[BLEND_THREADS];
+    __shared__ uint32_t s_live;
+    const uint32_t wbx = sa.bx0 + blockIdx.x % sa.nbx, wby = sa.by0 + blockIdx.x / sa.nbx;
+    const BinGeom bg(fa, (wby - fa.bin_row_begin) * fa.bins_x + wbx);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t bx = bg.bx, by = bg.by, begin = bg.begin, n = bg.n;
+    const QuadLane<DEPTH> ql(fa, bg, wave, lane);
+    // the lane's pixels inside the window that have not crossed yet: bit g = pixel (px, py0 + 4 g)
+    uint32_t pending = 0;
+#pragma unroll
+    for (uint32_t g = 0; g < 4u; g++) {
+        const uint32_t py = ql.py0 + 4u * g;
+        if (ql.px >= sa.wx0 && ql.px - sa.wx0 < sa.ww && py >= sa.wy0 && py - sa.wy0 < sa.wh) pending |= 1u << g;
+    }
+    const uint32_t mine = pending;
+    bool live_wave = __ballot(pending != 0u) != 0ull;
+    v2f T[2] = {{1.0f, 1.0f}, {1.0f, 1.0f}};
+    uint32_t hit[4] = {GS_SURFACE_NONE, GS_SURFACE_NONE, GS_SURFACE_NONE, GS_SURFACE_NONE};
+    for (uint32_t base = 0; base < n; base += BLEND_THREADS) {
+        const uint32_t cnt = min((uint32_t)BLEND_THREADS, n - base);
+        __syncthreads();                               // previous batch fully consumed, s_live read by everyone
+        uint32_t qm = 0, slot = 0;
+        if (tid < cnt) {
+            slot = fa.vals[begin + base + tid];
+            qm = quadrant_mask(fa.rects[slot], bx, by);
+            if (qm) {
+                const uint4 lo = fa.recs[2 * (size_t)slot], hi = fa.recs[2 * (size_t)slot + 1];
+                qm = exact_quadrants(qm, lo, hi, bx, by);
+                if (qm) stage_entry(&s_batch[tid], lo, hi, bx, by, DEPTH ? fa.zrec[slot] : 0.0f);
+            }
+        }
+        s_qmask[tid] = qm;
+        s_slot[tid] = slot;
+        if (tid == 0u) s_live = 0u;
+        __syncthreads();
+        if (live_wave) {
+            for (uint32_t g0 = 0; g0 < cnt && live_wave; g0 += 64u) {
+                unsigned long long m = __ballot((s_qmask[g0 + lane] >> wave) & 1u);
+                while (m) {
+                    const uint32_t j = g0 + (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1ull;
+                    Alpha al;
+                    BlendProf none;
+                    alpha_of(&s_batch[j], ql, al, none);
+                    const uint32_t sj = s_slot[j];
+#pragma unroll
+                    for (int h = 0; h < 2; h++) T[h] = fma2(-T[h], al.a[h], T[h]);
+#pragma unroll
+                    for (uint32_t g = 0; g < 4u; g++) {
+                        if (((pending >> g) & 1u) && T[g >> 1][g & 1] <= sa.threshold) {
+                            hit[g] = sj;
+                            pending &= ~(1u << g);
+                        }
+                    }
+                    if (__ballot(pending != 0u) == 0ull) {     // every pixel of the quadrant inside the window has its answer
+                        live_wave = false;
+                        break;
+                    }
+                }
+            }
+            if (live_wave) s_live = 1u;                // (every lane stores the same word, as in bin_body)
+        }
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane((int)s_live) == 0) break;
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < 4u; g++) {
+        if (!((mine >> g) & 1u)) continue;
+        uint32_t id = GS_SURFACE_NONE;
+        float z = 1.0f;
+        if (hit[g] != GS_SURFACE_NONE) {
+            const uint32_t pos = surface_position(sa.vis_mask, hit[g]);
+            if (pos < sa.count) {
+                id = sa.inv_perm ? sa.inv_perm[pos] : pos;
+                z = surface_depth(sa, pos);
+            }
+        }
+        const size_t o = (size_t)(ql.py0 + 4u * g - sa.wy0) * sa.ww + (ql.px - sa.wx0);
+        if (sa.ids) sa.ids[o] = id;
+        if (sa.depth) sa.depth[o] = z;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // GS_DRAW_ROP8: the reference's render target as a DRAW MODE (round 6; VERDICT r05 missing 2 / item 8)
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same composite as k_rop8_window - back to front, NormalBlending into RGBA8, every channel rounded to 8 bits after EVERY
@@ -1204,6 +1368,34 @@ static FrameArgs frame_args(const gs_mesh* m, const ProjectParams& pp) {
 
 int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev) {
     hipLaunchKernelGGL(k_rop8_window, dim3((w * h + 255u) / 256u), dim3(256), 0, m->ctx->stream, frame_args(m, pp), x0, y0, w, h, out_dev);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// the surface pass over the window [x0, x0 + w) x [y0, y0 + h) of the draw `pp` describes (checked by gs_mesh_surface)
+int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float threshold,
+                      uint32_t* ids_dev, float* depth_dev) {
+    const FrameArgs fa = frame_args(m, pp);
+    SurfaceArgs sa = {};
+    sa.vis_mask = m->vis_mask.as<unsigned long long>();
+    sa.inv_perm = m->reorder ? m->inv_perm.as<uint32_t>() : nullptr;
+    sa.cx = m->px.as<float>(); sa.cy = m->py.as<float>(); sa.cz = m->pz.as<float>();
+    sa.scene_idx = m->scene_idx.as<uint32_t>();
+    sa.scenes = m->scene_dev.as<gs_scene_params>();
+    memcpy(sa.view, pp.view, sizeof(sa.view));
+    memcpy(sa.proj, pp.proj, sizeof(sa.proj));
+    memcpy(sa.view_matrix, pp.view_matrix, sizeof(sa.view_matrix));
+    sa.dynamic = (pp.flags & GS_CAM_DYNAMIC) ? 1u : 0u;
+    sa.scene_count = pp.scene_count;
+    sa.count = pp.count;
+    sa.wx0 = x0; sa.wy0 = y0; sa.ww = w; sa.wh = h;
+    sa.bx0 = x0 / GS_BIN; sa.by0 = y0 / GS_BIN;
+    sa.nbx = (x0 + w - 1u) / GS_BIN - sa.bx0 + 1u;
+    const uint32_t nby = (y0 + h - 1u) / GS_BIN - sa.by0 + 1u;
+    sa.threshold = threshold;
+    sa.ids = ids_dev; sa.depth = depth_dev;
+    if (fa.depth_mode) hipLaunchKernelGGL(k_surface<true>, dim3(sa.nbx * nby), dim3(BLEND_THREADS), 0, m->ctx->stream, fa, sa);
+    else hipLaunchKernelGGL(k_surface<false>, dim3(sa.nbx * nby), dim3(BLEND_THREADS), 0, m->ctx->stream, fa, sa);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }

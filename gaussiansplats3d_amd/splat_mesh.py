@@ -312,6 +312,20 @@ class SplatMesh:
         vis = np.unpackbits(mask.view(np.uint8), bitorder="little")[:n].astype(bool)
         return recs, rects, vis
 
+    def debug_depths(self):
+        """The window depth the last draw's destination depth test compared for every splat (gs_mesh_debug_read what = 13 through
+        the slots of what = 9): float32 [n] in the caller's numbering, NaN where the splat was not visible.  Needs a draw with a
+        destination depth."""
+        n = self.splat_count
+        slots = np.empty(n, dtype=np.uint32)
+        plane = np.empty(self.max_splat_count, dtype=np.float32)
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 9, slots.ctypes.data, n))
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 13, plane.ctypes.data, self.max_splat_count))
+        vis = slots != 0xFFFFFFFF
+        out = np.full(n, np.nan, dtype=np.float32)
+        out[vis] = plane[slots[vis]]
+        return out
+
     def debug_cull_planes(self):
         """The upload-time planes behind the strip and block culls (gs_mesh_debug_read what = 10 / 11 / 12): (cov_bound float32 [n]
         by original splat index; block_box float32 [blocks, 8] per 256-splat storage block - min xyz, max xyz, largest member
@@ -451,6 +465,23 @@ class SplatMesh:
         out = np.empty((int(height), int(width), 4), dtype=np.uint8)
         L.check(self.lib.gs_mesh_debug_rop8(self.handle, int(x0), int(y0), int(width), int(height), out.ctypes.data))
         return out
+
+    def surface(self, x0, y0, width, height, threshold=0.5, ids_device_ptr=None, depth_device_ptr=None):
+        """Where the splat surface of the LAST draw is (gs_mesh_surface): per pixel of the window [x0, x0+width) x [y0, y0+height)
+        (GL window coordinates, row 0 = bottom) the first splat of the pixel's near -> far list after which the transmittance
+        T = prod(1 - alpha) has fallen to `threshold`, and the window depth of that splat's centre.  Returns (ids uint32 [h, w] -
+        the caller's splat numbering, 0xFFFFFFFF = the list ends first; depth float32 [h, w] - 0.5 * ndc.z + 0.5, 1.0 = none).
+        A plane given as a device pointer (uint32 / float32 [h, w]) is only enqueued on the context's stream and comes back as
+        None.  ``camera.unproject`` with the camera's view matrix turns (px + 0.5, py + 0.5, depth) into the world point."""
+        h, w = int(height), int(width)
+        ids = None if ids_device_ptr else np.empty((max(h, 0), max(w, 0)), dtype=np.uint32)
+        depth = None if depth_device_ptr else np.empty((max(h, 0), max(w, 0)), dtype=np.float32)
+        L.check(self.lib.gs_mesh_surface(self.handle, int(x0), int(y0), w, h, float(threshold),
+                                         ids.ctypes.data if ids is not None else None,
+                                         depth.ctypes.data if depth is not None else None,
+                                         C.c_void_p(int(ids_device_ptr)) if ids_device_ptr else None,
+                                         C.c_void_p(int(depth_device_ptr)) if depth_device_ptr else None))
+        return ids, depth
 
     def dispose(self):
         if self.handle:

@@ -508,6 +508,9 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * count <= the uploaded splats); 11 = the boxes of the 256-splat storage blocks, 8 floats per block: {min xyz, max xyz of the
  * members' centres (NaN left out), the largest member bound of what = 10 (NaN if any member's is), unused} (count = blocks <=
  * ceil(max_splat_count / 256)); 12 = per splat, in the caller's numbering, its storage position (uint32; block = position / 256).
+ * 13 = the window depths the last draw's destination depth test compared, float per RECORD SLOT (what = 9 gives a splat's slot; only
+ * the slots of visible splats are defined; count <= max_splat_count): 0.5 * ndc.z + 0.5 as the vertex stage formed it, or that value as
+ * a 24-bit integer under GS_DEST_DEPTH_UNORM24; refused when the last draw had no destination depth.
  * 10 .. 12 read what the uploads left and need no draw.  Like the reads above, 10 and 12 go through the mesh's upload staging
  * buffer: no debug read may run while another thread uploads to the same mesh.
  *
@@ -527,6 +530,32 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count);
  * splat, farthest first.  (x0, y0) in GL window coordinates (row 0 = bottom), inside the rows the last draw covered;
  * rgba_out_host: uint8[4*width*height], row-major from y0 upwards.  A thread per pixel walks its whole list: not a draw mode. */
 int gs_mesh_debug_rop8(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint8_t* rgba_out_host);
+
+/* THE SURFACE PASS: where the splat surface of the LAST draw is, per pixel of a window - what a host scene that draws AFTER the
+ * splats needs (transparent objects, a cursor, depth of field, collision, click-to-focus).  For the pixel centred at
+ * (px + 0.5, py + 0.5) the entry list of its list bin is walked near -> far; an entry is KEPT when its 16-px tile rect covers the
+ * pixel's tile, the fragment rule keeps it (power < 4 log2(e), i.e. A <= 8, as in the blend) and - when the last draw had a
+ * destination depth - its window depth passes the blend's test against the stored depth (GS_DEST_DEPTH_UNORM24 included: splats
+ * hidden by opaque geometry are not surface).  Each kept entry contributes a = exp2(-power) * alpha in the blend's own fp32
+ * arithmetic; from T = 1, T <- T (1 - a).  The answer is the FIRST kept entry after which T <= threshold - the "median depth" of
+ * the 3DGS literature at threshold 0.5:
+ *   ids    that splat's index in the caller's numbering, 0xFFFFFFFF when the list ends first;
+ *   depth  the window depth of that splat's centre, 0.5 * ndc.z + 0.5 as an unquantised float (the vertex stage's expression
+ *          order, per-scene transforms of GS_CAM_DYNAMIC included, read as they are set NOW), 1.0f when there is none.
+ * (x0, y0) in GL window coordinates (row 0 = bottom); the window is 1x1 .. the whole frame and lies inside the rows the last
+ * draw covered (a strip draw covers only its own rows).  Outputs: row-major from y0 upwards, `width` per row; any subset of the
+ * four pointers, at least one, and not a host and a device pointer for the same plane.  Host outputs wait for the result; device
+ * outputs only enqueue on the context's stream.  The answer does not depend on the window, on list batching, on the list-bin size,
+ * on the storage order or on how strips cut the frame.  The mesh must still hold the splats that draw saw: an upload or new scene
+ * parameters between the draw and this call are not detected, and the ids and depths then describe the new contents.
+ * GS_ERR_INVALID, nothing written: no draw yet; a gs_mesh_project is pending; the destination changed since the last draw; a
+ * threshold outside (0, 1) or NaN; an empty window or one that leaves the drawn rows; no output; both pointers of a plane.
+ * Cost (csrc/tile_blend.hip, k_surface): a workgroup per 32-px bin of the window, a wave per 16x16 quadrant, lists scanned in
+ * batches of 256 until every pixel of the bin has its answer - a few splats deep where the frame is opaque.  Translucent content
+ * that never reaches the threshold is walked to the end of its list by ONE wave per quadrant: there is no chunked or deep path
+ * here.  No existing kernel takes part: frames are unchanged. */
+int gs_mesh_surface(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float threshold,
+                    uint32_t* ids_out_host, float* depth_out_host, void* ids_out_dev, void* depth_out_dev);
 
 /* DRAW MODE of the draws that follow.
  *   GS_DRAW_FP32 (default)  the front-to-back fp32 composite, rounded to RGBA8 once (early termination, chunks, the deep pass):

@@ -382,6 +382,18 @@ export class SplatMesh {
     this._rop8 = enabled ? (full ? 2 : 1) : 0;
     if (this.core) this.core.setRop8(!!enabled, !!full);
   }
+  // HIP-engine extra: the splat surface of the LAST frame at the pixel (x, y) - GL window coordinates of `this.frame`, row 0 = bottom:
+  // the first splat of the pixel's near -> far list after which the transmittance has fallen to `threshold` (gs_mesh_surface: the
+  // "median depth" at 0.5; opacity and the destination's depth test count, unlike the reference's ray / sphere test).  Returns
+  // {splatIndex (global), depth (window depth of the splat's centre), position (THREE.Vector3, WORLD space: the pixel's centre at
+  // that depth through inverse(projection * camera.matrixWorldInverse) of the frame that was drawn - this.matrixWorld is part of the
+  // modelView the splats were drawn with, not of this un-projection)} or null where the pixel's splats never get there.
+  // node/Raycaster.mjs wraps it in the reference Raycaster's interface.
+  surfaceAt(x, y, threshold = 0.5) {
+    if (!this.core || !this.frame) return null;
+    const s = this.core.surfaceAt(x, y, threshold);
+    return s && { splatIndex: s.splatIndex, depth: s.depth, position: new THREE.Vector3(s.position[0], s.position[1], s.position[2]) };
+  }
   renderFrame(camera, out) {
     if (!this.core || this.getSplatCount() <= 0) return null;
     const view = camera.matrixWorldInverse ? camera.matrixWorldInverse : new THREE.Matrix4().copy(camera.matrixWorld).invert();

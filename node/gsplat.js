@@ -312,6 +312,7 @@ class SplatMeshHIP {
   renderStrip(group, rowBegin, rowEnd, root, out) {
     const c = this._camera();
     c.tileRowBegin = 0; c.tileRowEnd = 0;                                  // the library derives the strip from the row tables
+    this._keepDrawn(c);
     return addon.groupRenderGather(group.handle, this.handle, c, this.indexes, this.sortWorker ? this.sortWorker.handle : null,
                                    this.renderCount, rowBegin, rowEnd, root, out || null);
   }
@@ -320,9 +321,60 @@ class SplatMeshHIP {
     c.tileRowBegin = 0; c.tileRowEnd = 0;
     const pixels = out || new Uint8Array(c.width * c.height * 4);
     const stats = addon.meshRender(this.handle, c, this.indexes, this.sortWorker ? this.sortWorker.handle : null, this.renderCount, pixels);
+    this._keepDrawn(c);
     return { pixels, stats };
   }
+  // HIP-engine extra: where the splat surface of the LAST frame is (gs_mesh_surface).  Per pixel of the window (GL window
+  // coordinates, row 0 = bottom) the first splat of the pixel's near -> far list after which the transmittance has fallen to
+  // `threshold` - ids Uint32Array (0xFFFFFFFF = none) - and the window depth of its centre - depth Float32Array (1 = none).
+  surface(x0, y0, width, height, threshold = 0.5) {
+    const ids = new Uint32Array(width * height), depth = new Float32Array(width * height);
+    addon.meshSurface(this.handle, x0 >>> 0, y0 >>> 0, width >>> 0, height >>> 0, threshold, ids, depth);
+    return { ids, depth };
+  }
+  // ... at one pixel: {splatIndex, depth, position: [x, y, z]} or null.  The position is the pixel's centre at that depth taken back
+  // through inverse(projection * viewMatrix) in fp64, with the matrices of the draw the pass reads (kept by render / renderStrip: a
+  // camera set since then does not move it).  viewMatrix is the camera's own view matrix (setCameraMatrices' fourth argument), so
+  // the position is in WORLD space whatever the mesh's model matrix is; a caller that never passed one gets the space of its modelView.
+  surfaceAt(x, y, threshold = 0.5) {
+    const d = this._drawn;
+    if (!d) return null;
+    const { ids, depth } = this.surface(x, y, 1, 1, threshold);
+    if (ids[0] === 0xFFFFFFFF) return null;
+    const m = invert4(multiply4(d.proj, d.viewMatrix));
+    const n = [2 * (x + 0.5) / d.width - 1, 2 * (y + 0.5) / d.height - 1, 2 * depth[0] - 1, 1];
+    const p = [0, 1, 2, 3].map((r) => m[r] * n[0] + m[4 + r] * n[1] + m[8 + r] * n[2] + m[12 + r] * n[3]);
+    return { splatIndex: ids[0], depth: depth[0], position: [p[0] / p[3], p[1] / p[3], p[2] / p[3]] };
+  }
+  // the camera of the draw just enqueued, for surfaceAt
+  _keepDrawn(c) { this._drawn = { proj: Array.from(c.proj), viewMatrix: Array.from(c.viewMatrix), width: c.width, height: c.height }; }
   dispose() { if (this.handle) { addon.meshDestroy(this.handle); this.handle = null; } }
+}
+
+// column-major 4x4 helpers of surfaceAt (fp64)
+function multiply4(a, b) {
+  const o = new Array(16);
+  for (let c = 0; c < 4; c++) for (let r = 0; r < 4; r++) o[4 * c + r] = a[r] * b[4 * c] + a[4 + r] * b[4 * c + 1] + a[8 + r] * b[4 * c + 2] + a[12 + r] * b[4 * c + 3];
+  return o;
+}
+function invert4(m) {                                       // Gauss-Jordan with partial pivoting
+  const a = [];
+  for (let r = 0; r < 4; r++) { a.push([m[r], m[4 + r], m[8 + r], m[12 + r], 0, 0, 0, 0]); a[r][4 + r] = 1; }
+  for (let c = 0; c < 4; c++) {
+    let p = c;
+    for (let r = c + 1; r < 4; r++) if (Math.abs(a[r][c]) > Math.abs(a[p][c])) p = r;
+    [a[c], a[p]] = [a[p], a[c]];
+    const d = a[c][c];
+    for (let k = 0; k < 8; k++) a[c][k] /= d;
+    for (let r = 0; r < 4; r++) {
+      if (r === c) continue;
+      const f = a[r][c];
+      for (let k = 0; k < 8; k++) a[r][k] -= f * a[c][k];
+    }
+  }
+  const o = new Array(16);
+  for (let c = 0; c < 4; c++) for (let r = 0; r < 4; r++) o[4 * c + r] = a[r][4 + c];
+  return o;
 }
 
 // The strip gather of a multi-GPU draw (gs_group_*: RCCL behind the C ABI).  StripGroup.uniqueId() on one rank, the 128 bytes
@@ -348,4 +400,4 @@ const assetFormatOf = (fileName, bytes) => {
   if (/\.spz$/i.test(fileName) || (bytes[0] === 0x1f && bytes[1] === 0x8b)) return AssetFormat.spz;
   return bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? AssetFormat.ply : AssetFormat.ksplat;      // "ply"
 };
-module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon };
+module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon, multiply4, invert4 };

@@ -893,6 +893,23 @@ static napi_value MeshSetDestination(napi_env env, napi_callback_info info) {
     if (st < 0) return throw_gs(env, st);
     return NULL;
 }
+/* meshSurface(mesh, x0, y0, width, height, threshold, ids Uint32Array|null, depth Float32Array|null): the surface pass over a window of
+ * the last draw (gs_mesh_surface): per pixel the splat at which the transmittance falls to `threshold` (0xFFFFFFFF = none) and the
+ * window depth of its centre (1 = none), row-major from y0 upwards */
+static napi_value MeshSurface(napi_env env, napi_callback_info info) {
+    ARGS(8)
+    void *ids, *depth;
+    size_t ib, db;
+    if (!get_bytes(env, argv[6], &ids, &ib) || !get_bytes(env, argv[7], &depth, &db)) { napi_throw_type_error(env, NULL, "meshSurface: bad buffer"); return NULL; }
+    const uint32_t w = get_u32(env, argv[3]), h = get_u32(env, argv[4]);
+    const size_t px = (size_t)w * h;
+    if ((ids && ib < px * 4) || (depth && db < px * 4)) { napi_throw_range_error(env, NULL, "meshSurface: buffer shorter than width * height"); return NULL; }
+    int st;
+    LOCKED(st = gs_mesh_surface((gs_mesh*)get_external(env, argv[0]), get_u32(env, argv[1]), get_u32(env, argv[2]), w, h, (float)get_f64(env, argv[5]),
+                             (uint32_t*)ids, (float*)depth, NULL, NULL));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
 static napi_value Init(napi_env env, napi_value exports) {
     addon_state* state = (addon_state*)calloc(1, sizeof *state);
     if (!state || pthread_mutex_init(&state->lock, NULL) != 0 || napi_set_instance_data(env, state, state_free, NULL) != napi_ok) {
@@ -915,6 +932,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
         {"meshUploadAsset", MeshUploadAsset}, {"sorterUploadAssetCenters", SorterUploadAssetCenters},
+        {"meshSurface", MeshSurface},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
