@@ -169,7 +169,7 @@ def _depth_pass(draw, splats, px, py):
     return z[:, None] <= d[None, :]
 
 
-def bin_transmittances(draw, bin_x, bin_y, px, py, smap=None):
+def bin_transmittances(draw, bin_x, bin_y, px, py, smap=None, eta=ETA):
     """For the pixels (px, py) - all inside the 32-px bin (bin_x, bin_y) - the bin's candidate entries and both transmittances.
     Returns (splats uint32 [m] in list order, could_keep bool [m, p], T_lo, T_hi float64 [m, p])."""
     smap = draw.splat_of_slot() if smap is None else smap
@@ -190,8 +190,8 @@ def bin_transmittances(draw, bin_x, bin_y, px, py, smap=None):
     recs = draw.recs[splats]
     pw = power64(recs, px, py)
     a = np.exp2(-pw) * alpha64(recs)[:, None]
-    could = cover & (pw < CUT + ETA)
-    sure = cover & (pw < CUT - ETA)
+    could = cover & (pw < CUT + eta)
+    sure = cover & (pw < CUT - eta)
     T_lo = np.cumprod(np.where(could, 1.0 - a, 1.0), axis=0)
     T_hi = np.cumprod(np.where(sure, 1.0 - a, 1.0), axis=0)
     return splats, could, T_lo, T_hi
@@ -206,8 +206,9 @@ def valid_answers(splats, could, T_lo, T_hi, tau, delta=DELTA):
     return ok, none_ok
 
 
-def check_window(draw, x0, y0, ids, depth, tau, depth_tol=DEPTH_TOL):
-    """Every pixel of the window against the model.  Returns a list of complaints (empty = every pixel valid)."""
+def check_window(draw, x0, y0, ids, depth, tau, depth_tol=DEPTH_TOL, eta=ETA):
+    """Every pixel of the window against the model.  Returns a list of complaints (empty = every pixel valid).  `eta`: the band
+    around the cut in which a fragment may go either way, for scenes measured to need more than ETA (quadrant_ref.BAND)."""
     ids = np.asarray(ids)
     h, w = ids.shape
     bad = []
@@ -217,7 +218,7 @@ def check_window(draw, x0, y0, ids, depth, tau, depth_tol=DEPTH_TOL):
             ys = np.arange(max(y0, bin_y * BIN), min(y0 + h, bin_y * BIN + BIN))
             xs = np.arange(max(x0, bin_x * BIN), min(x0 + w, bin_x * BIN + BIN))
             py, px = (a.ravel() for a in np.meshgrid(ys, xs, indexing="ij"))
-            splats, could, T_lo, T_hi = bin_transmittances(draw, bin_x, bin_y, px, py, smap)
+            splats, could, T_lo, T_hi = bin_transmittances(draw, bin_x, bin_y, px, py, smap, eta)
             ok, none_ok = valid_answers(splats, could, T_lo, T_hi, tau)
             got = ids[py - y0, px - x0]
             gz = np.asarray(depth)[py - y0, px - x0]
