@@ -191,6 +191,18 @@ struct RadixScratch {
     }
 };
 
+// Inclusive scan over the 64 lanes of a wave (Hillis-Steele, six shuffles), for a 32-bit count or a packed 64-bit pair of them.
+// The project's one spelling of it; radix.hpp's wave_incl_scan_dpp is the same sum on the DPP network, used where it was measured.
+template <class T>
+__device__ __forceinline__ T wave_incl_scan(T v, uint32_t lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if ((int)lane >= o) v += t;
+    }
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------------

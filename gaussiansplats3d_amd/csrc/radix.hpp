@@ -16,6 +16,10 @@
 // tiles), the table has <= RADIX_MAX_BLOCKS rows whatever N is, and N may live in device memory (the tile-entry count and
 // the length of a frustum-culled list only exist on the device).
 //
+// The two scatter kernels differ in how keys leave the CU; what they share is said once: ScatterTile::fetch (a tile's loads as
+// two branch-free batches), scatter_offsets (the sums over the two-level table and the scan of the digit totals) and rank_tile
+// (below).  radix_launch is the one host-side sequence histogram -> scatter behind radix_pass, radix_pass_ex and radix_pass_chunk.
+//
 // Ranking inside a tile is wave64-native.  Fast path (ATOMIC_RANK): one `ds_add_rtn_u32` on a per-wave LDS
 // histogram per key.  gfx950's LDS serves the lanes of ONE wave instruction that hit the same address in ascending
 // lane order (tools/probes/lds_atomic_order.hip: 0 mismatches in 3.3e9 checks; re-verified by a self-test at
@@ -24,6 +28,7 @@
 // lower lanes + the per-wave counter.  Keys are then reordered through LDS so that every digit's run leaves the
 // CU as contiguous stores.
 #pragma once
+#include <type_traits>
 #include "gs_internal.hpp"
 
 // ---------------------------------------------------------------------------------------------------
@@ -31,16 +36,7 @@
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(v, o, 64);
-        if ((int)lane >= o) v += t;
-    }
-    return v;
-}
-
-// The same scan on the DPP network (no LDS round trips): Hillis-Steele inside each row of 16 lanes (row_shr 1, 2, 4, 8: a lane
+// wave_incl_scan (gs_internal.hpp) on the DPP network (no LDS round trips): Hillis-Steele inside each row of 16 lanes (row_shr 1, 2, 4, 8: a lane
 // whose source falls outside its row adds 0), then lane 15 of row r into row r + 1 (rows 1 and 3), then lane 31 into rows 2 and 3.
 __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
@@ -276,6 +272,129 @@ __global__ __launch_bounds__(HIST_THREADS) void k_radix_hist(Loader ld, int shif
     if (total) atomicAdd(&digit_total[(ch.id / RADIX_GROUP) * RADIX_BINS + tid], total);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// what the two scatter kernels share: a tile's loads, the offset prologue, the ranking
+// ---------------------------------------------------------------------------------------------------
+// One lane's ITEMS elements of a tile, as they come from memory.
+template <class Loader, int ITEMS>
+struct ScatterTile {
+    typename Loader::Raw raw[ITEMS];
+    uint32_t okm = 0;                                       // bit r: element r of this lane exists (and survives the loader)
+    // wave-striped load: the stable order inside a tile is (wave, r, lane).  All memory reads first, then the arithmetic.
+    // Branch-free: an element beyond the list re-reads the last one (its okm bit stays clear), so the eight loads of a lane are
+    // one batch behind one wait instead of eight exec-masked branches.
+    __device__ __forceinline__ void fetch(const Loader& ld, uint32_t tile, uint32_t n, uint32_t wave, uint32_t lane) {
+        const uint32_t wbase = tile * RADIX_TILE + wave * (64 * ITEMS) + lane;
+        uint32_t o[ITEMS];
+        okm = 0;
+#pragma unroll
+        for (int r = 0; r < ITEMS; r++) {
+            const uint32_t j = wbase + r * 64;
+            const bool in = j < n;
+            const uint32_t jc = in ? j : n - 1u;
+            const bool ok = in && ld.valid(jc);              // a loader that drops elements turns the pass into a stable compaction
+            o[r] = ld.pre(jc);
+            okm |= ok ? (1u << r) : 0u;
+        }
+#pragma unroll
+        for (int r = 0; r < ITEMS; r++) {
+            const uint32_t j = wbase + r * 64;
+            raw[r] = ld.fetch(j < n ? j : n - 1u, o[r]);
+        }
+    }
+};
+
+// The offset prologue of a THREADS-thread scatter workgroup.  For digit d = threadIdx.x (< 256): `tot` = keys of digit d in the
+// whole list, `smaller` = keys with a smaller digit, `mine` = keys of digit d in earlier workgroups; so smaller + mine is this
+// workgroup's first output slot of digit d.  THREADS / 256 threads per digit split the rows, every load is independent of the
+// others.  s_wave ([THREADS / 64][256], free until the tile loop uses it) carries the partial sums, s_tmp (>= THREADS / 64) the
+// scan; two barriers after the exchange, so both are free on return.
+struct ScatterOffsets {
+    uint32_t tot, smaller, mine;
+};
+template <int THREADS>
+__device__ __forceinline__ ScatterOffsets scatter_offsets(const RadixChunk& ch, const uint32_t* __restrict__ block_hist,
+                                                          const uint32_t* __restrict__ group_hist, uint32_t* s_wave, uint32_t* s_tmp,
+                                                          uint32_t* __restrict__ count_out) {
+    constexpr int WAVES = THREADS / 64, PARTS = THREADS / RADIX_BINS;      // PARTS = threads per digit
+    static_assert(THREADS % RADIX_BINS == 0 && 2 * PARTS <= WAVES, "offset prologue layout");
+    const uint32_t tid = threadIdx.x, d = tid & 255u, part = tid >> 8;     // `part` = which of the PARTS row subsets
+    const uint32_t g = ch.id / RADIX_GROUP, groups = (gridDim.x + RADIX_GROUP - 1) / RADIX_GROUP;
+    uint32_t before = 0, all = 0;
+    // batches of 8 independent loads (clamped rows + selects: no exec-masked branch per load); two to four round trips to L2
+    for (uint32_t r0 = part; r0 < groups; r0 += 8u * PARTS) {
+        uint32_t v[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(group_hist, min(r0 + k * PARTS, groups - 1u) * RADIX_BINS + d);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) {
+            const uint32_t r = r0 + k * PARTS;
+            all += r < groups ? v[k] : 0u;
+            before += r < g ? v[k] : 0u;
+        }
+    }
+    for (uint32_t r0 = g * RADIX_GROUP + part; r0 < ch.id; r0 += 8u * PARTS) {
+        uint32_t v[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(block_hist, min(r0 + k * PARTS, ch.id) * RADIX_BINS + d);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) before += (r0 + k * PARTS) < ch.id ? v[k] : 0u;
+    }
+    uint32_t* s_before = s_wave;                             // [PARTS][256]
+    uint32_t* s_all = s_wave + PARTS * RADIX_BINS;
+    s_before[tid] = before;
+    s_all[tid] = all;
+    __syncthreads();
+    ScatterOffsets o = {0u, 0u, 0u};
+    if (tid < RADIX_BINS) {
+#pragma unroll
+        for (int q = 0; q < PARTS; q++) {
+            o.tot += s_all[q * RADIX_BINS + tid];
+            o.mine += s_before[q * RADIX_BINS + tid];
+        }
+    }
+    uint32_t n_valid;
+    o.smaller = block_excl_scan<WAVES>(o.tot, s_tmp, &n_valid);
+    // a compacting pass (a loader that drops elements) publishes how many it keeps: the sum of its digit totals - one plain
+    // store, where one atomicAdd per workgroup of the key kernel on a single word cost ~12 ns each (25 us for 2048 of them)
+    if (count_out && blockIdx.x == 0 && tid == 0) *count_out = n_valid;
+    return o;
+}
+
+// Ranks of one lane's ITEMS keys among the equal digits its wave has seen in this tile (see the header).  `row` = the wave's own
+// row of digit counts, which only this wave zeroes and increments.  (Two loops, not one with the switch inside: the compiler
+// allocates the tile kernel's registers differently for the latter.)
+template <bool ATOMIC_RANK, int ITEMS>
+__device__ __forceinline__ void rank_tile(const uint32_t (&dg)[ITEMS], uint32_t okm, uint32_t* row, uint32_t lane, uint32_t (&rk)[ITEMS]) {
+    if (ATOMIC_RANK) {
+#pragma unroll
+        for (int r = 0; r < ITEMS; r++) {
+            // lanes of this instruction that share dg[r] are served in ascending lane order
+            rk[r] = 0u;
+            if ((okm >> r) & 1u) rk[r] = atomicAdd(&row[dg[r]], 1u);
+        }
+    } else {
+        const uint64_t lt_mask = (1ull << lane) - 1ull;
+        volatile uint32_t* my_hist = row;
+#pragma unroll
+        for (int r = 0; r < ITEMS; r++) {
+            const uint32_t digit = dg[r];
+            const bool ok = (okm >> r) & 1u;
+            uint64_t same = __ballot(ok);
+#pragma unroll
+            for (int bit = 0; bit < 8; bit++) {
+                const uint64_t vote = __ballot(ok && ((digit >> bit) & 1u));
+                same &= ((digit >> bit) & 1u) ? vote : ~vote;
+            }
+            rk[r] = 0u;
+            if (ok) {
+                const uint32_t prior = my_hist[digit];
+                rk[r] = prior + __popcll(same & lt_mask);
+                if ((same >> lane) == 1ull) my_hist[digit] = prior + __popcll(same);   // highest lane of the group
+            }
+        }
+    }
+}
 
 // One scatter pass.  Template switches:
 //   WRITE_KEYS  also emit the keys (every pass but the last of a key + value sort).
@@ -308,8 +427,6 @@ __global__ __launch_bounds__(HIST_THREADS) void k_radix_hist(Loader ld, int shif
 constexpr int SCATTER_THREADS = SCATTER_THREADS_CFG;
 constexpr int SCATTER_WAVES = SCATTER_THREADS / 64;
 constexpr int SCATTER_ITEMS = RADIX_TILE / SCATTER_THREADS;
-constexpr int SCATTER_PARTS = SCATTER_THREADS / RADIX_BINS;     // threads per digit in the offset prologue
-static_assert(SCATTER_THREADS % RADIX_BINS == 0 && 2 * SCATTER_PARTS <= SCATTER_WAVES, "offset prologue layout");
 static_assert(SCATTER_ITEMS * SCATTER_THREADS == RADIX_TILE && SCATTER_ITEMS <= 32, "tile layout");
 
 #ifdef GS_RADIX_PROFILE
@@ -348,84 +465,18 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
     // stays: it publishes the ranges / the kept count even of an empty list)
     if (ch.tile_begin >= ch.tile_end && blockIdx.x != 0) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    volatile uint32_t* my_hist = s_wave[wave];
     const int dshift = PACK_OUT ? 0 : shift;                // the staged key of a packing pass IS the digit
 
-    uint32_t okm = 0;                                       // bit r: element r of this lane exists (and survives the loader)
-    typename Loader::Raw raw[SCATTER_ITEMS];
-    // wave-striped load: the stable order inside a tile is (wave, r, lane).  All memory reads first, then the arithmetic.
-    // Branch-free: an element beyond the list re-reads the last one (its okm bit stays clear), so the eight loads of a lane are
-    // one batch behind one wait instead of eight exec-masked branches.
-    auto fetch_tile = [&](uint32_t tile) {
-        const uint32_t wbase = tile * RADIX_TILE + wave * (64 * SCATTER_ITEMS) + lane;
-        uint32_t o[SCATTER_ITEMS];
-        okm = 0;
-#pragma unroll
-        for (int r = 0; r < SCATTER_ITEMS; r++) {
-            const uint32_t j = wbase + r * 64;
-            const bool in = j < ch.n;
-            const uint32_t jc = in ? j : ch.n - 1u;
-            const bool ok = in && ld.valid(jc);              // a loader that drops elements turns the pass into a stable compaction
-            o[r] = ld.pre(jc);
-            okm |= ok ? (1u << r) : 0u;
-        }
-#pragma unroll
-        for (int r = 0; r < SCATTER_ITEMS; r++) {
-            const uint32_t j = wbase + r * 64;
-            raw[r] = ld.fetch(j < ch.n ? j : ch.n - 1u, o[r]);
-        }
-    };
-
-    {   // this workgroup's first output slot per digit = keys with a smaller digit + keys of this digit in earlier
-        // workgroups; SCATTER_PARTS threads per digit split the rows, every load is independent of the others
-        const uint32_t d = tid & 255u, half = tid >> 8;      // `half` = which of the SCATTER_PARTS row subsets
-        const uint32_t g = ch.id / RADIX_GROUP, groups = (gridDim.x + RADIX_GROUP - 1) / RADIX_GROUP;
-        uint32_t before = 0, all = 0;
-        if (ch.tile_begin < ch.tile_end) fetch_tile(ch.tile_begin);      // the first tile travels with the table rows
-        // batches of 8 independent loads (clamped rows + selects: no exec-masked branch per load); two to four round trips to L2
-        for (uint32_t r0 = half; r0 < groups; r0 += 8u * SCATTER_PARTS) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(group_hist, min(r0 + k * SCATTER_PARTS, groups - 1u) * RADIX_BINS + d);
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) {
-                const uint32_t r = r0 + k * SCATTER_PARTS;
-                all += r < groups ? v[k] : 0u;
-                before += r < g ? v[k] : 0u;
-            }
-        }
-        for (uint32_t r0 = g * RADIX_GROUP + half; r0 < ch.id; r0 += 8u * SCATTER_PARTS) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(block_hist, min(r0 + k * SCATTER_PARTS, ch.id) * RADIX_BINS + d);
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) before += (r0 + k * SCATTER_PARTS) < ch.id ? v[k] : 0u;
-        }
-        uint32_t* s_before = &s_wave[0][0];                  // [PARTS][256], free until the tile loop uses it
-        uint32_t* s_all = &s_wave[SCATTER_PARTS][0];
-        s_before[tid] = before;
-        s_all[tid] = all;
-        __syncthreads();
-        uint32_t tot = 0, mine = 0;
-        if (tid < RADIX_BINS) {
-#pragma unroll
-            for (int q = 0; q < SCATTER_PARTS; q++) {
-                tot += s_all[q * RADIX_BINS + tid];
-                mine += s_before[q * RADIX_BINS + tid];
-            }
-        }
-        uint32_t n_valid;
-        const uint32_t smaller = block_excl_scan<SCATTER_WAVES>(tot, s_tmp, &n_valid);    // (two barriers: s_wave is free after it)
-        if (tid < RADIX_BINS) s_base[tid] = smaller + mine;  // (read after barrier (1) of the first tile)
-        // a compacting pass (a loader that drops elements) publishes how many it keeps: the sum of its digit totals - one plain
-        // store, where one atomicAdd per workgroup of the key kernel on a single word cost ~12 ns each (25 us for 2048 of them)
-        if (count_out && blockIdx.x == 0 && tid == 0) *count_out = n_valid;
+    ScatterTile<Loader, SCATTER_ITEMS> tl;
+    if (ch.tile_begin < ch.tile_end) tl.fetch(ld, ch.tile_begin, ch.n, wave, lane);     // the first tile travels with the table rows
+    {
+        const ScatterOffsets so = scatter_offsets<SCATTER_THREADS>(ch, block_hist, group_hist, &s_wave[0][0], s_tmp, count_out);
+        if (tid < RADIX_BINS) s_base[tid] = so.smaller + so.mine;       // (read after barrier (1) of the first tile)
         // A single-pass sort's digit IS the key, so key d ends up in [smaller, smaller + tot): workgroup 0 publishes the
         // ranges of the first `direct_ranges` keys with plain stores.  (The RANGES path's atomicMin / atomicMax pairs all
         // land on ~9 cache lines when there are only 135 keys: 100 us for the 1080p entry sort instead of 30.)
         if (direct_ranges && blockIdx.x == 0 && tid < direct_ranges)
-            ranges[tid] = tot ? make_uint2(smaller, smaller + tot) : make_uint2(0xFFFFFFFFu, 0u);
+            ranges[tid] = so.tot ? make_uint2(so.smaller, so.smaller + so.tot) : make_uint2(0xFFFFFFFFu, 0u);
     }
     // every wave zeroes, increments and (after the scan) reads only ITS OWN row of s_wave
     *reinterpret_cast<uint4*>(&s_wave[wave][4 * lane]) = make_uint4(0u, 0u, 0u, 0u);
@@ -440,7 +491,7 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
 #pragma unroll
         for (int r = 0; r < SCATTER_ITEMS; r++) {
             uint32_t k = 0xFFFFFFFFu, v = 0u;
-            ld.decode(raw[r], k, v);
+            ld.decode(tl.raw[r], k, v);
             if (PACK_OUT) {
                 a[r] = ((k >> (shift + 8)) << val_bits) | v;
                 b[r] = (k >> shift) & 255u;
@@ -452,32 +503,11 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
         RADIX_PROF_WAIT();
         if (prof_tile) RADIX_PROF(2, wall_clock64());
 
-        if (ATOMIC_RANK) {
+        {
+            uint32_t dg[SCATTER_ITEMS];
 #pragma unroll
-            for (int r = 0; r < SCATTER_ITEMS; r++) {
-                const uint32_t digit = (b[r] >> dshift) & 255u;
-                // lanes of this instruction that share `digit` are served in ascending lane order (see header)
-                rk[r] = 0u;
-                if ((okm >> r) & 1u) rk[r] = atomicAdd(&s_wave[wave][digit], 1u);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < SCATTER_ITEMS; r++) {
-                const uint32_t digit = (b[r] >> dshift) & 255u;
-                const bool ok = (okm >> r) & 1u;
-                uint64_t same = __ballot(ok);
-#pragma unroll
-                for (int bit = 0; bit < 8; bit++) {
-                    const uint64_t vote = __ballot(ok && ((digit >> bit) & 1u));
-                    same &= ((digit >> bit) & 1u) ? vote : ~vote;
-                }
-                rk[r] = 0u;
-                if (ok) {
-                    const uint32_t prior = my_hist[digit];
-                    rk[r] = prior + __popcll(same & lt_mask);
-                    if ((same >> lane) == 1ull) my_hist[digit] = prior + __popcll(same);   // highest lane of the group
-                }
-            }
+            for (int r = 0; r < SCATTER_ITEMS; r++) dg[r] = (b[r] >> dshift) & 255u;
+            rank_tile<ATOMIC_RANK>(dg, tl.okm, s_wave[wave], lane, rk);
         }
         __syncthreads();                                     // (1) every wave's digit counts are final
         if (prof_tile) RADIX_PROF(3, wall_clock64());
@@ -517,7 +547,7 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
         if (prof_tile) RADIX_PROF(4, wall_clock64());
 #pragma unroll
         for (int r = 0; r < SCATTER_ITEMS; r++) {
-            if ((okm >> r) & 1u) {
+            if ((tl.okm >> r) & 1u) {
                 const uint32_t digit = (b[r] >> dshift) & 255u;
                 const uint32_t pos = s_wave[wave][digit] + rk[r];
                 s_keys[pos] = (KeyOutT)b[r];
@@ -525,8 +555,8 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
             }
         }
         // the registers are free: the next tile's reads travel while this one is stored
-        okm = 0;
-        if (tile + 1 < ch.tile_end) fetch_tile(tile + 1);
+        tl.okm = 0;
+        if (tile + 1 < ch.tile_end) tl.fetch(ld, tile + 1, ch.n, wave, lane);
         __syncthreads();                                     // (3)
         if (prof_tile) RADIX_PROF(5, wall_clock64());
         *reinterpret_cast<uint4*>(&s_wave[wave][4 * lane]) = make_uint4(0u, 0u, 0u, 0u);   // own row, read for the last time above
@@ -598,13 +628,11 @@ constexpr int CHUNK_TILES = CHUNK_TILES_CFG;
 constexpr int CHUNK_THREADS = CHUNK_THREADS_CFG;
 constexpr int CHUNK_WAVES = CHUNK_THREADS / 64;
 constexpr int CHUNK_ITEMS = RADIX_TILE / CHUNK_THREADS;
-constexpr int CHUNK_PARTS = CHUNK_THREADS / RADIX_BINS;
 constexpr int CHUNK_KEYS = CHUNK_TILES * RADIX_TILE;
 #ifndef CHUNK_TARGET_BLOCKS_CFG
 #define CHUNK_TARGET_BLOCKS_CFG 512
 #endif
 constexpr int CHUNK_TARGET_BLOCKS = CHUNK_TARGET_BLOCKS_CFG;                   // two workgroups per CU: the chunk length aims at this many of them
-static_assert(CHUNK_THREADS % RADIX_BINS == 0 && 2 * CHUNK_PARTS <= CHUNK_WAVES, "offset prologue layout");
 
 inline uint32_t radix_chunk_grid_for(uint32_t n_upper) {    // 0: too long for chunk-sized workgroups (the tile kernel takes it)
     uint32_t tiles = (n_upper + RADIX_TILE - 1) / RADIX_TILE;
@@ -632,80 +660,22 @@ __global__ __launch_bounds__(CHUNK_THREADS, CHUNK_OCC_CFG) void k_radix_scatter_
     const RadixChunk ch = radix_chunk(ld.count());
     if (ch.tile_begin >= ch.tile_end && blockIdx.x != 0) return;        // (no tile: see k_radix_scatter)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    volatile uint32_t* my_hist = s_wave[wave];
 
-    uint32_t okm = 0;
-    typename Loader::Raw raw[CHUNK_ITEMS];
-    auto fetch_tile = [&](uint32_t tile) {
-        const uint32_t wbase = tile * RADIX_TILE + wave * (64 * CHUNK_ITEMS) + lane;
-        uint32_t o[CHUNK_ITEMS];
-        okm = 0;
-#pragma unroll
-        for (int r = 0; r < CHUNK_ITEMS; r++) {
-            const uint32_t j = wbase + r * 64;
-            const bool in = j < ch.n;
-            const uint32_t jc = in ? j : ch.n - 1u;
-            const bool ok = in && ld.valid(jc);
-            o[r] = ld.pre(jc);
-            okm |= ok ? (1u << r) : 0u;
-        }
-#pragma unroll
-        for (int r = 0; r < CHUNK_ITEMS; r++) {
-            const uint32_t j = wbase + r * 64;
-            raw[r] = ld.fetch(j < ch.n ? j : ch.n - 1u, o[r]);
-        }
-    };
-    if (ch.tile_begin < ch.tile_end) fetch_tile(ch.tile_begin);         // travels with the table rows below
+    ScatterTile<Loader, CHUNK_ITEMS> tl;
+    if (ch.tile_begin < ch.tile_end) tl.fetch(ld, ch.tile_begin, ch.n, wave, lane);     // travels with the table rows below
 
     uint32_t chunk_count = 0;
-    {   // global slot of this chunk's first key of every digit = keys with a smaller digit + keys of the digit in earlier chunks
-        const uint32_t d = tid & 255u, part = tid >> 8;
-        const uint32_t g = ch.id / RADIX_GROUP, groups = (gridDim.x + RADIX_GROUP - 1) / RADIX_GROUP;
-        uint32_t before = 0, all = 0;
-        // batches of 8 independent loads (clamped rows + selects: no exec-masked branch per load); two to four round trips to L2
-        for (uint32_t r0 = part; r0 < groups; r0 += 8u * CHUNK_PARTS) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(group_hist, min(r0 + k * CHUNK_PARTS, groups - 1u) * RADIX_BINS + d);
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) {
-                const uint32_t r = r0 + k * CHUNK_PARTS;
-                all += r < groups ? v[k] : 0u;
-                before += r < g ? v[k] : 0u;
-            }
-        }
-        for (uint32_t r0 = g * RADIX_GROUP + part; r0 < ch.id; r0 += 8u * CHUNK_PARTS) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) v[k] = ld32(block_hist, min(r0 + k * CHUNK_PARTS, ch.id) * RADIX_BINS + d);
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; k++) before += (r0 + k * CHUNK_PARTS) < ch.id ? v[k] : 0u;
-        }
-        // this chunk's keys of digit d.  A workgroup WITHOUT tiles (only workgroup 0 of an empty list gets here) has no row: the
+    {   // global slot of this chunk's first key of every digit = the prologue's smaller + mine; its first staging slot = a scan
+        // of this chunk's own row.  A workgroup WITHOUT tiles (only workgroup 0 of an empty list gets here) has no row: the
         // histogram kernel wrote none for it, and row 0 still holds the previous sort's counts - reading it made the final sweep
-        // store that many never-written staging words through s_gbase of a zero table
-        const uint32_t own = (tid < RADIX_BINS && ch.tile_begin < ch.tile_end) ? ld32(block_hist, ch.id * RADIX_BINS + d) : 0u;
-        uint32_t* s_before = &s_wave[0][0];                  // [PARTS][256], free until the tile loop uses it
-        uint32_t* s_all = &s_wave[CHUNK_PARTS][0];
-        s_before[tid] = before;
-        s_all[tid] = all;
-        __syncthreads();
-        uint32_t tot = 0, mine = 0;
-        if (tid < RADIX_BINS) {
-#pragma unroll
-            for (int q = 0; q < CHUNK_PARTS; q++) {
-                tot += s_all[q * RADIX_BINS + tid];
-                mine += s_before[q * RADIX_BINS + tid];
-            }
-        }
-        uint32_t n_valid;
-        const uint32_t smaller = block_excl_scan<CHUNK_WAVES>(tot, s_tmp, &n_valid);
-        if (count_out && blockIdx.x == 0 && tid == 0) *count_out = n_valid;              // (see k_radix_scatter)
+        // store that many never-written staging words through s_gbase of a zero table.  (Read ahead of the
+        // prologue's rows: it is wanted after the prologue's barriers.)
+        const uint32_t own = (tid < RADIX_BINS && ch.tile_begin < ch.tile_end) ? ld32(block_hist, ch.id * RADIX_BINS + tid) : 0u;
+        const ScatterOffsets so = scatter_offsets<CHUNK_THREADS>(ch, block_hist, group_hist, &s_wave[0][0], s_tmp, count_out);
         const uint32_t first = block_excl_scan<CHUNK_WAVES>(own, s_tmp, &chunk_count);   // first staging slot of digit d
         if (tid < RADIX_BINS) {
             s_run[tid] = first;
-            s_gbase[tid] = smaller + mine - first;
+            s_gbase[tid] = so.smaller + so.mine - first;
         }
     }
     *reinterpret_cast<uint4*>(&s_wave[wave][4 * lane]) = make_uint4(0u, 0u, 0u, 0u);    // every wave zeroes and increments only its own row
@@ -715,35 +685,11 @@ __global__ __launch_bounds__(CHUNK_THREADS, CHUNK_OCC_CFG) void k_radix_scatter_
 #pragma unroll
         for (int r = 0; r < CHUNK_ITEMS; r++) {
             uint32_t k = 0xFFFFFFFFu, v = 0u;
-            ld.decode(raw[r], k, v);
+            ld.decode(tl.raw[r], k, v);
             dg[r] = (k >> shift) & 255u;
             a[r] = PACK_OUT ? (((k >> (shift + 8)) << val_bits) | v) : ((dg[r] << 24) | v);
         }
-        if (ATOMIC_RANK) {
-#pragma unroll
-            for (int r = 0; r < CHUNK_ITEMS; r++) {
-                rk[r] = 0u;
-                if ((okm >> r) & 1u) rk[r] = atomicAdd(&s_wave[wave][dg[r]], 1u);   // same-digit lanes are served in lane order (header)
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < CHUNK_ITEMS; r++) {
-                const uint32_t digit = dg[r];
-                const bool ok = (okm >> r) & 1u;
-                uint64_t same = __ballot(ok);
-#pragma unroll
-                for (int bit = 0; bit < 8; bit++) {
-                    const uint64_t vote = __ballot(ok && ((digit >> bit) & 1u));
-                    same &= ((digit >> bit) & 1u) ? vote : ~vote;
-                }
-                rk[r] = 0u;
-                if (ok) {
-                    const uint32_t prior = my_hist[digit];
-                    rk[r] = prior + __popcll(same & lt_mask);
-                    if ((same >> lane) == 1ull) my_hist[digit] = prior + __popcll(same);
-                }
-            }
-        }
+        rank_tile<ATOMIC_RANK>(dg, tl.okm, s_wave[wave], lane, rk);
         __syncthreads();                                     // (1) every wave's counts of this tile are final
         if (tid < RADIX_BINS) {                              // thread d: counts -> first slot of (wave, d), the digit's next slot moves on
             uint32_t run = s_run[tid];
@@ -758,14 +704,14 @@ __global__ __launch_bounds__(CHUNK_THREADS, CHUNK_OCC_CFG) void k_radix_scatter_
         __syncthreads();                                     // (2)
 #pragma unroll
         for (int r = 0; r < CHUNK_ITEMS; r++) {
-            if ((okm >> r) & 1u) {
+            if ((tl.okm >> r) & 1u) {
                 const uint32_t pos = s_wave[wave][dg[r]] + rk[r];
                 s_stage[pos] = a[r];
                 if (PACK_OUT) s_digit[pos] = (uint8_t)dg[r];
             }
         }
-        okm = 0;
-        if (tile + 1 < ch.tile_end) fetch_tile(tile + 1);   // the registers are free: the next tile's reads travel meanwhile
+        tl.okm = 0;
+        if (tile + 1 < ch.tile_end) tl.fetch(ld, tile + 1, ch.n, wave, lane);   // the registers are free: the next tile's reads travel meanwhile
         *reinterpret_cast<uint4*>(&s_wave[wave][4 * lane]) = make_uint4(0u, 0u, 0u, 0u);   // own row, read for the last time above
     }
     __syncthreads();                                         // the chunk is staged
@@ -808,24 +754,30 @@ inline uint32_t radix_grid_for(uint32_t n_upper) {
     return (tiles + per - 1) / per;
 }
 
-// n_upper: host-side upper bound of the element count (sizes the grid); pass_slot picks the zeroed
-// digit_total row (the caller zeroes RadixScratch::digit_total once per frame).
+// What every pass launches: the histogram over `grid` workgroups into the scratch's rows, then `scatter(atomic_rank, bh, dt)`
+// on the same grid with ATOMIC_RANK as a compile-time bool.  pass_slot picks the zeroed digit_total row (the caller zeroes
+// RadixScratch::digit_total once per frame).
+template <class HistLoader, class Scatter>
+int radix_launch(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, uint32_t grid, int pass_slot, Scatter&& scatter) {
+    uint32_t* bh = ex.scratch->block_hist.as<uint32_t>();
+    uint32_t* dt = ex.scratch->digit_total.as<uint32_t>() + pass_slot * RADIX_MAX_GROUPS * RADIX_BINS;
+    hipLaunchKernelGGL((k_radix_hist<HistLoader>), dim3(grid), dim3(HIST_THREADS), 0, ex.stream, ld_hist, hist_shift, bh, dt);
+    if (ex.atomic_rank) scatter(std::true_type(), bh, dt);
+    else scatter(std::false_type(), bh, dt);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// n_upper: host-side upper bound of the element count (sizes the grid).
 template <class HistLoader, class Loader, class KeyOutT, bool WRITE_KEYS, bool RANGES, bool PACK_OUT>
 int radix_pass_ex(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
                   int pass_slot, KeyOutT* keys_out, uint32_t* vals_out, uint2* ranges, uint32_t direct_ranges, uint32_t val_bits,
                   uint32_t* count_out = nullptr) {
     const uint32_t grid = radix_grid_for(n_upper);
-    uint32_t* bh = ex.scratch->block_hist.as<uint32_t>();
-    uint32_t* dt = ex.scratch->digit_total.as<uint32_t>() + pass_slot * RADIX_MAX_GROUPS * RADIX_BINS;
-    hipLaunchKernelGGL((k_radix_hist<HistLoader>), dim3(grid), dim3(HIST_THREADS), 0, ex.stream, ld_hist, hist_shift, bh, dt);
-    if (ex.atomic_rank)
-        hipLaunchKernelGGL((k_radix_scatter<Loader, KeyOutT, WRITE_KEYS, RANGES, true, PACK_OUT>), dim3(grid), dim3(SCATTER_THREADS), 0,
-                           ex.stream, ld, shift, bh, dt, keys_out, vals_out, ranges, direct_ranges, val_bits, count_out);
-    else
-        hipLaunchKernelGGL((k_radix_scatter<Loader, KeyOutT, WRITE_KEYS, RANGES, false, PACK_OUT>), dim3(grid), dim3(SCATTER_THREADS), 0,
-                           ex.stream, ld, shift, bh, dt, keys_out, vals_out, ranges, direct_ranges, val_bits, count_out);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
+    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
+        hipLaunchKernelGGL((k_radix_scatter<Loader, KeyOutT, WRITE_KEYS, RANGES, decltype(atomic)::value, PACK_OUT>), dim3(grid),
+                           dim3(SCATTER_THREADS), 0, ex.stream, ld, shift, bh, dt, keys_out, vals_out, ranges, direct_ranges, val_bits, count_out);
+    });
 }
 
 // A pass of the depth sort between / after packing passes (see k_radix_scatter_chunk); the caller checked radix_chunk_grid_for.
@@ -833,15 +785,10 @@ template <class HistLoader, class Loader, bool PACK_OUT>
 int radix_pass_chunk(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
                      int pass_slot, uint32_t* out, uint32_t val_bits, uint32_t* count_out = nullptr) {
     const uint32_t grid = radix_chunk_grid_for(n_upper);
-    uint32_t* bh = ex.scratch->block_hist.as<uint32_t>();
-    uint32_t* dt = ex.scratch->digit_total.as<uint32_t>() + pass_slot * RADIX_MAX_GROUPS * RADIX_BINS;
-    hipLaunchKernelGGL((k_radix_hist<HistLoader>), dim3(grid), dim3(HIST_THREADS), 0, ex.stream, ld_hist, hist_shift, bh, dt);
-    if (ex.atomic_rank)
-        hipLaunchKernelGGL((k_radix_scatter_chunk<Loader, PACK_OUT, true>), dim3(grid), dim3(CHUNK_THREADS), 0, ex.stream, ld, shift, bh, dt, out, val_bits, count_out);
-    else
-        hipLaunchKernelGGL((k_radix_scatter_chunk<Loader, PACK_OUT, false>), dim3(grid), dim3(CHUNK_THREADS), 0, ex.stream, ld, shift, bh, dt, out, val_bits, count_out);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
+    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
+        hipLaunchKernelGGL((k_radix_scatter_chunk<Loader, PACK_OUT, decltype(atomic)::value>), dim3(grid), dim3(CHUNK_THREADS), 0,
+                           ex.stream, ld, shift, bh, dt, out, val_bits, count_out);
+    });
 }
 
 template <class Loader, class KeyOutT, bool WRITE_KEYS, bool RANGES = false>

@@ -134,12 +134,7 @@ __device__ __forceinline__ SliceCount bin_count_slice(const uint32_t* __restrict
         }
         // packed inclusive scan: high word = compacted splats, low word = tile entries (both < 2^31 per workgroup)
         const unsigned long long mine = ((unsigned long long)cnt << 32) | ent;
-        unsigned long long incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long t = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += t;
-        }
+        const unsigned long long incl = wave_incl_scan(mine, lane);
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
         unsigned long long base = 0, total = 0;
@@ -477,12 +472,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
     }
 #pragma unroll
     for (uint32_t k = 0; k < PER_T; k++) own += mine[k];
-    unsigned long long incl = own;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long t = __shfl_up(incl, o, 64);
-        if ((int)lane >= o) incl += t;
-    }
+    const unsigned long long incl = wave_incl_scan(own, lane);
     if (lane == 63u) s_wsum[wave] = incl;
     __syncthreads();
     unsigned long long run = incl - own, D64 = 0;

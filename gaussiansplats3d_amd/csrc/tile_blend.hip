@@ -664,13 +664,7 @@ __global__ __launch_bounds__(256) void k_deep_scan(FrameArgs fa, DeepArgs da) {
 __device__ __forceinline__ uint32_t deep_prefix(const DeepArgs& da, uint32_t d, uint32_t q, uint32_t n, uint32_t lane) {
     static_assert(GS_DEEP_RANGES == 64, "one lane per range");
     const uint32_t nr = (n + GS_DEEP_RLEN - 1u) / GS_DEEP_RLEN;
-    uint32_t v = lane < nr ? da.cnt[((size_t)d * GS_DEEP_RANGES + lane) * 4u + q] : 0u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(v, o, 64);
-        if ((int)lane >= o) v += t;
-    }
-    return v;
+    return wave_incl_scan(lane < nr ? da.cnt[((size_t)d * GS_DEEP_RANGES + lane) * 4u + q] : 0u, lane);
 }
 
 // The units that exist: chunk c of quadrant q of deep bin d for every c below the quadrant's chunk count (a quadrant outside
@@ -698,12 +692,7 @@ __global__ __launch_bounds__(1024) void k_deep_plan(FrameArgs fa, DeepArgs da) {
     }
     // exclusive scan over the 1024 threads (16 waves)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if ((int)lane >= o) incl += t;
-    }
+    const uint32_t incl = wave_incl_scan(mine, lane);
     if (lane == 63u) s_tmp[wave] = incl;
     __syncthreads();
     uint32_t base = incl - mine, total_units = 0;

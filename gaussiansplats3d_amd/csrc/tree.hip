@@ -510,12 +510,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_tree_scan(PlanBuffers B) {
         v[2 * k] = q.x; v[2 * k + 1] = q.y;
         sum += q.x + q.y;
     }
-    unsigned long long incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long t = __shfl_up(incl, o, 64);
-        if ((int)lane >= o) incl += t;
-    }
+    const unsigned long long incl = wave_incl_scan(sum, lane);
     if (lane == 63u) s_w[wave] = incl;
     __syncthreads();
     unsigned long long run = incl - sum, total = 0;
@@ -539,12 +534,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_tree_scan(PlanBuffers B) {
 __device__ __forceinline__ unsigned long long plan_chunk_bases(const unsigned long long* chunk_sum, unsigned long long* s_base, unsigned long long* s_w) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const unsigned long long c = chunk_sum[tid];
-    unsigned long long incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long t = __shfl_up(incl, o, 64);
-        if ((int)lane >= o) incl += t;
-    }
+    const unsigned long long incl = wave_incl_scan(c, lane);
     if (lane == 63u) s_w[wave] = incl;
     __syncthreads();
     unsigned long long base = incl - c, total = 0;

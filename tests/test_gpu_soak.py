@@ -30,8 +30,21 @@ def test_sort_modes_on_unseen_seeds(ballot):
 
 
 def test_sort_at_the_kernels_size_boundaries():
-    """tile (4096), chunk (3 tiles) and 2^24 boundaries of radix.hpp (the table's 25.2 M boundary is in the long run only)"""
+    """tile (4096) and 2^24 boundaries of radix.hpp, and one to six workgroups of ONE tile each (12288 is three such workgroups, not
+    a chunk of three tiles: up to 512 tiles every workgroup has one).  Of these sizes only those around 2^24 make a workgroup loop
+    over tiles, under the default switches; the test below does that quickly under every switch.  (The table's 25.2 M boundary is
+    in the long run only.)"""
     print(_soak("soak_sort.py", "sizes", "1,2,65,4095,4096,4097,12287,12288,12289,24577,16777215,16777216,16777217"))
+
+
+@pytest.mark.parametrize("switch", [None, "GSPLAT_NO_SORT_CHUNK", "GSPLAT_NO_SORT_PACK", "GSPLAT_NO_LDS_ATOMIC_RANK"])
+def test_sort_where_a_workgroup_walks_several_tiles(switch):
+    """The smallest sizes at which the loop over tiles inside one scatter workgroup runs at all: 2 097 153 keys are 513 tiles (two
+    per workgroup, the last chunk holds one tile of one key), 4 194 305 are 1025 (three per workgroup, the last chunk holds two).
+    The prefetch of tile t + 1 behind the reorder of tile t, the re-zeroing of a wave's own row and the staging slots carried
+    across tiles run here - under the chunk-staged, tile-at-a-time, unpacked and ballot-ranked paths (the switches are read once
+    per process: a child each)."""
+    print(_soak("soak_sort.py", "sizes", "4097,2097153,4194305", env={switch: "1"} if switch else None))
 
 
 def test_octree_rows_on_unseen_seeds():

@@ -8,7 +8,8 @@ The oracle is the checker here, as in tests/.
 
 usage: python tests/tools/soak_sort.py [iterations=200] [first_seed=100] [max_splats=300000]
        python tests/tools/soak_sort.py sizes 4095,4096,12289,...     the listed splat counts exactly (tile / chunk / table boundaries of
-                                                               radix.hpp), each as int-16, float-20 and a permuted partial sort """
+                                                               radix.hpp), each as int-16, float-20, a permuted partial sort and a
+                                                               frustum-culled sort of a permuted list """
 import os
 import sys
 import time
@@ -20,12 +21,12 @@ import numpy as np
 
 import kat_cases
 import oracle
-from gaussiansplats3d_amd import Context, create_sort_worker
+from gaussiansplats3d_amd import Context, camera, create_sort_worker, util
 
 SIZES = None
 if len(sys.argv) > 2 and sys.argv[1] == "sizes":
     SIZES = [int(v) for v in sys.argv[2].split(",")]
-    sys.argv = [sys.argv[0], str(3 * len(SIZES)), "777", "2"]
+    sys.argv = [sys.argv[0], str(4 * len(SIZES)), "777", "2"]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 max_n = int(sys.argv[3]) if len(sys.argv) > 3 else 300000
@@ -50,13 +51,38 @@ for it in range(iters):
     if kind == 4: case["offset"] = float(rng.uniform(-800.0, 800.0))
     if rng.integers(0, 2) or render < n: case["permute"] = True
     if SIZES:
-        n = SIZES[it // 3]
+        n = SIZES[it // 4]
+        # (the first three rows of a size keep the seeds they had before there was a fourth)
+        seed = seed0 + 3 * (it // 4) + it % 4 if it % 4 < 3 else seed0 + 1000 + it // 4
         case = [dict(name=f"size{n}i", n=n, render=n, sort=n, precision=16, mode="int"),
                 dict(name=f"size{n}f", n=n, render=n, sort=n, precision=20, mode="float"),
-                dict(name=f"size{n}p", n=n, render=n - n // 7, sort=n - n // 3, precision=16, mode="int", permute=True)][it % 3]
-        render, sort = case["render"], case["sort"]
+                dict(name=f"size{n}p", n=n, render=n - n // 7, sort=n - n // 3, precision=16, mode="int", permute=True),
+                dict(name=f"size{n}c", n=n, culled=True)][it % 4]
+        render, sort = case.get("render", n), case.get("sort", n)
     label = " ".join(f"{k}={v}" for k, v in case.items() if k != "name")
     try:
+        if case.get("culled"):
+            # A frustum-culled sort of a permuted list: the DepthLoaderT<true, true> loaders, a compacting pass 0 that publishes
+            # the kept count, and later passes whose length lives on the device.  Static integer centres, 16 bits.
+            rng = np.random.default_rng(seed)
+            ci = util.integer_centers((rng.normal(size=(n, 3)) * 3.0).astype(np.float32))
+            idx = rng.permutation(n).astype(np.uint32)
+            mvp = camera.demo_camera("garden", 640, 360).sort_mvp()
+            expect, keep = oracle.culled_sort(idx, ci, mvp)
+            # a case that culls nothing or everything must not pass for a compaction (the share is 0.31; the standard deviation of
+            # a sample's share is 0.46 / sqrt(n): below 0.015 from 1024 on, and anything at all for a handful of splats)
+            if n >= 1024:
+                assert 0.2 <= keep.sum() / n <= 0.5, f"the oracle keeps {keep.sum()} of {n}"
+            w = create_sort_worker(ctxs[it & 1], n, True, True, True, False, 16)
+            w.post_message({"centers": ci, "range": {"from": 0, "to": n - 1, "count": n}})
+            w.set_frustum_cull(True)
+            reply = w.post_message({"sort": {"modelViewProj": mvp, "splatRenderCount": n, "splatSortCount": n, "indexesToSort": idx}})
+            assert reply["sortDone"], "no result"
+            assert reply["stats"].result_count == len(expect), f"result_count {reply['stats'].result_count} (oracle: {len(expect)})"
+            assert np.array_equal(reply["sortedIndexes"], expect), "culled list differs from the oracle's"
+            w.terminate()
+            print(f"ok   seed {seed}: {label} kept={len(expect)}", flush=True)
+            continue
         args = kat_cases.make_case(case, seed=seed)
         kw = {k: args[k] for k in ("sort_count", "render_count", "precision", "use_int", "dynamic")}
         expect, keys, buckets, (lo, hi), st = oracle.sort_indexes(args["indexes"], args["centers4"], args["mvp"], precomputed=args["precomputed"],
