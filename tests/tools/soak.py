@@ -102,6 +102,8 @@ for it in range(iters):
                 w.sort_on_device(cam.sort_mvp(), n)
                 vis, _ = mesh.render()
                 assert np.array_equal(vis, full), "frame from the visibility-culled list differs"
+                drawn = mesh.debug_records()[2]                # the binner tests visibility again: hold the list itself too
+                assert np.array_equal(w.debug_read(2, int(drawn.sum())), expect[drawn[expect]]), "visibility-culled list differs from the oracle's restricted to what the frame draws"
                 w.set_visibility_cull(False)
                 # a destination (depth the host's own geometry left + its colour): the engine against the oracle with the same one,
                 # strips tile it; clearing it restores the plain frame
