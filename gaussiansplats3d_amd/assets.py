@@ -6,8 +6,9 @@ Reference interface: ``PlyLoader.loadFromFileData`` / ``KSplatLoader.loadFromFil
 progressive file-order path, src/loaders/spz/SpzLoader.js with ``optimizeSplatData: false``) followed by
 ``SplatMesh.fillSplatDataArrays`` (src/splatmesh/SplatMesh.js:1853-1902), with the scene's static transform when
 ``SplatAsset.set_transform`` gave one.  ``load`` returns the arrays
-``SplatMesh.build`` / the sort worker take.  ``"ply"`` covers INRIA-v1 and the PlayCanvas / SuperSplat compressed PLY (decided
-from the header); ``"splat"`` has no magic number and is chosen by ``fmt`` or a file name's extension; ``"spz"`` is a gzip
+``SplatMesh.build`` / the sort worker take.  ``"ply"`` covers INRIA-v1, the PlayCanvas / SuperSplat compressed PLY and the INRIA-v2
+codebook PLY of the "reduced 3DGS" trainer (src/loaders/ply/INRIAV2PlyParser.js, kept in file order; decided from the header);
+``"splat"`` has no magic number and is chosen by ``fmt`` or a file name's extension; ``"spz"`` is a gzip
 member (``1f 8b``), inflated by the library itself, and is chosen by ``fmt``, the extension or that magic.  The ``write_*``
 helpers produce the same file formats (used by the tests and to stage synthetic scenes as real files); they are not part
 of the reference's API surface.
@@ -197,6 +198,92 @@ def write_spz(centers, log_scales, rotations, rgba, sh=None, version=2, fraction
     rgba: floats in 0..1 [n, 4]; sh: float [n, 9|24|45] in the file order of the other writers (all R coefficients, then
     G, then B); sh_degree defaults to what ``sh`` holds."""
     return gzip.compress(spz_stream(centers, log_scales, rotations, rgba, sh, version, fractional_bits, sh_degree), 6, mtime=0)
+
+
+_PLY_NP = {"char": "i1", "uchar": "u1", "short": "<i2", "ushort": "<u2", "int": "<i4", "uint": "<u4", "float": "<f4", "double": "<f8"}
+
+
+def _codebook_page(values):
+    """256 half-float entries at the quantiles of ``values`` and, per value, the index of the nearest entry."""
+    v = np.asarray(values, np.float64).reshape(-1)
+    finite = v[np.isfinite(v)]
+    finite = finite[::max(1, finite.size >> 20)]                    # a million values place the quantiles of a large scene
+    entries = np.sort(np.quantile(finite if finite.size else np.zeros(1), (np.arange(256) + 0.5) / 256).astype(np.float16))
+    e = entries.astype(np.float64)
+    index = np.searchsorted((e[:-1] + e[1:]) / 2, np.where(np.isfinite(v), v, 0.0)).astype(np.uint8)
+    return entries, index.reshape(np.shape(values))
+
+
+def write_inria_v2_ply(centers, log_scales, rotations_wxyz, f_dc, opacity_logit, f_rest=None, codebook_first=False, half_type="short",
+                       extra_vertex=None, extra_codebook=None, field_order=None, comment=None, codebook_override=None,
+                       index_override=None):
+    """INRIA-v2 codebook PLY (src/loaders/ply/INRIAV2PlyParser.js), a quantising writer: x y z as half floats, every other
+    attribute as one uchar index into a 256-entry page of the `codebook_centers` element (half floats too; halves are stored as
+    16-bit integers of ``half_type`` "short" / "ushort", as the trainer stores them).  The pages: features_dc (the three f_dc_*
+    share it), features_rest_k (coefficient k of all three channels), opacity, scaling (log scales), rotation_re (rot_0) and
+    rotation_im (rot_1..3); each holds the quantiles of its data, and a value is coded as its nearest entry.
+    log_scales / f_dc / opacity_logit may be None: the file then lacks those fields.  f_rest: [n, 9|24|45] channel-major as the
+    trainer writes it.  codebook_first: the codebook element precedes the vertex element.  extra_vertex / extra_codebook:
+    [(type, name)] properties nothing reads.  field_order: a permutation of the vertex property names.  codebook_override:
+    {page: {entry: value}} replaces entries after the indexes were chosen, {page: None} leaves the page out; index_override:
+    {field: {row: index}}."""
+    n = centers.shape[0]
+    q = np.asarray(rotations_wxyz, np.float64)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    pages, fields = {}, [(nm, half_type, np.asarray(centers, np.float64)[:, k].astype(np.float16).view(np.uint16)) for k, nm in enumerate("xyz")]
+
+    def group(page, names, values):
+        pages[page], index = _codebook_page(values)
+        fields.extend((nm, "uchar", index[:, k]) for k, nm in enumerate(names))
+
+    if f_dc is not None:
+        group("features_dc", ["f_dc_0", "f_dc_1", "f_dc_2"], np.asarray(f_dc).reshape(n, 3))
+    else:
+        pages["features_dc"] = _codebook_page(np.zeros(1))[0]
+    if f_rest is not None:
+        rest = np.asarray(f_rest, np.float64).reshape(n, 3, -1)                      # [splat, channel, coefficient]
+        cpc = rest.shape[2]
+        at = len(fields)
+        for k in range(cpc):
+            group(f"features_rest_{k}", [f"f_rest_{k + cpc * ch}" for ch in range(3)], rest[:, :, k])
+        fields[at:] = sorted(fields[at:], key=lambda f: int(f[0][7:]))              # f_rest_0 .. f_rest_{3 cpc - 1} in the row
+    for page, names, values in (("opacity", ["opacity"], opacity_logit), ("scaling", ["scale_0", "scale_1", "scale_2"], log_scales)):
+        if values is not None:
+            group(page, names, np.asarray(values).reshape(n, len(names)))
+        else:
+            pages[page] = _codebook_page(np.zeros(1))[0]
+    group("rotation_re", ["rot_0"], q[:, :1])
+    group("rotation_im", ["rot_1", "rot_2", "rot_3"], q[:, 1:])
+    for page, edits in (codebook_override or {}).items():
+        if edits is None:
+            del pages[page]
+        else:
+            for entry, value in edits.items():
+                pages[page][entry] = value
+    for k, (typ, nm) in enumerate(extra_vertex or []):
+        fields.append((nm, typ, (np.arange(n) % 251 + k).astype(_PLY_NP[typ])))
+    if field_order is not None:
+        assert sorted(field_order) == sorted(f[0] for f in fields)
+        fields = [next(f for f in fields if f[0] == nm) for nm in field_order]
+    book = [(nm, half_type, v.view(np.uint16)) for nm, v in pages.items()]
+    for k, (typ, nm) in enumerate(extra_codebook or []):
+        book.append((nm, typ, (np.arange(256) % 251 + k).astype(_PLY_NP[typ])))
+
+    def element(name, count, props):
+        rec = np.zeros(count, dtype=[(nm, _PLY_NP[typ]) for nm, typ, _ in props])
+        for nm, typ, v in props:
+            rec[nm] = np.asarray(v).view(_PLY_NP[typ]) if typ in ("short", "ushort") else v      # half bits under either name
+        for nm, rows in (index_override or {}).items():
+            if nm in rec.dtype.names:
+                for row, value in rows.items():
+                    rec[nm][row] = value
+        return f"element {name} {count}\n" + "".join(f"property {typ} {nm}\n" for nm, typ, _ in props), rec.tobytes()
+
+    parts = [element("vertex", n, fields), element("codebook_centers", 256, book)]
+    if codebook_first:
+        parts.reverse()
+    header = "ply\nformat binary_little_endian 1.0\n" + (f"comment {comment}\n" if comment else "")
+    return (header + parts[0][0] + parts[1][0] + "end_header\n").encode() + parts[0][1] + parts[1][1]
 
 
 def pack_unit_quaternions(rotations_wxyz):

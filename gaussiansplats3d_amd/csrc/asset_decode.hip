@@ -2,8 +2,8 @@
 // mesh upload commits (gs_mesh_upload_asset) and the sorter's `centers` message (gs_sorter_upload_asset_centers).
 // The kernels take a ROW SOURCE (a template parameter, as XF is one): the .ksplat image (also an INRIA-v1 PLY's level-0
 // image; KsplatSource, the reader the host fill uses too), the 32-byte rows of a .splat, the 16-byte vertex rows + chunk rows +
-// SH bytes of a PlayCanvas compressed PLY, or the six byte planes of an inflated .spz.  The last three produce the level-0 tuple
-// in registers through asset_internal.hpp's row arithmetic - the functions the host's image builder calls - so only file rows
+// SH bytes of a PlayCanvas compressed PLY, the six byte planes of an inflated .spz, or the index rows + decoded codebook of an INRIA-v2
+// PLY.  The last four produce the level-0 tuple in registers through asset_internal.hpp's row arithmetic - the functions the host's image builder calls - so only file rows
 // cross the bus and the level-0 image is never built on this path.
 // What a thread does with its row is asset_fill_splat (asset_internal.hpp): the one body gs_asset_fill (assets.hip) loops over,
 // compiled for both sides, so the planes are bit-equal to what gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.
@@ -144,6 +144,51 @@ struct SpzSource {
     }
 };
 
+// INRIA-v2 codebook PLY: the file's rows at their own stride (17 / 26 / 41 / 62 bytes and whatever extra properties add), row 0 at the
+// staging base.  A row is one index byte per attribute and three centre halves at any byte phase, so it is read with byte loads
+// (neighbouring lanes meet in the same cache lines): no load reaches past the row, let alone into the padding behind the last one.
+// The decoded codebook (assets.hip decodes it at open) is a table of 256-float pages; k_asset_decode copies the pages its degree
+// reads into LDS first (load_table), since a splat makes up to 38 data-dependent look-ups into them; k_asset_centers reads none.
+struct InriaV2Source {
+    const uint8_t* rows;           // row 0 = asset splat `base`
+    const float* codebook;         // the decoded table: global memory (16-byte aligned) until load_table puts its LDS copy here
+    uint32_t base;
+    uint32_t level, sh_degree, ncomp;   // 0, the output degree, 0 / 9 / 24
+    InriaV2Layout layout;
+    struct Row : TupleValues {
+        const uint8_t* row;
+        const InriaV2Layout& L;
+        const float* codebook;
+        __device__ __forceinline__ float value(uint32_t src) const { return inria_v2_row_sh(row, L, codebook, src); }
+        __device__ __forceinline__ double sh_wide(uint32_t src, double, double) const { return (double)value(src); }
+        __device__ __forceinline__ uint16_t sh_half(uint32_t src) const { return to_half_three((double)value(src)); }
+        __device__ __forceinline__ uint8_t sh_byte(uint32_t) const { return 0; }   // sh_level is 1: never stored as bytes
+    };
+    __device__ __forceinline__ const uint8_t* row_of(uint32_t splat) const { return rows + (size_t)layout.stride * (splat - base); }
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        Row r = {{}, row_of(splat), layout, codebook};
+        inria_v2_row_tuple(r.row, layout, codebook, r.t);
+        return r;
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const {    // the three halves alone
+        float c[3];
+        inria_v2_row_centre(row_of(splat), layout, c);
+        for (int k = 0; k < 3; k++) d[k] = c[k];
+    }
+    // Every thread of the workgroup, the ones past the range's end too: the pages the output degree reads (a prefix of the table),
+    // as coalesced 16-byte loads, then the barrier.
+    __device__ __forceinline__ void load_table(float* lds) {
+        const uint32_t quads = 64u * inria_v2_pages_read(sh_degree);
+        for (uint32_t k = threadIdx.x; k < quads; k += 256u) reinterpret_cast<float4*>(lds)[k] = reinterpret_cast<const float4*>(codebook)[k];
+        __syncthreads();
+        codebook = lds;
+    }
+};
+
+// floats of LDS a source's workgroup fills before its threads decode (Source::load_table): the 13 pages degree 2 reads
+template <class Source> struct LdsTable { static constexpr uint32_t floats = 0; };
+template <> struct LdsTable<InriaV2Source> { static constexpr uint32_t floats = 256u * (IV2_PAGE_REST + 8u); };
+
 struct NoTransform { uint32_t none; };   // the untransformed instantiations carry no matrix in their kernel argument
 struct DevTransform {          // the transformed ones: 16 + 9 + 25 doubles and the file's 8-bit SH range, by value
     AssetTransform t;
@@ -163,6 +208,10 @@ __global__ __launch_bounds__(256) void k_asset_decode(Source v, Transform xf, ui
                                                       uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
                                                       uint16_t* __restrict__ sh_f16, uint8_t* __restrict__ sh_u8) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if constexpr (LdsTable<Source>::floats != 0) {          // before any thread leaves: the last workgroup's spare threads copy and wait too
+        __shared__ __align__(16) float table[LdsTable<Source>::floats];
+        v.load_table(table);
+    }
     if (i >= count) return;
     asset_fill_splat<XF, false>(v.row(first + i), transform_of(xf), v.sh_degree, v.ncomp, sh_lo(xf), sh_hi(xf), min_alpha, i, centers,
                                 cov_f32, cov_f16, rgba, sh_f16, sh_u8, nullptr, nullptr);
@@ -303,6 +352,22 @@ int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceIm
     return GS_OK;
 }
 
+// INRIA-v2 PLY: rows [first, first + count) at their file stride, one piece at the staging base, padded to 16 bytes, and - unless only
+// centres are wanted (they lie in the row) - the decoded codebook (20 KiB).  gs_asset_open proved that the file holds every row.
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, InriaV2Source* src, bool centres_only) {
+    const size_t stride = a->iv2.stride, bytes = stride * count, table_bytes = a->iv2_codebook.size() * sizeof(float);
+    GS_TRY(dev.bytes.ensure((bytes + 15) & ~(size_t)15));
+    GS_HIP(hipMemcpyAsync(dev.bytes.p, a->file.data() + a->iv2_vertex_base + stride * first, bytes, hipMemcpyHostToDevice, st));
+    if (!centres_only) {
+        GS_TRY(dev.table.ensure(table_bytes));
+        GS_HIP(hipMemcpyAsync(dev.table.p, a->iv2_codebook.data(), table_bytes, hipMemcpyHostToDevice, st));
+    }
+    GS_HIP(hipStreamSynchronize(st));
+    *src = InriaV2Source{dev.bytes.as<uint8_t>(), centres_only ? nullptr : dev.table.as<float>(), first, 0u, a->sh_degree,
+                         sh_components(a->sh_degree), a->iv2};
+    return GS_OK;
+}
+
 // gs_mesh_upload_asset's source: a segment of the staging is filled by k_asset_decode
 DevTransform dev_transform(const gs_asset* a) { return DevTransform{a->xf, a->sh_min, a->sh_max}; }
 
@@ -365,6 +430,7 @@ int with_source_of(const gs_asset* a, F f) {
         case ASSET_ROWS_SPLAT: return f(SourceOf<SplatSource>());
         case ASSET_ROWS_COMPRESSED_PLY: return f(SourceOf<CompressedSource>());
         case ASSET_ROWS_SPZ: return f(SourceOf<SpzSource>());
+        case ASSET_ROWS_INRIA_V2: return f(SourceOf<InriaV2Source>());
         default: return f(SourceOf<KsplatSource>());
     }
 }

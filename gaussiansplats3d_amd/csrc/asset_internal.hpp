@@ -1,7 +1,7 @@
 // asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share, each said once as
 // __host__ __device__ code for both sides: the two half-float rules, the scene transform, the per-row arithmetic of the formats
-// whose file rows are decoded on both sides (.splat, PlayCanvas compressed PLY, .spz), the .ksplat row reader (KsplatSource)
-// and the per-splat fill (asset_fill_splat) that gs_asset_fill loops over and k_asset_decode runs one thread of.
+// whose file rows are decoded on both sides (.splat, PlayCanvas compressed PLY, .spz, INRIA-v2 codebook PLY), the .ksplat row
+// reader (KsplatSource) and the per-splat fill (asset_fill_splat) that gs_asset_fill loops over and k_asset_decode runs one thread of.
 #pragma once
 #include <math.h>
 
@@ -356,6 +356,57 @@ __host__ __device__ inline float spz_sh_value(uint32_t byte) {                  
     return (float)(((double)byte - 128.0) / 128.0);
 }
 
+// ---- INRIA-v2 codebook PLY: one index byte per attribute -> the level-0 tuple ---------------------------------------------------------
+// Restates, never copies: src/loaders/ply/INRIAV2PlyParser.js:202-269 (parseToUncompressedSplat), then the level-0 store of
+// SplatBuffer.writeSplatDataToSectionBuffer :1092-1124, 1168-1172.  The codebook is decoded ONCE, at open, on the host (assets.hip:
+// decodeCodeBook :128-160 and every per-row rule that depends on the entry alone), so all a row needs of an entry is one fp32 and
+// a row's decode is look-ups, the three centre halves and the quaternion's two normalisations.  The decoded table's pages, 256
+// floats each, in the order the output degrees read them: a degree reads the first inria_v2_pages_read(degree) pages.
+enum { IV2_PAGE_DC = 0, IV2_PAGE_OPACITY = 1, IV2_PAGE_SCALING = 2, IV2_PAGE_ROTATION_RE = 3, IV2_PAGE_ROTATION_IM = 4,
+       IV2_PAGE_REST = 5, IV2_PAGES = 20, IV2_ABSENT = 0xFFFF };
+__host__ __device__ inline uint32_t inria_v2_pages_read(uint32_t degree) { return IV2_PAGE_REST + (degree == 0 ? 0u : (degree == 1 ? 3u : 8u)); }
+
+// Where a splat's values lie in its file row, from the header (every offset < stride < 64 KiB).  x / y / z and rot_0..3 always
+// exist; any other field may be IV2_ABSENT, which reads as the reference reads `undefined`.
+struct InriaV2Layout {
+    uint32_t stride;           // bytes per file row
+    uint16_t pos[3];           // x, y, z: half bits
+    uint16_t rot[4], scale[3], dc[3], opacity;   // index bytes
+    uint16_t sh[24];           // the index byte of level-0 SH slot s: f_rest_{s%3 + cpc*(s/3)} below 9, f_rest_{3 + (s-9)%5 + cpc*((s-9)/5)} above
+};
+
+__host__ __device__ inline float inria_v2_entry(const float* codebook, uint32_t page, uint32_t index) { return codebook[256u * page + index]; }
+
+// the centre alone: fromHalfFloat of the three 16-bit words (:264-266; exact, as from_half is), stored fp32
+__host__ __device__ inline void inria_v2_row_centre(const uint8_t* row, const InriaV2Layout& L, float c[3]) {
+    for (int k = 0; k < 3; k++) c[k] = row_f32(from_half((uint16_t)((uint32_t)row[L.pos[k]] | ((uint32_t)row[L.pos[k] + 1u] << 8))));
+}
+
+__host__ __device__ inline void inria_v2_row_tuple(const uint8_t* row, const InriaV2Layout& L, const float* codebook, Level0Tuple& t) {
+#pragma clang fp contract(off)
+    inria_v2_row_centre(row, L, t.c);
+    for (int k = 0; k < 3; k++) {                                                      // :206-214; a missing scale_1 / 2 is `undefined || 0`
+        if (L.scale[0] == IV2_ABSENT) t.s[k] = (float)0.01;
+        else t.s[k] = L.scale[k] == IV2_ABSENT ? 0.0f : inria_v2_entry(codebook, IV2_PAGE_SCALING, row[L.scale[k]]);
+    }
+    {   // :252-262 Quaternion.set(rot_0..3).normalize(), then the second normalize of writeSplatDataToSectionBuffer :1093-1094
+        double q[4] = {(double)inria_v2_entry(codebook, IV2_PAGE_ROTATION_RE, row[L.rot[0]]), 0, 0, 0};
+        for (int k = 1; k < 4; k++) q[k] = (double)inria_v2_entry(codebook, IV2_PAGE_ROTATION_IM, row[L.rot[k]]);
+        row_normalize(q);
+        row_normalize(q);
+        for (int k = 0; k < 4; k++) t.r[k] = row_f32(q[k]);                            // an infinite entry: inf * (1 / inf) = a generated NaN
+    }
+    for (int k = 0; k < 3; k++)                                                        // :216-236; the red / green / blue branch is dead code
+        t.rgba[k] = L.dc[0] == IV2_ABSENT || L.dc[k] == IV2_ABSENT ? (uint8_t)0 : (uint8_t)inria_v2_entry(codebook, IV2_PAGE_DC, row[L.dc[k]]);
+    t.rgba[3] = L.opacity == IV2_ABSENT ? (uint8_t)0 : (uint8_t)inria_v2_entry(codebook, IV2_PAGE_OPACITY, row[L.opacity]);
+}
+
+// Level-0 SH float s of the row (:239-249): the pages are indexed by coefficient and shared by the three channels
+__host__ __device__ inline float inria_v2_row_sh(const uint8_t* row, const InriaV2Layout& L, const float* codebook, uint32_t s) {
+    if (L.sh[s] == IV2_ABSENT) return 0.0f;
+    return inria_v2_entry(codebook, IV2_PAGE_REST + (s < 9u ? s % 3u : 3u + (s - 9u) % 5u), row[L.sh[s]]);
+}
+
 // ---- .ksplat rows: one reader for the host fill and the kernels ------------------------------------------------------------------
 // Restates, never copies: SplatBuffer.js:108-163 (rows per compression level), :199-219 (bucket of a splat), :221-246 (centre).
 // Bytes of a row's parts per compression level, in row order: centre, scale, rotation, RGBA (4), SH
@@ -572,17 +623,20 @@ __host__ __device__ __forceinline__ void asset_fill_splat(const Row row, const A
     }
 }
 
-enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3 };
+enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3, ASSET_ROWS_INRIA_V2 = 4 };
 
 struct gs_asset {
     std::vector<uint8_t> buf;              // a .ksplat image (for an INRIA-v1 PLY: the level-0 section built from it; for the
                                            // row formats: built from `file` when a host fill first needs it)
     uint32_t rows = ASSET_ROWS_KSPLAT;     // what the device decode reads: the image, or the file's own rows
-    std::vector<uint8_t> file;             // .splat / compressed PLY: the file as it was given; .spz: the INFLATED stream
+    std::vector<uint8_t> file;             // .splat / compressed / INRIA-v2 PLY: the file as it was given; .spz: the INFLATED stream
     SpzLayout spz = {};                    // .spz: where the planes lie in `file`
     PcLayout pc = {};                      // compressed PLY: the header's layout
     size_t pc_chunk_base = 0, pc_vertex_base = 0, pc_sh_base = 0;   // where the three elements start in `file`
     uint32_t pc_chunk_count = 0;
+    InriaV2Layout iv2 = {};                // INRIA-v2 PLY: the vertex element's layout, where its rows start in `file`, and the
+    size_t iv2_vertex_base = 0;            // codebook decoded at open (IV2_PAGES x 256 floats)
+    std::vector<float> iv2_codebook;
     uint32_t level = 0, splat_count = 0, sh_degree = 0;
     float scene_center[3] = {0, 0, 0};
     double sh_min = -1.5, sh_max = 1.5;

@@ -1,6 +1,12 @@
 // assets.hip — native asset readers (host code; asset_decode.hip decodes the same image per splat on the device, through the
 // same .ksplat row reader and per-splat fill body: asset_internal.hpp says both once for the two sides): INRIA-v1 .ply,
-// PlayCanvas compressed .ply, .splat, .spz and .ksplat -> the arrays the render / sort seams consume.  Restates, never copies:
+// PlayCanvas compressed .ply, INRIA-v2 codebook .ply, .splat, .spz and .ksplat -> the arrays the render / sort seams consume.
+// Restates, never copies:
+//   INRIA-v2 PLY      src/loaders/ply/INRIAV2PlyParser.js:45-126 (sections), :128-160 (decodeCodeBook: decoded once, at open, with
+//                     every per-row rule that depends on the entry alone, so an entry is one fp32); the row arithmetic (:202-269 +
+//                     SplatBuffer.js:1092-1124) is in asset_internal.hpp, shared with the device.  FILE ORDER, as .splat below: the
+//                     reference has no file-order path for it (PlyParser.parseToUncompressedSplatBuffer throws), and its array path
+//                     drops and reorders; splat i here is the level-0 row of parseToUncompressedSplat(file row i)
 //   .spz              src/loaders/spz/SpzLoader.js:255-342 (container; the gzip reader and every refusal are in spz_container.hpp),
 //                     :366-388 with optimizeSplatData false (file order); the row arithmetic (:160-250, 84-145 + SplatBuffer.js
 //                     :1092-1124) is in asset_internal.hpp, shared with the device
@@ -23,11 +29,13 @@
 //                     then Vector3.applyMatrix4 :340-342, T3*C*T3^T :461-466, rotated SH :628-637, 684-688, 707-715, 766-817
 //   scene transform   three r160 Matrix4.decompose / Quaternion.setFromRotationMatrix / normalize / makeRotationFromQuaternion
 // An INRIA-v1 PLY is first laid out as the level-0 section the reference would build from it (file order, i.e. the reference's
-// `optimizeSplatData: false`), so every fill routine reads one format.  A .splat / compressed PLY / .spz asset keeps the file's
-// own rows (for .spz: the inflated planes; what the device decode uploads) and builds that level-0 section when a host fill
-// first needs it.
+// `optimizeSplatData: false`), so every fill routine reads one format.  A .splat / compressed PLY / INRIA-v2 PLY / .spz asset keeps
+// the file's own rows (for .spz: the inflated planes; what the device decode uploads) and builds that level-0 section when a host
+// fill first needs it.
 // Reference quirk, documented and not reproduced: PlayCanvasCompressedPlyParser.readPly (:297-313) throws on a compressed PLY
 // without an `sh` element (TypeError: 'count' of undefined); the progressive path loads such files, and so does this reader.
+// INRIAV2PlyParser.parseToUncompressedSplat keeps its raw row in a closure across calls, so a file that lacks a field can see the
+// previous file's last row; this reader behaves as a fresh parser does (absent scale_* -> 0.01, absent f_dc_* / opacity -> 0).
 #include <algorithm>
 #include <math.h>
 #include <string>
@@ -326,7 +334,7 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
     return parse_ksplat(a);
 }
 
-// What a host fill of a .splat / compressed PLY / .spz asset reads: every file row through the shared row arithmetic
+// What a host fill of a .splat / compressed PLY / .spz / INRIA-v2 PLY asset reads: every file row through the shared row arithmetic
 // (asset_internal.hpp) into the level-0 row the reference stores for it.  Built once, on the first fill.
 int build_level0_image(gs_asset* a) {
     if (a->rows == ASSET_ROWS_KSPLAT || !a->buf.empty()) return GS_OK;
@@ -357,6 +365,10 @@ int build_level0_image(gs_asset* a) {
             spz_row_tuple(L, b, t);
             const uint8_t* sh = f + L.off[SPZ_SH] + 3 * (size_t)L.file_dim * i;
             for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, spz_sh_value(sh[spz_sh_index(s)]));
+        } else if (a->rows == ASSET_ROWS_INRIA_V2) {
+            const uint8_t* row = a->file.data() + a->iv2_vertex_base + (size_t)a->iv2.stride * i;
+            inria_v2_row_tuple(row, a->iv2, a->iv2_codebook.data(), t);
+            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, inria_v2_row_sh(row, a->iv2, a->iv2_codebook.data(), s));
         } else {
             uint32_t w[4];
             memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
@@ -547,6 +559,148 @@ int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_
     return GS_OK;
 }
 
+// ---- INRIA-v2 codebook PLY ---------------------------------------------------------------------------------------------------
+// One entry of the decoded codebook (asset_internal.hpp says what a row does with it): fromHalfFloat, decodeCodeBook's rule for the
+// page (INRIAV2PlyParser.js:143-158), then what parseToUncompressedSplat (:206-237) and the level-0 store (SplatBuffer.js:1100-1121,
+// 1169-1170) do to a value whatever the row: floor, clamp 0..255, `|| 0`, fp32.  Math.exp is row_exp, as for the compressed PLY.
+float inria_v2_decode_entry(uint32_t page, uint16_t half) {
+    const double v = from_half(half), SH_C0 = 0.28209479177387814;
+    if (page == IV2_PAGE_DC || page == IV2_PAGE_OPACITY) {
+        const double c = page == IV2_PAGE_DC ? js_round((0.5 + SH_C0 * v) * 255) : js_round((1 / (1 + row_exp(-v))) * 255);
+        return (float)clamped_u8(clampd(floor(c), 0, 255));
+    }
+    if (page == IV2_PAGE_SCALING) {
+        const double e = row_exp(v);
+        return (float)(e == e ? e : 0.0);
+    }
+    if (page >= IV2_PAGE_REST) return v == v && v != 0 ? (float)v : 0.0f;              // `|| 0`: NaN and -0 become +0
+    return row_f32(v);                                                                 // rotation_re / rotation_im
+}
+
+// decodeHeaderFromBuffer + decodeCodeBook.  The sections are decoded as PlyParserUtils.decodeSectionHeader decodes them (trimmed lines,
+// /(\w+)\s+(\w+)\s+(\w+)/ on property lines, later duplicates of a name overwrite earlier ones, anything but element / property lines is
+// dropped).  The reference is memory-safe JavaScript and turns whatever the header describes into undefined / NaN; here everything the
+// row decode relies on is proven at open, and what the reference would make every splat NaN of is refused.
+int parse_inria_v2(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+    const std::string token = "end_header";
+    const std::string head((const char*)data, bytes < (1u << 20) ? bytes : (1u << 20));
+    const size_t tok = head.find(token);
+    GS_REQUIRE(tok != std::string::npos, "INRIA-v2 PLY: end_header not found");
+    const size_t header_bytes = tok + token.size() + 1;                                // INRIAV2PlyParser.js:104
+    struct Prop { std::string name; FieldType type; uint32_t offset; };
+    struct Section { std::string name; uint64_t count = 0, stride = 0; std::vector<Prop> props; size_t base = 0; };
+    std::vector<Section> sections;
+    for (size_t pos = 0; pos < tok + token.size();) {
+        size_t nl = head.find('\n', pos);
+        if (nl == std::string::npos) nl = head.size();
+        const std::string line = trim(head.substr(pos, nl - pos));
+        pos = nl + 1;
+        if (line == token) break;
+        if (line.rfind("format", 0) == 0) {
+            GS_REQUIRE(line.rfind("format binary_little_endian", 0) == 0, "INRIA-v2 PLY: the format is not binary_little_endian");
+        } else if (line.rfind("element", 0) == 0) {
+            char name[128], count[32];
+            if (sscanf(line.c_str(), "element %127s %31s", name, count) != 2) name[0] = count[0] = 0;
+            uint64_t v = 0;
+            size_t d = 0;
+            while (count[d] >= '0' && count[d] <= '9' && v <= 0xFFFFFFFFull) v = v * 10 + (uint64_t)(count[d++] - '0');
+            GS_REQUIRE(d > 0 && v <= 0xFFFFFFFFull, "INRIA-v2 PLY: an element count is not a number below 2^32");
+            sections.emplace_back();
+            sections.back().name = name;
+            sections.back().count = v;
+        } else if (line.rfind("property", 0) == 0) {
+            char w0[64], w1[64], w2[128];
+            if (sscanf(line.c_str(), "%63[A-Za-z0-9_] %63[A-Za-z0-9_] %127[A-Za-z0-9_]", w0, w1, w2) != 3) continue;
+            const FieldType type = field_type(w1);
+            GS_REQUIRE(field_size(type) > 0, "INRIA-v2 PLY: property type the reference does not size (bytesPerVertex would be NaN)");
+            GS_REQUIRE(!sections.empty(), "INRIA-v2 PLY: a property precedes every element");
+            Section& sec = sections.back();
+            GS_REQUIRE(sec.stride + (uint64_t)field_size(type) < (1u << 16), "INRIA-v2 PLY: an element row of 64 KiB or more");
+            sec.props.push_back({w2, type, (uint32_t)sec.stride});
+            sec.stride += (uint64_t)field_size(type);
+        }
+    }
+    const Section *book = nullptr, *vertex = nullptr;
+    size_t off = header_bytes;
+    for (Section& sec : sections) {                                                    // findVertexData: the elements' rows follow in header order
+        GS_REQUIRE(off <= bytes && sec.stride * sec.count <= bytes - off, "INRIA-v2 PLY: element data exceeds the file");
+        sec.base = off;
+        off += (size_t)(sec.stride * sec.count);
+        const Section*& slot = sec.name == "codebook_centers" ? book : vertex;
+        GS_REQUIRE(slot == nullptr, "INRIA-v2 PLY: more than one codebook_centers element, or more than one element besides it");
+        slot = &sec;
+    }
+    GS_REQUIRE(book != nullptr, "INRIA-v2 PLY: no codebook_centers element");
+    GS_REQUIRE(vertex != nullptr, "INRIA-v2 PLY: no element besides codebook_centers");
+    GS_REQUIRE(book->count >= 256, "INRIA-v2 PLY: fewer than 256 codebook rows (an index byte reaches any of 256)");
+
+    // ---- the vertex element: which byte of a row is which attribute's index
+    auto starts = [](const std::string& s, const char* prefix) { return s.rfind(prefix, 0) == 0; };
+    uint32_t f_rest = 0;
+    for (const Prop& p : vertex->props) {
+        if (p.name == "x" || p.name == "y" || p.name == "z")
+            GS_REQUIRE(p.type == T_SHORT || p.type == T_USHORT, "INRIA-v2 PLY: x / y / z are not short / ushort (half bits)");
+        if (starts(p.name, "f_dc_") || starts(p.name, "f_rest") || starts(p.name, "scale_") || starts(p.name, "rot_") || p.name == "opacity")
+            GS_REQUIRE(p.type == T_UCHAR, "INRIA-v2 PLY: an index field (f_dc_* / f_rest_* / opacity / scale_* / rot_*) is not uchar");
+        if (starts(p.name, "f_rest")) f_rest++;
+    }
+    GS_REQUIRE(f_rest == 0 || f_rest == 9 || f_rest == 24 || f_rest == 45, "INRIA-v2 PLY: the f_rest_* fields are not 0, 9, 24 or 45");
+    const uint32_t cpc = f_rest / 3, file_degree = cpc >= 8 ? 2u : (cpc >= 3 ? 1u : 0u);
+    auto find = [](const Section& sec, const std::string& name) {
+        uint16_t at = IV2_ABSENT;
+        for (const Prop& p : sec.props) if (p.name == name) at = (uint16_t)p.offset;    // later duplicates overwrite: keep the last
+        return at;
+    };
+    InriaV2Layout L = {};
+    L.stride = (uint32_t)vertex->stride;
+    L.pos[0] = find(*vertex, "x"); L.pos[1] = find(*vertex, "y"); L.pos[2] = find(*vertex, "z");
+    for (int k = 0; k < 4; k++) L.rot[k] = find(*vertex, "rot_" + std::to_string(k));
+    for (int k = 0; k < 3; k++) {
+        GS_REQUIRE(L.pos[k] != IV2_ABSENT, "INRIA-v2 PLY: x / y / z missing (the reference makes every centre NaN)");
+        L.scale[k] = find(*vertex, "scale_" + std::to_string(k));
+        L.dc[k] = find(*vertex, "f_dc_" + std::to_string(k));
+    }
+    for (int k = 0; k < 4; k++) GS_REQUIRE(L.rot[k] != IV2_ABSENT, "INRIA-v2 PLY: rot_0 .. rot_3 missing (the reference makes every rotation NaN)");
+    L.opacity = find(*vertex, "opacity");
+    for (uint32_t s = 0; s < 24; s++) {                                                // decodeSphericalHarmonicsFromSectionHeader, in level-0 slot order
+        const uint32_t k = s < 9 ? s % 3 + cpc * (s / 3) : 3 + (s - 9) % 5 + cpc * ((s - 9) / 5);
+        L.sh[s] = s < sh_components(file_degree) ? find(*vertex, "f_rest_" + std::to_string(k)) : (uint16_t)IV2_ABSENT;
+    }
+
+    // ---- the codebook: the pages the file's fields reach must exist as half bits; pages nothing reaches stay 0
+    static const char* const rest_names[15] = {"features_rest_0", "features_rest_1", "features_rest_2", "features_rest_3", "features_rest_4",
+                                               "features_rest_5", "features_rest_6", "features_rest_7", "features_rest_8", "features_rest_9",
+                                               "features_rest_10", "features_rest_11", "features_rest_12", "features_rest_13", "features_rest_14"};
+    const char* page_name[IV2_PAGES] = {"features_dc", "opacity", "scaling", "rotation_re", "rotation_im"};
+    bool needed[IV2_PAGES] = {L.dc[0] != IV2_ABSENT, L.opacity != IV2_ABSENT, L.scale[0] != IV2_ABSENT, true, true};
+    for (uint32_t k = 0; k < 15; k++) {
+        page_name[IV2_PAGE_REST + k] = rest_names[k];
+        needed[IV2_PAGE_REST + k] = k < (file_degree == 0 ? 0u : (file_degree == 1 ? 3u : 8u));
+    }
+    a->iv2_codebook.assign((size_t)IV2_PAGES * 256, 0.0f);
+    for (uint32_t page = 0; page < IV2_PAGES; page++) {
+        const Prop* prop = nullptr;
+        for (const Prop& p : book->props) if (p.name == page_name[page]) prop = &p;
+        GS_REQUIRE(prop || !needed[page], "INRIA-v2 PLY: a codebook page that the file's fields need is missing");
+        if (!prop) continue;
+        GS_REQUIRE(prop->type == T_SHORT || prop->type == T_USHORT, "INRIA-v2 PLY: a codebook property is not short / ushort (half bits)");
+        for (uint32_t i = 0; i < 256; i++) {
+            uint16_t h;
+            memcpy(&h, data + book->base + (size_t)book->stride * i + prop->offset, 2);
+            a->iv2_codebook[256 * page + i] = inria_v2_decode_entry(page, h);
+        }
+    }
+    uint32_t degree = want_degree < file_degree ? want_degree : file_degree;           // Math.min(out, file) :203; the level-0 row holds two bands
+    a->file.assign(data, data + bytes);
+    a->rows = ASSET_ROWS_INRIA_V2;
+    a->iv2 = L;
+    a->iv2_vertex_base = vertex->base;
+    a->splat_count = (uint32_t)vertex->count;
+    a->level = 0;
+    a->sh_degree = degree;
+    return GS_OK;
+}
+
 // gs_asset_fill's loop: every splat of the image through the shared per-splat body (asset_internal.hpp)
 template <bool XF>
 void fill_image(const gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba, uint16_t* sh_f16,
@@ -573,8 +727,7 @@ int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t ma
         if (format == GS_ASSET_PLY) {
             const PlyFlavour flavour = ply_flavour((const uint8_t*)data, (size_t)bytes);
             if (flavour == PLY_INRIA_V2) {
-                gs_set_error("invalid argument: INRIA-v2 PLY (element codebook_centers) is not supported");
-                st = GS_ERR_INVALID;
+                st = parse_inria_v2(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
             } else if (flavour == PLY_COMPRESSED) {
                 st = parse_compressed_ply(a, (const uint8_t*)data, (size_t)bytes, max_sh_degree);
             } else {

@@ -220,7 +220,16 @@ typedef struct gs_asset gs_asset;
 #define GS_ASSET_PLY 1u      /* .ply, binary little endian; the flavour is decided from the header as PlyParserUtils.js:257-271
                               * does: `element chunk` / `packed_` = PlayCanvas (SuperSplat) compressed
                               * (src/loaders/ply/PlayCanvasCompressedPlyParser.js), `element codebook_centers` = INRIA-v2
-                              * (refused), anything else INRIA-v1 (src/loaders/ply/INRIAV1PlyParser.js)                   */
+                              * (src/loaders/ply/INRIAV2PlyParser.js: half-float centres, one uchar index per attribute into
+                              * 256-entry codebook pages; kept in FILE order, every splat, as .splat is - the reference's array
+                              * path drops and reorders), anything else INRIA-v1 (src/loaders/ply/INRIAV1PlyParser.js).
+                              * An INRIA-v2 file is refused by name (`INRIA-v2 PLY: ...`) for: a format other than
+                              * binary_little_endian, no end_header, an unsized property type, an element count that is no
+                              * number below 2^32, more than one element besides codebook_centers or none, x / y / z or
+                              * rot_0..3 missing, x / y / z not short / ushort, an index field not uchar, an f_rest count outside
+                              * 0 / 9 / 24 / 45, a codebook property that is read and is not short / ushort, fewer than 256
+                              * codebook rows, a codebook page the file's fields need missing, element data beyond the end of
+                              * the file, a row of 64 KiB or more.  A degree-3 file is read at degree 2                    */
 #define GS_ASSET_KSPLAT 2u   /* .ksplat, compression levels 0/1/2: src/loaders/SplatBuffer.js                        */
 #define GS_ASSET_SPLAT 3u    /* .splat, 32-byte rows (centre 3 x f32, scale 3 x f32, RGBA, rotation 4 x u8), SH degree 0:
                               * src/loaders/splat/SplatParser.js:13-56, the progressive file-order path - every splat is
@@ -234,7 +243,8 @@ enum { GS_ASSET_SPZ = 4 };   /* .spz, versions 1 and 2: a gzip member around a 1
                               * degree-3 file is read at degree 2.  An enum constant, unlike its siblings: same value space   */
 /* Parses `data` (the bytes of the file).  max_sh_degree: outSphericalHarmonicsDegree (Viewer option
  * sphericalHarmonicsDegree); splats keep FILE order (the reference's optimizeSplatData:false).  A .splat / compressed
- * PLY / .spz asset keeps the file's own rows (.spz: the inflated planes): gs_mesh_upload_asset /
+ * PLY / INRIA-v2 PLY / .spz asset keeps the file's own rows (.spz: the inflated planes; INRIA-v2: with the codebook decoded once,
+ * at open): gs_mesh_upload_asset /
  * gs_sorter_upload_asset_centers send those to the device and decode them there, gs_asset_fill decodes them on the host the first time it is called (compression_level 0, sh_level 1). */
 int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t max_sh_degree, gs_asset** out);
 void gs_asset_close(gs_asset* a);

@@ -1,12 +1,12 @@
 """Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
-    python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply|spz] [--sh-degree 0..3]
+    python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply|spz|inria-v2] [--sh-degree 0..3]
                               [--repeats 5] [--transform identity | 16 numbers] [--out profiles/<tag>_load_time.txt]
   host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
   device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
 The file: $GS_DATA_DIR/<--file> when given (a name ending in .splat is one), else a seeded file of --n splats (the C3 count
 by default) in --format, from the writers of gaussiansplats3d_amd.assets: a level-2 SH-2 .ksplat (the default), an INRIA-v1
-PLY, a .splat, a PlayCanvas compressed PLY or a version-2 .spz with --sh-degree bands.  For .splat / compressed PLY / .spz the
-asset keeps the file's rows and the host decodes them on its first fill, so both paths open a fresh asset inside the timed
+PLY, a .splat, a PlayCanvas compressed PLY, a version-2 .spz or an INRIA-v2 codebook PLY with --sh-degree bands.  For .splat /
+compressed PLY / .spz / INRIA-v2 PLY the asset keeps the file's rows and the host decodes them on its first fill, so both paths open a fresh asset inside the timed
 region (for .spz that includes the inflate, on both paths).  --transform: the scene's static transform (Matrix4.elements, column-major; `identity` is what a static
 Viewer passes for a scene without one), set on the asset so both paths bake it (gs_asset_set_transform).  Every repeat loads into a fresh mesh and sorter (a re-upload would skip the Morton sort); the two paths
 alternate.  Prints median and spread (max - min) of both and the bytes each sends over PCIe; the device path passes when its
@@ -54,14 +54,17 @@ def seeded(fmt, n, sh_degree):
     if fmt == "compressed-ply":
         return assets.write_compressed_ply(centers, log_scales, rot, rng.random((n, 4)), sh), "ply", \
             f"seeded PlayCanvas compressed PLY, {ncoef} SH properties, {n} splats"
+    if fmt == "inria-v2":
+        return assets.write_inria_v2_ply(centers, log_scales, rot, rng.normal(size=(n, 3)), rng.normal(size=n), sh), "ply", \
+            f"seeded INRIA-v2 codebook PLY, {ncoef} f_rest fields, {n} splats"
     return assets.write_ply(centers, log_scales, rot, rng.normal(size=(n, 3)), rng.normal(size=n), sh), "ply", \
         f"seeded INRIA-v1 PLY, {ncoef} f_rest properties, {n} splats"
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", default="ksplat", choices=["ksplat", "ply", "splat", "compressed-ply", "spz"])
-    ap.add_argument("--sh-degree", type=int, default=2, choices=[0, 1, 2, 3], help="bands of a seeded ply / compressed-ply / spz")
+    ap.add_argument("--format", default="ksplat", choices=["ksplat", "ply", "splat", "compressed-ply", "spz", "inria-v2"])
+    ap.add_argument("--sh-degree", type=int, default=2, choices=[0, 1, 2, 3], help="bands of a seeded ply / compressed-ply / spz / inria-v2")
     ap.add_argument("--n", type=int, default=5_800_000)
     ap.add_argument("--file", default=None)
     ap.add_argument("--repeats", type=int, default=5)
@@ -89,8 +92,9 @@ def main():
     info = asset.info
     header = data[:data.index(b"end_header\n") + 11] if data[:3] == b"ply" else b""
     compressed = b"element chunk" in header
+    inria_v2 = not compressed and b"element codebook_centers" in header
     spz = fmt == "spz" or data[:2] == b"\x1f\x8b"
-    file_rows = fmt == "splat" or compressed or spz                   # the asset keeps the file's rows
+    file_rows = fmt == "splat" or compressed or spz or inria_v2       # the asset keeps the file's rows
     n, deg, sh8 = info.splat_count, info.sh_degree, info.sh_level == 2 and info.sh_degree > 0
     ncoef = {0: 0, 1: 9, 2: 24}[deg]
     ctx = Context(0)
@@ -136,6 +140,8 @@ def main():
     elif compressed:                                                  # vertex rows + chunk rows twice, the SH bytes once
         sh_file = n * header.count(b"property uchar f_rest_")
         device_bytes = 2 * (len(data) - len(header) - sh_file) + (sh_file if ncoef else 0)
+    elif inria_v2:                                                    # the index rows twice, the decoded codebook (20 pages of 256 floats) once
+        device_bytes = 2 * n * (6 + header.count(b"property uchar ")) + 20 * 256 * 4
     elif data[:3] == b"ply":
         device_bytes = 2 * n * (44 + 4 * ncoef)                       # the level-0 image the host built from the PLY
     else:
