@@ -87,6 +87,12 @@ class AssetInfo(C.Structure):
                 ("sh_level", C.c_uint32), ("scene_center", C.c_float * 3), ("sh_min", C.c_float), ("sh_max", C.c_float)]
 
 
+class Bounds(C.Structure):
+    """gs_bounds: what gs_mesh_bounds found over a range of splats."""
+    _fields_ = [("count", C.c_uint64), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("max_dist_sq", C.c_double)]
+
+
+GS_BOUNDS_TRANSFORM = 1
 GS_ASSET_PLY, GS_ASSET_KSPLAT, GS_ASSET_SPLAT, GS_ASSET_SPZ = 1, 2, 3, 4
 
 # every symbol include/gsplat_hip.h declares: (restype, argtypes)
@@ -144,6 +150,7 @@ SYMBOLS = {
     "gs_mesh_compute_distances": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "gs_mesh_debug_rop8": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "gs_mesh_surface": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP]),
+    "gs_mesh_bounds": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(Bounds)]),
     "gs_mesh_set_deep_pass": (C.c_int, [_VP, C.c_int]),
     "gs_mesh_set_draw_mode": (C.c_int, [_VP, C.c_uint32]),
     "gs_mesh_last_stats": (C.c_int, [_VP, C.POINTER(RenderStats)]),

@@ -477,6 +477,7 @@ struct gs_mesh {
     DevBuf upload_partials;    // CentrePartial per workgroup: bounds and sums of a segment decoded on the device (mesh.hip)
     AssetDeviceImage asset_dev;
     DevBuf distances;          // uint32 [n]: gs_mesh_compute_distances's result when no sorter receives it (distances.hip)
+    DevBuf bounds_buf;         // gs_mesh_bounds: a partial per workgroup, then the scenes' fp64 transforms (bounds.hip)
     // per-draw
     DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
     DevBuf zrec;               // float [n]     the survivor's window-space centre depth, same slots (only while a destination

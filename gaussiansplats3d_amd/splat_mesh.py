@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .reveal import SceneRevealMode, VisibleRegion
 from .util import distance_uniforms, to_half_three
 
 
@@ -19,7 +20,7 @@ class SplatMesh:
     def __init__(self, context, max_splat_count, spherical_harmonics_degree=0, half_precision_covariances=False,
                  antialiased=False, kernel_2d_size=0.3, max_screen_space_splat_size=1024.0, splat_scale=1.0,
                  point_cloud_mode=False, spherical_harmonics_8bit=False, dynamic_mode=False,
-                 enable_optional_effects=False, keep_order=False):
+                 enable_optional_effects=False, keep_order=False, scene_fade_in_rate_multiplier=1.0):
         self.ctx = context
         self.lib = context.lib
         self.max_splat_count = int(max_splat_count)
@@ -36,6 +37,10 @@ class SplatMesh:
         self.fade_in = None                                    # (sceneCenter, visibleRegionFadeStartRadius) or None
         self.keep_order = bool(keep_order)                     # GS_MESH_KEEP_ORDER: device storage in upload order (no Morton)
         self.scene_transforms = None                           # fp64 column-major 16-vectors of set_scenes (dynamic distance pass)
+        self.visible_region = VisibleRegion(scene_fade_in_rate_multiplier)   # the scene reveal (update_visible_region*)
+        self.scene_centers = [[0.0, 0.0, 0.0]]                 # the scenes' sceneCenter (update_visible_region)
+        self.last_build_splat_count = 0                        # splats the last update_visible_region had seen
+        self._scene_of = np.zeros(int(max_splat_count), np.uint32)   # host copy of the scene indexes (compute_bounding_box)
         self.splat_count = 0
         self.render_count = 0
         self._indexes = None          # host indexes from updateRenderIndexes
@@ -86,6 +91,7 @@ class SplatMesh:
         if scene_indexes is not None:
             si = np.ascontiguousarray(scene_indexes, dtype=np.uint32).reshape(n)
             L.check(self.lib.gs_mesh_upload_scene_indexes(self.handle, int(start), n, si.ctypes.data))
+            self._scene_of[int(start):int(start) + n] = si
         self.splat_count = max(self.splat_count, int(start) + n)
         return self
 
@@ -139,6 +145,68 @@ class SplatMesh:
     def set_fade_in(self, scene_center=None, visible_region_fade_start_radius=0.0):
         """fadeInComplete == 0 with these uniforms (SplatMesh.updateVisibleRegionFadeDistance); None = complete."""
         self.fade_in = None if scene_center is None else (np.asarray(scene_center, np.float32), float(visible_region_fade_start_radius))
+
+    # -- scene bounds and the scene reveal ----------------------------------------------------------
+    def bounds(self, start, count, center, transforms=None):
+        """gs_mesh_bounds over splats [start, start + count) of the caller's numbering, reduced on the device: {count - splats
+        that took part (a NaN component excludes one), min / max - float32 [3] box of the centres, max_dist_sq - the largest
+        |c - center|^2 in fp64, every operation rounded on its own in three.js's order}.  transforms (column-major 16-vectors,
+        one per scene): applied to every centre first as THREE.Vector3.applyMatrix4 does, by the splat's scene index."""
+        c = (C.c_double * 3)(*[float(v) for v in center])
+        out = L.Bounds()
+        t, flags = None, 0
+        if transforms is not None:
+            t = np.ascontiguousarray(np.asarray(transforms, np.float64).reshape(-1, 16))
+            flags = L.GS_BOUNDS_TRANSFORM
+        L.check(self.lib.gs_mesh_bounds(self.handle, int(start), int(count), C.cast(c, C.c_void_p),
+                                        t.ctypes.data if t is not None else None, t.shape[0] if t is not None else 0, flags,
+                                        C.byref(out)))
+        return {"count": int(out.count), "min": np.array(out.box_min[:], np.float32), "max": np.array(out.box_max[:], np.float32),
+                "max_dist_sq": float(out.max_dist_sq)}
+
+    def compute_bounding_box(self, apply_scene_transforms=False, scene_index=None):
+        """SplatMesh.computeBoundingBox(applySceneTransforms, sceneIndex) (SplatMesh.js:2066-2095) -> (min, max) float32 [3], over
+        the whole mesh or the splats of one scene.  This mirror holds no splat buffers: a static mesh stores the centres its
+        caller's fill produced and their box is returned whatever apply_scene_transforms says; a dynamic_mode mesh stores
+        untransformed centres and applies the transforms of set_scenes when asked to."""
+        start, count = 0, self.splat_count
+        if scene_index is not None:
+            scenes = max(len(self.scene_transforms or ()), int(self._scene_of[:self.splat_count].max(initial=0)) + 1)
+            if scene_index < 0 or scene_index >= scenes:
+                raise ValueError("SplatMesh::computeBoundingBox() -> Invalid scene index.")
+            own = np.flatnonzero(self._scene_of[:self.splat_count] == scene_index)       # a scene's splats are consecutive
+            start, count = (int(own[0]), int(own.size)) if own.size else (0, 0)
+        moved = apply_scene_transforms and self.dynamic_mode and self.scene_transforms is not None
+        b = self.bounds(start, count, (0.0, 0.0, 0.0), self.scene_transforms if moved else None)
+        return b["min"], b["max"]
+
+    def update_visible_region(self, since_last_build_only=False, scene_centers=None, final_build=False):
+        """SplatMesh.updateVisibleRegion(sinceLastBuildOnly) (SplatMesh.js:1172-1199), called after a build as the reference's
+        refreshDataTexturesFromSplatBuffers does: the largest distance from the averaged scene centre over the splats uploaded
+        since the last call (or over all of them) comes from the device (``bounds``); the radii follow in ``visible_region``.
+        scene_centers: the scenes' sceneCenter (kept from the last call when omitted)."""
+        if scene_centers is not None:
+            self.scene_centers = [[float(v) for v in c] for c in scene_centers]
+        start = self.last_build_splat_count if since_last_build_only else 0
+        transforms = self.scene_transforms if self.dynamic_mode else None
+
+        def max_distance_from(center):
+            return float(np.sqrt(self.bounds(start, self.splat_count - start, center, transforms)["max_dist_sq"]))
+        self.visible_region.update(since_last_build_only, self.scene_centers, final_build, max_distance_from)
+        self.last_build_splat_count = self.splat_count
+        return self.visible_region
+
+    def update_visible_region_fade_distance(self, scene_reveal_mode=SceneRevealMode.Default):
+        """SplatMesh.updateVisibleRegionFadeDistance(sceneRevealMode) (SplatMesh.js:1201-1220), once per frame: advances the
+        fade-in and sets the fade uniforms of the following ``set_camera`` / ``update_uniforms`` - on while the shader's
+        fadeInComplete is 0, off once it is 1."""
+        v = self.visible_region
+        v.update_fade_distance(scene_reveal_mode)
+        if v.shader_fade_in_complete:
+            self.set_fade_in(None)
+        else:
+            self.set_fade_in(v.calculated_scene_center, v.visible_region_fade_start_radius)
+        return v
 
     def get_splat_count(self):
         return self.splat_count

@@ -567,6 +567,38 @@ int gs_mesh_debug_rop8(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uin
 int gs_mesh_surface(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float threshold,
                     uint32_t* ids_out_host, float* depth_out_host, void* ids_out_dev, void* depth_out_dev);
 
+/* SCENE BOUNDS: where the splats [from, from + count) of the caller's numbering are - the reference's two host loops over every
+ * centre, as one read-only device pass over the planes the mesh keeps (csrc/bounds.hip):
+ *   SplatMesh.updateVisibleRegion  (src/splatmesh/SplatMesh.js:1172-1199)  max over the range of |c - center|, which drives the
+ *                                  scene fade-in (GS_CAM_FADE_IN: gs_camera::scene_center / fade_start_radius);
+ *   SplatMesh.computeBoundingBox   (:2066-2095)                            min / max of the centres as a Float32Array holds them.
+ * c is the stored fp32 centre widened to double, or - GS_BOUNDS_TRANSFORM - transforms[scene of the splat] applied to it first
+ * exactly as THREE.Vector3.applyMatrix4 writes it: w = 1 / (e3 x + e7 y + e11 z + e15), x' = (e0 x + e4 y + e8 z + e12) w, ...;
+ * the scene comes from the plane gs_mesh_upload_scene_indexes filled (none: every splat is scene 0; an index >= scene_count: 0).
+ * Every product, sum and the division is one fp64 operation in the reference's order, d = c - center per component, then
+ * (dx dx + dy dy) + dz dz: Vector3.sub(...).length() without the root.  The caller takes the root: sqrt is monotone and correctly
+ * rounded, so sqrt(max s) == max sqrt(s) bit for bit.  The box takes (float)x' - the Float32Array store - the distance the
+ * unrounded double.  The maximum uses `d > m` from 0, the box `<` and `>`; a splat with a NaN component (after the transform)
+ * takes part in neither and is not counted - the reference differs only when splat 0 is NaN (its box starts from splat 0
+ * unconditionally); +-Inf propagates.  Minimum and maximum are exact, so the result does not depend on the launch geometry or on
+ * the storage order (GS_MESH_KEEP_ORDER).
+ * Bit-equal to the reference's running maximum wherever the mesh's stored centres are the floats the reference reads (a level-0
+ * buffer with no or an identity baked transform; dynamic mode with GS_BOUNDS_TRANSFORM).  Where the reference keeps an unrounded
+ * double and the mesh its Float32Array rounding (a baked non-identity static transform, .ksplat level 1 / 2 bucket decoding,
+ * SplatBuffer.js:232-246) the radius differs by at most 2^-24 (R + |center|): half an ulp per component is |e| <= 2^-24 |c|, and
+ * | |a + e| - |a| | <= |e|.
+ * count == 0: GS_OK, every field 0.  A range that is not wholly uploaded: GS_ERR_INVALID, *out untouched.  The call enqueues
+ * behind the mesh's uploads on the context's stream, waits and returns; it writes none of the mesh's planes, so draws in flight
+ * are not disturbed.  No existing kernel takes part: frames are unchanged. */
+#define GS_BOUNDS_TRANSFORM 1u
+typedef struct gs_bounds {
+    uint64_t count;                /* splats of the range that took part                                            */
+    float box_min[3], box_max[3];  /* 0 when count == 0                                                             */
+    double max_dist_sq;            /* max |c - center|^2 over them; 0 for none                                      */
+} gs_bounds;
+int gs_mesh_bounds(gs_mesh* m, uint32_t from, uint32_t count, const double* center, const double* transforms,
+                   uint32_t scene_count, uint32_t flags, gs_bounds* out);
+
 /* DRAW MODE of the draws that follow.
  *   GS_DRAW_FP32 (default)  the front-to-back fp32 composite, rounded to RGBA8 once (early termination, chunks, the deep pass):
  *                           <= 0.52 / 255 from the exact composite, 3-4 / 255 from what a browser's RGBA8 target shows on

@@ -2,7 +2,7 @@
 //
 // Same constructor arguments, same `build(splatBuffers, sceneOptions, keepSceneTransforms, finalBuild, ...)`, same
 // getIntegerCenters / getSplatCount / getMaxSplatCount / updateRenderIndexes / updateUniforms / fillTransformsArray /
-// getSplatTree / setSplatScale ..., so that the Viewer's own code - addSplatBuffersToMesh (src/Viewer.js:1189-1228),
+// getSplatTree / setSplatScale / updateVisibleRegionFadeDistance / computeBoundingBox ..., so that the Viewer's own code - addSplatBuffersToMesh (src/Viewer.js:1189-1228),
 // setupSortWorker (:1235-1300), runSplatSort (:1833-1964), gatherSceneNodesForSort (:1969-2077), updateSplatMesh
 // (:651-677) and the draw `renderer.render(splatMesh, camera)` (:1616) - runs against it UNCHANGED
 // (tests/test_node_seam.py executes exactly that text).  Splat data reaches the device through the SplatBuffers' own
@@ -23,9 +23,10 @@ import * as THREE from 'three';
 import { createRequire } from 'module';
 const require = createRequire(import.meta.url);
 const { SplatMeshHIP: HipMeshCore, addon } = require('./gsplat.js');
+import { VisibleRegion, SceneRevealMode } from './VisibleRegion.mjs';
 
 export const SplatRenderMode = { ThreeD: 0, TwoD: 1 };
-export const SceneRevealMode = { Default: 0, Gradual: 1, Instant: 2 };
+export { SceneRevealMode };
 
 // SplatScene (src/splatmesh/SplatScene.js) without the Object3D base: the transform is compose(position, quaternion, scale)
 class HipSplatScene {
@@ -70,7 +71,15 @@ export class SplatMesh {
       disposed: false, visible: false, frustumCulled: false,
       matrixWorld: new THREE.Matrix4(),                     // Object3D.matrixWorld (src/Viewer.js:1891 multiplies by it)
       core: null,                                           // the device-side mesh (gs_mesh_*)
-      frame: null, shCompressionLevel: 1 });
+      frame: null, shCompressionLevel: 1,
+      _region: new VisibleRegion(this.sceneFadeInRateMultiplier), _sceneCenter: new THREE.Vector3() });
+    // The scene reveal's state under the reference's names (:144-149; src/Viewer.js:1585 reads visibleRegionChanging): kept by
+    // node/VisibleRegion.mjs, advanced by updateVisibleRegion (every build) and updateVisibleRegionFadeDistance (every frame).
+    for (const name of ['visibleRegionChanging', 'visibleRegionRadius', 'visibleRegionBufferRadius', 'visibleRegionFadeStartRadius',
+                        'maxSplatDistanceFromSceneCenter']) {
+      Object.defineProperty(this, name, { enumerable: true, get: () => this._region[name], set: (v) => { this._region[name] = v; } });
+    }
+    Object.defineProperty(this, 'calculatedSceneCenter', { enumerable: true, get: () => this._sceneCenter.fromArray(this._region.calculatedSceneCenter) });
   }
 
   // ---- statics, as the reference (:173-228, :1311-1341) --------------------------------------------------------------
@@ -118,6 +127,7 @@ export class SplatMesh {
                         splatBuffers.every((buffer, k) => buffer === this.lastBuildScenes[k].splatBuffer);
     const appendOnly = sameBuffers && this.scenes.length === 1 && this.lastBuildSceneCount === 1 && this.lastBuildMaxSplatCount === capacity;
     if (!appendOnly) {
+      if (!preserveVisibleRegion) { this._region.reset(); this.firstRenderTime = -1; }       // :356-362
       Object.assign(this, { lastBuildScenes: [], lastBuildSplatCount: 0, lastBuildMaxSplatCount: 0 });
       this.disposeMeshData();
       const maps = SplatMesh.buildSplatIndexMaps(splatBuffers);
@@ -178,7 +188,7 @@ export class SplatMesh {
         centerColors: { size: new THREE.Vector2(maxSplatCount, 1) } };       // sizes: Viewer.js:1289-1296 only logs them
     }
     const count = toSplat - fromSplat + 1;
-    if (count <= 0) return;
+    if (count <= 0) { this.updateVisibleRegion(sinceLastBuildOnly); return; }
     const covLevel = this.getTargetCovarianceCompressionLevel();
     const covariances = covLevel === 1 ? new Uint16Array(count * 6) : new Float32Array(count * 6);
     const centers = new Float32Array(count * 3);
@@ -199,6 +209,65 @@ export class SplatMesh {
       this.core.setSceneIndexes(sceneIndexes, fromSplat);
     }
     this._scenesDirty = true;
+    this.updateVisibleRegion(sinceLastBuildOnly);           // :634
+  }
+
+  // :1172-1199.  The reference's loop over every new centre (getSplatCenter(i, c, true): the scene's transform applied in double)
+  // is gs_mesh_bounds over the device mesh: a dynamic mesh stores the untransformed centres and the pass applies the scenes'
+  // transforms as applyMatrix4 does (bit-equal); a static mesh stores their Float32Array rounding, which moves the radius by at
+  // most 2^-24 (R + |centre|) - nothing with identity transforms.  Ends, as there, with one Default fade step; the fade uniforms
+  // are only set by updateVisibleRegionFadeDistance, which the Viewer calls once per frame with its sceneRevealMode.
+  updateVisibleRegion(sinceLastBuildOnly) {
+    if (!this.core || !this.scenes.length) return;
+    const splatCount = this.getSplatCount(true), from = sinceLastBuildOnly ? this.lastBuildSplatCount : 0;
+    const transforms = this.dynamicMode ? [].concat(...this.scenes.map((sc) => sc.transform.elements)) : null;
+    this._region.sceneFadeInRateMultiplier = this.sceneFadeInRateMultiplier;
+    this._region.update(sinceLastBuildOnly, this.scenes.map((sc) => sc.splatBuffer.sceneCenter.toArray()), this.finalBuild,
+                        (center) => (splatCount > from ? Math.sqrt(this.core.bounds(from, splatCount - from, center, transforms).maxDistSq) : 0));
+  }
+
+  // :1201-1220, once per frame (src/Viewer.js:1585-1588): advances the fade-in, then sets the vertex stage's fade uniforms
+  // (GS_CAM_FADE_IN) - on while the shader's fadeInComplete is 0, off once it is 1 (always under SceneRevealMode.Instant).  A mesh
+  // on which this is never called draws without a fade.
+  updateVisibleRegionFadeDistance(sceneRevealMode = SceneRevealMode.Default) {
+    const region = this._region;
+    region.sceneFadeInRateMultiplier = this.sceneFadeInRateMultiplier;
+    region.updateFadeDistance(sceneRevealMode);
+    if (!this.core) return;
+    if (region.shaderFadeInComplete) this.core.setFadeIn(null);
+    else this.core.setFadeIn(region.calculatedSceneCenter, region.visibleRegionFadeStartRadius);
+  }
+
+  // :2066-2095.  On the device (gs_mesh_bounds) where the mesh holds the centres the reference would fill: a dynamic mesh (the
+  // transforms applied by the pass when asked for), a static one whose transforms are all the identity, or a static one asked for
+  // the transformed box (that is what it stores).  Otherwise through fillSplatDataArrays on the host, as the reference does.
+  computeBoundingBox(applySceneTransforms = false, sceneIndex) {
+    let start = 0, splatCount = this.getSplatCount();
+    if (sceneIndex !== undefined && sceneIndex !== null) {
+      if (sceneIndex < 0 || sceneIndex >= this.scenes.length) throw new Error('SplatMesh::computeBoundingBox() -> Invalid scene index.');
+      for (let k = 0; k < sceneIndex; k++) start += this.scenes[k].splatBuffer.getSplatCount();
+      splatCount = this.scenes[sceneIndex].splatBuffer.getSplatCount();
+    }
+    const identity = new THREE.Matrix4().elements;
+    const allIdentity = this.scenes.every((sc) => sc.transform.elements.every((e, k) => e === identity[k]));
+    if (this.core && (this.dynamicMode || allIdentity || applySceneTransforms)) {
+      const transforms = this.dynamicMode && applySceneTransforms ? [].concat(...this.scenes.map((sc) => sc.transform.elements)) : null;
+      const b = this.core.bounds(start, splatCount, [0, 0, 0], transforms);
+      return new THREE.Box3(new THREE.Vector3().fromArray(b.min), new THREE.Vector3().fromArray(b.max));
+    }
+    const centers = new Float32Array(splatCount * 3);
+    this.fillSplatDataArrays(null, null, null, centers, null, null, applySceneTransforms, undefined, undefined, undefined, undefined, undefined, 0, sceneIndex);
+    const min = new THREE.Vector3(), max = new THREE.Vector3();
+    for (let i = 0; i < splatCount; i++) {
+      const x = centers[3 * i], y = centers[3 * i + 1], z = centers[3 * i + 2];
+      if (i === 0 || x < min.x) min.x = x;
+      if (i === 0 || y < min.y) min.y = y;
+      if (i === 0 || z < min.z) min.z = z;
+      if (i === 0 || x > max.x) max.x = x;
+      if (i === 0 || y > max.y) max.y = y;
+      if (i === 0 || z > max.z) max.z = z;
+    }
+    return new THREE.Box3(min, max);
   }
 
   getDataForDistancesComputation(start, end) {              // :572-581
@@ -288,7 +357,6 @@ export class SplatMesh {
   getSplatDataTextures() { return this.splatDataTextures; }
   setRenderer(renderer) { this.renderer = renderer; }
   freeIntermediateSplatData() {}                            // nothing is kept on the host
-  updateVisibleRegionFadeDistance() {}                      // SceneRevealMode.Instant semantics: fadeInComplete = 1 (:1201-1226)
 
   // :1701-1814.  Uniforms as the reference uploads them: the clip-z row of mvp (static) or of mvp * the scene's transform (dynamic,
   // one per scene), as Math.round(x * 1000) integers or as fp32.  The pass runs synchronously, so the Promise resolves with

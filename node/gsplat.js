@@ -261,6 +261,14 @@ class SplatMeshHIP {
     this.fadeIn = sceneCenter !== null && sceneCenter !== undefined;
     if (this.fadeIn) { this.cam.sceneCenter.set(sceneCenter); this.cam.fadeStartRadius = fadeStartRadius; }
   }
+  // Where splats [from, from + count) are (gs_mesh_bounds, reduced on the device): {count - the splats that took part (a NaN
+  // component excludes one), min / max - the box of the centres as a Float32Array holds them, maxDistSq - the largest
+  // |c - center|^2 in double, in three.js's operation order}.  transforms (16 numbers per scene, column-major): applied to every
+  // centre first as THREE.Vector3.applyMatrix4 does, by the splat's scene index.  SplatMesh.updateVisibleRegion's loop (the
+  // caller takes Math.sqrt) and SplatMesh.computeBoundingBox's in one pass.
+  bounds(from, count, center, transforms) {
+    return addon.meshBounds(this.handle, from >>> 0, count >>> 0, Float64Array.from(center), transforms ? Float64Array.from(transforms) : null);
+  }
   getSplatCount() { return this.splatCount; }
   updateRenderIndexes(globalIndexes, renderSplatCount) { this.indexes = globalIndexes; this.sortWorker = null; this.renderCount = renderSplatCount; }
   useSortWorkerResult(worker, renderSplatCount) { this.sortWorker = worker; this.indexes = null; this.renderCount = renderSplatCount; }

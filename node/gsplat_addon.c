@@ -910,6 +910,34 @@ static napi_value MeshSurface(napi_env env, napi_callback_info info) {
     if (st < 0) return throw_gs(env, st);
     return NULL;
 }
+/* meshBounds(mesh, from, count, center Float64Array[3], transforms Float64Array[16 * scenes]|null) -> {count, min: [x, y, z], max: [x, y, z],
+ * maxDistSq}: gs_mesh_bounds over splats [from, from + count) - the box of their centres and the largest squared distance from `center`,
+ * with the scenes' transforms applied first when given (SplatMesh.updateVisibleRegion / computeBoundingBox on the device) */
+static napi_value MeshBounds(napi_env env, napi_callback_info info) {
+    ARGS(5)
+    void *center, *xf;
+    size_t cb, xb;
+    if (!get_bytes(env, argv[3], &center, &cb) || !center || !get_bytes(env, argv[4], &xf, &xb)) { napi_throw_type_error(env, NULL, "meshBounds: center / transforms"); return NULL; }
+    if (cb != 24 || (xf && (xb == 0 || xb % 128 != 0))) { napi_throw_range_error(env, NULL, "meshBounds: center is 3 doubles, transforms 16 doubles per scene"); return NULL; }
+    gs_bounds b;
+    int st;
+    LOCKED(st = gs_mesh_bounds((gs_mesh*)get_external(env, argv[0]), get_u32(env, argv[1]), get_u32(env, argv[2]), (const double*)center,
+                            (const double*)xf, (uint32_t)(xb / 128), xf ? GS_BOUNDS_TRANSFORM : 0u, &b));
+    if (st < 0) return throw_gs(env, st);
+    napi_value r, mn, mx;
+    NAPI_OK(napi_create_object(env, &r));
+    NAPI_OK(napi_create_array_with_length(env, 3, &mn));
+    NAPI_OK(napi_create_array_with_length(env, 3, &mx));
+    for (uint32_t k = 0; k < 3; k++) {
+        napi_set_element(env, mn, k, num(env, b.box_min[k]));
+        napi_set_element(env, mx, k, num(env, b.box_max[k]));
+    }
+    set(env, r, "count", (double)b.count);
+    napi_set_named_property(env, r, "min", mn);
+    napi_set_named_property(env, r, "max", mx);
+    set(env, r, "maxDistSq", b.max_dist_sq);
+    return r;
+}
 static napi_value Init(napi_env env, napi_value exports) {
     addon_state* state = (addon_state*)calloc(1, sizeof *state);
     if (!state || pthread_mutex_init(&state->lock, NULL) != 0 || napi_set_instance_data(env, state, state_free, NULL) != napi_ok) {
@@ -932,7 +960,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
         {"meshUploadAsset", MeshUploadAsset}, {"sorterUploadAssetCenters", SorterUploadAssetCenters},
-        {"meshSurface", MeshSurface},
+        {"meshSurface", MeshSurface},       {"meshBounds", MeshBounds},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
