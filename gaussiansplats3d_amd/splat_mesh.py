@@ -450,11 +450,14 @@ class SplatMesh:
             L.check(self.lib.gs_mesh_debug_read(self.handle, 9, slots.ctypes.data, self.splat_count))
         return rng, entries, slots
 
-    def blend_bin_stats(self):
-        """Per 32-px blend bin of the last FULL-frame draw: (entries scanned, 2 x (splat, quadrant) pairs composited),
-        [bin_rows, bins_x, 2]."""
+    def blend_bin_stats(self, tile_rows=None):
+        """Per 32-px blend bin of the last draw - the full frame, or the strip `tile_rows` it drew: (entries scanned, 2 x (splat,
+        quadrant) pairs composited), [bin_rows, bins_x, 2], row 0 = the strip's first bin row."""
         cam = self._cam
-        bx, by = (cam.width + L.GS_BIN - 1) // L.GS_BIN, (cam.height + L.GS_BIN - 1) // L.GS_BIN
+        rows_total = (cam.height + L.GS_TILE - 1) // L.GS_TILE
+        r0, r1 = (0, rows_total) if tile_rows is None else tile_rows
+        y0, y1 = r0 * L.GS_TILE, min(r1 * L.GS_TILE, cam.height)
+        bx, by = (cam.width + L.GS_BIN - 1) // L.GS_BIN, (y1 + L.GS_BIN - 1) // L.GS_BIN - y0 // L.GS_BIN
         out = np.zeros((by * bx, 2), dtype=np.uint32)
         L.check(self.lib.gs_mesh_debug_read(self.handle, 4, out.ctypes.data, by * bx))
         return out.reshape(by, bx, 2)

@@ -4,7 +4,9 @@ Below one chunk that is the plain composite (every other GPU test); here the lis
 saturate.  Checked: the per-bin kernel (which closes chunks itself) and the deep pass (one wave per quadrant and chunk + a fold)
 produce the SAME bits; strips of a multi-GPU draw (with the per-rank visibility-culled sort) and both list-bin sizes reproduce the
 full frame bit for bit; the frame meets the same tolerance against the fp32 oracle as every other frame; lists too long for the
-deep pass's tables stay with the per-bin kernel."""
+deep pass's tables stay with the per-bin kernel.
+(That the two executors are RIGHT - each against a host model of the definition, on scenes that put survivor counts on both sides of
+every chunk edge - is tests/test_gpu_deep_edges.py.)"""
 import numpy as np
 import pytest
 
