@@ -353,6 +353,17 @@ struct gs_sorter {
     uint32_t dev_distances_count = 0;  // the mesh's uploaded splat count when they were computed
     bool dev_distances_integer = false;
     hipEvent_t ev_handover = nullptr;  // orders that hand-over between the context's stream and this sorter's
+    // The extreme set of the centres (extreme_set.hpp; static integer sorters only): AoS x4 rows that hold every hull vertex of
+    // the uploaded centres.  A sort's exact key range is its min / max over these rows (sorter.hip, sort_known_range).
+    std::vector<int32_t> extreme;
+    bool extreme_ok = true;            // a set exists (no centres: the empty one); false: it did not fit GS_EXTREME_CAP
+    uint32_t extreme_version = 0;      // the centers_version it covers: valid <=> extreme_ok && extreme_version == centers_version
+    // Pass 0's group rows alternate between slots 0 and 3 of RadixScratch::digit_total: k_depth_key_hist adds to them inside the
+    // launch that zeroes the others, so they are zeroed a sort earlier (a depth sort has <= 3 passes: slot 3 is otherwise unused).
+    uint32_t clean_slot = 3;           // zero at the start of the next sort, whatever path the last one took
+    bool last_known_range = false;     // what gs_sorter_debug_read(what = 4) reports of the last sort
+    int32_t last_range_lo = 0, last_range_hi = 0;
+    uint32_t last_pass0_slot = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------

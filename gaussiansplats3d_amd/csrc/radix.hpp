@@ -756,12 +756,13 @@ inline uint32_t radix_grid_for(uint32_t n_upper) {
 
 // What every pass launches: the histogram over `grid` workgroups into the scratch's rows, then `scatter(atomic_rank, bh, dt)`
 // on the same grid with ATOMIC_RANK as a compile-time bool.  pass_slot picks the zeroed digit_total row (the caller zeroes
-// RadixScratch::digit_total once per frame).
+// RadixScratch::digit_total once per frame).  skip_hist: the kernel in front of this pass already left the rows of this grid and
+// slot (sorter.hip, k_depth_key_hist).
 template <class HistLoader, class Scatter>
-int radix_launch(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, uint32_t grid, int pass_slot, Scatter&& scatter) {
+int radix_launch(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, uint32_t grid, int pass_slot, bool skip_hist, Scatter&& scatter) {
     uint32_t* bh = ex.scratch->block_hist.as<uint32_t>();
     uint32_t* dt = ex.scratch->digit_total.as<uint32_t>() + pass_slot * RADIX_MAX_GROUPS * RADIX_BINS;
-    hipLaunchKernelGGL((k_radix_hist<HistLoader>), dim3(grid), dim3(HIST_THREADS), 0, ex.stream, ld_hist, hist_shift, bh, dt);
+    if (!skip_hist) hipLaunchKernelGGL((k_radix_hist<HistLoader>), dim3(grid), dim3(HIST_THREADS), 0, ex.stream, ld_hist, hist_shift, bh, dt);
     if (ex.atomic_rank) scatter(std::true_type(), bh, dt);
     else scatter(std::false_type(), bh, dt);
     GS_HIP(hipGetLastError());
@@ -772,9 +773,9 @@ int radix_launch(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift,
 template <class HistLoader, class Loader, class KeyOutT, bool WRITE_KEYS, bool RANGES, bool PACK_OUT>
 int radix_pass_ex(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
                   int pass_slot, KeyOutT* keys_out, uint32_t* vals_out, uint2* ranges, uint32_t direct_ranges, uint32_t val_bits,
-                  uint32_t* count_out = nullptr) {
+                  uint32_t* count_out = nullptr, bool skip_hist = false) {
     const uint32_t grid = radix_grid_for(n_upper);
-    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
+    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, skip_hist, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
         hipLaunchKernelGGL((k_radix_scatter<Loader, KeyOutT, WRITE_KEYS, RANGES, decltype(atomic)::value, PACK_OUT>), dim3(grid),
                            dim3(SCATTER_THREADS), 0, ex.stream, ld, shift, bh, dt, keys_out, vals_out, ranges, direct_ranges, val_bits, count_out);
     });
@@ -783,9 +784,9 @@ int radix_pass_ex(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift
 // A pass of the depth sort between / after packing passes (see k_radix_scatter_chunk); the caller checked radix_chunk_grid_for.
 template <class HistLoader, class Loader, bool PACK_OUT>
 int radix_pass_chunk(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
-                     int pass_slot, uint32_t* out, uint32_t val_bits, uint32_t* count_out = nullptr) {
+                     int pass_slot, uint32_t* out, uint32_t val_bits, uint32_t* count_out = nullptr, bool skip_hist = false) {
     const uint32_t grid = radix_chunk_grid_for(n_upper);
-    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
+    return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, skip_hist, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
         hipLaunchKernelGGL((k_radix_scatter_chunk<Loader, PACK_OUT, decltype(atomic)::value>), dim3(grid), dim3(CHUNK_THREADS), 0,
                            ex.stream, ld, shift, bh, dt, out, val_bits, count_out);
     });

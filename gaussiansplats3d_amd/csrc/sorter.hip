@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "extreme_set.hpp"
 #include "radix.hpp"
 
 // WASM (emscripten) float->int: NaN / out of range -> INT32_MIN (same rule as oracle/sort_oracle.c)
@@ -138,9 +139,12 @@ __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g)
 
 // The housekeeping folded into the first kernel of a sort (two launches and their boundaries saved per sort): the radix digit
 // totals are zeroed before any histogram adds to them, and the OTHER SortFrame is reset for the next sort.  t / stride: the
-// thread's index in the grid / the grid's size.
-__device__ __forceinline__ void sort_begin(const KeyParams& p, uint32_t t, uint32_t stride) {
-    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride) p.digit_total[w] = 0u;
+// thread's index in the grid / the grid's size.  keep_slot: the slot of group rows this launch itself adds to (k_depth_key_hist) -
+// left alone here, zeroed by the sort before (gs_sorter::clean_slot).
+constexpr uint32_t RADIX_SLOT_WORDS = RADIX_MAX_GROUPS * RADIX_BINS;
+__device__ __forceinline__ void sort_begin(const KeyParams& p, uint32_t t, uint32_t stride, uint32_t keep_slot = 0xFFFFFFFFu) {
+    for (uint32_t w = t; w < (uint32_t)RADIX_TOTAL_WORDS; w += stride)
+        if (w / RADIX_SLOT_WORDS != keep_slot) p.digit_total[w] = 0u;
     if (t < SORT_SHARDS) {
         p.next_frame->key_min[t] = KEY_MIN_INIT;
         p.next_frame->key_max[t] = KEY_MAX_INIT;
@@ -853,11 +857,16 @@ struct DepthLoaderT : DepthLoaderArgs {
             lo = min(lo, __shfl_xor(lo, o, 64));
             hi = max(hi, __shfl_xor(hi, o, 64));
         }
-        // sorter.cpp:142-143: (float)(range-1) / ((float)max - (float)min), fp32, correctly rounded
-        range_map = __fdiv_rn((float)(range - 1), __fsub_rn((float)hi, (float)lo));
+        set_known_range(lo, hi);
         // wave-uniform by construction: keep both in scalar registers
         lo = __builtin_amdgcn_readfirstlane(lo);
         range_map = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(range_map)));
+    }
+    // the sort's min and max themselves (k_depth_key_hist has them as kernel arguments)
+    __device__ __forceinline__ void set_known_range(int32_t key_lo, int32_t key_hi) {
+        lo = key_lo;
+        // sorter.cpp:142-143: (float)(range-1) / ((float)max - (float)min), fp32, correctly rounded
+        range_map = __fdiv_rn((float)(range - 1), __fsub_rn((float)key_hi, (float)key_lo));
     }
     __device__ __forceinline__ uint32_t count() const { return render_count - sort_start; }
     __device__ __forceinline__ uint32_t bucket(uint32_t i) const { return bucket_of<false>(keys[i]); }
@@ -944,6 +953,80 @@ __global__ void k_unmap(const uint32_t* __restrict__ in, const uint32_t* __restr
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = unmap[min(in[i], last)];
 }
 
+// Phase A + the histogram of pass 0 in ONE streaming launch, for a sort whose exact key range the host already knows: a full sort
+// of the identity list in static integer mode whose keys cannot wrap (sort_known_range: min / max of im . c over the extreme set of
+// the centres, extreme_set.hpp).  A key's bucket needs the min and max over ALL keys (sorter.cpp:142-146); here they are kernel
+// arguments, so a workgroup buckets and counts its keys as it makes them: no min / max reduction, no wait for another workgroup,
+// no k_radix_hist and no re-read of the keys.  The grid is pass 0's scatter grid and a workgroup keys ITS chunk of that pass
+// (radix_chunk; logical element j = list position R - 1 - j), tile after tile, so row ch.id and the group rows are what the scatter
+// expects - also for lists too long for the chunk-staged scatter, where pass 0 runs the tile kernel over longer chunks.
+// The range goes into every shard of the sort's SortFrame with plain stores: DepthLoader::prepare of the scatter, k_debug_buckets
+// and the statistics read it as ever.  The group rows of pass 0 (`group_rows`, slot keep_slot) are added to inside this launch, so
+// sort_begin leaves them alone: they were zeroed by the sort before (gs_sorter::clean_slot).
+constexpr uint32_t KEY_HIST_VECS = 3;      // 16-byte vectors per plane a thread has in flight (one chunk of the chunk-staged pass)
+__global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, DepthLoader ld, int32_t key_lo, int32_t key_hi, int shift,
+                                                                  uint32_t keep_slot, uint32_t* __restrict__ block_hist,
+                                                                  uint32_t* __restrict__ group_rows) {
+    __shared__ uint32_t s_hist[4][RADIX_BINS];               // waves w, w+4, w+8, w+12 share one
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * HIST_THREADS + tid;
+    sort_begin(p, t, gridDim.x * HIST_THREADS, keep_slot);
+    if (t < SORT_SHARDS) {
+        p.frame->key_min[t] = key_lo;
+        p.frame->key_max[t] = key_hi;
+    }
+    ld.set_known_range(key_lo, key_hi);
+    for (uint32_t k = tid; k < 4u * RADIX_BINS; k += HIST_THREADS) (&s_hist[0][0])[k] = 0;
+    __syncthreads();
+    uint32_t* hist = s_hist[(tid >> 6) & 3u];
+    const uint32_t R = p.render_count;
+    const RadixChunk ch = radix_chunk(R);
+    // this chunk's logical elements [j0, j1) are list positions [R - j1, R - j0)
+    const uint32_t j0 = min(ch.tile_begin * (uint32_t)RADIX_TILE, R), j1 = min(ch.tile_end * (uint32_t)RADIX_TILE, R);
+    const uint32_t p0 = R - j1, p1 = R - j0;
+    auto count = [&](int32_t k) { atomicAdd(&hist[(ld.hist_key(k) >> shift) & 255u], 1u); };     // (hist_key counts a clamp)
+    auto scalars = [&](uint32_t begin, uint32_t end) {
+        for (uint32_t i = begin + tid; i < end; i += HIST_THREADS) {
+            const int32_t k = static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
+            p.keys_out[i] = k;
+            count(k);
+        }
+    };
+    // positions [a4 * 4, b4 * 4) as 16-byte vectors, the ragged head and tail one at a time (k_depth_key<true>'s cut)
+    const uint32_t a4 = (p0 + 3u) / 4u, b4 = p1 / 4u;
+    if (a4 < b4) {
+        scalars(p0, a4 * 4u);
+        scalars(b4 * 4u, p1);
+        const uint4* x4 = reinterpret_cast<const uint4*>(p.cx);
+        const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
+        const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
+        int4* o4 = reinterpret_cast<int4*>(p.keys_out);
+        for (uint32_t v0 = a4; v0 < b4; v0 += KEY_HIST_VECS * HIST_THREADS) {
+            uint4 x[KEY_HIST_VECS], y[KEY_HIST_VECS], z[KEY_HIST_VECS];
+#pragma unroll
+            for (uint32_t k = 0; k < KEY_HIST_VECS; k++) {                 // (unconditional loads of clamped positions: one batch)
+                const uint32_t v = min(v0 + k * HIST_THREADS + tid, b4 - 1u);
+                x[k] = x4[v]; y[k] = y4[v]; z[k] = z4[v];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < KEY_HIST_VECS; k++) {
+                const uint32_t v = v0 + k * HIST_THREADS + tid;
+                const int4 key = static_key_int4(p, x[k], y[k], z[k]);
+                if (v < b4) {
+                    o4[v] = key;
+                    count(key.x); count(key.y); count(key.z); count(key.w);
+                }
+            }
+        }
+    } else {                                               // fewer than one aligned vector
+        scalars(p0, p1);
+    }
+    __syncthreads();
+    if (tid >= RADIX_BINS || ch.tile_begin >= ch.tile_end) return;      // (a workgroup without tiles has no row)
+    const uint32_t total = s_hist[0][tid] + s_hist[1][tid] + s_hist[2][tid] + s_hist[3][tid];
+    block_hist[ch.id * RADIX_BINS + tid] = total;
+    if (total) atomicAdd(&group_rows[(ch.id / RADIX_GROUP) * RADIX_BINS + tid], total);   // (k_radix_hist's two-level table)
+}
+
 __global__ void k_debug_buckets(DepthLoader ld, int32_t* out) {
     ld.prepare();
     for (uint32_t i = ld.sort_start + blockIdx.x * blockDim.x + threadIdx.x; i < ld.render_count;
@@ -960,6 +1043,8 @@ struct Pass0Args {
     void* kbuf0;
     uint32_t* vo;
     uint32_t* kept_out;
+    int slot;                           // pass 0's slot of group rows (0, or gs_sorter::clean_slot of a known-range sort)
+    bool skip_hist;                     // k_depth_key_hist already left pass 0's histogram rows
 };
 template <bool CULL, bool IDX>
 static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
@@ -967,10 +1052,10 @@ static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
     const L d = {a.ld};
     L h = d;                            // only the histogram launch counts clamped buckets (once per element)
     h.count_clamps = 1;
-    if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, a.vo, a.val_bits, a.kept_out);
-    if (a.pack) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint8_t*)nullptr, a.vo, nullptr, 0u, a.val_bits, a.kept_out);
-    if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out);
-    return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, 0, (uint16_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out);
+    if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, a.vo, a.val_bits, a.kept_out, a.skip_hist);
+    if (a.pack) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint8_t*)nullptr, a.vo, nullptr, 0u, a.val_bits, a.kept_out, a.skip_hist);
+    if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
+    return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint16_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
 }
 
 static inline uint32_t grid_for(uint32_t n, uint32_t per_block, uint32_t cap) {
@@ -1061,6 +1146,46 @@ void gs_sorter_destroy(gs_sorter* s) {
 }
 
 static void sorter_tell_mesh(gs_sorter* s);   // (defined with gs_sorter_bind_mesh)
+
+// $GSPLAT_NO_KNOWN_RANGE: no extreme set is kept and every sort takes the key kernel + histogram kernel path (read once per process)
+static bool known_range_off() {
+    static const bool off = getenv("GSPLAT_NO_KNOWN_RANGE") != nullptr;
+    return off;
+}
+
+// The extreme set follows the centres (static integer sorters): called after centers_version moved on, with the stream idle.
+// Rows [from, end) of `caos` were written (zero_fill: with zeros), old_uploaded rows were in use before.  hull(old U new) =
+// hull(set(old) U new): a range behind the old rows extends the set, a range that overwrites old rows rebuilds it from every row.
+// The rows are read back from the device - one path for centres from the host, from an asset's decode and for never-written gaps.
+static int sorter_update_extreme(gs_sorter* s, uint32_t from, uint32_t end, uint32_t old_uploaded, bool zero_fill) {
+    if (s->flags != GS_SORT_INTEGER || known_range_off()) return GS_OK;
+    const bool current = s->extreme_ok && s->extreme_version + 1u == s->centers_version;   // it covered the centres until now
+    const bool append = from >= old_uploaded;
+    if (append && !current) {                              // no set to extend: none until an overwrite rebuilds it
+        s->extreme_ok = false;
+        return GS_OK;
+    }
+    const uint32_t first = append ? old_uploaded : 0u, last = end > old_uploaded ? end : old_uploaded;
+    std::vector<int32_t> rows, out;
+    try {
+        if (zero_fill && append) rows.assign(4, 0);        // (0, 0, 0), as often as it likes
+        else rows.resize((size_t)(last - first) * 4);
+    } catch (const std::bad_alloc&) {
+        s->extreme_ok = false;
+        return GS_OK;
+    }
+    if (!(zero_fill && append) && last > first) {
+        GS_HIP(hipMemcpyAsync(rows.data(), s->caos.as<uint4>() + first, (size_t)(last - first) * 16, hipMemcpyDeviceToHost, s->stream));
+        GS_HIP(hipStreamSynchronize(s->stream));
+    }
+    const bool prior = append && !s->extreme.empty();
+    s->extreme_ok = gs_extreme_set(prior ? s->extreme.data() : nullptr, prior ? s->extreme.size() / 4 : 0, rows.data(), rows.size() / 4,
+                                   GS_EXTREME_CAP, out);
+    s->extreme.swap(out);
+    s->extreme_version = s->centers_version;
+    return GS_OK;
+}
+
 int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const void* centers_aos4,
                              const uint32_t* scene_indexes) {
     GS_REQUIRE(s && centers_aos4, "sorter / centers == NULL");
@@ -1086,8 +1211,10 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     if (s->flags & GS_SORT_DYNAMIC)
         GS_HIP(hipMemcpyAsync(s->scene_idx.as<uint32_t>() + from, scene_indexes, (size_t)count * 4, hipMemcpyHostToDevice, st));
     GS_HIP(hipStreamSynchronize(st));   // staging and the caller's buffers are reusable on return
+    const uint32_t old_uploaded = s->uploaded;
     if (from + count > s->uploaded) s->uploaded = from + count;   // uploadedSplatCount, SortWorker.js:97
     s->centers_version++;
+    GS_TRY(sorter_update_extreme(s, from, from + count, old_uploaded, false));
     sorter_tell_mesh(s);                                   // (more centres than the bound mesh holds: no position map, no derived mask)
     return GS_OK;
 }
@@ -1108,6 +1235,7 @@ int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
     GS_HIP(hipStreamSynchronize(st));
     s->uploaded = count;
     s->centers_version++;
+    GS_TRY(sorter_update_extreme(s, (uint32_t)from, count, (uint32_t)from, true));
     sorter_tell_mesh(s);
     return GS_OK;
 }
@@ -1143,13 +1271,14 @@ struct SortSwitches {
     const char* vis_front;     // $GSPLAT_VIS_FRONT = stream | compact: forces one front end of the visibility cull
     bool no_pack;              // $GSPLAT_NO_SORT_PACK: the unpacked radix passes
     bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
+    bool no_known_range;       // $GSPLAT_NO_KNOWN_RANGE: never k_depth_key_hist (and no extreme set: sorter_update_extreme)
 };
 static SortSwitches sort_switches() {
     static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
     static const char* vis_front = getenv("GSPLAT_VIS_FRONT");
     static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
     static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
-    return {tree_no_fuse, vis_front, no_pack, no_chunk};
+    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off()};
 }
 
 static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
@@ -1193,7 +1322,57 @@ struct SortPlan {
     // launch_front_end
     bool vec4;                         // identity list + static integer mode
     bool vis_front;                    // the visibility cull's front end wrote keys and payloads of the survivors itself
+    bool known_range;                  // k_depth_key_hist keyed the list and left pass 0's histogram (sort_known_range)
+    int32_t range_lo, range_hi;        // ... with this exact key range
+    uint32_t pass0_slot;               // pass 0's slot of group rows
 };
+
+// How pass 0 of the radix sort runs, for run_radix_passes and for the kernel that leaves its histogram ahead of it.
+struct Pass0Shape { bool pack, chunked; uint32_t grid; };
+static Pass0Shape pass0_shape(const gs_sorter* s, const SortPlan& pl) {
+    Pass0Shape sh;
+    // Packed passes stage a whole chunk in LDS (radix.hpp) when the list is short enough for <= CHUNK_TILES tiles per
+    // workgroup and the payload leaves 8 bits for the digit beside it in the last pass's staging word.
+    sh.chunked = !pl.sw.no_chunk && pl.val_bits <= 24u && radix_chunk_grid_for(pl.Rs) != 0u;
+    sh.pack = s->precision > 8u && !pl.sw.no_pack && (s->precision - 8u) + pl.val_bits <= 32u;
+    sh.grid = (sh.pack && sh.chunked) ? radix_chunk_grid_for(pl.Rs) : radix_grid_for(pl.Rs);
+    return sh;
+}
+
+// The exact key range of a sort, known before anything is launched: min / max of im . c over the extreme set.  Only the plain full
+// sort of every uploaded centre in static integer mode, and only when neither end leaves int32 - then no key wraps, every key is
+// its true value, and [lo, hi] is what the device-wide reduction would find.  Everything else keeps the key kernel + histogram path.
+static bool sort_known_range(const gs_sorter* s, const SortPlan& pl, const KeyParams& kp, int32_t& lo_out, int32_t& hi_out) {
+    if (pl.sw.no_known_range || kp.mode != MODE_INT || pl.idx_dev || pl.device_list || pl.fused_tree || pl.vis_cull || pl.cull ||
+        pl.list_count_dev || pl.sort_start != 0u || pl.R != s->uploaded || pl.R == 0u)
+        return false;
+    if (!s->extreme_ok || s->extreme_version != s->centers_version || s->extreme.empty()) return false;
+    const int32_t* c = s->extreme.data();
+    const size_t n = s->extreme.size() / 4;
+    const int64_t a0 = kp.im0, a1 = kp.im1, a2 = kp.im2;
+    const int64_t small = (int64_t)1 << 29;                // |im| <= 2^29: three products of at most 2^60 add up in int64
+    __int128 lo, hi;
+    if (a0 >= -small && a0 <= small && a1 >= -small && a1 <= small && a2 >= -small && a2 <= small) {
+        int64_t l = INT64_MAX, h = INT64_MIN;
+        for (size_t i = 0; i < n; i++) {
+            const int64_t v = a0 * c[4 * i] + a1 * c[4 * i + 1] + a2 * c[4 * i + 2];
+            l = v < l ? v : l;
+            h = v > h ? v : h;
+        }
+        lo = l; hi = h;
+    } else {
+        lo = hi = (__int128)a0 * c[0] + (__int128)a1 * c[1] + (__int128)a2 * c[2];
+        for (size_t i = 1; i < n; i++) {
+            const __int128 v = (__int128)a0 * c[4 * i] + (__int128)a1 * c[4 * i + 1] + (__int128)a2 * c[4 * i + 2];
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+    }
+    if (lo < INT32_MIN || hi > INT32_MAX) return false;    // a key could wrap
+    lo_out = (int32_t)lo;
+    hi_out = (int32_t)hi;
+    return true;
+}
 
 // 1. argument checks and count clamps; what the flags and the bound mesh make of the call
 static int sort_check(gs_sorter* s, uint32_t sort_count, uint32_t render_count, SortPlan& pl) {
@@ -1445,7 +1624,18 @@ static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     hipStream_t st = s->stream;
     const uint32_t cus = (uint32_t)ctx->cu_count;
     pl.vec4 = (kp.mode == MODE_INT) && !pl.idx_dev;
-    if (pl.fused_tree) {
+    pl.known_range = sort_known_range(s, pl, kp, pl.range_lo, pl.range_hi);
+    pl.pass0_slot = pl.known_range ? s->clean_slot : 0u;
+    // every other front end zeroes all four slots and the passes use slots 0 .. 2; the known-range kernel zeroes all but its own
+    s->clean_slot = pl.pass0_slot == 3u ? 0u : 3u;
+    if (pl.known_range) {
+        DepthLoaderArgs hl = {};
+        hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
+        hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
+        hipLaunchKernelGGL(k_depth_key_hist, dim3(pass0_shape(s, pl).grid), dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo,
+                           pl.range_hi, 0, pl.pass0_slot, s->radix.block_hist.as<uint32_t>(),
+                           s->radix.digit_total.as<uint32_t>() + pl.pass0_slot * RADIX_SLOT_WORDS);
+    } else if (pl.fused_tree) {
         GS_TRY(launch_tree_front(s, pl, kp));
     } else if (pl.vis_cull) {
         GS_TRY(launch_vis_cull_front(s, pl, kp));
@@ -1486,9 +1676,7 @@ static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& k
     // payload in one 32-bit word (payloads are splat positions < uploaded: 23 bits at 5.8 M splats, 24 at 16 M, so the default
     // 16-bit buckets always do below 2^24 splats) the pass writes that word instead of a key array and a value array
     // (radix.hpp PACK_OUT); otherwise 16- or 32-bit keys + values as before, and a later pass packs as soon as it can.
-    // Packed passes stage a whole chunk in LDS (radix.hpp) when the list is short enough for <= CHUNK_TILES tiles per
-    // workgroup and the payload leaves 8 bits for the digit beside it in the last pass's staging word.
-    const bool chunked = !pl.sw.no_chunk && val_bits <= 24u && radix_chunk_grid_for(Rs) != 0u;
+    const bool chunked = pass0_shape(s, pl).chunked;
     const bool wide = s->precision > 16;
     // after a culling pass 0 the element count is the device-resident kept count
     const uint32_t* n_dev = (pl.cull || pl.vis_cull || pl.list_count_dev) ? &kp.frame->kept : nullptr;
@@ -1504,6 +1692,8 @@ static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& k
             a.ld = dl; a.Rs = Rs; a.val_bits = val_bits; a.shift = shift;
             a.pack = pack; a.chunked = chunked; a.wide = wide; a.kbuf0 = kbuf[0]; a.vo = vo;
             a.kept_out = pl.cull ? &kp.frame->kept : nullptr;      // a culling pass 0 compacts: it publishes the result's length
+            a.slot = (int)pl.pass0_slot;
+            a.skip_hist = pl.known_range;
             const bool has_idx = dl.idx != nullptr;
             if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
             else if (pl.cull) GS_TRY((depth_pass0<true, false>(ex, a)));
@@ -1543,6 +1733,10 @@ static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, ui
     s->last_render = pl.R;
     s->last_sort = pl.Rs;
     s->last_passes = passes;
+    s->last_known_range = pl.known_range;
+    s->last_range_lo = pl.known_range ? pl.range_lo : 0;
+    s->last_range_hi = pl.known_range ? pl.range_hi : 0;
+    s->last_pass0_slot = pl.pass0_slot;
     s->last_identity = (pl.idx_dev == nullptr);
     s->last_culled = (pl.cull || pl.vis_cull || pl.list_count_dev) && pl.Rs > 0;   // the result's length lives in result_frame->kept
     s->last_vis_culled = pl.vis_cull && pl.Rs > 0;
@@ -1658,6 +1852,16 @@ int gs_sorter_last_stats(gs_sorter* s, gs_sort_stats* stats) {
 int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     GS_REQUIRE(s && dst, "sorter / dst == NULL");
     GS_REQUIRE(s->has_result, "no sort has run");
+    if (what == 4) {
+        // the last sort's front end, host words: {1 = k_depth_key_hist with a known range, |extreme set| (0: none), lo, hi as the
+        // host computed them (0, 0 on the other path), 1 = the set covers the current centres, pass 0's slot of group rows}
+        const bool valid = s->extreme_ok && s->extreme_version == s->centers_version;
+        const int32_t w[6] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
+                              valid ? 1 : 0, (int32_t)s->last_pass0_slot};
+        GS_REQUIRE(count <= 6u, "selector 4 holds 6 words");
+        memcpy(dst, w, (size_t)count * 4);
+        return GS_OK;
+    }
     GS_REQUIRE(count <= s->last_render, "count exceeds the last render_count");
     ScopedDevice sd(s->ctx->device);
     hipStream_t st = s->stream;

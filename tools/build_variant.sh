@@ -10,7 +10,7 @@ SRC=${GS_VARIANT_SRC:-$ROOT/gaussiansplats3d_amd/csrc}     # (GS_VARIANT_SRC: an
 OUT=$ROOT/gpurun_ab; OBJ=/tmp/gsvar_$NAME
 rm -rf $OBJ
 mkdir -p $OUT $OBJ/gaussiansplats3d_amd/csrc $OBJ/include
-cp $SRC/Makefile $SRC/*.hip $SRC/*.hpp $OBJ/gaussiansplats3d_amd/csrc/
+cp $SRC/Makefile $SRC/*.hip $SRC/*.hpp $(ls $SRC/*.cpp 2>/dev/null) $OBJ/gaussiansplats3d_amd/csrc/     # (*.cpp: host-only sources, none in older trees)
 cp $SRC/../../include/*.h $OBJ/include/
 make -s -C $OBJ/gaussiansplats3d_amd/csrc -j${MAX_JOBS:-16} libgsplat_hip.so \
      CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function $*"
