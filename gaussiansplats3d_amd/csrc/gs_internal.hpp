@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
+#include "draw_plan.hpp"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -89,27 +90,7 @@ struct DevBuf {
 // ---------------------------------------------------------------------------------------------------
 // radix sort geometry (radix.hpp)
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t GS_BIN_SHIFT = 1;                       // a blend workgroup owns a bin of 2x2 tiles of 16 px = 32x32 px
-constexpr uint32_t GS_BIN = GS_TILE << GS_BIN_SHIFT;
-// The entry lists are per LIST BIN of (16 << GS_LIST_SHIFT) px.  The blend reads only the head of a list before its pixels
-// saturate (C3: the first 256 of ~2900 entries per 32-px bin, tools/blend_profile.py), so emitting and sorting per-32-px
-// entries mostly produced entries nobody read.  128-px list bins cut the entries 3.7x and their sort to ONE 8-bit pass at
-// 1080p (15 x 9 = 135 lists); a blend workgroup scans its parent list and keeps what touches its own 32-px block.
-// That only pays when splats are large enough to share lists: a scene of many tiny splats (C4: 16 M splats of ~1.5 tiles)
-// gains no entries and makes every blend workgroup scan 16 bins' worth of them, so the size is chosen per mesh from the
-// statistics of its last measured draw (gs_mesh::list_shift): 128 px when a visible splat covers >= 3 tiles, else 32 px.
-constexpr uint32_t GS_LIST_SHIFT_LARGE = 3;                // 128-px list bins
-constexpr uint32_t GS_LIST_SHIFT_SMALL = GS_BIN_SHIFT;     // 32-px list bins = one list per blend workgroup
-constexpr float GS_LIST_TILES_PER_SPLAT = 3.0f;
-// ... and 256- / 512-px list bins when splats are larger still: what matters is the list bin's area against the splat's (a bin
-// scans the entries of its whole list): 128 px at 10 tiles per splat (C3) is 6x, and lists of 36x (C2 at 256 px) or 100x (C3T at
-// 512 px) make the blend scan itself to a standstill (r04 tools/list_shift_ab.py: C2 0.281 -> 0.372 -> 0.947 ms at 128 / 256 / 512
-// px, C3T 0.598 -> 0.906 -> 2.20).  So the size follows the splats at <= ~12x: 256 px from 21 tiles per visible splat, 512 px
-// from 80 (an 8K frame of the garden stand-in covers 101: entries 5.96 M -> 2.19 M, its 2040 lists become 135 and its two-pass
-// entry sort one pass (0.082 -> 0.022 ms), the binner 0.091 -> 0.056 ms, the blend scans 24 % more (0.654 -> 0.686 ms): frame
-// 0.903 -> 0.837 ms; a rank of eight 0.267 -> 0.228 ms).
-constexpr uint32_t GS_LIST_SHIFT_BIG = 4, GS_LIST_SHIFT_HUGE = 5;          // 256- / 512-px list bins
-constexpr float GS_LIST_TILES_PER_SPLAT_BIG = 21.0f, GS_LIST_TILES_PER_SPLAT_HUGE = 80.0f;
+// (GS_BIN, the list-bin sizes GS_LIST_SHIFT_* and GS_DEEP_MAX_BINS: draw_plan.hpp - the host policy reads them as well)
 // CHUNKED COMPOSITE (tile_blend.hip).  The value of a pixel is DEFINED per 16x16 quadrant as a two-level fold: the quadrant's
 // ordered survivors (the entries of its list whose exact reach test includes the quadrant) are cut into chunks (below), each
 // chunk is composited front to back from T = 1, C = 0, and the chunks are merged near -> far (C = fma(T, C_c, C); T = T * T_c).
@@ -144,7 +125,7 @@ constexpr uint32_t GS_CHUNK = 1024;                         // the first (and th
 // (k_deep_scan: exact quadrant masks of every list entry + survivor counts per GS_DEEP_RLEN entries) and composited by one wave per
 // (bin, quadrant, chunk); k_deep_fold merges.  Lists longer than GS_DEEP_LIST_CAP stay with the one-workgroup-per-bin kernel, which
 // closes chunks itself (partials in a pool).
-constexpr uint32_t GS_DEEP_MAX_BINS = 512, GS_DEEP_LIST_CAP = 65536, GS_DEEP_RLEN = 1024, GS_DEEP_RANGES = GS_DEEP_LIST_CAP / GS_DEEP_RLEN;
+constexpr uint32_t GS_DEEP_LIST_CAP = 65536, GS_DEEP_RLEN = 1024, GS_DEEP_RANGES = GS_DEEP_LIST_CAP / GS_DEEP_RLEN;
 constexpr uint32_t GS_DEEP_SCAN_WGS = 32;                   // k_deep_scan workgroups per deep bin (each strides over the ranges)
 constexpr uint32_t GS_DEEP_UNITS = GS_DEEP_MAX_BINS * 4u * GS_CHUNKS_MAX;   // (bin, quadrant, chunk) waves of the deep pass
 constexpr uint32_t GS_POOL_SLOTS = 16384;                   // chunk partials (4 KB each) the per-bin kernel may close per draw
@@ -423,27 +404,16 @@ struct ProjectParams {
     uint32_t depth_mode;           // destination depth test (gs_mesh_set_destination): 0 = off, 1 = fp32 compare, 2 = as a 24-bit buffer
 };
 
-// The switches of the draw path (A/B runs and tests): read by draw_switches() (mesh.hip) and nowhere else, fetched once per
-// gs_mesh_render / gs_mesh_project and handed down.  (What a mesh or a context reads when it is created lives on gs_mesh / gs_context.)
-struct DrawSwitches {
-    // read once per process, at its first draw (the tests and the soaks start a child process per setting):
-    uint32_t deep_min;             // $GSPLAT_DEEP_MIN: (splat, quadrant) pairs a bin's previous draw walked before the deep pass takes it (4 * GS_CHUNK)
-    uint32_t deep_factor;          // $GSPLAT_DEEP_FACTOR: ... and that many times the mean bin (3)
-    uint32_t pool_slots;           // $GSPLAT_POOL_SLOTS: chunk partials the per-bin kernel may close, at most GS_POOL_SLOTS
-    bool no_lazy_mask;             // $GSPLAT_NO_LAZY_MASK: gs_mesh_project writes the by-original-index mask itself, never the bound sorter
-    // read on every draw (tests, tools and the bench set them inside a running process):
-    bool no_blend_order;           // $GSPLAT_NO_BLEND_ORDER: no schedule job, the blend's bins in row-major order
-    float order_motion;            // $GSPLAT_ORDER_MOTION: parallax, in screen heights, up to which the previous draw's order is taken (0.045)
-    bool no_stat_shift;            // $GSPLAT_NO_STAT_SHIFT: the previous draw's statistics are read unshifted
-    bool blend_order_stale;        // $GSPLAT_BLEND_ORDER_STALE: order from whatever draw came before (rounds 2-5)
-    bool deep_row_major_on_motion; // $GSPLAT_DEEP_ROW_MAJOR_ON_MOTION: a deep-pass draw of a moved camera drops the order as well
-    bool no_async_list_bins;       // $GSPLAT_NO_ASYNC_LIST_BINS: the list-bin size follows statistics reads only, not the mapped words
-    bool deep_units_last;          // $GSPLAT_DEEP_UNITS_LAST: the deep pass's workgroups behind every bin, all of them
-    float deep_share_k;            // $GSPLAT_DEEP_SHARE_K: the pass's workgroups per share of the previous walk (0.6)
-    bool deep_unit_at_set, deep_unit_wgs_set;
-    uint32_t deep_unit_at;         // $GSPLAT_DEEP_UNIT_AT: where the pass's workgroups sit in the blend's launch (tools/probes)
-    uint32_t deep_unit_wgs;        // $GSPLAT_DEEP_UNIT_WGS: ... and how many (clamped to 1 .. what the device holds by gs_launch_blend)
-};
+// the part of a draw's parameters the host policy reads (draw_plan.hpp)
+inline PlanView plan_view(const ProjectParams& pp) {
+    PlanView v;
+    memcpy(v.view, pp.view, sizeof(v.view));
+    memcpy(v.proj, pp.proj, sizeof(v.proj));
+    v.width = pp.width; v.height = pp.height; v.count = pp.count; v.list_shift = pp.list_shift;
+    return v;
+}
+
+// (struct DrawSwitches: draw_plan.hpp)
 DrawSwitches draw_switches();
 
 struct gs_mesh {
@@ -451,10 +421,8 @@ struct gs_mesh {
     uint32_t list_shift = GS_LIST_SHIFT_LARGE;     // list-bin size of the next draw (mesh_collect_stats re-evaluates it)
     uint32_t drawn_list_shift = GS_LIST_SHIFT_LARGE;   // ... of the last draw (what tile_ranges / the statistics refer to)
     ProjectParams last_pp = {};                    // the last draw's geometry (gs_mesh_debug_rop8 walks its lists)
-    ProjectParams stats_pp = {};                   // ... of the draw that wrote blend_stats (set once that draw is enqueued)
-    bool stats_pp_valid = false;
     double centre_sum[3] = {0.0, 0.0, 0.0}, centre_sq = 0.0;   // over every finite centre ever uploaded: where the scene is and how large
-    uint64_t centre_n = 0;                          // (tile_bin.hip: how far a camera moved, in screen heights)
+    uint64_t centre_n = 0;                          // (draw_plan.cpp: how far a camera moved, in screen heights)
     int forced_list_shift = -1;                    // GSPLAT_LIST_SHIFT (A/B and tests)
     uint32_t max_count = 0, sh_degree = 0, flags = 0, uploaded = 0;
     // SoA planes
@@ -512,24 +480,17 @@ struct gs_mesh {
     DevBuf fb;                 // internal RGBA8 framebuffer
     DevBuf blend_stats;        // uint2 [blend workgroups of the last draw]: {entries staged, half quadrants evaluated}, then
                                // uint32 [the same]: (splat, quadrant) pairs walked
-    uint32_t blend_bins = 0, blend_row_begin = 0, blend_width = 0;    // the bins the last draw blended
-    DevBuf deep_flags;         // uint32 words, layout above (GS_FLAG_*)
+    StatsOf stats_of = {};     // the draw blend_stats describes: its bins, draw mode and view (mesh_draw_once sets it, draw_plan.hpp)
+    DevBuf deep_flags;        // uint32 words, layout above (GS_FLAG_*)
     DevBuf chunk_pool;         // float4 [GS_POOL_SLOTS][256]: chunk partials closed by the per-bin kernel
     DevBuf deep_ent;           // uint32 [GS_DEEP_MAX_BINS][GS_DEEP_LIST_CAP]: slot | quadrant mask << 28 per list entry (deep pass)
     DevBuf deep_cnt;           // uint32 [GS_DEEP_MAX_BINS][GS_DEEP_RANGES][4]: survivors per range and quadrant
     DevBuf deep_partial;       // float4 [GS_DEEP_UNITS][256]: {C, T} of every (deep bin, quadrant, chunk)
     DevBuf deep_work;          // uint32 [GS_DEEP_UNITS]: the (bin, quadrant, chunk) units that exist, packed (k_deep_plan)
     uint32_t draw_mode = 0;    // GS_DRAW_FP32 | GS_DRAW_ROP8 (gs_mesh_set_draw_mode)
-    int32_t blend_stats_mode = 0;    // the draw mode (GS_DRAW_*) that wrote blend_stats: they schedule a later draw of the SAME mode only
     bool no_deep = false;      // GSPLAT_NO_DEEP: never launch the deep pass (the per-bin kernel draws everything)
-    bool deep_pass = false;    // this draw runs the deep pass (decided in gs_launch_binning)
     DevBuf blend_order;        // uint32 [blend bins]: this draw's bins by descending cost in the previous draw (k_bin_emit)
-    bool blend_order_valid = false;
-    struct ScheduleArgs {      // what the last draw's schedule job was given (gs_mesh_debug_read(what = 7); tests)
-        uint32_t ran, blend_bins;
-        int32_t sx, sy;
-        uint32_t deep, deep_min, deep_factor;
-    } sched = {};
+    SchedulePlan plan = {};    // what the last draw decided (gs_launch_binning; gs_mesh_debug_read(what = 7); tests)
     RadixScratch radix;
     uint32_t entry_capacity = 0;
     uint32_t sorted_buf = 0;   // ping-pong buffer index holding the tile-sorted entries of the last draw
@@ -558,8 +519,7 @@ struct gs_mesh {
     gs_render_stats last = {};
     bool has_draw = false;
     uint32_t last_count = 0;
-    uint32_t* mirror_host = nullptr;   // mapped pinned words written by every draw's k_bin_emit: [0..3] {serial, overflow, entries lo, hi},
-                                       // [4] bins over the deep pass's threshold, [5] their share of the last walk in 1 / 1024, [8..11] {serial, visible splats, 16-px tiles lo, hi}
+    uint32_t* mirror_host = nullptr;   // mapped pinned words written by every draw's k_bin_emit (GS_MIRROR_*, read_feedback: draw_plan.hpp)
     uint32_t* mirror_dev = nullptr;
     uint32_t draw_serial = 0, healed_serial = 0, adapted_serial = 0;
     uint32_t grow_entries_to = 0;         // entry capacity wanted before the next draw (the list bins became smaller: mesh.hip)
@@ -623,8 +583,8 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
 constexpr int GS_ORIG_MASK_NONE = 0, GS_ORIG_MASK_WRITE = 1, GS_ORIG_MASK_DERIVED = 2;
 int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,
                       bool whole_stage = false);
-int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
-int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, uint8_t* out_dev);
+int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
+int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, uint8_t* out_dev);
 int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev);
 int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float threshold,
                       uint32_t* ids_dev, float* depth_dev);   // either output may be null

@@ -258,14 +258,6 @@ DrawSwitches draw_switches() {
     sw.deep_row_major_on_motion = getenv("GSPLAT_DEEP_ROW_MAJOR_ON_MOTION") != nullptr;
     sw.no_async_list_bins = getenv("GSPLAT_NO_ASYNC_LIST_BINS") != nullptr;
     sw.deep_units_last = getenv("GSPLAT_DEEP_UNITS_LAST") != nullptr;
-    const char* share_k = getenv("GSPLAT_DEEP_SHARE_K");
-    sw.deep_share_k = share_k ? (float)atof(share_k) : 0.6f;
-    const char* unit_at = getenv("GSPLAT_DEEP_UNIT_AT");
-    const char* unit_wgs = getenv("GSPLAT_DEEP_UNIT_WGS");
-    sw.deep_unit_at_set = unit_at != nullptr;
-    sw.deep_unit_wgs_set = unit_wgs != nullptr;
-    sw.deep_unit_at = unit_at ? (uint32_t)atoi(unit_at) : 0u;
-    sw.deep_unit_wgs = unit_wgs ? (uint32_t)atoi(unit_wgs) : 0u;
     return sw;
 }
 
@@ -735,25 +727,6 @@ int gs_mesh_set_scenes(gs_mesh* m, const gs_scene_params* params) {
     return GS_OK;
 }
 
-// List-bin size of the following draws, from what a draw saw: the 16-px tiles its visible splats touch.  Large lists only pay when
-// splats are large enough to share them (a scene of tiny splats under 128-px lists makes every 32-px bin scan 16 bins' worth of
-// entries: the capture-like C3S stand-in draws in 4.5 ms instead of 1.2).  Fed by gs_mesh_last_stats / a draw with statistics AND by
-// the words every draw leaves in mapped host memory (mesh_read_view_share), so that a host that never asks for statistics - a
-// viewer's render loop - gets the same bins a few frames later (profiles/r06w_motion_ab.txt: the flaw this closed).
-// (with 8 % of hysteresis around each threshold: a camera that sits on one does not flip the size - and with it the entry
-// statistics and the frame time - from draw to draw)
-static void mesh_adapt_list_bins(gs_mesh* m, uint64_t tiles16, uint32_t visible) {
-    if (visible == 0u) return;
-    const float tiles = (float)tiles16, vis = (float)visible;
-    static const uint32_t shifts[4] = {GS_LIST_SHIFT_SMALL, GS_LIST_SHIFT_LARGE, GS_LIST_SHIFT_BIG, GS_LIST_SHIFT_HUGE};
-    static const float thr[3] = {GS_LIST_TILES_PER_SPLAT, GS_LIST_TILES_PER_SPLAT_BIG, GS_LIST_TILES_PER_SPLAT_HUGE};
-    uint32_t level = 0;
-    while (level < 3u && shifts[level] != m->list_shift) level++;
-    while (level < 3u && tiles >= 1.08f * thr[level] * vis) level++;
-    while (level > 0u && tiles < 0.92f * thr[level - 1u] * vis) level--;
-    m->list_shift = shifts[level];
-}
-
 static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
     hipStream_t st = m->ctx->stream;
     RenderFrame f;
@@ -791,8 +764,8 @@ static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
     m->last.entries_scanned = 0;
     m->last.splats_walked = 0;
     m->last.halves_evaluated = 0;
-    if (m->blend_bins) {                                   // per-workgroup counters of the blend, summed here
-        const size_t nb = m->blend_bins;
+    if (m->stats_of.bins) {                                // per-workgroup counters of the blend, summed here
+        const size_t nb = m->stats_of.bins;
         std::vector<uint32_t> bs(3 * nb);                  // uint2 [nb] {staged, halves} | uint32 [nb] pairs
         GS_HIP(hipMemcpyAsync(bs.data(), m->blend_stats.p, nb * 12, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
@@ -802,7 +775,7 @@ static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
             m->last.splats_walked += bs[2 * nb + b];
         }
     }
-    mesh_adapt_list_bins(m, m->last.tiles16, m->last.visible_splats);
+    m->list_shift = adapt_list_shift(m->list_shift, m->last.tiles16, m->last.visible_splats);
     if (stats) *stats = m->last;
     return f.overflow ? 1 : 0;
 }
@@ -866,11 +839,21 @@ static int mesh_draw_once(gs_mesh* m, const DrawSwitches& sw, const ProjectParam
     if (timed) GS_HIP(hipEventRecord(m->ev[1], st));
     // the index list is in the caller's splat numbering unless it comes from a sorter bound to this mesh
     m->translate = m->reorder && !(sorter && sorter->result_mesh == m);
-    GS_TRY(gs_launch_binning(m, sw, pp, order_dev, sorter, R));   // records ev[2] between emit and the tile sort
+    // one snapshot of the mapped words per enqueued draw: the deep pass's decision and the placement of its workgroups go by the same verdict
+    const DrawFeedback fb = read_feedback(m->mirror_host);
+    GS_TRY(gs_launch_binning(m, sw, fb, pp, order_dev, sorter, R));   // records ev[2] between emit and the tile sort
     if (timed) GS_HIP(hipEventRecord(m->ev[3], st));
-    GS_TRY(gs_launch_blend(m, sw, pp, out_dev));
-    m->stats_pp = pp;                                          // whose view the per-bin blend statistics now describe
-    m->stats_pp_valid = true;
+    GS_TRY(gs_launch_blend(m, sw, fb, pp, out_dev));
+    // whose bins, draw mode and view the per-bin blend statistics now describe.  (An empty strip blends nothing: the statistics
+    // stay those of the bins before it; a GS_DRAW_ROP8 draw's neither order a later fp32 draw's bins nor pick its deep bins.)
+    if (m->plan.blend_bins > 0u) {
+        m->stats_of.bins = m->plan.blend_bins;
+        m->stats_of.row_begin = pp.bin_row_begin;
+        m->stats_of.width_px = (uint32_t)pp.width;
+        m->stats_of.draw_mode = m->draw_mode;
+    }
+    m->stats_of.view = plan_view(pp);
+    m->stats_of.valid = true;
     m->drawn_dest_depth = m->dest_depth; m->drawn_dest_rgba = m->dest_rgba;      // the destination this draw saw (gs_mesh_debug_rop8)
     m->drawn_dest_w = m->dest_w; m->drawn_dest_h = m->dest_h; m->drawn_dest_flags = m->dest_flags;
     if (timed) {
@@ -955,10 +938,9 @@ static int mesh_params(gs_mesh* m, const gs_camera* cam, ProjectParams& pp) {
 // The share of the scene in view, from the last FULL-frame draw whose verdict has arrived (a 16-byte store of k_bin_emit's into the
 // mapped words: {serial, visible, 16-px tiles}), and the size of the list bins from the last draw of any kind; hints for the vertex
 // stage's launch shape (project.hip) and the binner's geometry: frames do not depend on either.
-static void mesh_read_view_share(gs_mesh* m, const DrawSwitches& sw) {
-    volatile uint32_t* mir = m->mirror_host;
-    const uint32_t vs = mir[8], vv = mir[9], t_lo = mir[10], t_hi = mir[11];
-    if (vs == 0u || mir[8] != vs) return;                   // nothing yet / a newer draw is writing: look again next time
+static void mesh_read_view_share(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb) {
+    if (!fb.view_valid) return;                             // nothing yet / a newer draw is writing: look again next time
+    const uint32_t vs = fb.view_serial, vv = fb.visible;
     if (vs == m->full_serial[vs & 7u]) {
         m->measured_visible = vv;
         m->measured_count = m->full_count[vs & 7u];
@@ -967,12 +949,12 @@ static void mesh_read_view_share(gs_mesh* m, const DrawSwitches& sw) {
         m->adapted_serial = vs;
         if (!sw.no_async_list_bins) {
             const uint32_t before = m->list_shift;
-            const uint64_t tiles16 = ((uint64_t)t_hi << 32) | t_lo;
-            mesh_adapt_list_bins(m, tiles16, vv);
+            const uint64_t tiles16 = fb.tiles16;
+            m->list_shift = adapt_list_shift(before, tiles16, vv);
             // smaller list bins mean more entries - at most one per 16-px tile touched: room for them before the first draw that
             // uses the new size, instead of one truncated frame and a heal after it (mesh_heal_overflow grows the buffers)
             if (m->list_shift < before) {
-                const uint64_t want = tiles16 + tiles16 / 8 + 1024;
+                const uint64_t want = entry_room(tiles16);
                 m->grow_entries_to = (uint32_t)(want > 0x7FFFFFFFull ? 0x7FFFFFFFull : want);
             }
         }
@@ -981,20 +963,20 @@ static void mesh_read_view_share(gs_mesh* m, const DrawSwitches& sw) {
 
 static int mesh_heal_overflow(gs_mesh* m, const DrawSwitches& sw, bool* healed) {
     *healed = false;
-    volatile uint32_t* mir = m->mirror_host;
-    mesh_read_view_share(m, sw);
+    DrawFeedback fb = read_feedback(m->mirror_host);
+    mesh_read_view_share(m, sw, fb);
     if (m->grow_entries_to > m->entry_capacity) {           // the list bins just became smaller (mesh_read_view_share)
         GS_HIP(hipStreamSynchronize(m->ctx->stream));       // draws in flight still use the old buffers
         GS_TRY(mesh_alloc_entries(m, m->grow_entries_to));
+        fb = read_feedback(m->mirror_host);                 // (every draw's verdict has arrived by now)
     }
     m->grow_entries_to = 0;
-    const uint32_t serial = mir[0];
-    if (serial == m->healed_serial || !mir[1]) return GS_OK;
-    const uint64_t need = ((uint64_t)mir[3] << 32) | mir[2];
-    if (mir[0] != serial) return GS_OK;                     // a newer draw is writing: look again next time
-    m->healed_serial = serial;
+    if (fb.serial == m->healed_serial || !fb.overflow) return GS_OK;
+    if (!fb.entries_valid) return GS_OK;                    // a newer draw is writing: look again next time
+    const uint64_t need = fb.entries;
+    m->healed_serial = fb.serial;
     if (need <= m->entry_capacity) return GS_OK;            // already grown (by a synchronous draw or gs_mesh_last_stats)
-    uint64_t want = need + need / 8 + 1024;
+    uint64_t want = entry_room(need);
     if (want > 0x7FFFFFFFull) want = 0x7FFFFFFFull;
     GS_HIP(hipStreamSynchronize(m->ctx->stream));           // draws in flight still use the old buffers
     GS_TRY(mesh_alloc_entries(m, (uint32_t)want));
@@ -1070,7 +1052,7 @@ int gs_mesh_render(gs_mesh* m, const gs_camera* cam, const uint32_t* sorted_host
         if (ov < 0) return ov;
         int guard = 0;
         while (ov == 1 && guard++ < 4) {
-            uint64_t want = m->last.tile_entries + m->last.tile_entries / 8 + 1024;
+            const uint64_t want = entry_room(m->last.tile_entries);
             if (want > 0x7FFFFFFFull) {
                 gs_set_error("tile entries (%llu) exceed the 2^31 limit", (unsigned long long)m->last.tile_entries);
                 return GS_ERR_CAPACITY;
@@ -1111,7 +1093,7 @@ int gs_mesh_last_stats(gs_mesh* m, gs_render_stats* stats) {
     stats->overflowed = was_overflowed;
     if (ov == 1) {
         // an asynchronous draw overflowed its entry buffer: grow now so the next draw fits, and tell the caller
-        uint64_t want = m->last.tile_entries + m->last.tile_entries / 8 + 1024;
+        uint64_t want = entry_room(m->last.tile_entries);
         if (want > 0x7FFFFFFFull) want = 0x7FFFFFFFull;
         GS_TRY(mesh_alloc_entries(m, (uint32_t)want));
         gs_set_error("tile entry buffer overflowed (%llu entries); capacity grown, redraw the frame",
@@ -1197,7 +1179,7 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_REQUIRE((size_t)count * 8 <= m->tile_ranges.bytes, "count exceeds the tile count of the last draw");
         GS_HIP(hipMemcpyAsync(dst, m->tile_ranges.p, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     } else if (what == 4) {   // per 32-px blend bin of the last draw: {entries staged, (splat, tile) pairs walked}
-        GS_REQUIRE(count <= m->blend_bins, "count exceeds the blend bins of the last draw");
+        GS_REQUIRE(count <= m->stats_of.bins, "count exceeds the blend bins of the last draw");
         if (count) GS_HIP(hipMemcpyAsync(dst, m->blend_stats.p, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     } else if (what == 5) {   // the last draw's deep pass: {bins it drew, bins over the threshold, chunk partials the per-bin kernel closed,
                               // pool exhausted, then the bin numbers}; count = words (4 .. 4 + GS_DEEP_MAX_BINS)
@@ -1208,20 +1190,20 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
                               // and where the last vertex stage ran its block test (1 separate kernel, 0 per workgroup, 2 nowhere)
         GS_REQUIRE(count == 3, "count == 3");
         GS_HIP(hipStreamSynchronize(st));
-        mesh_read_view_share(m, draw_switches());          // (the mapped words the last draw left)
+        mesh_read_view_share(m, draw_switches(), read_feedback(m->mirror_host));   // (the mapped words the last draw left)
         uint32_t* w = static_cast<uint32_t*>(dst);
         w[0] = m->measured_visible; w[1] = m->measured_count; w[2] = m->last_project_mode;
         return GS_OK;
     } else if (what == 7) {   // the last draw's blend schedule (tile_bin.hip blend_schedule_job): GS_SCHEDULE_WORDS words, then
                               // blend_order [0, count - GS_SCHEDULE_WORDS); count = GS_SCHEDULE_WORDS .. + blend bins
-        GS_REQUIRE(count >= GS_SCHEDULE_WORDS && count - GS_SCHEDULE_WORDS <= m->sched.blend_bins &&
-                   (count == GS_SCHEDULE_WORDS || (m->sched.ran && (size_t)(count - GS_SCHEDULE_WORDS) * 4 <= m->blend_order.bytes)),
+        const SchedulePlan& a = m->plan;
+        GS_REQUIRE(count >= GS_SCHEDULE_WORDS && count - GS_SCHEDULE_WORDS <= a.blend_bins &&
+                   (count == GS_SCHEDULE_WORDS || (a.order_wg && (size_t)(count - GS_SCHEDULE_WORDS) * 4 <= m->blend_order.bytes)),
                    "count outside GS_SCHEDULE_WORDS .. + the blend bins of a draw that ran the schedule");
         GS_HIP(hipStreamSynchronize(st));
-        volatile uint32_t* mir = (volatile uint32_t*)m->mirror_host;
-        const gs_mesh::ScheduleArgs& a = m->sched;
-        const uint32_t head[GS_SCHEDULE_WORDS] = {a.ran, a.blend_bins, (uint32_t)a.sx, (uint32_t)a.sy, a.deep, a.deep_min, a.deep_factor, 0u /* reserved */,
-                                                  mir ? mir[4] : 0u, mir ? mir[5] : 0u};
+        const DrawFeedback fb = read_feedback(m->mirror_host);   // (what that draw's schedule job left)
+        const uint32_t head[GS_SCHEDULE_WORDS] = {a.order_wg ? 1u : 0u, a.blend_bins, (uint32_t)a.sx, (uint32_t)a.sy, a.deep_pass ? 1u : 0u, a.deep_min,
+                                                  a.deep_factor, a.order_taken ? 1u : 0u, fb.deep_candidates, fb.deep_share};
         memcpy(dst, head, sizeof(head));
         if (count > GS_SCHEDULE_WORDS)
             GS_HIP(hipMemcpyAsync(static_cast<uint32_t*>(dst) + GS_SCHEDULE_WORDS, m->blend_order.p, (size_t)(count - GS_SCHEDULE_WORDS) * 4,

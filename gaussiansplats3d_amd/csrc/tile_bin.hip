@@ -289,7 +289,7 @@ __device__ __forceinline__ uint32_t bin_emit_batch(const uint32_t* __restrict__ 
 }
 
 // The previous draw's per-bin statistics describe ITS view.  When the camera has moved since, the host says how far the scene's centre
-// of mass moved on screen, in bins (binning_typed): the schedule reads the statistics of the bin a bin's content came FROM - a camera
+// of mass moved on screen, in bins (draw_plan.cpp, plan_schedule): the schedule reads the statistics of the bin a bin's content came FROM - a camera
 // that turns about its own position shifts the whole picture, and with it the costly bins and the deep pass's members, by that much.
 struct StatShift {
     int32_t sx, sy;            // this draw's bin (bx, by) shows what the previous draw's bin (bx - sx, by - sy) showed
@@ -397,10 +397,10 @@ __device__ __forceinline__ void blend_schedule_job(const uint2* prev_blend_stats
         deep_flags[GS_FLAG_CAND] = s_trigger ? s_deep_n : 0u;
         if (deep) deep_flags[GS_FLAG_COUNT] = s_deep_n;
         if (mirror) {
-            mirror[4] = s_trigger ? s_deep_n : 0u;
+            mirror[GS_MIRROR_DEEP_CANDIDATES] = s_trigger ? s_deep_n : 0u;
             // ... and what share of the previous draw's walk those bins were, in 1 / 1024: how many of the blend's workgroups the pass
             // should get (tile_blend.hip, gs_launch_blend)
-            mirror[5] = (uint32_t)(((unsigned long long)s_deep_cost << 14) / (unsigned long long)max(total_walked, 1u));
+            mirror[GS_MIRROR_DEEP_SHARE] = (uint32_t)(((unsigned long long)s_deep_cost << 14) / (unsigned long long)max(total_walked, 1u));
         }
     }
 }
@@ -523,12 +523,12 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
             if (mirror) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const u32x4 v = {serial, D64 > capacity ? 1u : 0u, (uint32_t)D64, (uint32_t)(D64 >> 32)};
-                *reinterpret_cast<volatile u32x4*>(mirror) = v;
+                *reinterpret_cast<volatile u32x4*>(mirror + GS_MIRROR_SERIAL) = v;
                 // ... and, as a second 16-byte store, {serial, visible splats, 16-px tiles they touch}: what tells the following draws how
                 // much of the scene is in view (project.hip: where the block test runs) and how large its splats are on screen (the size
-                // of the list bins, mesh.hip: mesh_adapt_list_bins) without anybody asking for statistics
+                // of the list bins, draw_plan.cpp: adapt_list_shift) without anybody asking for statistics
                 const u32x4 sv = {serial, s_vis[0] + s_vis[1] + s_vis[2] + s_vis[3], (uint32_t)tsum, (uint32_t)(tsum >> 32)};
-                *reinterpret_cast<volatile u32x4*>(mirror + 8) = sv;
+                *reinterpret_cast<volatile u32x4*>(mirror + GS_MIRROR_VIEW_SERIAL) = sv;
             }
         }
     }
@@ -549,8 +549,25 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
     (void)emitted;
 }
 
+// what plan_schedule (draw_plan.hpp) is told about this draw, the mesh and the draw before
+static ScheduleInputs schedule_inputs(const gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp) {
+    ScheduleInputs in;
+    in.stats = m->stats_of;
+    in.now = plan_view(pp);
+    in.bins_x = pp.bins_x; in.bin_row_begin = pp.bin_row_begin; in.bin_row_end = pp.bin_row_end;
+    in.block_cull = pp.block_cull;
+    in.draw_mode = m->draw_mode;
+    in.draw_serial = m->draw_serial;
+    in.no_deep = m->no_deep;
+    memcpy(in.centre_sum, m->centre_sum, sizeof(in.centre_sum));
+    in.centre_n = m->centre_n;
+    in.feedback = fb;
+    in.sw = sw;
+    return in;
+}
+
 template <class KeyT>
-static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R, uint32_t tiles /* sort keys */) {
+static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R, uint32_t tiles /* sort keys */) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream;
     const RadixExec ex = {st, &m->radix, ctx->lds_atomic_lane_order};
@@ -569,104 +586,19 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const ProjectParams
         GS_HIP(hipEventRecord(sorter->ev_consumed, st));
         sorter->consumer_pending = true;
     }
-    // the previous draw's per-bin blend statistics order this draw's blend workgroups, if it drew the same bins
-    // (only while the bins outnumber the resident workgroups by a small factor: an 8K frame's 32 k bins balance themselves by
-    // backfilling, and ordering them in one workgroup would cost more than it gives)
-    // deep pass: a bin qualifies when its previous draw walked >= deep_min (splat, quadrant) pairs and >= deep_factor x the mean bin
-    // (4096 pairs.  C3S frame ms at 2048 / 3072 / 4096 / 6144 / 8192: 1.336 / 1.338 / 1.309 / 1.296 / 1.500 - k_deep_scan costs
-    // 0.17 ms for 512 bins and is bound by its gathers, so: fewer, deeper bins; profiles/r03zz_kstats_C3S.txt)
-    const uint32_t deep_factor = sw.deep_factor;
-    // (a GS_DRAW_ROP8 draw has no deep pass - rounding after every splat does not split into chunks - and must not raise its trigger)
-    const uint32_t deep_min = m->draw_mode == GS_DRAW_FP32 ? sw.deep_min : 0x7FFFFFFFu;
-    const bool order_ok = blend_bins > 0 && blend_bins <= 8192u && m->blend_bins == blend_bins && m->blend_row_begin == pp.bin_row_begin &&
-                          m->blend_width == (uint32_t)pp.width && m->blend_stats_mode == m->draw_mode && !sw.no_blend_order;
-    // (the same draw mode: a GS_DRAW_ROP8 draw walks its lists to the saturation depth twice or to their ends - its per-bin counters
-    // say nothing about what an fp32 draw costs, and the other way round)
-    if (order_ok) GS_TRY(m->blend_order.ensure((size_t)blend_bins * 4));
-    // ... and they ORDER this draw's blend workgroups only when that draw had THIS draw's view.  Heaviest-first from statistics of
-    // the same view is worth 5-8 % of a frame (C3 demo pose 0.261 -> 0.248 ms, the orbit's poses held fixed 0.350 -> 0.322); from
-    // a view 6 degrees away it is worth less than the workgroup that computes it costs - a moving camera draws its frames faster
-    // in plain row-major order (C3 orbit 0.359 -> 0.349 ms per frame, C2 0.264 -> 0.255; profiles/r06g_orbit_gate.txt).  Two
-    // stateless orders were built and measured as well, both no better than row-major: by the length of the list a bin scans (a
-    // long list is a dense region that saturates at once: C2 fixed pose 0.327 vs 0.318 ms without any order, r06c) and a stride
-    // permutation that makes the late starters a uniform sample of the screen (r06e: 0.3624 vs 0.3625).  The deep pass's
-    // membership (which executor composites a bin, not when) keeps using the statistics of whatever view came before.
-    const ProjectParams& lp = m->stats_pp;
-    const bool same_frame = m->stats_pp_valid && memcmp(lp.proj, pp.proj, sizeof(pp.proj)) == 0 && lp.width == pp.width && lp.height == pp.height &&
-                            lp.count == pp.count && lp.list_shift == pp.list_shift;
-    bool same_view = same_frame && memcmp(lp.view, pp.view, sizeof(pp.view)) == 0;
-    // ... or a view close to it.  Two things are taken from the two cameras (second half of round 6; tools/motion_ab.py):
-    //  * how far the scene's centre of mass moved on screen, in whole bins: the schedule reads the statistics of the bin a bin's
-    //    content came FROM (StatShift).  A camera turning about its own position shifts the whole picture - and the costly bins, and
-    //    the deep pass's members - by that much: capture-like C3S turning 2 / 4 / 8 degrees per frame 2.14 / 2.77 / 3.78 -> 1.16 / 1.39 /
-    //    2.06 ms per frame, C2 with the previous order at 4 / 8 degrees 0.3175 / 0.3139 -> 0.2913 / 0.3001 (row-major: 0.303)
-    //    (profiles/r06zz_stat_shift_ab.txt; $GSPLAT_NO_STAT_SHIFT);
-    //  * what that shift does NOT describe - parallax: how far points at half and at twice the centre's distance, on the previous
-    //    camera's ray through the centre, end up from the centre in the new picture, in screen heights.  Orbiting the scene at 0.25 ...
-    //    6 degrees per frame the previous frame's order beats row-major up to 2 degrees (C2 7-11 %, C3 1-2 % of the frame), is level
-    //    at 3 and loses 2.5-3 % at 6 (profiles/r06w_motion_ab.txt): the order is taken below a parallax of 0.045 screen heights
-    //    ($GSPLAT_ORDER_MOTION; 0 = the same view only).  Turning in place has none, at any speed.
-    StatShift stat_shift = {0, 0, pp.bins_x};
-    if (same_frame && !same_view && pp.block_cull && m->centre_n > 0) {
-        const float limit = sw.order_motion;
-        const double inv_n = 1.0 / (double)m->centre_n;
-        const float c[3] = {(float)(m->centre_sum[0] * inv_n), (float)(m->centre_sum[1] * inv_n), (float)(m->centre_sum[2] * inv_n)};
-        auto window = [&](const ProjectParams& q, const float* p, float* xy) {       // (column-major matrices, window y up: project.hip)
-            float v[4], o[4];
-            for (int r = 0; r < 4; r++) v[r] = q.view[r] * p[0] + q.view[4 + r] * p[1] + q.view[8 + r] * p[2] + q.view[12 + r];
-            for (int r = 0; r < 4; r++) o[r] = q.proj[r] * v[0] + q.proj[4 + r] * v[1] + q.proj[8 + r] * v[2] + q.proj[12 + r] * v[3];
-            if (!(o[3] > 1e-6f)) return false;
-            xy[0] = (o[0] / o[3] * 0.5f + 0.5f) * q.width;
-            xy[1] = (o[1] / o[3] * 0.5f + 0.5f) * q.height;
-            return true;
-        };
-        float was[2], is[2];
-        if (window(lp, c, was) && window(pp, c, is)) {
-            const float dx = (is[0] - was[0]) / (float)GS_BIN, dy = (is[1] - was[1]) / (float)GS_BIN;
-            const bool shift_ok = fabsf(dx) < 4096.0f && fabsf(dy) < 4096.0f && !sw.no_stat_shift;   // (false for NaN)
-            if (shift_ok) {
-                stat_shift.sx = (int32_t)lrintf(dx);
-                stat_shift.sy = (int32_t)lrintf(dy);
-            }
-            // the previous camera's position in the splats' own space: -A^-1 b of its modelView = [A | b]
-            const float* V = lp.view;
-            const float a00 = V[0], a10 = V[1], a20 = V[2], a01 = V[4], a11 = V[5], a21 = V[6], a02 = V[8], a12 = V[9], a22 = V[10];
-            const float c00 = a11 * a22 - a12 * a21, c01 = a02 * a21 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-            const float det = a00 * c00 + a10 * c01 + a20 * c02;
-            const float b0 = V[12], b1 = V[13], b2 = V[14], id = 1.0f / det;
-            const float eye[3] = {-(c00 * b0 + c01 * b1 + c02 * b2) * id,
-                                  -((a12 * a20 - a10 * a22) * b0 + (a00 * a22 - a02 * a20) * b1 + (a02 * a10 - a00 * a12) * b2) * id,
-                                  -((a10 * a21 - a11 * a20) * b0 + (a01 * a20 - a00 * a21) * b1 + (a00 * a11 - a01 * a10) * b2) * id};
-            float parallax = 0.0f;
-            bool seen = fabsf(det) > 1e-20f;
-            for (int k = 0; k < 2 && seen; k++) {
-                const float t = k ? 2.0f : 0.5f;
-                const float p[3] = {eye[0] + t * (c[0] - eye[0]), eye[1] + t * (c[1] - eye[1]), eye[2] + t * (c[2] - eye[2])};
-                float at[2];
-                seen = window(pp, p, at);
-                if (seen) parallax = fmaxf(parallax, sqrtf((at[0] - is[0]) * (at[0] - is[0]) + (at[1] - is[1]) * (at[1] - is[1])));
-            }
-            // (without the shift the whole motion counts, not only the parallax)
-            const float moved = (parallax + (shift_ok ? 0.0f : sqrtf(dx * dx + dy * dy) * (float)GS_BIN)) / fmaxf(pp.height, 1.0f);
-            same_view = seen && moved <= limit;            // (NaN compares false)
-        }
-    }
-    const bool stale_order = sw.blend_order_stale;   // (A/B: rounds 2-5 - order from whatever draw came before)
-    // The deep pass runs when the last draw whose verdict has arrived (mapped host word, no synchronisation) left bins over the
-    // threshold - the decision only moves work between executors, the pixels do not depend on it (tile_blend.hip)
-    m->deep_pass = order_ok && m->draw_mode == GS_DRAW_FP32 && !m->no_deep && m->mirror_host && ((volatile uint32_t*)m->mirror_host)[4] > 0u;
-    if (m->deep_pass) {
+    // whether the previous draw's statistics order this draw's bins (read shifted by how many bins), and whether the deep pass
+    // runs: draw_plan.cpp (the result is kept for gs_launch_blend and gs_mesh_debug_read(what = 7))
+    m->plan = plan_schedule(schedule_inputs(m, sw, fb, pp));
+    const SchedulePlan& plan = m->plan;
+    if (plan.order_ok) GS_TRY(m->blend_order.ensure((size_t)blend_bins * 4));
+    if (plan.deep_pass) {
         GS_TRY(m->deep_ent.ensure((size_t)GS_DEEP_MAX_BINS * GS_DEEP_LIST_CAP * 4));
         GS_TRY(m->deep_cnt.ensure((size_t)GS_DEEP_MAX_BINS * GS_DEEP_RANGES * 4 * 4));
         GS_TRY(m->deep_partial.ensure((size_t)GS_DEEP_UNITS * 256 * sizeof(float4)));
         GS_TRY(m->deep_work.ensure((size_t)GS_DEEP_UNITS * 4));
     }
-    // (+ one workgroup that orders the blend's bins and names the deep pass's members)
-    // (that workgroup also raises the deep pass's trigger, so under a camera that keeps moving it still runs when the pass is on,
-    // for scenes of tiny splats - the ones that grow deep bins - and every 8th draw otherwise)
-    const bool order_wg = order_ok && (same_view || stale_order || m->deep_pass || pp.list_shift == GS_LIST_SHIFT_SMALL || (m->draw_serial & 7u) == 7u);
-    // (what the schedule job of this draw is given: gs_mesh_debug_read(what = 7))
-    m->sched = {order_wg ? 1u : 0u, blend_bins, stat_shift.sx, stat_shift.sy, m->deep_pass ? 1u : 0u, deep_min, deep_factor};
+    const bool order_wg = plan.order_wg;
+    const StatShift stat_shift = {plan.sx, plan.sy, pp.bins_x};
     ++m->draw_serial;
     if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the mapped words carry the serial: 0 is "no draw yet", mesh_read_view_share)
     hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
@@ -678,12 +610,7 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const ProjectParams
                        m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
                        m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,
                        order_wg ? m->blend_stats.as<uint2>() : nullptr, blend_bins, order_wg ? m->blend_order.as<uint32_t>() : nullptr,
-                       m->deep_pass ? 1u : 0u, m->deep_flags.as<uint32_t>(), m->blend_stats.as<uint32_t>(), deep_min, deep_factor, stat_shift);
-    // ... and whenever the deep pass runs: its frames have the long tail that an order - even one from a view several degrees away -
-    // and the pass's workgroups behind the costliest bins (tile_blend.hip) shorten.  Capture-like C3S, orbit at 3 / 6 / 12 degrees per
-    // frame: 1.24 / 1.356 / 1.54 -> 1.18 / 1.31 / 1.51 ms, turning 4 degrees per frame 2.84 -> 2.77, never slower
-    // (profiles/r06zz_deep_keeps_order_ab.txt; $GSPLAT_DEEP_ROW_MAJOR_ON_MOTION=1 is the earlier rule).
-    m->blend_order_valid = order_ok && (same_view || stale_order || (m->deep_pass && !sw.deep_row_major_on_motion));
+                       plan.deep_pass ? 1u : 0u, m->deep_flags.as<uint32_t>(), m->blend_stats.as<uint32_t>(), plan.deep_min, plan.deep_factor, stat_shift);
     GS_HIP(hipGetLastError());
     if (pp.row_begin == 0u && pp.row_end >= pp.tiles_y) {     // (a strip's visible count says nothing about the scene: mesh_heal_overflow)
         m->full_serial[m->draw_serial & 7u] = m->draw_serial;
@@ -712,8 +639,8 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const ProjectParams
     return GS_OK;
 }
 
-int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count) {
+int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count) {
     const uint32_t tiles = pp.lists_x * (pp.list_row_end - pp.list_row_begin);   // one list per sort key
-    if (tiles <= 65536u && !m->ctx->wide_entry_keys) return binning_typed<uint16_t>(m, sw, pp, order_dev, sorter, render_count, tiles);
-    return binning_typed<uint32_t>(m, sw, pp, order_dev, sorter, render_count, tiles);
+    if (tiles <= 65536u && !m->ctx->wide_entry_keys) return binning_typed<uint16_t>(m, sw, fb, pp, order_dev, sorter, render_count, tiles);
+    return binning_typed<uint32_t>(m, sw, fb, pp, order_dev, sorter, render_count, tiles);
 }

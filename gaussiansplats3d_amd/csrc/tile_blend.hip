@@ -1389,17 +1389,18 @@ int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t
     return GS_OK;
 }
 
-int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, uint8_t* out_dev) {
+// (what the statistics this blend writes describe is recorded by the caller once this returns: mesh.hip, mesh_draw_once)
+int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, uint8_t* out_dev) {
     const uint32_t bins = pp.bins_x * (pp.bin_row_end - pp.bin_row_begin);
     if (bins == 0) return GS_OK;
     GS_TRY(m->blend_stats.ensure((size_t)bins * 12));     // uint2 [bins] {scanned, halves} | uint32 [bins] pairs
-    m->blend_bins = bins;
+    const SchedulePlan& plan = m->plan;                    // (of this draw: gs_launch_binning)
     hipStream_t st = m->ctx->stream;
     FrameArgs fa = frame_args(m, pp);
     fa.out = reinterpret_cast<uint32_t*>(out_dev);
     fa.bin_stats = m->blend_stats.as<uint2>();
     fa.bin_pairs = m->blend_stats.as<uint32_t>() + 2 * (size_t)bins;
-    fa.bin_order = m->blend_order_valid ? m->blend_order.as<uint32_t>() : nullptr;
+    fa.bin_order = plan.order_taken ? m->blend_order.as<uint32_t>() : nullptr;
     // (the buffers were sized and the flag words reset by the binner's launches: gs_launch_binning)
     DeepArgs da;
     da.flags = m->deep_flags.as<uint32_t>();
@@ -1409,52 +1410,24 @@ int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp,
     da.pool = m->chunk_pool.as<float4>();
     da.pool_slots = sw.pool_slots;
     da.work = m->deep_work.as<uint32_t>();
-    // (as many workgroups as the device holds at BLEND_OCC per CU: their waves loop over the unit list)
-    da.unit_wgs = m->deep_pass ? (uint32_t)m->ctx->cu_count * BLEND_OCC : 0u;
-    // Where the deep pass's workgroups sit in the launch, and how many.  Their waves take (bin, quadrant, chunk) units from a list
-    // until it is empty, so any number of them finishes the pass; what matters is WHEN they run against the per-bin workgroups
-    // (tools/probes: GSPLAT_DEEP_UNIT_AT / _WGS; capture-like C3S, profiles/r06z_deep_unit_ab.txt):
-    //  * bins in costliest-first order (this view's statistics): the units used to come last, started 340 us into a 985 us launch and
-    //    ended it alone; all 1536 of them in front (AT = 0) crowd the costliest bins out.  Two workgroups per CU behind the deep bins'
-    //    own (empty) workgroups and the ~1.5 costliest bins per CU: frame 1.300 -> 1.13 ms at the demo pose, 1.300 -> 1.105 in the mean
-    //    of the orbit's poses held fixed;
-    //  * bins in row-major order (the camera moved on: no order): units are the fine-grained work that fills the end of the launch -
-    //    in the middle they cost 13 % (moving camera 1.35 -> 1.52 ms) - so they stay last, all of them.
-    da.unit_at = bins;
-    if (m->deep_pass && m->blend_order_valid && !sw.deep_units_last) {
-        const uint32_t cus = (uint32_t)m->ctx->cu_count;
-        const uint32_t deep_hint = m->mirror_host ? ((volatile uint32_t*)m->mirror_host)[4] : 0u;      // bins the last verdict put in the pass
-        // two per CU - or, when the pass's bins were most of the previous draw's walk, 0.6 of their share of the resident workgroups
-        // (C3S: share 0.55, best at a third of the workgroups whatever AT is: 256 / 512 / 768 / 1536 -> 1.30 / 1.125 / 1.15 / 1.20 ms;
-        // with exactly the share, 1.17)
-        const float share = (float)std::min(m->mirror_host ? ((volatile uint32_t*)m->mirror_host)[5] : 0u, 1024u) * (1.0f / 1024.0f);
-        const float k = sw.deep_share_k;
-        da.unit_wgs = std::min(da.unit_wgs, std::max(2u * cus, (uint32_t)(k * share * (float)da.unit_wgs + 0.5f)));
-        da.unit_at = std::min(bins, std::min(deep_hint, (uint32_t)GS_DEEP_MAX_BINS) + cus + cus / 2u);
-    }
-    if (sw.deep_unit_at_set && m->deep_pass) da.unit_at = sw.deep_unit_at;
-    if (sw.deep_unit_wgs_set && m->deep_pass)
-        da.unit_wgs = std::max(1u, std::min<uint32_t>(sw.deep_unit_wgs, (uint32_t)m->ctx->cu_count * BLEND_OCC));
+    // where the deep pass's workgroups sit in the launch, and how many: draw_plan.cpp
+    const DeepUnits du = place_deep_units(plan, bins, (uint32_t)m->ctx->cu_count, BLEND_OCC, fb, sw);
+    da.unit_at = du.unit_at;
+    da.unit_wgs = du.unit_wgs;
     if (m->draw_mode != GS_DRAW_FP32) {                    // the reference's RGBA8 target, splat by splat (no deep pass: nothing to schedule)
         static void (*const rop8[2][2])(FrameArgs, uint32_t) = {                // [DEPTH][BOUNDED]
             {k_tile_blend_rop8<false, false>, k_tile_blend_rop8<false, true>}, {k_tile_blend_rop8<true, false>, k_tile_blend_rop8<true, true>}};
         hipLaunchKernelGGL(rop8[fa.depth_mode != 0u][m->draw_mode != GS_DRAW_ROP8_FULL], dim3(bins), dim3(BLEND_THREADS), 0, st, fa, bins);
-        m->blend_stats_mode = m->draw_mode;                // (a later fp32 draw neither orders its bins nor picks deep bins from these)
-        m->blend_row_begin = pp.bin_row_begin;
-        m->blend_width = (uint32_t)pp.width;
         GS_HIP(hipGetLastError());
         return GS_OK;
     }
-    if (m->deep_pass) {
+    if (plan.deep_pass) {
         hipLaunchKernelGGL(k_deep_scan, dim3(GS_DEEP_MAX_BINS * GS_DEEP_SCAN_WGS), dim3(256), 0, st, fa, da);
         hipLaunchKernelGGL(k_deep_plan, dim3(1), dim3(1024), 0, st, fa, da);
     }
     if (fa.depth_mode) hipLaunchKernelGGL(k_tile_blend<true>, dim3(bins + da.unit_wgs), dim3(BLEND_THREADS), 0, st, fa, da, bins);
     else hipLaunchKernelGGL(k_tile_blend<false>, dim3(bins + da.unit_wgs), dim3(BLEND_THREADS), 0, st, fa, da, bins);
-    if (m->deep_pass) hipLaunchKernelGGL(k_deep_fold, dim3(GS_DEEP_MAX_BINS), dim3(BLEND_THREADS), 0, st, fa, da);
-    m->blend_stats_mode = GS_DRAW_FP32;
-    m->blend_row_begin = pp.bin_row_begin;
-    m->blend_width = (uint32_t)pp.width;
+    if (plan.deep_pass) hipLaunchKernelGGL(k_deep_fold, dim3(GS_DEEP_MAX_BINS), dim3(BLEND_THREADS), 0, st, fa, da);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }

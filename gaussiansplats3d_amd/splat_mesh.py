@@ -492,7 +492,8 @@ class SplatMesh:
     def blend_schedule(self):
         """What the last draw's blend schedule was given and produced (tile_bin.hip blend_schedule_job): {ran, blend_bins, sx, sy
         (this draw's bin (x, y) read the statistics of bin (x - sx, y - sy) of the draw before), deep (this draw ran the deep
-        pass), deep_min, deep_factor, candidates (mirror word 4: bins over the deep pass's trigger, else 0),
+        pass), deep_min, deep_factor, order_taken (the blend visited its bins in the schedule's order, else row-major),
+        candidates (mirror word 4: bins over the deep pass's trigger, else 0),
         share (mirror word 5: the members' share of the walk in 1/1024), order (the bins in blend order; None when it did not
         run)}.  Scheduling only: frames do not depend on it."""
         head = np.zeros(L.GS_SCHEDULE_WORDS, dtype=np.uint32)
@@ -502,7 +503,7 @@ class SplatMesh:
         L.check(self.lib.gs_mesh_debug_read(self.handle, 7, out.ctypes.data, out.size))
         sx, sy = out[2:4].view(np.int32)
         return {"ran": bool(out[0]), "blend_bins": int(out[1]), "sx": int(sx), "sy": int(sy), "deep": bool(out[4]),
-                "deep_min": int(out[5]), "deep_factor": int(out[6]), "candidates": int(out[8]),
+                "deep_min": int(out[5]), "deep_factor": int(out[6]), "order_taken": bool(out[7] & 1), "candidates": int(out[8]),
                 "share": int(out[9]), "order": out[L.GS_SCHEDULE_WORDS:].copy() if out[0] else None}
 
     def view_share(self):

@@ -506,8 +506,8 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * host, and where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all);
  * 7 = the blend schedule of the last draw (the one workgroup that orders the blend's bins by the previous draw's per-bin statistics,
  * what = 4, and names the deep pass's members), GS_SCHEDULE_WORDS words: {1 if it ran, blend bins, shift x, shift y (int32: this
- * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, 0
- * (reserved), the bins it put over the deep pass's trigger (0 when none reached it), the members' share of the walk in
+ * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, bit 0:
+ * the blend visited its bins in that order (other bits reserved, 0), the bins it put over the deep pass's trigger (0 when none reached it), the members' share of the walk in
  * 1/1024}, then the bin order itself (count = GS_SCHEDULE_WORDS .. + blend bins; the order only after a draw that ran it);
  * 8 = the entry values of the last draw in list order: `count` uint32 record slots (count <= min(tile_entries, entry_capacity) of
  * that draw), the array the [begin,end) ranges of what = 2 index, each list near -> far; refused while a gs_mesh_project is pending
