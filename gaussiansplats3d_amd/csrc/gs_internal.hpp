@@ -286,6 +286,8 @@ struct gs_sorter {
     DevBuf idx_in;             // indexesToSort on device
     DevBuf precomputed;
     DevBuf keys;               // int32 depth key per list position (mappedDistances, phase A)
+    DevBuf keys16;             // uint16 radix key (range - 1 - bucket) per list position: all a known-range sort with <= 16-bit
+                               // buckets stores (k_depth_key_hist<true>); never an alias of keyA, which the unpacked pass 0 writes
     DevBuf keyA, keyB, valA, valB;   // radix ping-pong
     DevBuf sorted;             // uint32 [render_count]: the sortDone payload, stays resident for the mesh
     DevBuf frame;              // SortFrame [2]: the sort in flight uses one, its first kernel resets the other
@@ -345,6 +347,12 @@ struct gs_sorter {
     bool last_known_range = false;     // what gs_sorter_debug_read(what = 4) reports of the last sort
     int32_t last_range_lo = 0, last_range_hi = 0;
     uint32_t last_pass0_slot = 0;
+    bool last_narrow = false;          // ... and whether it stored 16-bit radix keys instead of the int32 depth keys
+    // After such a sort `keys` still holds an earlier sort's depths.  gs_sorter_debug_read (selectors 0 and 1) and an upload of
+    // centres first rebuild them from the planes with the sort's own coefficients (sorter.hip, sorter_refresh_keys).
+    bool keys_stale = false;
+    int32_t stale_im[3] = {0, 0, 0};   // KeyParams::im0 .. im2 of that sort
+    uint32_t stale_count = 0;          // its render count
 };
 
 // ---------------------------------------------------------------------------------------------------

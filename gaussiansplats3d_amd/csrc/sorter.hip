@@ -839,10 +839,14 @@ struct DepthLoaderArgs {                   // what every (CULL, IDX) variant is 
     uint32_t count_clamps;                 // only the histogram launch counts, so each element counts once
     int32_t lo;
     float range_map;
+    const uint16_t* __restrict__ keys16;   // NARROW: the radix key of every list position, as k_depth_key_hist<true> left it
 };
-template <bool CULL, bool IDX>
+// NARROW: the front end knew the key range and stored key' = range - 1 - bucket itself, 2 bytes per list position, instead of the
+// depth: the loader reads that and decodes nothing (no range, no SortFrame, no bucket arithmetic between the scatter's two waits).
+template <bool CULL, bool IDX, bool NARROW = false>
 struct DepthLoaderT : DepthLoaderArgs {
     __device__ __forceinline__ void prepare() {
+        if (NARROW) return;                                     // (a known-range sort: the list's length is on the host)
         if (n_dev) render_count = *n_dev;                       // sort_start is 0 in that variant
         // the sort's min / max live in SORT_SHARDS words each: lane l reads shard l, five xor-shuffles reduce them
         // (every thread reading all 64 words cost the histogram kernel 5 us)
@@ -898,18 +902,20 @@ struct DepthLoaderT : DepthLoaderArgs {
     }
     __device__ __forceinline__ Raw fetch(uint32_t j, uint32_t o) const {
         Raw r;
-        r.depth = ld32(keys, render_count - 1 - j);
+        r.depth = NARROW ? (int32_t)ld32(keys16, render_count - 1 - j) : ld32(keys, render_count - 1 - j);
         r.payload = map ? ld32(map, o) : o;
         return r;
     }
     __device__ __forceinline__ void decode(const Raw& r, uint32_t& k, uint32_t& v) const {
-        k = (range - 1) - bucket_of<false>(r.depth);
+        k = NARROW ? (uint32_t)r.depth : (range - 1) - bucket_of<false>(r.depth);
         v = r.payload;
     }
-    // the histogram's view of element j
+    // the histogram's view of element j (NARROW: never launched - the front end left pass 0's rows - but the pass templates name it)
     typedef int32_t HRaw;
-    __device__ __forceinline__ HRaw hist_fetch(uint32_t j) const { return ld32(keys, render_count - 1 - j); }
-    __device__ __forceinline__ uint32_t hist_key(HRaw depth) const { return (range - 1) - bucket_of<true>(depth); }
+    __device__ __forceinline__ HRaw hist_fetch(uint32_t j) const {
+        return NARROW ? (int32_t)ld32(keys16, render_count - 1 - j) : ld32(keys, render_count - 1 - j);
+    }
+    __device__ __forceinline__ uint32_t hist_key(HRaw depth) const { return NARROW ? (uint32_t)depth : (range - 1) - bucket_of<true>(depth); }
     __device__ __forceinline__ bool valid(uint32_t j) const {
         if (!CULL) return true;
         const uint32_t i = render_count - 1 - j;
@@ -963,10 +969,20 @@ __global__ void k_unmap(const uint32_t* __restrict__ in, const uint32_t* __restr
 // The range goes into every shard of the sort's SortFrame with plain stores: DepthLoader::prepare of the scatter, k_debug_buckets
 // and the statistics read it as ever.  The group rows of pass 0 (`group_rows`, slot keep_slot) are added to inside this launch, so
 // sort_begin leaves them alone: they were zeroed by the sort before (gs_sorter::clean_slot).
+// NARROW (buckets of <= 16 bits): the kernel knows every key's final bucket as it makes it, so it stores the radix key itself,
+// key' = range - 1 - bucket, as 16 bits at the key's list position - what it counts - and nothing goes to keys_out: 2 bytes per
+// splat written here and 2 read by pass 0 (DepthLoaderT<.., .., true>) instead of 4 and 4, and no bucket arithmetic in the scatter.
+// A lane owns TWO adjacent vectors per plane there and stores its eight keys as one 16-byte store, one such pair in flight
+// (GS_KEY_HIST_PAIR = 2: two pairs; 0: one vector per lane and step as below, four keys as an 8-byte store - both measured slower,
+// profiles/r08_narrow_keys_ab.txt).  gs_sorter::keys is stale after such a sort (sorter_refresh_keys).
 constexpr uint32_t KEY_HIST_VECS = 3;      // 16-byte vectors per plane a thread has in flight (one chunk of the chunk-staged pass)
+#ifndef GS_KEY_HIST_PAIR
+#define GS_KEY_HIST_PAIR 1
+#endif
+template <bool NARROW>
 __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, DepthLoader ld, int32_t key_lo, int32_t key_hi, int shift,
                                                                   uint32_t keep_slot, uint32_t* __restrict__ block_hist,
-                                                                  uint32_t* __restrict__ group_rows) {
+                                                                  uint32_t* __restrict__ group_rows, uint16_t* __restrict__ keys16) {
     __shared__ uint32_t s_hist[4][RADIX_BINS];               // waves w, w+4, w+8, w+12 share one
     const uint32_t tid = threadIdx.x, t = blockIdx.x * HIST_THREADS + tid;
     sort_begin(p, t, gridDim.x * HIST_THREADS, keep_slot);
@@ -983,41 +999,65 @@ __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, De
     // this chunk's logical elements [j0, j1) are list positions [R - j1, R - j0)
     const uint32_t j0 = min(ch.tile_begin * (uint32_t)RADIX_TILE, R), j1 = min(ch.tile_end * (uint32_t)RADIX_TILE, R);
     const uint32_t p0 = R - j1, p1 = R - j0;
-    auto count = [&](int32_t k) { atomicAdd(&hist[(ld.hist_key(k) >> shift) & 255u], 1u); };     // (hist_key counts a clamp)
+    // counts one depth's radix key (hist_key counts a clamp) and returns it
+    auto count = [&](int32_t k) {
+        const uint32_t r = ld.hist_key(k);
+        atomicAdd(&hist[(r >> shift) & 255u], 1u);
+        return r;
+    };
     auto scalars = [&](uint32_t begin, uint32_t end) {
         for (uint32_t i = begin + tid; i < end; i += HIST_THREADS) {
             const int32_t k = static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
-            p.keys_out[i] = k;
-            count(k);
+            const uint32_t r = count(k);
+            if (NARROW) keys16[i] = (uint16_t)r;
+            else p.keys_out[i] = k;
         }
     };
-    // positions [a4 * 4, b4 * 4) as 16-byte vectors, the ragged head and tail one at a time (k_depth_key<true>'s cut)
-    const uint32_t a4 = (p0 + 3u) / 4u, b4 = p1 / 4u;
-    if (a4 < b4) {
-        scalars(p0, a4 * 4u);
-        scalars(b4 * 4u, p1);
+    // A unit = VPU adjacent 16-byte vectors per plane, one lane's: positions [a * UPOS, b * UPOS) as units, the ragged head and tail
+    // one at a time (k_depth_key<true>'s cut).  UNITS units per thread are in flight.
+    constexpr uint32_t VPU = (NARROW && GS_KEY_HIST_PAIR) ? 2u : 1u, UPOS = 4u * VPU;
+    constexpr uint32_t UNITS = VPU == 2u ? (uint32_t)(GS_KEY_HIST_PAIR ? GS_KEY_HIST_PAIR : 1) : KEY_HIST_VECS;
+    const uint32_t a = (p0 + UPOS - 1u) / UPOS, b = p1 / UPOS;
+    if (a < b) {
+        scalars(p0, a * UPOS);
+        scalars(b * UPOS, p1);
         const uint4* x4 = reinterpret_cast<const uint4*>(p.cx);
         const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
         const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
         int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-        for (uint32_t v0 = a4; v0 < b4; v0 += KEY_HIST_VECS * HIST_THREADS) {
-            uint4 x[KEY_HIST_VECS], y[KEY_HIST_VECS], z[KEY_HIST_VECS];
+        for (uint32_t u0 = a; u0 < b; u0 += UNITS * HIST_THREADS) {
+            uint4 x[UNITS][VPU], y[UNITS][VPU], z[UNITS][VPU];
 #pragma unroll
-            for (uint32_t k = 0; k < KEY_HIST_VECS; k++) {                 // (unconditional loads of clamped positions: one batch)
-                const uint32_t v = min(v0 + k * HIST_THREADS + tid, b4 - 1u);
-                x[k] = x4[v]; y[k] = y4[v]; z[k] = z4[v];
+            for (uint32_t k = 0; k < UNITS; k++) {                         // (unconditional loads of clamped positions: one batch)
+                const uint32_t u = min(u0 + k * HIST_THREADS + tid, b - 1u);
+#pragma unroll
+                for (uint32_t q = 0; q < VPU; q++) { x[k][q] = x4[u * VPU + q]; y[k][q] = y4[u * VPU + q]; z[k][q] = z4[u * VPU + q]; }
             }
 #pragma unroll
-            for (uint32_t k = 0; k < KEY_HIST_VECS; k++) {
-                const uint32_t v = v0 + k * HIST_THREADS + tid;
-                const int4 key = static_key_int4(p, x[k], y[k], z[k]);
-                if (v < b4) {
-                    o4[v] = key;
-                    count(key.x); count(key.y); count(key.z); count(key.w);
+            for (uint32_t k = 0; k < UNITS; k++) {
+                const uint32_t u = u0 + k * HIST_THREADS + tid;
+                int4 key[VPU];
+#pragma unroll
+                for (uint32_t q = 0; q < VPU; q++) key[q] = static_key_int4(p, x[k][q], y[k][q], z[k][q]);
+                if (u < b) {
+                    if constexpr (NARROW) {
+                        uint32_t w[2u * VPU];                              // two radix keys per word, the lower position in the low half
+#pragma unroll
+                        for (uint32_t q = 0; q < VPU; q++) {
+                            const uint32_t r0 = count(key[q].x), r1 = count(key[q].y), r2 = count(key[q].z), r3 = count(key[q].w);
+                            w[2u * q] = r0 | (r1 << 16);
+                            w[2u * q + 1u] = r2 | (r3 << 16);
+                        }
+                        if constexpr (VPU == 2u) reinterpret_cast<uint4*>(keys16)[u] = make_uint4(w[0], w[1], w[2], w[3]);
+                        else reinterpret_cast<uint2*>(keys16)[u] = make_uint2(w[0], w[1]);
+                    } else {
+                        o4[u] = key[0];
+                        count(key[0].x); count(key[0].y); count(key[0].z); count(key[0].w);
+                    }
                 }
             }
         }
-    } else {                                               // fewer than one aligned vector
+    } else {                                               // fewer than one aligned unit
         scalars(p0, p1);
     }
     __syncthreads();
@@ -1034,7 +1074,14 @@ __global__ void k_debug_buckets(DepthLoader ld, int32_t* out) {
         out[i] = (int32_t)ld.bucket(i);
 }
 
-// Pass 0 of a depth sort for one (CULL, IDX) combination of the loader: packed + chunk-staged, packed, or key + value output.
+// The int32 depth keys of a sort that stored only 16-bit radix keys (k_depth_key_hist<true>: the identity list, static integer
+// mode), for the test hooks.  Nothing else: no housekeeping, no min / max - the sort's SortFrame stays as that sort left it.
+__global__ __launch_bounds__(256) void k_debug_rekey(KeyParams p, uint32_t n) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        p.keys_out[i] = static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
+}
+
+// Pass 0 of a depth sort for one (CULL, IDX, NARROW) combination of the loader: packed + chunk-staged, packed, or key + value output.
 struct Pass0Args {
     DepthLoaderArgs ld;
     uint32_t Rs, val_bits;
@@ -1046,15 +1093,16 @@ struct Pass0Args {
     int slot;                           // pass 0's slot of group rows (0, or gs_sorter::clean_slot of a known-range sort)
     bool skip_hist;                     // k_depth_key_hist already left pass 0's histogram rows
 };
-template <bool CULL, bool IDX>
+template <bool CULL, bool IDX, bool NARROW = false>
 static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
-    typedef DepthLoaderT<CULL, IDX> L;
+    typedef DepthLoaderT<CULL, IDX, NARROW> L;
     const L d = {a.ld};
     L h = d;                            // only the histogram launch counts clamped buckets (once per element)
     h.count_clamps = 1;
     if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, a.vo, a.val_bits, a.kept_out, a.skip_hist);
     if (a.pack) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint8_t*)nullptr, a.vo, nullptr, 0u, a.val_bits, a.kept_out, a.skip_hist);
-    if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
+    if constexpr (!NARROW)              // (16-bit radix keys: buckets of <= 16 bits)
+        if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
     return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint16_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
 }
 
@@ -1093,6 +1141,7 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     A(s->cx, b4 + 16); A(s->cy, b4 + 16); A(s->cz, b4 + 16); A(s->caos, n * 16);   // (+16: k_cull_front reads whole 16-byte vectors)
     if (flags & GS_SORT_DYNAMIC) { A(s->cw, b4); A(s->scene_idx, b4); A(s->scene_rows, sizeof(SceneRows)); }
     A(s->keys, b4); A(s->keyA, b4); A(s->keyB, b4); A(s->valA, b4); A(s->valB, b4); A(s->sorted, b4);
+    A(s->keys16, n * 2 + 16);
     A(s->frame, 2 * sizeof(SortFrame));
     if (st == GS_OK) st = s->radix.init();
     if (st == GS_OK && (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess ||
@@ -1186,6 +1235,22 @@ static int sorter_update_extreme(gs_sorter* s, uint32_t from, uint32_t end, uint
     return GS_OK;
 }
 
+// A sort that stored 16-bit radix keys left `keys` stale, and gs_sorter_debug_read (selectors 0 and 1) describes the sort that ran:
+// its depth keys are rebuilt here, on the sorter's stream, from the planes and the coefficients of that sort - before a selector
+// reads them, and before an upload overwrites the planes they come from (set-up calls: one streaming kernel is free there).
+static int sorter_refresh_keys(gs_sorter* s) {
+    if (!s->keys_stale) return GS_OK;
+    KeyParams kp = {};
+    kp.cx = s->cx.as<uint32_t>(); kp.cy = s->cy.as<uint32_t>(); kp.cz = s->cz.as<uint32_t>();
+    kp.keys_out = s->keys.as<int32_t>();
+    kp.mode = MODE_INT;
+    kp.im0 = s->stale_im[0]; kp.im1 = s->stale_im[1]; kp.im2 = s->stale_im[2];
+    hipLaunchKernelGGL(k_debug_rekey, dim3(grid_for(s->stale_count, 1024, 2048)), dim3(256), 0, s->stream, kp, s->stale_count);
+    GS_HIP(hipGetLastError());
+    s->keys_stale = false;
+    return GS_OK;
+}
+
 int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const void* centers_aos4,
                              const uint32_t* scene_indexes) {
     GS_REQUIRE(s && centers_aos4, "sorter / centers == NULL");
@@ -1193,6 +1258,7 @@ int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || scene_indexes, "dynamic sorter needs scene_indexes");
     if (count == 0) return GS_OK;
     ScopedDevice sd(s->ctx->device);
+    GS_TRY(sorter_refresh_keys(s));                        // (ordered before the copies below)
     GS_HIP(hipMemcpyAsync(s->caos.as<uint4>() + from, centers_aos4, (size_t)count * 16, hipMemcpyHostToDevice, s->stream));
     return gs_sorter_commit_centers(s, from, count, scene_indexes);
 }
@@ -1203,6 +1269,7 @@ int gs_sorter_upload_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
 // asset_decode.hip's k_asset_centers): the SoA planes, the scene indexes and the bookkeeping of a `centers` message.
 int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const uint32_t* scene_indexes) {
     hipStream_t st = s->stream;
+    GS_TRY(sorter_refresh_keys(s));                        // (an asset's decode comes straight here: before the planes change)
     uint4* aos = s->caos.as<uint4>() + from;               // kept: index-list sorts gather 16 bytes per splat from it
     hipLaunchKernelGGL(k_aos4_to_soa, dim3(grid_for(count, 256, 4096)), dim3(256), 0, st, aos, count,
                        from, s->cx.as<uint32_t>(), s->cy.as<uint32_t>(), s->cz.as<uint32_t>(),
@@ -1272,13 +1339,15 @@ struct SortSwitches {
     bool no_pack;              // $GSPLAT_NO_SORT_PACK: the unpacked radix passes
     bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
     bool no_known_range;       // $GSPLAT_NO_KNOWN_RANGE: never k_depth_key_hist (and no extreme set: sorter_update_extreme)
+    bool no_narrow_keys;       // $GSPLAT_NO_NARROW_KEYS: k_depth_key_hist stores the int32 depths whatever the precision
 };
 static SortSwitches sort_switches() {
     static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
     static const char* vis_front = getenv("GSPLAT_VIS_FRONT");
     static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
     static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
-    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off()};
+    static const bool no_narrow_keys = getenv("GSPLAT_NO_NARROW_KEYS") != nullptr;
+    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off(), no_narrow_keys};
 }
 
 static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
@@ -1324,6 +1393,7 @@ struct SortPlan {
     bool vis_front;                    // the visibility cull's front end wrote keys and payloads of the survivors itself
     bool known_range;                  // k_depth_key_hist keyed the list and left pass 0's histogram (sort_known_range)
     int32_t range_lo, range_hi;        // ... with this exact key range
+    bool narrow;                       // ... and stored 16-bit radix keys (gs_sorter::keys16) instead of the depths
     uint32_t pass0_slot;               // pass 0's slot of group rows
 };
 
@@ -1628,13 +1698,20 @@ static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     pl.pass0_slot = pl.known_range ? s->clean_slot : 0u;
     // every other front end zeroes all four slots and the passes use slots 0 .. 2; the known-range kernel zeroes all but its own
     s->clean_slot = pl.pass0_slot == 3u ? 0u : 3u;
+    // a radix key of <= 16 bits travels as 16 bits (the same lo and hi decide the buckets, whichever kernel applies them)
+    pl.narrow = pl.known_range && s->precision <= 16u && !pl.sw.no_narrow_keys;
     if (pl.known_range) {
         DepthLoaderArgs hl = {};
         hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
         hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
-        hipLaunchKernelGGL(k_depth_key_hist, dim3(pass0_shape(s, pl).grid), dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo,
-                           pl.range_hi, 0, pl.pass0_slot, s->radix.block_hist.as<uint32_t>(),
-                           s->radix.digit_total.as<uint32_t>() + pl.pass0_slot * RADIX_SLOT_WORDS);
+        const dim3 grid(pass0_shape(s, pl).grid);
+        uint32_t* group_rows = s->radix.digit_total.as<uint32_t>() + pl.pass0_slot * RADIX_SLOT_WORDS;
+        if (pl.narrow)
+            hipLaunchKernelGGL(k_depth_key_hist<true>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
+                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>());
+        else
+            hipLaunchKernelGGL(k_depth_key_hist<false>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
+                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, (uint16_t*)nullptr);
     } else if (pl.fused_tree) {
         GS_TRY(launch_tree_front(s, pl, kp));
     } else if (pl.vis_cull) {
@@ -1658,6 +1735,7 @@ static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& k
     const bool own_payloads = pl.fused_tree || pl.vis_front;    // the fused copy / the cull's front end wrote the payloads themselves
     DepthLoaderArgs dl = {};
     dl.keys = s->keys.as<int32_t>();
+    dl.keys16 = s->keys16.as<uint16_t>();
     dl.keep = pl.cull ? kp.keep : nullptr;
     dl.idx = own_payloads ? s->pay_in.as<uint32_t>() : pl.idx_dev;
     dl.map = own_payloads ? nullptr : pl.map;
@@ -1695,7 +1773,8 @@ static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& k
             a.slot = (int)pl.pass0_slot;
             a.skip_hist = pl.known_range;
             const bool has_idx = dl.idx != nullptr;
-            if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
+            if (pl.narrow) GS_TRY((depth_pass0<false, false, true>(ex, a)));      // (a known-range sort: the identity list, no cull)
+            else if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
             else if (pl.cull) GS_TRY((depth_pass0<true, false>(ex, a)));
             else if (has_idx) GS_TRY((depth_pass0<false, true>(ex, a)));
             else GS_TRY((depth_pass0<false, false>(ex, a)));
@@ -1737,6 +1816,12 @@ static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, ui
     s->last_range_lo = pl.known_range ? pl.range_lo : 0;
     s->last_range_hi = pl.known_range ? pl.range_hi : 0;
     s->last_pass0_slot = pl.pass0_slot;
+    s->last_narrow = pl.narrow;
+    if (pl.Rs > 0) {                           // (a front end ran: `keys` holds this sort's depths, or it is stale from now on)
+        s->keys_stale = pl.narrow;
+        s->stale_im[0] = kp.im0; s->stale_im[1] = kp.im1; s->stale_im[2] = kp.im2;
+        s->stale_count = pl.R;
+    }
     s->last_identity = (pl.idx_dev == nullptr);
     s->last_culled = (pl.cull || pl.vis_cull || pl.list_count_dev) && pl.Rs > 0;   // the result's length lives in result_frame->kept
     s->last_vis_culled = pl.vis_cull && pl.Rs > 0;
@@ -1854,11 +1939,12 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     GS_REQUIRE(s->has_result, "no sort has run");
     if (what == 4) {
         // the last sort's front end, host words: {1 = k_depth_key_hist with a known range, |extreme set| (0: none), lo, hi as the
-        // host computed them (0, 0 on the other path), 1 = the set covers the current centres, pass 0's slot of group rows}
+        // host computed them (0, 0 on the other path), 1 = the set covers the current centres, pass 0's slot of group rows,
+        // 1 = that front end stored 16-bit radix keys}
         const bool valid = s->extreme_ok && s->extreme_version == s->centers_version;
-        const int32_t w[6] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
-                              valid ? 1 : 0, (int32_t)s->last_pass0_slot};
-        GS_REQUIRE(count <= 6u, "selector 4 holds 6 words");
+        const int32_t w[7] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
+                              valid ? 1 : 0, (int32_t)s->last_pass0_slot, s->last_narrow ? 1 : 0};
+        GS_REQUIRE(count <= 7u, "selector 4 holds 7 words");
         memcpy(dst, w, (size_t)count * 4);
         return GS_OK;
     }
@@ -1866,6 +1952,7 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     ScopedDevice sd(s->ctx->device);
     hipStream_t st = s->stream;
     const void* src = nullptr;
+    if (what == 0 || what == 1) GS_TRY(sorter_refresh_keys(s));     // (the depths of a sort that stored only 16-bit radix keys)
     if (what == 0) src = s->keys.p;
     else if (what == 2) {
         src = s->sorted.p;
