@@ -348,6 +348,27 @@ bool gs_extreme_set(const int32_t* a, size_t na, const int32_t* b, size_t nb, ui
     }
 }
 
+bool gs_compact_offsets(const int32_t* set_aos4, size_t n, int32_t offset[3]) {
+    if (!set_aos4 || n == 0) return false;
+    int32_t lo[3], hi[3];
+    for (int k = 0; k < 3; k++) lo[k] = hi[k] = set_aos4[k];
+    for (size_t i = 1; i < n; i++)
+        for (int k = 0; k < 3; k++) {
+            const int32_t v = set_aos4[4 * i + k];
+            lo[k] = std::min(lo[k], v);
+            hi[k] = std::max(hi[k], v);
+        }
+    for (int k = 0; k < 3; k++)
+        if ((int64_t)hi[k] - (int64_t)lo[k] > 65535) return false;     // (int64: hi - lo reaches 2^32 - 1)
+    for (int k = 0; k < 3; k++) offset[k] = lo[k];
+    return true;
+}
+
+extern "C" int gs_debug_compact_offsets(const int32_t* set_aos4, uint32_t count, int32_t* offset3) {
+    if (!offset3 || (count && !set_aos4)) return -1;
+    return gs_compact_offsets(set_aos4, count, offset3) ? 1 : 0;
+}
+
 extern "C" int gs_debug_extreme_set(const int32_t* prior_aos4, uint32_t prior_count, const int32_t* aos4, uint32_t count, uint32_t cap,
                                     int32_t* out_aos4, uint32_t* out_count) {
     if (!out_aos4 || !out_count || (prior_count && !prior_aos4) || (count && !aos4)) return -1;

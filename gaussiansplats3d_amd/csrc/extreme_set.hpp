@@ -21,6 +21,16 @@ constexpr uint32_t GS_EXTREME_CAP = 4096;      // points (64 KB as AoS x4); a sc
 // points could not be proven interior (or the work budget ran out) - no set, `out` is empty.
 bool gs_extreme_set(const int32_t* a, size_t na, const int32_t* b, size_t nb, uint32_t cap, std::vector<int32_t>& out);
 
+// Whether the centres fit 16-BIT OFFSET PLANES, decided from their extreme set (AoS x4 rows, `n` of them): every hull vertex is in
+// the set, so the per-axis min and max of ALL centres are attained in it.  true: max - min <= 65535 on every axis (int64: centres
+// sit anywhere in int32) and offset[k] = the minimum of axis k, so 0 <= c - offset <= 65535 for every centre.  false: an axis is
+// wider, or the set is empty - `offset` is left alone.  The sorter then streams c - offset as uint16 planes in its known-range
+// front end (sorter.hip, k_depth_key_hist<true, true>): im . c == im . offset + im . (c - offset) mod 2^32.
+bool gs_compact_offsets(const int32_t* set_aos4, size_t n, int32_t offset[3]);
+
+// Debug entry for the tests (pure host): 1 and offset3 = the offsets when the rows fit, 0 when they do not, -1 on bad arguments.
+extern "C" int gs_debug_compact_offsets(const int32_t* set_aos4, uint32_t count, int32_t* offset3);
+
 // Debug entry for the tests (pure host).  out holds up to cap rows.  Returns 0 and *out_count = |C|, 1 when the set does not fit
 // (*out_count = 0), -1 on bad arguments.
 extern "C" int gs_debug_extreme_set(const int32_t* prior_aos4, uint32_t prior_count, const int32_t* aos4, uint32_t count, uint32_t cap,

@@ -341,6 +341,15 @@ struct gs_sorter {
     std::vector<int32_t> extreme;
     bool extreme_ok = true;            // a set exists (no centres: the empty one); false: it did not fit GS_EXTREME_CAP
     uint32_t extreme_version = 0;      // the centers_version it covers: valid <=> extreme_ok && extreme_version == centers_version
+    // The centres as 16-bit offset planes, c - c16_off per axis (static integer sorters whose extreme set spans < 2^16 per axis;
+    // extreme_set.hpp, gs_compact_offsets): 6 bytes per splat instead of 12 for the known-range front end with 16-bit radix keys,
+    // the only reader.  Built from the int32 planes whenever centres are committed (sorter.hip, sorter_update_compact), allocated
+    // at the first build; the builder counts elements outside [0, 65535] into c16_bad, and a count other than 0 refuses the planes.
+    DevBuf cx16, cy16, cz16;           // uint16 [max] (+16 bytes: read as whole 16-byte vectors, like keys16)
+    DevBuf c16_bad;                    // uint32: the builder's violation count
+    bool c16_ok = false;               // the planes hold the centres of c16_version
+    uint32_t c16_version = 0;          // valid <=> c16_ok && c16_version == centers_version
+    int32_t c16_off[3] = {0, 0, 0};    // the per-axis minimum they are relative to
     // Pass 0's group rows alternate between slots 0 and 3 of RadixScratch::digit_total: k_depth_key_hist adds to them inside the
     // launch that zeroes the others, so they are zeroed a sort earlier (a depth sort has <= 3 passes: slot 3 is otherwise unused).
     uint32_t clean_slot = 3;           // zero at the start of the next sort, whatever path the last one took
@@ -348,6 +357,7 @@ struct gs_sorter {
     int32_t last_range_lo = 0, last_range_hi = 0;
     uint32_t last_pass0_slot = 0;
     bool last_narrow = false;          // ... and whether it stored 16-bit radix keys instead of the int32 depth keys
+    bool last_compact = false;         // ... and whether it read the 16-bit centre planes
     // After such a sort `keys` still holds an earlier sort's depths.  gs_sorter_debug_read (selectors 0 and 1) and an upload of
     // centres first rebuild them from the planes with the sort's own coefficients (sorter.hip, sorter_refresh_keys).
     bool keys_stale = false;

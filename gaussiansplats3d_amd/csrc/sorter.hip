@@ -73,6 +73,24 @@ __global__ __launch_bounds__(256) void k_aos4_to_soa(const uint4* __restrict__ a
     }
 }
 
+// The 16-bit offset planes of positions [from, end) from the int32 planes: d = c - o per axis (int64: centres sit anywhere in int32).
+// Every d must lie in [0, 65535]; the ones that do not are counted into *bad (and stored truncated - the host refuses the planes
+// when the count is not 0, so nothing ever reads them).
+__global__ __launch_bounds__(256) void k_compact_centres(const int32_t* __restrict__ x, const int32_t* __restrict__ y,
+                                                         const int32_t* __restrict__ z, uint32_t from, uint32_t end, int32_t ox, int32_t oy,
+                                                         int32_t oz, uint16_t* __restrict__ x16, uint16_t* __restrict__ y16,
+                                                         uint16_t* __restrict__ z16, uint32_t* __restrict__ bad) {
+    uint32_t nbad = 0;
+    for (uint32_t i = from + blockIdx.x * blockDim.x + threadIdx.x; i < end; i += gridDim.x * blockDim.x) {
+        const int64_t dx = (int64_t)x[i] - ox, dy = (int64_t)y[i] - oy, dz = (int64_t)z[i] - oz;
+        nbad += (dx < 0 || dx > 65535 || dy < 0 || dy > 65535 || dz < 0 || dz > 65535) ? 1u : 0u;
+        x16[i] = (uint16_t)dx;
+        y16[i] = (uint16_t)dy;
+        z16[i] = (uint16_t)dz;
+    }
+    if (nbad) atomicAdd(bad, nbad);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // The rules every front-end kernel shares, each said once: the static key, the centre as the frustum test sees it, the
 // housekeeping of a sort's first kernel, the min / max accumulator.
@@ -975,14 +993,34 @@ __global__ void k_unmap(const uint32_t* __restrict__ in, const uint32_t* __restr
 // A lane owns TWO adjacent vectors per plane there and stores its eight keys as one 16-byte store, one such pair in flight
 // (GS_KEY_HIST_PAIR = 2: two pairs; 0: one vector per lane and step as below, four keys as an 8-byte store - both measured slower,
 // profiles/r08_narrow_keys_ab.txt).  gs_sorter::keys is stale after such a sort (sorter_refresh_keys).
+// COMPACT (NARROW only): the centres come from the sorter's 16-bit offset planes (gs_sorter::cx16 ..: d = c - o per axis, o the
+// per-axis minimum, every d in [0, 65535] - counted by the builder, k_compact_centres), 6 bytes per splat instead of 12.  The key is
+// a wrapping 32-bit dot product, linear mod 2^32: im . c == im . o + im . d bit for bit, whatever wraps on the way; k0 = im . o is the
+// host's.  One 16-byte vector per plane is a lane's eight positions, so three 16-byte loads feed the one 16-byte store, and
+// GS_KEY_HIST_C16_UNITS of them are in flight per lane (one: 2 and 4 measured slower, profiles/r09_compact_centres_ab.txt).  The
+// ragged head and tail read the same planes one position at a time.  Keys, buckets, counts and the stored bytes are those of the
+// int32 planes.
 constexpr uint32_t KEY_HIST_VECS = 3;      // 16-byte vectors per plane a thread has in flight (one chunk of the chunk-staged pass)
 #ifndef GS_KEY_HIST_PAIR
 #define GS_KEY_HIST_PAIR 1
 #endif
-template <bool NARROW>
+#ifndef GS_KEY_HIST_C16_UNITS
+#define GS_KEY_HIST_C16_UNITS 1
+#endif
+struct CompactCentres {                    // the 16-bit offset planes as k_depth_key_hist<true, true> reads them
+    const uint16_t *x, *y, *z;
+    uint32_t k0;                           // static_key_int of the offset itself, wrapping
+};
+// The static integer key of one position of those planes (dx, dy, dz < 2^16): uint32 wrap-around, as static_key_int's.
+__device__ __forceinline__ int32_t compact_key_int(const KeyParams& p, uint32_t k0, uint32_t dx, uint32_t dy, uint32_t dz) {
+    return (int32_t)(k0 + dx * (uint32_t)p.im0 + dy * (uint32_t)p.im1 + dz * (uint32_t)p.im2);
+}
+template <bool NARROW, bool COMPACT = false>
 __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, DepthLoader ld, int32_t key_lo, int32_t key_hi, int shift,
                                                                   uint32_t keep_slot, uint32_t* __restrict__ block_hist,
-                                                                  uint32_t* __restrict__ group_rows, uint16_t* __restrict__ keys16) {
+                                                                  uint32_t* __restrict__ group_rows, uint16_t* __restrict__ keys16,
+                                                                  CompactCentres cc) {
+    static_assert(NARROW || !COMPACT, "the 16-bit centre planes feed the 16-bit radix keys only");
     __shared__ uint32_t s_hist[4][RADIX_BINS];               // waves w, w+4, w+8, w+12 share one
     const uint32_t tid = threadIdx.x, t = blockIdx.x * HIST_THREADS + tid;
     sort_begin(p, t, gridDim.x * HIST_THREADS, keep_slot);
@@ -1007,52 +1045,81 @@ __global__ __launch_bounds__(HIST_THREADS) void k_depth_key_hist(KeyParams p, De
     };
     auto scalars = [&](uint32_t begin, uint32_t end) {
         for (uint32_t i = begin + tid; i < end; i += HIST_THREADS) {
-            const int32_t k = static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
+            const int32_t k = COMPACT ? compact_key_int(p, cc.k0, cc.x[i], cc.y[i], cc.z[i]) : static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
             const uint32_t r = count(k);
             if (NARROW) keys16[i] = (uint16_t)r;
             else p.keys_out[i] = k;
         }
     };
     // A unit = VPU adjacent 16-byte vectors per plane, one lane's: positions [a * UPOS, b * UPOS) as units, the ragged head and tail
-    // one at a time (k_depth_key<true>'s cut).  UNITS units per thread are in flight.
-    constexpr uint32_t VPU = (NARROW && GS_KEY_HIST_PAIR) ? 2u : 1u, UPOS = 4u * VPU;
+    // one at a time (k_depth_key<true>'s cut).  UNITS units per thread are in flight.  COMPACT: a unit is ONE vector per plane,
+    // eight positions of 16 bits.
+    constexpr uint32_t VPU = (NARROW && GS_KEY_HIST_PAIR) ? 2u : 1u, UPOS = COMPACT ? 8u : 4u * VPU;
     constexpr uint32_t UNITS = VPU == 2u ? (uint32_t)(GS_KEY_HIST_PAIR ? GS_KEY_HIST_PAIR : 1) : KEY_HIST_VECS;
     const uint32_t a = (p0 + UPOS - 1u) / UPOS, b = p1 / UPOS;
     if (a < b) {
         scalars(p0, a * UPOS);
         scalars(b * UPOS, p1);
-        const uint4* x4 = reinterpret_cast<const uint4*>(p.cx);
-        const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
-        const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
-        int4* o4 = reinterpret_cast<int4*>(p.keys_out);
-        for (uint32_t u0 = a; u0 < b; u0 += UNITS * HIST_THREADS) {
-            uint4 x[UNITS][VPU], y[UNITS][VPU], z[UNITS][VPU];
+        if constexpr (COMPACT) {
+            constexpr uint32_t CU = GS_KEY_HIST_C16_UNITS;
+            const uint4* x8 = reinterpret_cast<const uint4*>(cc.x);
+            const uint4* y8 = reinterpret_cast<const uint4*>(cc.y);
+            const uint4* z8 = reinterpret_cast<const uint4*>(cc.z);
+            // two positions of one word per plane -> their two radix keys as one word, the lower position in the low half
+            auto two = [&](uint32_t xw, uint32_t yw, uint32_t zw) {
+                const uint32_t r0 = count(compact_key_int(p, cc.k0, xw & 0xFFFFu, yw & 0xFFFFu, zw & 0xFFFFu));
+                const uint32_t r1 = count(compact_key_int(p, cc.k0, xw >> 16, yw >> 16, zw >> 16));
+                return r0 | (r1 << 16);
+            };
+            for (uint32_t u0 = a; u0 < b; u0 += CU * HIST_THREADS) {
+                uint4 x[CU], y[CU], z[CU];
 #pragma unroll
-            for (uint32_t k = 0; k < UNITS; k++) {                         // (unconditional loads of clamped positions: one batch)
-                const uint32_t u = min(u0 + k * HIST_THREADS + tid, b - 1u);
+                for (uint32_t k = 0; k < CU; k++) {                        // (unconditional loads of clamped positions: one batch)
+                    const uint32_t u = min(u0 + k * HIST_THREADS + tid, b - 1u);
+                    x[k] = x8[u]; y[k] = y8[u]; z[k] = z8[u];
+                }
 #pragma unroll
-                for (uint32_t q = 0; q < VPU; q++) { x[k][q] = x4[u * VPU + q]; y[k][q] = y4[u * VPU + q]; z[k][q] = z4[u * VPU + q]; }
+                for (uint32_t k = 0; k < CU; k++) {
+                    const uint32_t u = u0 + k * HIST_THREADS + tid;
+                    if (u < b)
+                        reinterpret_cast<uint4*>(keys16)[u] = make_uint4(two(x[k].x, y[k].x, z[k].x), two(x[k].y, y[k].y, z[k].y),
+                                                                         two(x[k].z, y[k].z, z[k].z), two(x[k].w, y[k].w, z[k].w));
+                }
             }
+        } else {
+            const uint4* x4 = reinterpret_cast<const uint4*>(p.cx);
+            const uint4* y4 = reinterpret_cast<const uint4*>(p.cy);
+            const uint4* z4 = reinterpret_cast<const uint4*>(p.cz);
+            int4* o4 = reinterpret_cast<int4*>(p.keys_out);
+            for (uint32_t u0 = a; u0 < b; u0 += UNITS * HIST_THREADS) {
+                uint4 x[UNITS][VPU], y[UNITS][VPU], z[UNITS][VPU];
 #pragma unroll
-            for (uint32_t k = 0; k < UNITS; k++) {
-                const uint32_t u = u0 + k * HIST_THREADS + tid;
-                int4 key[VPU];
+                for (uint32_t k = 0; k < UNITS; k++) {                         // (unconditional loads of clamped positions: one batch)
+                    const uint32_t u = min(u0 + k * HIST_THREADS + tid, b - 1u);
 #pragma unroll
-                for (uint32_t q = 0; q < VPU; q++) key[q] = static_key_int4(p, x[k][q], y[k][q], z[k][q]);
-                if (u < b) {
-                    if constexpr (NARROW) {
-                        uint32_t w[2u * VPU];                              // two radix keys per word, the lower position in the low half
+                    for (uint32_t q = 0; q < VPU; q++) { x[k][q] = x4[u * VPU + q]; y[k][q] = y4[u * VPU + q]; z[k][q] = z4[u * VPU + q]; }
+                }
 #pragma unroll
-                        for (uint32_t q = 0; q < VPU; q++) {
-                            const uint32_t r0 = count(key[q].x), r1 = count(key[q].y), r2 = count(key[q].z), r3 = count(key[q].w);
-                            w[2u * q] = r0 | (r1 << 16);
-                            w[2u * q + 1u] = r2 | (r3 << 16);
+                for (uint32_t k = 0; k < UNITS; k++) {
+                    const uint32_t u = u0 + k * HIST_THREADS + tid;
+                    int4 key[VPU];
+#pragma unroll
+                    for (uint32_t q = 0; q < VPU; q++) key[q] = static_key_int4(p, x[k][q], y[k][q], z[k][q]);
+                    if (u < b) {
+                        if constexpr (NARROW) {
+                            uint32_t w[2u * VPU];                              // two radix keys per word, the lower position in the low half
+#pragma unroll
+                            for (uint32_t q = 0; q < VPU; q++) {
+                                const uint32_t r0 = count(key[q].x), r1 = count(key[q].y), r2 = count(key[q].z), r3 = count(key[q].w);
+                                w[2u * q] = r0 | (r1 << 16);
+                                w[2u * q + 1u] = r2 | (r3 << 16);
+                            }
+                            if constexpr (VPU == 2u) reinterpret_cast<uint4*>(keys16)[u] = make_uint4(w[0], w[1], w[2], w[3]);
+                            else reinterpret_cast<uint2*>(keys16)[u] = make_uint2(w[0], w[1]);
+                        } else {
+                            o4[u] = key[0];
+                            count(key[0].x); count(key[0].y); count(key[0].z); count(key[0].w);
                         }
-                        if constexpr (VPU == 2u) reinterpret_cast<uint4*>(keys16)[u] = make_uint4(w[0], w[1], w[2], w[3]);
-                        else reinterpret_cast<uint2*>(keys16)[u] = make_uint2(w[0], w[1]);
-                    } else {
-                        o4[u] = key[0];
-                        count(key[0].x); count(key[0].y); count(key[0].z); count(key[0].w);
                     }
                 }
             }
@@ -1235,6 +1302,48 @@ static int sorter_update_extreme(gs_sorter* s, uint32_t from, uint32_t end, uint
     return GS_OK;
 }
 
+// $GSPLAT_NO_COMPACT_CENTRES: no 16-bit centre planes are kept and the known-range front end reads the int32 planes (read once per
+// process)
+static bool compact_centres_off() {
+    static const bool off = getenv("GSPLAT_NO_COMPACT_CENTRES") != nullptr;
+    return off;
+}
+
+// The 16-bit centre planes follow the centres and their extreme set: called after sorter_update_extreme, with the stream idle and
+// the int32 planes of [from, end) written.  Valid only with a valid extreme set whose per-axis extent fits 16 bits
+// (gs_compact_offsets).  The same offsets as for the version before: only [from, end) is rebuilt - with the never-written gap in
+// front of a range that starts behind the old_uploaded rows in use before, which the set counts too; else every uploaded position.
+// The builder counts what does not fit - a hull vertex missing from the set then costs the planes, never a key.
+static int sorter_update_compact(gs_sorter* s, uint32_t from, uint32_t end, uint32_t old_uploaded) {
+    const bool was_current = s->c16_ok && s->c16_version + 1u == s->centers_version;
+    s->c16_ok = false;
+    if (s->flags != GS_SORT_INTEGER || compact_centres_off() || s->uploaded == 0u) return GS_OK;
+    if (!s->extreme_ok || s->extreme_version != s->centers_version) return GS_OK;
+    int32_t off[3];
+    if (!gs_compact_offsets(s->extreme.data(), s->extreme.size() / 4, off)) return GS_OK;
+    const size_t bytes = (size_t)s->max_count * 2 + 16;
+    bool fresh[3];
+    GS_TRY(s->cx16.ensure(bytes, &fresh[0])); GS_TRY(s->cy16.ensure(bytes, &fresh[1])); GS_TRY(s->cz16.ensure(bytes, &fresh[2]));
+    GS_TRY(s->c16_bad.ensure(4));
+    const bool keep = was_current && !fresh[0] && !fresh[1] && !fresh[2] && off[0] == s->c16_off[0] && off[1] == s->c16_off[1] &&
+                      off[2] == s->c16_off[2];
+    from = keep ? std::min(from, old_uploaded) : 0u;
+    if (!keep) end = s->uploaded;
+    hipStream_t st = s->stream;
+    uint32_t bad = 1u;
+    GS_HIP(hipMemsetAsync(s->c16_bad.p, 0, 4, st));
+    hipLaunchKernelGGL(k_compact_centres, dim3(grid_for(end - from, 1024, 4096)), dim3(256), 0, st, s->cx.as<int32_t>(), s->cy.as<int32_t>(),
+                       s->cz.as<int32_t>(), from, end, off[0], off[1], off[2], s->cx16.as<uint16_t>(), s->cy16.as<uint16_t>(),
+                       s->cz16.as<uint16_t>(), s->c16_bad.as<uint32_t>());
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpyAsync(&bad, s->c16_bad.p, 4, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    memcpy(s->c16_off, off, sizeof(off));
+    s->c16_version = s->centers_version;
+    s->c16_ok = bad == 0u;
+    return GS_OK;
+}
+
 // A sort that stored 16-bit radix keys left `keys` stale, and gs_sorter_debug_read (selectors 0 and 1) describes the sort that ran:
 // its depth keys are rebuilt here, on the sorter's stream, from the planes and the coefficients of that sort - before a selector
 // reads them, and before an upload overwrites the planes they come from (set-up calls: one streaming kernel is free there).
@@ -1282,6 +1391,7 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     if (from + count > s->uploaded) s->uploaded = from + count;   // uploadedSplatCount, SortWorker.js:97
     s->centers_version++;
     GS_TRY(sorter_update_extreme(s, from, from + count, old_uploaded, false));
+    GS_TRY(sorter_update_compact(s, from, from + count, old_uploaded));
     sorter_tell_mesh(s);                                   // (more centres than the bound mesh holds: no position map, no derived mask)
     return GS_OK;
 }
@@ -1303,6 +1413,7 @@ int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
     s->uploaded = count;
     s->centers_version++;
     GS_TRY(sorter_update_extreme(s, (uint32_t)from, count, (uint32_t)from, true));
+    GS_TRY(sorter_update_compact(s, (uint32_t)from, count, (uint32_t)from));
     sorter_tell_mesh(s);
     return GS_OK;
 }
@@ -1340,6 +1451,8 @@ struct SortSwitches {
     bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
     bool no_known_range;       // $GSPLAT_NO_KNOWN_RANGE: never k_depth_key_hist (and no extreme set: sorter_update_extreme)
     bool no_narrow_keys;       // $GSPLAT_NO_NARROW_KEYS: k_depth_key_hist stores the int32 depths whatever the precision
+    bool no_compact_centres;   // $GSPLAT_NO_COMPACT_CENTRES: k_depth_key_hist reads the int32 centre planes (and no 16-bit planes are
+                               // kept: sorter_update_compact)
 };
 static SortSwitches sort_switches() {
     static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
@@ -1347,7 +1460,7 @@ static SortSwitches sort_switches() {
     static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
     static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
     static const bool no_narrow_keys = getenv("GSPLAT_NO_NARROW_KEYS") != nullptr;
-    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off(), no_narrow_keys};
+    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off(), no_narrow_keys, compact_centres_off()};
 }
 
 static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
@@ -1394,6 +1507,7 @@ struct SortPlan {
     bool known_range;                  // k_depth_key_hist keyed the list and left pass 0's histogram (sort_known_range)
     int32_t range_lo, range_hi;        // ... with this exact key range
     bool narrow;                       // ... and stored 16-bit radix keys (gs_sorter::keys16) instead of the depths
+    bool compact;                      // ... out of the 16-bit centre planes (gs_sorter::cx16 ..) instead of the int32 ones
     uint32_t pass0_slot;               // pass 0's slot of group rows
 };
 
@@ -1700,18 +1814,28 @@ static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     s->clean_slot = pl.pass0_slot == 3u ? 0u : 3u;
     // a radix key of <= 16 bits travels as 16 bits (the same lo and hi decide the buckets, whichever kernel applies them)
     pl.narrow = pl.known_range && s->precision <= 16u && !pl.sw.no_narrow_keys;
+    // ... and then its centres come from the 16-bit offset planes, where they hold the centres as they are now
+    pl.compact = pl.narrow && !pl.sw.no_compact_centres && s->c16_ok && s->c16_version == s->centers_version;
     if (pl.known_range) {
         DepthLoaderArgs hl = {};
         hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
         hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
         const dim3 grid(pass0_shape(s, pl).grid);
         uint32_t* group_rows = s->radix.digit_total.as<uint32_t>() + pl.pass0_slot * RADIX_SLOT_WORDS;
-        if (pl.narrow)
+        CompactCentres cc = {};
+        if (pl.compact) {
+            cc.x = s->cx16.as<uint16_t>(); cc.y = s->cy16.as<uint16_t>(); cc.z = s->cz16.as<uint16_t>();
+            cc.k0 = (uint32_t)s->c16_off[0] * (uint32_t)kp.im0 + (uint32_t)s->c16_off[1] * (uint32_t)kp.im1 +
+                    (uint32_t)s->c16_off[2] * (uint32_t)kp.im2;         // static_key_int of the offset: uint32 wrap-around
+            hipLaunchKernelGGL((k_depth_key_hist<true, true>), grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi,
+                               0, pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>(), cc);
+        } else if (pl.narrow) {
             hipLaunchKernelGGL(k_depth_key_hist<true>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
-                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>());
-        else
+                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>(), cc);
+        } else {
             hipLaunchKernelGGL(k_depth_key_hist<false>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
-                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, (uint16_t*)nullptr);
+                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, (uint16_t*)nullptr, cc);
+        }
     } else if (pl.fused_tree) {
         GS_TRY(launch_tree_front(s, pl, kp));
     } else if (pl.vis_cull) {
@@ -1817,6 +1941,7 @@ static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, ui
     s->last_range_hi = pl.known_range ? pl.range_hi : 0;
     s->last_pass0_slot = pl.pass0_slot;
     s->last_narrow = pl.narrow;
+    s->last_compact = pl.compact;
     if (pl.Rs > 0) {                           // (a front end ran: `keys` holds this sort's depths, or it is stale from now on)
         s->keys_stale = pl.narrow;
         s->stale_im[0] = kp.im0; s->stale_im[1] = kp.im1; s->stale_im[2] = kp.im2;
@@ -1940,11 +2065,11 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     if (what == 4) {
         // the last sort's front end, host words: {1 = k_depth_key_hist with a known range, |extreme set| (0: none), lo, hi as the
         // host computed them (0, 0 on the other path), 1 = the set covers the current centres, pass 0's slot of group rows,
-        // 1 = that front end stored 16-bit radix keys}
+        // 1 = that front end stored 16-bit radix keys, 1 = it read the 16-bit centre planes}
         const bool valid = s->extreme_ok && s->extreme_version == s->centers_version;
-        const int32_t w[7] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
-                              valid ? 1 : 0, (int32_t)s->last_pass0_slot, s->last_narrow ? 1 : 0};
-        GS_REQUIRE(count <= 7u, "selector 4 holds 7 words");
+        const int32_t w[8] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
+                              valid ? 1 : 0, (int32_t)s->last_pass0_slot, s->last_narrow ? 1 : 0, s->last_compact ? 1 : 0};
+        GS_REQUIRE(count <= 8u, "selector 4 holds 8 words");
         memcpy(dst, w, (size_t)count * 4);
         return GS_OK;
     }

@@ -162,9 +162,11 @@ int gs_sorter_set_visibility_cull(gs_sorter* s, int enable);
  *       3 = keep bits of the last culled sort, bit (i & 31) of uint32 word i >> 5: per list position i after a frustum-culled
  *           sort, per ORIGINAL splat index i (the bound mesh's visibility mask as the sort consumed it) after a
  *           visibility-culled one,
- *       4 = the last sort's front end, up to 7 host words: {1 = the known-range kernel ran, size of the extreme set of the
+ *       4 = the last sort's front end, up to 8 host words: {1 = the known-range kernel ran, size of the extreme set of the
  *           centres (0: none), lo, hi of the key range as the host computed it (0, 0 on the other path), 1 = the set covers
- *           the current centres, pass 0's slot of group rows, 1 = the sort stored 16-bit radix keys instead of the depths}.
+ *           the current centres, pass 0's slot of group rows, 1 = the sort stored 16-bit radix keys instead of the depths,
+ *           1 = that kernel read the centres as 16-bit offset planes (an extreme set no wider than 65535 per axis; off with
+ *           $GSPLAT_NO_COMPACT_CENTRES) instead of the int32 planes}.
  * Selectors 0 and 1 always describe the sort that ran.  A sort that stored 16-bit radix keys (word 6 of selector 4) keeps
  * no depths: they are rebuilt on the device from the centres and that sort's coefficients when a selector asks for them,
  * and before an upload of centres overwrites what they are made from. */
