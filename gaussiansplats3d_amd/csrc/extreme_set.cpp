@@ -369,6 +369,39 @@ extern "C" int gs_debug_compact_offsets(const int32_t* set_aos4, uint32_t count,
     return gs_compact_offsets(set_aos4, count, offset3) ? 1 : 0;
 }
 
+bool gs_key_range(const int32_t* set_aos4, size_t n, const int32_t im[3], int32_t* lo_out, int32_t* hi_out) {
+    if (!set_aos4 || n == 0) return false;
+    const int32_t* c = set_aos4;
+    const int64_t a0 = im[0], a1 = im[1], a2 = im[2];
+    const int64_t small = (int64_t)1 << 29;                // |im| <= 2^29: three products of at most 2^60 add up in int64
+    __int128 lo, hi;
+    if (a0 >= -small && a0 <= small && a1 >= -small && a1 <= small && a2 >= -small && a2 <= small) {
+        int64_t l = INT64_MAX, h = INT64_MIN;
+        for (size_t i = 0; i < n; i++) {
+            const int64_t v = a0 * c[4 * i] + a1 * c[4 * i + 1] + a2 * c[4 * i + 2];
+            l = v < l ? v : l;
+            h = v > h ? v : h;
+        }
+        lo = l; hi = h;
+    } else {
+        lo = hi = (__int128)a0 * c[0] + (__int128)a1 * c[1] + (__int128)a2 * c[2];
+        for (size_t i = 1; i < n; i++) {
+            const __int128 v = (__int128)a0 * c[4 * i] + (__int128)a1 * c[4 * i + 1] + (__int128)a2 * c[4 * i + 2];
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+    }
+    if (lo < INT32_MIN || hi > INT32_MAX) return false;    // a key could wrap
+    *lo_out = (int32_t)lo;
+    *hi_out = (int32_t)hi;
+    return true;
+}
+
+extern "C" int gs_debug_key_range(const int32_t* set_aos4, uint32_t count, const int32_t* im3, int32_t* lo_hi2) {
+    if (!im3 || !lo_hi2 || (count && !set_aos4)) return -1;
+    return gs_key_range(set_aos4, count, im3, &lo_hi2[0], &lo_hi2[1]) ? 1 : 0;
+}
+
 extern "C" int gs_debug_extreme_set(const int32_t* prior_aos4, uint32_t prior_count, const int32_t* aos4, uint32_t count, uint32_t cap,
                                     int32_t* out_aos4, uint32_t* out_count) {
     if (!out_aos4 || !out_count || (prior_count && !prior_aos4) || (count && !aos4)) return -1;

@@ -31,6 +31,15 @@ bool gs_compact_offsets(const int32_t* set_aos4, size_t n, int32_t offset[3]);
 // Debug entry for the tests (pure host): 1 and offset3 = the offsets when the rows fit, 0 when they do not, -1 on bad arguments.
 extern "C" int gs_debug_compact_offsets(const int32_t* set_aos4, uint32_t count, int32_t* offset3);
 
+// The EXACT KEY RANGE of a sort, known before anything is launched: min / max of im . c over the extreme set (AoS x4 rows, `n` of
+// them), in exact integers.  true only when neither end leaves int32 - then no key of any centre wraps, every key is its true
+// value, and [lo, hi] is what the device-wide reduction would find.  false: a key could wrap, or the set is empty - lo / hi are
+// left alone.  (Whether a sort may use the range at all is sort_plan.cpp's decision.)
+bool gs_key_range(const int32_t* set_aos4, size_t n, const int32_t im[3], int32_t* lo, int32_t* hi);
+
+// Debug entry for the tests (pure host): 1 and lo_hi2 = {lo, hi}, 0 when there is no range, -1 on bad arguments.
+extern "C" int gs_debug_key_range(const int32_t* set_aos4, uint32_t count, const int32_t* im3, int32_t* lo_hi2);
+
 // Debug entry for the tests (pure host).  out holds up to cap rows.  Returns 0 and *out_count = |C|, 1 when the set does not fit
 // (*out_count = 0), -1 on bad arguments.
 extern "C" int gs_debug_extreme_set(const int32_t* prior_aos4, uint32_t prior_count, const int32_t* aos4, uint32_t count, uint32_t cap,

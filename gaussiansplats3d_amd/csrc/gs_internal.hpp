@@ -11,6 +11,7 @@
 
 #include "../../include/gsplat_hip.h"
 #include "draw_plan.hpp"
+#include "sort_plan.hpp"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -138,26 +139,8 @@ constexpr uint32_t GS_DEEP_NONE = 0xFFFFFFFFu;
 constexpr uint32_t GS_FLAG_COUNT = 0, GS_FLAG_CAND = 1, GS_FLAG_POOL_NEXT = 2, GS_FLAG_POOL_OVER = 3, GS_FLAG_UNITS = 4, GS_FLAG_UNIT_NEXT = 5, GS_FLAG_LIST = 8,
                    GS_FLAG_OF = GS_FLAG_LIST + GS_DEEP_MAX_BINS;
 
-#ifndef RADIX_TILE_CFG
-#define RADIX_TILE_CFG 4096
-#endif
-constexpr int RADIX_TILE = RADIX_TILE_CFG;                // keys per workgroup iteration
-// Rows of a radix pass's offset table = the most workgroups (chunks) a pass may have.  The chunk-staged passes of the depth
-// sort (radix.hpp) want <= 3 tiles per workgroup: 2048 rows cover 25 M keys.
-#ifndef RADIX_MAX_BLOCKS_CFG
-#define RADIX_MAX_BLOCKS_CFG 2048
-#endif
-constexpr int RADIX_MAX_BLOCKS = RADIX_MAX_BLOCKS_CFG;
-// Grid cap of the tile-at-a-time scatter kernel.  Every workgroup starts by summing rows of the two-level offset table, so fewer,
-// longer workgroups win: same-box A/B of the isolated C3 depth sort (r04a/b) 256: 0.0806 ms, 384: 0.0798, 512: 0.0733,
-// 1024: 0.0822, 2048: 0.093 (r01e, whole frames: 2048: 0.498, 1024: 0.477, 512: 0.471, 384: 0.489, 256: 0.483).
-#ifndef RADIX_TILE_GRID_CFG
-#define RADIX_TILE_GRID_CFG 512
-#endif
-constexpr int RADIX_TILE_GRID = RADIX_TILE_GRID_CFG;
-static_assert(RADIX_TILE_GRID <= RADIX_MAX_BLOCKS, "the tile kernel's grid needs a table row per workgroup");
+// (RADIX_TILE, RADIX_MAX_BLOCKS, RADIX_TILE_GRID, RADIX_MAX_PASSES and the grids of a pass: sort_plan.hpp)
 constexpr int RADIX_BINS = 256;
-constexpr int RADIX_MAX_PASSES = 4;
 constexpr int RADIX_GROUP = 32;                           // workgroups per group row of the two-level offset table (radix.hpp)
 constexpr int RADIX_MAX_GROUPS = RADIX_MAX_BLOCKS / RADIX_GROUP;
 constexpr int RADIX_TOTAL_WORDS = RADIX_MAX_PASSES * RADIX_MAX_GROUPS * RADIX_BINS;
@@ -321,23 +304,24 @@ struct gs_sorter {
     uint32_t leaf_cache_centers = 0, leaf_cache_layout = 0, leaf_cache_uploaded = 0;
     const void* leaf_cache_mesh = nullptr;
     uint32_t last_render = 0, last_sort = 0, last_passes = 0;
-    bool last_identity = true;
     bool has_result = false;
     bool frustum_cull = false;         // gs_sorter_set_frustum_cull
     bool visibility_cull = false;      // gs_sorter_set_visibility_cull
-    bool last_culled = false;          // the resident result holds only the kept splats; its length lives in result_frame
+    // The last sort as it was planned and ran (sort_plan.hpp): gs_sorter_debug_read (selectors 4, 5), the statistics and a draw read
+    // it.  last_plan.count_on_device: the resident result holds only the kept splats; its length lives in result_frame.
+    SortPlanIn last_in = {};
+    SortPlan last_plan = {};
     const SortFrame* result_frame = nullptr;
     DevBuf keep_mask;                  // 1 bit per list position (frustum-cull variant)
     DevBuf chunk_counts;               // survivors per chunk of the identity list (visibility-cull variant)
     DevBuf mask_copy;                  // the bound mesh's visibility mask as the last visibility-culled sort consumed it
-    bool last_vis_culled = false;
     // distances a gs_mesh_compute_distances(..., dst = this sorter) left in `precomputed` (sorts with GS_PRECOMPUTED_DEVICE)
     bool dev_distances = false;        // cleared when a sort copies host distances over them
     uint32_t dev_distances_count = 0;  // the mesh's uploaded splat count when they were computed
     bool dev_distances_integer = false;
     hipEvent_t ev_handover = nullptr;  // orders that hand-over between the context's stream and this sorter's
     // The extreme set of the centres (extreme_set.hpp; static integer sorters only): AoS x4 rows that hold every hull vertex of
-    // the uploaded centres.  A sort's exact key range is its min / max over these rows (sorter.hip, sort_known_range).
+    // the uploaded centres.  A sort's exact key range is its min / max over these rows (extreme_set.hpp, gs_key_range).
     std::vector<int32_t> extreme;
     bool extreme_ok = true;            // a set exists (no centres: the empty one); false: it did not fit GS_EXTREME_CAP
     uint32_t extreme_version = 0;      // the centers_version it covers: valid <=> extreme_ok && extreme_version == centers_version
@@ -353,12 +337,7 @@ struct gs_sorter {
     // Pass 0's group rows alternate between slots 0 and 3 of RadixScratch::digit_total: k_depth_key_hist adds to them inside the
     // launch that zeroes the others, so they are zeroed a sort earlier (a depth sort has <= 3 passes: slot 3 is otherwise unused).
     uint32_t clean_slot = 3;           // zero at the start of the next sort, whatever path the last one took
-    bool last_known_range = false;     // what gs_sorter_debug_read(what = 4) reports of the last sort
-    int32_t last_range_lo = 0, last_range_hi = 0;
-    uint32_t last_pass0_slot = 0;
-    bool last_narrow = false;          // ... and whether it stored 16-bit radix keys instead of the int32 depth keys
-    bool last_compact = false;         // ... and whether it read the 16-bit centre planes
-    // After such a sort `keys` still holds an earlier sort's depths.  gs_sorter_debug_read (selectors 0 and 1) and an upload of
+    // After a sort that stored 16-bit radix keys `keys` still holds an earlier sort's depths.  gs_sorter_debug_read (selectors 0 and 1) and an upload of
     // centres first rebuild them from the planes with the sort's own coefficients (sorter.hip, sorter_refresh_keys).
     bool keys_stale = false;
     int32_t stale_im[3] = {0, 0, 0};   // KeyParams::im0 .. im2 of that sort

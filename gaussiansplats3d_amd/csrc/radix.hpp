@@ -615,33 +615,17 @@ __global__ __launch_bounds__(SCATTER_THREADS, SCATTER_OCC_CFG) void k_radix_scat
 //   PACK_OUT   out word = (key >> (shift + 8)) << val_bits | value (what the next pass reads), digit staged as a byte beside it;
 //   otherwise  the last pass after a packing one: staged digit << 24 | value (value < 2^24 whenever a pass packs 8 key bits), out = value.
 // Geometry: 512 threads, 8 keys per lane and tile; LDS = 5 (4) bytes per key of the chunk + 8 KB: two workgroups per CU.
-#ifndef CHUNK_TILES_CFG
-#define CHUNK_TILES_CFG 3
-#endif
 #ifndef CHUNK_THREADS_CFG
 #define CHUNK_THREADS_CFG 512
 #endif
 #ifndef CHUNK_OCC_CFG
 #define CHUNK_OCC_CFG 4
 #endif
-constexpr int CHUNK_TILES = CHUNK_TILES_CFG;
 constexpr int CHUNK_THREADS = CHUNK_THREADS_CFG;
 constexpr int CHUNK_WAVES = CHUNK_THREADS / 64;
 constexpr int CHUNK_ITEMS = RADIX_TILE / CHUNK_THREADS;
 constexpr int CHUNK_KEYS = CHUNK_TILES * RADIX_TILE;
-#ifndef CHUNK_TARGET_BLOCKS_CFG
-#define CHUNK_TARGET_BLOCKS_CFG 512
-#endif
-constexpr int CHUNK_TARGET_BLOCKS = CHUNK_TARGET_BLOCKS_CFG;                   // two workgroups per CU: the chunk length aims at this many of them
-
-inline uint32_t radix_chunk_grid_for(uint32_t n_upper) {    // 0: too long for chunk-sized workgroups (the tile kernel takes it)
-    uint32_t tiles = (n_upper + RADIX_TILE - 1) / RADIX_TILE;
-    if (tiles < 1) tiles = 1;
-    uint32_t per = (tiles + CHUNK_TARGET_BLOCKS - 1) / CHUNK_TARGET_BLOCKS;
-    if (per > (uint32_t)CHUNK_TILES) per = CHUNK_TILES;
-    const uint32_t grid = (tiles + per - 1) / per;
-    return grid <= (uint32_t)RADIX_MAX_BLOCKS ? grid : 0u;
-}
+// (CHUNK_TILES, CHUNK_TARGET_BLOCKS and radix_chunk_grid_for: sort_plan.hpp)
 
 template <class Loader, bool PACK_OUT, bool ATOMIC_RANK>
 __global__ __launch_bounds__(CHUNK_THREADS, CHUNK_OCC_CFG) void k_radix_scatter_chunk(Loader ld, int shift,
@@ -746,14 +730,6 @@ __global__ __launch_bounds__(CHUNK_THREADS, CHUNK_OCC_CFG) void k_radix_scatter_
 // ---------------------------------------------------------------------------------------------------
 // host launcher for one pass
 // ---------------------------------------------------------------------------------------------------
-inline uint32_t radix_grid_for(uint32_t n_upper) {
-    uint32_t tiles = (n_upper + RADIX_TILE - 1) / RADIX_TILE;
-    if (tiles < 1) tiles = 1;
-    if (tiles <= (uint32_t)RADIX_TILE_GRID) return tiles;
-    const uint32_t per = (tiles + RADIX_TILE_GRID - 1) / RADIX_TILE_GRID;
-    return (tiles + per - 1) / per;
-}
-
 // What every pass launches: the histogram over `grid` workgroups into the scratch's rows, then `scatter(atomic_rank, bh, dt)`
 // on the same grid with ATOMIC_RANK as a compile-time bool.  pass_slot picks the zeroed digit_total row (the caller zeroes
 // RadixScratch::digit_total once per frame).  skip_hist: the kernel in front of this pass already left the rows of this grid and
@@ -769,32 +745,31 @@ int radix_launch(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift,
     return GS_OK;
 }
 
-// n_upper: host-side upper bound of the element count (sizes the grid).
+// grid: the caller's radix_grid_for(an upper bound of the element count) - the depth sort's is planned (sort_plan.hpp).
 template <class HistLoader, class Loader, class KeyOutT, bool WRITE_KEYS, bool RANGES, bool PACK_OUT>
-int radix_pass_ex(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
+int radix_pass_ex(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t grid, int shift,
                   int pass_slot, KeyOutT* keys_out, uint32_t* vals_out, uint2* ranges, uint32_t direct_ranges, uint32_t val_bits,
                   uint32_t* count_out = nullptr, bool skip_hist = false) {
-    const uint32_t grid = radix_grid_for(n_upper);
     return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, skip_hist, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
         hipLaunchKernelGGL((k_radix_scatter<Loader, KeyOutT, WRITE_KEYS, RANGES, decltype(atomic)::value, PACK_OUT>), dim3(grid),
                            dim3(SCATTER_THREADS), 0, ex.stream, ld, shift, bh, dt, keys_out, vals_out, ranges, direct_ranges, val_bits, count_out);
     });
 }
 
-// A pass of the depth sort between / after packing passes (see k_radix_scatter_chunk); the caller checked radix_chunk_grid_for.
+// A pass of the depth sort between / after packing passes (see k_radix_scatter_chunk); grid: the planned radix_chunk_grid_for, not 0.
 template <class HistLoader, class Loader, bool PACK_OUT>
-int radix_pass_chunk(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t n_upper, int shift,
+int radix_pass_chunk(const RadixExec& ex, const HistLoader& ld_hist, int hist_shift, const Loader& ld, uint32_t grid, int shift,
                      int pass_slot, uint32_t* out, uint32_t val_bits, uint32_t* count_out = nullptr, bool skip_hist = false) {
-    const uint32_t grid = radix_chunk_grid_for(n_upper);
     return radix_launch(ex, ld_hist, hist_shift, grid, pass_slot, skip_hist, [&](auto atomic, uint32_t* bh, uint32_t* dt) {
         hipLaunchKernelGGL((k_radix_scatter_chunk<Loader, PACK_OUT, decltype(atomic)::value>), dim3(grid), dim3(CHUNK_THREADS), 0,
                            ex.stream, ld, shift, bh, dt, out, val_bits, count_out);
     });
 }
 
+// n_upper: host-side upper bound of the element count (sizes the grid).
 template <class Loader, class KeyOutT, bool WRITE_KEYS, bool RANGES = false>
 int radix_pass(const RadixExec& ex, const Loader& ld_hist, const Loader& ld, uint32_t n_upper, int shift, int pass_slot,
                KeyOutT* keys_out, uint32_t* vals_out, uint2* ranges = nullptr, uint32_t direct_ranges = 0) {
-    return radix_pass_ex<Loader, Loader, KeyOutT, WRITE_KEYS, RANGES, false>(ex, ld_hist, shift, ld, n_upper, shift, pass_slot, keys_out,
+    return radix_pass_ex<Loader, Loader, KeyOutT, WRITE_KEYS, RANGES, false>(ex, ld_hist, shift, ld, radix_grid_for(n_upper), shift, pass_slot, keys_out,
                                                                              vals_out, ranges, direct_ranges, 0u);
 }

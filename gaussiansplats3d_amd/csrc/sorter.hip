@@ -5,6 +5,9 @@
 //                    key' = range-1-bucket of the REVERSED list, which reproduces the reference's output
 //                    order exactly: buckets far->near, equal buckets in reverse input order
 //                    (sorter.cpp:142-167).
+// What one sort launches - which front end, on which grids, what every radix pass reads and writes - is decided before anything is
+// enqueued, by plan_sort (sort_plan.cpp: host only, held to a host model by tests/test_sort_plan.py); the host code at the end of
+// this file gathers the plan's inputs, runs the refusals and acts on the plan.
 // Arithmetic that decides the order is spelled with non-contracting intrinsics (__fmul_rn ...) so hipcc's
 // default fp-contract=fast cannot fuse it; this file is also built with -ffp-contract=off.
 #include <math.h>
@@ -20,9 +23,6 @@ __host__ __device__ static inline int32_t trunc_f64_i32(double v) {
 }
 
 constexpr uint32_t MODE_INT = 1, MODE_DYNAMIC = 2, MODE_PRECOMPUTED = 4;
-#ifndef GS_KEY_GRID_MULT
-#define GS_KEY_GRID_MULT 2             // workgroups of k_depth_key<VEC4> per CU
-#endif
 
 struct SceneRows {                 // per-scene clip-z row (mvp * transform)[2], as int x1000 and as float
     int32_t im[GS_MAX_SCENES][4];
@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyPar
 //                    sort keeps the reference's tie order), its length -> SortFrame::kept;
 //   then the ordinary index-list sort runs on that list with the min / max above (k_depth_key ext_minmax, DepthLoader n_dev).
 // A rank of a multi-GPU draw therefore streams 12 bytes per splat and radix-sorts only what its strip draws.
-constexpr uint32_t VC_THREADS = 256, VC_SPAN = 1024;       // positions per workgroup iteration (4 per lane; 32 mask words)
+// (VC_THREADS = 256 threads, VC_SPAN = 1024 positions per workgroup iteration - 4 per lane, 32 mask words: sort_plan.hpp)
 
 __global__ __launch_bounds__(VC_THREADS) void k_minmax_count(KeyParams p, const uint32_t* __restrict__ mask, uint32_t chunk_len,
                                                              uint32_t* __restrict__ chunk_counts) {
@@ -615,9 +615,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_mask_compact(uint32_t* __restric
 // for nothing; one contiguous run per WAVE needs no barrier at all but makes 8192 concurrent DRAM streams - 36-42 us for the 93 MB;
 // spans handled one by one put a store round trip between them - predicated stores cannot be counted, the compiler drains the queue -
 // and a run-time `map ? load : index` put every payload load in a branch of its own with a full wait behind it.)
-constexpr uint32_t VC_WAVE_SPAN = 256;                     // positions per wave and span (4 per lane; 8 mask words)
-constexpr uint32_t VC_UNROLL = 2;                          // spans per wave and turn (two turns' loads in flight: 2 x 8 x 16 bytes per lane)
-constexpr uint32_t VC_TURN = VC_UNROLL * VC_WAVE_SPAN * (VC_THREADS / 64u);   // positions per workgroup and turn (4096)
+// (VC_WAVE_SPAN, VC_UNROLL and VC_TURN = 2048 positions per workgroup and turn: sort_plan.hpp)
 
 __global__ __launch_bounds__(VC_THREADS) void k_mask_count(KeyParams p, const uint32_t* __restrict__ mask, uint32_t chunk_len,
                                                            uint32_t* __restrict__ chunk_counts) {
@@ -978,7 +976,7 @@ __global__ void k_unmap(const uint32_t* __restrict__ in, const uint32_t* __restr
 }
 
 // Phase A + the histogram of pass 0 in ONE streaming launch, for a sort whose exact key range the host already knows: a full sort
-// of the identity list in static integer mode whose keys cannot wrap (sort_known_range: min / max of im . c over the extreme set of
+// of the identity list in static integer mode whose keys cannot wrap (sort_plan.cpp; gs_key_range: min / max of im . c over the extreme set of
 // the centres, extreme_set.hpp).  A key's bucket needs the min and max over ALL keys (sorter.cpp:142-146); here they are kernel
 // arguments, so a workgroup buckets and counts its keys as it makes them: no min / max reduction, no wait for another workgroup,
 // no k_radix_hist and no re-read of the keys.  The grid is pass 0's scatter grid and a workgroup keys ITS chunk of that pass
@@ -1148,29 +1146,66 @@ __global__ __launch_bounds__(256) void k_debug_rekey(KeyParams p, uint32_t n) {
         p.keys_out[i] = static_key_int(p, p.cx[i], p.cy[i], p.cz[i]);
 }
 
-// Pass 0 of a depth sort for one (CULL, IDX, NARROW) combination of the loader: packed + chunk-staged, packed, or key + value output.
-struct Pass0Args {
-    DepthLoaderArgs ld;
+// One radix pass of a depth sort as the plan records it (sort_plan.hpp, SortPass): the buffers it may touch ...
+struct PassBuffers {
+    DepthLoaderArgs dl;                 // pass 0's loader
+    const uint32_t* n_dev;              // the later passes' element count when it lives on the device (else nullptr: Rs)
     uint32_t Rs, val_bits;
-    int shift;
-    bool pack, chunked, wide;
-    void* kbuf0;
-    uint32_t* vo;
-    uint32_t* kept_out;
-    int slot;                           // pass 0's slot of group rows (0, or gs_sorter::clean_slot of a known-range sort)
-    bool skip_hist;                     // k_depth_key_hist already left pass 0's histogram rows
+    void* kbuf[2];                      // key / value ping-pong
+    uint32_t* vbuf[2];
+    uint32_t* out_tail;                 // the sorted part of the result
+    uint32_t* kept_out;                 // a culling pass 0 publishes the result's length here
 };
+// ... pass 0 for one (CULL, IDX, NARROW) combination of the loader: packed + chunk-staged, packed, or key + value output ...
 template <bool CULL, bool IDX, bool NARROW = false>
-static int depth_pass0(const RadixExec& ex, const Pass0Args& a) {
+static int launch_depth_pass(const RadixExec& ex, const SortPass& ps, const PassBuffers& b, uint32_t* vo) {
     typedef DepthLoaderT<CULL, IDX, NARROW> L;
-    const L d = {a.ld};
+    const L d = {b.dl};
     L h = d;                            // only the histogram launch counts clamped buckets (once per element)
     h.count_clamps = 1;
-    if (a.pack && a.chunked) return radix_pass_chunk<L, L, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, a.vo, a.val_bits, a.kept_out, a.skip_hist);
-    if (a.pack) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint8_t*)nullptr, a.vo, nullptr, 0u, a.val_bits, a.kept_out, a.skip_hist);
+    const int hs = (int)ps.hist_shift, sh = (int)ps.shift, slot = (int)ps.slot;
+    const bool skip = ps.skip_hist != 0u;
+    if (ps.out == SORT_OUT_PACKED && ps.chunked) return radix_pass_chunk<L, L, true>(ex, h, hs, d, ps.grid, sh, slot, vo, b.val_bits, b.kept_out, skip);
+    if (ps.out == SORT_OUT_PACKED) return radix_pass_ex<L, L, uint8_t, false, false, true>(ex, h, hs, d, ps.grid, sh, slot, (uint8_t*)nullptr, vo, nullptr, 0u, b.val_bits, b.kept_out, skip);
     if constexpr (!NARROW)              // (16-bit radix keys: buckets of <= 16 bits)
-        if (a.wide) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint32_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
-    return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, a.shift, d, a.Rs, a.shift, a.slot, (uint16_t*)a.kbuf0, a.vo, nullptr, 0u, 0u, a.kept_out, a.skip_hist);
+        if (ps.out == SORT_OUT_KV32) return radix_pass_ex<L, L, uint32_t, true, false, false>(ex, h, hs, d, ps.grid, sh, slot, (uint32_t*)b.kbuf[0], vo, nullptr, 0u, 0u, b.kept_out, skip);
+    return radix_pass_ex<L, L, uint16_t, true, false, false>(ex, h, hs, d, ps.grid, sh, slot, (uint16_t*)b.kbuf[0], vo, nullptr, 0u, 0u, b.kept_out, skip);
+}
+// ... and pass p, whatever it reads and writes.
+static int launch_pass(const RadixExec& ex, const SortPass& ps, uint32_t p, const PassBuffers& b) {
+    typedef ArrayLoader<uint32_t> A32;
+    typedef ArrayLoader<uint16_t> A16;
+    uint32_t* vo = ps.last ? b.out_tail : b.vbuf[p & 1];
+    const void* kin = b.kbuf[(p + 1) & 1];                 // what pass p - 1 wrote
+    const uint32_t* vin = b.vbuf[(p + 1) & 1];
+    const int hs = (int)ps.hist_shift, sh = (int)ps.shift, slot = (int)ps.slot;
+    const bool packs = ps.out == SORT_OUT_PACKED;
+    switch (ps.in) {
+    case SORT_IN_DEPTH:
+        if (ps.in_narrow) return launch_depth_pass<false, false, true>(ex, ps, b, vo);   // (a known-range sort: the identity list, no cull)
+        if (ps.in_cull) return ps.in_idx ? launch_depth_pass<true, true>(ex, ps, b, vo) : launch_depth_pass<true, false>(ex, ps, b, vo);
+        return ps.in_idx ? launch_depth_pass<false, true>(ex, ps, b, vo) : launch_depth_pass<false, false>(ex, ps, b, vo);
+    case SORT_IN_PACKED: {
+        const PackedLoader pk = {vin, b.n_dev, b.Rs, b.val_bits};
+        const A32 ph = {vin, nullptr, b.n_dev, b.Rs};      // (the histogram reads the packed words as plain keys)
+        if (ps.chunked && packs) return radix_pass_chunk<A32, PackedLoader, true>(ex, ph, hs, pk, ps.grid, sh, slot, vo, b.val_bits);
+        if (ps.chunked) return radix_pass_chunk<A32, PackedLoader, false>(ex, ph, hs, pk, ps.grid, sh, slot, vo, 0u);
+        if (packs) return radix_pass_ex<A32, PackedLoader, uint8_t, false, false, true>(ex, ph, hs, pk, ps.grid, sh, slot, (uint8_t*)nullptr, vo, nullptr, 0u, b.val_bits);
+        return radix_pass_ex<A32, PackedLoader, uint8_t, false, false, false>(ex, ph, hs, pk, ps.grid, sh, slot, (uint8_t*)nullptr, vo, nullptr, 0u, 0u);
+    }
+    case SORT_IN_KEYS32: {
+        const A32 al = {(const uint32_t*)kin, vin, b.n_dev, b.Rs};
+        if (ps.out == SORT_OUT_FINAL) return radix_pass_ex<A32, A32, uint32_t, false, false, false>(ex, al, hs, al, ps.grid, sh, slot, (uint32_t*)nullptr, vo, nullptr, 0u, 0u);
+        if (packs) return radix_pass_ex<A32, A32, uint8_t, false, false, true>(ex, al, hs, al, ps.grid, sh, slot, (uint8_t*)nullptr, vo, nullptr, 0u, b.val_bits);
+        return radix_pass_ex<A32, A32, uint32_t, true, false, false>(ex, al, hs, al, ps.grid, sh, slot, (uint32_t*)b.kbuf[p & 1], vo, nullptr, 0u, 0u);
+    }
+    case SORT_IN_KEYS16: {
+        const A16 al = {(const uint16_t*)kin, vin, b.n_dev, b.Rs};
+        if (ps.out == SORT_OUT_FINAL) return radix_pass_ex<A16, A16, uint16_t, false, false, false>(ex, al, hs, al, ps.grid, sh, slot, (uint16_t*)nullptr, vo, nullptr, 0u, 0u);
+        return radix_pass_ex<A16, A16, uint16_t, true, false, false>(ex, al, hs, al, ps.grid, sh, slot, (uint16_t*)b.kbuf[p & 1], vo, nullptr, 0u, 0u);
+    }
+    }
+    GS_REQUIRE(false, "sort plan: unknown loader");
 }
 
 static inline uint32_t grid_for(uint32_t n, uint32_t per_block, uint32_t cap) {
@@ -1263,10 +1298,21 @@ void gs_sorter_destroy(gs_sorter* s) {
 
 static void sorter_tell_mesh(gs_sorter* s);   // (defined with gs_sorter_bind_mesh)
 
-// $GSPLAT_NO_KNOWN_RANGE: no extreme set is kept and every sort takes the key kernel + histogram kernel path (read once per process)
-static bool known_range_off() {
-    static const bool off = getenv("GSPLAT_NO_KNOWN_RANGE") != nullptr;
-    return off;
+// The switches of this file (sort_plan.hpp, SortSwitches), read here and nowhere else: once per process, at the first upload or sort.
+static SortSwitches sort_switches() {
+    static const SortSwitches sw = [] {
+        SortSwitches w = {};
+        const char* vis_front = getenv("GSPLAT_VIS_FRONT");
+        w.tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
+        w.vis_front = !vis_front ? 0u : vis_front[0] == 's' ? 1u : 2u;
+        w.no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
+        w.no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
+        w.no_known_range = getenv("GSPLAT_NO_KNOWN_RANGE") != nullptr;
+        w.no_narrow_keys = getenv("GSPLAT_NO_NARROW_KEYS") != nullptr;
+        w.no_compact_centres = getenv("GSPLAT_NO_COMPACT_CENTRES") != nullptr;
+        return w;
+    }();
+    return sw;
 }
 
 // The extreme set follows the centres (static integer sorters): called after centers_version moved on, with the stream idle.
@@ -1274,7 +1320,7 @@ static bool known_range_off() {
 // hull(set(old) U new): a range behind the old rows extends the set, a range that overwrites old rows rebuilds it from every row.
 // The rows are read back from the device - one path for centres from the host, from an asset's decode and for never-written gaps.
 static int sorter_update_extreme(gs_sorter* s, uint32_t from, uint32_t end, uint32_t old_uploaded, bool zero_fill) {
-    if (s->flags != GS_SORT_INTEGER || known_range_off()) return GS_OK;
+    if (s->flags != GS_SORT_INTEGER || sort_switches().no_known_range) return GS_OK;
     const bool current = s->extreme_ok && s->extreme_version + 1u == s->centers_version;   // it covered the centres until now
     const bool append = from >= old_uploaded;
     if (append && !current) {                              // no set to extend: none until an overwrite rebuilds it
@@ -1302,13 +1348,6 @@ static int sorter_update_extreme(gs_sorter* s, uint32_t from, uint32_t end, uint
     return GS_OK;
 }
 
-// $GSPLAT_NO_COMPACT_CENTRES: no 16-bit centre planes are kept and the known-range front end reads the int32 planes (read once per
-// process)
-static bool compact_centres_off() {
-    static const bool off = getenv("GSPLAT_NO_COMPACT_CENTRES") != nullptr;
-    return off;
-}
-
 // The 16-bit centre planes follow the centres and their extreme set: called after sorter_update_extreme, with the stream idle and
 // the int32 planes of [from, end) written.  Valid only with a valid extreme set whose per-axis extent fits 16 bits
 // (gs_compact_offsets).  The same offsets as for the version before: only [from, end) is rebuilt - with the never-written gap in
@@ -1317,7 +1356,7 @@ static bool compact_centres_off() {
 static int sorter_update_compact(gs_sorter* s, uint32_t from, uint32_t end, uint32_t old_uploaded) {
     const bool was_current = s->c16_ok && s->c16_version + 1u == s->centers_version;
     s->c16_ok = false;
-    if (s->flags != GS_SORT_INTEGER || compact_centres_off() || s->uploaded == 0u) return GS_OK;
+    if (s->flags != GS_SORT_INTEGER || sort_switches().no_compact_centres || s->uploaded == 0u) return GS_OK;
     if (!s->extreme_ok || s->extreme_version != s->centers_version) return GS_OK;
     int32_t off[3];
     if (!gs_compact_offsets(s->extreme.data(), s->extreme.size() / 4, off)) return GS_OK;
@@ -1435,167 +1474,81 @@ static int sorter_collect_stats(gs_sorter* s, gs_sort_stats* stats) {
     stats->key_max = key_hi;
     stats->clamped = f.clamped;
     stats->passes = s->last_passes;
-    stats->result_count = s->last_culled ? f.kept : s->last_render;
+    stats->result_count = s->last_plan.count_on_device ? f.kept : s->last_render;
     return f.clamped ? GS_WARN_KEY_CLAMPED : GS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
-// One sort, in steps: sort_check -> sort_stage_inputs -> launch_front_end -> run_radix_passes -> sort_finish.
+// One sort, in steps: sort_check (the inputs of the plan, the refusals) -> plan_sort (sort_plan.cpp: everything that is decided) ->
+// sort_stage_inputs -> launch_front_end -> run_radix_passes -> sort_finish, which all act on the plan and change none of it.
 // ---------------------------------------------------------------------------------------------------
-// The switches of this file (A/B runs and tests), read here and nowhere else: once per process, at its first sort (the tests and
-// the soaks start a child process per setting).
-struct SortSwitches {
-    bool tree_no_fuse;         // $GSPLAT_TREE_NO_FUSE: a planned gather is copied by tree.hip, never by the key kernel
-    const char* vis_front;     // $GSPLAT_VIS_FRONT = stream | compact: forces one front end of the visibility cull
-    bool no_pack;              // $GSPLAT_NO_SORT_PACK: the unpacked radix passes
-    bool no_chunk;             // $GSPLAT_NO_SORT_CHUNK: the tile-at-a-time scatter for packed passes
-    bool no_known_range;       // $GSPLAT_NO_KNOWN_RANGE: never k_depth_key_hist (and no extreme set: sorter_update_extreme)
-    bool no_narrow_keys;       // $GSPLAT_NO_NARROW_KEYS: k_depth_key_hist stores the int32 depths whatever the precision
-    bool no_compact_centres;   // $GSPLAT_NO_COMPACT_CENTRES: k_depth_key_hist reads the int32 centre planes (and no 16-bit planes are
-                               // kept: sorter_update_compact)
-};
-static SortSwitches sort_switches() {
-    static const bool tree_no_fuse = getenv("GSPLAT_TREE_NO_FUSE") != nullptr;
-    static const char* vis_front = getenv("GSPLAT_VIS_FRONT");
-    static const bool no_pack = getenv("GSPLAT_NO_SORT_PACK") != nullptr;
-    static const bool no_chunk = getenv("GSPLAT_NO_SORT_CHUNK") != nullptr;
-    static const bool no_narrow_keys = getenv("GSPLAT_NO_NARROW_KEYS") != nullptr;
-    return {tree_no_fuse, vis_front, no_pack, no_chunk, known_range_off(), no_narrow_keys, compact_centres_off()};
-}
-
 static bool sorter_mesh_alive(const gs_context* ctx, const gs_mesh* m) {   // a sorter never dereferences a destroyed mesh
     for (const gs_mesh* l : ctx->live_meshes)
         if (l == m) return m != nullptr;
     return false;
 }
 
-// The cut of R > 0 positions for a streaming front end: a workgroup owns a contiguous run of whole units, at most two
-// workgroups per CU.
-struct ChunkGrid { uint32_t grid, len; };
-static ChunkGrid chunk_grid(const gs_context* ctx, uint32_t R, uint32_t unit) {
-    const uint32_t units = (R + unit - 1u) / unit;
-    const uint32_t grid = units < (uint32_t)ctx->cu_count * 2u ? units : (uint32_t)ctx->cu_count * 2u;
-    return {grid, ((units + grid - 1u) / grid) * unit};
-}
-
-struct SortPlan {
-    // the call
+// The call as it came in, and what of it sort_check worked out for the launch code
+struct SortCall {
     const float* mvp;
     const uint32_t* indexes_to_sort;
     bool device_list;                  // the list is what gs_tree_gather left (or planned) in idx_in
     const void* precomputed;
     const float* transforms;
     const uint32_t* list_count_dev;    // the list's real length lives on the device (asynchronous gs_tree_gather); R bounds it
-    // sort_check
-    uint32_t R, Rs, sort_start;        // render count, sort count (both clamped), R - Rs
-    bool pre_device, dynamic;
-    bool vis_cull;                     // compact by the bound mesh's visibility mask, then sort the survivors
-    bool cull;                         // the frustum cull's keep-mask path; the visibility cull compacts instead
+    uint32_t sort_count, render_count;
+    int32_t im[3];                     // the static integer key's coefficients: (int)(mvp[k]*1000.0), k = 2,6,10  (sorter.cpp:64)
     const uint32_t *map, *unmap;       // a bound mesh stores its splats in its own (Morton) order: hand it positions in that order
-    uint32_t last_splat;               // uploaded - 1: list entries are clamped to it
-    // The payload's range, not the list's: with a bound mesh a payload is perm[o], a position inside the mesh's slotted range,
-    // which reaches mesh.uploaded - 1 even when fewer centres have reached this sorter (gs_mesh_payload_map allows
-    // sorter.uploaded <= mesh.uploaded).  Sized from last_splat alone, the payload's top bits OR-ed into the key.
-    uint32_t max_payload, val_bits;
-    SortSwitches sw;
-    // sort_stage_inputs
-    const uint32_t* idx_dev;           // the index list on the device (nullptr: identity)
-    bool fused_tree;                   // the gathered list is still to be copied, and this sort does it itself
-    // launch_front_end
-    bool vec4;                         // identity list + static integer mode
-    bool vis_front;                    // the visibility cull's front end wrote keys and payloads of the survivors itself
-    bool known_range;                  // k_depth_key_hist keyed the list and left pass 0's histogram (sort_known_range)
-    int32_t range_lo, range_hi;        // ... with this exact key range
-    bool narrow;                       // ... and stored 16-bit radix keys (gs_sorter::keys16) instead of the depths
-    bool compact;                      // ... out of the 16-bit centre planes (gs_sorter::cx16 ..) instead of the int32 ones
-    uint32_t pass0_slot;               // pass 0's slot of group rows
 };
 
-// How pass 0 of the radix sort runs, for run_radix_passes and for the kernel that leaves its histogram ahead of it.
-struct Pass0Shape { bool pack, chunked; uint32_t grid; };
-static Pass0Shape pass0_shape(const gs_sorter* s, const SortPlan& pl) {
-    Pass0Shape sh;
-    // Packed passes stage a whole chunk in LDS (radix.hpp) when the list is short enough for <= CHUNK_TILES tiles per
-    // workgroup and the payload leaves 8 bits for the digit beside it in the last pass's staging word.
-    sh.chunked = !pl.sw.no_chunk && pl.val_bits <= 24u && radix_chunk_grid_for(pl.Rs) != 0u;
-    sh.pack = s->precision > 8u && !pl.sw.no_pack && (s->precision - 8u) + pl.val_bits <= 32u;
-    sh.grid = (sh.pack && sh.chunked) ? radix_chunk_grid_for(pl.Rs) : radix_grid_for(pl.Rs);
-    return sh;
-}
-
-// The exact key range of a sort, known before anything is launched: min / max of im . c over the extreme set.  Only the plain full
-// sort of every uploaded centre in static integer mode, and only when neither end leaves int32 - then no key wraps, every key is
-// its true value, and [lo, hi] is what the device-wide reduction would find.  Everything else keeps the key kernel + histogram path.
-static bool sort_known_range(const gs_sorter* s, const SortPlan& pl, const KeyParams& kp, int32_t& lo_out, int32_t& hi_out) {
-    if (pl.sw.no_known_range || kp.mode != MODE_INT || pl.idx_dev || pl.device_list || pl.fused_tree || pl.vis_cull || pl.cull ||
-        pl.list_count_dev || pl.sort_start != 0u || pl.R != s->uploaded || pl.R == 0u)
-        return false;
-    if (!s->extreme_ok || s->extreme_version != s->centers_version || s->extreme.empty()) return false;
-    const int32_t* c = s->extreme.data();
-    const size_t n = s->extreme.size() / 4;
-    const int64_t a0 = kp.im0, a1 = kp.im1, a2 = kp.im2;
-    const int64_t small = (int64_t)1 << 29;                // |im| <= 2^29: three products of at most 2^60 add up in int64
-    __int128 lo, hi;
-    if (a0 >= -small && a0 <= small && a1 >= -small && a1 <= small && a2 >= -small && a2 <= small) {
-        int64_t l = INT64_MAX, h = INT64_MIN;
-        for (size_t i = 0; i < n; i++) {
-            const int64_t v = a0 * c[4 * i] + a1 * c[4 * i + 1] + a2 * c[4 * i + 2];
-            l = v < l ? v : l;
-            h = v > h ? v : h;
-        }
-        lo = l; hi = h;
-    } else {
-        lo = hi = (__int128)a0 * c[0] + (__int128)a1 * c[1] + (__int128)a2 * c[2];
-        for (size_t i = 1; i < n; i++) {
-            const __int128 v = (__int128)a0 * c[4 * i] + (__int128)a1 * c[4 * i + 1] + (__int128)a2 * c[4 * i + 2];
-            lo = v < lo ? v : lo;
-            hi = v > hi ? v : hi;
-        }
-    }
-    if (lo < INT32_MIN || hi > INT32_MAX) return false;    // a key could wrap
-    lo_out = (int32_t)lo;
-    hi_out = (int32_t)hi;
-    return true;
-}
-
-// 1. argument checks and count clamps; what the flags and the bound mesh make of the call
-static int sort_check(gs_sorter* s, uint32_t sort_count, uint32_t render_count, SortPlan& pl) {
-    pl.pre_device = pl.precomputed == GS_PRECOMPUTED_DEVICE;
-    if (pl.pre_device) {
+// 1. the inputs of the plan, from the sorter, the call and the bound mesh - and the refusals, in the order and at the places they
+// have always had between the calls with side effects
+static int sort_check(gs_sorter* s, SortCall& c, SortPlanIn& in) {
+    in = SortPlanIn();
+    in.flags = s->flags; in.precision = s->precision; in.uploaded = s->uploaded;
+    in.frustum_cull = s->frustum_cull; in.visibility_cull = s->visibility_cull;
+    in.clean_slot = s->clean_slot;
+    in.pending_gather = s->pending_tree != nullptr; in.pending_keep_zeroed = s->pending_keep_zeroed;
+    in.extreme_current = s->extreme_ok && s->extreme_version == s->centers_version && !s->extreme.empty();
+    in.c16_current = s->c16_ok && s->c16_version == s->centers_version;
+    in.sort_count = c.sort_count; in.render_count = c.render_count;
+    in.list = c.device_list ? SORT_LIST_DEVICE : c.indexes_to_sort ? SORT_LIST_HOST : SORT_LIST_IDENTITY;
+    in.precomputed = !c.precomputed ? SORT_PRE_NONE : c.precomputed == GS_PRECOMPUTED_DEVICE ? SORT_PRE_DEVICE : SORT_PRE_HOST;
+    in.count_on_device = c.list_count_dev != nullptr;
+    in.cu_count = (uint32_t)s->ctx->cu_count;
+    in.sw = sort_switches();
+    if (in.precomputed == SORT_PRE_DEVICE) {
         GS_REQUIRE(s->dev_distances, "GS_PRECOMPUTED_DEVICE: no gs_mesh_compute_distances has handed distances to this sorter");
         GS_REQUIRE(s->dev_distances_count >= s->uploaded, "GS_PRECOMPUTED_DEVICE: fewer distances than the sorter's uploaded splats");
         GS_REQUIRE(s->dev_distances_integer == ((s->flags & GS_SORT_INTEGER) != 0),
                    "GS_PRECOMPUTED_DEVICE: the distances were computed for the other GS_SORT_INTEGER setting");
     }
-    // SortWorker.js:100-101 clamps both counts to the uploaded splat count
-    if (render_count > s->uploaded) render_count = s->uploaded;
-    if (sort_count > s->uploaded) sort_count = s->uploaded;
-    GS_REQUIRE(sort_count <= render_count, "splatSortCount > splatRenderCount");
-    pl.dynamic = (s->flags & GS_SORT_DYNAMIC) != 0;
-    GS_REQUIRE(!pl.dynamic || pl.transforms, "dynamic sorter needs transforms");
-    pl.vis_cull = s->visibility_cull && !pl.list_count_dev;   // (sorts the identity list: not combinable with a gathered one)
-    pl.cull = s->frustum_cull && !pl.vis_cull;
-    GS_REQUIRE(!pl.list_count_dev || (pl.device_list && sort_count == render_count && !pl.dynamic && !pl.precomputed),
+    const SortCounts n = sort_counts(in);
+    const bool dynamic = (s->flags & GS_SORT_DYNAMIC) != 0;
+    GS_REQUIRE(n.Rs <= n.R, "splatSortCount > splatRenderCount");
+    GS_REQUIRE(!dynamic || c.transforms, "dynamic sorter needs transforms");
+    GS_REQUIRE(!c.list_count_dev || (c.device_list && n.Rs == n.R && !dynamic && !c.precomputed),
                "a gathered list whose length lives on the device needs a full sort of a static scene without precomputed distances");
-    GS_REQUIRE(!(pl.cull || pl.vis_cull) || (sort_count == render_count && !pl.dynamic && !pl.precomputed),
+    GS_REQUIRE(!(n.cull || n.vis_cull) || (n.Rs == n.R && !dynamic && !c.precomputed),
                "a per-splat cull needs a full sort (splatSortCount == splatRenderCount) of a static scene without precomputed distances");
-    pl.R = render_count;
-    pl.Rs = sort_count;
-    pl.sort_start = render_count - sort_count;
     if (!sorter_mesh_alive(s->ctx, s->bound_mesh)) s->bound_mesh = nullptr;   // the mesh may have been destroyed since the bind
-    pl.map = s->bound_mesh ? gs_mesh_payload_map(s->bound_mesh, s->uploaded) : nullptr;
-    if (pl.vis_cull) {
-        GS_REQUIRE(s->bound_mesh && s->bound_mesh->projection_pending && s->bound_mesh->uploaded >= s->uploaded,
+    const gs_mesh* mesh = s->bound_mesh;
+    c.map = mesh ? gs_mesh_payload_map(s->bound_mesh, s->uploaded) : nullptr;
+    if (n.vis_cull) {
+        GS_REQUIRE(mesh && mesh->projection_pending && mesh->uploaded >= s->uploaded,
                    "the visibility cull needs gs_sorter_bind_mesh and a gs_mesh_project of this frame's camera before the sort");
-        GS_REQUIRE(!pl.indexes_to_sort && !pl.device_list, "the visibility cull sorts the identity list (pass indexes_to_sort = NULL)");
+        GS_REQUIRE(!c.indexes_to_sort && !c.device_list, "the visibility cull sorts the identity list (pass indexes_to_sort = NULL)");
+        // (projected_cam is the camera of the gs_mesh_project this sort consumes)
+        const gs_camera& pc = mesh->projected_cam;
+        const uint32_t rows_total = (pc.height + GS_TILE - 1u) / GS_TILE;
+        in.mesh_strip = !(pc.tile_row_begin == 0u && (pc.tile_row_end == 0u || pc.tile_row_end >= rows_total));
+        in.mesh_lazy_mask = mesh->vis_orig_lazy;
     }
-    pl.unmap = pl.map ? gs_mesh_payload_unmap(s->bound_mesh) : nullptr;
-    pl.last_splat = s->uploaded ? s->uploaded - 1u : 0u;
-    pl.max_payload = pl.last_splat;
-    if (pl.map && s->bound_mesh->uploaded && s->bound_mesh->uploaded - 1u > pl.max_payload) pl.max_payload = s->bound_mesh->uploaded - 1u;
-    pl.val_bits = 1;
-    while (pl.val_bits < 32u && (pl.max_payload >> pl.val_bits)) pl.val_bits++;
-    pl.sw = sort_switches();
+    c.unmap = c.map ? gs_mesh_payload_unmap(s->bound_mesh) : nullptr;
+    in.mesh_map = c.map != nullptr;
+    in.mesh_uploaded = mesh ? mesh->uploaded : 0u;
+    for (int k = 0; k < 3; k++) c.im[k] = trunc_f64_i32((double)c.mvp[2 + 4 * k] * 1000.0);
+    if (sort_wants_key_range(in)) in.range_ok = gs_key_range(s->extreme.data(), s->extreme.size() / 4, c.im, &in.range_lo, &in.range_hi);
     return GS_OK;
 }
 
@@ -1620,10 +1573,11 @@ static int store_scene_rows(gs_sorter* s, const float* mvp, const float* transfo
 }
 
 // 2. stream ordering and input staging: what the sort waits for, the index list, the distances, the scene rows, KeyParams
-static int sort_stage_inputs(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
+static int sort_stage_inputs(gs_sorter* s, const SortCall& c, const SortPlan& pl, KeyParams& kp) {
     gs_context* ctx = s->ctx;
     hipStream_t st = s->stream;
-    const float* mvp = pl.mvp;
+    const float* mvp = c.mvp;
+    const bool dynamic = (s->flags & GS_SORT_DYNAMIC) != 0;
     if (pl.vis_cull && s->bound_mesh->ev_p1 && ctx->aux != st) GS_HIP(hipStreamWaitEvent(st, s->bound_mesh->ev_p1, 0));   // the mask it reads
     if (ctx->fork_join && st != ctx->stream) {
         // serial frames on a multi-stream context: this sort starts when everything the context's stream holds now (the previous
@@ -1636,15 +1590,11 @@ static int sort_stage_inputs(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
         s->consumer_pending = false;
     }
 
-    if (pl.device_list) {
-        pl.idx_dev = s->idx_in.as<uint32_t>();             // written by gs_tree_gather on this stream ...
-        if (s->pending_tree) {                             // ... or only planned by it (tree.hip): the copy is ours
-            pl.fused_tree = !pl.sw.tree_no_fuse && pl.Rs == pl.R && pl.Rs > 0 && !pl.dynamic && !pl.precomputed && !pl.vis_cull &&
-                            (!pl.cull || s->pending_keep_zeroed);
-            if (!pl.fused_tree) {
-                GS_TRY(gs_tree_copy_plain(s->pending_tree, s->idx_in.as<uint32_t>(), st));
-                gs_tree_forget_sorter(s->pending_tree, s);
-            }
+    if (c.device_list) {
+        kp.idx_in = s->idx_in.as<uint32_t>();              // written by gs_tree_gather on this stream ...
+        if (pl.gather == SORT_GATHER_PLAIN) {              // ... or only planned by it (tree.hip): the copy is ours, here or fused
+            GS_TRY(gs_tree_copy_plain(s->pending_tree, s->idx_in.as<uint32_t>(), st));
+            gs_tree_forget_sorter(s->pending_tree, s);
         }
     } else {
         // A sort that does not consume the gathered list may destroy what a gather left for a later gs_sorter_sort_gathered
@@ -1654,32 +1604,31 @@ static int sort_stage_inputs(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
         // the front end of a visibility-culled sort is chosen - ADVICE r05: the streaming one writes pay_in and leaves idx_in alone).
         if (s->pending_tree) {
             if (pl.cull) s->pending_keep_zeroed = false;
-        } else if (pl.indexes_to_sort) {
+        } else if (c.indexes_to_sort) {
             s->has_gathered = false;
         }
-        if (pl.indexes_to_sort) {
+        if (c.indexes_to_sort) {
             GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
-            if (pl.R) GS_HIP(hipMemcpyAsync(s->idx_in.p, pl.indexes_to_sort, (size_t)pl.R * 4, hipMemcpyHostToDevice, st));
-            pl.idx_dev = s->idx_in.as<uint32_t>();
+            if (pl.R) GS_HIP(hipMemcpyAsync(s->idx_in.p, c.indexes_to_sort, (size_t)pl.R * 4, hipMemcpyHostToDevice, st));
+            kp.idx_in = s->idx_in.as<uint32_t>();
         }
     }
-    kp.mode = ((s->flags & GS_SORT_INTEGER) ? MODE_INT : 0) | (pl.dynamic ? MODE_DYNAMIC : 0) | (pl.precomputed ? MODE_PRECOMPUTED : 0);
-    if (pl.precomputed) {
+    kp.mode = ((s->flags & GS_SORT_INTEGER) ? MODE_INT : 0) | (dynamic ? MODE_DYNAMIC : 0) | (c.precomputed ? MODE_PRECOMPUTED : 0);
+    if (c.precomputed) {
         GS_TRY(s->precomputed.ensure((size_t)s->max_count * 4));
-        if (!pl.pre_device) {                  // (the device hand-over: gs_mesh_compute_distances wrote the buffer in place)
-            GS_HIP(hipMemcpyAsync(s->precomputed.p, pl.precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
+        if (c.precomputed != GS_PRECOMPUTED_DEVICE) {   // (the device hand-over: gs_mesh_compute_distances wrote the buffer in place)
+            GS_HIP(hipMemcpyAsync(s->precomputed.p, c.precomputed, (size_t)s->uploaded * 4, hipMemcpyHostToDevice, st));
             s->dev_distances = false;
         }
         kp.precomputed = s->precomputed.as<uint32_t>();
     }
-    if (pl.dynamic && !pl.precomputed) {
-        GS_TRY(store_scene_rows(s, mvp, pl.transforms));
+    if (dynamic && !c.precomputed) {
+        GS_TRY(store_scene_rows(s, mvp, c.transforms));
         kp.rows = s->scene_rows.as<SceneRows>();
     }
     kp.cx = s->cx.as<uint32_t>(); kp.cy = s->cy.as<uint32_t>(); kp.cz = s->cz.as<uint32_t>();
     kp.cw = s->cw.as<uint32_t>(); kp.scene_idx = s->scene_idx.as<uint32_t>();
     kp.aos = s->caos.as<uint4>();
-    kp.idx_in = pl.idx_dev;
     kp.keys_out = s->keys.as<int32_t>();
     if (pl.Rs > 0) s->frame_index ^= 1u;       // this sort's frame was reset by the previous sort's first kernel (or at create)
     kp.frame = s->frame.as<SortFrame>() + s->frame_index;
@@ -1688,27 +1637,25 @@ static int sort_stage_inputs(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
     kp.sort_start = pl.sort_start;
     kp.render_count = pl.R;
     kp.last_splat = pl.last_splat;
-    kp.im0 = trunc_f64_i32((double)mvp[2] * 1000.0);     // sorter.cpp:64
-    kp.im1 = trunc_f64_i32((double)mvp[6] * 1000.0);
-    kp.im2 = trunc_f64_i32((double)mvp[10] * 1000.0);
+    kp.im0 = c.im[0]; kp.im1 = c.im[1]; kp.im2 = c.im[2];
     kp.fm0 = mvp[2]; kp.fm1 = mvp[6]; kp.fm2 = mvp[10];
     if (pl.cull) {
         GS_TRY(s->keep_mask.ensure((((size_t)s->max_count + 63) / 64 + 8) * 8));   // the key kernel writes whole 256-position windows
         kp.keep = s->keep_mask.as<unsigned long long>();
         memcpy(kp.mvp, mvp, sizeof(kp.mvp));
     }
-    kp.count_dev = pl.list_count_dev;
+    kp.count_dev = c.list_count_dev;
     return GS_OK;
 }
 
 // 3a. copy + keys (+ keep bits) of a planned gather in one kernel over leaf-major copies of the centres and payloads
-static int launch_tree_front(gs_sorter* s, const SortPlan& pl, const KeyParams& kp) {
+static int launch_tree_front(gs_sorter* s, const SortCall& c, const SortPlan& pl, const KeyParams& kp) {
     gs_context* ctx = s->ctx;
     hipStream_t st = s->stream;
     TreeCopyParams cp;
     gs_tree_view(s->pending_tree, &cp.v);
-    const void* mesh_key = pl.map ? (const void*)s->bound_mesh : nullptr;
-    const uint32_t layout = pl.map ? s->bound_mesh->layout_version : 0u;
+    const void* mesh_key = c.map ? (const void*)s->bound_mesh : nullptr;
+    const uint32_t layout = c.map ? s->bound_mesh->layout_version : 0u;
     GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
     if (s->leaf_cache_tree != cp.v.tree_uid || s->leaf_cache_centers != s->centers_version || s->leaf_cache_mesh != mesh_key ||
         s->leaf_cache_layout != layout || s->leaf_cache_uploaded != s->uploaded || !s->leaf_centers.p) {
@@ -1716,7 +1663,7 @@ static int launch_tree_front(gs_sorter* s, const SortPlan& pl, const KeyParams& 
         GS_TRY(s->leaf_pos.ensure((size_t)cp.v.tree_splats * 4 + 16));
         if (cp.v.tree_splats)
             hipLaunchKernelGGL(k_tree_leaf_cache, dim3(grid_for(cp.v.tree_splats, 1024, 4096)), dim3(256), 0, st, cp.v.leaf_indexes,
-                               cp.v.tree_splats, s->caos.as<uint4>(), pl.map, kp.last_splat, s->leaf_centers.as<uint4>(),
+                               cp.v.tree_splats, s->caos.as<uint4>(), c.map, kp.last_splat, s->leaf_centers.as<uint4>(),
                                s->leaf_pos.as<uint32_t>());
         s->leaf_cache_tree = cp.v.tree_uid; s->leaf_cache_centers = s->centers_version; s->leaf_cache_mesh = mesh_key;
         s->leaf_cache_layout = layout; s->leaf_cache_uploaded = s->uploaded;
@@ -1728,7 +1675,7 @@ static int launch_tree_front(gs_sorter* s, const SortPlan& pl, const KeyParams& 
     // (a workgroup ends with one atomic on the sort's kept counter, and same-address atomics retire at ~12 ns each:
     // 6.5 k workgroups queue ~80 us of them behind 30 us of memory traffic - eight workgroups per CU walk the leaves)
     const uint32_t cgrid = grid_for(cp.v.leaves, 4, (uint32_t)ctx->cu_count * 8u);
-    if (pl.cull) hipLaunchKernelGGL(k_tree_copy_keys<true>, dim3(cgrid), dim3(256), 0, st, cp, kp);
+    if (pl.front == SORT_FRONT_TREE_CULL) hipLaunchKernelGGL(k_tree_copy_keys<true>, dim3(cgrid), dim3(256), 0, st, cp, kp);
     else hipLaunchKernelGGL(k_tree_copy_keys<false>, dim3(cgrid), dim3(256), 0, st, cp, kp);
     gs_tree_forget_sorter(s->pending_tree, s);
     return GS_OK;
@@ -1736,228 +1683,140 @@ static int launch_tree_front(gs_sorter* s, const SortPlan& pl, const KeyParams& 
 
 // 3b. the visibility cull: compact, then sort the survivors (see k_minmax_count) - the list is what the bound mesh's vertex
 // stage kept.  Leaves the list's length on the device (kp.count_dev) and min / max in the frame (kp.ext_minmax).
-static int launch_vis_cull_front(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
-    gs_context* ctx = s->ctx;
+static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan& pl, KeyParams& kp) {
     hipStream_t st = s->stream;
     gs_mesh* mesh = s->bound_mesh;
     const uint32_t R = pl.R;
+    const bool stream = pl.front == SORT_FRONT_VIS_STREAM, lazy = pl.vis_derive != 0u;
     GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
     GS_TRY(s->mask_copy.ensure(((size_t)s->max_count + 31) / 32 * 4 + 64));
     uint32_t* mask = mesh->vis_orig.as<uint32_t>();
-    uint32_t* counts = nullptr;                            // (set once chunk_counts has its size)
     // The projection left the by-original-index mask to us (gs_mesh_project of a full frame for a mesh whose bound sorter
     // culls by visibility): k_mask_derive_count builds it from the storage-order mask through the payload map.
-    const bool lazy = mesh->vis_orig_lazy;
-    GS_REQUIRE(!lazy || pl.map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
-    constexpr uint32_t DERIVE_SUBS = 4;
-    // (a chunk of the derived mask is a whole number of DERIVE_SUBS x turns: one piece per sub-workgroup)
-    const ChunkGrid dg = chunk_grid(ctx, R, VC_TURN * DERIVE_SUBS);
-    auto derive = [&]() {
-        hipLaunchKernelGGL(k_mask_derive_count, dim3(dg.grid * DERIVE_SUBS), dim3(VC_THREADS), 0, st, kp, pl.map,
-                           mesh->vis_mask.as<unsigned long long>(), mesh->block_any.as<uint8_t>(), (mesh->uploaded + 255u) >> 8, dg.len,
-                           DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), counts);
-    };
-    // Two front ends, chosen by what the vertex stage drew.  A full frame keeps a large part of the scene (C3: a quarter):
-    // the streaming front end keys the survivors on the way (N = 1 frame 0.285 -> 0.270 ms, r05k).  A rank's strip keeps
-    // a few per cent: round 4's chain - a 12-byte-per-splat min / max pass, a compaction of the mask, and centre gathers
-    // for the few survivors - is the cheaper one there (C3 rank 4 of 8: 0.116 vs 0.126 ms, same box), because the streaming
-    // kernel also reads the payload table (+4 bytes per splat) and runs at 2.8 TB/s where the pure reduction reaches 4.
-    // $GSPLAT_VIS_FRONT = stream | compact forces one (A/B and tests).
-    // (projected_cam is the camera of the gs_mesh_project this sort consumes: the entry checks refused the call unless
-    // the bound mesh's projection_pending is set)
-    const gs_camera& pc = mesh->projected_cam;
-    const uint32_t rows_total = (pc.height + GS_TILE - 1u) / GS_TILE;
-    const bool strip = !(pc.tile_row_begin == 0u && (pc.tile_row_end == 0u || pc.tile_row_end >= rows_total));
-    pl.vis_front = pl.sw.vis_front ? pl.sw.vis_front[0] == 's' : !strip;
-    if (pl.vis_front) {
-        // one contiguous run of positions per workgroup, walked in turns of 4096 (two workgroups per CU)
-        const ChunkGrid wg = lazy ? dg : chunk_grid(ctx, R, VC_TURN);
-        GS_TRY(s->chunk_counts.ensure((size_t)wg.grid * DERIVE_SUBS * 4));
-        GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
-        counts = s->chunk_counts.as<uint32_t>();
-        if (lazy) derive();
-        else hipLaunchKernelGGL(k_mask_count, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, wg.len, counts);
-        if (pl.map) hipLaunchKernelGGL(k_cull_front<true>, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                       counts, wg.len, pl.map, s->pay_in.as<uint32_t>(), lazy ? DERIVE_SUBS : 1u);
-        else hipLaunchKernelGGL(k_cull_front<false>, dim3(wg.grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                counts, wg.len, pl.map, s->pay_in.as<uint32_t>(), 1u);
+    GS_REQUIRE(!lazy || c.map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
+    if (!stream && !s->pending_tree) s->has_gathered = false;   // k_mask_compact overwrites a gathered list that was already copied into idx_in
+    GS_TRY(s->chunk_counts.ensure((size_t)pl.counts_words * 4));
+    if (stream) GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
+    uint32_t* counts = s->chunk_counts.as<uint32_t>();
+    // (a forced compact front end derives the mask first as well: its counts are redone by k_minmax_count)
+    if (lazy) hipLaunchKernelGGL(k_mask_derive_count, dim3(pl.derive_grid * VC_DERIVE_SUBS), dim3(VC_THREADS), 0, st, kp, c.map,
+                                 mesh->vis_mask.as<unsigned long long>(), mesh->block_any.as<uint8_t>(), (mesh->uploaded + 255u) >> 8,
+                                 pl.derive_len, VC_DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), counts);
+    if (stream) {
+        if (!lazy) hipLaunchKernelGGL(k_mask_count, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, pl.front_len, counts);
+        if (c.map) hipLaunchKernelGGL(k_cull_front<true>, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
+                                      counts, pl.front_len, c.map, s->pay_in.as<uint32_t>(), lazy ? VC_DERIVE_SUBS : 1u);
+        else hipLaunchKernelGGL(k_cull_front<false>, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
+                                counts, pl.front_len, c.map, s->pay_in.as<uint32_t>(), 1u);
     } else {
-        const ChunkGrid cg = chunk_grid(ctx, R, VC_SPAN);
-        if (!s->pending_tree) s->has_gathered = false;     // k_mask_compact overwrites a gathered list that was already copied into idx_in
-        GS_TRY(s->chunk_counts.ensure((size_t)std::max(lazy ? dg.grid * DERIVE_SUBS : 0u, cg.grid) * 4));
-        counts = s->chunk_counts.as<uint32_t>();
-        if (lazy) derive();                                // (a forced compact front end: the mask first, its counts are redone below)
-        hipLaunchKernelGGL(k_minmax_count, dim3(cg.grid), dim3(VC_THREADS), 0, st, kp, mask, cg.len, counts);
-        hipLaunchKernelGGL(k_mask_compact, dim3(cg.grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(), counts, R, cg.len,
-                           s->idx_in.as<uint32_t>(), kp.frame);
+        hipLaunchKernelGGL(k_minmax_count, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, pl.front_len, counts);
+        hipLaunchKernelGGL(k_mask_compact, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(), counts, R,
+                           pl.front_len, s->idx_in.as<uint32_t>(), kp.frame);
     }
     // the mask is all zero again if this sort covered every splat the vertex stage looked at - and, where it derived the
     // mask itself, if the words beyond the ones it wrote were zero already (gs_mesh_project)
     if (R >= mesh->vis_orig_count && (!lazy || mesh->vis_orig_tail_zero)) mesh->vis_orig_dirty = false;
-    pl.idx_dev = s->idx_in.as<uint32_t>();
-    kp.idx_in = pl.idx_dev;
+    kp.idx_in = s->idx_in.as<uint32_t>();
     kp.count_dev = &kp.frame->kept;
     kp.ext_minmax = 1u;
-    if (!pl.vis_front) hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(pl.Rs, 256 * 4, (uint32_t)ctx->cu_count * 2)), dim3(256), 0, st, kp);
+    if (!stream) hipLaunchKernelGGL(k_depth_key<false>, dim3(pl.key_grid), dim3(256), 0, st, kp);
     return GS_OK;
 }
 
-// 3. the first kernel(s) of the sort: keys, min / max, the housekeeping (sort_begin) - one branch per kernel family
-static int launch_front_end(gs_sorter* s, SortPlan& pl, KeyParams& kp) {
-    gs_context* ctx = s->ctx;
+// 3. the first kernel(s) of the sort: keys, min / max, the housekeeping (sort_begin) - one case per kernel family
+static int launch_front_end(gs_sorter* s, const SortCall& c, const SortPlan& pl, KeyParams& kp) {
     hipStream_t st = s->stream;
-    const uint32_t cus = (uint32_t)ctx->cu_count;
-    pl.vec4 = (kp.mode == MODE_INT) && !pl.idx_dev;
-    pl.known_range = sort_known_range(s, pl, kp, pl.range_lo, pl.range_hi);
-    pl.pass0_slot = pl.known_range ? s->clean_slot : 0u;
-    // every other front end zeroes all four slots and the passes use slots 0 .. 2; the known-range kernel zeroes all but its own
-    s->clean_slot = pl.pass0_slot == 3u ? 0u : 3u;
-    // a radix key of <= 16 bits travels as 16 bits (the same lo and hi decide the buckets, whichever kernel applies them)
-    pl.narrow = pl.known_range && s->precision <= 16u && !pl.sw.no_narrow_keys;
-    // ... and then its centres come from the 16-bit offset planes, where they hold the centres as they are now
-    pl.compact = pl.narrow && !pl.sw.no_compact_centres && s->c16_ok && s->c16_version == s->centers_version;
-    if (pl.known_range) {
+    const dim3 grid(pl.front_grid);
+    switch (pl.front) {
+    case SORT_FRONT_KNOWN_WIDE: case SORT_FRONT_KNOWN_NARROW: case SORT_FRONT_KNOWN_COMPACT: {
         DepthLoaderArgs hl = {};
         hl.keys = s->keys.as<int32_t>(); hl.frame = kp.frame; hl.sort_start = 0u; hl.render_count = pl.R; hl.range = 1u << s->precision;
         hl.last_splat = kp.last_splat; hl.count_clamps = 1u;
-        const dim3 grid(pass0_shape(s, pl).grid);
+        const dim3 hgrid(pl.pass[0].grid);                 // the kernel writes pass 0's histogram rows: one per workgroup of THAT grid
         uint32_t* group_rows = s->radix.digit_total.as<uint32_t>() + pl.pass0_slot * RADIX_SLOT_WORDS;
+        uint32_t* bh = s->radix.block_hist.as<uint32_t>();
         CompactCentres cc = {};
-        if (pl.compact) {
+        if (pl.front == SORT_FRONT_KNOWN_COMPACT) {
             cc.x = s->cx16.as<uint16_t>(); cc.y = s->cy16.as<uint16_t>(); cc.z = s->cz16.as<uint16_t>();
             cc.k0 = (uint32_t)s->c16_off[0] * (uint32_t)kp.im0 + (uint32_t)s->c16_off[1] * (uint32_t)kp.im1 +
                     (uint32_t)s->c16_off[2] * (uint32_t)kp.im2;         // static_key_int of the offset: uint32 wrap-around
-            hipLaunchKernelGGL((k_depth_key_hist<true, true>), grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi,
-                               0, pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>(), cc);
-        } else if (pl.narrow) {
-            hipLaunchKernelGGL(k_depth_key_hist<true>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
-                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, s->keys16.as<uint16_t>(), cc);
+            hipLaunchKernelGGL((k_depth_key_hist<true, true>), hgrid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi,
+                               0, pl.pass0_slot, bh, group_rows, s->keys16.as<uint16_t>(), cc);
+        } else if (pl.front == SORT_FRONT_KNOWN_NARROW) {
+            hipLaunchKernelGGL(k_depth_key_hist<true>, hgrid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
+                               pl.pass0_slot, bh, group_rows, s->keys16.as<uint16_t>(), cc);
         } else {
-            hipLaunchKernelGGL(k_depth_key_hist<false>, grid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
-                               pl.pass0_slot, s->radix.block_hist.as<uint32_t>(), group_rows, (uint16_t*)nullptr, cc);
+            hipLaunchKernelGGL(k_depth_key_hist<false>, hgrid, dim3(HIST_THREADS), 0, st, kp, DepthLoader{hl}, pl.range_lo, pl.range_hi, 0,
+                               pl.pass0_slot, bh, group_rows, (uint16_t*)nullptr, cc);
         }
-    } else if (pl.fused_tree) {
-        GS_TRY(launch_tree_front(s, pl, kp));
-    } else if (pl.vis_cull) {
-        GS_TRY(launch_vis_cull_front(s, pl, kp));
-    } else if (pl.cull) {
-        if (pl.vec4) hipLaunchKernelGGL(k_depth_key_cull<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * 2)), dim3(256), 0, st, kp);
-        else hipLaunchKernelGGL(k_depth_key_cull<false>, dim3(grid_for(pl.Rs, 256 * 4, cus * 4)), dim3(256), 0, st, kp);
-    } else if (pl.vec4) {
-        hipLaunchKernelGGL(k_depth_key<true>, dim3(grid_for(pl.Rs, 256 * 16, cus * GS_KEY_GRID_MULT)), dim3(256), 0, st, kp);
-    } else {
-        hipLaunchKernelGGL(k_depth_key<false>, dim3(grid_for(pl.Rs, 256 * 4, cus * 2)), dim3(256), 0, st, kp);
+        break;
+    }
+    case SORT_FRONT_TREE: case SORT_FRONT_TREE_CULL: GS_TRY(launch_tree_front(s, c, pl, kp)); break;
+    case SORT_FRONT_VIS_STREAM: case SORT_FRONT_VIS_COMPACT: GS_TRY(launch_vis_cull_front(s, c, pl, kp)); break;
+    case SORT_FRONT_CULL_VEC4: hipLaunchKernelGGL(k_depth_key_cull<true>, grid, dim3(256), 0, st, kp); break;
+    case SORT_FRONT_CULL_IDX: hipLaunchKernelGGL(k_depth_key_cull<false>, grid, dim3(256), 0, st, kp); break;
+    case SORT_FRONT_KEY_VEC4: hipLaunchKernelGGL(k_depth_key<true>, grid, dim3(256), 0, st, kp); break;
+    case SORT_FRONT_KEY_IDX: hipLaunchKernelGGL(k_depth_key<false>, grid, dim3(256), 0, st, kp); break;
+    default: GS_REQUIRE(false, "sort plan: unknown front end");
     }
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
 
-// 4. the radix passes over key' = range - 1 - bucket of the reversed list: pass 0 reads the keys through a DepthLoader
-static int run_radix_passes(gs_sorter* s, const SortPlan& pl, const KeyParams& kp) {
+// 4. the radix passes the plan lists
+static int run_radix_passes(gs_sorter* s, const SortCall& c, const SortPlan& pl, const KeyParams& kp) {
     const RadixExec ex = {s->stream, &s->radix, s->ctx->lds_atomic_lane_order};
-    const uint32_t Rs = pl.Rs, val_bits = pl.val_bits;
-    const bool own_payloads = pl.fused_tree || pl.vis_front;    // the fused copy / the cull's front end wrote the payloads themselves
-    DepthLoaderArgs dl = {};
-    dl.keys = s->keys.as<int32_t>();
-    dl.keys16 = s->keys16.as<uint16_t>();
-    dl.keep = pl.cull ? kp.keep : nullptr;
-    dl.idx = own_payloads ? s->pay_in.as<uint32_t>() : pl.idx_dev;
-    dl.map = own_payloads ? nullptr : pl.map;
-    dl.frame = kp.frame;
-    dl.sort_start = pl.sort_start;
-    dl.render_count = pl.R;
-    dl.range = 1u << s->precision;
+    PassBuffers b = {};
+    b.dl.keys = s->keys.as<int32_t>();
+    b.dl.keys16 = s->keys16.as<uint16_t>();
+    b.dl.keep = pl.cull ? kp.keep : nullptr;
+    b.dl.idx = pl.own_payloads ? s->pay_in.as<uint32_t>() : kp.idx_in;
+    b.dl.map = pl.own_payloads ? nullptr : c.map;
+    b.dl.frame = kp.frame;
+    b.dl.sort_start = pl.sort_start;
+    b.dl.render_count = pl.R;
+    b.dl.range = 1u << s->precision;
     // (the loader clamps what it reads from `idx`: splat indexes normally, ready-made payloads after a fused copy / front end)
-    dl.last_splat = own_payloads ? pl.max_payload : kp.last_splat;
-    dl.n_dev = pl.vis_cull ? &kp.frame->kept : pl.list_count_dev;
-    const uint32_t passes = (s->precision + 7) / 8;
-    uint32_t* out_tail = s->sorted.as<uint32_t>() + pl.sort_start;
-    void* kbuf[2] = {s->keyA.p, s->keyB.p};
-    uint32_t* vbuf[2] = {s->valA.as<uint32_t>(), s->valB.as<uint32_t>()};
-    // What travels between the passes: after pass p the key still holds precision - 8 (p + 1) bits.  When those fit above the
-    // payload in one 32-bit word (payloads are splat positions < uploaded: 23 bits at 5.8 M splats, 24 at 16 M, so the default
-    // 16-bit buckets always do below 2^24 splats) the pass writes that word instead of a key array and a value array
-    // (radix.hpp PACK_OUT); otherwise 16- or 32-bit keys + values as before, and a later pass packs as soon as it can.
-    const bool chunked = pass0_shape(s, pl).chunked;
-    const bool wide = s->precision > 16;
-    // after a culling pass 0 the element count is the device-resident kept count
-    const uint32_t* n_dev = (pl.cull || pl.vis_cull || pl.list_count_dev) ? &kp.frame->kept : nullptr;
-    bool in_packed = false;                                                       // the previous pass packed
-    for (uint32_t p = 0; p < passes; p++) {
-        const bool last = (p + 1 == passes);
-        const int left = (int)s->precision - 8 * (int)(p + 1);                    // key bits after this pass
-        const bool pack = !last && !pl.sw.no_pack && (uint32_t)left + val_bits <= 32u;
-        const int shift = in_packed ? 0 : 8 * (int)p;
-        uint32_t* vo = last ? out_tail : vbuf[p & 1];
-        if (p == 0) {
-            Pass0Args a = {};
-            a.ld = dl; a.Rs = Rs; a.val_bits = val_bits; a.shift = shift;
-            a.pack = pack; a.chunked = chunked; a.wide = wide; a.kbuf0 = kbuf[0]; a.vo = vo;
-            a.kept_out = pl.cull ? &kp.frame->kept : nullptr;      // a culling pass 0 compacts: it publishes the result's length
-            a.slot = (int)pl.pass0_slot;
-            a.skip_hist = pl.known_range;
-            const bool has_idx = dl.idx != nullptr;
-            if (pl.narrow) GS_TRY((depth_pass0<false, false, true>(ex, a)));      // (a known-range sort: the identity list, no cull)
-            else if (pl.cull && has_idx) GS_TRY((depth_pass0<true, true>(ex, a)));
-            else if (pl.cull) GS_TRY((depth_pass0<true, false>(ex, a)));
-            else if (has_idx) GS_TRY((depth_pass0<false, true>(ex, a)));
-            else GS_TRY((depth_pass0<false, false>(ex, a)));
-        } else if (in_packed) {
-            PackedLoader pk = {vbuf[(p - 1) & 1], n_dev, Rs, val_bits};
-            ArrayLoader<uint32_t> ph = {vbuf[(p - 1) & 1], nullptr, n_dev, Rs};
-            if (chunked && last) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, false>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, vo, 0u)));
-            else if (chunked) GS_TRY((radix_pass_chunk<ArrayLoader<uint32_t>, PackedLoader, true>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, vo, val_bits)));
-            else if (last) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, false>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, 0u)));
-            else GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, PackedLoader, uint8_t, false, false, true>(ex, ph, (int)val_bits, pk, Rs, 0, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
-        } else if (wide) {
-            ArrayLoader<uint32_t> al = {(const uint32_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
-            if (last) GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, false>(ex, al, al, Rs, shift, (int)p, (uint32_t*)nullptr, vo)));
-            else if (pack) GS_TRY((radix_pass_ex<ArrayLoader<uint32_t>, ArrayLoader<uint32_t>, uint8_t, false, false, true>(ex, al, shift, al, Rs, shift, (int)p, (uint8_t*)nullptr, vo, nullptr, 0u, val_bits)));
-            else GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, true>(ex, al, al, Rs, shift, (int)p, (uint32_t*)kbuf[p & 1], vo)));
-        } else {
-            ArrayLoader<uint16_t> al = {(const uint16_t*)kbuf[(p - 1) & 1], vbuf[(p - 1) & 1], n_dev, Rs};
-            if (last) GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, false>(ex, al, al, Rs, shift, (int)p, (uint16_t*)nullptr, vo)));
-            else GS_TRY((radix_pass<ArrayLoader<uint16_t>, uint16_t, true>(ex, al, al, Rs, shift, (int)p, (uint16_t*)kbuf[p & 1], vo)));
-        }
-        in_packed = in_packed || pack;
-    }
+    b.dl.last_splat = pl.own_payloads ? pl.max_payload : kp.last_splat;
+    b.dl.n_dev = pl.pass0_count == SORT_COUNT_KEPT ? &kp.frame->kept : pl.pass0_count == SORT_COUNT_LIST ? c.list_count_dev : nullptr;
+    b.n_dev = pl.count_on_device ? &kp.frame->kept : nullptr;
+    b.Rs = pl.Rs; b.val_bits = pl.val_bits;
+    b.kbuf[0] = s->keyA.p; b.kbuf[1] = s->keyB.p;
+    b.vbuf[0] = s->valA.as<uint32_t>(); b.vbuf[1] = s->valB.as<uint32_t>();
+    b.out_tail = s->sorted.as<uint32_t>() + pl.sort_start;
+    b.kept_out = pl.pass0_publishes ? &kp.frame->kept : nullptr;
+    for (uint32_t p = 0; p < pl.passes; p++) GS_TRY(launch_pass(ex, pl.pass[p], p, b));
     return GS_OK;
 }
 
 // 5. the unsorted head, the result's bookkeeping, the optional host copy and statistics
-static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, uint32_t passes, uint32_t* sorted_out, gs_sort_stats* stats) {
+static int sort_finish(gs_sorter* s, const SortCall& c, const SortPlanIn& in, const SortPlan& pl, const KeyParams& kp, uint32_t* sorted_out,
+                       gs_sort_stats* stats) {
     hipStream_t st = s->stream;
     if (pl.sort_start > 0) {
-        hipLaunchKernelGGL(k_copy_head, dim3(grid_for(pl.sort_start, 1024, 2048)), dim3(256), 0, st, pl.idx_dev, pl.map,
+        hipLaunchKernelGGL(k_copy_head, dim3(grid_for(pl.sort_start, 1024, 2048)), dim3(256), 0, st, kp.idx_in, c.map,
                            s->sorted.as<uint32_t>(), pl.sort_start, s->uploaded - 1u);
     }
     GS_HIP(hipGetLastError());
     if (s->timed_sort || st != s->ctx->stream) GS_HIP(hipEventRecord(s->ev1, st));   // a draw on another stream waits for it
     s->last_render = pl.R;
     s->last_sort = pl.Rs;
-    s->last_passes = passes;
-    s->last_known_range = pl.known_range;
-    s->last_range_lo = pl.known_range ? pl.range_lo : 0;
-    s->last_range_hi = pl.known_range ? pl.range_hi : 0;
-    s->last_pass0_slot = pl.pass0_slot;
-    s->last_narrow = pl.narrow;
-    s->last_compact = pl.compact;
+    s->last_passes = pl.passes;
+    s->last_in = in;                           // what gs_sorter_debug_read (4, 5), the statistics and the draw read of this sort
+    s->last_plan = pl;
     if (pl.Rs > 0) {                           // (a front end ran: `keys` holds this sort's depths, or it is stale from now on)
-        s->keys_stale = pl.narrow;
+        s->keys_stale = pl.front == SORT_FRONT_KNOWN_NARROW || pl.front == SORT_FRONT_KNOWN_COMPACT;
         s->stale_im[0] = kp.im0; s->stale_im[1] = kp.im1; s->stale_im[2] = kp.im2;
         s->stale_count = pl.R;
     }
-    s->last_identity = (pl.idx_dev == nullptr);
-    s->last_culled = (pl.cull || pl.vis_cull || pl.list_count_dev) && pl.Rs > 0;   // the result's length lives in result_frame->kept
-    s->last_vis_culled = pl.vis_cull && pl.Rs > 0;
     s->result_frame = kp.frame;
-    s->result_mesh = pl.map ? s->bound_mesh : nullptr;
-    s->result_unmap = pl.unmap;
+    s->result_mesh = c.map ? s->bound_mesh : nullptr;
+    s->result_unmap = c.unmap;
     s->result_payload_max = pl.max_payload;    // (the clamp of the host-visible un-mapping: payloads of a bound mesh are positions in ITS storage)
     s->has_result = true;
 
     uint32_t out_count = pl.R;
-    if (sorted_out && s->last_culled) {            // the result's length is only known on the device
+    if (sorted_out && pl.count_on_device) {        // the result's length is only known on the device
         SortFrame f;
         GS_HIP(hipMemcpyAsync(&f, kp.frame, sizeof(f), hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
@@ -1965,9 +1824,9 @@ static int sort_finish(gs_sorter* s, const SortPlan& pl, const KeyParams& kp, ui
     }
     if (sorted_out && out_count) {
         const void* src = s->sorted.p;
-        if (pl.unmap) {                            // the host always sees the caller's splat indexes
+        if (c.unmap) {                             // the host always sees the caller's splat indexes
             GS_TRY(s->debug.ensure((size_t)s->max_count * 4));
-            hipLaunchKernelGGL(k_unmap, dim3(grid_for(out_count, 1024, 2048)), dim3(256), 0, st, s->sorted.as<uint32_t>(), pl.unmap,
+            hipLaunchKernelGGL(k_unmap, dim3(grid_for(out_count, 1024, 2048)), dim3(256), 0, st, s->sorted.as<uint32_t>(), c.unmap,
                                s->debug.as<uint32_t>(), out_count, s->result_payload_max);
             GS_HIP(hipGetLastError());
             src = s->debug.p;
@@ -1982,22 +1841,23 @@ static int sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_t
                        uint32_t render_count, const void* precomputed, const float* transforms, uint32_t* sorted_out,
                        gs_sort_stats* stats, const uint32_t* list_count_dev = nullptr) {
     GS_REQUIRE(s && mvp, "sorter / mvp == NULL");
-    SortPlan pl = {};
-    pl.mvp = mvp; pl.indexes_to_sort = indexes_to_sort; pl.device_list = device_list; pl.precomputed = precomputed;
-    pl.transforms = transforms; pl.list_count_dev = list_count_dev;
+    SortCall c = {};
+    c.mvp = mvp; c.indexes_to_sort = indexes_to_sort; c.device_list = device_list; c.precomputed = precomputed;
+    c.transforms = transforms; c.list_count_dev = list_count_dev; c.sort_count = sort_count; c.render_count = render_count;
+    SortPlanIn in;
+    GS_TRY(sort_check(s, c, in));
+    const SortPlan pl = plan_sort(in);
     KeyParams kp = {};
-    GS_TRY(sort_check(s, sort_count, render_count, pl));
     ScopedDevice sd(s->ctx->device);
-    GS_TRY(sort_stage_inputs(s, pl, kp));
+    GS_TRY(sort_stage_inputs(s, c, pl, kp));
     s->timed_sort = stats != nullptr || s->ctx->stage_events;
     if (s->timed_sort) GS_HIP(hipEventRecord(s->ev0, s->stream));
-    uint32_t passes = 0;
-    if (pl.Rs > 0) {
-        GS_TRY(launch_front_end(s, pl, kp));
-        GS_TRY(run_radix_passes(s, pl, kp));
-        passes = (s->precision + 7) / 8;
+    s->clean_slot = pl.next_clean_slot;        // (unchanged when nothing is sorted)
+    if (pl.front != SORT_FRONT_NONE) {
+        GS_TRY(launch_front_end(s, c, pl, kp));
+        GS_TRY(run_radix_passes(s, c, pl, kp));
     }
-    return sort_finish(s, pl, kp, passes, sorted_out, stats);
+    return sort_finish(s, c, in, pl, kp, sorted_out, stats);
 }
 
 int gs_sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_sort, uint32_t sort_count,
@@ -2062,14 +1922,26 @@ int gs_sorter_last_stats(gs_sorter* s, gs_sort_stats* stats) {
 int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
     GS_REQUIRE(s && dst, "sorter / dst == NULL");
     GS_REQUIRE(s->has_result, "no sort has run");
+    const SortPlan& lp = s->last_plan;
     if (what == 4) {
         // the last sort's front end, host words: {1 = k_depth_key_hist with a known range, |extreme set| (0: none), lo, hi as the
         // host computed them (0, 0 on the other path), 1 = the set covers the current centres, pass 0's slot of group rows,
         // 1 = that front end stored 16-bit radix keys, 1 = it read the 16-bit centre planes}
         const bool valid = s->extreme_ok && s->extreme_version == s->centers_version;
-        const int32_t w[8] = {s->last_known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, s->last_range_lo, s->last_range_hi,
-                              valid ? 1 : 0, (int32_t)s->last_pass0_slot, s->last_narrow ? 1 : 0, s->last_compact ? 1 : 0};
+        const bool compact = lp.front == SORT_FRONT_KNOWN_COMPACT, narrow = compact || lp.front == SORT_FRONT_KNOWN_NARROW;
+        const int32_t w[8] = {lp.known_range ? 1 : 0, valid ? (int32_t)(s->extreme.size() / 4) : 0, lp.range_lo, lp.range_hi,
+                              valid ? 1 : 0, (int32_t)lp.pass0_slot, narrow ? 1 : 0, compact ? 1 : 0};
         GS_REQUIRE(count <= 8u, "selector 4 holds 8 words");
+        memcpy(dst, w, (size_t)count * 4);
+        return GS_OK;
+    }
+    if (what == 5) {
+        // the last sort's plan, host words: the SortPlanIn it was made from, then the SortPlan that ran (sort_plan.hpp)
+        constexpr uint32_t IN_WORDS = sizeof(SortPlanIn) / 4, WORDS = IN_WORDS + sizeof(SortPlan) / 4;
+        GS_REQUIRE(count <= WORDS, "selector 5 holds the words of SortPlanIn and SortPlan");
+        uint32_t w[WORDS];
+        memcpy(w, &s->last_in, sizeof(SortPlanIn));
+        memcpy(w + IN_WORDS, &lp, sizeof(SortPlan));
         memcpy(dst, w, (size_t)count * 4);
         return GS_OK;
     }
@@ -2103,8 +1975,8 @@ int gs_sorter_debug_read(gs_sorter* s, int what, void* dst, uint32_t count) {
         GS_HIP(hipGetLastError());
         src = s->debug.p;
     } else if (what == 3) {
-        GS_REQUIRE(s->last_culled, "the last sort did not cull");
-        if (s->last_vis_culled) {                  // the bound mesh's per-splat mask (original splat numbering), as consumed
+        GS_REQUIRE(lp.count_on_device, "the last sort did not cull");
+        if (lp.vis_cull) {                  // the bound mesh's per-splat mask (original splat numbering), as consumed
             GS_REQUIRE((size_t)count * 4 <= s->mask_copy.bytes, "count exceeds the mask length");
             src = s->mask_copy.p;
         } else {

@@ -576,7 +576,7 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback&
     if (grid < 1) grid = 1;
     if (grid > (uint32_t)BIN_MAX_BLOCKS) grid = BIN_MAX_BLOCKS;
     const uint32_t cap = m->entry_capacity;
-    const uint32_t* R_dev = (sorter && sorter->last_culled) ? &sorter->result_frame->kept : nullptr;
+    const uint32_t* R_dev = (sorter && sorter->last_plan.count_on_device) ? &sorter->result_frame->kept : nullptr;
     const uint32_t blend_bins = pp.bins_x * (pp.bin_row_end - pp.bin_row_begin);
     // the chunked composite's per-draw words and the pool the per-bin kernel closes chunks into (reset by k_bin_count)
     GS_TRY(m->deep_flags.ensure(((size_t)GS_FLAG_OF + blend_bins) * 4 + 64));

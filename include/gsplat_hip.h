@@ -166,7 +166,11 @@ int gs_sorter_set_visibility_cull(gs_sorter* s, int enable);
  *           centres (0: none), lo, hi of the key range as the host computed it (0, 0 on the other path), 1 = the set covers
  *           the current centres, pass 0's slot of group rows, 1 = the sort stored 16-bit radix keys instead of the depths,
  *           1 = that kernel read the centres as 16-bit offset planes (an extreme set no wider than 65535 per axis; off with
- *           $GSPLAT_NO_COMPACT_CENTRES) instead of the int32 planes}.
+ *           $GSPLAT_NO_COMPACT_CENTRES) instead of the int32 planes},
+ *       5 = the last sort's host plan, host words: the inputs it was planned from, then the plan that ran - every field a
+ *           32-bit word, in the order of SortPlanIn and SortPlan in csrc/sort_plan.hpp (typed by tests/sort_plan_cases.py): the
+ *           front end and its grids, what became of a pending gather, pass 0's slot, and per radix pass its loader, output,
+ *           shifts, slot and grid.
  * Selectors 0 and 1 always describe the sort that ran.  A sort that stored 16-bit radix keys (word 6 of selector 4) keeps
  * no depths: they are rebuilt on the device from the centres and that sort's coefficients when a selector asks for them,
  * and before an upload of centres overwrites what they are made from. */

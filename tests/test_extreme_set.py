@@ -153,3 +153,85 @@ def test_appended_ranges_extend_the_set_like_a_rebuild():
     check_extremes(np.concatenate([line, [[1, 1, 1]]]), cset)
     cset = extreme_set(np.array([[-50, 400, 3]]), prior=cset)
     check_extremes(np.concatenate([line, [[1, 1, 1]], [[-50, 400, 3]]]), cset)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the exact key range of a sort over the set (gs_key_range): min / max of im . c in exact integers, refused when a key could wrap
+# ---------------------------------------------------------------------------------------------------------------------------
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def key_range(rows, im):
+    """rows: (n, 3) integers, im: 3 integers (all int32).  (lo, hi), or None when the library reports no range."""
+    a = np.full((len(rows), 4), 77, dtype=np.int32)            # (the w lane is ignored)
+    if len(rows):
+        a[:, :3] = np.asarray(rows, dtype=np.int64)
+    im3 = np.asarray(im, dtype=np.int32)
+    out = np.array([123, 456], dtype=np.int32)
+    fn = g.load().gs_debug_key_range
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    st = fn(a.ctypes.data if len(rows) else None, len(rows), im3.ctypes.data, out.ctypes.data)
+    assert st in (0, 1), st
+    if st == 0:
+        assert out.tolist() == [123, 456]                      # lo / hi are left alone
+        return None
+    return int(out[0]), int(out[1])
+
+
+def key_range_model(rows, im):
+    if not len(rows):
+        return None
+    v = _dots(rows, tuple(int(k) for k in im))
+    return (min(v), max(v)) if min(v) >= INT32_MIN and max(v) <= INT32_MAX else None
+
+
+BIG = 1 << 29
+KEY_RANGE_CASES = [
+    # (name, rows, im, expected or "model")
+    ("empty_set", [], (1, 2, 3), None),
+    ("one_row", [(5, -7, 11)], (1000, -2000, 3000), (5000 + 14000 + 33000, 52000)),
+    ("zero_coefficients", [(INT32_MAX, INT32_MIN, 5), (1, 2, 3)], (0, 0, 0), (0, 0)),
+    # coefficients at +-2^29: the int64 branch's largest products (3 x 2^29 x 2^31 = 3 x 2^60), far outside int32
+    ("im_at_2p29_extreme_rows", [(INT32_MAX, INT32_MAX, INT32_MAX), (INT32_MIN, INT32_MIN, INT32_MIN)], (BIG, BIG, BIG), None),
+    ("im_at_minus_2p29_extreme_rows", [(INT32_MIN, INT32_MIN, INT32_MIN), (INT32_MAX, INT32_MIN, INT32_MAX)], (-BIG, -BIG, -BIG), None),
+    ("im_at_2p29_small_rows", [(1, 1, 1), (-1, -2, -1), (0, 3, 0)], (BIG, BIG, BIG), (-4 * BIG, 3 * BIG)),
+    ("im_at_2p29_cancelling", [(INT32_MAX, INT32_MIN + 1, 0), (3, 0, 0)], (BIG, BIG, -BIG), (0, 3 * BIG)),
+    # ... and beyond: the __int128 branch (sums reach 3 x 2^62)
+    ("im_beyond_2p29_small_rows", [(1, 0, 0), (0, 0, 1), (-1, 0, 0)], (BIG + 1, 5, -7), (-(BIG + 1), BIG + 1)),
+    ("im_int32_extremes_wrap", [(INT32_MIN, INT32_MIN, INT32_MIN), (INT32_MAX, INT32_MAX, INT32_MAX)], (INT32_MIN, INT32_MIN, INT32_MIN), None),
+    ("im_int32_max_cancelling", [(INT32_MAX, INT32_MAX, 0), (2, 1, 0)], (INT32_MAX, -INT32_MAX, 1), (0, INT32_MAX)),
+    ("im_int32_min_times_one", [(1, 0, 0), (0, 0, 0)], (INT32_MIN, 0, 0), (INT32_MIN, 0)),
+    ("im_int32_min_times_minus_one_is_one_beyond", [(-1, 0, 0), (0, 0, 0)], (INT32_MIN, 0, 0), None),
+    # ranges that end exactly at INT32_MIN / INT32_MAX, and one beyond them - in either branch
+    ("hi_at_int32_max", [(INT32_MAX, 0, 0), (0, 0, 0)], (1, 1, 1), (0, INT32_MAX)),
+    ("hi_one_beyond_int32_max", [(INT32_MAX, 1, 0), (0, 0, 0)], (1, 1, 1), None),
+    ("lo_at_int32_min", [(INT32_MIN, 0, 0), (0, 0, 0)], (1, 1, 1), (INT32_MIN, 0)),
+    ("lo_one_beyond_int32_min", [(INT32_MIN, -1, 0), (0, 0, 0)], (1, 1, 1), None),
+    ("both_ends_exact", [(INT32_MAX, 0, 0), (0, INT32_MIN, 0)], (1, 1, 0), (INT32_MIN, INT32_MAX)),
+    ("hi_at_int32_max_int128", [(0, 0, INT32_MAX), (0, 0, 0)], (BIG + 5, 7, 1), (0, INT32_MAX)),
+    ("hi_one_beyond_int32_max_int128", [(0, 1, INT32_MAX), (0, 0, 0)], (BIG + 5, 1, 1), None),
+    ("lo_at_int32_min_int128", [(0, 0, INT32_MIN), (0, 0, 0)], (-BIG - 5, 7, 1), (INT32_MIN, 0)),
+    ("lo_one_beyond_int32_min_int128", [(0, -1, INT32_MIN), (0, 0, 0)], (-BIG - 5, 1, 1), None),
+    ("product_exact_2p31_minus_1_factors", [(46341, 0, 0), (0, 0, 0)], (46340, 0, 0), (0, 46341 * 46340)),
+]
+
+
+@pytest.mark.parametrize("name,rows,im,expected", KEY_RANGE_CASES, ids=[c[0] for c in KEY_RANGE_CASES])
+def test_key_range_in_exact_integers(name, rows, im, expected):
+    assert key_range_model(rows, im) == expected, "the case's own expectation against Python integers"
+    assert key_range(rows, im) == expected
+
+
+def test_key_range_random_rows_and_coefficients():
+    """Seeded rows and coefficients of every magnitude, both branches, against Python integers."""
+    rng = np.random.default_rng(29)
+    seen = {True: 0, False: 0}
+    for k in range(400):
+        cbits, ibits = int(rng.integers(1, 32)), int(rng.integers(1, 32))
+        rows = rng.integers(-(1 << cbits), 1 << cbits, size=(int(rng.integers(1, 40)), 3)).clip(INT32_MIN, INT32_MAX)
+        im = rng.integers(-(1 << ibits), 1 << ibits, size=3).clip(INT32_MIN, INT32_MAX)
+        want = key_range_model(rows, im)
+        assert key_range(rows, im) == want, (k, im.tolist())
+        seen[want is not None] += 1
+    assert min(seen.values()) >= 50                            # both verdicts, often
