@@ -116,8 +116,7 @@ extern "C" int gs_mesh_bounds(gs_mesh* m, uint32_t from, uint32_t count, const d
     // the slotted range that holds the whole of [from, from + count): a fresh segment is stored in its own slots, so the splats
     // of a slotted range occupy exactly the storage positions of that range
     uint32_t pos_begin = 0u, pos_end = 0u;
-    for (const auto& s : m->slotted)
-        if (s.first <= from && (uint64_t)from + count <= s.second) { pos_begin = s.first; pos_end = s.second; }
+    if (const SlotRange* s = m->slotted.holding(from, count)) { pos_begin = s->begin; pos_end = s->end; }
     GS_REQUIRE(pos_end > pos_begin && pos_end <= m->uploaded && pos_end <= m->max_count, "the range is not wholly uploaded");
     ScopedDevice sd(m->ctx->device);
     hipStream_t st = m->ctx->stream;

@@ -6,12 +6,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
-#include <utility>
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
 #include "draw_plan.hpp"
 #include "sort_plan.hpp"
+#include "upload_plan.hpp"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -413,6 +413,27 @@ inline PlanView plan_view(const ProjectParams& pp) {
 // (struct DrawSwitches: draw_plan.hpp)
 DrawSwitches draw_switches();
 
+// One set of the vertex stage's outputs, with everything that belongs to it (gs_mesh::sets).
+struct ProjSet {
+    DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
+    DevBuf zrec;               // float [n]     the survivor's window-space centre depth, same slots (only while a destination
+                               //               depth is set: the blend's depth test, gs_mesh_set_destination)
+    DevBuf rects;              // uint2 [n]     tile rect per survivor, same slots
+    DevBuf vis_mask;           // uint64 [4*ceil(n/256)]  1 = splat survived the vertex stage and touches a pixel
+    DevBuf block_any;          // uint8 [ceil(n/256)]      1 = some splat of the 256-splat block survived the vertex stage
+    DevBuf vis32;              // uint2 [8*ceil(n/256)]   {the same mask per 32 splats, slot of its first visible splat}
+    DevBuf prect;              // uint2 [n]: per splat POSITION of a live block {x0:12|y0:12|slot in block:8, x1:12|y1:12|visible:1}:
+                               //            the binner's one gather per sorted index (project.hip)
+    DevBuf vis_orig;           // uint32 [ceil(n/32)]     the mask by ORIGINAL splat index (gs_mesh_project only: feeds the
+                               //                         visibility-culled sort)
+    hipEvent_t ev_done = nullptr;         // end of the last draw that read this set (on ctx->stream)
+    bool drawn = false;                   // a draw has read this set (ev_done is recorded)
+    bool vis_orig_lazy = false;           // the projection left vis_orig to the bound sorter: it holds nothing yet
+    bool vis_orig_dirty = true;           // vis_orig may hold bits (cleared by the sort that consumes it, see k_mask_compact)
+    bool vis_orig_tail_zero = false;      // (lazy projection) the words its sorter does not write were zero: the sort leaves all zero
+    uint32_t vis_orig_count = 0;          // splats the last gs_mesh_project into this set looked at
+};
+
 struct gs_mesh {
     gs_context* ctx = nullptr;
     uint32_t list_shift = GS_LIST_SHIFT_LARGE;     // list-bin size of the next draw (mesh_collect_stats re-evaluates it)
@@ -435,7 +456,7 @@ struct gs_mesh {
                                // u8  : sh0 = uint4 (bytes 0..15), sh1 = uint2 (bytes 16..23, SH2 only)
     DevBuf perm;               // uint32 [n]: original splat index -> internal (Morton-ordered) position
     DevBuf inv_perm;           // uint32 [n]: internal position -> original splat index
-    std::vector<std::pair<uint32_t, uint32_t>> slotted;   // [begin, end) ranges of splats that own storage slots (disjoint, sorted)
+    SlottedRanges slotted;     // the splats that own storage slots (upload_plan.hpp)
     bool reorder = true;
     uint32_t layout_version = 0;   // bumped whenever splats receive storage slots (perm changes): a sorter's per-tree payload cache
     bool no_block_cull = false;    // GSPLAT_NO_BLOCK_CULL=1 (A/B and tests)
@@ -455,17 +476,6 @@ struct gs_mesh {
     DevBuf distances;          // uint32 [n]: gs_mesh_compute_distances's result when no sorter receives it (distances.hip)
     DevBuf bounds_buf;         // gs_mesh_bounds: a partial per workgroup, then the scenes' fp64 transforms (bounds.hip)
     // per-draw
-    DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
-    DevBuf zrec;               // float [n]     the survivor's window-space centre depth, same slots (only while a destination
-                               //               depth is set: the blend's depth test, gs_mesh_set_destination)
-    DevBuf rects;              // uint2 [n]     tile rect per survivor, same slots
-    DevBuf vis_mask;           // uint64 [4*ceil(n/256)]  1 = splat survived the vertex stage and touches a pixel
-    DevBuf block_any;          // uint8 [ceil(n/256)]      1 = some splat of the 256-splat block survived the vertex stage
-    DevBuf vis32;              // uint2 [8*ceil(n/256)]   {the same mask per 32 splats, slot of its first visible splat}
-    DevBuf prect;              // uint2 [n]: per splat POSITION of a live block {x0:12|y0:12|slot in block:8, x1:12|y1:12|visible:1}:
-                               //            the binner's one gather per sorted index (project.hip)
-    DevBuf vis_orig;           // uint32 [ceil(n/32)]     the mask by ORIGINAL splat index (gs_mesh_project only: feeds the
-                               //                         visibility-culled sort)
     DevBuf cidx;               // uint32 [render_count] record slots of the visible splats in traversal order (compacted per workgroup)
     DevBuf order;              // uint32 [render_count] when the caller supplies host indexes
     DevBuf rect_q;             // uint2 [render_count] their rects, same layout as cidx
@@ -501,18 +511,14 @@ struct gs_mesh {
     uint32_t ring_next = 0;
     double proj_sum_ms = 0.0, stage_sum_ms = 0.0;  // k_project alone (sampled draws) | block test + mask memset + k_project (timed draws)
     uint32_t proj_launches = 0, stage_launches = 0;
-    hipEvent_t ev_done = nullptr;                  // end of the last draw that read THIS set of vertex-stage outputs (on ctx->stream)
     // The vertex stage's outputs exist twice on a context with streams of its own: the vertex stage of frame k + 1 writes the set
-    // frame k - 1 drew from while frame k is still binned and blended from the other one (mesh_project swaps the two; every field
-    // that belongs to a set is swapped with it).  `alt` is the set that is NOT current.
-    struct ProjSet {
-        DevBuf recs, zrec, rects, vis_mask, block_any, vis32, prect, vis_orig;
-        hipEvent_t ev_done = nullptr;
-        bool drawn = false, vis_orig_dirty = true, vis_orig_lazy = false, vis_orig_tail_zero = false;
-        uint32_t vis_orig_count = 0;
-    } alt;
-    bool two_sets = false;                         // alt is allocated and in use
-    bool set_drawn = false;                        // a draw has read the current set (ev_done is recorded)
+    // frame k - 1 drew from while frame k is still binned and blended from the other one (mesh_project flips cur_set).  A
+    // launcher binds set() once at its top.  One set (a single-stream context, $GSPLAT_ONE_RECORD_SET): set 0 only.
+    ProjSet sets[2];
+    uint32_t cur_set = 0;
+    bool two_sets = false;                         // sets[1] is allocated and in use
+    ProjSet& set() { return sets[cur_set]; }         // the current set
+    const ProjSet& set() const { return sets[cur_set]; }
     gs_render_stats last = {};
     bool has_draw = false;
     uint32_t last_count = 0;
@@ -525,10 +531,7 @@ struct gs_mesh {
     uint32_t last_project_mode = 1;       // gs_launch_project: 1 = k_block_test + k_project, 0 = the test in every workgroup, 2 = no test
     bool derive_orig_mask = false;        // a bound sorter builds vis_orig itself from vis_mask + its position map (sorter.hip,
                                           // k_mask_derive_count): full-frame gs_mesh_project calls skip the per-survivor atomics
-    bool vis_orig_lazy = false;           // ... and the pending projection did: vis_orig holds nothing yet
-    bool vis_orig_dirty = true;           // vis_orig may hold bits (cleared by the sort that consumes it, see k_mask_compact)
-    bool vis_orig_tail_zero = false;      // (lazy projection) the words its sorter does not write were zero: the sort leaves all zero
-    uint32_t vis_orig_count = 0;          // splats the last gs_mesh_project looked at
+                                          // (ProjSet::vis_orig_lazy: the pending projection did)
     bool timed_project = false;           // the last vertex stage was bracketed with ev_p0 / ev_p1
     bool timed_draw = false;              // the last draw recorded its stage events (see gs_context::stage_events)
     uint32_t truncated_draws = 0;      // asynchronous draws that overflowed the entry buffer (noticed after the fact)
@@ -554,11 +557,8 @@ const uint32_t* gs_mesh_payload_unmap(gs_mesh* m);
 // One upload into a mesh = per segment "fill the staging" (the source's half) + "commit the staging" (mesh.hip's half: Morton
 // keys, radix passes, permutation, the split kernels, the block boxes).  gs_mesh_upload fills by hipMemcpy from host arrays,
 // gs_mesh_upload_asset (asset_decode.hip) with a decode kernel; everything else of an upload is gs_mesh_upload_from's.
-struct MeshStaging {                       // where a segment's arrays sit in gs_mesh::staging
-    char* base;                            // centres: float [3n]
-    size_t off_cov, off_sh, off_rgba;      // covariance float [6n] or half bits [6n] | SH half bits or uint8 [ncoef n] | rgba uint8 [4n]
-    uint32_t ncoef;                        // SH values per splat the source stages (0: none)
-    bool sh_u8;                            // ... as uint8 (a GS_MESH_SH_U8 mesh whose source stages them), else half bits
+struct MeshStaging : UploadLayout {        // where a segment's arrays sit in gs_mesh::staging (upload_plan.hpp)
+    char* base = nullptr;                  // centres: float [3n]
 };
 struct MeshUploadSource {
     const float* host_centers = nullptr;   // the range's centres in host memory; NULL: bounds and scene sums are reduced on the device

@@ -6,7 +6,6 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <utility>
 
 #include "radix.hpp"
 
@@ -303,19 +302,20 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     if (const char* ls = getenv("GSPLAT_LIST_SHIFT"))
         if (ls[0] >= '1' && ls[0] <= '6' && ls[1] == '\0') m->forced_list_shift = ls[0] - '0';
     if (m->reorder) { A(m->perm, n * 4 + 16); A(m->inv_perm, n * 4); }   // (+16: the sorter's k_cull_front reads perm as 16-byte vectors)
-    A(m->recs, n * sizeof(SplatRec)); A(m->rects, n * 8); A(m->rect_q, n * 8 + 2048); A(m->cidx, n * 4 + 1024); A(m->coff, n * 4 + 1024);
-    A(m->vis_mask, ((n + 255) / 256) * 32 + 32);   // whole 256-splat blocks: 4 words each
-    A(m->vis32, ((n + 255) / 256) * 64 + 64);
-    A(m->prect, ((n + 255) / 256) * 256 * 8 + 64);
-    A(m->block_any, ((n + 255) / 256 + 127) & ~(size_t)63);
+    A(m->rect_q, n * 8 + 2048); A(m->cidx, n * 4 + 1024); A(m->coff, n * 4 + 1024);
     // (a context with one stream runs the frames' kernels in order: a second set would never be written early)
     m->two_sets = ctx->aux != ctx->stream && !getenv("GSPLAT_ONE_RECORD_SET");
-    if (m->two_sets) {
-        A(m->alt.recs, n * sizeof(SplatRec)); A(m->alt.rects, n * 8);
-        A(m->alt.vis_mask, ((n + 255) / 256) * 32 + 32);
-        A(m->alt.vis32, ((n + 255) / 256) * 64 + 64);
-        A(m->alt.prect, ((n + 255) / 256) * 256 * 8 + 64);
-        A(m->alt.block_any, ((n + 255) / 256 + 127) & ~(size_t)63);
+    for (int k = 0; k < (m->two_sets ? 2 : 1); k++) {      // (zrec and vis_orig: by the first vertex stage that writes them)
+        ProjSet& ps = m->sets[k];
+        A(ps.recs, n * sizeof(SplatRec)); A(ps.rects, n * 8);
+        A(ps.vis_mask, ((n + 255) / 256) * 32 + 32);   // whole 256-splat blocks: 4 words each
+        A(ps.vis32, ((n + 255) / 256) * 64 + 64);
+        A(ps.prect, ((n + 255) / 256) * 256 * 8 + 64);
+        A(ps.block_any, ((n + 255) / 256 + 127) & ~(size_t)63);
+        if (st == GS_OK && hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming) != hipSuccess) {
+            gs_set_error("hipEventCreate failed");
+            st = GS_ERR_HIP;
+        }
     }
     A(m->bin_sums, 4 * 3 * 2048 + 64);               // uint32 [3][BIN_MAX_BLOCKS] + the batches-per-workgroup of the last count
     A(m->frame, sizeof(RenderFrame));
@@ -353,11 +353,6 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
             gs_set_error("hipEventCreate failed");
             st = GS_ERR_HIP;
         }
-    if (st == GS_OK && (hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming) != hipSuccess ||
-                        (m->two_sets && hipEventCreateWithFlags(&m->alt.ev_done, hipEventDisableTiming) != hipSuccess))) {
-        gs_set_error("hipEventCreate failed");
-        st = GS_ERR_HIP;
-    }
     for (int i = 0; i < gs_mesh::TIMING_RING && st == GS_OK; i++)
         if (hipEventCreate(&m->ring0[i]) != hipSuccess || hipEventCreate(&m->ring1[i]) != hipSuccess) {
             gs_set_error("hipEventCreate failed");
@@ -397,34 +392,23 @@ void gs_mesh_destroy(gs_mesh* m) {
         if (m->ring0[i]) (void)hipEventDestroy(m->ring0[i]);
         if (m->ring1[i]) (void)hipEventDestroy(m->ring1[i]);
     }
-    if (m->ev_done) (void)hipEventDestroy(m->ev_done);
-    if (m->alt.ev_done) (void)hipEventDestroy(m->alt.ev_done);
+    for (ProjSet& ps : m->sets)
+        if (ps.ev_done) (void)hipEventDestroy(ps.ev_done);
     if (m->mirror_host) (void)hipHostFree(m->mirror_host);
     delete m;
 }
 
 // true when every splat of [from, from + count) already owns a storage slot (gs_mesh_upload has seen it)
 static bool mesh_range_slotted(const gs_mesh* m, uint32_t from, uint32_t count) {
-    if (!m->reorder || count == 0) return true;
-    for (const auto& r : m->slotted)
-        if (r.first <= from && from + count <= r.second) return true;      // ranges are merged, so one must cover it
-    return false;
+    return !m->reorder || count == 0 || m->slotted.holding(from, count);
 }
 
 }  // extern "C"
 
-// Where a segment's arrays sit in gs_mesh::staging (MeshStaging, gs_internal.hpp).  sh_u8: the source stages the uint8 SH of a
-// GS_MESH_SH_U8 mesh too (the host path hands those to gs_mesh_upload_sh_u8 instead).
+// Where a segment's arrays sit in gs_mesh::staging (upload_layout, upload_plan.hpp), and the room for them.
 static int mesh_staging_layout(gs_mesh* m, uint32_t count, bool sh_u8, MeshStaging* s) {
-    const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
-    const bool mesh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
-    s->ncoef = (m->sh_degree == 0 || (mesh_u8 && !sh_u8)) ? 0 : (m->sh_degree == 1 ? 9 : 24);
-    s->sh_u8 = mesh_u8 && s->ncoef != 0;
-    const size_t b_c = (size_t)count * 12, b_cov = (size_t)count * (half ? 12 : 24), b_sh = (size_t)count * s->ncoef * (s->sh_u8 ? 1 : 2);
-    s->off_cov = (b_c + 255) & ~(size_t)255;
-    s->off_sh = (s->off_cov + b_cov + 255) & ~(size_t)255;
-    s->off_rgba = (s->off_sh + b_sh + 255) & ~(size_t)255;
-    GS_TRY(m->staging.ensure(s->off_sh + b_sh + 512 + (size_t)count * 4));
+    static_cast<UploadLayout&>(*s) = upload_layout(count, (m->flags & GS_MESH_COV_HALF) != 0, (m->flags & GS_MESH_SH_U8) != 0, m->sh_degree, sh_u8);
+    GS_TRY(m->staging.ensure(s->bytes));
     s->base = m->staging.as<char>();
     return GS_OK;
 }
@@ -484,12 +468,14 @@ __global__ __launch_bounds__(256) void k_centre_reduce(const float* __restrict__
     }
 }
 
-// The commit half of an upload: what the source's fill left in the staging -> the mesh's planes.  fresh: these splats have no
-// storage slots yet - they get the Morton order of the segment; otherwise they keep the slots an earlier upload gave them (perm
+// The commit half of an upload: what the source's fill left in the staging -> the mesh's planes.  seg.fresh: these splats have
+// no storage slots yet - they get the Morton order of the segment; otherwise they keep the slots an earlier upload gave them (perm
 // stays a bijection, planes uploaded through the other entry points and a bound sorter's resident result stay valid).
 // host_centers: the segment's centres on the host (the Morton bounds are taken from them), or NULL: bounds and the scene's
 // centre sums are reduced on the device.
-static int mesh_commit_segment(gs_mesh* m, uint32_t from, uint32_t count, const MeshStaging& s, const float* host_centers, bool fresh) {
+static int mesh_commit_segment(gs_mesh* m, const UploadSegment& seg, const MeshStaging& s, const float* host_centers) {
+    const uint32_t from = seg.begin, count = seg.end - seg.begin;
+    const bool fresh = seg.fresh;
     const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
     hipStream_t st = m->ctx->stream;
     char* stg = s.base;
@@ -557,19 +543,9 @@ static int mesh_commit_segment(gs_mesh* m, uint32_t from, uint32_t count, const 
     else if (s.ncoef)
         hipLaunchKernelGGL(k_split_sh, g, b, 0, st, (const uint16_t*)(stg + s.off_sh), count, from, perm, s.ncoef, m->sh0.as<uint4>(),
                            m->sh1.p, m->sh2.as<uint4>());
-    {   // The boxes of the storage blocks this segment touches.  A fresh segment owns the slots [from, from + count); splats
-        // uploaded before keep THEIR slots, scattered over the Morton run(s) of the earlier upload(s) - anywhere inside the merged
-        // slotted range that contains the segment (segments are cut at the borders of those ranges): all of its blocks are redone.
-        // (only [from, from + count) was redone, so a block kept the box of the data it held before the edit and
-        // k_project's block cull could drop splats that had moved into view.)
-        uint32_t lo = from, hi = from + count;
-        if (!fresh && m->reorder)
-            for (const auto& r : m->slotted)
-                if (r.first <= from && from + count <= r.second) { lo = r.first; hi = r.second; }
-        const uint32_t b0 = lo / 256u, b1 = (hi + 255u) / 256u;
-        hipLaunchKernelGGL(k_block_boxes, dim3(b1 - b0), dim3(256), 0, st, m->px.as<float>(), m->py.as<float>(), m->pz.as<float>(),
-                           m->cov_bound.as<float>(), m->max_count, b0, m->block_box.as<float>());
-    }
+    // the boxes of the storage blocks this segment invalidates (UploadSegment, upload_plan.hpp)
+    hipLaunchKernelGGL(k_block_boxes, dim3(seg.b1 - seg.b0), dim3(256), 0, st, m->px.as<float>(), m->py.as<float>(), m->pz.as<float>(),
+                       m->cov_bound.as<float>(), m->max_count, seg.b0, m->block_box.as<float>());
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;
@@ -578,8 +554,8 @@ static int mesh_commit_segment(gs_mesh* m, uint32_t from, uint32_t count, const 
 // SplatMesh.updateDataTexturesFromBaseData(fromSplat, toSplat) accepts any range, any number of times
 // (/root/reference/src/splatmesh/SplatMesh.js:900-1062).  Splats seen for the first time are stored along the Morton curve
 // of their own contiguous run; splats uploaded before keep their slots and only have their data replaced.
-// One upload, whatever fills the staging (MeshUploadSource): the stream discipline, the fresh / non-fresh segment cuts and the
-// slotted-range bookkeeping are said here once for gs_mesh_upload and gs_mesh_upload_asset.
+// One upload, whatever fills the staging (MeshUploadSource): the stream discipline and the order of its steps are said here
+// once for gs_mesh_upload and gs_mesh_upload_asset; the fresh / non-fresh segment cuts and the slotted ranges are upload_plan.hpp's.
 int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSource& src) {
     if (count == 0) return GS_OK;
     m->projection_pending = false;                        // the scene changed under a pending gs_mesh_project
@@ -600,36 +576,14 @@ int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSou
         }
         m->centre_sum[0] += sx; m->centre_sum[1] += sy; m->centre_sum[2] += sz; m->centre_sq += sq; m->centre_n += n;
     }
-    // cut [from, end) at the borders of the ranges that already own storage slots (disjoint, sorted by begin)
-    std::vector<std::pair<uint32_t, bool>> cuts;          // (segment begin, fresh)
-    uint32_t pos = from;
-    for (const auto& r : m->slotted) {
-        if (r.second <= pos) continue;
-        if (r.first >= end) break;
-        if (r.first > pos) { cuts.push_back({pos, true}); pos = r.first; }
-        cuts.push_back({pos, false});
-        pos = r.second < end ? r.second : end;
-        if (pos == end) break;
-    }
-    if (pos < end) cuts.push_back({pos, true});
-    for (size_t k = 0; k < cuts.size(); k++) {
-        const uint32_t b = cuts[k].first, e = k + 1 < cuts.size() ? cuts[k + 1].first : end, o = b - from;
+    for (const UploadSegment& seg : plan_upload(m->slotted, from, count, m->reorder)) {
+        const uint32_t o = seg.begin - from;
         MeshStaging stg;
-        GS_TRY(mesh_staging_layout(m, e - b, src.stages_sh_u8, &stg));
-        GS_TRY(src.fill(m, o, e - b, stg, m->ctx->stream));
-        GS_TRY(mesh_commit_segment(m, b, e - b, stg, src.host_centers ? src.host_centers + 3 * (size_t)o : nullptr,
-                                   cuts[k].second || !m->reorder));
+        GS_TRY(mesh_staging_layout(m, seg.end - seg.begin, src.stages_sh_u8, &stg));
+        GS_TRY(src.fill(m, o, seg.end - seg.begin, stg, m->ctx->stream));
+        GS_TRY(mesh_commit_segment(m, seg, stg, src.host_centers ? src.host_centers + 3 * (size_t)o : nullptr));
     }
-    // merge [from, end) into the slotted ranges
-    std::vector<std::pair<uint32_t, uint32_t>> merged;
-    std::pair<uint32_t, uint32_t> cur(from, end);
-    for (const auto& r : m->slotted) {
-        if (r.second < cur.first || r.first > cur.second) merged.push_back(r);
-        else { cur.first = r.first < cur.first ? r.first : cur.first; cur.second = r.second > cur.second ? r.second : cur.second; }
-    }
-    merged.push_back(cur);
-    std::sort(merged.begin(), merged.end());
-    m->slotted.swap(merged);
+    m->slotted.add(from, end);
     if (end > m->uploaded) m->uploaded = end;
     return GS_OK;
 }
@@ -783,23 +737,13 @@ static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
 // The vertex stage of a draw.  It only depends on the scene and the camera, so it runs on ctx->aux next to whatever the
 // caller-visible stream and the sorter's stream are doing; it may start once the previous draw has consumed the records /
 // rects / mask it is about to overwrite.
-static void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
-static void mesh_swap_sets(gs_mesh* m) {
-    gs_mesh::ProjSet& o = m->alt;
-    swap_buf(m->recs, o.recs); swap_buf(m->zrec, o.zrec); swap_buf(m->rects, o.rects); swap_buf(m->vis_mask, o.vis_mask); swap_buf(m->block_any, o.block_any);
-    swap_buf(m->vis32, o.vis32); swap_buf(m->prect, o.prect); swap_buf(m->vis_orig, o.vis_orig);
-    std::swap(m->ev_done, o.ev_done); std::swap(m->set_drawn, o.drawn);
-    std::swap(m->vis_orig_dirty, o.vis_orig_dirty); std::swap(m->vis_orig_count, o.vis_orig_count); std::swap(m->vis_orig_lazy, o.vis_orig_lazy);
-    std::swap(m->vis_orig_tail_zero, o.vis_orig_tail_zero);
-}
-
 static int mesh_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, bool timed) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream, aux = ctx->aux;
     if (timed) GS_HIP(hipEventRecord(m->ev[0], st));
     // the set this vertex stage writes: the one the draw BEFORE the last read (two sets), else the last draw's own
-    if (m->two_sets) mesh_swap_sets(m);
-    if (aux != st && m->set_drawn) GS_HIP(hipStreamWaitEvent(aux, m->ev_done, 0));
+    if (m->two_sets) m->cur_set ^= 1u;
+    if (aux != st && m->set().drawn) GS_HIP(hipStreamWaitEvent(aux, m->set().ev_done, 0));
     const bool sample = timed || aux != st || (ctx->kernel_sample && m->project_serial++ % ctx->kernel_sample == 0);
     if (sample) {   // next slot of the timing ring; a slot about to be reused is harvested first (skipped if still in flight)
         const uint32_t slot = m->ring_next++ % gs_mesh::TIMING_RING;
@@ -860,8 +804,8 @@ static int mesh_draw_once(gs_mesh* m, const DrawSwitches& sw, const ProjectParam
         GS_HIP(hipEventRecord(m->ev[4], st));
         GS_HIP(hipEventRecord(m->ev[5], st));
     }
-    if (aux != st) GS_HIP(hipEventRecord(m->ev_done, st));     // only another stream ever waits for it
-    m->set_drawn = true;
+    if (aux != st) GS_HIP(hipEventRecord(m->set().ev_done, st));     // only another stream ever waits for it
+    m->set().drawn = true;
     m->has_draw = true;
     return GS_OK;
 }
@@ -994,7 +938,7 @@ int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
     // consumer is a bound sorter that holds the mesh's position map, left to that sorter (k_mask_derive_count: 25 us of a C3 frame)
     const bool lazy = m->derive_orig_mask && m->reorder && !draw_switches().no_lazy_mask && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
     GS_TRY(mesh_project(m, pp, lazy ? GS_ORIG_MASK_DERIVED : GS_ORIG_MASK_WRITE, m->ctx->stage_events));
-    m->vis_orig_lazy = lazy;
+    m->set().vis_orig_lazy = lazy;
     m->projection_pending = true;
     m->projected_cam = *cam;
     m->projected_depth_mode = pp.depth_mode;
@@ -1144,6 +1088,7 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
     GS_REQUIRE(m && dst, "mesh / dst == NULL");
     ScopedDevice sd(m->ctx->device);
     hipStream_t st = m->ctx->stream;
+    const ProjSet& ps = m->set();
     if (what >= 10 && what <= 12) {   // the upload-time planes behind the strip and block culls (no draw needed)
         if (count == 0) return GS_OK;
         if (what == 11) {             // block_box rows: 8 floats per storage block
@@ -1166,11 +1111,11 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         if (count == 0) return GS_OK;
         const uint32_t splats = what == 3 ? (count * 64u < m->last_count ? count * 64u : m->last_count) : count;
         const size_t bytes = what == 3 ? (size_t)count * 8 : (size_t)count * (what == 0 ? sizeof(SplatRec) : what == 9 ? 4 : 8);
-        GS_REQUIRE(what != 3 || (size_t)count * 8 <= m->vis_mask.bytes, "count exceeds the mask length");
+        GS_REQUIRE(what != 3 || (size_t)count * 8 <= ps.vis_mask.bytes, "count exceeds the mask length");
         GS_TRY(m->staging.ensure(bytes + 64));
         if (what == 3) GS_HIP(hipMemsetAsync(m->staging.p, 0, bytes, st));
-        hipLaunchKernelGGL(k_debug_expand, dim3((splats + 255u) / 256u), dim3(256), 0, st, m->vis_mask.as<unsigned long long>(), m->vis32.as<uint2>(), splats,
-                           m->reorder ? m->perm.as<uint32_t>() : nullptr, m->recs.as<uint4>(), m->rects.as<uint2>(),
+        hipLaunchKernelGGL(k_debug_expand, dim3((splats + 255u) / 256u), dim3(256), 0, st, ps.vis_mask.as<unsigned long long>(), ps.vis32.as<uint2>(), splats,
+                           m->reorder ? m->perm.as<uint32_t>() : nullptr, ps.recs.as<uint4>(), ps.rects.as<uint2>(),
                            what == 0 ? m->staging.as<uint4>() : nullptr, what == 1 ? m->staging.as<uint2>() : nullptr,
                            what == 3 ? m->staging.as<unsigned long long>() : nullptr, what == 9 ? m->staging.as<uint32_t>() : nullptr);
         GS_HIP(hipGetLastError());
@@ -1218,9 +1163,9 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         if (count) GS_HIP(hipMemcpyAsync(dst, (m->sorted_buf ? m->evalB : m->evalA).p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     } else if (what == 13) {  // the window depths the last draw's depth test compared, by record slot (what = 9 names a splat's slot)
         GS_REQUIRE(!m->projection_pending, "a gs_mesh_project is pending: the depths of the last draw are no longer current (draw first)");
-        GS_REQUIRE(m->last_pp.depth_mode != 0u && (size_t)count * 4 <= m->zrec.bytes && count <= m->max_count,
+        GS_REQUIRE(m->last_pp.depth_mode != 0u && (size_t)count * 4 <= ps.zrec.bytes && count <= m->max_count,
                    "the last draw had no destination depth (no depths were written) / count exceeds the mesh");
-        if (count) GS_HIP(hipMemcpyAsync(dst, m->zrec.p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+        if (count) GS_HIP(hipMemcpyAsync(dst, ps.zrec.p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
     } else GS_REQUIRE(false, "unknown debug selector");
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;
@@ -1325,7 +1270,7 @@ int gs_mesh_surface(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32
     }
     GS_TRY(gs_launch_surface(m, pp, x0, y0, width, height, threshold, ids_dev, depth_dev));
     // (the pass reads the record set the last draw read: the next vertex stage into that set, on ctx->aux, waits for it as well)
-    if (m->ctx->aux != st) GS_HIP(hipEventRecord(m->ev_done, st));
+    if (m->ctx->aux != st) GS_HIP(hipEventRecord(m->set().ev_done, st));
     if (ids_out_host) GS_HIP(hipMemcpyAsync(ids_out_host, ids_dev, plane, hipMemcpyDeviceToHost, st));
     if (depth_out_host) GS_HIP(hipMemcpyAsync(depth_out_host, depth_dev, plane, hipMemcpyDeviceToHost, st));
     if (ids_out_host || depth_out_host) GS_HIP(hipStreamSynchronize(st));

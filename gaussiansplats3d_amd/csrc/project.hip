@@ -599,16 +599,17 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
     mp.sh0 = m->sh0.as<uint4>(); mp.sh1 = m->sh1.p; mp.sh2 = m->sh2.as<uint4>();
     mp.scene_idx = m->scene_idx.as<uint32_t>();
     mp.scenes = m->scene_dev.as<gs_scene_params>();
+    ProjSet& ps = m->set();                                 // the set this vertex stage writes
     if (orig_mask == GS_ORIG_MASK_DERIVED) {
         // The bound sorter derives the mask: it writes (and, consuming it, clears) the words of the positions it sorts, and leaves
         // every word beyond them as it was.  A fresh buffer is zeroed here, on the stream the sorter waits for, so that a later
         // projection that skips the clear (vis_orig_dirty false) never ORs bits into garbage.
         bool fresh = false;
-        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
-        if (fresh) GS_HIP(hipMemsetAsync(m->vis_orig.p, 0, m->vis_orig.bytes, m->ctx->aux));
-        m->vis_orig_tail_zero = fresh || !m->vis_orig_dirty;  // every word the sorter will not write is zero
-        m->vis_orig_dirty = true;
-        m->vis_orig_count = pp.count;
+        GS_TRY(ps.vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
+        if (fresh) GS_HIP(hipMemsetAsync(ps.vis_orig.p, 0, ps.vis_orig.bytes, m->ctx->aux));
+        ps.vis_orig_tail_zero = fresh || !ps.vis_orig_dirty;  // every word the sorter will not write is zero
+        ps.vis_orig_dirty = true;
+        ps.vis_orig_count = pp.count;
     }
     if (pp.count == 0) {
         if (ev_before) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));
@@ -624,27 +625,27 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
     if (ev_before && whole_stage) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));
     if (pretest)
         hipLaunchKernelGGL(k_block_test, dim3((blocks + 31u) / 32u), dim3(256), 0, m->ctx->aux, pp, mp.block_box, blocks,
-                           m->vis_mask.as<unsigned long long>(), m->vis32.as<uint2>(), m->block_any.as<uint8_t>());
-    if (pp.depth_mode) GS_TRY(m->zrec.ensure((size_t)m->max_count * 4 + 16));
+                           ps.vis_mask.as<unsigned long long>(), ps.vis32.as<uint2>(), ps.block_any.as<uint8_t>());
+    if (pp.depth_mode) GS_TRY(ps.zrec.ensure((size_t)m->max_count * 4 + 16));
     uint32_t* vis_orig = nullptr;
     if (orig_mask == GS_ORIG_MASK_WRITE) {
         bool fresh = false;                             // (allocated just now: it holds nothing anybody wrote)
-        GS_TRY(m->vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
+        GS_TRY(ps.vis_orig.ensure(((size_t)m->max_count + 63) / 64 * 8 + 64, &fresh));
         // the visibility-culled sort that consumes the mask leaves it zeroed (k_mask_compact); only a mask nobody consumed
         // (two gs_mesh_project in a row, a sort over fewer splats) is cleared here
-        if (fresh || m->vis_orig_dirty)
-            GS_HIP(hipMemsetAsync(m->vis_orig.p, 0, ((size_t)m->max_count + 31) / 32 * 4, m->ctx->aux));
-        m->vis_orig_dirty = true;
-        m->vis_orig_count = pp.count;
-        vis_orig = m->vis_orig.as<uint32_t>();
+        if (fresh || ps.vis_orig_dirty)
+            GS_HIP(hipMemsetAsync(ps.vis_orig.p, 0, ((size_t)m->max_count + 31) / 32 * 4, m->ctx->aux));
+        ps.vis_orig_dirty = true;
+        ps.vis_orig_count = pp.count;
+        vis_orig = ps.vis_orig.as<uint32_t>();
     }
     const uint32_t* inv_perm = m->reorder ? m->inv_perm.as<uint32_t>() : nullptr;
     const bool ext = pp.sh_u8 || pp.scene_count > 1 ||
                      (pp.flags & (GS_CAM_ORTHOGRAPHIC | GS_CAM_FADE_IN | GS_CAM_SCENE_EFFECTS | GS_CAM_DYNAMIC));
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, m->ctx->aux, pp, mp, m->recs.as<SplatRec>(), m->rects.as<uint2>(),
-                           m->vis_mask.as<unsigned long long>(), m->vis32.as<uint2>(), vis_orig, inv_perm, m->block_any.as<uint8_t>(),
-                           m->prect.as<uint2>(), m->zrec.as<float>());
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, m->ctx->aux, pp, mp, ps.recs.as<SplatRec>(), ps.rects.as<uint2>(),
+                           ps.vis_mask.as<unsigned long long>(), ps.vis32.as<uint2>(), vis_orig, inv_perm, ps.block_any.as<uint8_t>(),
+                           ps.prect.as<uint2>(), ps.zrec.as<float>());
     };
     const bool depth = pp.depth_mode != 0u;
     if (ev_before && !whole_stage) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));

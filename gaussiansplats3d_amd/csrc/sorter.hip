@@ -1542,7 +1542,7 @@ static int sort_check(gs_sorter* s, SortCall& c, SortPlanIn& in) {
         const gs_camera& pc = mesh->projected_cam;
         const uint32_t rows_total = (pc.height + GS_TILE - 1u) / GS_TILE;
         in.mesh_strip = !(pc.tile_row_begin == 0u && (pc.tile_row_end == 0u || pc.tile_row_end >= rows_total));
-        in.mesh_lazy_mask = mesh->vis_orig_lazy;
+        in.mesh_lazy_mask = mesh->set().vis_orig_lazy;
     }
     c.unmap = c.map ? gs_mesh_payload_unmap(s->bound_mesh) : nullptr;
     in.mesh_map = c.map != nullptr;
@@ -1686,11 +1686,12 @@ static int launch_tree_front(gs_sorter* s, const SortCall& c, const SortPlan& pl
 static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan& pl, KeyParams& kp) {
     hipStream_t st = s->stream;
     gs_mesh* mesh = s->bound_mesh;
+    ProjSet& ps = mesh->set();                              // the set the pending gs_mesh_project wrote
     const uint32_t R = pl.R;
     const bool stream = pl.front == SORT_FRONT_VIS_STREAM, lazy = pl.vis_derive != 0u;
     GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
     GS_TRY(s->mask_copy.ensure(((size_t)s->max_count + 31) / 32 * 4 + 64));
-    uint32_t* mask = mesh->vis_orig.as<uint32_t>();
+    uint32_t* mask = ps.vis_orig.as<uint32_t>();
     // The projection left the by-original-index mask to us (gs_mesh_project of a full frame for a mesh whose bound sorter
     // culls by visibility): k_mask_derive_count builds it from the storage-order mask through the payload map.
     GS_REQUIRE(!lazy || c.map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
@@ -1700,7 +1701,7 @@ static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan
     uint32_t* counts = s->chunk_counts.as<uint32_t>();
     // (a forced compact front end derives the mask first as well: its counts are redone by k_minmax_count)
     if (lazy) hipLaunchKernelGGL(k_mask_derive_count, dim3(pl.derive_grid * VC_DERIVE_SUBS), dim3(VC_THREADS), 0, st, kp, c.map,
-                                 mesh->vis_mask.as<unsigned long long>(), mesh->block_any.as<uint8_t>(), (mesh->uploaded + 255u) >> 8,
+                                 ps.vis_mask.as<unsigned long long>(), ps.block_any.as<uint8_t>(), (mesh->uploaded + 255u) >> 8,
                                  pl.derive_len, VC_DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), counts);
     if (stream) {
         if (!lazy) hipLaunchKernelGGL(k_mask_count, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, pl.front_len, counts);
@@ -1715,7 +1716,7 @@ static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan
     }
     // the mask is all zero again if this sort covered every splat the vertex stage looked at - and, where it derived the
     // mask itself, if the words beyond the ones it wrote were zero already (gs_mesh_project)
-    if (R >= mesh->vis_orig_count && (!lazy || mesh->vis_orig_tail_zero)) mesh->vis_orig_dirty = false;
+    if (R >= ps.vis_orig_count && (!lazy || ps.vis_orig_tail_zero)) ps.vis_orig_dirty = false;
     kp.idx_in = s->idx_in.as<uint32_t>();
     kp.count_dev = &kp.frame->kept;
     kp.ext_minmax = 1u;

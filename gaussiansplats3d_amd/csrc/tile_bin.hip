@@ -570,6 +570,7 @@ template <class KeyT>
 static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t R, uint32_t tiles /* sort keys */) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream;
+    const ProjSet& ps = m->set();                           // the set this draw's vertex stage wrote
     const RadixExec ex = {st, &m->radix, ctx->lds_atomic_lane_order};
     RenderFrame* frame = m->frame.as<RenderFrame>();
     uint32_t grid = (R + BIN_THREADS - 1) / BIN_THREADS;
@@ -602,10 +603,10 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback&
     ++m->draw_serial;
     if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the mapped words carry the serial: 0 is "no draw yet", mesh_read_view_share)
     hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
-                       m->translate ? m->perm.as<uint32_t>() : nullptr, m->prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
+                       m->translate ? m->perm.as<uint32_t>() : nullptr, ps.prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
                        m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
                        m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
-                       m->block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
+                       ps.block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
     hipLaunchKernelGGL((k_bin_emit<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, frame, cap, m->cidx.as<uint32_t>(),
                        m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
                        m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,

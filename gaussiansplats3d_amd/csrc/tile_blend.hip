@@ -1340,16 +1340,17 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_tile_blend_rop8(FrameArgs fa,
 // destination as the kernels see it (pp.depth_mode was derived from the same fields: mesh_params)
 static FrameArgs frame_args(const gs_mesh* m, const ProjectParams& pp) {
     FrameArgs fa = {};
+    const ProjSet& ps = m->set();                          // the set the draw was binned from
     fa.ranges = m->tile_ranges.as<uint2>();
     fa.vals = (m->sorted_buf ? m->evalB : m->evalA).as<uint32_t>();
-    fa.recs = m->recs.as<uint4>();
-    fa.rects = m->rects.as<uint2>();
+    fa.recs = ps.recs.as<uint4>();
+    fa.rects = ps.rects.as<uint2>();
     fa.width = (uint32_t)pp.width; fa.height = (uint32_t)pp.height; fa.y0 = pp.y0; fa.y1 = pp.y1;
     fa.bins_x = pp.bins_x; fa.bin_row_begin = pp.bin_row_begin;
     // (list_shift counts 16-px tiles per list bin edge, as in the binner: a list bin is (16 << list_shift) px)
     fa.lists_x = pp.lists_x; fa.list_row_begin = pp.list_row_begin; fa.list_shift = pp.list_shift;
     fa.depth_mode = pp.depth_mode;
-    fa.zrec = pp.depth_mode ? m->zrec.as<float>() : nullptr;
+    fa.zrec = pp.depth_mode ? ps.zrec.as<float>() : nullptr;
     fa.dst_depth = pp.depth_mode ? m->dest_depth : nullptr;
     fa.dst_rgba = m->dest_rgba;
     return fa;
@@ -1366,7 +1367,7 @@ int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t
                       uint32_t* ids_dev, float* depth_dev) {
     const FrameArgs fa = frame_args(m, pp);
     SurfaceArgs sa = {};
-    sa.vis_mask = m->vis_mask.as<unsigned long long>();
+    sa.vis_mask = m->set().vis_mask.as<unsigned long long>();
     sa.inv_perm = m->reorder ? m->inv_perm.as<uint32_t>() : nullptr;
     sa.cx = m->px.as<float>(); sa.cy = m->py.as<float>(); sa.cz = m->pz.as<float>();
     sa.scene_idx = m->scene_idx.as<uint32_t>();

@@ -1,0 +1,102 @@
+// upload_plan.cpp — see upload_plan.hpp.  Host only.
+#include "upload_plan.hpp"
+
+#include <algorithm>
+
+const SlotRange* SlottedRanges::holding(uint32_t from, uint32_t count) const {
+    for (const SlotRange& r : r_)
+        if (r.begin <= from && (uint64_t)from + count <= r.end) return &r;   // ranges that touch are merged, so one must cover it
+    return nullptr;
+}
+
+std::vector<SlotCut> SlottedRanges::cut(uint32_t from, uint32_t end) const {
+    std::vector<SlotCut> cuts;
+    uint32_t pos = from;
+    for (const SlotRange& r : r_) {
+        if (pos >= end || r.begin >= end) break;
+        if (r.end <= pos) continue;
+        if (r.begin > pos) { cuts.push_back({pos, r.begin, true}); pos = r.begin; }
+        const uint32_t stop = std::min(r.end, end);
+        cuts.push_back({pos, stop, false});
+        pos = stop;
+    }
+    if (pos < end) cuts.push_back({pos, end, true});
+    return cuts;
+}
+
+void SlottedRanges::add(uint32_t from, uint32_t end) {
+    if (from >= end) return;
+    std::vector<SlotRange> merged;
+    SlotRange cur = {from, end};
+    bool placed = false;
+    for (const SlotRange& r : r_) {
+        if (r.end < cur.begin) merged.push_back(r);
+        else if (r.begin > cur.end) {                      // (sorted: so is every range after it - cur is final)
+            if (!placed) merged.push_back(cur);
+            placed = true;
+            merged.push_back(r);
+        } else {                                           // overlaps or touches: one range
+            cur.begin = std::min(cur.begin, r.begin);
+            cur.end = std::max(cur.end, r.end);
+        }
+    }
+    if (!placed) merged.push_back(cur);
+    r_.swap(merged);
+}
+
+std::vector<UploadSegment> plan_upload(const SlottedRanges& ranges, uint32_t from, uint32_t count, bool reorder) {
+    std::vector<UploadSegment> segs;
+    for (const SlotCut& c : ranges.cut(from, from + count)) {
+        UploadSegment s = {c.begin, c.end, c.fresh || !reorder, 0u, 0u};
+        uint32_t lo = c.begin, hi = c.end;
+        if (!s.fresh)
+            if (const SlotRange* r = ranges.holding(c.begin, c.end - c.begin)) { lo = r->begin; hi = r->end; }
+        s.b0 = lo / UPLOAD_BLOCK;
+        s.b1 = (hi + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK;
+        segs.push_back(s);
+    }
+    return segs;
+}
+
+UploadLayout upload_layout(uint32_t count, bool cov_half, bool mesh_sh_u8, uint32_t sh_degree, bool source_stages_sh_u8) {
+    UploadLayout l;
+    l.ncoef = (sh_degree == 0 || (mesh_sh_u8 && !source_stages_sh_u8)) ? 0 : (sh_degree == 1 ? 9 : 24);
+    l.sh_u8 = mesh_sh_u8 && l.ncoef != 0;
+    const size_t b_c = (size_t)count * 12, b_cov = (size_t)count * (cov_half ? 12 : 24), b_sh = (size_t)count * l.ncoef * (l.sh_u8 ? 1 : 2);
+    l.off_cov = (b_c + 255) & ~(size_t)255;
+    l.off_sh = (l.off_cov + b_cov + 255) & ~(size_t)255;
+    l.off_rgba = (l.off_sh + b_sh + 255) & ~(size_t)255;
+    l.bytes = l.off_sh + b_sh + 512 + (size_t)count * 4;
+    return l;
+}
+
+extern "C" int gs_debug_upload_plan(const gs_upload_plan_debug_in* in, gs_upload_plan_debug_out* out) {
+    if (!in || !out || in->n_ranges > UPLOAD_DEBUG_MAX || (uint64_t)in->from + in->count > UPLOAD_MAX_SPLATS) return -1;
+    SlottedRanges sl;
+    for (uint32_t k = 0; k < in->n_ranges; k++) {
+        if (in->ranges[k][0] >= in->ranges[k][1] || in->ranges[k][1] > UPLOAD_MAX_SPLATS) return -1;
+        sl.add(in->ranges[k][0], in->ranges[k][1]);
+    }
+    *out = gs_upload_plan_debug_out();
+    auto copy = [](const SlottedRanges& s, uint32_t* n, uint32_t (*rows)[2]) {
+        *n = (uint32_t)s.ranges().size();
+        for (uint32_t k = 0; k < *n; k++) { rows[k][0] = s.ranges()[k].begin; rows[k][1] = s.ranges()[k].end; }
+    };
+    copy(sl, &out->n_before, out->before);
+    if (const SlotRange* r = sl.holding(in->hold_from, in->hold_count)) { out->held = 1; out->hold_begin = r->begin; out->hold_end = r->end; }
+    const std::vector<UploadSegment> segs = plan_upload(sl, in->from, in->count, in->reorder != 0u);
+    if (segs.size() > UPLOAD_DEBUG_MAX) return -1;
+    out->n_segments = (uint32_t)segs.size();
+    for (uint32_t k = 0; k < out->n_segments; k++) {
+        const UploadSegment& s = segs[k];
+        const uint32_t row[5] = {s.begin, s.end, s.fresh ? 1u : 0u, s.b0, s.b1};
+        std::copy(row, row + 5, out->segments[k]);
+    }
+    sl.add(in->from, in->from + in->count);
+    if (sl.ranges().size() > UPLOAD_DEBUG_MAX) return -1;
+    copy(sl, &out->n_after, out->after);
+    const UploadLayout l = upload_layout(in->layout_count, in->cov_half != 0u, in->mesh_sh_u8 != 0u, in->sh_degree, in->source_stages_sh_u8 != 0u);
+    out->ncoef = l.ncoef; out->sh_u8 = l.sh_u8 ? 1u : 0u;
+    out->off_cov = l.off_cov; out->off_sh = l.off_sh; out->off_rgba = l.off_rgba; out->bytes = l.bytes;
+    return 0;
+}

@@ -1,0 +1,81 @@
+// upload_plan.hpp — the host policy of an upload into a mesh (mesh.hip, bounds.hip): which splats own storage slots, where one
+// upload is cut into fresh and non-fresh segments, which storage blocks get new boxes, and where a segment's arrays sit in the
+// staging buffer.  Host only: no HIP, no gs_mesh, no context.  tests/test_upload_plan.py holds it to a bitmap model through
+// gs_debug_upload_plan; tests/tools/upload_plan_fuzz.cpp is the stand-alone program for a sanitizer run.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+constexpr uint32_t UPLOAD_MAX_SPLATS = 1u << 28;           // gs_mesh_create's limit: spans of a plan end at or below it
+constexpr uint32_t UPLOAD_BLOCK = 256;                     // splats per storage block (gs_mesh::block_box)
+
+struct SlotRange { uint32_t begin, end; };                 // [begin, end)
+struct SlotCut { uint32_t begin, end; bool fresh; };       // fresh: none of its splats owns a slot; else all of them do
+
+// The splats that own storage slots (an upload has seen them): ranges that are non-empty, sorted by begin, disjoint and never
+// adjacent - ranges that touch are one range.  A fresh segment is stored in its own slots, so the splats of a range occupy
+// exactly the storage positions of that range.
+class SlottedRanges {
+public:
+    // the one range that contains [from, from + count) whole (summed in 64 bits), or nullptr
+    const SlotRange* holding(uint32_t from, uint32_t count) const;
+    // [from, end) as consecutive segments, cut at the ranges' borders
+    std::vector<SlotCut> cut(uint32_t from, uint32_t end) const;
+    // merges [from, end) in
+    void add(uint32_t from, uint32_t end);
+    const std::vector<SlotRange>& ranges() const { return r_; }
+private:
+    std::vector<SlotRange> r_;
+};
+
+// One segment of an upload: splats [begin, end), and the storage blocks [b0, b1) whose boxes it invalidates.  A fresh segment
+// receives the slots [begin, end).  Splats uploaded before keep THEIR slots, scattered over the Morton run(s) of the earlier
+// upload(s) - anywhere inside the range that held the segment before this upload: all of that range's blocks are redone.
+// (only the segment's own span was redone, so a block kept the box of the data it held before the edit and k_project's
+// block cull could drop splats that had moved into view.)
+struct UploadSegment {
+    uint32_t begin, end;
+    bool fresh;                    // the cut's verdict; always true on a mesh that keeps upload order
+    uint32_t b0, b1;
+};
+// the segments of an upload of [from, from + count), from + count <= UPLOAD_MAX_SPLATS, in order; `ranges` as they are BEFORE it
+std::vector<UploadSegment> plan_upload(const SlottedRanges& ranges, uint32_t from, uint32_t count, bool reorder);
+
+// Where a segment's arrays sit in the staging buffer: centres float [3n] at 0 | covariance float [6n] or half bits [6n] | SH half
+// bits or uint8 [ncoef n] | rgba uint8 [4n]; every plane starts on a multiple of 256 bytes.  The decode kernels of
+// asset_decode.hip write the same planes.
+struct UploadLayout {
+    uint32_t ncoef;                // SH values per splat the source stages (0: none)
+    bool sh_u8;                    // ... as uint8 (a GS_MESH_SH_U8 mesh whose source stages them), else half bits
+    size_t off_cov, off_sh, off_rgba;
+    size_t bytes;                  // the staging buffer holds at least this much
+};
+// source_stages_sh_u8: the source stages the uint8 SH of a GS_MESH_SH_U8 mesh too (the host path hands those to
+// gs_mesh_upload_sh_u8 instead)
+UploadLayout upload_layout(uint32_t count, bool cov_half, bool mesh_sh_u8, uint32_t sh_degree, bool source_stages_sh_u8);
+
+// ---------------------------------------------------------------------------------------------------
+// Debug entry for the tests (pure host; typed by tests/upload_plan_cases.py, not in the public header).  Flags are uint32 (0 / 1).
+constexpr uint32_t UPLOAD_DEBUG_MAX = 64;                  // ranges in, ranges out, segments
+struct gs_upload_plan_debug_in {
+    uint32_t n_ranges;                                     // the state before the upload: add()ed in this order
+    uint32_t ranges[UPLOAD_DEBUG_MAX][2];
+    uint32_t from, count, reorder;                         // the upload
+    uint32_t hold_from, hold_count;                        // holding(), asked before the upload
+    uint32_t layout_count, cov_half, mesh_sh_u8, sh_degree, source_stages_sh_u8;
+};
+struct gs_upload_plan_debug_out {
+    uint32_t n_segments;
+    uint32_t segments[UPLOAD_DEBUG_MAX][5];                // begin, end, fresh, b0, b1
+    uint32_t n_before;                                     // the ranges the inputs made
+    uint32_t before[UPLOAD_DEBUG_MAX][2];
+    uint32_t n_after;                                      // ... and after add(from, from + count)
+    uint32_t after[UPLOAD_DEBUG_MAX][2];
+    uint32_t held, hold_begin, hold_end;
+    uint32_t ncoef, sh_u8;
+    uint64_t off_cov, off_sh, off_rgba, bytes;
+};
+// 0; -1 on a NULL argument, an empty or reversed input range, a span beyond UPLOAD_MAX_SPLATS or more than UPLOAD_DEBUG_MAX rows
+extern "C" int gs_debug_upload_plan(const gs_upload_plan_debug_in* in, gs_upload_plan_debug_out* out);
