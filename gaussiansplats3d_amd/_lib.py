@@ -92,6 +92,12 @@ class Bounds(C.Structure):
     _fields_ = [("count", C.c_uint64), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("max_dist_sq", C.c_double)]
 
 
+class KsplatParams(C.Structure):
+    """gs_ksplat_params: what gs_asset_encode_ksplat writes."""
+    _fields_ = [("compression_level", C.c_uint32), ("min_alpha", C.c_uint32), ("bucket_size", C.c_uint32),
+                ("block_size", C.c_float), ("scene_center", C.c_float * 3), ("flags", C.c_uint32)]
+
+
 GS_BOUNDS_TRANSFORM = 1
 GS_ASSET_PLY, GS_ASSET_KSPLAT, GS_ASSET_SPLAT, GS_ASSET_SPZ = 1, 2, 3, 4
 
@@ -122,6 +128,8 @@ SYMBOLS = {
     "gs_asset_get_info": (C.c_int, [_VP, C.POINTER(AssetInfo)]),
     "gs_asset_set_transform": (C.c_int, [_VP, _VP]),
     "gs_asset_fill": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gs_asset_encode_ksplat": (C.c_int, [_VP, _VP, C.POINTER(KsplatParams), C.POINTER(_VP), _VP]),
+    "gs_asset_bytes": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     "gs_mesh_upload_asset": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     "gs_sorter_upload_asset_centers": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),
     "gs_tree_create": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),

@@ -93,6 +93,29 @@ class SplatAsset:
                                                         scene.ctypes.data if scene is not None else None))
         sorter.uploaded_splat_count = max(sorter.uploaded_splat_count, int(frm) + int(count))
 
+    def encode_ksplat(self, ctx, compression_level=1, minimum_alpha=1, block_size=5.0, bucket_size=256, scene_center=(0, 0, 0)):
+        """This asset as a one-section .ksplat, encoded on the device (gs_asset_encode_ksplat): byte for byte what
+        ``SplatBuffer.generateFromUncompressedSplatArrays`` returns for the asset's level-0 rows in file order
+        (/root/reference/src/loaders/SplatBuffer.js:1177-1326; util/create-ksplat.js without its partitioner).  Returns
+        ``(SplatAsset, order)``: the opened result (``to_bytes()`` is the file) and, per output position, the index of the
+        source splat stored there."""
+        p = L.KsplatParams(int(compression_level), int(minimum_alpha), int(bucket_size), float(block_size),
+                           (C.c_float * 3)(*[float(v) for v in scene_center]), 0)
+        order = np.empty(self.info.splat_count, np.uint32)
+        handle = C.c_void_p()
+        L.check(self.lib.gs_asset_encode_ksplat(ctx.handle if ctx is not None else None, self.handle, C.byref(p), C.byref(handle),
+                                                order.ctypes.data))
+        out = SplatAsset.__new__(SplatAsset)
+        out.lib, out.handle, out.info = self.lib, handle, L.AssetInfo()
+        L.check(self.lib.gs_asset_get_info(handle, C.byref(out.info)))
+        return out, order[:out.info.splat_count].copy()
+
+    def to_bytes(self):
+        """The file image of an ``encode_ksplat`` result (gs_asset_bytes)."""
+        data, size = C.c_void_p(), C.c_uint64()
+        L.check(self.lib.gs_asset_bytes(self.handle, C.byref(data), C.byref(size)))
+        return C.string_at(data, size.value)
+
     def close(self):
         if self.handle:
             self.lib.gs_asset_close(self.handle)

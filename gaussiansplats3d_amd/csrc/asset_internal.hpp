@@ -644,6 +644,7 @@ struct gs_asset {
     std::vector<uint32_t> partial_end;     // ... and the partial bucket ends of all of them
     bool has_transform = false;            // gs_asset_set_transform
     AssetTransform xf = {};
+    bool encoded = false;                  // `buf` is a file image gs_asset_encode_ksplat made (gs_asset_bytes hands it out)
 
     template <class T>
     T rd(size_t off) const {

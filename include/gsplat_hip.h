@@ -293,6 +293,47 @@ int gs_asset_set_transform(gs_asset* a, const double* transform16);
 int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba,
                   uint16_t* sh_f16, uint8_t* sh_u8, float* scales, float* rotations);
 
+/* The reference's offline conversion (util/create-ksplat.js, KSplatLoader.downloadFile) on the device: an opened asset ->
+ * a one-section .ksplat at compression level 0, 1 or 2.  The file is byte for byte what
+ * SplatBuffer.generateFromUncompressedSplatArrays([rows], min_alpha, compression_level, scene_center, block_size,
+ * bucket_size) returns (src/loaders/SplatBuffer.js:1177-1326), `rows` holding the values of the source's LEVEL-0 ROWS in file
+ * order: three fp32 centres, three fp32 scales, the four rotation floats in slot order, the colour bytes and the fp32 SH of
+ * the opened degree.  One section, file order, no SplatPartitioner (its sort's tie order is the engine's, not the format's).
+ *   dropped          alpha < min_alpha (:1219); the kept splats keep file order
+ *   SH range         scanned over ALL rows, dropped ones too, components FRC0..FRC22 only (:1193: the 24th never takes part),
+ *                    by `!m || v < m` (:1194-1199: a running 0 or NaN is replaced by whatever comes next), `|| -1.5` / `|| 1.5`
+ *                    at the end (:1204-1205); written into the header at every level, used by toUint8 at level 2
+ *   bucket ids       computeBucketsForUncompressedSplatArray (:1328-1399): exact min / max of the kept centres, y/zBlocks =
+ *                    ceil(dim / block_size), xBlock = floor((c - min) / block_size) as an IEEE fp64 subtraction and division,
+ *                    id = xBlock * (yBlocks * zBlocks) + yBlock * zBlocks + zBlock; a centre on the far face shares an id
+ *   buckets          a bucket's centre is the block centre of the splat that opened it (:1365-1375); it closes at bucket_size
+ *                    splats and the id opens a new one (:1379-1382); full buckets in closing order, then the open ones in
+ *                    ascending id order (:1386); rows are written bucket by bucket at level 0 too (:1245-1257)
+ *   rows             writeSplatDataToSectionBuffer (:1075-1173): the quaternion normalised again in double, `|| 0` on scale
+ *                    and SH, level-1/2 centres clamp(Math.round(delta * (32767 / (block_size * 0.5))) + 32767, 0, 65535)
+ *                    against the double bucket centre, halves by THREE.DataUtils.toHalfFloat, level-2 SH by toUint8
+ *   headers          writeHeaderToBuffer (:856-875), writeSectionHeaderToBuffer (:944-960): a level-0 section header carries 0
+ *                    for bucket size, bucket count, block size and scale range
+ * Only the source's file rows cross to the device; the bucket bookkeeping runs there as a stable sort by id.
+ * Refused with nothing produced, the parameter checks before the device is touched: GS_ERR_INVALID for a level outside 0..2,
+ * unknown flags, a block_size that is negative or not finite, a bucket_size above 65535 (0 selects the reference's default in
+ * both, as its `||` does), a source with a scene transform, no splat surviving min_alpha, a kept centre that is not finite (its
+ * id would be the property name "NaN"); GS_ERR_UNSUPPORTED for a source of compression_level 1 or 2 (its values are
+ * quantised already) and for a scene of 2^32 - 1 or more blocks (JavaScript's key order stops being numeric there). */
+typedef struct gs_ksplat_params {
+    uint32_t compression_level;   /* 0, 1, 2                                                                      */
+    uint32_t min_alpha;           /* alphaRemovalThreshold                                                        */
+    uint32_t bucket_size;         /* 0 = 256 (SplatBuffer.BucketSize)                                             */
+    float    block_size;          /* 0 = 5.0 (SplatBuffer.BucketBlockSize)                                        */
+    float    scene_center[3];
+    uint32_t flags;               /* 0                                                                            */
+} gs_ksplat_params;
+/* out: a new GS_ASSET_KSPLAT asset that owns the encoded bytes, exactly as gs_asset_open of those bytes would be (close it
+ * with gs_asset_close); order_out_host: uint32 per kept splat, the source index stored at each output position, or NULL */
+int gs_asset_encode_ksplat(gs_context* ctx, gs_asset* src, const gs_ksplat_params* p, gs_asset** out, uint32_t* order_out_host);
+/* The file image of an encoder result (valid until gs_asset_close); GS_ERR_INVALID for other assets */
+int gs_asset_bytes(gs_asset* a, const void** data, uint64_t* bytes);
+
 /* ------------------------------------------------------------------------------------------------ *
  * RENDER SEAM
  * ------------------------------------------------------------------------------------------------ */

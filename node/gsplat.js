@@ -408,4 +408,19 @@ const assetFormatOf = (fileName, bytes) => {
   if (/\.spz$/i.test(fileName) || (bytes[0] === 0x1f && bytes[1] === 0x8b)) return AssetFormat.spz;
   return bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? AssetFormat.ply : AssetFormat.ksplat;      // "ply"
 };
-module.exports = { createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon, multiply4, invert4 };
+// util/create-ksplat.js's conversion on the device (gs_asset_encode_ksplat): asset = { bytes, format (AssetFormat; default: from the
+// bytes), sphericalHarmonicsDegree (the degree the file is read at) }; options named as the tool's: compressionLevel (0),
+// splatAlphaRemovalThreshold (1), sceneCenter ([0, 0, 0]), blockSize (5.0), bucketSize (256), outSphericalHarmonicsDegree (the
+// asset's, else 0 as the tool's).
+// Returns the file as a Buffer: one section, file order, no SplatPartitioner.
+function encodeKsplat(asset, options = {}) {
+  const bytes = asset.bytes || asset;
+  const format = asset.format || assetFormatOf(asset.fileName || '', bytes);
+  const or = (v, d) => (v === undefined || v === null ? d : v);
+  const c = or(options.sceneCenter, [0, 0, 0]);
+  const centre = Array.isArray(c) ? c : [c.x, c.y, c.z];
+  return addon.assetEncodeKsplat(getContext(options.device).handle, bytes, format, or(options.outSphericalHarmonicsDegree, or(asset.sphericalHarmonicsDegree, 0)),
+                                 or(options.compressionLevel, 0), or(options.splatAlphaRemovalThreshold, 1), or(options.bucketSize, 256),
+                                 or(options.blockSize, 5.0), +centre[0], +centre[1], +centre[2]);
+}
+module.exports = { encodeKsplat, createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon, multiply4, invert4 };

@@ -865,6 +865,39 @@ static napi_value upload_asset(napi_env env, napi_callback_info info, int to_sor
 static napi_value MeshUploadAsset(napi_env env, napi_callback_info info) { return upload_asset(env, info, 0); }
 static napi_value SorterUploadAssetCenters(napi_env env, napi_callback_info info) { return upload_asset(env, info, 1); }
 
+/* assetEncodeKsplat(ctx, bytes, format, maxShDegree, compressionLevel, minAlpha, bucketSize, blockSize, cx, cy, cz) -> Buffer
+ * gs_asset_encode_ksplat of the opened bytes: the .ksplat the reference's generateFromUncompressedSplatArrays writes for the file's
+ * level-0 rows, encoded on the device; the Buffer is a copy of gs_asset_bytes. */
+static napi_value AssetEncodeKsplat(napi_env env, napi_callback_info info) {
+    ARGS(11)
+    void* data;
+    size_t nb;
+    if (!get_bytes(env, argv[1], &data, &nb) || !data) { napi_throw_type_error(env, NULL, "assetEncodeKsplat: bytes"); return NULL; }
+    gs_asset *a = NULL, *made = NULL;
+    int st;
+    LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[2]), get_u32(env, argv[3]), &a));
+    if (st < 0) return throw_gs(env, st);
+    gs_ksplat_params p;
+    memset(&p, 0, sizeof p);
+    p.compression_level = get_u32(env, argv[4]);
+    p.min_alpha = get_u32(env, argv[5]);
+    p.bucket_size = get_u32(env, argv[6]);
+    p.block_size = (float)get_f64(env, argv[7]);
+    for (int k = 0; k < 3; k++) p.scene_center[k] = (float)get_f64(env, argv[8 + k]);
+    LOCKED(st = gs_asset_encode_ksplat((gs_context*)get_external(env, argv[0]), a, &p, &made, NULL));
+    LOCKED(gs_asset_close(a));
+    if (st < 0) return throw_gs(env, st);
+    const void* image = NULL;
+    uint64_t size = 0;
+    napi_value r = NULL;
+    st = gs_asset_bytes(made, &image, &size);
+    napi_status ns = st < 0 ? napi_ok : napi_create_buffer_copy(env, (size_t)size, image, NULL, &r);
+    LOCKED(gs_asset_close(made));
+    if (st < 0) return throw_gs(env, st);
+    NAPI_OK(ns);
+    return r;
+}
+
 /* meshSetDestination(mesh, depth Float32Array(W*H)|null, rgba Uint8Array(4*W*H)|null, width, height, flags): what the following
  * draws are depth-tested against and blended over (gs_mesh_set_destination; SplatMaterial3D.js:72-73, src/Viewer.js:1610-1616,
  * src/DropInViewer.js:34-42).  Both null: back to a cleared target without a depth test. */
@@ -953,7 +986,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"meshUploadSceneIndexes", MeshUploadSceneIndexes},                   {"meshSetScenes", MeshSetScenes},
         {"sorterBindMesh", SorterBindMesh}, {"sorterSetFrustumCull", SorterSetFrustumCull}, {"sorterSortGathered", SorterSortGathered},
         {"treeCreate", TreeCreate},         {"treeDestroy", TreeDestroy},     {"treeInfo", TreeInfo},
-        {"treeGather", TreeGather},         {"treeRead", TreeRead},         {"assetLoad", AssetLoad},
+        {"treeGather", TreeGather},         {"treeRead", TreeRead},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
