@@ -1,6 +1,8 @@
 // draw_plan.cpp — see draw_plan.hpp.  Host arithmetic only; the comments that carry a measurement stand next to the rule it chose.
 #include "draw_plan.hpp"
 
+#include "bin_word.hpp"
+
 #include <math.h>
 #include <string.h>
 
@@ -56,6 +58,10 @@ int block_test_mode(uint32_t measured_visible, uint32_t measured_count, bool str
     const bool test = block_cull && (!all_live || strip || block_test_always);
     const bool pretest = test && !no_block_list && (!half_live || strip || block_test_always);
     return pretest ? 1 : (test ? 0 : 2);
+}
+
+bool narrow_bin_word(uint32_t tiles_x, uint32_t tiles_y, const DrawSwitches& sw) {
+    return tiles_x <= BIN_WORD_NARROW_TILES && tiles_y <= BIN_WORD_NARROW_TILES && !sw.no_compact_bin_word;
 }
 
 SchedulePlan plan_schedule(const ScheduleInputs& in) {
@@ -231,5 +237,24 @@ extern "C" int gs_debug_draw_plan(const gs_draw_plan_debug_in* in, gs_draw_plan_
     out->list_shift = adapt_list_shift(in->list_current, in->tiles16, in->visible);
     out->block_test = block_test_mode(in->measured_visible, in->measured_count, in->strip != 0u, in->block_cull != 0u, in->no_block_list != 0u,
                                       in->block_test_always != 0u);
+    return 0;
+}
+
+extern "C" int gs_debug_bin_word(const gs_bin_word_debug_in* in, gs_bin_word_debug_out* out) {
+    if (!in || !out) return -1;
+    DrawSwitches sw = {};
+    sw.no_compact_bin_word = in->no_compact_bin_word != 0u;
+    *out = gs_bin_word_debug_out();
+    out->narrow = narrow_bin_word(in->tiles_x, in->tiles_y, sw) ? 1u : 0u;
+    const BinRect r = {in->x0 | (in->y0 << 16), in->x1 | (in->y1 << 16)};
+    out->word = bin_word_pack_narrow(in->visible != 0u, in->slot, r);
+    const BinWordOut n = bin_word_unpack_narrow(out->word);
+    out->visible = n.visible; out->escape = n.escape; out->slot = n.slot;
+    if (n.visible && !n.escape) { out->x0 = n.rect.lo & 0xFFFFu; out->y0 = n.rect.lo >> 16; out->x1 = n.rect.hi & 0xFFFFu; out->y1 = n.rect.hi >> 16; }
+    const BinWordWide w = bin_word_pack_wide(in->visible != 0u, in->slot, r);
+    out->wide_lo = w.x; out->wide_hi = w.y;
+    const BinWordOut u = bin_word_unpack_wide(w);
+    out->wide_visible = u.visible; out->wide_slot = u.slot;
+    out->wide_x0 = u.rect.lo & 0xFFFFu; out->wide_y0 = u.rect.lo >> 16; out->wide_x1 = u.rect.hi & 0xFFFFu; out->wide_y1 = u.rect.hi >> 16;
     return 0;
 }

@@ -85,6 +85,7 @@ struct DrawSwitches {
     bool deep_row_major_on_motion; // $GSPLAT_DEEP_ROW_MAJOR_ON_MOTION: a deep-pass draw of a moved camera drops the order as well
     bool no_async_list_bins;       // $GSPLAT_NO_ASYNC_LIST_BINS: the list-bin size follows statistics reads only, not the mapped words
     bool deep_units_last;          // $GSPLAT_DEEP_UNITS_LAST: the deep pass's workgroups behind every bin, all of them
+    bool no_compact_bin_word;      // $GSPLAT_NO_COMPACT_BIN_WORD: the binner's look-up word is the 8-byte one on every frame
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -102,6 +103,10 @@ inline uint64_t entry_room(uint64_t need) { return need + need / 8 + 1024; }
 // measured_visible / measured_count: of the mesh's last measured full-frame draw (count 0: nothing measured); strip: this draw
 // covers only some tile rows; block_cull: ProjectParams::block_cull; the two switches: $GSPLAT_NO_BLOCK_LIST, $GSPLAT_BLOCK_TEST_ALWAYS.
 int block_test_mode(uint32_t measured_visible, uint32_t measured_count, bool strip, bool block_cull, bool no_block_list, bool block_test_always);
+
+// Which look-up word (bin_word.hpp) the vertex stage leaves for the binner: the 4-byte one where its origin fields hold every tile
+// of the frame, the 8-byte one beyond 256 tiles in either direction (an 8K frame) and under $GSPLAT_NO_COMPACT_BIN_WORD.
+bool narrow_bin_word(uint32_t tiles_x, uint32_t tiles_y, const DrawSwitches& sw);
 
 // ---------------------------------------------------------------------------------------------------
 // the blend schedule and the deep pass
@@ -185,3 +190,18 @@ struct gs_draw_plan_debug_out {
     int32_t block_test;
 };
 extern "C" int gs_debug_draw_plan(const gs_draw_plan_debug_in* in, gs_draw_plan_debug_out* out);   // 0, or -1 on a NULL argument
+
+// ... and for tests/test_bin_word.py: the word policy, and one splat position through both words of bin_word.hpp, packed and
+// unpacked on the host by the functions the kernels use.  Rect coordinates are 16-px tiles, inclusive.
+struct gs_bin_word_debug_in {
+    uint32_t tiles_x, tiles_y, no_compact_bin_word;   // narrow_bin_word
+    uint32_t visible, slot, x0, y0, x1, y1;           // the position: slot = its record's slot in the 256-splat block
+};
+struct gs_bin_word_debug_out {
+    uint32_t narrow;                                   // 1: a draw of tiles_x x tiles_y tiles uses the 4-byte word
+    uint32_t word;                                     // the 4-byte word ...
+    uint32_t visible, escape, slot, x0, y0, x1, y1;    // ... unpacked (escape: the rect is not in the word, x0 .. y1 are 0)
+    uint32_t wide_lo, wide_hi;                         // the 8-byte word ...
+    uint32_t wide_visible, wide_slot, wide_x0, wide_y0, wide_x1, wide_y1;   // ... unpacked
+};
+extern "C" int gs_debug_bin_word(const gs_bin_word_debug_in* in, gs_bin_word_debug_out* out);   // 0, or -1 on a NULL argument

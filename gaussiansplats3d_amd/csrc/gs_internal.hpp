@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
+#include "bin_word.hpp"
 #include "draw_plan.hpp"
 #include "sort_plan.hpp"
 #include "upload_plan.hpp"
@@ -422,8 +423,10 @@ struct ProjSet {
     DevBuf vis_mask;           // uint64 [4*ceil(n/256)]  1 = splat survived the vertex stage and touches a pixel
     DevBuf block_any;          // uint8 [ceil(n/256)]      1 = some splat of the 256-splat block survived the vertex stage
     DevBuf vis32;              // uint2 [8*ceil(n/256)]   {the same mask per 32 splats, slot of its first visible splat}
-    DevBuf prect;              // uint2 [n]: per splat POSITION of a live block {x0:12|y0:12|slot in block:8, x1:12|y1:12|visible:1}:
-                               //            the binner's one gather per sorted index (project.hip)
+    DevBuf prect;              // [n] words of bin_word.hpp (room for 8 bytes each), per splat POSITION of a live block: {visible, slot in
+                               //            block, tile rect}, the binner's one gather per sorted index (project.hip) ...
+    bool narrow_word = false;  // ... 4-byte words (else 8-byte ones): what the vertex stage that last wrote this set chose
+                               //            (draw_plan.cpp, narrow_bin_word); a narrow word's escape reads `rects` of THIS set
     DevBuf vis_orig;           // uint32 [ceil(n/32)]     the mask by ORIGINAL splat index (gs_mesh_project only: feeds the
                                //                         visibility-culled sort)
     hipEvent_t ev_done = nullptr;         // end of the last draw that read this set (on ctx->stream)

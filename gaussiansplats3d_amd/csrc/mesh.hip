@@ -257,6 +257,7 @@ DrawSwitches draw_switches() {
     sw.deep_row_major_on_motion = getenv("GSPLAT_DEEP_ROW_MAJOR_ON_MOTION") != nullptr;
     sw.no_async_list_bins = getenv("GSPLAT_NO_ASYNC_LIST_BINS") != nullptr;
     sw.deep_units_last = getenv("GSPLAT_DEEP_UNITS_LAST") != nullptr;
+    sw.no_compact_bin_word = getenv("GSPLAT_NO_COMPACT_BIN_WORD") != nullptr;
     return sw;
 }
 
@@ -307,7 +308,8 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     m->two_sets = ctx->aux != ctx->stream && !getenv("GSPLAT_ONE_RECORD_SET");
     for (int k = 0; k < (m->two_sets ? 2 : 1); k++) {      // (zrec and vis_orig: by the first vertex stage that writes them)
         ProjSet& ps = m->sets[k];
-        A(ps.recs, n * sizeof(SplatRec)); A(ps.rects, n * 8);
+        A(ps.recs, n * sizeof(SplatRec));
+        A(ps.rects, ((n + 255) / 256) * 256 * 8);      // whole blocks: whatever slot a 4-byte look-up word's escape names is inside (bin_word.hpp)
         A(ps.vis_mask, ((n + 255) / 256) * 32 + 32);   // whole 256-splat blocks: 4 words each
         A(ps.vis32, ((n + 255) / 256) * 64 + 64);
         A(ps.prect, ((n + 255) / 256) * 256 * 8 + 64);
@@ -737,13 +739,14 @@ static int mesh_collect_stats(gs_mesh* m, gs_render_stats* stats) {
 // The vertex stage of a draw.  It only depends on the scene and the camera, so it runs on ctx->aux next to whatever the
 // caller-visible stream and the sorter's stream are doing; it may start once the previous draw has consumed the records /
 // rects / mask it is about to overwrite.
-static int mesh_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, bool timed) {
+static int mesh_project(gs_mesh* m, const DrawSwitches& sw, const ProjectParams& pp, int orig_mask, bool timed) {
     gs_context* ctx = m->ctx;
     hipStream_t st = ctx->stream, aux = ctx->aux;
     if (timed) GS_HIP(hipEventRecord(m->ev[0], st));
     // the set this vertex stage writes: the one the draw BEFORE the last read (two sets), else the last draw's own
     if (m->two_sets) m->cur_set ^= 1u;
     if (aux != st && m->set().drawn) GS_HIP(hipStreamWaitEvent(aux, m->set().ev_done, 0));
+    m->set().narrow_word = narrow_bin_word(pp.tiles_x, pp.tiles_y, sw);      // the binner reads the set the way it was written
     const bool sample = timed || aux != st || (ctx->kernel_sample && m->project_serial++ % ctx->kernel_sample == 0);
     if (sample) {   // next slot of the timing ring; a slot about to be reused is harvested first (skipped if still in flight)
         const uint32_t slot = m->ring_next++ % gs_mesh::TIMING_RING;
@@ -775,7 +778,7 @@ static int mesh_draw_once(gs_mesh* m, const DrawSwitches& sw, const ProjectParam
     m->timed_draw = timed;
     const uint32_t tiles = pp.lists_x * (pp.list_row_end - pp.list_row_begin);  // one entry list per list bin
     GS_TRY(m->tile_ranges.ensure((size_t)tiles * 8 + 16));
-    if (!projected) GS_TRY(mesh_project(m, pp, GS_ORIG_MASK_NONE, timed));   // else gs_mesh_project already ran it for this camera
+    if (!projected) GS_TRY(mesh_project(m, sw, pp, GS_ORIG_MASK_NONE, timed));   // else gs_mesh_project already ran it for this camera
     else if (timed) GS_HIP(hipEventRecord(m->ev[0], st));
     // join: projection and (if a sorter feeds this draw) the sort result
     if (aux != st) GS_HIP(hipStreamWaitEvent(st, m->ev_p1, 0));
@@ -936,8 +939,9 @@ int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
     ScopedDevice sd(m->ctx->device);
     // + the per-splat mask a visibility-culled sort reads: written here by one atomic per survivor - or, for a full frame whose
     // consumer is a bound sorter that holds the mesh's position map, left to that sorter (k_mask_derive_count: 25 us of a C3 frame)
-    const bool lazy = m->derive_orig_mask && m->reorder && !draw_switches().no_lazy_mask && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
-    GS_TRY(mesh_project(m, pp, lazy ? GS_ORIG_MASK_DERIVED : GS_ORIG_MASK_WRITE, m->ctx->stage_events));
+    const DrawSwitches sw = draw_switches();
+    const bool lazy = m->derive_orig_mask && m->reorder && !sw.no_lazy_mask && pp.row_begin == 0u && pp.row_end >= pp.tiles_y && pp.count == m->uploaded;
+    GS_TRY(mesh_project(m, sw, pp, lazy ? GS_ORIG_MASK_DERIVED : GS_ORIG_MASK_WRITE, m->ctx->stage_events));
     m->set().vis_orig_lazy = lazy;
     m->projection_pending = true;
     m->projected_cam = *cam;
@@ -1166,6 +1170,11 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_REQUIRE(m->last_pp.depth_mode != 0u && (size_t)count * 4 <= ps.zrec.bytes && count <= m->max_count,
                    "the last draw had no destination depth (no depths were written) / count exceeds the mesh");
         if (count) GS_HIP(hipMemcpyAsync(dst, ps.zrec.p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    } else if (what == 14) {  // which look-up word (bin_word.hpp) the last draw's vertex stage wrote and its binner read: 1 = 4 bytes, 0 = 8
+        GS_REQUIRE(count == 1, "count == 1");
+        GS_REQUIRE(!m->projection_pending, "a gs_mesh_project is pending: the current record set is no longer the last draw's (draw first)");
+        *static_cast<uint32_t*>(dst) = ps.narrow_word ? 1u : 0u;
+        return GS_OK;
     } else GS_REQUIRE(false, "unknown debug selector");
     GS_HIP(hipStreamSynchronize(st));
     return GS_OK;

@@ -204,12 +204,13 @@ __device__ __forceinline__ void sh_colour(const ProjectParams& pp, const MeshPla
 // DEPTH: a destination depth is set (gs_mesh_set_destination) and the blend wants every survivor's window depth - a compile-time
 // switch, because one more pointer and two more uniforms pushed the plain kernel over its scalar-register budget (106 SGPRs, 24
 // spilled: the all-visible C4 launch went 250 -> 278 us, r05m).
-template <bool EXT, bool TEST, bool DEPTH>
+// NARROW: the binner's look-up word is the 4-byte one (bin_word.hpp; the draw's choice, draw_plan.cpp narrow_bin_word).
+template <bool EXT, bool TEST, bool DEPTH, bool NARROW>
 __device__ __forceinline__ void project_block(const ProjectParams& pp, const MeshPlanes& mp, const uint32_t blk, SplatRec* __restrict__ recs,
                                               uint2* __restrict__ rects, unsigned long long* __restrict__ vis_mask,
                                               uint2* __restrict__ vis32, uint32_t* __restrict__ vis_orig,
                                               const uint32_t* __restrict__ inv_perm, uint8_t* __restrict__ block_any,
-                                              uint2* __restrict__ prect, float* __restrict__ zrec) {
+                                              void* __restrict__ prect, float* __restrict__ zrec) {
     const uint32_t i = blk * 256u + threadIdx.x;
     // Block-level cull.  Storage order is Morton order, so a block of 256 splats is a small box in space; its eight corners
     // (one lane each, wave 0) decide whether EVERY splat inside must fail the vertex stage - then nothing of the block is
@@ -535,15 +536,21 @@ __device__ __forceinline__ void project_block(const ProjectParams& pp, const Mes
         const uint32_t lo = (uint32_t)vis, hi = (uint32_t)(vis >> 32);
         vis32[i >> 5] = lane == 0u ? make_uint2(lo, wave_base) : make_uint2(hi, wave_base + (uint32_t)__popc(lo));
     }
-    // The binner's look-up, one 8-byte word per splat POSITION of a live block: {x0:12 | y0:12 | slot in the block:8,
-    // x1:12 | y1:12 | visible:1} - visibility, record slot and tile rect in ONE gather per sorted index (r02: a visibility word
-    // and then the rect, two dependent 64-byte sectors per visible splat: 2.2 GB of the 6.0 GB a C4 frame moved).  Dead blocks
-    // write nothing: the binner never looks past their block_any byte.
+    // The binner's look-up, one word per splat POSITION of a live block (bin_word.hpp: 4 bytes on frames of <= 256 x 256 tiles, 8
+    // beyond): visibility, record slot and tile rect in ONE gather per sorted index (r02: a visibility word and then the rect, two
+    // dependent 64-byte sectors per visible splat: 2.2 GB of the 6.0 GB a C4 frame moved).  A rect the 4-byte word cannot hold is
+    // read from `rects` below, by the slot.  Dead blocks write nothing: the binner never looks past their block_any byte.
     {
         const uint32_t slot = wave_base + (uint32_t)__popcll(vis & ((1ull << lane) - 1ull));
-        const uint32_t x0 = rect.x & 0xFFFFu, y0 = rect.x >> 16, x1 = rect.y & 0xFFFFu, y1 = rect.y >> 16;
-        if (i < pp.count)
-            prect[i] = visible ? make_uint2(x0 | (y0 << 12) | ((slot - block_base) << 24), x1 | (y1 << 12) | (1u << 24)) : make_uint2(0u, 0u);
+        const BinRect br = {rect.x, rect.y};
+        if (i < pp.count) {
+            if (NARROW) {
+                static_cast<uint32_t*>(prect)[i] = bin_word_pack_narrow(visible, slot - block_base, br);
+            } else {
+                const BinWordWide w = bin_word_pack_wide(visible, slot - block_base, br);
+                static_cast<uint2*>(prect)[i] = make_uint2(w.x, w.y);
+            }
+        }
     }
     if (visible) {
         const uint32_t slot = wave_base + (uint32_t)__popcll(vis & ((1ull << lane) - 1ull));
@@ -573,19 +580,19 @@ __device__ __forceinline__ void project_block(const ProjectParams& pp, const Mes
 // (per-scene transforms, or a full-frame draw of a scene that was > 90 % in view at its last full-frame draw: the test finds nothing
 // to drop there, and its code costs the all-visible launch scalar registers - C4 250 -> 278 us with it compiled in, r05m).  The
 // rule and its measurements: gs_launch_project below.
-template <bool EXT, int MODE, bool DEPTH>
+template <bool EXT, int MODE, bool DEPTH, bool NARROW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_project(ProjectParams pp, MeshPlanes mp, SplatRec* __restrict__ recs,
                                                  uint2* __restrict__ rects, unsigned long long* __restrict__ vis_mask,
                                                  uint2* __restrict__ vis32, uint32_t* __restrict__ vis_orig,
                                                  const uint32_t* __restrict__ inv_perm, uint8_t* __restrict__ block_any,
-                                                 uint2* __restrict__ prect, float* __restrict__ zrec) {
+                                                 void* __restrict__ prect, float* __restrict__ zrec) {
     if (MODE == 1) {
         if (block_any[blockIdx.x] == 0) return;
-        project_block<EXT, false, DEPTH>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
+        project_block<EXT, false, DEPTH, NARROW>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
     } else if (MODE == 2) {
-        project_block<EXT, false, DEPTH>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
+        project_block<EXT, false, DEPTH, NARROW>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
     } else {
-        project_block<EXT, true, DEPTH>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
+        project_block<EXT, true, DEPTH, NARROW>(pp, mp, blockIdx.x, recs, rects, vis_mask, vis32, vis_orig, inv_perm, block_any, prect, zrec);
     }
 }
 
@@ -645,21 +652,27 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, m->ctx->aux, pp, mp, ps.recs.as<SplatRec>(), ps.rects.as<uint2>(),
                            ps.vis_mask.as<unsigned long long>(), ps.vis32.as<uint2>(), vis_orig, inv_perm, ps.block_any.as<uint8_t>(),
-                           ps.prect.as<uint2>(), ps.zrec.as<float>());
+                           ps.prect.p, ps.zrec.as<float>());
     };
     const bool depth = pp.depth_mode != 0u;
     if (ev_before && !whole_stage) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));
+#define GS_PROJECT_LAUNCH_W(E, D, W)                                                                             \
+    do {                                                                                                         \
+        if (mode == 1) launch(k_project<E, 1, D, W>);                                                            \
+        else if (mode == 2) launch(k_project<E, 2, D, W>);                                                       \
+        else launch(k_project<E, 0, D, W>);                                                                      \
+    } while (0)
 #define GS_PROJECT_LAUNCH(E, D)                                                                                  \
     do {                                                                                                         \
-        if (mode == 1) launch(k_project<E, 1, D>);                                                               \
-        else if (mode == 2) launch(k_project<E, 2, D>);                                                          \
-        else launch(k_project<E, 0, D>);                                                                         \
+        if (ps.narrow_word) GS_PROJECT_LAUNCH_W(E, D, true);                                                     \
+        else GS_PROJECT_LAUNCH_W(E, D, false);                                                                   \
     } while (0)
     if (ext && depth) GS_PROJECT_LAUNCH(true, true);
     else if (ext) GS_PROJECT_LAUNCH(true, false);
     else if (depth) GS_PROJECT_LAUNCH(false, true);
     else GS_PROJECT_LAUNCH(false, false);
 #undef GS_PROJECT_LAUNCH
+#undef GS_PROJECT_LAUNCH_W
     if (ev_after) GS_HIP(hipEventRecord(ev_after, m->ctx->aux));
     GS_HIP(hipGetLastError());
     return GS_OK;

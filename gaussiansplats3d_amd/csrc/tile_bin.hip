@@ -4,10 +4,13 @@
 // (/root/reference/src/splatmesh/SplatGeometry.js:11-37, SplatMaterial3D.js:65-75, src/Viewer.js:1616).  A
 // tile rasteriser needs each tile's splats as a list in that same draw order, so:
 //   k_bin_count   walk the sorted index list NEAR->FAR (q = R-1-p).  One flag per 256-splat storage block (block_any, kept as a
-//                 bitmap in LDS) filters the list before anything is gathered; a position of a live block gathers ONE 8-byte
-//                 word written by k_project - {visible, record slot in the block, tile rect}.  Survivors are compacted
-//                 (wave64 ballot + popcount prefix) into the workgroup's own slice of a (slot, rect, offset) list, and
-//                 entry counts are reduced.  The kernel runs at the machine's random-gather rate.
+//                 bitmap in LDS) filters the list before anything is gathered; a position of a live block gathers ONE word
+//                 written by k_project - {visible, record slot in the block, tile rect}, 4 bytes on frames of <= 256 x 256
+//                 tiles and 8 beyond (bin_word.hpp); the few rects the 4-byte word cannot hold (a span over 14 tiles: 0.36 %
+//                 of C3's visible splats) cost their lanes a second, dependent gather of the record's own rect.  Survivors are
+//                 compacted (wave64 ballot + popcount prefix) into the workgroup's own slice of a (slot, rect, offset) list,
+//                 and entry counts are reduced.  The kernel is a chain of random gathers, and what they cost follows the
+//                 words' footprint in the live blocks (profiles/r12_gather_live_blocks.txt).
 //   k_bin_emit    splat-centric expansion into (list bin, record slot) pairs, one lane per surviving splat, runs
 //                 written at the offsets the count pass fixed; each workgroup scans the binning workgroups' counts itself
 //                 (no scan kernel) and takes batches of 256 splats round-robin, so the near end of the list - whose splats
@@ -76,8 +79,11 @@ extern "C" int gs_debug_bin_prof(void* dst) {
 struct SliceCount {
     uint32_t entries, splats, t16;       // entries emitted by the slice | compacted (visible) splats | this LANE's 16-px tiles (statistics)
 };
+// NARROW: prect holds the 4-byte word; `rects` (the record set's per-slot rects) answers its escapes.
+template <bool NARROW>
 __device__ __forceinline__ SliceCount bin_count_slice(const uint32_t* __restrict__ order, uint32_t R, const uint32_t* __restrict__ perm,
-                                                      const uint2* __restrict__ prect, uint32_t* __restrict__ cidx, uint2* __restrict__ crect,
+                                                      const void* __restrict__ prect, const uint2* __restrict__ rects,
+                                                      uint32_t* __restrict__ cidx, uint2* __restrict__ crect,
                                                       uint32_t* __restrict__ coff, uint32_t list_shift, uint32_t splat_count,
                                                       const uint8_t* __restrict__ block_any, bool coarse, const uint32_t* s_any,
                                                       unsigned long long* s_w, uint32_t pos_begin, uint32_t pos_end) {
@@ -105,8 +111,8 @@ __device__ __forceinline__ SliceCount bin_count_slice(const uint32_t* __restrict
 #pragma unroll
             for (int k = 0; k < BIN_PER_LANE; k++) idx[k] = perm[idx[k]];
         }
-        // k_project compacts survivors inside their 256-splat block and leaves, per position of a live block, one 8-byte word
-        // {visible, slot in the block, tile rect}: a single gather gives the filter, the slot and the rect
+        // k_project compacts survivors inside their 256-splat block and leaves, per position of a live block, one word
+        // {visible, slot in the block, tile rect} (bin_word.hpp): a single gather gives the filter, the slot and the rect
         if (coarse) {
 #pragma unroll
             for (int k = 0; k < BIN_PER_LANE; k++) keep[k] = keep[k] && ((s_any[idx[k] >> 13] >> ((idx[k] >> 8) & 31u)) & 1u);
@@ -115,13 +121,35 @@ __device__ __forceinline__ SliceCount bin_count_slice(const uint32_t* __restrict
             for (int k = 0; k < BIN_PER_LANE; k++) keep[k] = keep[k] && block_any[idx[k] >> 8] != 0;
         }
         uint32_t slot[BIN_PER_LANE];
+        if (NARROW) {
+            uint32_t w[BIN_PER_LANE];
 #pragma unroll
-        for (int k = 0; k < BIN_PER_LANE; k++) {
-            const uint2 w = keep[k] ? prect[idx[k]] : make_uint2(0u, 0u);
-            keep[k] = keep[k] && ((w.y >> 24) & 1u);
-            slot[k] = (idx[k] & ~255u) + (w.x >> 24);
-            r[k] = keep[k] ? make_uint2((w.x & 0xFFFu) | (((w.x >> 12) & 0xFFFu) << 16), (w.y & 0xFFFu) | (((w.y >> 12) & 0xFFFu) << 16))
-                           : make_uint2(0xFFFFu, 0u);
+            for (int k = 0; k < BIN_PER_LANE; k++) w[k] = keep[k] ? static_cast<const uint32_t*>(prect)[idx[k]] : BIN_WORD_INVISIBLE;
+            bool esc[BIN_PER_LANE];
+#pragma unroll
+            for (int k = 0; k < BIN_PER_LANE; k++) {
+                const BinWordOut o = bin_word_unpack_narrow(w[k]);
+                keep[k] = o.visible;                       // (a position that was not kept carries the invisible word)
+                esc[k] = o.escape;
+                slot[k] = (idx[k] & ~255u) + o.slot;
+                r[k] = make_uint2(o.rect.lo, o.rect.hi);
+            }
+            // a rect the word could not hold: the record's own, one more dependent gather for these few lanes
+#pragma unroll
+            for (int k = 0; k < BIN_PER_LANE; k++)
+                if (esc[k]) r[k] = rects[slot[k]];
+#pragma unroll
+            for (int k = 0; k < BIN_PER_LANE; k++)
+                if (!keep[k]) r[k] = make_uint2(0xFFFFu, 0u);
+        } else {
+#pragma unroll
+            for (int k = 0; k < BIN_PER_LANE; k++) {
+                const uint2 g = keep[k] ? static_cast<const uint2*>(prect)[idx[k]] : make_uint2(0u, 0u);
+                const BinWordOut o = bin_word_unpack_wide(BinWordWide{g.x, g.y});
+                keep[k] = keep[k] && o.visible;
+                slot[k] = (idx[k] & ~255u) + o.slot;
+                r[k] = keep[k] ? make_uint2(o.rect.lo, o.rect.hi) : make_uint2(0xFFFFu, 0u);
+            }
         }
 #pragma unroll
         for (int k = 0; k < BIN_PER_LANE; k++) t16 += rect_tiles(r[k]);
@@ -171,10 +199,12 @@ __device__ __forceinline__ SliceCount bin_count_slice(const uint32_t* __restrict
 // Dealing spans of 1024 positions round-robin instead of one contiguous chunk per workgroup, with a scan kernel between count
 // and emit, was tried as well: the entries per workgroup even out (max 1841 vs 3681) but the body time does not - 24.6 us max
 // either way, it is a chain of loaded memory round trips - and the extra kernel makes the C3 frame 3 us slower.)
+template <bool NARROW>
 __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bin_count(const uint32_t* __restrict__ order, uint32_t R_host,
                                                            const uint32_t* __restrict__ R_dev /* nullable */,
                                                            const uint32_t* __restrict__ perm,
-                                                           const uint2* __restrict__ prect,
+                                                           const void* __restrict__ prect,
+                                                           const uint2* __restrict__ rects /* the same set's: a narrow word's escapes */,
                                                            uint32_t* __restrict__ cidx,
                                                            uint2* __restrict__ crect, uint32_t* __restrict__ coff,
                                                            uint32_t* __restrict__ block_sums,
@@ -185,7 +215,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
                                                            uint32_t lds_bitmap /* 0: $GSPLAT_NO_COARSE_VIS, the flag bytes themselves */) {
     __shared__ unsigned long long s_w[4];
     // Coarse visibility, one bit per 256-splat storage block, in LDS.  75 % of a scene's splats draw nothing and, stored along
-    // a Morton curve, mostly whole blocks of them; an LDS bit test spares those list positions the 8-byte L2 gather of their
+    // a Morton curve, mostly whole blocks of them; an LDS bit test spares those list positions the L2 gather of their
     // visibility word (5.8 M random L2 transactions per frame were this kernel's real cost: making the rects dense did nothing)
     __shared__ uint32_t s_any[ANY_WORDS];
     BIN_PROF(0, 0, wall_clock64());
@@ -226,7 +256,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t pos_begin = ch.begin * BIN_THREADS, pos_end = min(ch.end * BIN_THREADS, R);
-    const SliceCount sc = bin_count_slice(order, R, perm, prect, cidx, crect, coff, list_shift, splat_count, block_any, coarse, s_any, s_w, pos_begin, pos_end);
+    const SliceCount sc = bin_count_slice<NARROW>(order, R, perm, prect, rects, cidx, crect, coff, list_shift, splat_count, block_any, coarse, s_any, s_w, pos_begin, pos_end);
     uint32_t t16 = sc.t16;
     const uint32_t sum = sc.entries, out = pos_begin + sc.splats;
 #pragma unroll
@@ -602,11 +632,16 @@ static int binning_typed(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback&
     const StatShift stat_shift = {plan.sx, plan.sy, pp.bins_x};
     ++m->draw_serial;
     if (m->draw_serial == 0u) m->draw_serial = 1u;       // (the mapped words carry the serial: 0 is "no draw yet", mesh_read_view_share)
-    hipLaunchKernelGGL(k_bin_count, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
-                       m->translate ? m->perm.as<uint32_t>() : nullptr, ps.prect.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
-                       m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
-                       m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
-                       ps.block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
+    // (the word the vertex stage wrote into this set: mesh.hip, mesh_project)
+    auto count_pass = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(BIN_THREADS), 0, st, order_dev, R, R_dev,
+                           m->translate ? m->perm.as<uint32_t>() : nullptr, ps.prect.p, ps.rects.as<uint2>(), m->cidx.as<uint32_t>(), m->rect_q.as<uint2>(), m->coff.as<uint32_t>(),
+                           m->bin_sums.as<uint32_t>(), m->radix.digit_total.as<uint32_t>(),
+                           m->tile_ranges.as<uint2>(), tiles, pp.list_shift, pp.count,
+                           ps.block_any.as<uint8_t>(), m->deep_flags.as<uint32_t>(), blend_bins, m->no_coarse_vis ? 0u : 1u);
+    };
+    if (ps.narrow_word) count_pass(k_bin_count<true>);
+    else count_pass(k_bin_count<false>);
     hipLaunchKernelGGL((k_bin_emit<KeyT>), dim3(grid + (order_wg ? 1u : 0u)), dim3(BIN_THREADS), 0, st, frame, cap, m->cidx.as<uint32_t>(),
                        m->rect_q.as<uint2>(), m->coff.as<uint32_t>(), m->bin_sums.as<uint32_t>(), grid, pp.lists_x, pp.list_row_begin,
                        m->ekeyA.as<KeyT>(), m->evalA.as<uint32_t>(), pp.list_shift, m->mirror_dev, m->draw_serial,

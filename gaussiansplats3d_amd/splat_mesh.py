@@ -450,6 +450,13 @@ class SplatMesh:
             L.check(self.lib.gs_mesh_debug_read(self.handle, 9, slots.ctypes.data, self.splat_count))
         return rng, entries, slots
 
+    def bin_word_narrow(self):
+        """Which look-up word the last draw's vertex stage left for its binner (csrc/bin_word.hpp; gs_mesh_debug_read what = 14):
+        True = the 4-byte word, False = the 8-byte one (a frame beyond 256 tiles in either direction, $GSPLAT_NO_COMPACT_BIN_WORD)."""
+        word = np.zeros(1, dtype=np.uint32)
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 14, word.ctypes.data, 1))
+        return bool(word[0])
+
     def blend_bin_stats(self, tile_rows=None):
         """Per 32-px blend bin of the last draw - the full frame, or the strip `tile_rows` it drew: (entries scanned, 2 x (splat,
         quadrant) pairs composited), [bin_rows, bins_x, 2], row 0 = the strip's first bin row."""
