@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 DrawFeedback read_feedback(const volatile uint32_t* mirror) {
     DrawFeedback f = {};
@@ -257,4 +258,19 @@ extern "C" int gs_debug_bin_word(const gs_bin_word_debug_in* in, gs_bin_word_deb
     out->wide_visible = u.visible; out->wide_slot = u.slot;
     out->wide_x0 = u.rect.lo & 0xFFFFu; out->wide_y0 = u.rect.lo >> 16; out->wide_x1 = u.rect.hi & 0xFFFFu; out->wide_y1 = u.rect.hi >> 16;
     return 0;
+}
+
+extern "C" int64_t gs_debug_live_units(const uint32_t* cnt, uint32_t slices, uint32_t* units, uint32_t room) {
+    if (!cnt || slices == 0u || (!units && room != 0u)) return -1;
+    std::vector<uint32_t> words(slices);
+    uint32_t total = 0;
+    for (uint32_t b = 0; b < slices; b++) {
+        words[b] = live_unit_word(total, cnt[b]);
+        total += live_batches(cnt[b]);
+    }
+    for (uint32_t l = 0; l < std::min(total, room); l++) {
+        const LiveUnit u = live_unit_find([&](uint32_t b) { return words[b]; }, slices, total, l);
+        units[3u * l] = u.slice; units[3u * l + 1u] = u.batch; units[3u * l + 2u] = u.count;
+    }
+    return (int64_t)total;
 }

@@ -109,6 +109,55 @@ int block_test_mode(uint32_t measured_visible, uint32_t measured_count, bool str
 bool narrow_bin_word(uint32_t tiles_x, uint32_t tiles_y, const DrawSwitches& sw);
 
 // ---------------------------------------------------------------------------------------------------
+// k_bin_emit's work units (host and device: the kernel and gs_debug_live_units run the same two functions)
+// ---------------------------------------------------------------------------------------------------
+// k_bin_count leaves cnt[b] compacted splats in slice b (one binning workgroup's part of the walk, room for per * 256); k_bin_emit
+// expands them in batches of GS_EMIT_BATCH.  Only the batches that hold a splat are dealt - at C3 a slice keeps a quarter of its
+// positions, so three of four (slice, batch) pairs are empty and, dealt round-robin by pair, the empty ones land on the same
+// workgroups every time.  Live unit l of a draw is batch l - first[b] of the slice b with first[b] <= l < first[b + 1], where first
+// is the exclusive prefix of ceil(cnt / 256) over the slices and first[slices] = the draw's live units.  Workgroup wg of wgs takes
+// l = wg, wg + wgs, ...: the near end of the walk stays spread over the grid.
+// One word per slice, so the kernel's LDS holds what it held: first[b] in 24 bits (a sorted list is < 2^32 positions, and fewer than
+// 2^24 batches since its array is < 4 GiB) | (cnt[b] - 1) & 255 above: a slice's batches are full but for its last one.
+#if defined(__HIP__)       // (the attributes spelled out: draw_plan.cpp includes no HIP header)
+#define GS_PLAN_FN __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
+#else
+#define GS_PLAN_FN inline
+#endif
+constexpr uint32_t GS_EMIT_BATCH = 256;
+constexpr uint32_t GS_LIVE_FIRST_MASK = 0x00FFFFFFu;
+GS_PLAN_FN uint32_t live_batches(uint32_t cnt) { return (cnt + GS_EMIT_BATCH - 1u) / GS_EMIT_BATCH; }
+GS_PLAN_FN uint32_t live_unit_word(uint32_t first, uint32_t cnt) { return (first & GS_LIVE_FIRST_MASK) | (((cnt - 1u) & 255u) << 24); }
+struct LiveUnit {
+    uint32_t slice, batch;         // batch `batch` of slice `slice` ...
+    uint32_t count;                // ... which holds this many splats (1 .. 256)
+};
+// Unit l, once its slice is known: `word` is the slice's, next_first the first unit of the slice after it (the draw's live units
+// behind the last slice).
+GS_PLAN_FN LiveUnit live_unit_of(uint32_t slice, uint32_t word, uint32_t next_first, uint32_t l) {
+    const uint32_t first = word & GS_LIVE_FIRST_MASK;
+    LiveUnit u;
+    u.slice = slice;
+    u.batch = l - first;
+    u.count = u.batch + 1u < next_first - first ? GS_EMIT_BATCH : (word >> 24) + 1u;
+    return u;
+}
+// word_at(b): the word of slice b < slices; total: the draw's live units; l < total.  The unit's slice is the LAST one whose first
+// is <= l: never an empty one (an empty slice's successor has the same first).  A binary search here; k_bin_emit finds the same
+// slice with two ballots of a wave over its LDS (tile_bin.hip, live_unit_find_wave: eleven dependent LDS reads per unit were a
+// third of a unit's time) and decodes it with live_unit_of as well.
+template <class WordAt>
+GS_PLAN_FN LiveUnit live_unit_find(WordAt word_at, uint32_t slices, uint32_t total, uint32_t l) {
+    uint32_t lo = 0u, hi = slices;                         // first[lo] <= l < first[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((word_at(mid) & GS_LIVE_FIRST_MASK) <= l) lo = mid;
+        else hi = mid;
+    }
+    return live_unit_of(lo, word_at(lo), hi < slices ? (word_at(hi) & GS_LIVE_FIRST_MASK) : total, l);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // the blend schedule and the deep pass
 // ---------------------------------------------------------------------------------------------------
 // A draw's camera and what else of its geometry the statistics of its blend depend on
@@ -205,3 +254,9 @@ struct gs_bin_word_debug_out {
     uint32_t wide_visible, wide_slot, wide_x0, wide_y0, wide_x1, wide_y1;   // ... unpacked
 };
 extern "C" int gs_debug_bin_word(const gs_bin_word_debug_in* in, gs_bin_word_debug_out* out);   // 0, or -1 on a NULL argument
+
+// ... and for tests/test_emit_units.py: k_bin_emit's live units of a draw whose slices hold cnt[0 .. slices) compacted splats.  The
+// words are built as the kernel's prologue builds them (live_unit_word over the exclusive prefix of live_batches), and every unit
+// l < min(total, room) is looked up with live_unit_find: (slice, batch, count) into units[3 * l ..].  Returns the draw's live units,
+// or -1 on a NULL argument or slices == 0.
+extern "C" int64_t gs_debug_live_units(const uint32_t* cnt, uint32_t slices, uint32_t* units, uint32_t room);

@@ -14,7 +14,8 @@
 //   k_bin_emit    splat-centric expansion into (list bin, record slot) pairs, one lane per surviving splat, runs
 //                 written at the offsets the count pass fixed; each workgroup scans the binning workgroups' counts itself
 //                 (no scan kernel) and takes batches of 256 splats round-robin, so the near end of the list - whose splats
-//                 touch 30x the mean number of lists - is spread over the whole grid.
+//                 touch 30x the mean number of lists - is spread over the whole grid.  Only batches that hold a splat are
+//                 dealt (draw_plan.hpp: live units), and a workgroup loads its next batch before it expands this one.
 //   entry sort    stable LSD radix passes on the list-bin id (radix.hpp): stability keeps near->far order per list;
 //                 one pass for <= 256 lists (1080p at 128-px lists), and the pass publishes every list's [begin,end)
 // Entry count D only ever lives on the device; downstream grids are sized for the capacity and read D there.
@@ -64,7 +65,7 @@ __device__ __forceinline__ BinChunk bin_chunk(uint32_t n) {
 // 64-bit block scan per 1024 positions yields both the compaction slot and the entry offset.
 #ifdef GS_BIN_PROFILE
 // tools/bin_profile.py: per workgroup of k_bin_count [0] / k_bin_emit [1]: {start, after the prologue, end} of the 100 MHz
-// clock and the workgroup's output count
+// clock and the workgroup's output count (k_bin_emit: | the live units it expanded << 32)
 __device__ unsigned long long g_bin_prof[2 * 2048 * 4];
 extern "C" int gs_debug_bin_prof(void* dst) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_bin_prof), sizeof(unsigned long long) * 2 * 2048 * 4, 0, hipMemcpyDeviceToHost);
@@ -272,13 +273,57 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     BIN_PROF(0, 3, (unsigned long long)sum);
 }
 
-// One batch of <= 256 compacted splats of a slice -> (list bin, record slot) entries from slot `base` on: a lane writes the first
-// EMIT_OWN entries of its own splat walking the rect row-major, what is left of the few splats that cover more list bins is written
-// by the whole wave.  src: this thread's position in the compacted lists; live: it holds a splat.  Returns the lane's entry count.
+// What a lane reads of one live unit (draw_plan.hpp: a batch of <= 256 compacted splats of a slice that holds at least one): its
+// splat's rect, record slot and first entry slot.  The three loads of a workgroup's NEXT unit are issued before this unit is
+// expanded: a unit is loads -> arithmetic -> stores, and a workgroup's units are all known once its prologue is done.
+struct EmitLoad {
+    bool live;                 // the lane holds a splat (false for every lane: no such unit, or the draw overflowed before its slice)
+    uint2 rect;                // 16-px tiles
+    uint32_t idx, off, base;   // record slot | first entry slot = base (the slice's) + off (in the slice), added when the unit is expanded
+};
+// live_unit_find (draw_plan.hpp) by a wave over the words in LDS, every lane with the same answer: lane i asks the first slice of
+// block i (LIVE_BLOCK slices: 33, so that the 64 reads fall into different banks), a ballot names the block; 34 lanes then read the
+// block's slices and the next block's first one, and a second ballot names the slice.  Two LDS round trips instead of eleven.
+constexpr uint32_t LIVE_BLOCK = 33;
+static_assert((uint32_t)BIN_MAX_BLOCKS <= 64u * LIVE_BLOCK, "one lane per block of slices");
+__device__ __forceinline__ LiveUnit live_unit_find_wave(const uint32_t* s_live, uint32_t slices, uint32_t total, uint32_t l) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i1 = lane * LIVE_BLOCK;
+    const bool p1 = i1 < slices && (s_live[min(i1, slices - 1u)] & GS_LIVE_FIRST_MASK) <= l;
+    const uint32_t block = (uint32_t)__popcll(__ballot(p1)) - 1u;                      // (slice 0's first is 0 <= l)
+    const uint32_t i2 = block * LIVE_BLOCK + lane;
+    const bool mine = lane <= LIVE_BLOCK && i2 < slices;
+    const uint32_t w2 = mine ? s_live[min(i2, slices - 1u)] : 0u;
+    const bool p2 = mine && lane < LIVE_BLOCK && (w2 & GS_LIVE_FIRST_MASK) <= l;
+    const uint32_t in_block = (uint32_t)__popcll(__ballot(p2)) - 1u;                   // (the block's first slice has first <= l)
+    const uint32_t slice = block * LIVE_BLOCK + in_block;
+    const uint32_t word = __shfl(w2, (int)in_block, 64), after = __shfl(w2, (int)in_block + 1, 64);
+    return live_unit_of(slice, word, slice + 1u < slices ? (after & GS_LIVE_FIRST_MASK) : total, l);
+}
+
+__device__ __forceinline__ EmitLoad bin_emit_load(const uint32_t* __restrict__ cidx, const uint2* __restrict__ crect, const uint32_t* __restrict__ coff,
+                                                  const uint32_t* s_live, const uint32_t* s_eoff, uint32_t slices, uint32_t total, uint32_t per,
+                                                  uint32_t l, uint32_t limit) {
+    EmitLoad ld;
+    ld.live = false; ld.rect = make_uint2(0u, 0u); ld.idx = 0u; ld.off = 0u; ld.base = 0u;
+    if (l >= total) return ld;
+    const LiveUnit u = live_unit_find_wave(s_live, slices, total, l);
+    const uint32_t boff = s_eoff[u.slice];
+    if (boff >= limit || threadIdx.x >= u.count) return ld;
+    const uint32_t src = (u.slice * per + u.batch) * BIN_THREADS + threadIdx.x;   // the slice's part of the compacted lists
+    ld.live = true;
+    ld.rect = crect[src];
+    ld.idx = cidx[src];
+    ld.off = coff[src];
+    ld.base = boff;
+    return ld;
+}
+
+// One unit -> (list bin, record slot) entries: a lane writes the first EMIT_OWN entries of its own splat walking the rect row-major,
+// what is left of the few splats that cover more list bins is written by the whole wave.  Returns the lane's entry count.
 constexpr uint32_t EMIT_OWN = 16;      // entries a lane writes for its own splat; longer runs are shared by the wave
 template <class KeyT>
-__device__ __forceinline__ uint32_t bin_emit_batch(const uint32_t* __restrict__ cidx, const uint2* __restrict__ crect, const uint32_t* __restrict__ coff,
-                                                   uint32_t src, bool live, uint32_t base, uint32_t limit, uint32_t tiles_x, uint32_t row_begin,
+__device__ __forceinline__ uint32_t bin_emit_batch(const EmitLoad ld, uint32_t limit, uint32_t tiles_x, uint32_t row_begin,
                                                    uint32_t list_shift, KeyT* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
     const uint32_t lane = threadIdx.x & 63u;
     auto put = [&](uint32_t e, uint32_t key, uint32_t idx) {
@@ -286,14 +331,8 @@ __device__ __forceinline__ uint32_t bin_emit_batch(const uint32_t* __restrict__ 
         keys_out[e] = (KeyT)key;
         vals_out[e] = idx;
     };
-    uint2 r = make_uint2(0u, 0u);
-    uint32_t idx = 0, e0 = 0, n = 0;
-    if (live) {
-        r = rect_to_bins(crect[src], list_shift);                    // the list bins the splat touches
-        idx = cidx[src];
-        e0 = base + coff[src];
-        n = rect_tiles(r);
-    }
+    const uint2 r = rect_to_bins(ld.rect, list_shift);               // the list bins the splat touches
+    const uint32_t idx = ld.idx, e0 = ld.base + ld.off, n = ld.live ? rect_tiles(r) : 0u;
     const uint32_t x0 = r.x & 0xFFFFu, y0 = r.x >> 16, w = (r.y & 0xFFFFu) - x0 + 1u;
     for (uint32_t k = 0, xx = x0, yy = y0; k < min(n, EMIT_OWN); k++) {     // row-major walk of the rect, no k / w, k % w
         put(e0 + k, (yy - row_begin) * tiles_x + xx, idx);
@@ -330,8 +369,9 @@ struct StatShift {
 // __restrict__ on either)
 __device__ __forceinline__ void blend_schedule_job(const uint2* prev_blend_stats, uint32_t blend_bins, uint32_t* __restrict__ blend_order,
                                                    uint32_t deep, uint32_t* __restrict__ deep_flags, uint32_t* blend_stats_w,
-                                                   uint32_t deep_min, uint32_t deep_factor, volatile uint32_t* __restrict__ mirror, StatShift sh) {
-    __shared__ uint32_t s_cost[RADIX_BINS], s_tmp2[4];
+                                                   uint32_t deep_min, uint32_t deep_factor, volatile uint32_t* __restrict__ mirror, StatShift sh,
+                                                   uint32_t* s_tmp2 /* 4 words of LDS for the block scans */) {
+    __shared__ uint32_t s_cost[RADIX_BINS];
     // (the chunked composite's per-draw words - no deep bins yet, an empty partial pool - were reset by k_bin_count, a kernel boundary ago)
     // three sweeps over the statistics, 8 loads in flight per lane (registers for all 8192 / 256 values would set the
     // whole kernel's VGPR allocation and cost every emitting workgroup its occupancy)
@@ -436,8 +476,12 @@ __device__ __forceinline__ void blend_schedule_job(const uint2* prev_blend_stats
 }
 
 // k_bin_emit: splat-centric expansion of the compacted list into (list bin, record slot) pairs.
-// Work unit = one batch of 256 compacted splats of one binning workgroup's slice; the units are dealt round-robin to the
-// workgroups.  (One workgroup per binning workgroup, the r01 shape, lasted as long as its heaviest slice: the slices that hold
+// Work unit = one batch of 256 compacted splats of one binning workgroup's slice that holds at least one splat (a live unit,
+// draw_plan.hpp); the units are dealt round-robin to the workgroups.  (Dealing every (slice, batch) pair, empty or not, gave the
+// workgroups of one residue class most of the live ones: C3 has 12 batches per slice of which the first three or four are live, and
+// 2048 workgroups step through the pairs by 2048 mod 12 = 8, so a workgroup only ever met the batch indices {r, r + 4, r + 8} - a
+// quarter of the grid expanded 4.7 live batches each, the rest 2 to 3.3, and the kernel lasted as long as the former:
+// profiles/r13_emit_timeline_before.txt.)  (One workgroup per binning workgroup, the r01 shape, lasted as long as its heaviest slice: the slices that hold
 // the nearest splats carry 30x the mean entry count - r02n timeline: mean workgroup 8 us, last one 27 us, and the same 27 us
 // for a strip-sharded rank that emits an eighth of the entries.)  A lane writes the first OWN entries of its splat itself,
 // walking the rect row-major; what is left of the few splats that cover more list bins is written by the whole wave.
@@ -459,9 +503,9 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
                                                           uint32_t* __restrict__ deep_flags, uint32_t* blend_stats_w,
                                                           uint32_t deep_min, uint32_t deep_factor, StatShift sh) {
     __shared__ __attribute__((aligned(16))) uint32_t s_eoff[BIN_MAX_BLOCKS];   // entries of the binning workgroups before b (saturating)
-    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[BIN_MAX_BLOCKS];    // compacted splats of binning workgroup b
+    __shared__ __attribute__((aligned(16))) uint32_t s_live[BIN_MAX_BLOCKS];   // live batches before b | its last batch's splats (draw_plan.hpp, live_unit_word)
     __shared__ unsigned long long s_wsum[4], s_t16[4];
-    __shared__ uint32_t s_vis[4];
+    __shared__ uint32_t s_vis[4], s_lsum[4];                                   // (s_lsum: the schedule job's scan scratch as well)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     BIN_PROF(1, 0, wall_clock64());
     BIN_PROF(1, 2, 0ull);
@@ -473,7 +517,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
     // keys is irrelevant (pixels do not depend on which workgroup draws a bin).
     const uint32_t first_wg = blend_order ? 1u : 0u;
     if (blend_order && blockIdx.x == 0) {
-        blend_schedule_job(prev_blend_stats, blend_bins, blend_order, deep, deep_flags, blend_stats_w, deep_min, deep_factor, mirror, sh);
+        blend_schedule_job(prev_blend_stats, blend_bins, blend_order, deep, deep_flags, blend_stats_w, deep_min, deep_factor, mirror, sh, s_lsum);
         BIN_PROF(1, 1, wall_clock64());
         BIN_PROF(1, 2, wall_clock64());
         return;
@@ -483,8 +527,9 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
     // with 16-byte loads (block_sums rows are 16-byte aligned)
     constexpr uint32_t PER_T = BIN_MAX_BLOCKS / BIN_THREADS;
     static_assert(PER_T % 4 == 0, "16-byte loads of the workgroup sums");
-    uint32_t mine[PER_T];
+    uint32_t mine[PER_T], cnt[PER_T];
     unsigned long long own = 0;
+    uint32_t own_live = 0;
 #pragma unroll
     for (uint32_t q = 0; q < PER_T / 4; q++) {
         const uint32_t i0 = threadIdx.x * PER_T + 4 * q;
@@ -498,19 +543,24 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
         c.y = i0 + 1 < bin_grid ? c.y : 0u;
         c.z = i0 + 2 < bin_grid ? c.z : 0u;
         c.w = i0 + 3 < bin_grid ? c.w : 0u;
-        reinterpret_cast<uint4*>(s_cnt)[i0 / 4] = c;
+        cnt[4 * q + 0] = c.x; cnt[4 * q + 1] = c.y; cnt[4 * q + 2] = c.z; cnt[4 * q + 3] = c.w;
     }
 #pragma unroll
-    for (uint32_t k = 0; k < PER_T; k++) own += mine[k];
+    for (uint32_t k = 0; k < PER_T; k++) { own += mine[k]; own_live += live_batches(cnt[k]); }
     const unsigned long long incl = wave_incl_scan(own, lane);
-    if (lane == 63u) s_wsum[wave] = incl;
+    const uint32_t incl_live = wave_incl_scan(own_live, lane);
+    if (lane == 63u) { s_wsum[wave] = incl; s_lsum[wave] = incl_live; }
     __syncthreads();
     unsigned long long run = incl - own, D64 = 0;
+    uint32_t run_live = incl_live - own_live, L = 0;         // live batches before this thread's slices | of the draw
 #pragma unroll
     for (uint32_t w = 0; w < 4; w++) {
         const unsigned long long c = s_wsum[w];
         run += w < wave ? c : 0ull;
         D64 += c;
+        const uint32_t cl = s_lsum[w];
+        run_live += w < wave ? cl : 0u;
+        L += cl;
     }
 #pragma unroll
     for (uint32_t q = 0; q < PER_T / 4; q++) {
@@ -521,6 +571,12 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
             run += mine[4 * q + k];
         }
         reinterpret_cast<uint4*>(s_eoff)[(threadIdx.x * PER_T + 4 * q) / 4] = make_uint4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            v[k] = live_unit_word(run_live, cnt[4 * q + k]);
+            run_live += live_batches(cnt[4 * q + k]);
+        }
+        reinterpret_cast<uint4*>(s_live)[(threadIdx.x * PER_T + 4 * q) / 4] = make_uint4(v[0], v[1], v[2], v[3]);
     }
     const uint32_t D = D64 > capacity ? capacity : (uint32_t)D64;
     if (wg == 0) {                                           // the frame's scalars (read by the sort passes and the host)
@@ -562,21 +618,24 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(RenderFrame* __restric
             }
         }
     }
-    __syncthreads();                                         // s_eoff complete
+    __syncthreads();                                         // s_eoff and s_live complete
     BIN_PROF(1, 1, wall_clock64());
     const uint32_t per = block_sums[3 * BIN_MAX_BLOCKS];     // batches per binning workgroup (k_bin_count)
-    const uint32_t units = bin_grid * per;
-    uint32_t emitted = 0;
-    for (uint32_t u = wg; u < units; u += wgs) {
-        const uint32_t b = u / per, jb = (u - b * per) * BIN_THREADS;    // batch jb / 256 of binning workgroup b (uniform)
-        const uint32_t cnt = s_cnt[b], boff = s_eoff[b];
-        if (jb >= cnt || boff >= D) continue;
-        const uint32_t src = b * per * BIN_THREADS + jb + threadIdx.x;   // the workgroup's slice of the compacted list
-        emitted += bin_emit_batch<KeyT>(cidx, crect, coff, src, jb + threadIdx.x < cnt, boff, D, tiles_x, row_begin, list_shift, keys_out, vals_out);
+    // the draw's L live units, round-robin (draw_plan.hpp); the next unit's loads fly while this one is expanded
+    uint32_t emitted = 0, walked = 0;
+    EmitLoad cur = bin_emit_load(cidx, crect, coff, s_live, s_eoff, bin_grid, L, per, wg, D);
+    // (the first unit's loads are awaited HERE: left to the compiler, their wait lands in the loop, behind the next unit's loads -
+    // the counter is in order - and every iteration waits for the loads it has just issued.  vmcnt(0), the other counters untouched)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    for (uint32_t l = wg; l < L; l += wgs) {
+        const EmitLoad next = bin_emit_load(cidx, crect, coff, s_live, s_eoff, bin_grid, L, per, l + wgs, D);
+        emitted += bin_emit_batch<KeyT>(cur, D, tiles_x, row_begin, list_shift, keys_out, vals_out);
+        cur = next;
+        walked++;
     }
     BIN_PROF(1, 2, wall_clock64());
-    BIN_PROF(1, 3, (unsigned long long)emitted);
-    (void)emitted;
+    BIN_PROF(1, 3, (unsigned long long)emitted | ((unsigned long long)walked << 32));
+    (void)emitted; (void)walked;
 }
 
 // what plan_schedule (draw_plan.hpp) is told about this draw, the mesh and the draw before

@@ -37,7 +37,8 @@ assert lib.gs_debug_bin_prof(buf.ctypes.data) == 0
 for k, kname in enumerate(("k_bin_count", "k_bin_emit")):
     b = buf[k].astype(np.int64)
     used = b[:, 0] > 0
-    t0, t1, t2, out = b[used, 0], b[used, 1], b[used, 2], b[used, 3]
+    t0, t1, t2, out = b[used, 0], b[used, 1], b[used, 2], b[used, 3] & 0xFFFFFFFF
+    walked = b[used, 3] >> 32              # k_bin_emit: live units (batches that held a splat) the workgroup expanded
     t2 = np.where(t2 > 0, t2, t1)          # workgroups that returned after the prologue
     s = t0.min()
     print(f"{name} {kname} strip={strip}: workgroups {used.sum()}  span {(t2.max() - s) / 100:.1f} us | first start..last start "
@@ -48,7 +49,19 @@ for k, kname in enumerate(("k_bin_count", "k_bin_emit")):
     for a, e in zip(edges[:-1], edges[1:]):
         act = (((t0 - s) / 100 < e) & ((t2 - s) / 100 > a)).sum()
         print(f"   {a:6.1f}-{e:6.1f} us active workgroups {act}")
-    late = np.argsort(t2)[-5:][::-1]
     ids = np.nonzero(used)[0]
+    if k == 1:
+        body = (t2 - t1) / 100
+        print(f"   live units walked {walked.sum()}: per workgroup mean {walked.mean():.2f} max {walked.max()} | "
+              f"histogram {np.bincount(walked, minlength=1).tolist()}")
+        for c in range(4):                 # the classes of the round-robin deal (block index mod 4)
+            sel = ids % 4 == c
+            print(f"   block % 4 == {c}: workgroups {sel.sum()} live units mean {walked[sel].mean():.2f} max {walked[sel].max()} | "
+                  f"body mean {body[sel].mean():.2f} p90 {np.percentile(body[sel], 90):.2f} max {body[sel].max():.2f} us")
+        for n in range(int(walked.max()) + 1):
+            sel = walked == n
+            if sel.any():
+                print(f"   workgroups with {n} live units: {sel.sum()} body mean {body[sel].mean():.2f} max {body[sel].max():.2f} us")
+    late = np.argsort(t2)[-5:][::-1]
     for i in late:
         print(f"   block {ids[i]} start {(t0[i] - s) / 100:.1f} prologue end {(t1[i] - s) / 100:.1f} end {(t2[i] - s) / 100:.1f} out {out[i]}")
