@@ -532,6 +532,7 @@ struct gs_mesh {
     uint32_t full_serial[8] = {0, 0, 0, 0, 0, 0, 0, 0}, full_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last full-frame draws: serial (slot = serial & 7) and splats projected
     uint32_t project_serial = 0;
     uint32_t last_project_mode = 1;       // gs_launch_project: 1 = k_block_test + k_project, 0 = the test in every workgroup, 2 = no test
+    uint32_t last_project_instance = 0;   // gs_launch_project: the k_project instance it launched, ext | depth << 1 | narrow << 2
     bool derive_orig_mask = false;        // a bound sorter builds vis_orig itself from vis_mask + its position map (sorter.hip,
                                           // k_mask_derive_count): full-frame gs_mesh_project calls skip the per-survivor atomics
                                           // (ProjSet::vis_orig_lazy: the pending projection did)

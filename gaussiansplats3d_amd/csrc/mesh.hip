@@ -1136,12 +1136,14 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_HIP(hipMemcpyAsync(dst, m->deep_flags.as<uint32_t>(), 16, hipMemcpyDeviceToHost, st));
         if (count > 4) GS_HIP(hipMemcpyAsync(static_cast<uint32_t*>(dst) + 4, m->deep_flags.as<uint32_t>() + GS_FLAG_LIST, (size_t)(count - 4) * 4, hipMemcpyDeviceToHost, st));
     } else if (what == 6) {   // host state: {visible splats, splats projected} of the last full-frame draw whose verdict has arrived,
-                              // and where the last vertex stage ran its block test (1 separate kernel, 0 per workgroup, 2 nowhere)
-        GS_REQUIRE(count == 3, "count == 3");
+                              // where the last vertex stage ran its block test (1 separate kernel, 0 per workgroup, 2 nowhere) and,
+                              // for count == 4, the k_project instance it launched (ext | depth << 1 | narrow << 2)
+        GS_REQUIRE(count == 3 || count == 4, "count == 3 or 4");
         GS_HIP(hipStreamSynchronize(st));
         mesh_read_view_share(m, draw_switches(), read_feedback(m->mirror_host));   // (the mapped words the last draw left)
         uint32_t* w = static_cast<uint32_t*>(dst);
         w[0] = m->measured_visible; w[1] = m->measured_count; w[2] = m->last_project_mode;
+        if (count == 4) w[3] = m->last_project_instance;
         return GS_OK;
     } else if (what == 7) {   // the last draw's blend schedule (tile_bin.hip blend_schedule_job): GS_SCHEDULE_WORDS words, then
                               // blend_order [0, count - GS_SCHEDULE_WORDS); count = GS_SCHEDULE_WORDS .. + blend bins

@@ -655,6 +655,7 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
                            ps.prect.p, ps.zrec.as<float>());
     };
     const bool depth = pp.depth_mode != 0u;
+    m->last_project_instance = (ext ? 1u : 0u) | (depth ? 2u : 0u) | (ps.narrow_word ? 4u : 0u);
     if (ev_before && !whole_stage) GS_HIP(hipEventRecord(ev_before, m->ctx->aux));
 #define GS_PROJECT_LAUNCH_W(E, D, W)                                                                             \
     do {                                                                                                         \

@@ -515,11 +515,12 @@ class SplatMesh:
 
     def view_share(self):
         """{visible, projected: of the last full-frame draw whose verdict has reached the host (a mapped word, no statistics call
-        needed), block_test: where the last vertex stage ran its block test - 1 a kernel of its own, 0 in every workgroup, 2 nowhere}.
-        Scheduling only: frames do not depend on it."""
-        out = np.zeros(3, dtype=np.uint32)
-        L.check(self.lib.gs_mesh_debug_read(self.handle, 6, out.ctypes.data, 3))
-        return {"visible": int(out[0]), "projected": int(out[1]), "block_test": int(out[2])}
+        needed), block_test: where the last vertex stage ran its block test - 1 a kernel of its own, 0 in every workgroup, 2 nowhere,
+        instance: the k_project instance it launched - bit 0 the shader-permutation kernel, bit 1 window depths written, bit 2 the
+        4-byte look-up word}.  Scheduling only: frames do not depend on it."""
+        out = np.zeros(4, dtype=np.uint32)
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 6, out.ctypes.data, 4))
+        return {"visible": int(out[0]), "projected": int(out[1]), "block_test": int(out[2]), "instance": int(out[3])}
 
     def tile_row_costs(self):
         """Work estimate per 16-px tile row of the last FULL-frame draw (used to balance multi-GPU strips).  The blend is

@@ -555,8 +555,11 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * bins_x = ceil(width / 32)) the pair {list entries scanned, 2 x (splat, 16x16-px quadrant) pairs composited}: the blend's
  * real cost, used to balance multi-GPU strips; 5 = the deep pass of the last draw: {bins it composited, bins over its threshold,
  * chunk partials the per-bin kernel closed itself, 1 if that pool ran out}, then the bin numbers (count = 4 .. 4 + 512 words);
- * 6 = host state (count = 3 words): {visible splats, splats projected} of the last full-frame draw whose verdict has reached the
- * host, and where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all);
+ * 6 = host state (count = 3 or 4 words): {visible splats, splats projected} of the last full-frame draw whose verdict has reached the
+ * host, where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all), and - with
+ * count = 4 - which k_project instance that stage launched: bit 0 = the shader-permutation kernel (orthographic, fade-in, scene
+ * effects, per-scene transforms, 8-bit SH, several scenes), bit 1 = it wrote window depths (a destination depth), bit 2 = the 4-byte
+ * look-up word;
  * 7 = the blend schedule of the last draw (the one workgroup that orders the blend's bins by the previous draw's per-bin statistics,
  * what = 4, and names the deep pass's members), GS_SCHEDULE_WORDS words: {1 if it ran, blend bins, shift x, shift y (int32: this
  * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, bit 0:

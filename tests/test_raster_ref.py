@@ -133,6 +133,16 @@ def engine_mesh(ctx, case):
     return mesh
 
 
+def check_dropped_splats_miss_the_frame(viewport, centre, b1, b2, dropped):
+    """The thin-or-outside rule: a splat the vertex stage of the reference draws (window centre [n, 2], basis vectors b1, b2 [n, 2] in
+    px) and the engine drops (`dropped` bool [n]) must be one whose ellipse misses all pixel centres of the frame."""
+    ext_x, ext_y = np.sqrt(b1[:, 0] ** 2 + b2[:, 0] ** 2), np.sqrt(b1[:, 1] ** 2 + b2[:, 1] ** 2)      # half extents of the ellipse's box
+    W, H = viewport
+    inside = (centre[:, 0] + ext_x > 0.5) & (centre[:, 0] - ext_x < W - 0.5) & (centre[:, 1] + ext_y > 0.5) & (centre[:, 1] - ext_y < H - 0.5)
+    thin = np.minimum(ext_x, ext_y) < 0.5 + 1e-3              # its box can slip between two rows / columns of pixel centres
+    assert (thin | ~inside)[dropped].all(), "a dropped splat must miss every pixel centre of the frame"
+
+
 def check_engine_records(case, res, recs, on_screen):
     """The engine's vertex-stage records (debug_records) against a shader's outputs `res` ([n, 4, 10]) of the same splats."""
     u = case["uniforms"]
@@ -154,12 +164,7 @@ def check_engine_records(case, res, recs, on_screen):
     got = np.stack([(recs[k, 6] & 0xFFFF), (recs[k, 6] >> 16), (recs[k, 7] & 0xFFFF), (recs[k, 7] >> 16)], axis=1) / 65535.0
     np.testing.assert_allclose(got, np.clip(colour[k], 0, 1), rtol=0, atol=tol)
     # every splat the shader draws and the engine drops must be one whose ellipse misses all pixel centres of the frame
-    dropped = drawn & ~on_screen
-    ext_x, ext_y = np.sqrt(b1[:, 0] ** 2 + b2[:, 0] ** 2), np.sqrt(b1[:, 1] ** 2 + b2[:, 1] ** 2)      # half extents of the ellipse's box
-    W, H = u["viewport"]
-    inside = (centre[:, 0] + ext_x > 0.5) & (centre[:, 0] - ext_x < W - 0.5) & (centre[:, 1] + ext_y > 0.5) & (centre[:, 1] - ext_y < H - 0.5)
-    thin = np.minimum(ext_x, ext_y) < 0.5 + 1e-3              # its box can slip between two rows / columns of pixel centres
-    assert (thin | ~inside)[dropped].all(), "a dropped splat must miss every pixel centre of the frame"
+    check_dropped_splats_miss_the_frame(u["viewport"], centre, b1, b2, drawn & ~on_screen)
 
 
 @pytest.mark.gpu
