@@ -137,6 +137,9 @@ SYMBOLS = {
     "gs_tree_get_info": (C.c_int, [_VP, C.POINTER(TreeInfo)]),
     "gs_tree_read": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "gs_tree_gather": (C.c_int, [_VP, C.POINTER(GatherParams), _VP, C.POINTER(C.c_uint32), _VP]),
+    "gs_tree_create_scenes": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
+    "gs_tree_scene_leaves": (C.c_int, [_VP, _VP]),
+    "gs_tree_gather_scenes": (C.c_int, [_VP, C.POINTER(GatherParams), _VP, C.c_uint32, _VP, C.POINTER(C.c_uint32), _VP]),
     "gs_sorter_last_stats": (C.c_int, [_VP, C.POINTER(SortStats)]),
     "gs_mesh_create": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "gs_mesh_destroy": (None, [_VP]),

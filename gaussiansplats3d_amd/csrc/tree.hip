@@ -30,6 +30,8 @@ struct TreeLeaf {
     uint32_t begin, count;      // slice of gs_tree::indexes
 };
 
+constexpr uint32_t TREE_STAGE_SLOTS = 4;      // pinned staging slots for the scenes' modelViews of a tree of several sub-trees
+
 struct gs_tree {
     gs_context* ctx = nullptr;
     uint32_t max_depth = 8, max_centers = 1000;
@@ -46,6 +48,20 @@ struct gs_tree {
     DevBuf d_center, d_size, d_begin, d_count, d_indexes;
     DevBuf d_bucket;            // uint64 hist [TREE_BUCKETS] | uint64 start [TREE_BUCKETS] | uint32 fill [TREE_BUCKETS] | uint64 chunk sums
     DevBuf d_key, d_rank, d_offset, d_total, d_out;   // d_total: {splats gathered, leaves kept}
+    // one sub-tree per scene (gs_tree_create_scenes, the reference's dynamic mode); a plain tree is one scene and uses none of it
+    uint32_t scene_count = 1;
+    std::vector<uint32_t> scene_first_leaf;   // [scene_count + 1]: where each sub-tree's leaves start in `leaves`
+    std::vector<double> scene_box;            // [6 * scene_count]: sceneMin xyz, sceneMax xyz of each sub-tree
+    std::vector<uint8_t> scene_empty;         // [scene_count]: the filter kept nothing of the scene (no box)
+    DevBuf d_scene, d_scene_mv;               // uint32 scene per leaf; double [16 * scene_count] modelViews of the gather in flight
+    double* mv_stage = nullptr;               // pinned: TREE_STAGE_SLOTS x 16 * scene_count doubles
+    hipEvent_t mv_stage_read[TREE_STAGE_SLOTS] = {};   // recorded behind the copy out of each slot
+    uint32_t mv_stage_next = 0;
+    ~gs_tree() {
+        for (hipEvent_t e : mv_stage_read)
+            if (e) (void)hipEventDestroy(e);
+        if (mv_stage) (void)hipHostFree(mv_stage);
+    }
 };
 
 namespace {
@@ -498,6 +514,25 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_tree_test(GatherParams p, Plan
     if (kb != TREE_INF) atomicAdd(&B.hist[tree_bucket(k, scale)], (1ull << 40) | (unsigned long long)B.count[i]);
 }
 
+// k_tree_test for a tree of several sub-trees (dynamic mode, Viewer.js:2005-2011): every leaf is tested under the modelView of
+// its own scene, read from a table of 16 doubles per scene (up to 4 KiB: too much to ride along as kernel arguments).  A kernel
+// of its own, so that k_tree_test stays what it is; everything else of the plan works on the flat leaf table and is shared.
+__global__ __launch_bounds__(PLAN_THREADS) void k_tree_test_scenes(GatherParams p, PlanBuffers B, double scale, double prev_scale,
+                                                                    const uint32_t* __restrict__ leaf_scene,
+                                                                    const double* __restrict__ scene_mv) {
+    const uint32_t i = blockIdx.x * PLAN_THREADS + threadIdx.x;
+    if (i >= p.leaves) return;
+    const unsigned long long old = B.key[i];
+    if (old != TREE_INF) B.fill[tree_bucket(__longlong_as_double((long long)old), prev_scale)] = 0u;
+    const double* mv = scene_mv + 16 * (size_t)leaf_scene[i];
+#pragma unroll
+    for (int k = 0; k < 16; k++) p.mv[k] = mv[k];
+    const double k = tree_leaf_key(p, B.center[3 * (size_t)i], B.center[3 * (size_t)i + 1], B.center[3 * (size_t)i + 2], B.size[i]);
+    const unsigned long long kb = (unsigned long long)__double_as_longlong(k);
+    B.key[i] = kb;
+    if (kb != TREE_INF) atomicAdd(&B.hist[tree_bucket(k, scale)], (1ull << 40) | (unsigned long long)B.count[i]);
+}
+
 __global__ __launch_bounds__(PLAN_THREADS) void k_tree_scan(PlanBuffers B) {
     __shared__ unsigned long long s_w[4];
     const uint32_t tid = threadIdx.x, wg = blockIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -619,21 +654,13 @@ __global__ __launch_bounds__(64 * COPY_WAVES) void k_tree_copy(uint32_t leaves, 
 
 static uint64_t g_tree_uid = 0;
 
-extern "C" {
+namespace {
 
-int gs_tree_create(gs_context* ctx, const float* centers, const uint8_t* keep, uint32_t count, uint32_t first_index,
-                   uint32_t max_depth, uint32_t max_centers_per_node, gs_tree** out) {
-    GS_REQUIRE(out && (centers || count == 0), "out / centers == NULL");
-    *out = nullptr;
-    GS_REQUIRE(max_centers_per_node > 0, "max_centers_per_node == 0");
-    gs_tree* t = new (std::nothrow) gs_tree();
-    if (!t) return GS_ERR_NOMEM;
-    t->ctx = ctx;
-    t->uid = ++g_tree_uid;
-    t->max_depth = max_depth;
-    t->max_centers = max_centers_per_node;
+// buildSubTree + processSplatTreeNode (SplatTree.js:132-246) over `count` centres whose global indexes start at first_index:
+// root box over the FILTERED centres, root list in upload order, leaves and their index lists into t
+int tree_build(gs_tree* t, gs_context* ctx, const float* centers, const uint8_t* keep, uint32_t count, uint32_t first_index,
+               bool* kept_any) {
     try {
-        // buildSubTree, SplatTree.js:218-246: bounds over the FILTERED centres, root list in upload order
         std::vector<uint32_t> root;
         root.reserve(count);
         bool first = true;
@@ -647,21 +674,19 @@ int gs_tree_create(gs_context* ctx, const float* centers, const uint8_t* keep, u
             first = false;
             root.push_back(i);
         }
+        if (kept_any) *kept_any = !root.empty();
         // with a context: level-synchronous build on the device (same leaves, see tree_build_device); the recursive host
         // builder serves host-only trees, empty inputs and the degenerate case of a membership buffer that overflows
         int dev = GS_ERR_CAPACITY;
         if (ctx && !root.empty() && !getenv("GSPLAT_TREE_HOST_BUILD")) {
             dev = tree_build_device(t, ctx, centers, root, count, first_index);
-            if (dev < 0 && dev != GS_ERR_CAPACITY) {
-                delete t;
-                return dev;
-            }
+            if (dev < 0 && dev != GS_ERR_CAPACITY) return dev;
         }
         t->built_on_device = dev == GS_OK;
         if (!t->built_on_device) {
             t->leaves.clear(); t->indexes.clear();
             t->nodes = t->all_leaves = 0;
-            BuildCtx b = {centers, first_index, max_depth, max_centers_per_node, std::vector<uint8_t>(count, 0), t};
+            BuildCtx b = {centers, first_index, t->max_depth, t->max_centers, std::vector<uint8_t>(count, 0), t};
             Box box;
             for (int k = 0; k < 3; k++) {
                 box.mn[k] = t->scene_min[k];
@@ -670,55 +695,187 @@ int gs_tree_create(gs_context* ctx, const float* centers, const uint8_t* keep, u
             process_node(b, box, 0, root);
         }
     } catch (const std::bad_alloc&) {
-        delete t;
         gs_set_error("out of host memory while building the splat tree");
         return GS_ERR_NOMEM;
     }
-    if (ctx) {
-        ScopedDevice sd(ctx->device);
-        const size_t L = t->leaves.size();
-        std::vector<double> center(3 * L), size(L);
-        std::vector<uint32_t> begin(L), cnt(L);
-        for (size_t i = 0; i < L; i++) {
-            const TreeLeaf& lf = t->leaves[i];
-            for (int k = 0; k < 3; k++) center[3 * i + k] = lf.center[k];
-            // nodeSize: tempMax.copy(node.max).sub(node.min).length(), Viewer.js:1983-1986
-            const double dx = lf.mx[0] - lf.mn[0], dy = lf.mx[1] - lf.mn[1], dz = lf.mx[2] - lf.mn[2];
-            size[i] = sqrt(dx * dx + dy * dy + dz * dz);
-            begin[i] = lf.begin;
-            cnt[i] = lf.count;
-        }
-        int st = GS_OK;
-        auto A = [&](DevBuf& buf, size_t bytes) { if (st == GS_OK) st = buf.alloc(bytes); };
-        A(t->d_center, 24 * L + 24); A(t->d_size, 8 * L + 8); A(t->d_begin, 4 * L + 4); A(t->d_count, 4 * L + 4);
-        if (!t->built_on_device) A(t->d_indexes, 4 * t->indexes.size() + 4);      // the device build left them there
-        A(t->d_key, 8 * L + 8); A(t->d_rank, 4 * L + 4); A(t->d_offset, 4 * L + 4);
-        A(t->d_bucket, (size_t)TREE_BUCKETS * (8 + 8 + 4) + 8 * PLAN_GRID);
-        A(t->d_total, 64);                        // {splats gathered, kept leaves}
-        if (st != GS_OK) {
-            delete t;
-            return st;
-        }
-        hipStream_t s = ctx->stream;
-        hipError_t e = hipSuccess;
-        auto UP = [&](DevBuf& buf, const void* src, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s);
-        };
-        UP(t->d_center, center.data(), 24 * L); UP(t->d_size, size.data(), 8 * L); UP(t->d_begin, begin.data(), 4 * L);
-        UP(t->d_count, cnt.data(), 4 * L);
-        if (!t->built_on_device) UP(t->d_indexes, t->indexes.data(), 4 * t->indexes.size());
-        if (e == hipSuccess) e = hipMemsetAsync(t->d_total.p, 0, 64, s);
-        if (e == hipSuccess) e = hipMemsetAsync(t->d_bucket.p, 0, (size_t)TREE_BUCKETS * (8 + 8 + 4) + 8 * PLAN_GRID, s);   // the gather kernels keep hist / fill zero
-        std::vector<unsigned long long> inf(L + 1, TREE_INF);          // "no previous gather": nothing for k_tree_test to reset
-        UP(t->d_key, inf.data(), 8 * L);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            gs_set_error("uploading the splat tree failed: %s", hipGetErrorString(e));
-            delete t;
-            return GS_ERR_HIP;
-        }
+    return GS_OK;
+}
+
+// the device mirror of the flat leaf table and the plan's tables (t->ctx != NULL)
+int tree_upload(gs_tree* t) {
+    gs_context* ctx = t->ctx;
+    ScopedDevice sd(ctx->device);
+    const size_t L = t->leaves.size();
+    std::vector<double> center(3 * L), size(L);
+    std::vector<uint32_t> begin(L), cnt(L);
+    for (size_t i = 0; i < L; i++) {
+        const TreeLeaf& lf = t->leaves[i];
+        for (int k = 0; k < 3; k++) center[3 * i + k] = lf.center[k];
+        // nodeSize: tempMax.copy(node.max).sub(node.min).length(), Viewer.js:1983-1986
+        const double dx = lf.mx[0] - lf.mn[0], dy = lf.mx[1] - lf.mn[1], dz = lf.mx[2] - lf.mn[2];
+        size[i] = sqrt(dx * dx + dy * dy + dz * dz);
+        begin[i] = lf.begin;
+        cnt[i] = lf.count;
+    }
+    int st = GS_OK;
+    auto A = [&](DevBuf& buf, size_t bytes) { if (st == GS_OK) st = buf.alloc(bytes); };
+    A(t->d_center, 24 * L + 24); A(t->d_size, 8 * L + 8); A(t->d_begin, 4 * L + 4); A(t->d_count, 4 * L + 4);
+    if (!t->built_on_device) A(t->d_indexes, 4 * t->indexes.size() + 4);      // the device build left them there
+    A(t->d_key, 8 * L + 8); A(t->d_rank, 4 * L + 4); A(t->d_offset, 4 * L + 4);
+    A(t->d_bucket, (size_t)TREE_BUCKETS * (8 + 8 + 4) + 8 * PLAN_GRID);
+    A(t->d_total, 64);                        // {splats gathered, kept leaves}
+    if (st != GS_OK) return st;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipSuccess;
+    auto UP = [&](DevBuf& buf, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s);
+    };
+    UP(t->d_center, center.data(), 24 * L); UP(t->d_size, size.data(), 8 * L); UP(t->d_begin, begin.data(), 4 * L);
+    UP(t->d_count, cnt.data(), 4 * L);
+    if (!t->built_on_device) UP(t->d_indexes, t->indexes.data(), 4 * t->indexes.size());
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_total.p, 0, 64, s);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_bucket.p, 0, (size_t)TREE_BUCKETS * (8 + 8 + 4) + 8 * PLAN_GRID, s);   // the gather kernels keep hist / fill zero
+    std::vector<unsigned long long> inf(L + 1, TREE_INF);          // "no previous gather": nothing for k_tree_test to reset
+    UP(t->d_key, inf.data(), 8 * L);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        gs_set_error("uploading the splat tree failed: %s", hipGetErrorString(e));
+        return GS_ERR_HIP;
+    }
+    return GS_OK;
+}
+
+// Matrix4.multiplyMatrices (three r160), its expression order, fp64, unfused (this file is built with -ffp-contract=off)
+void mat4_multiply(const double* a, const double* b, double* te) {
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++)
+            te[r + 4 * c] = a[r] * b[4 * c] + a[r + 4] * b[4 * c + 1] + a[r + 8] * b[4 * c + 2] + a[r + 12] * b[4 * c + 3];
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_tree_create(gs_context* ctx, const float* centers, const uint8_t* keep, uint32_t count, uint32_t first_index,
+                   uint32_t max_depth, uint32_t max_centers_per_node, gs_tree** out) {
+    GS_REQUIRE(out && (centers || count == 0), "out / centers == NULL");
+    *out = nullptr;
+    GS_REQUIRE(max_centers_per_node > 0, "max_centers_per_node == 0");
+    gs_tree* t = new (std::nothrow) gs_tree();
+    if (!t) return GS_ERR_NOMEM;
+    t->ctx = ctx;
+    t->uid = ++g_tree_uid;
+    t->max_depth = max_depth;
+    t->max_centers = max_centers_per_node;
+    int st = tree_build(t, ctx, centers, keep, count, first_index, nullptr);
+    if (st == GS_OK && ctx) st = tree_upload(t);
+    if (st != GS_OK) {
+        delete t;
+        return st;
     }
     *out = t;
+    return GS_OK;
+}
+
+int gs_tree_create_scenes(gs_context* ctx, const float* centers, const uint8_t* keep, uint32_t scene_count,
+                          const uint32_t* scene_splat_counts, uint32_t max_depth, uint32_t max_centers_per_node, gs_tree** out) {
+    GS_REQUIRE(out && scene_splat_counts, "out / scene_splat_counts == NULL");
+    *out = nullptr;
+    GS_REQUIRE(scene_count >= 1 && scene_count <= GS_MAX_SCENES, "scene_count must be 1 .. GS_MAX_SCENES");
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < scene_count; s++) total += scene_splat_counts[s];
+    GS_REQUIRE(total <= 0xFFFFFFFFull, "more than 2^32 - 1 splats");
+    GS_REQUIRE(centers || total == 0, "centers == NULL");
+    if (scene_count == 1)                 // the reference's single sub-tree: the plain tree, leaf for leaf
+        return gs_tree_create(ctx, centers, keep, scene_splat_counts[0], 0, max_depth, max_centers_per_node, out);
+    GS_REQUIRE(max_centers_per_node > 0, "max_centers_per_node == 0");
+    gs_tree* t = new (std::nothrow) gs_tree();
+    if (!t) return GS_ERR_NOMEM;
+    t->ctx = ctx;
+    t->uid = ++g_tree_uid;
+    t->max_depth = max_depth;
+    t->max_centers = max_centers_per_node;
+    t->scene_count = scene_count;
+    int st = GS_OK;
+    try {
+        t->scene_first_leaf.assign(scene_count + 1, 0u);
+        t->scene_box.assign(6 * (size_t)scene_count, 0.0);
+        t->scene_empty.assign(scene_count, 1);
+        std::vector<uint32_t> leaf_scene;
+        uint32_t first_index = 0;
+        bool any = false;
+        for (uint32_t s = 0; s < scene_count && st == GS_OK; s++) {
+            // createSplatTree, SplatTree.js:262-267: one sub-tree per scene, each built as gs_tree_create builds a tree over
+            // the scene's range (its own root box, the same device build)
+            gs_tree sub;
+            sub.ctx = ctx;
+            sub.max_depth = max_depth;
+            sub.max_centers = max_centers_per_node;
+            const uint32_t n = scene_splat_counts[s];
+            bool kept_any = false;
+            st = tree_build(&sub, ctx, centers + 3 * (size_t)first_index, keep ? keep + first_index : nullptr, n, first_index, &kept_any);
+            if (st != GS_OK) break;
+            const uint32_t base = (uint32_t)t->indexes.size();
+            for (TreeLeaf lf : sub.leaves) {
+                lf.begin += base;
+                t->leaves.push_back(lf);
+                leaf_scene.push_back(s);
+            }
+            t->indexes.insert(t->indexes.end(), sub.indexes.begin(), sub.indexes.end());
+            t->nodes += sub.nodes;
+            t->all_leaves += sub.all_leaves;
+            t->scene_first_leaf[s + 1] = (uint32_t)t->leaves.size();
+            t->scene_empty[s] = kept_any ? 0 : 1;
+            for (int k = 0; k < 3; k++) {
+                t->scene_box[6 * (size_t)s + k] = sub.scene_min[k];
+                t->scene_box[6 * (size_t)s + 3 + k] = sub.scene_max[k];
+                if (!kept_any) continue;
+                if (!any || sub.scene_min[k] < t->scene_min[k]) t->scene_min[k] = sub.scene_min[k];
+                if (!any || sub.scene_max[k] > t->scene_max[k]) t->scene_max[k] = sub.scene_max[k];
+            }
+            any = any || kept_any;
+            first_index += n;
+        }
+        t->built_on_device = false;         // the sub-trees' lists were concatenated on the host: tree_upload sends them
+        if (st == GS_OK && ctx) {
+            st = tree_upload(t);
+            const size_t L = t->leaves.size(), mv_bytes = 128 * (size_t)scene_count;
+            ScopedDevice sd(ctx->device);
+            if (st == GS_OK) st = t->d_scene.alloc(4 * L + 4);
+            if (st == GS_OK) st = t->d_scene_mv.alloc(mv_bytes);
+            hipError_t e = hipSuccess;
+            if (st == GS_OK) {
+                e = hipHostMalloc((void**)&t->mv_stage, TREE_STAGE_SLOTS * mv_bytes, hipHostMallocDefault);
+                for (uint32_t k = 0; k < TREE_STAGE_SLOTS && e == hipSuccess; k++)
+                    e = hipEventCreateWithFlags(&t->mv_stage_read[k], hipEventDisableTiming);
+                if (e == hipSuccess && L) e = hipMemcpyAsync(t->d_scene.p, leaf_scene.data(), 4 * L, hipMemcpyHostToDevice, ctx->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                if (e != hipSuccess) {
+                    gs_set_error("uploading the splat tree's scene table failed: %s", hipGetErrorString(e));
+                    st = GS_ERR_HIP;
+                }
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        gs_set_error("out of host memory while building the splat tree");
+        st = GS_ERR_NOMEM;
+    }
+    if (st != GS_OK) {
+        delete t;
+        return st;
+    }
+    *out = t;
+    return GS_OK;
+}
+
+int gs_tree_scene_leaves(gs_tree* t, uint32_t* first_leaf) {
+    GS_REQUIRE(t && first_leaf, "tree / first_leaf == NULL");
+    if (t->scene_count == 1) {
+        first_leaf[0] = 0u;
+        first_leaf[1] = (uint32_t)t->leaves.size();
+    } else {
+        memcpy(first_leaf, t->scene_first_leaf.data(), 4 * ((size_t)t->scene_count + 1));
+    }
     return GS_OK;
 }
 
@@ -768,8 +925,12 @@ int gs_tree_read(gs_tree* t, double* bounds, double* centers, uint32_t* depths, 
     return GS_OK;
 }
 
-int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint32_t* render_count, uint32_t* indexes_out_host) {
-    GS_REQUIRE(t && gp, "tree / params == NULL");
+}  // extern "C"
+
+// gs_tree_gather / gs_tree_gather_scenes.  scene_mv: the modelView of every scene of a tree of several sub-trees (16 doubles
+// each), nullptr for a plain tree, whose only modelView is gp->model_view.
+static int tree_gather(gs_tree* t, const gs_gather_params* gp, const double* scene_mv, gs_sorter* dst, uint32_t* render_count,
+                       uint32_t* indexes_out_host) {
     GS_REQUIRE(render_count || (dst && !indexes_out_host), "render_count == NULL (asynchronous gather) needs a sorter and no host copy");
     GS_REQUIRE(t->ctx != nullptr, "host-only tree (created without a context) cannot gather");
     GS_REQUIRE(!dst || dst->ctx == t->ctx, "sorter lives on another context");
@@ -811,12 +972,16 @@ int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint3
     p.gather_all = gp->gather_all ? 1u : 0u;
     p.leaves = L;
     // bucket scale: the farthest a leaf centre can be from the eye = the farthest corner of the scene box under this modelView
-    // (the distance is convex in the point); the order never depends on it (tree_bucket clamps), only how the leaves spread
+    // (the distance is convex in the point); the order never depends on it (tree_bucket clamps), only how the leaves spread.
+    // Several sub-trees: the largest over the scenes, each scene's box under its own modelView.
     double far = 0.0;
-    for (int c = 0; c < 8; c++) {
-        const double x = (c & 1) ? t->scene_max[0] : t->scene_min[0], y = (c & 2) ? t->scene_max[1] : t->scene_min[1],
-                     z = (c & 4) ? t->scene_max[2] : t->scene_min[2];
-        const double* e = p.mv;
+    for (uint32_t sc = 0; sc < (scene_mv ? 8u * t->scene_count : 8u); sc++) {
+        const uint32_t c = sc & 7u, s = sc >> 3;
+        if (scene_mv && t->scene_empty[s]) continue;
+        const double* mn = scene_mv ? &t->scene_box[6 * (size_t)s] : t->scene_min;
+        const double* mx = scene_mv ? &t->scene_box[6 * (size_t)s + 3] : t->scene_max;
+        const double x = (c & 1) ? mx[0] : mn[0], y = (c & 2) ? mx[1] : mn[1], z = (c & 4) ? mx[2] : mn[2];
+        const double* e = scene_mv ? scene_mv + 16 * (size_t)s : p.mv;
         double w = e[3] * x + e[7] * y + e[11] * z + e[15];
         w = w != 0.0 ? 1.0 / w : 1.0;
         const double vx = (e[0] * x + e[4] * y + e[8] * z + e[12]) * w, vy = (e[1] * x + e[5] * y + e[9] * z + e[13]) * w,
@@ -834,7 +999,8 @@ int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint3
     // The copy is DEFERRED to the sorter when nothing but the sorter will read the list: a full sort of a static scene then
     // copies the lists, keys them (and tests them against the frustum) in one kernel that streams the centres in leaf order
     // (sorter.hip, k_tree_copy_keys); any other sort copies first (gs_tree_copy_plain) and goes on as before.
-    const bool deferred = dst && !indexes_out_host && !(dst->flags & GS_SORT_DYNAMIC) && !getenv("GSPLAT_TREE_NO_DEFER");
+    // (never for a tree of several sub-trees: the fused copy and its leaf-ordered centre planes know one modelView)
+    const bool deferred = dst && !indexes_out_host && !(dst->flags & GS_SORT_DYNAMIC) && !getenv("GSPLAT_TREE_NO_DEFER") && !scene_mv;
     PlanBuffers pb;
     pb.center = t->d_center.as<double>(); pb.size = t->d_size.as<double>(); pb.count = t->d_count.as<uint32_t>();
     pb.key = t->d_key.as<unsigned long long>();
@@ -851,7 +1017,24 @@ int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint3
         pb.keep_words = (uint32_t)(((size_t)t->indexes.size() + 63) / 64 + 2);
     }
     const uint32_t lgrid = (L + PLAN_THREADS - 1u) / PLAN_THREADS;
-    hipLaunchKernelGGL(k_tree_test, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale, t->prev_scale);
+    if (scene_mv) {
+        // The scenes' modelViews reach the device by a stream-ordered copy out of pinned staging, which the copy engine reads
+        // when the stream gets there - possibly after this call has returned (asynchronous gather).  The staging has
+        // TREE_STAGE_SLOTS slots used in turn, each with an event recorded behind its copy: a slot is rewritten only after that
+        // event has passed, so no copy in flight ever reads a later gather's matrices.  The device table itself is rewritten in
+        // stream order, like every other table of the plan.
+        const uint32_t slot = t->mv_stage_next;
+        t->mv_stage_next = (slot + 1u) % TREE_STAGE_SLOTS;
+        const size_t mv_count = 16 * (size_t)t->scene_count;
+        GS_HIP(hipEventSynchronize(t->mv_stage_read[slot]));
+        memcpy(t->mv_stage + slot * mv_count, scene_mv, 8 * mv_count);
+        GS_HIP(hipMemcpyAsync(t->d_scene_mv.p, t->mv_stage + slot * mv_count, 8 * mv_count, hipMemcpyHostToDevice, st));
+        GS_HIP(hipEventRecord(t->mv_stage_read[slot], st));
+        hipLaunchKernelGGL(k_tree_test_scenes, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale, t->prev_scale,
+                           t->d_scene.as<uint32_t>(), t->d_scene_mv.as<double>());
+    } else {
+        hipLaunchKernelGGL(k_tree_test, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale, t->prev_scale);
+    }
     hipLaunchKernelGGL(k_tree_scan, dim3(PLAN_GRID), dim3(PLAN_THREADS), 0, st, pb);
     hipLaunchKernelGGL(k_tree_fill, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale);
     hipLaunchKernelGGL(k_tree_offsets, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale);
@@ -888,6 +1071,36 @@ int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint3
         dst->has_gathered = true;
     }
     return GS_OK;
+}
+
+extern "C" {
+
+int gs_tree_gather_scenes(gs_tree* t, const gs_gather_params* gp, const double* scene_transforms, uint32_t transform_count,
+                          gs_sorter* dst, uint32_t* render_count, uint32_t* indexes_out_host) {
+    GS_REQUIRE(t && gp, "tree / params == NULL");
+    GS_REQUIRE(t->ctx != nullptr, "host-only tree (created without a context) cannot gather");
+    if (scene_transforms && transform_count != t->scene_count) {
+        gs_set_error("invalid argument: %u scene transforms for a tree of %u scenes", transform_count, t->scene_count);
+        return GS_ERR_INVALID;
+    }
+    // Viewer.js:2007-2011: modelView = baseModelView x sceneTransform(s); no transforms = every scene under the base
+    double mv[16 * GS_MAX_SCENES];
+    for (uint32_t s = 0; s < t->scene_count; s++) {
+        if (scene_transforms) mat4_multiply(gp->model_view, scene_transforms + 16 * (size_t)s, mv + 16 * (size_t)s);
+        else memcpy(mv + 16 * (size_t)s, gp->model_view, sizeof(gp->model_view));
+    }
+    if (t->scene_count == 1) {             // a plain tree: its one modelView rides along with the kernel arguments, as ever
+        gs_gather_params one = *gp;
+        memcpy(one.model_view, mv, sizeof(one.model_view));
+        return tree_gather(t, &one, nullptr, dst, render_count, indexes_out_host);
+    }
+    return tree_gather(t, gp, mv, dst, render_count, indexes_out_host);
+}
+
+int gs_tree_gather(gs_tree* t, const gs_gather_params* gp, gs_sorter* dst, uint32_t* render_count, uint32_t* indexes_out_host) {
+    GS_REQUIRE(t && gp, "tree / params == NULL");
+    if (t->scene_count > 1) return gs_tree_gather_scenes(t, gp, nullptr, 0, dst, render_count, indexes_out_host);
+    return tree_gather(t, gp, nullptr, dst, render_count, indexes_out_host);
 }
 
 }  // extern "C"

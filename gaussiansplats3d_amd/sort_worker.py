@@ -117,12 +117,16 @@ class SortWorker:
                               "indexesToSort": indexes, "transforms": np.tile(np.eye(4, dtype=np.float32).reshape(16), 32)},
                              keep_on_device=True)
 
-    def sort_gathered(self, mvp, sort_count=None, keep_on_device=False, precomputed_on_device=False):
+    def sort_gathered(self, mvp, sort_count=None, keep_on_device=False, precomputed_on_device=False, transforms=None):
         """Sort the device-resident indexesToSort list (and splatRenderCount) the last
         ``SplatTree.gather_scene_nodes_for_sort(..., sort_worker=self)`` produced.  precomputed_on_device: key it by the
-        distances ``SplatMesh.compute_distances_on_gpu(..., sort_worker=self)`` left on the device."""
+        distances ``SplatMesh.compute_distances_on_gpu(..., sort_worker=self)`` left on the device.  transforms (dynamic mode):
+        the scenes' matrices as in a `sort` message; identity when omitted."""
         mvp = np.ascontiguousarray(np.asarray(mvp, dtype=np.float64).astype(np.float32))
         tr = np.tile(np.eye(4, dtype=np.float32).reshape(16), L.GS_MAX_SCENES) if self.dynamic_mode else None
+        if tr is not None and transforms is not None:
+            t_in = np.asarray(transforms, dtype=np.float32).reshape(-1)
+            tr[:t_in.size] = t_in
         stats = L.SortStats()
         # render count is held by the library; ask for the sorted list only when the caller wants it on the host
         out = None if keep_on_device else np.empty(self.gathered_count, dtype=np.uint32)

@@ -24,6 +24,7 @@ class SplatTree:
         self.max_centers_per_node = int(max_centers_per_node)
         self.handle = C.c_void_p()
         self.splat_count = 0
+        self.scene_count = 1
         self._splats = None           # splats held by the leaves (info().splats), cached for asynchronous gathers
         if context is not None:
             context._adopt(self)
@@ -40,8 +41,36 @@ class SplatTree:
                                         keep.ctypes.data if keep is not None else None, c.shape[0], int(first_index),
                                         self.max_depth, self.max_centers_per_node, C.byref(self.handle)))
         self.splat_count = c.shape[0]
+        self.scene_count = 1
         self._splats = None
         return self
+
+    def process_splat_mesh_scenes(self, centers, scene_counts, alphas=None, min_alphas=None):
+        """SplatTree.processSplatMesh of a dynamicMode mesh (SplatTree.js:378-386): one sub-tree per scene over the scene's
+        untransformed centres.  centers float32 [n,3], the scenes back to back; scene_counts their splat counts; alphas uint8
+        [n] with the filter ``alpha >= min_alphas[s]`` per scene (SplatMesh.js:239-244; every minAlpha defaults to 1)."""
+        self.dispose()
+        c = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 3)
+        counts = np.ascontiguousarray(scene_counts, dtype=np.uint32).reshape(-1)
+        if int(counts.astype(np.int64).sum()) != c.shape[0]:
+            raise ValueError("scene_counts sum to %d, centers hold %d splats" % (int(counts.astype(np.int64).sum()), c.shape[0]))
+        keep = None
+        if alphas is not None:
+            mins = np.ones(len(counts)) if min_alphas is None else np.asarray(min_alphas)
+            keep = np.ascontiguousarray(np.asarray(alphas).reshape(-1) >= np.repeat(mins, counts), dtype=np.uint8)
+        L.check(self.lib.gs_tree_create_scenes(self.ctx.handle if self.ctx is not None else None, c.ctypes.data,
+                                               keep.ctypes.data if keep is not None else None, len(counts), counts.ctypes.data,
+                                               self.max_depth, self.max_centers_per_node, C.byref(self.handle)))
+        self.splat_count = c.shape[0]
+        self.scene_count = len(counts)
+        self._splats = None
+        return self
+
+    def scene_leaves(self):
+        """uint32 [scene_count + 1]: where each sub-tree's leaves start in what ``leaves()`` returns."""
+        first = np.empty(self.scene_count + 1, np.uint32)
+        L.check(self.lib.gs_tree_scene_leaves(self.handle, first.ctypes.data))
+        return first
 
     def info(self):
         info = L.TreeInfo()
@@ -60,11 +89,14 @@ class SplatTree:
         return bounds, centers, depths, offsets, indexes
 
     def gather_scene_nodes_for_sort(self, camera, sort_worker=None, gather_all_nodes=False, mesh_world=None,
-                                    fov_deg=cam_math.THREE_FOV_DEG, to_host=True, model_view=None, asynchronous=False):
+                                    fov_deg=cam_math.THREE_FOV_DEG, to_host=True, model_view=None, asynchronous=False,
+                                    scene_transforms=None):
         """Viewer.gatherSceneNodesForSort: returns {'splatRenderCount', 'shouldSortAll', 'indexesToSort'}.  With a
         sort worker the list is written into its device buffer (``sort_worker.sort_gathered`` consumes it).
         asynchronous=True (needs a sort worker, no host list): nothing returns to the host - splatRenderCount stays on the
-        device next to the list and the reply carries the tree's splat count as its upper bound."""
+        device next to the list and the reply carries the tree's splat count as its upper bound.
+        scene_transforms (dynamic mode): float64 [scenes,16], SplatMesh.getSceneTransform per scene; scene s is tested under
+        model_view x scene_transforms[s], and model_view is then inverse(camera.matrixWorld) alone (Viewer.js:2000)."""
         gp = L.GatherParams()
         if model_view is not None:        # inverse(camera.matrixWorld) * splatMesh.matrixWorld, already multiplied (fp64)
             mv = np.asarray(model_view, np.float64)
@@ -75,15 +107,23 @@ class SplatTree:
         gp.render_width, gp.render_height = float(camera.width), float(camera.height)
         gp.gather_all = 1 if gather_all_nodes else 0
         count = C.c_uint32(0)
+        if scene_transforms is not None:
+            tr = np.ascontiguousarray(scene_transforms, dtype=np.float64).reshape(-1, 16)
+
+            def gather(dst, render_count, host):
+                return self.lib.gs_tree_gather_scenes(self.handle, C.byref(gp), tr.ctypes.data, tr.shape[0], dst, render_count, host)
+        else:
+            def gather(dst, render_count, host):
+                return self.lib.gs_tree_gather(self.handle, C.byref(gp), dst, render_count, host)
         if asynchronous:
             if self._splats is None:
                 self._splats = int(self.info().splats)
-            L.check(self.lib.gs_tree_gather(self.handle, C.byref(gp), sort_worker.handle, None, None))
+            L.check(gather(sort_worker.handle, None, None))
             sort_worker.gathered_count = self._splats
             return {"splatRenderCount": self._splats, "shouldSortAll": False, "indexesToSort": None, "countOnDevice": True}
         out = np.empty(self.info().splats, dtype=np.uint32) if to_host else None
-        L.check(self.lib.gs_tree_gather(self.handle, C.byref(gp), sort_worker.handle if sort_worker is not None else None,
-                                        C.byref(count), out.ctypes.data if out is not None else None))
+        L.check(gather(sort_worker.handle if sort_worker is not None else None, C.byref(count),
+                       out.ctypes.data if out is not None else None))
         if sort_worker is not None:
             sort_worker.gathered_count = int(count.value)
         return {"splatRenderCount": int(count.value), "shouldSortAll": False,

@@ -225,6 +225,33 @@ typedef struct gs_gather_params {
 int gs_tree_gather(gs_tree* t, const gs_gather_params* params, gs_sorter* dst, uint32_t* render_count,
                    uint32_t* indexes_out_host);
 
+/* The octree of a dynamicMode mesh: SplatTree.processSplatMesh builds ONE SUB-TREE PER SCENE over that scene's untransformed
+ * centres (src/splattree/SplatTree.js:378-390, worker :252-271), and Viewer.gatherSceneNodesForSort tests each sub-tree's
+ * leaves under its own scene's transform and pools the kept leaves of all of them into one list (src/Viewer.js:1999-2055).
+ *   centers / keep       the scenes back to back: scene s owns the global indexes sum(counts[<s]) .. sum(counts[<=s]) - 1
+ *   scene_count          1 .. GS_MAX_SCENES; 1 is gs_tree_create(ctx, centers, keep, counts[0], 0, ...), leaf for leaf
+ *   scene_splat_counts   uint32[scene_count]
+ * Every sub-tree is built as gs_tree_create builds a tree over the scene's range with first_index = the range's start (its
+ * own root box, the same build).  gs_tree_read returns the sub-trees' nodesWithIndexes one after the other, in scene order;
+ * gs_tree_get_info sums the counts and reports the union of the scenes' boxes.  A scene whose filter keeps nothing has no leaf. */
+int gs_tree_create_scenes(gs_context* ctx, const float* centers, const uint8_t* keep, uint32_t scene_count,
+                          const uint32_t* scene_splat_counts, uint32_t max_depth, uint32_t max_centers_per_node, gs_tree** out);
+/* first_leaf uint32[scene_count + 1]: where each sub-tree starts in what gs_tree_read returns ({0, leaves} for a tree from
+ * gs_tree_create). */
+int gs_tree_scene_leaves(gs_tree* t, uint32_t* first_leaf);
+/* gs_tree_gather with one modelView per scene; dst / render_count / indexes_out_host as there (synchronous and asynchronous
+ * forms, host copy, sorter hand-over).
+ *   params->model_view   the BASE matrix.  In dynamic mode the reference does NOT multiply splatMesh.matrixWorld into it
+ *                        (src/Viewer.js:2000): pass inverse(camera.matrixWorld) alone
+ *   scene_transforms     double[16 * transform_count], column-major, SplatMesh.getSceneTransform(s); scene s is tested under
+ *                        base x transform_s (Matrix4.multiplyMatrices' expression order, fp64, unfused).  NULL: every scene is
+ *                        tested under the base (transform_count is then ignored)
+ *   transform_count      must equal the tree's scene count, else GS_ERR_INVALID
+ * Leaves at the same distance keep the order in which the reference appends them: sub-tree first, nodesWithIndexes second.
+ * A tree of several sub-trees never defers its copy to the sorter.  gs_tree_gather on such a tree is this call with NULL. */
+int gs_tree_gather_scenes(gs_tree* t, const gs_gather_params* params, const double* scene_transforms, uint32_t transform_count,
+                          gs_sorter* dst, uint32_t* render_count, uint32_t* indexes_out_host);
+
 /* ------------------------------------------------------------------------------------------------ *
  * ASSETS (host side, no GPU needed): the reference's file readers up to the arrays the seams consume
  * ------------------------------------------------------------------------------------------------ */

@@ -482,20 +482,24 @@ export class SplatMesh {
       const centers = new Float32Array(total * 3), colors = new Uint8Array(total * 4);
       // getSplatCenter / getSplatColor of every splat (:239-244): scene transforms applied as for a static mesh, alpha filter
       this.fillSplatDataArrays(null, null, null, centers, null, null, this.dynamicMode ? false : true);
-      const keep = new Uint8Array(splatCount);
+      const keep = new Uint8Array(splatCount), sceneSplatCounts = new Uint32Array(this.scenes.length);
       let dest = 0;
       for (const sc of this.scenes) {
         const s = this.scenes.indexOf(sc), buffer = sc.splatBuffer, n = buffer.getSplatCount();
+        sceneSplatCounts[s] = n;
         buffer.fillSplatColorArray(colors, 0, undefined, undefined, dest);
         const minAlpha = minAlphas[s] || 1;
         for (let i = 0; i < n; i++) keep[dest + i] = colors[4 * (dest + i) + 3] >= minAlpha ? 1 : 0;
         dest += n;
       }
       if (onSplatTreeIndexesUpload) onSplatTreeIndexesUpload(false);
-      const handle = addon.treeCreate(this.core.ctx.handle, centers, keep, splatCount, 0, 8, 1000);      // maxDepth 8, 1000 per node (:236)
+      // maxDepth 8, 1000 per node (:236).  dynamicMode: one sub-tree per scene over the scene's untransformed centres
+      // (SplatTree.js:378-386); otherwise the one tree over every (transformed) centre
+      const handle = this.dynamicMode ? addon.treeCreateScenes(this.core.ctx.handle, centers, keep, sceneSplatCounts, 8, 1000) :
+                                        addon.treeCreate(this.core.ctx.handle, centers, keep, splatCount, 0, 8, 1000);
       if (onSplatTreeIndexesUpload) onSplatTreeIndexesUpload(true);
       if (onSplatTreeConstruction) onSplatTreeConstruction(false);
-      this.splatTree = this.baseSplatTree = new HipSplatTree(handle, this);
+      this.splatTree = this.baseSplatTree = new HipSplatTree(handle, this, this.dynamicMode ? this.scenes.length : 1);
       if (onSplatTreeConstruction) onSplatTreeConstruction(true);
       resolve();
     });
@@ -513,9 +517,9 @@ export class SplatMesh {
 // SplatTree in the shape Viewer.gatherSceneNodesForSort walks (src/Viewer.js:1998-2059, src/splattree/SplatTree.js:275-318):
 // subTrees[s].nodesWithIndexes[k] = {min, max, center: THREE.Vector3, data: {indexes}}.  The leaves come from gs_tree_read
 // (built on the device, bit-identical to the reference's worker); `gather(...)` is the engine's own device-side gather for
-// callers that skip the JS walk.
+// callers that skip the JS walk.  A dynamicMode mesh has one sub-tree per scene (sceneCount of them), a static one a single one.
 class HipSplatTree {
-  constructor(handle, splatMesh) {
+  constructor(handle, splatMesh, sceneCount = 1) {
     this.handle = handle;
     this.splatMesh = splatMesh;
     this.maxDepth = 8;
@@ -528,11 +532,32 @@ class HipSplatTree {
                    center: new THREE.Vector3(t.centers[3 * k], t.centers[3 * k + 1], t.centers[3 * k + 2]), depth: t.depths[k],
                    data: { indexes: t.indexes.subarray(t.offsets[k], t.offsets[k + 1]) }, children: [], id: k });
     }
-    this.subTrees = [{ nodesWithIndexes: nodes, maxDepth: this.maxDepth, maxCentersPerNode: this.maxCentersPerNode }];
+    const first = sceneCount > 1 ? addon.treeSceneLeaves(handle, sceneCount) : [0, nodes.length];
+    this.subTrees = [];
+    for (let s = 0; s < sceneCount; s++) {
+      this.subTrees.push({ nodesWithIndexes: nodes.slice(first[s], first[s + 1]), maxDepth: this.maxDepth, maxCentersPerNode: this.maxCentersPerNode });
+    }
+    this.sceneCount = sceneCount;
+    this.splats = info.splats;
     this.leaves = info.allLeaves;
   }
   countLeaves() { return this.leaves; }
-  visitLeaves(visitFunc) { for (const node of this.subTrees[0].nodesWithIndexes) visitFunc(node); }
+  visitLeaves(visitFunc) { for (const subTree of this.subTrees) for (const node of subTree.nodesWithIndexes) visitFunc(node); }
+  // Viewer.gatherSceneNodesForSort (src/Viewer.js:1987-2060) on the device.  camera: {fov, matrixWorld}; renderDimensions: {x, y};
+  // sorter: a device sorter's handle whose indexesToSort receives the list, or null; out: Uint32Array(splats) for a host copy,
+  // or null.  Returns {splatRenderCount, shouldSortAll}.  dynamicMode: the base is inverse(camera.matrixWorld) alone (:2000) and
+  // every sub-tree is tested under base x getSceneTransform(s).
+  gather(camera, renderDimensions, gatherAllNodes = false, sorter = null, out = null) {
+    const mesh = this.splatMesh, base = new THREE.Matrix4().copy(camera.matrixWorld).invert();
+    const args = [this.handle, Float64Array.from(base.elements), camera.fov, renderDimensions.x, renderDimensions.y, gatherAllNodes ? 1 : 0];
+    if (!mesh.dynamicMode) {
+      args[1] = Float64Array.from(base.multiply(mesh.matrixWorld).elements);
+      return { splatRenderCount: addon.treeGather(...args, sorter, out), shouldSortAll: false };
+    }
+    const transforms = new Float64Array(16 * this.sceneCount), matrix = new THREE.Matrix4();
+    for (let s = 0; s < this.sceneCount; s++) { mesh.getSceneTransform(s, matrix); transforms.set(matrix.elements, 16 * s); }
+    return { splatRenderCount: addon.treeGatherScenes(...args, transforms, sorter, out), shouldSortAll: false };
+  }
   dispose() { if (this.handle) { addon.treeDestroy(this.handle); this.handle = null; } }
 }
 

@@ -680,6 +680,44 @@ static napi_value TreeCreate(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_external(env, t, NULL, NULL, &r));
     return r;
 }
+/* treeCreateScenes(ctx|null, centers Float32Array(3n), keep Uint8Array|null, sceneSplatCounts Uint32Array(scenes), maxDepth,
+ *                  maxCentersPerNode): one sub-tree per scene (gs_tree_create_scenes), the scenes' centres back to back */
+static napi_value TreeCreateScenes(napi_env env, napi_callback_info info) {
+    ARGS(6)
+    void *c, *k, *sc;
+    size_t cb, kb, sb;
+    if (!get_bytes(env, argv[1], &c, &cb) || !get_bytes(env, argv[2], &k, &kb) || !get_bytes(env, argv[3], &sc, &sb) || !sc) {
+        napi_throw_type_error(env, NULL, "treeCreateScenes: bad buffer");
+        return NULL;
+    }
+    const uint32_t scenes = (uint32_t)(sb / 4);
+    uint64_t count = 0;
+    for (uint32_t s = 0; s < scenes; s++) count += ((const uint32_t*)sc)[s];
+    if (cb < count * 12 || (k && kb < count)) { napi_throw_range_error(env, NULL, "treeCreateScenes: buffer shorter than the scenes' splat counts"); return NULL; }
+    gs_tree* t = NULL;
+    int st;
+
+    LOCKED(st = gs_tree_create_scenes((gs_context*)get_external(env, argv[0]), (const float*)c, (const uint8_t*)k, scenes, (const uint32_t*)sc,
+                                   get_u32(env, argv[4]), get_u32(env, argv[5]), &t));
+    if (st < 0) return throw_gs(env, st);
+    napi_value r;
+    NAPI_OK(napi_create_external(env, t, NULL, NULL, &r));
+    return r;
+}
+/* treeSceneLeaves(tree, sceneCount) -> Uint32Array(sceneCount + 1): where each sub-tree starts in treeRead's leaves */
+static napi_value TreeSceneLeaves(napi_env env, napi_callback_info info) {
+    ARGS(2)
+    const uint32_t scenes = get_u32(env, argv[1]);
+    if (scenes < 1 || scenes > GS_MAX_SCENES) { napi_throw_range_error(env, NULL, "treeSceneLeaves: sceneCount"); return NULL; }
+    void* first;
+    napi_value ab, ta;
+    int st;
+    NAPI_OK(napi_create_arraybuffer(env, 4 * ((size_t)scenes + 1), &first, &ab));
+    LOCKED(st = gs_tree_scene_leaves((gs_tree*)get_external(env, argv[0]), (uint32_t*)first));
+    if (st < 0) return throw_gs(env, st);
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, (size_t)scenes + 1, ab, 0, &ta));
+    return ta;
+}
 static napi_value TreeDestroy(napi_env env, napi_callback_info info) {
     ARGS(1)
     LOCKED(gs_tree_destroy((gs_tree*)get_external(env, argv[0])));
@@ -755,6 +793,36 @@ static napi_value TreeGather(napi_env env, napi_callback_info info) {
     int st;
 
     LOCKED(st = gs_tree_gather(t, &gp, (gs_sorter*)get_external(env, argv[6]), &render_count, (uint32_t*)out));
+    if (st < 0) return throw_gs(env, st);
+    return num(env, render_count);
+}
+/* treeGatherScenes(tree, baseModelView Float64Array(16), fovYDeg, renderWidth, renderHeight, gatherAll,
+ *                  sceneTransforms Float64Array(16 * scenes)|null, sorter|null, out Uint32Array|null) -> splatRenderCount
+ * (gs_tree_gather_scenes: scene s is tested under baseModelView x sceneTransforms[s]) */
+static napi_value TreeGatherScenes(napi_env env, napi_callback_info info) {
+    ARGS(9)
+    gs_gather_params gp;
+    memset(&gp, 0, sizeof gp);
+    void *mv, *tr, *out;
+    size_t mb, tb, ob;
+    if (!get_bytes(env, argv[1], &mv, &mb) || mb < 128 || !get_bytes(env, argv[6], &tr, &tb) || tb % 128 || !get_bytes(env, argv[8], &out, &ob)) {
+        napi_throw_type_error(env, NULL, "treeGatherScenes: baseModelView must be a Float64Array(16), sceneTransforms a Float64Array(16 * scenes)");
+        return NULL;
+    }
+    memcpy(gp.model_view, mv, 128);
+    gp.fov_y_deg = get_f64(env, argv[2]);
+    gp.render_width = get_f64(env, argv[3]);
+    gp.render_height = get_f64(env, argv[4]);
+    gp.gather_all = get_u32(env, argv[5]);
+    gs_tree_info ti;
+    gs_tree* t = (gs_tree*)get_external(env, argv[0]);
+    if (gs_tree_get_info(t, &ti) < 0) return throw_gs(env, GS_ERR_INVALID);
+    if (out && ob < (size_t)ti.splats * 4) { napi_throw_range_error(env, NULL, "treeGatherScenes: out shorter than the tree's splat count"); return NULL; }
+    uint32_t render_count = 0;
+    int st;
+
+    LOCKED(st = gs_tree_gather_scenes(t, &gp, (const double*)tr, (uint32_t)(tb / 128), (gs_sorter*)get_external(env, argv[7]), &render_count,
+                                   (uint32_t*)out));
     if (st < 0) return throw_gs(env, st);
     return num(env, render_count);
 }
@@ -986,7 +1054,8 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"meshUploadSceneIndexes", MeshUploadSceneIndexes},                   {"meshSetScenes", MeshSetScenes},
         {"sorterBindMesh", SorterBindMesh}, {"sorterSetFrustumCull", SorterSetFrustumCull}, {"sorterSortGathered", SorterSortGathered},
         {"treeCreate", TreeCreate},         {"treeDestroy", TreeDestroy},     {"treeInfo", TreeInfo},
-        {"treeGather", TreeGather},         {"treeRead", TreeRead},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
+        {"treeGather", TreeGather},         {"treeRead", TreeRead},         {"treeCreateScenes", TreeCreateScenes},
+        {"treeSceneLeaves", TreeSceneLeaves}, {"treeGatherScenes", TreeGatherScenes},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
