@@ -196,6 +196,7 @@ struct gs_context {
     bool lds_atomic_lane_order = false;   // self-test result: ds_add_rtn serves same-address lanes in lane order
     RadixScratch radix;                   // scratch of the create-time self-test
     std::vector<gs_mesh*> live_meshes;    // so that a sorter bound to a mesh never dereferences a destroyed one
+    std::vector<gs_sorter*> live_sorters; // so that gs_mesh_remove finds the sorters bound to the mesh
 };
 
 struct RadixExec {                        // where and with what scratch a radix pass runs
@@ -460,6 +461,7 @@ struct gs_mesh {
     DevBuf perm;               // uint32 [n]: original splat index -> internal (Morton-ordered) position
     DevBuf inv_perm;           // uint32 [n]: internal position -> original splat index
     SlottedRanges slotted;     // the splats that own storage slots (upload_plan.hpp)
+    std::vector<SlotRange> runs;   // the Morton runs: the span of every fresh segment, sorted, never merged (gs_mesh_remove, mesh_edit.hip)
     bool reorder = true;
     uint32_t layout_version = 0;   // bumped whenever splats receive storage slots (perm changes): a sorter's per-tree payload cache
     bool no_block_cull = false;    // GSPLAT_NO_BLOCK_CULL=1 (A/B and tests)
@@ -574,6 +576,21 @@ struct MeshUploadSource {
 int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSource& src);
 // what follows the AoS x4 centres of [from, from + count) landing in gs_sorter::caos, on the sorter's stream (sorter.hip)
 int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const uint32_t* scene_indexes);
+
+// Removing splats (mesh_edit.hip; gs_sorter_remove in sorter.hip).  The cuts of a RemovePlan as the gather kernel's argument:
+struct RemoveMap {
+    uint32_t n;                            // cuts
+    uint32_t new_begin[REMOVE_MAX_RANGES]; // first NEW position at or behind cut k
+    uint32_t old_begin[REMOVE_MAX_RANGES]; // first OLD position of cut k
+    uint32_t cum[REMOVE_MAX_RANGES];       // removed positions up to and including cut k
+    uint32_t scene[GS_MAX_SCENES];         // scene index -> scene index (the identity where the caller named none)
+};
+constexpr int GS_REMOVE_PLAIN = 0, GS_REMOVE_POSITIONS = 1, GS_REMOVE_SCENES = 2;
+RemoveMap gs_remove_map(const RemovePlan& p, const uint32_t* scene_remap, uint32_t scene_remap_count);
+int gs_remove_compact(hipStream_t st, const RemoveMap& map, void* plane, uint32_t elem_bytes, int mode, uint32_t base, uint32_t new_end,
+                      uint32_t old_end, void* scratch);
+int gs_mesh_block_boxes(gs_mesh* m, uint32_t b0, uint32_t b1);   // k_block_boxes over storage blocks [b0, b1), on ctx->stream (mesh.hip)
+void gs_sorter_mesh_edited(gs_sorter* s);                        // the bound mesh renumbered its splats (sorter.hip)
 
 // kernels' host launchers ---------------------------------------------------------------------------
 // (ev_before / ev_after, nullable, recorded on ctx->aux: around the whole vertex stage - block test, mask memset, k_project - when

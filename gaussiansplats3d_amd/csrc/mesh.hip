@@ -553,6 +553,14 @@ static int mesh_commit_segment(gs_mesh* m, const UploadSegment& seg, const MeshS
     return GS_OK;
 }
 
+int gs_mesh_block_boxes(gs_mesh* m, uint32_t b0, uint32_t b1) {
+    if (b1 <= b0) return GS_OK;
+    hipLaunchKernelGGL(k_block_boxes, dim3(b1 - b0), dim3(256), 0, m->ctx->stream, m->px.as<float>(), m->py.as<float>(), m->pz.as<float>(),
+                       m->cov_bound.as<float>(), m->max_count, b0, m->block_box.as<float>());
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 // SplatMesh.updateDataTexturesFromBaseData(fromSplat, toSplat) accepts any range, any number of times
 // (/root/reference/src/splatmesh/SplatMesh.js:900-1062).  Splats seen for the first time are stored along the Morton curve
 // of their own contiguous run; splats uploaded before keep their slots and only have their data replaced.
@@ -584,6 +592,10 @@ int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSou
         GS_TRY(mesh_staging_layout(m, seg.end - seg.begin, src.stages_sh_u8, &stg));
         GS_TRY(src.fill(m, o, seg.end - seg.begin, stg, m->ctx->stream));
         GS_TRY(mesh_commit_segment(m, seg, stg, src.host_centers ? src.host_centers + 3 * (size_t)o : nullptr));
+        if (m->reorder && seg.fresh) {                      // a Morton run of its own (plan_remove, upload_plan.hpp)
+            auto at = std::upper_bound(m->runs.begin(), m->runs.end(), seg.begin, [](uint32_t b, const SlotRange& r) { return b < r.begin; });
+            m->runs.insert(at, SlotRange{seg.begin, seg.end});
+        }
     }
     m->slotted.add(from, end);
     if (end > m->uploaded) m->uploaded = end;

@@ -1,0 +1,220 @@
+// mesh_edit.hip — removing splats from a live mesh on the device (gs_mesh_remove), and the plane compaction the sorter's half
+// (sorter.hip, gs_sorter_remove) shares.  Replaces the dispose + rebuild of Viewer.removeSplatScenes
+// (the reference's src/Viewer.js:1326-1429) for the device objects: the survivors' storage spans move down, nothing crosses the bus.
+// Which spans move where, and which calls are refused, is upload_plan.hpp's (plan_remove); DESIGN.md 8.13.
+#include <algorithm>
+
+#include "gs_internal.hpp"
+
+static_assert(REMOVE_MAX_RANGES == GS_MAX_SCENES, "one removed range per scene");
+
+// ---------------------------------------------------------------------------------------------------
+// The move.  Source and destination of a span overlap whenever it is longer than its shift, so a plane is never moved in place:
+// one launch gathers every position from `base` to the new end into a scratch buffer (16 bytes per position at most: the
+// staging buffer), one copy between the two distinct buffers puts them back.  No workgroup waits for another, no copy overlaps
+// itself, and the launches are per plane, not per range: the <= 32 cuts travel as kernel arguments (scalar registers).
+// ---------------------------------------------------------------------------------------------------
+RemoveMap gs_remove_map(const RemovePlan& p, const uint32_t* scene_remap, uint32_t scene_remap_count) {
+    RemoveMap r = {};
+    r.n = (uint32_t)p.cuts.size();
+    uint32_t cum = 0;
+    for (uint32_t k = 0; k < r.n; k++) {
+        r.old_begin[k] = p.cuts[k].begin;
+        r.new_begin[k] = p.cuts[k].begin - cum;
+        cum += p.cuts[k].end - p.cuts[k].begin;
+        r.cum[k] = cum;
+    }
+    for (uint32_t k = 0; k < GS_MAX_SCENES; k++) r.scene[k] = (scene_remap && k < scene_remap_count) ? scene_remap[k] : k;
+    return r;
+}
+
+// removed positions below the survivor that lands on NEW position j (the cuts are uniform: scalar loads and compares)
+__device__ __forceinline__ uint32_t removed_below_new(const RemoveMap& r, uint32_t j) {
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < r.n; k++) s = j >= r.new_begin[k] ? r.cum[k] : s;
+    return s;
+}
+// ... below the survivor at OLD position v
+__device__ __forceinline__ uint32_t removed_below_old(const RemoveMap& r, uint32_t v) {
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < r.n; k++) s = v >= r.old_begin[k] ? r.cum[k] : s;
+    return s;
+}
+
+// scratch[g] = the 16 bytes of new positions base + g * V .. + V of a plane of T (V = 16 / sizeof(T); zeros beyond n_out).
+// MODE: GS_REMOVE_PLAIN the elements as they are | GS_REMOVE_POSITIONS they are positions (perm, inv_perm): index space and
+// storage space share one shift function under the run rule | GS_REMOVE_SCENES they are scene indexes: through the table
+template <class T, int MODE>
+__global__ __launch_bounds__(256) void k_remove_gather(const T* __restrict__ plane, uint32_t base, uint32_t n_out, RemoveMap r,
+                                                       uint4* __restrict__ scratch) {
+    constexpr uint32_t V = 16u / sizeof(T), W = sizeof(T) / 4u;      // elements per 16 bytes, words per element
+    static_assert(MODE == GS_REMOVE_PLAIN || W == 1u, "positions and scene indexes are words");
+    const uint32_t groups = (n_out + V - 1u) / V;
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t t = 0; t < V; t++) {
+            const uint32_t o = g * V + t;
+            if (o >= n_out) continue;
+            const uint32_t j = base + o;
+            __builtin_memcpy(&w[t * W], &plane[j + removed_below_new(r, j)], sizeof(T));   // (one load of the element's size)
+            if constexpr (MODE == GS_REMOVE_POSITIONS) w[t] -= removed_below_old(r, w[t]);
+            if constexpr (MODE == GS_REMOVE_SCENES) w[t] = w[t] < GS_MAX_SCENES ? r.scene[w[t]] : w[t];
+        }
+        scratch[g] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_remove_iota(uint32_t* __restrict__ a, uint32_t* __restrict__ b, uint32_t from, uint32_t end) {
+    for (uint32_t i = from + blockIdx.x * blockDim.x + threadIdx.x; i < end; i += gridDim.x * blockDim.x) a[i] = b[i] = i;
+}
+
+static inline uint32_t edit_grid(uint32_t n) {
+    const uint32_t g = (n + 255u) / 256u;
+    return g < 1u ? 1u : (g > 4096u ? 4096u : g);
+}
+
+// One plane: positions [base, new_end) gathered and put back, [new_end, old_end) zeroed (what a fresh object holds there).
+// scratch holds >= 16 * (new_end - base) + 16 bytes.  Enqueued on st; the caller checks hipGetLastError.
+int gs_remove_compact(hipStream_t st, const RemoveMap& map, void* plane, uint32_t elem_bytes, int mode, uint32_t base, uint32_t new_end,
+                      uint32_t old_end, void* scratch) {
+    if (!plane) return GS_OK;
+    const uint32_t n_out = new_end - base;
+    if (n_out) {
+        const dim3 g(edit_grid((uint32_t)(((size_t)n_out * elem_bytes + 15u) / 16u))), b(256);
+        uint4* sc = static_cast<uint4*>(scratch);
+        if (elem_bytes == 16) hipLaunchKernelGGL((k_remove_gather<uint4, GS_REMOVE_PLAIN>), g, b, 0, st, (const uint4*)plane, base, n_out, map, sc);
+        else if (elem_bytes == 8) hipLaunchKernelGGL((k_remove_gather<uint2, GS_REMOVE_PLAIN>), g, b, 0, st, (const uint2*)plane, base, n_out, map, sc);
+        else if (mode == GS_REMOVE_POSITIONS)
+            hipLaunchKernelGGL((k_remove_gather<uint32_t, GS_REMOVE_POSITIONS>), g, b, 0, st, (const uint32_t*)plane, base, n_out, map, sc);
+        else if (mode == GS_REMOVE_SCENES)
+            hipLaunchKernelGGL((k_remove_gather<uint32_t, GS_REMOVE_SCENES>), g, b, 0, st, (const uint32_t*)plane, base, n_out, map, sc);
+        else hipLaunchKernelGGL((k_remove_gather<uint32_t, GS_REMOVE_PLAIN>), g, b, 0, st, (const uint32_t*)plane, base, n_out, map, sc);
+        GS_HIP(hipGetLastError());
+        GS_HIP(hipMemcpyAsync(static_cast<char*>(plane) + (size_t)base * elem_bytes, scratch, (size_t)n_out * elem_bytes, hipMemcpyDeviceToDevice, st));
+    }
+    if (old_end > new_end)
+        GS_HIP(hipMemsetAsync(static_cast<char*>(plane) + (size_t)new_end * elem_bytes, 0, (size_t)(old_end - new_end) * elem_bytes, st));
+    return GS_OK;
+}
+
+// The centre sums of positions [0, n) (gs_mesh::centre_sum / centre_sq / centre_n: a heuristic's inputs, not pinned): per
+// workgroup {x, y, z, x*x + y*y + z*z, count} in fp64.  Never-uploaded positions inside [0, n) count as the zero centres they hold.
+constexpr uint32_t CENTRE_SUM_BLOCKS = 256;
+__global__ __launch_bounds__(256) void k_remove_centre_sums(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
+                                                            uint32_t n, double* __restrict__ out) {
+    __shared__ double s_part[4][5];
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float x = px[i], y = py[i], z = pz[i];
+        const float r2 = x * x + y * y + z * z;
+        if (!(r2 < 1e30f)) continue;                          // NaN / infinite centres draw nothing
+        s[0] += x; s[1] += y; s[2] += z; s[3] += r2; s[4] += 1.0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+        for (int k = 0; k < 5; k++) s[k] += __shfl_xor(s[k], o, 64);
+    if ((threadIdx.x & 63u) == 0u)
+        for (int k = 0; k < 5; k++) s_part[threadIdx.x >> 6][k] = s[k];
+    __syncthreads();
+    if (threadIdx.x < 5u) out[5u * blockIdx.x + threadIdx.x] = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+}
+
+static int mesh_recount_centres(gs_mesh* m) {
+    m->centre_sum[0] = m->centre_sum[1] = m->centre_sum[2] = m->centre_sq = 0.0;
+    m->centre_n = 0;
+    if (m->uploaded == 0) return GS_OK;
+    hipStream_t st = m->ctx->stream;
+    double part[CENTRE_SUM_BLOCKS * 5];
+    const uint32_t blocks = std::min((m->uploaded + 255u) / 256u, CENTRE_SUM_BLOCKS);
+    GS_TRY(m->staging.ensure(sizeof(part)));
+    hipLaunchKernelGGL(k_remove_centre_sums, dim3(blocks), dim3(256), 0, st, m->px.as<float>(), m->py.as<float>(), m->pz.as<float>(), m->uploaded,
+                       m->staging.as<double>());
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpyAsync(part, m->staging.p, sizeof(double) * 5 * blocks, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    for (uint32_t b = 0; b < blocks; b++) {
+        for (int k = 0; k < 3; k++) m->centre_sum[k] += part[5 * b + k];
+        m->centre_sq += part[5 * b + 3];
+        m->centre_n += (uint64_t)part[5 * b + 4];
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count) {
+    GS_REQUIRE(m != nullptr, "mesh == NULL");
+    if (n_ranges == 0) return GS_OK;
+    GS_REQUIRE(ranges != nullptr, "ranges == NULL");
+    GS_REQUIRE(n_ranges <= GS_MAX_SCENES, "gs_mesh_remove: more than GS_MAX_SCENES ranges");
+    GS_REQUIRE(scene_remap || scene_remap_count == 0, "gs_mesh_remove: scene_remap == NULL with a count");
+    GS_REQUIRE(scene_remap_count <= GS_MAX_SCENES, "gs_mesh_remove: scene_remap_count > GS_MAX_SCENES");
+    for (uint32_t k = 0; k < scene_remap_count; k++) GS_REQUIRE(scene_remap[k] < GS_MAX_SCENES, "gs_mesh_remove: scene_remap entry >= GS_MAX_SCENES");
+    const RemovePlan plan = plan_remove(m->runs, m->slotted, m->uploaded, m->max_count, m->reorder, ranges, n_ranges);
+    if (plan.refused) {
+        gs_set_error("invalid argument: gs_mesh_remove: %s", plan.refused);
+        return GS_ERR_INVALID;
+    }
+    if (plan.removed == 0) return GS_OK;                    // every range lies beyond the uploaded splats
+    gs_context* ctx = m->ctx;
+    ScopedDevice sd(ctx->device);
+    hipStream_t st = ctx->stream;
+    // draws in flight read the planes and the permutation on either stream, a bound sorter's sort reads the permutation on its own
+    GS_HIP(hipStreamSynchronize(st));
+    if (ctx->aux != st) GS_HIP(hipStreamSynchronize(ctx->aux));
+    for (gs_sorter* s : ctx->live_sorters)
+        if ((s->bound_mesh == m || s->result_mesh == m) && s->stream != st) GS_HIP(hipStreamSynchronize(s->stream));
+
+    const uint32_t old_end = m->uploaded, new_end = plan.uploaded;
+    const uint32_t base = plan.cuts[0].begin & ~3u;         // a multiple of every plane's elements per 16 bytes; <= new_end
+    GS_TRY(m->staging.ensure((size_t)(new_end - base) * 16 + 16));
+    const RemoveMap map = gs_remove_map(plan, scene_remap, scene_remap_count);
+    const bool half = (m->flags & GS_MESH_COV_HALF) != 0, sh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    struct Plane { DevBuf* buf; uint32_t bytes; int mode; };
+    const Plane planes[] = {
+        {&m->px, 4, GS_REMOVE_PLAIN}, {&m->py, 4, GS_REMOVE_PLAIN}, {&m->pz, 4, GS_REMOVE_PLAIN},
+        {&m->covA, half ? 8u : 16u, GS_REMOVE_PLAIN}, {&m->covB, half ? 4u : 8u, GS_REMOVE_PLAIN},
+        {&m->cov_bound, 4, GS_REMOVE_PLAIN}, {&m->rgba, 4, GS_REMOVE_PLAIN},
+        {&m->sh0, 16, GS_REMOVE_PLAIN}, {&m->sh1, sh_u8 ? 8u : (m->sh_degree == 2 ? 16u : 4u), GS_REMOVE_PLAIN}, {&m->sh2, 16, GS_REMOVE_PLAIN},
+        {&m->scene_idx, 4, GS_REMOVE_SCENES}, {&m->perm, 4, GS_REMOVE_POSITIONS}, {&m->inv_perm, 4, GS_REMOVE_POSITIONS},
+    };
+    for (const Plane& p : planes)
+        GS_TRY(gs_remove_compact(st, map, p.buf->p, p.bytes, p.mode, base, new_end, old_end, m->staging.p));
+    if (m->reorder) {                                       // the tail is the identity again, as gs_mesh_create left it
+        hipLaunchKernelGGL(k_remove_iota, dim3(edit_grid(old_end - new_end)), dim3(256), 0, st, m->perm.as<uint32_t>(), m->inv_perm.as<uint32_t>(),
+                           new_end, old_end);
+        GS_HIP(hipGetLastError());
+    }
+    // the boxes of every storage block from the first one that changed to the old end (the blocks behind the new end: the origin)
+    GS_TRY(gs_mesh_block_boxes(m, plan.first_block, (old_end + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK));
+    GS_HIP(hipStreamSynchronize(st));
+
+    // the numbering changed: everything that described the old one goes back to its state at creation
+    m->slotted = plan.slotted;
+    m->runs = plan.runs;
+    m->uploaded = new_end;
+    m->layout_version++;
+    m->projection_pending = false;
+    m->has_draw = false;
+    m->last_count = 0;
+    m->last = gs_render_stats();
+    m->last_pp = ProjectParams();
+    m->stats_of = StatsOf();
+    m->plan = SchedulePlan();
+    m->list_shift = m->drawn_list_shift = GS_LIST_SHIFT_LARGE;
+    m->measured_visible = m->measured_count = 0;
+    m->draw_serial = m->healed_serial = m->adapted_serial = 0;
+    m->grow_entries_to = 0;
+    m->truncated_draws = 0;
+    for (int k = 0; k < 8; k++) m->full_serial[k] = m->full_count[k] = 0;
+    memset(m->mirror_host, 0, 64);                          // the draw feedback words (no draw is in flight)
+    m->cur_set = 0;
+    for (ProjSet& ps : m->sets) {
+        ps.drawn = false;
+        ps.vis_orig_lazy = false; ps.vis_orig_dirty = true; ps.vis_orig_tail_zero = false; ps.vis_orig_count = 0;
+    }
+    GS_TRY(mesh_recount_centres(m));                       // a heuristic's inputs: the sums of the survivors
+    for (gs_sorter* s : ctx->live_sorters)
+        if (s->bound_mesh == m || s->result_mesh == m) gs_sorter_mesh_edited(s);
+    return GS_OK;
+}

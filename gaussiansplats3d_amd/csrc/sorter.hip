@@ -13,6 +13,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "extreme_set.hpp"
 #include "radix.hpp"
 
@@ -1278,12 +1280,15 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
         gs_sorter_destroy(s);
         return st;
     }
+    ctx->live_sorters.push_back(s);
     *out = s;
     return GS_OK;
 }
 
 void gs_sorter_destroy(gs_sorter* s) {
     if (!s) return;
+    std::vector<gs_sorter*>& live = s->ctx->live_sorters;
+    live.erase(std::remove(live.begin(), live.end(), s), live.end());
     if (s->pending_tree) gs_tree_forget_sorter(s->pending_tree, s);
     ScopedDevice sd(s->ctx->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
@@ -1435,7 +1440,73 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
     return GS_OK;
 }
 
+// Every state of a sorter that names splats by their numbering: the resident result, a gathered (or planned) list, the per-tree
+// payload caches, the mask a visibility-culled sort consumed, the stale-key state and device distances.
+static void sorter_forget_numbering(gs_sorter* s) {
+    if (s->pending_tree) gs_tree_forget_sorter(s->pending_tree, s);
+    s->pending_tree = nullptr;
+    s->pending_keep_zeroed = false;
+    s->has_result = false;
+    s->result_mesh = nullptr; s->result_unmap = nullptr; s->result_frame = nullptr; s->result_payload_max = 0;
+    s->last_render = s->last_sort = s->last_passes = 0;
+    s->last_in = SortPlanIn(); s->last_plan = SortPlan();
+    s->has_gathered = false; s->gathered_on_device = false; s->gathered = 0;
+    s->leaf_cache_tree = 0; s->leaf_cache_mesh = nullptr;
+    s->keys_stale = false; s->stale_count = 0;
+    s->dev_distances = false; s->dev_distances_count = 0;
+    s->mask_copy.release();
+}
+
+void gs_sorter_mesh_edited(gs_sorter* s) {
+    sorter_forget_numbering(s);
+    sorter_tell_mesh(s);
+}
+
 extern "C" {
+
+int gs_sorter_remove(gs_sorter* s, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count) {
+    GS_REQUIRE(s != nullptr, "sorter == NULL");
+    if (n_ranges == 0) return GS_OK;
+    GS_REQUIRE(ranges != nullptr, "ranges == NULL");
+    GS_REQUIRE(n_ranges <= GS_MAX_SCENES, "gs_sorter_remove: more than GS_MAX_SCENES ranges");
+    GS_REQUIRE(scene_remap || scene_remap_count == 0, "gs_sorter_remove: scene_remap == NULL with a count");
+    GS_REQUIRE(scene_remap_count <= GS_MAX_SCENES, "gs_sorter_remove: scene_remap_count > GS_MAX_SCENES");
+    for (uint32_t k = 0; k < scene_remap_count; k++) GS_REQUIRE(scene_remap[k] < GS_MAX_SCENES, "gs_sorter_remove: scene_remap entry >= GS_MAX_SCENES");
+    const RemovePlan plan = plan_remove(std::vector<SlotRange>(), SlottedRanges(), s->uploaded, s->max_count, false, ranges, n_ranges);
+    if (plan.refused) {
+        gs_set_error("invalid argument: gs_sorter_remove: %s", plan.refused);
+        return GS_ERR_INVALID;
+    }
+    if (plan.removed == 0) return GS_OK;                    // every range lies beyond the uploaded centres
+    ScopedDevice sd(s->ctx->device);
+    hipStream_t st = s->stream;
+    GS_HIP(hipStreamSynchronize(st));                      // the sort in flight
+    if (s->ctx->stream != st) GS_HIP(hipStreamSynchronize(s->ctx->stream));   // a draw may still be reading `sorted`
+    // the rows as uploaded move down (and the scene indexes, through the table); the SoA planes, the extreme set and the 16-bit
+    // planes are derived from the surviving rows as an upload derives them
+    const uint32_t old_end = s->uploaded, new_end = plan.uploaded, base = plan.cuts[0].begin & ~3u;
+    GS_TRY(s->staging.ensure((size_t)(new_end - base) * 16 + 16));
+    const RemoveMap map = gs_remove_map(plan, scene_remap, scene_remap_count);
+    GS_TRY(gs_remove_compact(st, map, s->caos.p, 16, GS_REMOVE_PLAIN, base, new_end, old_end, s->staging.p));
+    if (s->flags & GS_SORT_DYNAMIC) GS_TRY(gs_remove_compact(st, map, s->scene_idx.p, 4, GS_REMOVE_SCENES, base, new_end, old_end, s->staging.p));
+    if (new_end > base) {
+        hipLaunchKernelGGL(k_aos4_to_soa, dim3(grid_for(new_end - base, 256, 4096)), dim3(256), 0, st, s->caos.as<uint4>() + base, new_end - base,
+                           base, s->cx.as<uint32_t>(), s->cy.as<uint32_t>(), s->cz.as<uint32_t>(),
+                           (s->flags & GS_SORT_DYNAMIC) ? s->cw.as<uint32_t>() : nullptr);
+        GS_HIP(hipGetLastError());
+    }
+    GS_HIP(hipStreamSynchronize(st));
+    s->uploaded = new_end;
+    s->centers_version++;
+    sorter_forget_numbering(s);
+    s->extreme.clear();                                    // no centres: the empty set ...
+    s->extreme_ok = true;
+    s->extreme_version = s->centers_version;
+    if (new_end) GS_TRY(sorter_update_extreme(s, 0, new_end, new_end, false));   // ... else rebuilt from every surviving row
+    GS_TRY(sorter_update_compact(s, 0, new_end, new_end));
+    sorter_tell_mesh(s);
+    return GS_OK;
+}
 
 int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
     GS_REQUIRE(s != nullptr, "sorter == NULL");

@@ -70,6 +70,88 @@ UploadLayout upload_layout(uint32_t count, bool cov_half, bool mesh_sh_u8, uint3
     return l;
 }
 
+RemovePlan plan_remove(const std::vector<SlotRange>& runs, const SlottedRanges& slotted, uint32_t uploaded, uint32_t max_count,
+                       bool reorder, const uint32_t* ranges, uint32_t n) {
+    RemovePlan p;
+    if (!ranges || n == 0 || n > REMOVE_MAX_RANGES) { p.refused = "1 .. 32 ranges"; return p; }
+    uint64_t prev_end = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint64_t from = ranges[2 * k], end = from + ranges[2 * k + 1];
+        if (end == from) { p.refused = "a range is empty"; return p; }
+        if (from < prev_end) { p.refused = "the ranges are not ascending and disjoint"; return p; }
+        if (end > max_count) { p.refused = "a range exceeds max_splat_count"; return p; }
+        prev_end = end;
+        if (reorder)
+            for (const SlotRange& r : runs)
+                if ((r.begin < from && from < r.end) || (r.begin < end && end < r.end)) {
+                    p.refused = "a range border falls inside a Morton run (the span of one fresh upload segment)";
+                    return p;
+                }
+        if (from < uploaded) p.cuts.push_back({(uint32_t)from, (uint32_t)std::min<uint64_t>(end, uploaded)});
+    }
+    // the survivors between and behind the cuts, each with the removed count below it
+    uint32_t shift = 0;
+    for (size_t k = 0; k < p.cuts.size(); k++) {
+        shift += p.cuts[k].end - p.cuts[k].begin;
+        const uint32_t stop = k + 1 < p.cuts.size() ? p.cuts[k + 1].begin : uploaded;
+        if (p.cuts[k].end < stop) p.moves.push_back({p.cuts[k].end, stop, shift});
+    }
+    p.removed = shift;
+    p.uploaded = uploaded - shift;
+    p.first_block = p.cuts.empty() ? 0u : p.cuts[0].begin / UPLOAD_BLOCK;
+    // what is left of [b, e), piece by piece, in the new numbering
+    auto survivors = [&](uint32_t b, uint32_t e, auto&& emit) {
+        uint32_t below = 0, pos = b;                       // below: the removed positions below pos
+        for (const SlotRange& c : p.cuts) {
+            if (c.begin >= e) break;
+            if (c.end > pos) {
+                if (c.begin > pos) emit(pos - below, c.begin - below);
+                pos = c.end;
+            }
+            below += c.end - c.begin;
+        }
+        if (pos < e) emit(pos - below, e - below);
+    };
+    if (reorder)                                           // (each whole or not at all: one piece; no other mesh has runs)
+        for (const SlotRange& r : runs) survivors(r.begin, r.end, [&](uint32_t b, uint32_t e) { p.runs.push_back({b, e}); });
+    for (const SlotRange& r : slotted.ranges())
+        survivors(r.begin, r.end, [&](uint32_t b, uint32_t e) { p.slotted.add(b, e); });
+    return p;
+}
+
+extern "C" int gs_debug_remove_plan(const gs_remove_plan_debug_in* in, gs_remove_plan_debug_out* out) {
+    if (!in || !out || in->n_runs > UPLOAD_DEBUG_MAX || in->n_slotted > UPLOAD_DEBUG_MAX || in->n_ranges > UPLOAD_DEBUG_MAX) return -1;
+    if (in->max_count > UPLOAD_MAX_SPLATS || in->uploaded > in->max_count) return -1;
+    std::vector<SlotRange> runs;
+    SlottedRanges sl;
+    uint32_t prev = 0;
+    for (uint32_t k = 0; k < in->n_runs; k++) {
+        if (in->runs[k][0] >= in->runs[k][1] || in->runs[k][0] < prev || in->runs[k][1] > in->uploaded) return -1;
+        runs.push_back({in->runs[k][0], in->runs[k][1]});
+        prev = in->runs[k][1];
+    }
+    for (uint32_t k = 0; k < in->n_slotted; k++) {
+        if (in->slotted[k][0] >= in->slotted[k][1] || in->slotted[k][1] > in->uploaded) return -1;
+        sl.add(in->slotted[k][0], in->slotted[k][1]);
+    }
+    *out = gs_remove_plan_debug_out();
+    const RemovePlan p = plan_remove(runs, sl, in->uploaded, in->max_count, in->reorder != 0u, &in->ranges[0][0], in->n_ranges);
+    if (p.refused) { out->refused = 1; return 0; }
+    if (p.moves.size() > UPLOAD_DEBUG_MAX || p.runs.size() > UPLOAD_DEBUG_MAX || p.slotted.ranges().size() > UPLOAD_DEBUG_MAX) return -1;
+    out->n_moves = (uint32_t)p.moves.size();
+    for (uint32_t k = 0; k < out->n_moves; k++) {
+        out->moves[k][0] = p.moves[k].begin; out->moves[k][1] = p.moves[k].end; out->moves[k][2] = p.moves[k].shift;
+    }
+    out->n_runs = (uint32_t)p.runs.size();
+    for (uint32_t k = 0; k < out->n_runs; k++) { out->runs[k][0] = p.runs[k].begin; out->runs[k][1] = p.runs[k].end; }
+    out->n_slotted = (uint32_t)p.slotted.ranges().size();
+    for (uint32_t k = 0; k < out->n_slotted; k++) {
+        out->slotted[k][0] = p.slotted.ranges()[k].begin; out->slotted[k][1] = p.slotted.ranges()[k].end;
+    }
+    out->removed = p.removed; out->uploaded = p.uploaded; out->first_block = p.first_block;
+    return 0;
+}
+
 extern "C" int gs_debug_upload_plan(const gs_upload_plan_debug_in* in, gs_upload_plan_debug_out* out) {
     if (!in || !out || in->n_ranges > UPLOAD_DEBUG_MAX || (uint64_t)in->from + in->count > UPLOAD_MAX_SPLATS) return -1;
     SlottedRanges sl;

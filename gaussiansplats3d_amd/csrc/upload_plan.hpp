@@ -57,6 +57,29 @@ struct UploadLayout {
 UploadLayout upload_layout(uint32_t count, bool cov_half, bool mesh_sh_u8, uint32_t sh_degree, bool source_stages_sh_u8);
 
 // ---------------------------------------------------------------------------------------------------
+// Removing splats from a mesh or a sorter (mesh_edit.hip, sorter.hip: gs_mesh_remove / gs_sorter_remove).  The removed ranges go
+// away, every survivor i becomes i - (removed positions below i), and - because a fresh segment occupies the storage slots of its
+// own index range - the storage spans move by the same shift as the indexes.  That holds only while no border of a removed range
+// falls inside a Morton run (the span of one fresh segment of a mesh that re-orders: its splats are scattered over the whole run),
+// so the mesh remembers its runs - SlottedRanges merges the ones that touch - and plan_remove refuses such a border.
+constexpr uint32_t REMOVE_MAX_RANGES = 32;                 // GS_MAX_SCENES
+struct RemoveMove { uint32_t begin, end, shift; };         // the survivors [begin, end) (old numbering) move down by shift > 0
+struct RemovePlan {
+    const char* refused = nullptr;                         // why not (then nothing else is filled in), or nullptr
+    std::vector<SlotRange> cuts;                           // the removed ranges clipped to [0, uploaded), none empty, ascending
+    std::vector<RemoveMove> moves;                         // ascending; together with the untouched head they are the survivors
+    std::vector<SlotRange> runs;                           // the runs that survive, shifted (never merged)
+    SlottedRanges slotted;                                 // the slotted ranges that survive, shifted (those that now touch are one)
+    uint32_t removed = 0;                                  // positions below `uploaded` that go away
+    uint32_t uploaded = 0;                                 // the uploaded count afterwards
+    uint32_t first_block = 0;                              // first storage block whose content changes (removed > 0)
+};
+// ranges: n pairs {from, count} in the caller's numbering - 1 <= n <= REMOVE_MAX_RANGES, ascending, disjoint, non-empty, inside
+// [0, max_count].  runs: sorted, disjoint, inside [0, uploaded) (empty for a sorter and a mesh that keeps upload order).
+RemovePlan plan_remove(const std::vector<SlotRange>& runs, const SlottedRanges& slotted, uint32_t uploaded, uint32_t max_count,
+                       bool reorder, const uint32_t* ranges, uint32_t n);
+
+// ---------------------------------------------------------------------------------------------------
 // Debug entry for the tests (pure host; typed by tests/upload_plan_cases.py, not in the public header).  Flags are uint32 (0 / 1).
 constexpr uint32_t UPLOAD_DEBUG_MAX = 64;                  // ranges in, ranges out, segments
 struct gs_upload_plan_debug_in {
@@ -79,3 +102,27 @@ struct gs_upload_plan_debug_out {
 };
 // 0; -1 on a NULL argument, an empty or reversed input range, a span beyond UPLOAD_MAX_SPLATS or more than UPLOAD_DEBUG_MAX rows
 extern "C" int gs_debug_upload_plan(const gs_upload_plan_debug_in* in, gs_upload_plan_debug_out* out);
+
+// ... and for plan_remove (typed by tests/remove_plan_cases.py)
+struct gs_remove_plan_debug_in {
+    uint32_t n_runs;                                       // the state before: the runs as the mesh remembers them
+    uint32_t runs[UPLOAD_DEBUG_MAX][2];
+    uint32_t n_slotted;                                    // ... and its slotted ranges, add()ed in this order
+    uint32_t slotted[UPLOAD_DEBUG_MAX][2];
+    uint32_t uploaded, max_count, reorder;
+    uint32_t n_ranges;                                     // the call: {from, count} pairs, handed on as they are
+    uint32_t ranges[UPLOAD_DEBUG_MAX][2];
+};
+struct gs_remove_plan_debug_out {
+    uint32_t refused;                                      // 1: the plan refused the call (nothing else is filled in)
+    uint32_t n_moves;
+    uint32_t moves[UPLOAD_DEBUG_MAX][3];                   // begin, end, shift
+    uint32_t n_runs;
+    uint32_t runs[UPLOAD_DEBUG_MAX][2];
+    uint32_t n_slotted;
+    uint32_t slotted[UPLOAD_DEBUG_MAX][2];
+    uint32_t removed, uploaded, first_block;
+};
+// 0; -1 on a NULL argument, more than UPLOAD_DEBUG_MAX rows, or a state no mesh can be in (runs or slotted ranges that are empty,
+// unsorted, overlapping or beyond `uploaded`; uploaded > max_count; max_count > UPLOAD_MAX_SPLATS)
+extern "C" int gs_debug_remove_plan(const gs_remove_plan_debug_in* in, gs_remove_plan_debug_out* out);

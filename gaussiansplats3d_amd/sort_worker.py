@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .util import remove_args, removed_below
 
 DEFAULT_PRECISION = 16     # Constants.DefaultSplatSortDistanceMapPrecision, src/Constants.js:3
 
@@ -45,6 +46,8 @@ class SortWorker:
             return self._on_centers(msg)
         if "sort" in msg:
             return self._on_sort(msg["sort"])
+        if "remove" in msg:                              # (not a message of the reference's worker: its Viewer rebuilds the worker)
+            return self.remove(msg["remove"]["ranges"], msg["remove"].get("sceneRemap"))
         raise ValueError("unknown sort-worker message: " + ", ".join(msg.keys()))
 
     def _reply(self, msg):
@@ -146,6 +149,15 @@ class SortWorker:
         posts only precomputed distances.  Splats that never received centres get zero ones."""
         L.check(self.lib.gs_sorter_set_uploaded_count(self.handle, int(count)))
         self.uploaded_splat_count = max(self.uploaded_splat_count, int(count))
+
+    def remove(self, ranges, scene_remap=None):
+        """gs_sorter_remove: the centres of the (from, count) ranges go away on the device and the survivors are renumbered
+        as SplatMesh.remove renumbers them; scene_remap[k] is the new index of scene k (dynamic mode).  The resident result
+        and a gathered list are forgotten: sort again."""
+        r, n, m, mc = remove_args(ranges, scene_remap)
+        L.check(self.lib.gs_sorter_remove(self.handle, r.ctypes.data if n else None, n, m.ctypes.data if m is not None else None, mc))
+        self.uploaded_splat_count -= removed_below(r, self.uploaded_splat_count)
+        self.gathered_count = 0
 
     def set_frustum_cull(self, enable=True):
         """Fuse a per-splat frustum cull into full sorts (gs_sorter_set_frustum_cull): the result is the reference's

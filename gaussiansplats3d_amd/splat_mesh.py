@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from .reveal import SceneRevealMode, VisibleRegion
-from .util import distance_uniforms, to_half_three
+from .util import distance_uniforms, remove_args, removed_below, to_half_three
 
 
 class SplatMesh:
@@ -93,6 +93,31 @@ class SplatMesh:
             L.check(self.lib.gs_mesh_upload_scene_indexes(self.handle, int(start), n, si.ctypes.data))
             self._scene_of[int(start):int(start) + n] = si
         self.splat_count = max(self.splat_count, int(start) + n)
+        return self
+
+    def remove(self, ranges, scene_remap=None):
+        """gs_mesh_remove: the (from, count) ranges go away on the device, every surviving splat i becomes i - (removed splats
+        below i); no data crosses the bus.  A mesh in Morton order accepts only ranges whose borders do not split the span of
+        one fresh upload (whole scenes); keep_order meshes accept any.  scene_remap[k]: the new index of scene k - call
+        set_scenes for the survivors afterwards.  The last draw, a pending project() and bound sorters' results are forgotten."""
+        r, n, m, mc = remove_args(ranges, scene_remap)
+        L.check(self.lib.gs_mesh_remove(self.handle, r.ctypes.data if n else None, n, m.ctypes.data if m is not None else None, mc))
+        old = self.splat_count
+        gone = removed_below(r, old)
+        if gone:                                           # the host copy of the scene indexes follows: the pieces between the cuts
+            pieces, at = [], 0
+            for start, count in r.tolist():
+                pieces.append(self._scene_of[at:min(start, old)])
+                at = max(at, min(start + count, old))
+            so = np.concatenate(pieces + [self._scene_of[at:old]])
+            if mc:
+                so = np.where(so < mc, m[np.minimum(so, mc - 1)], so)
+            self._scene_of[:so.size] = so
+            self._scene_of[so.size:old] = 0
+            self.splat_count = old - gone
+        self.render_count = min(self.render_count, self.splat_count)
+        self.last_build_splat_count = min(self.last_build_splat_count, self.splat_count)
+        self._indexes = None
         return self
 
     def set_scenes(self, transforms=None, camera_position=None, opacity=None, visible=None, sh8_range=None):

@@ -102,3 +102,19 @@ def distance_uniforms(model_view_proj, integer, dynamic, scene_transforms=None):
             rows += m
     out = np.array(rows, dtype=np.int32) if integer else np.array(rows, dtype=np.float64).astype(np.float32)
     return out, len(transforms)
+
+
+def remove_args(ranges, scene_remap):
+    """The arguments of gs_mesh_remove / gs_sorter_remove: (ranges uint32 [n, 2] of (from, count) pairs, n, scene_remap uint32
+    array or None, its length)."""
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if r.size and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+        raise ValueError("ranges must hold unsigned 32-bit (from, count) pairs")
+    r = np.ascontiguousarray(r.astype(np.uint32))
+    m = None if scene_remap is None else np.ascontiguousarray(scene_remap, dtype=np.uint32).reshape(-1)
+    return r, r.shape[0], m, 0 if m is None else m.size
+
+
+def removed_below(ranges, count):
+    """How many of the positions [0, count) the (from, count) ranges of an accepted removal take away."""
+    return sum(max(0, min(start + n, count) - min(start, count)) for start, n in np.asarray(ranges, dtype=np.int64).reshape(-1, 2).tolist())

@@ -131,6 +131,15 @@ int gs_sorter_sort_gathered(gs_sorter* s, const float* mvp, uint32_t sort_count,
  * that never received centres get zero ones, what the reference's zero-filled WASM memory holds.  A smaller count is a no-op. */
 int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count);
 
+/* Remove centres on the device (Viewer.removeSplatScenes without rebuilding the worker, src/Viewer.js:1326-1429): the sorter's half
+ * of gs_mesh_remove, same arguments and renumbering.  A sorter accepts any ranges.  Afterwards every sort's list is what a fresh
+ * sorter of the same capacity and flags gives that received the surviving centres at their new positions: the SoA planes, the
+ * extreme set and the 16-bit centre planes are derived again from the surviving rows.  The call waits for the sort in flight; the
+ * resident result, a gathered list, the per-tree caches and device distances are dropped - sort again (and gather from a new
+ * tree) before the next draw.  GS_ERR_INVALID, and nothing changes, on malformed ranges. */
+int gs_sorter_remove(gs_sorter* s, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap,
+                     uint32_t scene_remap_count);
+
 /* Optional coupling of the two seams: a sorter bound to a mesh leaves its device-resident result as positions in
  * that mesh's internal storage order, so gs_mesh_render(m, ..., sorter = s, ...) needs no per-frame index translation.
  * Host-visible results (sorted_out, gs_sorter_debug_read) are always the caller's splat indexes.  m = NULL unbinds. */
@@ -417,6 +426,24 @@ int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uin
 
 /* Per-splat scene index (sceneIndexesTexture, SplatMesh.js:881-897): needed when more than one scene is loaded. */
 int gs_mesh_upload_scene_indexes(gs_mesh* m, uint32_t from, uint32_t count, const uint32_t* scene_indexes);
+
+/* Remove splats on the device (Viewer.removeSplatScenes without dispose + rebuild, src/Viewer.js:1326-1429).
+ *   ranges       n_ranges pairs {from, count} in the caller's numbering: ascending, disjoint, non-empty, inside
+ *                [0, max_splat_count], 1 <= n_ranges <= GS_MAX_SCENES.  Positions no upload has touched, or beyond the uploaded
+ *                count, simply go away.  n_ranges == 0: GS_OK, nothing happens.
+ *   scene_remap  NULL, or scene_remap_count <= GS_MAX_SCENES words (each < GS_MAX_SCENES): a surviving splat's scene index k
+ *                becomes scene_remap[k] (k >= scene_remap_count: unchanged).  Send the surviving scenes' parameters again with
+ *                gs_mesh_set_scenes.
+ * Every surviving splat i becomes i - (removed positions below i); the uploaded count shrinks, the capacity and every allocation
+ * stay.  No data crosses the bus: the storage spans of the survivors move down on the device.  A mesh in Morton storage order (no
+ * GS_MESH_KEEP_ORDER) accepts a range only if neither of its borders falls inside a Morton run - the span of one fresh segment of
+ * an upload (a first upload of [a, b) is one run); a GS_MESH_KEEP_ORDER mesh accepts any range.
+ * Afterwards the mesh behaves, in every output, as a fresh mesh of the same capacity and flags that received the survivors by the
+ * same uploads at their new positions.  The call waits for the mesh's work in flight and forgets what described the old numbering:
+ * a pending gs_mesh_project, the last draw (gs_mesh_surface, gs_mesh_debug_rop8 and the draw's debug reads answer as before a
+ * first draw), the statistics, and the resident result of every sorter bound to it.  Destination, draw mode and deep-pass switch
+ * stay.  Trees are not edited: build a new one.  GS_ERR_INVALID, and nothing changes, on anything refused. */
+int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count);
 
 /* Per-scene uniforms (SplatMesh.updateUniforms :1263-1276, setupDataTextures :868-878). */
 typedef struct gs_scene_params {

@@ -151,6 +151,56 @@ export class SplatMesh {
     return update;
   }
 
+  // HIP-engine extra, for the body of Viewer.removeSplatScenes (src/Viewer.js:1326-1429) in place of dispose + rebuild: the scenes
+  // `indexes` go away.  Host bookkeeping as a build of the remaining buffers would leave it (scenes - the same objects, so their
+  // transforms stay -, sceneOptions, the two global index maps, the lastBuild* fields, the visible region through
+  // updateVisibleRegion(false)); the device mesh is edited in place (gs_mesh_remove: every scene's range is its buffer's
+  // getMaxSplatCount() span, as buildSplatIndexMaps numbers it) and nothing is filled or uploaded again.  Where the device cannot
+  // do that - a buffer still loading (getSplatCount() < getMaxSplatCount()), or a mesh whose scenes were not uploaded one by
+  // one - the device mesh is built afresh from the remaining buffers, as before.  The splat tree is disposed of either way: call
+  // buildSplatTree.  Returns {edited, ranges, sceneRemap}: what the sort worker's `{remove: {ranges, sceneRemap}}` message takes
+  // when edited is true (else the worker is rebuilt, as the reference does).
+  removeScenes(indexes) {
+    const gone = new Set(indexes);
+    for (const k of gone) if (!(Number.isInteger(k) && k >= 0 && k < this.scenes.length)) throw new Error('SplatMesh::removeScenes() -> Invalid scene index.');
+    const ranges = [], sceneRemap = [], survivors = [], options = [];
+    let at = 0, whole = !!this.core && this.lastBuildSplatCount === this.getSplatCount(true);
+    this.scenes.forEach((sc, k) => {
+      const n = sc.splatBuffer.getMaxSplatCount();
+      whole = whole && sc.splatBuffer.getSplatCount() === n;
+      sceneRemap.push(gone.has(k) ? 0 : survivors.length);
+      if (gone.has(k)) { if (n > 0) ranges.push([at, n]); } else { survivors.push(sc); options.push((this.sceneOptions || [])[k] || {}); }
+      at += n;
+    });
+    if (!gone.size) return { edited: true, ranges, sceneRemap };
+    // (a build of the remaining buffers may choose another SH degree or SH format: then the planes cannot stay)
+    const degree = survivors.reduce((d, sc) => Math.min(d, sc.splatBuffer.getMinSphericalHarmonicsDegree()), Math.min(3, this.sphericalHarmonicsDegree));
+    const level = survivors.length ? Math.max(1, ...survivors.map((sc) => sc.splatBuffer.compressionLevel)) : this.shCompressionLevel;
+    whole = whole && degree === this.minSphericalHarmonicsDegree && level === this.shCompressionLevel;
+    this.minSphericalHarmonicsDegree = degree;
+    let edited = false;
+    if (whole && survivors.length && ranges.length) {
+      try { this.core.remove(ranges, sceneRemap); edited = true; } catch (e) { if (!/Morton run/.test(String(e && e.message))) throw e; }
+    }
+    this.disposeSplatTree();
+    this.scenes = survivors;
+    this.sceneOptions = options;
+    const maps = SplatMesh.buildSplatIndexMaps(survivors.map((sc) => sc.splatBuffer));
+    this.globalSplatIndexToLocalSplatIndexMap = maps.localSplatIndexMap;
+    this.globalSplatIndexToSceneIndexMap = maps.sceneIndexMap;
+    if (!edited) {                                          // the device mesh afresh, from the buffers that stay
+      Object.assign(this, { lastBuildScenes: [], lastBuildSplatCount: 0, lastBuildMaxSplatCount: 0 });
+      this.disposeMeshData();
+      if (survivors.length) this.refreshDataTexturesFromSplatBuffers(false);
+    }
+    Object.assign(this, { lastBuildScenes: survivors.slice(), lastBuildSplatCount: this.getSplatCount(true),
+                          lastBuildMaxSplatCount: this.getMaxSplatCount(), lastBuildSceneCount: survivors.length });
+    this._scenesDirty = true;
+    if (edited) this.updateVisibleRegion(false);            // (a refresh ends with it)
+    this.visible = survivors.length > 0;
+    return { edited, ranges, sceneRemap };
+  }
+
   // setupDataTextures' decisions (:637-690, 1060-1090) without the textures: covariance as fp16 when asked for, SH as fp16
   // (compression level <= 1) or uint8 (level 2: kept 8-bit end to end, like the reference's sphericalHarmonics8BitMode)
   _compressionLevels() { return this.scenes.map((sc) => sc.splatBuffer.compressionLevel); }
@@ -199,8 +249,19 @@ export class SplatMesh {
     // updateBaseDataFromSplatBuffers (:900-913): source range [fromSplat, toSplat], written from 0 of these range arrays
     this.fillSplatDataArrays(covariances, null, null, centers, colors, sh, undefined, covLevel, 0, this.shCompressionLevel,
                              sinceLastBuildOnly ? fromSplat : undefined, sinceLastBuildOnly ? toSplat : undefined, 0);
-    addon.meshUpload(this.core.handle, fromSplat, count, centers, covLevel === 1 ? null : covariances, covLevel === 1 ? covariances : null,
-                     colors, sh && this.shCompressionLevel !== 2 ? sh : null);
+    // A mesh of several scenes receives every scene by an upload of its own - one Morton run each, so that removeScenes can take
+    // whole scenes out on the device (gs_mesh_remove refuses a border inside a run).  One scene, and a progressive load's
+    // appended range, go up in one call as ever.
+    const spans = [];
+    if (!sinceLastBuildOnly && this.scenes.length > 1) {
+      let at = 0;
+      for (const sc of this.scenes) { const c = sc.splatBuffer.getSplatCount(); if (c > 0) spans.push([at, c]); at += c; }
+    } else spans.push([0, count]);
+    for (const [at, c] of spans) {
+      const cut = (array, width) => (array ? array.subarray(at * width, (at + c) * width) : null);
+      addon.meshUpload(this.core.handle, fromSplat + at, c, cut(centers, 3), covLevel === 1 ? null : cut(covariances, 6),
+                       covLevel === 1 ? cut(covariances, 6) : null, cut(colors, 4), sh && this.shCompressionLevel !== 2 ? cut(sh, shComponents) : null);
+    }
     if (sh && this.shCompressionLevel === 2) addon.meshUploadShU8(this.core.handle, fromSplat, count, sh);
     this.core.splatCount = Math.max(this.core.splatCount, fromSplat + count);
     if (this.scenes.length > 1 || this.dynamicMode || this.enableOptionalEffects) {

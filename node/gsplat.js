@@ -131,6 +131,14 @@ class HipSortWorker {
         this._emit(done(r));
         this._drain();
       });
+    } else if (msg.remove) {
+      // HIP-engine extra (the reference's Viewer disposes of its worker instead, src/Viewer.js:1326-1429): the centres of the
+      // {from, count} ranges go away on the device and the survivors are renumbered, in order with the other messages
+      const ranges = Uint32Array.from(msg.remove.ranges.flatMap((r) => (Array.isArray(r) ? r : [r.from, r.count])));
+      addon.sorterRemove(this.handle, ranges, msg.remove.sceneRemap ? Uint32Array.from(msg.remove.sceneRemap) : null);
+      let gone = 0;
+      for (let k = 0; k < ranges.length; k += 2) gone += Math.max(0, Math.min(ranges[k] + ranges[k + 1], this.uploadedSplatCount) - Math.min(ranges[k], this.uploadedSplatCount));
+      this.uploadedSplatCount -= gone;
     } else if (msg.init) {
       // the reference ships its WASM bytes through an init message (SortWorker.js:116-199); nothing to do here
     }
@@ -253,6 +261,15 @@ class SplatMeshHIP {
   // uploaded splats into `out` (Int32Array / Float32Array by original index) and / or a sort worker's device buffer
   computeDistances(flags, uniforms, sceneCount, out, sortWorker) {
     addon.meshComputeDistances(this.handle, flags, uniforms, sceneCount, out || null, this.splatCount, sortWorker ? sortWorker.handle : null);
+  }
+  // the splats of the [from, count] ranges go away on the device; every survivor i becomes i - (removed splats below i)
+  remove(ranges, sceneRemap = null) {
+    const flat = Uint32Array.from(ranges.flatMap((r) => (Array.isArray(r) ? r : [r.from, r.count])));
+    addon.meshRemove(this.handle, flat, sceneRemap ? Uint32Array.from(sceneRemap) : null);
+    let gone = 0;
+    for (let k = 0; k < flat.length; k += 2) gone += Math.max(0, Math.min(flat[k] + flat[k + 1], this.splatCount) - Math.min(flat[k], this.splatCount));
+    this.splatCount -= gone;
+    this.renderCount = Math.min(this.renderCount, this.splatCount);
   }
   setSceneIndexes(sceneIndexes, start = 0) { addon.meshUploadSceneIndexes(this.handle, start, sceneIndexes.length, sceneIndexes); }
   setScenes(params) { addon.meshSetScenes(this.handle, params); this.hasScenes = true; }

@@ -312,6 +312,27 @@ static napi_value SorterSetUploadedCount(napi_env env, napi_callback_info info) 
     return NULL;
 }
 
+/* meshRemove(mesh, ranges Uint32Array {from, count, ...}, sceneRemap Uint32Array|null) and sorterRemove(sorter, ...): the splats
+ * of the ranges go away on the device, the survivors are renumbered (gs_mesh_remove / gs_sorter_remove) */
+static napi_value remove_call(napi_env env, napi_callback_info info, int sorter) {
+    ARGS(3)
+    void *r = NULL, *m = NULL;
+    size_t rb = 0, mb = 0;
+    if (!get_bytes(env, argv[1], &r, &rb) || (rb % 8) != 0) { napi_throw_type_error(env, NULL, "remove: ranges must be a Uint32Array of {from, count} pairs"); return NULL; }
+    napi_valuetype vt;
+    napi_typeof(env, argv[2], &vt);
+    if (vt != napi_null && vt != napi_undefined && !get_bytes(env, argv[2], &m, &mb)) { napi_throw_type_error(env, NULL, "remove: sceneRemap must be a Uint32Array or null"); return NULL; }
+    void* h = get_external(env, argv[0]);
+    int st;
+
+    if (sorter) { LOCKED(st = gs_sorter_remove((gs_sorter*)h, (const uint32_t*)r, (uint32_t)(rb / 8), (const uint32_t*)m, (uint32_t)(mb / 4))); }
+    else { LOCKED(st = gs_mesh_remove((gs_mesh*)h, (const uint32_t*)r, (uint32_t)(rb / 8), (const uint32_t*)m, (uint32_t)(mb / 4))); }
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+static napi_value MeshRemove(napi_env env, napi_callback_info info) { return remove_call(env, info, 0); }
+static napi_value SorterRemove(napi_env env, napi_callback_info info) { return remove_call(env, info, 1); }
+
 /* meshComputeDistances(mesh, flags, uniforms Int32Array|Float32Array, sceneCount, out Int32Array|Float32Array|null, count,
  *                      sorter|null): SplatMesh.computeDistancesOnGPU's pass (gs_mesh_compute_distances).  `count` = the mesh's
  * uploaded splat count (what the pass writes into `out`).  Synchronous under the addon's lock, like every other call here: it
@@ -1058,6 +1079,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"treeSceneLeaves", TreeSceneLeaves}, {"treeGatherScenes", TreeGatherScenes},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
+        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
