@@ -163,6 +163,15 @@ def sort_indexes(indexes, centers4, mvp, sort_count=None, render_count=None, pre
     return out
 
 
+def count_clamped(keys, lo, hi, precision):
+    """How many of `keys` (int32, the sorted part of sort_indexes' keys) the C oracle's bucket map clamped: buckets outside
+    [0, 1 << precision) before the clamp, by the map's own fp32 arithmetic - in integer and in float mode alike."""
+    keys = np.ascontiguousarray(keys, dtype=np.int32)
+    fn = _lib().gso_count_clamped
+    fn.restype = C.c_uint32
+    return int(fn(_p(keys, _i32p), C.c_uint32(0), C.c_uint32(keys.shape[0]), C.c_int32(lo), C.c_int32(hi), C.c_uint32(1 << precision)))
+
+
 def ref_sort_indexes(indexes, centers4, mvp, sort_count=None, render_count=None, precision=16,
                      use_int=True, dynamic=False, precomputed=None, scene_indexes=None, transforms=None):
     """The reference's own compiled sorter (oracle/_ref).  Guards the hi==lo case, where the native

@@ -40,6 +40,14 @@ CASES = [
          permute=True),
     dict(name="pre_int", n=30000, render=30000, sort=30000, precision=16, mode="int", precomputed=True),
     dict(name="pre_float", n=30000, render=30000, sort=30000, precision=16, mode="float", precomputed=True),
+    # precisions whose last digit has 5, 1 and 3 live bits, and float mode's 21, 23 and 24 (this 24-bit case clamps nothing: where
+    # one does, the reference overflows - tests/test_oracle_sort.py, test_precision_24_overflow_is_a_reference_defect_we_flag)
+    dict(name="p13", n=5000, render=5000, sort=5000, precision=13, mode="int"),
+    dict(name="p17", n=5000, render=5000, sort=5000, precision=17, mode="int"),
+    dict(name="p19", n=5000, render=5000, sort=5000, precision=19, mode="int"),
+    dict(name="float_p21", n=5000, render=5000, sort=5000, precision=21, mode="float"),
+    dict(name="float_p23", n=5000, render=5000, sort=5000, precision=23, mode="float"),
+    dict(name="float_p24_small", n=5000, render=5000, sort=5000, precision=24, mode="float"),
 ]
 
 

@@ -43,17 +43,20 @@ def expected_clamps(keys, lo, hi, precision):
 
 
 def check_sort(w, centers4, mvp, path, sort_count=None, render_count=None, indexes=None, precision=16, use_int=True, dynamic=False,
-               scene_indexes=None, transforms=None, what=""):
-    """One sort of `w` (which holds centers4) against the oracle; returns debug_read(4)."""
-    n = centers4.shape[0]
+               scene_indexes=None, transforms=None, precomputed=None, uploaded=None, what=""):
+    """One sort of `w` (which holds centers4) against the oracle; returns debug_read(4).  use_int = False: fp32 centres (or
+    distances); precomputed: one distance per uploaded splat; uploaded: the sorter's count where centers4 is longer (only the
+    listed rows of centers4 are read)."""
+    n = centers4.shape[0] if uploaded is None else uploaded
     R = n if render_count is None else render_count
     Rs = R if sort_count is None else sort_count
-    reply = w.post_message({"sort": {"modelViewProj": mvp, "splatRenderCount": R, "splatSortCount": Rs, "usePrecomputedDistances": False,
-                                     "indexesToSort": indexes, "transforms": transforms, "precomputedDistances": None}})
+    reply = w.post_message({"sort": {"modelViewProj": mvp, "splatRenderCount": R, "splatSortCount": Rs,
+                                     "usePrecomputedDistances": precomputed is not None, "indexesToSort": indexes, "transforms": transforms,
+                                     "precomputedDistances": precomputed}})
     idx = np.arange(n, dtype=np.uint32) if indexes is None else indexes
     exp, keys, buckets, (lo, hi), st = oracle.sort_indexes(idx, centers4, mvp, sort_count=Rs, render_count=R, precision=precision,
-                                                          use_int=use_int, dynamic=dynamic, scene_indexes=scene_indexes,
-                                                          transforms=transforms, return_intermediates=True)
+                                                          use_int=use_int, dynamic=dynamic, precomputed=precomputed,
+                                                          scene_indexes=scene_indexes, transforms=transforms, return_intermediates=True)
     tag = f"{what} n {n} R {R} Rs {Rs}"
     sel = w.debug_read(4, 6)
     assert sel[0] == (1 if path == KNOWN else 0), f"{tag}: front end {sel.tolist()}, expected the {path} path"
@@ -63,7 +66,9 @@ def check_sort(w, centers4, mvp, path, sort_count=None, render_count=None, index
     np.testing.assert_array_equal(w.debug_read(1, R)[s0:], buckets[s0:], err_msg=tag)
     stats = reply["stats"]
     assert (stats.key_min, stats.key_max) == (lo, hi), tag
-    assert stats.clamped == expected_clamps(keys[s0:], lo, hi, precision), tag
+    # (integer mode: the formula above; float mode: what the oracle's own bucket map clamped)
+    clamps = expected_clamps(keys[s0:], lo, hi, precision) if use_int else oracle.count_clamped(keys[s0:], lo, hi, precision)
+    assert stats.clamped == clamps, f"{tag}: clamped {stats.clamped}, the oracle {clamps}"
     assert reply["status"] == st, tag
     if path == KNOWN:
         assert (int(sel[2]), int(sel[3])) == (lo, hi), f"{tag}: the host's range {sel.tolist()} against the oracle's {(lo, hi)}"

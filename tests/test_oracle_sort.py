@@ -66,6 +66,30 @@ def test_c_oracle_matches_compiled_reference_random(seed):
     np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+@pytest.mark.parametrize("precision", range(10, 25))
+def test_c_oracle_matches_compiled_reference_random_float(precision):
+    """Float mode (fp32 centres x 4096, or precomputed fp32 distances) at every precision the Viewer allows it; at 24 bits under the
+    rule of test_precision_24_overflow_is_a_reference_defect_we_flag below."""
+    for seed, pre in ((0, False), (1, False), (2, True)):
+        rng = np.random.default_rng([precision, seed])
+        n = int(rng.integers(1000, 60000))
+        c4 = np.concatenate([rng.normal(size=(n, 3)).astype(np.float32) * 5, np.ones((n, 1), np.float32)], axis=1)
+        idx = rng.permutation(n).astype(np.uint32)
+        render = int(rng.integers(n // 2, n + 1))
+        sort = int(rng.integers(2, render + 1))
+        mvp = rng.normal(size=16)
+        kw = dict(sort_count=sort, render_count=render, precision=precision, use_int=False,
+                  precomputed=rng.uniform(-30.0, 30.0, size=n).astype(np.float32) if pre else None)
+        a, _, _, _, status = oracle.sort_indexes(idx[:render], c4, mvp, return_intermediates=True, **kw)
+        b = oracle.ref_sort_indexes(idx[:render], c4, mvp, **kw)
+        assert np.array_equal(np.sort(a), np.sort(idx[:render]))
+        if precision == 24 and not np.array_equal(np.sort(b), np.sort(idx[:render])):
+            assert status == 1 and (a != b).sum() <= 4         # the reference's overflow: we clamp and say so
+        else:
+            np.testing.assert_array_equal(a, b)
+
+
 def test_integer_centers_round_half_up():
     c = np.array([[0.0005, -0.0005, 1.2345], [-1.0005, 2.5, -2.5]], np.float32)
     got = oracle.integer_centers(c)
