@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "extreme_set.hpp"
 #include "radix.hpp"
@@ -136,6 +137,42 @@ __device__ __forceinline__ int32_t static_key_centre(const KeyParams& p, const u
     return static_key_float(p, c.x, c.y, c.z);
 }
 
+// The dynamic key of one centre (x, y, z, w: its four words as uploaded - w is whatever the caller sent, not a constant) and the
+// row of its scene (four words of SceneRows::im or ::fm, the mode's).  Integer mode: uint32 wrap-around (sorter.cpp:41-62);
+// float mode: fp32 left to right, no contraction, then x4096 in double and WASM's truncation (:110-126).
+__device__ __forceinline__ int32_t dynamic_key(uint32_t mode, const uint4& r, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    if (mode & MODE_INT) return (int32_t)(x * r.x + y * r.y + z * r.z + w * r.w);
+    float s = __fmul_rn(__uint_as_float(r.x), __uint_as_float(x));
+    s = __fadd_rn(s, __fmul_rn(__uint_as_float(r.y), __uint_as_float(y)));
+    s = __fadd_rn(s, __fmul_rn(__uint_as_float(r.z), __uint_as_float(z)));
+    s = __fadd_rn(s, __fmul_rn(__uint_as_float(r.w), __uint_as_float(w)));
+    return trunc_f64_i32((double)s * 4096.0);
+}
+// The row of scene `si` in the mode in use, as four words.  An index beyond the table is masked into it: the key of such a splat
+// is unspecified, the read is not.
+static_assert((GS_MAX_SCENES & (GS_MAX_SCENES - 1)) == 0, "scene indexes are masked into the table");
+__device__ __forceinline__ uint4 scene_row(const SceneRows* rows, uint32_t mode, uint32_t si) {
+    si &= GS_MAX_SCENES - 1u;
+    if (mode & MODE_INT) {
+        const int32_t* r = rows->im[si];
+        return make_uint4((uint32_t)r[0], (uint32_t)r[1], (uint32_t)r[2], (uint32_t)r[3]);
+    }
+    const float* r = rows->fm[si];
+    return make_uint4(__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3]));
+}
+// ... for the streaming kernels of a dynamic sort: the 32 rows of the mode in use, staged in LDS once per workgroup (512 bytes;
+// the caller's next barrier publishes them)
+__device__ __forceinline__ void stage_scene_rows(const KeyParams& p, uint4* s_rows) {
+    if (threadIdx.x < GS_MAX_SCENES) s_rows[threadIdx.x] = scene_row(p.rows, p.mode, threadIdx.x);
+}
+// four consecutive splats of the planes (x, y, z, w, scene index: one 16-byte vector each), rows from LDS
+__device__ __forceinline__ int4 dynamic_key4(uint32_t mode, const uint4* s_rows, const uint4& x, const uint4& y, const uint4& z,
+                                             const uint4& w, const uint4& si) {
+    constexpr uint32_t M = GS_MAX_SCENES - 1u;
+    return make_int4(dynamic_key(mode, s_rows[si.x & M], x.x, y.x, z.x, w.x), dynamic_key(mode, s_rows[si.y & M], x.y, y.y, z.y, w.y),
+                     dynamic_key(mode, s_rows[si.z & M], x.z, y.z, z.z, w.z), dynamic_key(mode, s_rows[si.w & M], x.w, y.w, z.w, w.w));
+}
+
 // Every mode, for the splat a list entry names: precomputed and dynamic keys, else the static key of its gathered centre.
 __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g) {
     if (p.mode & MODE_PRECOMPUTED) {
@@ -145,16 +182,10 @@ __device__ __forceinline__ int32_t depth_key_one(const KeyParams& p, uint32_t g)
     }
     const uint4 c = p.aos[g];                                                              // gathered by list index
     if (!(p.mode & MODE_DYNAMIC)) return static_key(p, c.x, c.y, c.z);                     // (w lane unused)
-    if (p.mode & MODE_INT) {                                                               // :41-62, wrap-around int32
-        const int32_t* r = p.rows->im[p.scene_idx[g]];
-        return (int32_t)(c.x * (uint32_t)r[0] + c.y * (uint32_t)r[1] + c.z * (uint32_t)r[2] + c.w * (uint32_t)r[3]);
-    }
-    const float* r = p.rows->fm[p.scene_idx[g]];                                           // :110-126
-    float s = __fmul_rn(r[0], __uint_as_float(c.x));
-    s = __fadd_rn(s, __fmul_rn(r[1], __uint_as_float(c.y)));
-    s = __fadd_rn(s, __fmul_rn(r[2], __uint_as_float(c.z)));
-    s = __fadd_rn(s, __fmul_rn(r[3], __uint_as_float(c.w)));
-    return trunc_f64_i32((double)s * 4096.0);
+    // (the mode branch around the row's load, constant modes inside: the row stays one 16-byte load behind one branch)
+    const uint32_t si = p.scene_idx[g];
+    if (p.mode & MODE_INT) return dynamic_key(MODE_INT, scene_row(p.rows, MODE_INT, si), c.x, c.y, c.z, c.w);
+    return dynamic_key(0u, scene_row(p.rows, 0u, si), c.x, c.y, c.z, c.w);
 }
 
 // The housekeeping folded into the first kernel of a sort (two launches and their boundaries saved per sort): the radix digit
@@ -528,17 +559,48 @@ __global__ __launch_bounds__(256) void k_tree_copy_keys(TreeCopyParams c, KeyPar
 // A rank of a multi-GPU draw therefore streams 12 bytes per splat and radix-sorts only what its strip draws.
 // (VC_THREADS = 256 threads, VC_SPAN = 1024 positions per workgroup iteration - 4 per lane, 32 mask words: sort_plan.hpp)
 
+// DYN: a dynamic-mode sorter (a compile-time instance, as in k_cull_front) - the key of a position comes from five planes, x, y, z,
+// w and the scene index (20 bytes per splat, one 16-byte vector per plane and lane in both modes), and the scene's row from LDS.
+template <bool DYN>
 __global__ __launch_bounds__(VC_THREADS) void k_minmax_count(KeyParams p, const uint32_t* __restrict__ mask, uint32_t chunk_len,
                                                              uint32_t* __restrict__ chunk_counts) {
     __shared__ uint32_t s_cnt[4];
+    __shared__ uint4 s_rows[DYN ? GS_MAX_SCENES : 1];
     sort_begin(p, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    if (DYN) {
+        stage_scene_rows(p, s_rows);
+        __syncthreads();
+    }
     const uint32_t N = p.render_count;
     const uint32_t begin = min(blockIdx.x * chunk_len, N), end = min(begin + chunk_len, N);     // chunk_len % VC_SPAN == 0
     MinMax mm;
     uint32_t cnt = 0;
+    // DYN: the five vectors of span k + 1 are requested before span k is keyed (two register sets, as in k_cull_front: the grid is
+    // two workgroups per CU, so what is in flight per lane is what hides the latency).  Unconditional loads, clamped into the list -
+    // the planes are padded by 16 bytes, so the vector that holds the list's last position is readable whatever N is.
+    struct Span { uint4 x, y, z, w, s; };
+    Span cur, nxt;
+    auto fetch = [&](uint32_t base, Span& v) {
+        const uint32_t i0 = base + 4u * threadIdx.x, q = (i0 < N ? i0 : 0u) >> 2;
+        v.x = reinterpret_cast<const uint4*>(p.cx)[q]; v.y = reinterpret_cast<const uint4*>(p.cy)[q];
+        v.z = reinterpret_cast<const uint4*>(p.cz)[q]; v.w = reinterpret_cast<const uint4*>(p.cw)[q];
+        v.s = reinterpret_cast<const uint4*>(p.scene_idx)[q];
+    };
+    if constexpr (DYN) { if (begin < end) fetch(begin, cur); }
     for (uint32_t base = begin; base < end; base += VC_SPAN) {
         const uint32_t i0 = base + 4u * threadIdx.x;
-        if ((p.mode & MODE_INT) && i0 + 4u <= end) {               // 16-byte plane loads
+        if constexpr (DYN) {
+            fetch(base + VC_SPAN, nxt);
+            const int4 k = dynamic_key4(p.mode, s_rows, cur.x, cur.y, cur.z, cur.w, cur.s);
+            if (i0 + 4u <= end) {
+                mm.take(k);
+            } else {                                               // (the list's ragged end: min / max over its positions only)
+                if (i0 < end) mm.take(k.x);
+                if (i0 + 1u < end) mm.take(k.y);
+                if (i0 + 2u < end) mm.take(k.z);
+            }
+            cur = nxt;
+        } else if ((p.mode & MODE_INT) && i0 + 4u <= end) {        // 16-byte plane loads
             mm.take(static_key_int4(p, reinterpret_cast<const uint4*>(p.cx)[i0 >> 2], reinterpret_cast<const uint4*>(p.cy)[i0 >> 2],
                                     reinterpret_cast<const uint4*>(p.cz)[i0 >> 2]));
         } else {
@@ -718,13 +780,21 @@ __global__ __launch_bounds__(VC_THREADS) void k_mask_derive_count(KeyParams p, c
 }
 
 // MAP: payloads come from the bound mesh's position table (a compile-time switch, see above)
-template <bool MAP>
+// DYN: a dynamic-mode sorter - two more 16-byte vectors per lane and span (four w, four scene indexes: 24 bytes per position with
+// the payload map instead of 16) and the scenes' rows of the mode in use from LDS, staged once per workgroup behind the barrier the
+// prologue has anyway.  A compile-time instance for the reason MAP is one; every lane reads the row of each of its positions (no
+// wave-uniform shortcut: scenes drawn at random per splat are as valid as scenes back to back).
+struct CullTurnStatic {};
+struct CullTurnDynamic { uint4 W[VC_UNROLL], S[VC_UNROLL]; };
+template <bool MAP, bool DYN>
 __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t* __restrict__ mask, uint32_t* __restrict__ mask_copy,
                                                            const uint32_t* __restrict__ chunk_counts, uint32_t chunk_len,
                                                            const uint32_t* __restrict__ map, uint32_t* __restrict__ pay_out, uint32_t subs) {
     __shared__ uint32_t s_before[4], s_all[4], s_turn[2][4];
+    __shared__ uint4 s_rows[DYN ? GS_MAX_SCENES : 1];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     static_assert(VC_THREADS == 256, "four waves per workgroup");
+    if (DYN) stage_scene_rows(p, s_rows);                           // (published by the barrier below)
     uint32_t before = 0, all = 0;                                   // survivors of the chunks before this one / of all chunks
     // (the counts arrive in `subs` consecutive pieces per chunk: k_mask_count writes one, k_mask_derive_count one per sub-workgroup)
     const uint32_t pieces = gridDim.x * subs, mine = blockIdx.x * subs;
@@ -754,11 +824,15 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
     const uint4* __restrict__ x4 = reinterpret_cast<const uint4*>(p.cx);
     const uint4* __restrict__ y4 = reinterpret_cast<const uint4*>(p.cy);
     const uint4* __restrict__ z4 = reinterpret_cast<const uint4*>(p.cz);
+    const uint4* __restrict__ w4 = reinterpret_cast<const uint4*>(p.cw);
+    const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(p.scene_idx);
     int32_t* __restrict__ keys_out = p.keys_out;
     const uint4* __restrict__ map4 = reinterpret_cast<const uint4*>(map);
     // The loads of turn t + 1 are issued BEFORE turn t is keyed and stored (two register sets): all workgroups run in step, so a
     // turn that loads, then computes, then stores left the memory system idle between the bursts - 36-44 us for 93 MB (r05h/i).
-    struct Turn { uint4 X[VC_UNROLL], Y[VC_UNROLL], Z[VC_UNROLL], M[VC_UNROLL]; uint32_t raw[VC_UNROLL]; };
+    struct Turn : std::conditional<DYN, CullTurnDynamic, CullTurnStatic>::type {
+        uint4 X[VC_UNROLL], Y[VC_UNROLL], Z[VC_UNROLL], M[VC_UNROLL]; uint32_t raw[VC_UNROLL];
+    };
     auto fetch = [&](uint32_t base, Turn& t) {
         const uint32_t wbase = base + wave * (VC_UNROLL * VC_WAVE_SPAN);    // this wave's spans of the turn
 #pragma unroll
@@ -768,6 +842,7 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
             // list's last position is readable whatever N is)
             const uint32_t ic = i0 < N ? i0 : 0u;
             t.X[u] = x4[ic >> 2]; t.Y[u] = y4[ic >> 2]; t.Z[u] = z4[ic >> 2];
+            if constexpr (DYN) { t.W[u] = w4[ic >> 2]; t.S[u] = s4[ic >> 2]; }     // (padded as the other planes are)
             t.M[u] = MAP ? map4[ic >> 2] : make_uint4(ic, ic + 1u, ic + 2u, ic + 3u);   // the payloads travel with the centres
             t.raw[u] = i0 < end ? mask[i0 >> 5] : 0u;                      // the mask word of the four positions (eight lanes share one)
         }
@@ -787,7 +862,13 @@ __global__ __launch_bounds__(VC_THREADS) void k_cull_front(KeyParams p, uint32_t
             int32_t k[4] = {0, 0, 0, 0};
             uint32_t word = cur.raw[u];
             if (i0 < end && end - (i0 & ~31u) < 32u) word &= (1u << (end - (i0 & ~31u))) - 1u;    // positions beyond this sort's list
-            {   // keys from the vectors (no memory access in this phase: a load in a branch here puts a full wait at its join)
+            if constexpr (DYN) {   // (the rows: unconditional LDS reads, the index masked into the table)
+                const int4 k4 = dynamic_key4(p.mode, s_rows, cur.X[u], cur.Y[u], cur.Z[u], cur.W[u], cur.S[u]);
+                k[0] = k4.x; k[1] = k4.y; k[2] = k4.z; k[3] = k4.w;
+#pragma unroll
+                for (uint32_t c = 0; c < 4u; c++)
+                    if (i0 + c < end) mm.take(k[c]);
+            } else {   // keys from the vectors (no memory access in this phase: a load in a branch here puts a full wait at its join)
                 const uint32_t xs[4] = {cur.X[u].x, cur.X[u].y, cur.X[u].z, cur.X[u].w}, ys[4] = {cur.Y[u].x, cur.Y[u].y, cur.Y[u].z, cur.Y[u].w},
                                zs[4] = {cur.Z[u].x, cur.Z[u].y, cur.Z[u].z, cur.Z[u].w};
 #pragma unroll
@@ -1243,7 +1324,7 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     int st = GS_OK;
     auto A = [&](DevBuf& b, size_t bytes) { if (st == GS_OK) st = b.alloc(bytes); };
     A(s->cx, b4 + 16); A(s->cy, b4 + 16); A(s->cz, b4 + 16); A(s->caos, n * 16);   // (+16: k_cull_front reads whole 16-byte vectors)
-    if (flags & GS_SORT_DYNAMIC) { A(s->cw, b4); A(s->scene_idx, b4); A(s->scene_rows, sizeof(SceneRows)); }
+    if (flags & GS_SORT_DYNAMIC) { A(s->cw, b4 + 16); A(s->scene_idx, b4 + 16); A(s->scene_rows, sizeof(SceneRows)); }   // (+16: as above)
     A(s->keys, b4); A(s->keyA, b4); A(s->keyB, b4); A(s->valA, b4); A(s->valB, b4); A(s->sorted, b4);
     A(s->keys16, n * 2 + 16);
     A(s->frame, 2 * sizeof(SortFrame));
@@ -1600,8 +1681,9 @@ static int sort_check(gs_sorter* s, SortCall& c, SortPlanIn& in) {
     GS_REQUIRE(!dynamic || c.transforms, "dynamic sorter needs transforms");
     GS_REQUIRE(!c.list_count_dev || (c.device_list && n.Rs == n.R && !dynamic && !c.precomputed),
                "a gathered list whose length lives on the device needs a full sort of a static scene without precomputed distances");
-    GS_REQUIRE(!(n.cull || n.vis_cull) || (n.Rs == n.R && !dynamic && !c.precomputed),
-               "a per-splat cull needs a full sort (splatSortCount == splatRenderCount) of a static scene without precomputed distances");
+    GS_REQUIRE(!(n.cull || n.vis_cull) || (n.Rs == n.R && !c.precomputed),
+               "a per-splat cull needs a full sort (splatSortCount == splatRenderCount) without precomputed distances");
+    GS_REQUIRE(!n.cull || !dynamic, "the per-splat frustum cull needs a static scene (a dynamic-mode sorter culls by visibility only)");
     if (!sorter_mesh_alive(s->ctx, s->bound_mesh)) s->bound_mesh = nullptr;   // the mesh may have been destroyed since the bind
     const gs_mesh* mesh = s->bound_mesh;
     c.map = mesh ? gs_mesh_payload_map(s->bound_mesh, s->uploaded) : nullptr;
@@ -1760,6 +1842,8 @@ static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan
     ProjSet& ps = mesh->set();                              // the set the pending gs_mesh_project wrote
     const uint32_t R = pl.R;
     const bool stream = pl.front == SORT_FRONT_VIS_STREAM, lazy = pl.vis_derive != 0u;
+    // a dynamic-mode sorter: the DYN instances key from five planes and the rows sort_stage_inputs stored on this stream (kp.rows)
+    const bool dynamic = (kp.mode & MODE_DYNAMIC) != 0u;
     GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
     GS_TRY(s->mask_copy.ensure(((size_t)s->max_count + 31) / 32 * 4 + 64));
     uint32_t* mask = ps.vis_orig.as<uint32_t>();
@@ -1776,12 +1860,13 @@ static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan
                                  pl.derive_len, VC_DERIVE_SUBS, reinterpret_cast<unsigned long long*>(mask), counts);
     if (stream) {
         if (!lazy) hipLaunchKernelGGL(k_mask_count, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, pl.front_len, counts);
-        if (c.map) hipLaunchKernelGGL(k_cull_front<true>, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                      counts, pl.front_len, c.map, s->pay_in.as<uint32_t>(), lazy ? VC_DERIVE_SUBS : 1u);
-        else hipLaunchKernelGGL(k_cull_front<false>, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(),
-                                counts, pl.front_len, c.map, s->pay_in.as<uint32_t>(), 1u);
+        auto* front = c.map ? (dynamic ? k_cull_front<true, true> : k_cull_front<true, false>)
+                            : (dynamic ? k_cull_front<false, true> : k_cull_front<false, false>);
+        hipLaunchKernelGGL(front, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, s->mask_copy.as<uint32_t>(), counts, pl.front_len,
+                           c.map, s->pay_in.as<uint32_t>(), lazy ? VC_DERIVE_SUBS : 1u);     // (lazy: only with a map, see above)
     } else {
-        hipLaunchKernelGGL(k_minmax_count, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask, pl.front_len, counts);
+        hipLaunchKernelGGL(dynamic ? k_minmax_count<true> : k_minmax_count<false>, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, kp, mask,
+                           pl.front_len, counts);
         hipLaunchKernelGGL(k_mask_compact, dim3(pl.front_grid), dim3(VC_THREADS), 0, st, mask, s->mask_copy.as<uint32_t>(), counts, R,
                            pl.front_len, s->idx_in.as<uint32_t>(), kp.frame);
     }
@@ -1978,7 +2063,6 @@ int gs_sorter_set_frustum_cull(gs_sorter* s, int enable) {
 
 int gs_sorter_set_visibility_cull(gs_sorter* s, int enable) {
     GS_REQUIRE(s != nullptr, "sorter == NULL");
-    GS_REQUIRE(!enable || !(s->flags & GS_SORT_DYNAMIC), "the visibility cull is not available to a dynamic-mode sorter");
     s->visibility_cull = enable != 0;
     sorter_tell_mesh(s);
     return GS_OK;

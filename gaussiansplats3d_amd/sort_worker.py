@@ -168,7 +168,10 @@ class SortWorker:
     def set_visibility_cull(self, enable=True):
         """Exact per-splat cull (gs_sorter_set_visibility_cull): a full sort keeps the list positions whose splat survived
         ``SplatMesh.project`` of this frame's camera (and strip).  Needs ``mesh.use_sorter_result(self, ...)`` (the bind)
-        and, every frame, ``mesh.project()`` before the sort."""
+        and, every frame, ``mesh.project()`` before the sort.  A dynamic-mode worker culls the same way: the `sort` message
+        carries `transforms` as always, and the mesh must be a dynamic_mode one projected under the same transforms
+        (``mesh.set_scenes``).  Still refused: a partial sort or precomputed distances under the cull, a dynamic worker's
+        ``sort_gathered`` of an asynchronous gather, and ``set_frustum_cull`` on a dynamic worker."""
         L.check(self.lib.gs_sorter_set_visibility_cull(self.handle, 1 if enable else 0))
         self.visibility_cull = bool(enable)
 

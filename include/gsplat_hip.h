@@ -163,7 +163,13 @@ int gs_sorter_set_frustum_cull(gs_sorter* s, int enable);
  * list position, so the result is the reference's sorted list restricted to the splats this frame (this rank's strip)
  * draws, and the frame is bit-identical.  This is how the tile-row strips of a multi-GPU draw shard the sort: each rank
  * keys all splats (12 bytes each) but radix-sorts and bins only its own.  Order per frame:
- *     gs_mesh_project(m, cam) -> gs_sorter_sort(s, mvp of the same camera, ...) -> gs_mesh_render(m, cam, sorter = s). */
+ *     gs_mesh_project(m, cam) -> gs_sorter_sort(s, mvp of the same camera, ...) -> gs_mesh_render(m, cam, sorter = s).
+ * A GS_SORT_DYNAMIC sorter culls the same way (20 bytes per splat keyed: x, y, z, w and the scene index): the sort takes
+ * `transforms` as any dynamic sort does, and the mesh's projection must have been made with GS_CAM_DYNAMIC and the same scene
+ * transforms (gs_mesh_set_scenes) - the mask is what THAT projection drew.  A scene index >= GS_MAX_SCENES gives an unspecified key.
+ * Refused (GS_ERR_INVALID at the sort): a partial sort (sort_count < render_count) and precomputed distances under the cull, for
+ * either kind of sorter; for a dynamic one also a gathered list whose length lives on the device (gs_tree_gather with
+ * render_count == NULL).  gs_sorter_set_frustum_cull keeps refusing a dynamic sorter. */
 int gs_sorter_set_visibility_cull(gs_sorter* s, int enable);
 
 /* Test hooks: intermediates of the last sort, positions [0, render_count) (valid in the sorted tail).

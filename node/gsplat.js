@@ -157,7 +157,9 @@ class HipSortWorker {
   }
 
   // HIP-engine extras (no counterpart in the reference).  bindMesh: results stay on the device as positions in the mesh's
-  // storage order; setVisibilityCull: full sorts keep only what mesh.project() of this frame's camera (and strip) draws
+  // storage order; setVisibilityCull: full sorts keep only what mesh.project() of this frame's camera (and strip) draws - also for
+  // a dynamicMode worker, whose sort message carries `transforms` as always (the mesh: dynamicMode, setScenes with the same ones);
+  // setFrustumCull stays refused there
   bindMesh(mesh) { addon.sorterBindMesh(this.handle, mesh ? mesh.handle : null); }
   setVisibilityCull(enable) {
     addon.sorterSetVisibilityCull(this.handle, enable ? 1 : 0);
