@@ -11,7 +11,8 @@ Runs only where /root/reference exists (with Node and g++).
 4. Seeded scenes (tests/raster_cases.py) go through the vertex shader for all four quad corners, sample fragments through
    the fragment shader; outputs are stored.  tests/test_raster_ref.py compares the C raster oracle (CPU tier) and the HIP
    vertex stage (GPU tier) with them.
-usage: python -m oracle.make_golden_raster"""
+usage: python -m oracle.make_golden_raster            (tests/raster_cases.py       -> tests/golden/raster_ref.npz)
+       python -m oracle.make_golden_raster --combos   (tests/raster_combo_cases.py -> tests/golden/raster_combo_ref.npz)"""
 import ctypes as C
 import hashlib
 import json
@@ -106,7 +107,10 @@ def harness_inputs(case):
         u.transforms[s_][:] = np.asarray(t, np.float64).astype(np.float32).tolist()
         u.scene_opacity[s_] = un["scene_opacity"][s_] if s_ < len(un["scene_opacity"]) else 1.0
         u.scene_visibility[s_] = un["scene_visibility"][s_] if s_ < len(un["scene_visibility"]) else 1
-        u.sh8_min[s_], u.sh8_max[s_] = un["sh8_range"]
+        r = un["sh8_range"]                                   # one (min, max) for every scene, or a list with one per scene
+        if isinstance(r, list):
+            r = r[s_] if s_ < len(r) else r[0]
+        u.sh8_min[s_], u.sh8_max[s_] = r
     return sc, u, keep
 
 
@@ -129,11 +133,11 @@ def run_fragment(lib, v_position, v_color):
     return col, disc
 
 
-def main():
+def build_shaders(builds):
+    """SplatMaterial3D.build(...) per entry of `builds` -> ({name: harness library}, {name: sha-256 of the texts + material state})."""
     assert os.path.isdir(REF_SRC), "reference not present"
     scratch = os.path.join(ROOT, "oracle", "_ref", "shaders")
     os.makedirs(scratch, exist_ok=True)
-    builds = raster_cases.shader_builds()
     json.dump([dict(name=k, **v) for k, v in builds.items()], open(os.path.join(scratch, "perms.json"), "w"))
     subprocess.check_call(["node", "--no-warnings", "--experimental-loader", os.path.join(ROOT, "oracle", "three_loader.mjs"),
                            os.path.join(ROOT, "oracle", "shader_dump.mjs"), REF_SRC, scratch, os.path.join(scratch, "perms.json")],
@@ -145,6 +149,19 @@ def main():
         libs[name] = build_shader_lib(name, vert, frag, defines, scratch)
         meta[name] = dict(vert_sha256=hashlib.sha256(vert.encode()).hexdigest(), frag_sha256=hashlib.sha256(frag.encode()).hexdigest(),
                           state=json.load(open(os.path.join(scratch, name + ".state.json"))))
+    return libs, meta
+
+
+def shader_verdicts(res):
+    """Per splat of a run_vertex result: (drawn, rejected by gl_Position = (0, 0, 2, 1), left by an early `return`)."""
+    reject = (res[:, 0, 2] == 2.0) & (res[:, 0, 3] == 1.0) & (res[:, 0, 0] == 0.0)
+    early = ~np.isfinite(res[:, :, 0:4]).all(axis=(1, 2))
+    z = res[:, 0, 2].astype(np.float64)
+    return ~reject & ~early & (z >= -1.0) & (z <= 1.0), reject, early
+
+
+def main():
+    libs, meta = build_shaders(raster_cases.shader_builds())
     out = {}
     for cname in raster_cases.CASES:
         case = raster_cases.make_case(cname)
@@ -160,5 +177,47 @@ def main():
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "raster_ref.npz"), **out)
 
 
+def combo_census(case, res, sibling_res):
+    """What keeps a combined case from passing vacuously, counted on the reference shader's outputs alone (`sibling_res`: the same
+    inputs through the build without `antialiased`, or None).  tests/test_raster_combo_ref.py asserts the bounds."""
+    import raster_combo_cases as rcc
+    u = case["uniforms"]
+    drawn, reject, early = shader_verdicts(res)
+    k = max(u["scene_count"], 1)
+    of = case["scene_idx"] if case["scene_idx"] is not None else np.zeros(res.shape[0], np.uint32)
+    census = dict(drawn=int(drawn.sum()), drawn_per_scene=np.bincount(of[drawn], minlength=k).tolist(),
+                  rejected_per_scene=np.bincount(of[reject], minlength=k).tolist())
+    if not u["fade_in_complete"]:
+        f = rcc.fade_factor(case)
+        alpha = res[:, 0, 7]                                  # vColor.a: exactly 0 where the shader's own factor is 0
+        census["fade_partial"] = int((drawn & (f > 1e-3) & (f < 1.0 - 1e-3) & (alpha > 0)).sum())
+        census["fade_zero"] = int((drawn & (f == 0.0) & (alpha == 0)).sum())
+    if sibling_res is not None:
+        census["aa_only_rejects"] = int((early & shader_verdicts(sibling_res)[0]).sum())
+    if case["max_splat_px"] < 1024.0:                         # |basisVector1| = splatScale * clamp px, seen through inverseFocalAdjustment
+        vp = np.asarray(u["viewport"], np.float64)
+        b1 = (res[:, 2, 0:2].astype(np.float64) - res[:, 1, 0:2]) * 0.25 * vp
+        at = case["max_splat_px"] * u["splat_scale"] * u["inverse_focal_adjustment"]
+        census["at_clamp"] = int((drawn & (np.abs(np.hypot(b1[:, 0], b1[:, 1]) - at) <= 1e-3 * at)).sum())
+    return census
+
+
+def combos():
+    """The combined permutations (tests/raster_combo_cases.py) -> tests/golden/raster_combo_ref.npz."""
+    import raster_combo_cases as rcc
+    libs, meta = build_shaders({**rcc.shader_builds(), **rcc.census_builds()})
+    out, census = {}, {}
+    for cname in rcc.CASES:
+        case = rcc.make_case(cname)
+        res = run_vertex(libs[case["build"]], case)
+        out["vs_" + cname] = res
+        sibling = rcc.CENSUS_SIBLING.get(case["build"]) if cname in rcc.AA_REJECT_CASES else None
+        census[cname] = combo_census(case, res, run_vertex(libs[sibling], case) if sibling else None)
+        print(f"{cname:22s} build={case['build']:14s} {census[cname]}")
+    meta = dict(builds={k: meta[k] for k in rcc.shader_builds()}, census_builds={k: meta[k] for k in rcc.census_builds()}, census=census)
+    out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "raster_combo_ref.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    combos() if "--combos" in sys.argv[1:] else main()

@@ -33,6 +33,18 @@ def _from_shader(res, viewport):
     return drawn, centre, b1, b2, res[:, 0, 4:8].astype(np.float64)
 
 
+def _scene_switches(case):
+    """(dynamicMode, enableOptionalEffects) of a case: what a combined case (tests/raster_combo_cases.py) says itself, else what the
+    single-feature builds of raster_cases.py stand for."""
+    return case.get("dynamic", case["build"] == "dynamic2"), case.get("effects", case["build"] == "effects1")
+
+
+def _scene_ranges(u):
+    """uniforms["sh8_range"] as a list with one (min, max) per scene: it is either that already, or one range for all scenes."""
+    r = u["sh8_range"]
+    return list(r) if isinstance(r, list) else [r] * max(u["scene_count"], 1)
+
+
 def _oracle_camera(case):
     u, cam = case["uniforms"], case["camera"]
     ocam = oracle.make_camera(u["model_view"], u["projection"], u["camera_position"], cam.width, cam.height,
@@ -45,41 +57,58 @@ def _oracle_camera(case):
     if not u["fade_in_complete"]:
         ocam.fade_in, ocam.fade_start = 1, u["fade_start_radius"]
         ocam.scene_center[:] = u["scene_center"]
+    dynamic, effects = _scene_switches(case)
     if case["sh8"]:
         ocam.sh8 = 1
-        oracle.set_scenes(ocam, sh8_range=[u["sh8_range"]] * max(u["scene_count"], 1), opacity=[1.0] * max(u["scene_count"], 1))
-    if case["build"] == "effects1":
-        oracle.set_scenes(ocam, opacity=u["scene_opacity"], visible=u["scene_visibility"], effects=True)
-    if case["build"] == "dynamic2":
-        oracle.set_scenes(ocam, view_matrix=u["view_matrix"], transforms=u["transforms"], camera_position=u["camera_position"],
-                          dynamic=True)
+    if case["sh8"] or dynamic or effects:                     # one call: set_scenes writes every per-scene table and both switches
+        k = max(u["scene_count"], 1)
+        oracle.set_scenes(ocam, view_matrix=u["view_matrix"] if dynamic else None, transforms=u["transforms"] if dynamic else None,
+                          camera_position=u["camera_position"] if dynamic else None, opacity=u["scene_opacity"] or [1.0] * k,
+                          visible=u["scene_visibility"] or None, sh8_range=_scene_ranges(u) if case["sh8"] else None,
+                          dynamic=dynamic, effects=effects)
     return ocam
 
 
-@pytest.mark.parametrize("name", raster_cases.CASES)
-def test_c_oracle_vertex_stage_matches_the_reference_shader(name):
-    case = raster_cases.make_case(name)
-    drawn, centre, b1, b2, colour = _from_shader(G["vs_" + name], case["uniforms"]["viewport"])
+def oracle_project(case, ocam, scene_indexes=None):
+    """oracle.project of a raster case through `ocam` (8-bit SH as the stored bytes); scene_indexes: instead of the case's own."""
     sh = None
     if case["sh_stored"]:
         sh = case["sh_u8"].astype(np.float32) if case["sh8"] else case["sh_sampled"]
-    o = oracle.project(_oracle_camera(case), case["centers"], case["cov"], case["rgba"], sh, scene_indexes=case["scene_idx"])
+    return oracle.project(ocam, case["centers"], case["cov"], case["rgba"], sh,
+                          scene_indexes=case["scene_idx"] if scene_indexes is None else scene_indexes)
+
+
+def check_oracle_projection(case, res, o):
+    """The CPU tier's gate: the C oracle's projection `o` of a case against a shader's outputs `res` ([n, 4, 10]) of the same splats.
+    Returns the worst differences seen: centre in px, basis as a fraction of its bound, colour."""
+    drawn, centre, b1, b2, colour = _from_shader(res, case["uniforms"]["viewport"])
     vis = o["visible"] == 1
     assert drawn.sum() > 100
     np.testing.assert_array_equal(vis, drawn, err_msg="accept / reject decisions differ from the shader's")
     k = drawn
     np.testing.assert_allclose(o["cx"][k], centre[k, 0], rtol=0, atol=2e-3)
     np.testing.assert_allclose(o["cy"][k], centre[k, 1], rtol=0, atol=2e-3)
+    worst = dict(centre=float(max(np.abs(o["cx"][k] - centre[k, 0]).max(), np.abs(o["cy"][k] - centre[k, 1]).max())), basis=0.0, colour=0.0)
+    # the shader adds the basis to an NDC centre of magnitude <= 1.2 before the harness subtracts it again: that costs
+    # up to 1.2 * 2^-24 * viewport / 2 px of absolute precision
+    atol = 1e-4 * max(case["uniforms"]["viewport"]) / 100
     for col, ref in (("b1x", b1[:, 0]), ("b1y", b1[:, 1]), ("b2x", b2[:, 0]), ("b2y", b2[:, 1])):
-        # the shader adds the basis to an NDC centre of magnitude <= 1.2 before the harness subtracts it again: that costs
-        # up to 1.2 * 2^-24 * viewport / 2 px of absolute precision
-        np.testing.assert_allclose(o[col][k], ref[k], rtol=2e-4, atol=1e-4 * max(case["uniforms"]["viewport"]) / 100)
-    tol = 2e-4 if name == "dynamic" else 3e-6                 # dynamic: GLSL inverse() in fp32 vs the host's fp64 inverse
+        np.testing.assert_allclose(o[col][k], ref[k], rtol=2e-4, atol=atol)
+        worst["basis"] = max(worst["basis"], float((np.abs(o[col][k] - ref[k]) / (atol + 2e-4 * np.abs(ref[k]))).max()))
+    tol = 2e-4 if _scene_switches(case)[0] else 3e-6          # dynamic: GLSL inverse() in fp32 vs the host's fp64 inverse
     for ch, col in enumerate("rgba"):
         np.testing.assert_allclose(o[col][k], colour[k, ch], rtol=0, atol=tol)
+        worst["colour"] = max(worst["colour"], float(np.abs(o[col][k] - colour[k, ch]).max()))
     # vPosition of the four corners = corner * sqrt(8)
     corners = np.array([[-1, -1], [-1, 1], [1, 1], [1, -1]], np.float32) * SQRT8
-    np.testing.assert_array_equal(G["vs_" + name][k][:, :, 8:10], np.broadcast_to(corners, (int(k.sum()), 4, 2)))
+    np.testing.assert_array_equal(res[k][:, :, 8:10], np.broadcast_to(corners, (int(k.sum()), 4, 2)))
+    return worst
+
+
+@pytest.mark.parametrize("name", raster_cases.CASES)
+def test_c_oracle_vertex_stage_matches_the_reference_shader(name):
+    case = raster_cases.make_case(name)
+    check_oracle_projection(case, G["vs_" + name], oracle_project(case, _oracle_camera(case)))
 
 
 def test_fragment_rule_matches_the_reference_shader():
@@ -119,14 +148,14 @@ def engine_mesh(ctx, case):
     mesh = SplatMesh(ctx, sc.count, sc.sh_degree, half_precision_covariances=case["cov_half"], antialiased=case["antialiased"],
                      kernel_2d_size=case["kernel2d"], max_screen_space_splat_size=case["max_splat_px"], splat_scale=u["splat_scale"],
                      point_cloud_mode=bool(u["point_cloud"]), spherical_harmonics_8bit=case["sh8"],
-                     dynamic_mode=case["build"] == "dynamic2", enable_optional_effects=case["build"] == "effects1")
+                     dynamic_mode=_scene_switches(case)[0], enable_optional_effects=_scene_switches(case)[1])
     mesh.build(sc.centers, sc.cov, sc.rgba, case["sh_u8"] if case["sh8"] else (sc.sh if sc.sh_degree else None),
                scene_indexes=case["scene_idx"])
     if case["sh8"] or case["scene_idx"] is not None:
         k = max(u["scene_count"], 1)
         mesh.set_scenes(transforms=u["transforms"] or None, camera_position=u["camera_position"],
                         opacity=u["scene_opacity"] or [1.0] * k, visible=u["scene_visibility"] or [1] * k,
-                        sh8_range=[u["sh8_range"]] * k)
+                        sh8_range=_scene_ranges(u))
     if not u["fade_in_complete"]:
         mesh.set_fade_in(u["scene_center"], u["fade_start_radius"])
     mesh.set_camera(case["camera"], focal_adjustment=1.0 / u["inverse_focal_adjustment"], spherical_harmonics_degree=u["sh_degree"])
