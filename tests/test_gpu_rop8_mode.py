@@ -8,6 +8,8 @@ import pytest
 
 import helpers
 import oracle
+import rop8_ref
+import surface_cases
 from gaussiansplats3d_amd import Context, SplatMesh, camera, create_sort_worker, util
 from test_gpu_depth import _occluder, _order
 
@@ -57,7 +59,14 @@ def test_rop8_draw_matches_the_rop_emulating_oracle_on_every_pixel(ctx, sh_degre
     r8 = mesh.rop8_window(*win).astype(np.int32)
     dd = np.abs(r8 - got[win[1]:win[1] + win[3], win[0]:win[0] + win[2]].astype(np.int32))
     assert dd.max() <= 1 and (dd == 0).mean() >= 0.995, (int(dd.max()), float((dd == 0).mean()))
-    # the mode walks every list to its end: at least the pairs the fp32 draw walked before its pixels saturated
+    # the pairs the mode walks, predicted from the draw's own lists (tests/rop8_ref.py): every survivor of every live quadrant for the
+    # full walk, the survivors in front of each quadrant's stop for the bounded one - exact wherever the model has one candidate
+    lo, hi = rop8_ref.walked_range(surface_cases.draw_of(mesh, scene.centers), rop8_ref.FULL if full else rop8_ref.BOUNDED)
+    print(f"splats_walked {int(st.splats_walked)}, the model says {lo} .. {hi} (the fp32 draw walked {int(st32.splats_walked)})")
+    assert lo <= st.splats_walked <= hi, (int(st.splats_walked), lo, hi)
+    # ... and the prediction says something: the full walk's range is open only by the pairs in the quadrant test's band (a per cent
+    # at the most), the bounded walk's also by the tests at which a gradually saturating quadrant may stop (a quarter at the most)
+    assert hi - lo <= (0.01 if full else 0.25) * lo, (lo, hi)
     assert st.splats_walked >= st32.splats_walked and st.visible_splats == st32.visible_splats
     # strips reproduce the frame bit for bit, and the fp32 mode comes back unchanged
     rows = (h + 15) // 16
