@@ -148,6 +148,7 @@ SYMBOLS = {
     "gs_mesh_upload_sh_u8": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
     "gs_mesh_upload_scene_indexes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
     "gs_mesh_remove": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint32]),
+    "gs_mesh_reorder": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "gs_mesh_set_scenes": (C.c_int, [_VP, C.POINTER(SceneParams)]),
     "gs_mesh_project": (C.c_int, [_VP, C.POINTER(Camera)]),
     "gs_mesh_set_destination": (C.c_int, [_VP, C.POINTER(Destination)]),

@@ -591,6 +591,12 @@ int gs_remove_compact(hipStream_t st, const RemoveMap& map, void* plane, uint32_
                       uint32_t old_end, void* scratch);
 int gs_mesh_block_boxes(gs_mesh* m, uint32_t b0, uint32_t b1);   // k_block_boxes over storage blocks [b0, b1), on ctx->stream (mesh.hip)
 void gs_sorter_mesh_edited(gs_sorter* s);                        // the bound mesh renumbered its splats (sorter.hip)
+// Folding Morton runs (mesh_edit.hip: gs_mesh_reorder).  The Morton order of a run is mesh.hip's, for an upload and for the fold:
+int gs_mesh_centre_bounds(gs_mesh* m, const float* c3, uint32_t count, float mn[3], float mx[3], bool add_sums);
+int gs_mesh_morton_sort(gs_mesh* m, const float* c3, uint32_t count, const float mn[3], const float mx[3], const uint32_t** sorted_local,
+                        uint32_t** spare);
+int gs_mesh_assign_slots(gs_mesh* m, const uint32_t* sorted_local, uint32_t from, uint32_t count);
+void gs_sorter_mesh_reordered(gs_sorter* s);                     // the bound mesh changed its storage order only (sorter.hip)
 
 // kernels' host launchers ---------------------------------------------------------------------------
 // (ev_before / ev_after, nullable, recorded on ctx->aux: around the whole vertex stage - block test, mask memset, k_project - when

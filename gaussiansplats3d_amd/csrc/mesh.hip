@@ -470,6 +470,65 @@ __global__ __launch_bounds__(256) void k_centre_reduce(const float* __restrict__
     }
 }
 
+// Bounds of `count` centres float [3n] in device memory, reduced on the device (k_centre_reduce); add_sums: the partial sums
+// join the mesh's centre sums.  Waits for the stream.
+int gs_mesh_centre_bounds(gs_mesh* m, const float* c3, uint32_t count, float mn[3], float mx[3], bool add_sums) {
+    hipStream_t st = m->ctx->stream;
+    const uint32_t blocks = std::min((count + 255u) / 256u, CENTRE_REDUCE_BLOCKS);
+    GS_TRY(m->upload_partials.ensure(sizeof(CentrePartial) * CENTRE_REDUCE_BLOCKS));
+    hipLaunchKernelGGL(k_centre_reduce, dim3(blocks), dim3(256), 0, st, c3, count, m->upload_partials.as<CentrePartial>());
+    GS_HIP(hipGetLastError());
+    std::vector<CentrePartial> part(blocks);
+    GS_HIP(hipMemcpyAsync(part.data(), m->upload_partials.p, sizeof(CentrePartial) * blocks, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    for (const CentrePartial& p : part) {                     // in workgroup order
+        for (int k = 0; k < 3; k++) {
+            if (p.mn[k] < mn[k]) mn[k] = p.mn[k];
+            if (p.mx[k] > mx[k]) mx[k] = p.mx[k];
+            if (add_sums) m->centre_sum[k] += p.s[k];
+        }
+        if (add_sums) { m->centre_sq += p.s[3]; m->centre_n += p.n; }
+    }
+    return GS_OK;
+}
+
+// The Morton order of one run, said once for a fresh segment of an upload and for gs_mesh_reorder (mesh_edit.hip).  c3: the run's
+// centres float [3n] in device memory, in ORIGINAL index order; mn / mx: their bounds by the `v < mn` / `v > mx` tests (NaN never
+// moves one, an infinite value does).  30-bit codes, then 4 stable radix passes with the entry ping-pong buffers as scratch: equal
+// codes stay in original index order.  *sorted_local: the run's local indexes in storage order (entry buffer memory: valid until
+// the next draw or upload); *spare (nullable): `count` words of scratch beside it.  Enqueued on ctx->stream.
+int gs_mesh_morton_sort(gs_mesh* m, const float* c3, uint32_t count, const float mn[3], const float mx[3], const uint32_t** sorted_local,
+                        uint32_t** spare) {
+    hipStream_t st = m->ctx->stream;
+    const dim3 g(up_grid(count)), b(256);
+    float3 lo = make_float3(mn[0], mn[1], mn[2]), inv;
+    inv.x = mx[0] > mn[0] ? 1.0f / (mx[0] - mn[0]) : 0.0f;
+    inv.y = mx[1] > mn[1] ? 1.0f / (mx[1] - mn[1]) : 0.0f;
+    inv.z = mx[2] > mn[2] ? 1.0f / (mx[2] - mn[2]) : 0.0f;
+    if (count > m->entry_capacity) GS_TRY(mesh_alloc_entries(m, count));
+    uint32_t* kbuf[2] = {m->ekeyA.as<uint32_t>(), m->ekeyB.as<uint32_t>()};
+    uint32_t* vbuf[2] = {m->evalA.as<uint32_t>(), m->evalB.as<uint32_t>()};
+    hipLaunchKernelGGL(k_morton_keys, g, b, 0, st, c3, count, lo, inv, kbuf[0], vbuf[0]);
+    GS_HIP(hipMemsetAsync(m->radix.digit_total.p, 0, sizeof(uint32_t) * RADIX_TOTAL_WORDS, st));
+    const RadixExec ex = {st, &m->radix, m->ctx->lds_atomic_lane_order};
+    for (int pass = 0; pass < 4; pass++) {
+        ArrayLoader<uint32_t> al = {kbuf[pass & 1], vbuf[pass & 1], nullptr, count};
+        GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, true>(ex, al, al, count, 8 * pass, pass, kbuf[(pass + 1) & 1],
+                                                                 vbuf[(pass + 1) & 1])));
+    }
+    *sorted_local = vbuf[0];
+    if (spare) *spare = vbuf[1];
+    return GS_OK;
+}
+
+// perm[original] = internal and its inverse for the run [from, from + count) whose storage order gs_mesh_morton_sort gave
+int gs_mesh_assign_slots(gs_mesh* m, const uint32_t* sorted_local, uint32_t from, uint32_t count) {
+    hipLaunchKernelGGL(k_perm_from_sorted, dim3(up_grid(count)), dim3(256), 0, m->ctx->stream, sorted_local, count, from, m->perm.as<uint32_t>(),
+                       m->inv_perm.as<uint32_t>());
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 // The commit half of an upload: what the source's fill left in the staging -> the mesh's planes.  seg.fresh: these splats have
 // no storage slots yet - they get the Morton order of the segment; otherwise they keep the slots an earlier upload gave them (perm
 // stays a bijection, planes uploaded through the other entry points and a bound sorter's resident result stay valid).
@@ -484,28 +543,10 @@ static int mesh_commit_segment(gs_mesh* m, const UploadSegment& seg, const MeshS
     const dim3 g(up_grid(count)), b(256);
     const uint32_t* perm = m->reorder ? m->perm.as<uint32_t>() : nullptr;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if (!host_centers) {
-        const uint32_t blocks = std::min((count + 255u) / 256u, CENTRE_REDUCE_BLOCKS);
-        GS_TRY(m->upload_partials.ensure(sizeof(CentrePartial) * CENTRE_REDUCE_BLOCKS));
-        hipLaunchKernelGGL(k_centre_reduce, dim3(blocks), b, 0, st, (const float*)stg, count, m->upload_partials.as<CentrePartial>());
-        GS_HIP(hipGetLastError());
-        std::vector<CentrePartial> part(blocks);
-        GS_HIP(hipMemcpyAsync(part.data(), m->upload_partials.p, sizeof(CentrePartial) * blocks, hipMemcpyDeviceToHost, st));
-        GS_HIP(hipStreamSynchronize(st));
-        for (const CentrePartial& p : part) {                 // in workgroup order
-            for (int k = 0; k < 3; k++) {
-                if (p.mn[k] < mn[k]) mn[k] = p.mn[k];
-                if (p.mx[k] > mx[k]) mx[k] = p.mx[k];
-                m->centre_sum[k] += p.s[k];
-            }
-            m->centre_sq += p.s[3];
-            m->centre_n += p.n;
-        }
-    }
+    if (!host_centers) GS_TRY(gs_mesh_centre_bounds(m, (const float*)stg, count, mn, mx, true));
     if (fresh) m->layout_version++;
     if (m->reorder && fresh) {
-        // Morton order of this segment: bounds (on the host when the centres are host memory anyway), 30-bit codes, 4 stable
-        // radix passes with the entry ping-pong buffers as scratch, then perm[original] = internal
+        // Morton order of this segment: bounds (on the host when the centres are host memory anyway), then gs_mesh_morton_sort
         if (host_centers)
             for (uint32_t i = 0; i < count; i++)
                 for (int k = 0; k < 3; k++) {
@@ -513,22 +554,9 @@ static int mesh_commit_segment(gs_mesh* m, const UploadSegment& seg, const MeshS
                     if (v < mn[k]) mn[k] = v;
                     if (v > mx[k]) mx[k] = v;
                 }
-        float3 lo = make_float3(mn[0], mn[1], mn[2]), inv;
-        inv.x = mx[0] > mn[0] ? 1.0f / (mx[0] - mn[0]) : 0.0f;
-        inv.y = mx[1] > mn[1] ? 1.0f / (mx[1] - mn[1]) : 0.0f;
-        inv.z = mx[2] > mn[2] ? 1.0f / (mx[2] - mn[2]) : 0.0f;
-        if (count > m->entry_capacity) GS_TRY(mesh_alloc_entries(m, count));
-        uint32_t* kbuf[2] = {m->ekeyA.as<uint32_t>(), m->ekeyB.as<uint32_t>()};
-        uint32_t* vbuf[2] = {m->evalA.as<uint32_t>(), m->evalB.as<uint32_t>()};
-        hipLaunchKernelGGL(k_morton_keys, g, b, 0, st, (const float*)stg, count, lo, inv, kbuf[0], vbuf[0]);
-        GS_HIP(hipMemsetAsync(m->radix.digit_total.p, 0, sizeof(uint32_t) * RADIX_TOTAL_WORDS, st));
-        const RadixExec ex = {st, &m->radix, m->ctx->lds_atomic_lane_order};
-        for (int pass = 0; pass < 4; pass++) {
-            ArrayLoader<uint32_t> al = {kbuf[pass & 1], vbuf[pass & 1], nullptr, count};
-            GS_TRY((radix_pass<ArrayLoader<uint32_t>, uint32_t, true>(ex, al, al, count, 8 * pass, pass, kbuf[(pass + 1) & 1],
-                                                                     vbuf[(pass + 1) & 1])));
-        }
-        hipLaunchKernelGGL(k_perm_from_sorted, g, b, 0, st, vbuf[0], count, from, m->perm.as<uint32_t>(), m->inv_perm.as<uint32_t>());
+        const uint32_t* sorted_local = nullptr;
+        GS_TRY(gs_mesh_morton_sort(m, (const float*)stg, count, mn, mx, &sorted_local, nullptr));
+        GS_TRY(gs_mesh_assign_slots(m, sorted_local, from, count));
     }
     hipLaunchKernelGGL(k_scatter_u32, g, b, 0, st, (const uint32_t*)(stg + s.off_rgba), count, from, perm, m->rgba.as<uint32_t>());
     hipLaunchKernelGGL(k_split_centers, g, b, 0, st, (const float*)stg, count, from, perm, m->px.as<float>(), m->py.as<float>(),

@@ -2,6 +2,8 @@
 // (sorter.hip, gs_sorter_remove) shares.  Replaces the dispose + rebuild of Viewer.removeSplatScenes
 // (the reference's src/Viewer.js:1326-1429) for the device objects: the survivors' storage spans move down, nothing crosses the bus.
 // Which spans move where, and which calls are refused, is upload_plan.hpp's (plan_remove); DESIGN.md 8.13.
+// Second half of the file: gs_mesh_reorder, which folds the Morton runs of a range - one per fresh upload, as a progressive load leaves
+// them - into the one run a single upload would have been (plan_reorder).
 #include <algorithm>
 
 #include "gs_internal.hpp"
@@ -142,6 +144,31 @@ static int mesh_recount_centres(gs_mesh* m) {
     return GS_OK;
 }
 
+// Everything that described the old storage layout goes back to its state at creation: a pending projection, the last draw, the
+// statistics, the draw feedback words and the per-set visibility masks.  No work of the mesh is in flight.
+static void mesh_forget_layout(gs_mesh* m) {
+    m->layout_version++;
+    m->projection_pending = false;
+    m->has_draw = false;
+    m->last_count = 0;
+    m->last = gs_render_stats();
+    m->last_pp = ProjectParams();
+    m->stats_of = StatsOf();
+    m->plan = SchedulePlan();
+    m->list_shift = m->drawn_list_shift = GS_LIST_SHIFT_LARGE;
+    m->measured_visible = m->measured_count = 0;
+    m->draw_serial = m->healed_serial = m->adapted_serial = 0;
+    m->grow_entries_to = 0;
+    m->truncated_draws = 0;
+    for (int k = 0; k < 8; k++) m->full_serial[k] = m->full_count[k] = 0;
+    memset(m->mirror_host, 0, 64);                          // the draw feedback words (no draw is in flight)
+    m->cur_set = 0;
+    for (ProjSet& ps : m->sets) {
+        ps.drawn = false;
+        ps.vis_orig_lazy = false; ps.vis_orig_dirty = true; ps.vis_orig_tail_zero = false; ps.vis_orig_count = 0;
+    }
+}
+
 extern "C" int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count) {
     GS_REQUIRE(m != nullptr, "mesh == NULL");
     if (n_ranges == 0) return GS_OK;
@@ -189,32 +216,141 @@ extern "C" int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ran
     GS_TRY(gs_mesh_block_boxes(m, plan.first_block, (old_end + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK));
     GS_HIP(hipStreamSynchronize(st));
 
-    // the numbering changed: everything that described the old one goes back to its state at creation
+    // the numbering changed
     m->slotted = plan.slotted;
     m->runs = plan.runs;
     m->uploaded = new_end;
-    m->layout_version++;
-    m->projection_pending = false;
-    m->has_draw = false;
-    m->last_count = 0;
-    m->last = gs_render_stats();
-    m->last_pp = ProjectParams();
-    m->stats_of = StatsOf();
-    m->plan = SchedulePlan();
-    m->list_shift = m->drawn_list_shift = GS_LIST_SHIFT_LARGE;
-    m->measured_visible = m->measured_count = 0;
-    m->draw_serial = m->healed_serial = m->adapted_serial = 0;
-    m->grow_entries_to = 0;
-    m->truncated_draws = 0;
-    for (int k = 0; k < 8; k++) m->full_serial[k] = m->full_count[k] = 0;
-    memset(m->mirror_host, 0, 64);                          // the draw feedback words (no draw is in flight)
-    m->cur_set = 0;
-    for (ProjSet& ps : m->sets) {
-        ps.drawn = false;
-        ps.vis_orig_lazy = false; ps.vis_orig_dirty = true; ps.vis_orig_tail_zero = false; ps.vis_orig_count = 0;
-    }
+    mesh_forget_layout(m);
     GS_TRY(mesh_recount_centres(m));                       // a heuristic's inputs: the sums of the survivors
     for (gs_sorter* s : ctx->live_sorters)
         if (s->bound_mesh == m || s->result_mesh == m) gs_sorter_mesh_edited(s);
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Folding the Morton runs of a range into one (gs_mesh_reorder).  The range keeps its storage slots; inside them
+// the splats take the order one upload of the range would have given them.  The order itself is mesh.hip's (gs_mesh_morton_sort),
+// fed with the centres as an upload stages them: in original index order, out of the planes.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_reorder_centres(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
+                                                         const uint32_t* __restrict__ perm, uint32_t from, uint32_t count,
+                                                         float* __restrict__ c3) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const uint32_t s = perm[from + i];                  // (inside [from, from + count): the range is the union of its runs)
+        c3[3 * (size_t)i] = px[s];
+        c3[3 * (size_t)i + 1] = py[s];
+        c3[3 * (size_t)i + 2] = pz[s];
+    }
+}
+
+// source[p] = where, counted from `from`, the splat of the NEW storage position from + p lies now (read before perm is rewritten)
+__global__ __launch_bounds__(256) void k_reorder_source(const uint32_t* __restrict__ sorted_local, const uint32_t* __restrict__ perm, uint32_t from,
+                                                        uint32_t count, uint32_t* __restrict__ source) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < count; p += gridDim.x * blockDim.x) {
+        const uint32_t s = perm[from + sorted_local[p]] - from;
+        source[p] = s < count ? s : count - 1u;             // (inside the range by the run rule; were it ever not, the move reads no wild address)
+    }
+}
+
+// The move of one plane group: up to 16 bytes per splat, planes of one element size, so that a position's source index is read
+// once for all of them.  The reads are scattered by nature (the old order is the trainer's); the writes are in order.
+constexpr uint32_t REORDER_GROUP_BYTES = 16;
+template <class T>
+struct ReorderGroup {
+    T* plane[REORDER_GROUP_BYTES / sizeof(T)];              // the planes' first elements
+    uint32_t n;
+};
+template <class T>
+__global__ __launch_bounds__(256) void k_reorder_move(ReorderGroup<T> g, const T* __restrict__ scratch, uint32_t stride,
+                                                      const uint32_t* __restrict__ source, uint32_t from, uint32_t count) {
+    constexpr uint32_t MAXP = REORDER_GROUP_BYTES / sizeof(T);
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < count; p += gridDim.x * blockDim.x) {
+        const uint32_t s = source[p];
+        T v[MAXP];
+#pragma unroll
+        for (uint32_t k = 0; k < MAXP; k++)
+            if (k < g.n) v[k] = scratch[(size_t)k * stride + s];
+#pragma unroll
+        for (uint32_t k = 0; k < MAXP; k++)
+            if (k < g.n) g.plane[k][from + p] = v[k];
+    }
+}
+
+// copies the range of every plane of the group into the scratch (one behind the other, `stride` elements apart), then gathers back
+template <class T>
+static int reorder_group(hipStream_t st, const ReorderGroup<T>& g, void* scratch, uint32_t stride, const uint32_t* source, uint32_t from,
+                         uint32_t count) {
+    for (uint32_t k = 0; k < g.n; k++)
+        GS_HIP(hipMemcpyAsync(static_cast<T*>(scratch) + (size_t)k * stride, g.plane[k] + from, (size_t)count * sizeof(T), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_reorder_move<T>, dim3(edit_grid(count)), dim3(256), 0, st, g, (const T*)scratch, stride, source, from, count);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// every plane of `bytes`-sized elements among planes[0 .. n), a group at a time
+template <class T>
+static int reorder_planes_of(hipStream_t st, void* const* planes, const uint32_t* bytes, uint32_t n, void* scratch, uint32_t stride,
+                             const uint32_t* source, uint32_t from, uint32_t count) {
+    ReorderGroup<T> g = {};
+    for (uint32_t k = 0; k < n; k++) {
+        if (!planes[k] || bytes[k] != sizeof(T)) continue;
+        g.plane[g.n++] = static_cast<T*>(planes[k]);
+        if (g.n == REORDER_GROUP_BYTES / sizeof(T)) {
+            GS_TRY(reorder_group(st, g, scratch, stride, source, from, count));
+            g.n = 0;
+        }
+    }
+    if (g.n) GS_TRY(reorder_group(st, g, scratch, stride, source, from, count));
+    return GS_OK;
+}
+
+extern "C" int gs_mesh_reorder(gs_mesh* m, uint32_t from, uint32_t count) {
+    GS_REQUIRE(m != nullptr, "mesh == NULL");
+    const ReorderPlan plan = plan_reorder(m->runs, m->slotted, m->uploaded, m->reorder, from, count);
+    if (plan.refused) {
+        gs_set_error("invalid argument: gs_mesh_reorder: %s", plan.refused);
+        return GS_ERR_INVALID;
+    }
+    if (plan.noop) return GS_OK;
+    gs_context* ctx = m->ctx;
+    ScopedDevice sd(ctx->device);
+    hipStream_t st = ctx->stream;
+    // draws in flight read the planes and the permutation on either stream, a bound sorter's sort reads the permutation on its own
+    GS_HIP(hipStreamSynchronize(st));
+    if (ctx->aux != st) GS_HIP(hipStreamSynchronize(ctx->aux));
+    for (gs_sorter* s : ctx->live_sorters)
+        if ((s->bound_mesh == m || s->result_mesh == m) && s->stream != st) GS_HIP(hipStreamSynchronize(s->stream));
+
+    // the scratch: first the centres float [3n], then one plane group (stride: whole 16-byte units per plane)
+    const uint32_t stride16 = (count + 3u) & ~3u;
+    GS_TRY(m->staging.ensure((size_t)stride16 * REORDER_GROUP_BYTES));
+    float* c3 = m->staging.as<float>();
+    hipLaunchKernelGGL(k_reorder_centres, dim3(edit_grid(count)), dim3(256), 0, st, m->px.as<float>(), m->py.as<float>(), m->pz.as<float>(),
+                       m->perm.as<uint32_t>(), from, count, c3);
+    GS_HIP(hipGetLastError());
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    GS_TRY(gs_mesh_centre_bounds(m, c3, count, mn, mx, false));   // the centre sums stay: the fold moves splats, it changes none
+    const uint32_t* sorted_local = nullptr;
+    uint32_t* source = nullptr;
+    GS_TRY(gs_mesh_morton_sort(m, c3, count, mn, mx, &sorted_local, &source));
+    hipLaunchKernelGGL(k_reorder_source, dim3(edit_grid(count)), dim3(256), 0, st, sorted_local, m->perm.as<uint32_t>(), from, count, source);
+    GS_HIP(hipGetLastError());
+    GS_TRY(gs_mesh_assign_slots(m, sorted_local, from, count));
+
+    // every per-splat plane kept in storage order (gs_mesh_remove's list; perm and inv_perm are rewritten above)
+    const bool half = (m->flags & GS_MESH_COV_HALF) != 0, sh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
+    void* const planes[] = {m->px.p, m->py.p, m->pz.p, m->cov_bound.p, m->rgba.p, m->scene_idx.p, m->covA.p, m->covB.p, m->sh0.p, m->sh1.p, m->sh2.p};
+    const uint32_t bytes[] = {4, 4, 4, 4, 4, 4, half ? 8u : 16u, half ? 4u : 8u, 16, sh_u8 ? 8u : (m->sh_degree == 2 ? 16u : 4u), 16};
+    constexpr uint32_t N = sizeof(bytes) / sizeof(bytes[0]);
+    GS_TRY(reorder_planes_of<uint32_t>(st, planes, bytes, N, m->staging.p, stride16, source, from, count));
+    GS_TRY(reorder_planes_of<uint2>(st, planes, bytes, N, m->staging.p, stride16, source, from, count));
+    GS_TRY(reorder_planes_of<uint4>(st, planes, bytes, N, m->staging.p, stride16, source, from, count));
+    GS_TRY(gs_mesh_block_boxes(m, plan.first_block, plan.end_block));
+    GS_HIP(hipStreamSynchronize(st));
+
+    m->runs = plan.runs;
+    mesh_forget_layout(m);
+    for (gs_sorter* s : ctx->live_sorters)
+        if (s->bound_mesh == m || s->result_mesh == m) gs_sorter_mesh_reordered(s);
     return GS_OK;
 }

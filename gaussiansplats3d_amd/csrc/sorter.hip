@@ -1543,6 +1543,18 @@ void gs_sorter_mesh_edited(gs_sorter* s) {
     sorter_tell_mesh(s);
 }
 
+// The bound mesh changed its storage order and kept the caller's numbering (gs_mesh_reorder): what goes is what the sorter keeps in
+// storage order - the resident result (its payloads are storage positions), the leaf-ordered payload cache and the mask of the
+// last visibility-culled sort.  Gathered lists, trees, stale keys and device distances are in the caller's numbering and stay.
+void gs_sorter_mesh_reordered(gs_sorter* s) {
+    s->has_result = false;
+    s->result_mesh = nullptr; s->result_unmap = nullptr; s->result_frame = nullptr; s->result_payload_max = 0;
+    s->last_render = s->last_sort = s->last_passes = 0;
+    s->leaf_cache_tree = 0; s->leaf_cache_mesh = nullptr;
+    s->mask_copy.release();
+    sorter_tell_mesh(s);
+}
+
 extern "C" {
 
 int gs_sorter_remove(gs_sorter* s, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count) {

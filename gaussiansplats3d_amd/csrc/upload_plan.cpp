@@ -119,21 +119,74 @@ RemovePlan plan_remove(const std::vector<SlotRange>& runs, const SlottedRanges& 
     return p;
 }
 
+ReorderPlan plan_reorder(const std::vector<SlotRange>& runs, const SlottedRanges& slotted, uint32_t uploaded, bool reorder, uint32_t from,
+                         uint32_t count) {
+    ReorderPlan p;
+    if (count == 0) { p.noop = true; return p; }
+    const uint64_t end = (uint64_t)from + count;
+    if (end > uploaded) { p.refused = "the range exceeds the uploaded splat count"; return p; }
+    if (!reorder) { p.noop = true; return p; }            // upload order is kept: there are no runs
+    if (!slotted.holding(from, count)) { p.refused = "a position of the range was never uploaded"; return p; }
+    uint32_t inside = 0;
+    for (const SlotRange& r : runs) {
+        if ((r.begin < from && from < r.end) || (r.begin < end && end < r.end)) {
+            p.refused = "a range border falls inside a Morton run (the span of one fresh upload segment)";
+            return p;
+        }
+        if (r.begin >= from && r.end <= end) inside++;
+    }
+    if (inside <= 1) { p.noop = true; return p; }
+    bool placed = false;
+    for (const SlotRange& r : runs) {
+        if (r.begin >= from && r.end <= end) {
+            if (!placed) p.runs.push_back({from, (uint32_t)end});
+            placed = true;
+        } else {
+            p.runs.push_back(r);
+        }
+    }
+    p.first_block = from / UPLOAD_BLOCK;
+    p.end_block = (uint32_t)((end + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK);
+    return p;
+}
+
+// the state of a mesh out of a debug struct's rows; false when no mesh can be in it
+static bool debug_state(const uint32_t (*run_rows)[2], uint32_t n_runs, const uint32_t (*slot_rows)[2], uint32_t n_slotted, uint32_t uploaded,
+                        std::vector<SlotRange>* runs, SlottedRanges* sl) {
+    uint32_t prev = 0;
+    for (uint32_t k = 0; k < n_runs; k++) {
+        if (run_rows[k][0] >= run_rows[k][1] || run_rows[k][0] < prev || run_rows[k][1] > uploaded) return false;
+        runs->push_back({run_rows[k][0], run_rows[k][1]});
+        prev = run_rows[k][1];
+    }
+    for (uint32_t k = 0; k < n_slotted; k++) {
+        if (slot_rows[k][0] >= slot_rows[k][1] || slot_rows[k][1] > uploaded) return false;
+        sl->add(slot_rows[k][0], slot_rows[k][1]);
+    }
+    return true;
+}
+
+extern "C" int gs_debug_reorder_plan(const gs_reorder_plan_debug_in* in, gs_reorder_plan_debug_out* out) {
+    if (!in || !out || in->n_runs > UPLOAD_DEBUG_MAX || in->n_slotted > UPLOAD_DEBUG_MAX || in->uploaded > UPLOAD_MAX_SPLATS) return -1;
+    std::vector<SlotRange> runs;
+    SlottedRanges sl;
+    if (!debug_state(in->runs, in->n_runs, in->slotted, in->n_slotted, in->uploaded, &runs, &sl)) return -1;
+    *out = gs_reorder_plan_debug_out();
+    const ReorderPlan p = plan_reorder(runs, sl, in->uploaded, in->reorder != 0u, in->from, in->count);
+    if (p.refused) { out->refused = 1; return 0; }
+    if (p.noop) { out->noop = 1; return 0; }
+    out->n_runs = (uint32_t)p.runs.size();                 // (never more than came in)
+    for (uint32_t k = 0; k < out->n_runs; k++) { out->runs[k][0] = p.runs[k].begin; out->runs[k][1] = p.runs[k].end; }
+    out->first_block = p.first_block; out->end_block = p.end_block;
+    return 0;
+}
+
 extern "C" int gs_debug_remove_plan(const gs_remove_plan_debug_in* in, gs_remove_plan_debug_out* out) {
     if (!in || !out || in->n_runs > UPLOAD_DEBUG_MAX || in->n_slotted > UPLOAD_DEBUG_MAX || in->n_ranges > UPLOAD_DEBUG_MAX) return -1;
     if (in->max_count > UPLOAD_MAX_SPLATS || in->uploaded > in->max_count) return -1;
     std::vector<SlotRange> runs;
     SlottedRanges sl;
-    uint32_t prev = 0;
-    for (uint32_t k = 0; k < in->n_runs; k++) {
-        if (in->runs[k][0] >= in->runs[k][1] || in->runs[k][0] < prev || in->runs[k][1] > in->uploaded) return -1;
-        runs.push_back({in->runs[k][0], in->runs[k][1]});
-        prev = in->runs[k][1];
-    }
-    for (uint32_t k = 0; k < in->n_slotted; k++) {
-        if (in->slotted[k][0] >= in->slotted[k][1] || in->slotted[k][1] > in->uploaded) return -1;
-        sl.add(in->slotted[k][0], in->slotted[k][1]);
-    }
+    if (!debug_state(in->runs, in->n_runs, in->slotted, in->n_slotted, in->uploaded, &runs, &sl)) return -1;
     *out = gs_remove_plan_debug_out();
     const RemovePlan p = plan_remove(runs, sl, in->uploaded, in->max_count, in->reorder != 0u, &in->ranges[0][0], in->n_ranges);
     if (p.refused) { out->refused = 1; return 0; }

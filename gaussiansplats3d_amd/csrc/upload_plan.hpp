@@ -1,7 +1,8 @@
 // upload_plan.hpp — the host policy of an upload into a mesh (mesh.hip, bounds.hip): which splats own storage slots, where one
 // upload is cut into fresh and non-fresh segments, which storage blocks get new boxes, and where a segment's arrays sit in the
 // staging buffer.  Host only: no HIP, no gs_mesh, no context.  tests/test_upload_plan.py holds it to a bitmap model through
-// gs_debug_upload_plan; tests/tools/upload_plan_fuzz.cpp is the stand-alone program for a sanitizer run.
+// gs_debug_upload_plan; tests/tools/upload_plan_fuzz.cpp is the stand-alone program for a sanitizer run.  Also here: the plans of
+// gs_mesh_remove / gs_sorter_remove (plan_remove) and of gs_mesh_reorder (plan_reorder), each with its debug entry, test and program.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -80,6 +81,20 @@ RemovePlan plan_remove(const std::vector<SlotRange>& runs, const SlottedRanges& 
                        bool reorder, const uint32_t* ranges, uint32_t n);
 
 // ---------------------------------------------------------------------------------------------------
+// Folding the Morton runs of [from, from + count) into one (mesh_edit.hip: gs_mesh_reorder).  The runs in the range keep its
+// storage slots between them, so the range must be their union: all of it uploaded, neither border inside a run.  The checks, in
+// this order: count == 0 does nothing; a range beyond `uploaded` is refused (on any mesh); a mesh that keeps upload order does
+// nothing; a never-uploaded position and a border inside a run are refused; a range of at most one run does nothing.
+struct ReorderPlan {
+    const char* refused = nullptr;                         // why not (then nothing else is filled in), or nullptr
+    bool noop = false;                                     // nothing to do (then nothing else is filled in)
+    std::vector<SlotRange> runs;                           // the runs afterwards: those of the range are the one run [from, from + count)
+    uint32_t first_block = 0, end_block = 0;               // the storage blocks [first_block, end_block) get new boxes
+};
+ReorderPlan plan_reorder(const std::vector<SlotRange>& runs, const SlottedRanges& slotted, uint32_t uploaded, bool reorder, uint32_t from,
+                         uint32_t count);
+
+// ---------------------------------------------------------------------------------------------------
 // Debug entry for the tests (pure host; typed by tests/upload_plan_cases.py, not in the public header).  Flags are uint32 (0 / 1).
 constexpr uint32_t UPLOAD_DEBUG_MAX = 64;                  // ranges in, ranges out, segments
 struct gs_upload_plan_debug_in {
@@ -126,3 +141,23 @@ struct gs_remove_plan_debug_out {
 // 0; -1 on a NULL argument, more than UPLOAD_DEBUG_MAX rows, or a state no mesh can be in (runs or slotted ranges that are empty,
 // unsorted, overlapping or beyond `uploaded`; uploaded > max_count; max_count > UPLOAD_MAX_SPLATS)
 extern "C" int gs_debug_remove_plan(const gs_remove_plan_debug_in* in, gs_remove_plan_debug_out* out);
+
+// ... and for plan_reorder (typed by tests/reorder_plan_cases.py)
+struct gs_reorder_plan_debug_in {
+    uint32_t n_runs;                                       // the state before: the runs as the mesh remembers them
+    uint32_t runs[UPLOAD_DEBUG_MAX][2];
+    uint32_t n_slotted;                                    // ... and its slotted ranges, add()ed in this order
+    uint32_t slotted[UPLOAD_DEBUG_MAX][2];
+    uint32_t uploaded, reorder;
+    uint32_t from, count;                                  // the call
+};
+struct gs_reorder_plan_debug_out {
+    uint32_t refused;                                      // 1: the plan refused the call (nothing else is filled in)
+    uint32_t noop;                                         // 1: nothing to do (nothing else is filled in)
+    uint32_t n_runs;
+    uint32_t runs[UPLOAD_DEBUG_MAX][2];
+    uint32_t first_block, end_block;
+};
+// 0; -1 on a NULL argument, more than UPLOAD_DEBUG_MAX rows, or a state no mesh can be in (as gs_debug_remove_plan; uploaded >
+// UPLOAD_MAX_SPLATS)
+extern "C" int gs_debug_reorder_plan(const gs_reorder_plan_debug_in* in, gs_reorder_plan_debug_out* out);

@@ -120,6 +120,16 @@ class SplatMesh:
         self._indexes = None
         return self
 
+    def reorder(self, frm=0, count=None):
+        """gs_mesh_reorder: the Morton runs (one per fresh upload) inside [frm, frm + count) become one run on the device, as if
+        the range had arrived by one upload - what a progressive load wants at its final build.  count=None: every uploaded
+        splat from frm on.  The numbering stays; the last draw, a pending project() and bound sorters' results are forgotten
+        unless the call had nothing to do (count 0, a keep_order mesh, at most one run in the range)."""
+        if count is None:
+            count = max(self.splat_count - int(frm), 0)
+        L.check(self.lib.gs_mesh_reorder(self.handle, int(frm), int(count)))
+        return self
+
     def set_scenes(self, transforms=None, camera_position=None, opacity=None, visible=None, sh8_range=None):
         """Per-scene uniforms: uniforms.transforms (dynamicMode), sceneOpacity / sceneVisibility
         (enableOptionalEffects), sphericalHarmonics8BitCompressionRangeMin/Max.  transforms: column-major 16-vectors;

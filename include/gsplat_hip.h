@@ -451,6 +451,22 @@ int gs_mesh_upload_scene_indexes(gs_mesh* m, uint32_t from, uint32_t count, cons
  * stay.  Trees are not edited: build a new one.  GS_ERR_INVALID, and nothing changes, on anything refused. */
 int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap, uint32_t scene_remap_count);
 
+/* Fold the Morton runs that lie in [from, from + count) into ONE run, on the device: what a progressive load (one upload per
+ * section, each a run of its own whose storage blocks span the scene) does at its final build.  Afterwards the mesh behaves, in
+ * every output, as a fresh mesh of the same capacity and flags in which [from, from + count) arrived by one upload and every
+ * other range by the uploads it did arrive by.  The caller's numbering does not change, no data crosses the bus, the capacity and
+ * every allocation stay; splats outside the range keep their storage positions, the range keeps the storage slots
+ * [from, from + count) and orders them as one upload would (bounds of its centres, 30-bit Morton codes, ties by index).
+ * The call waits for the mesh's work in flight and forgets what described the old storage order: a pending gs_mesh_project, the
+ * last draw (gs_mesh_surface, gs_mesh_debug_rop8 and the draw's debug reads answer as before a first draw), the statistics, and
+ * the resident result of every sorter bound to it.  Destination, draw mode, deep-pass switch, scene parameters and trees stay
+ * (they live in the caller's numbering).  The centre sums behind the motion heuristics stay as they are.
+ * GS_OK and nothing happens - not even the last draw is forgotten - when count == 0, on a GS_MESH_KEEP_ORDER mesh, and when the
+ * range holds at most one run.  GS_ERR_INVALID, and nothing changes, when from + count exceeds the uploaded count (on any mesh),
+ * when a position of the range was never uploaded, or when a border of the range falls inside a Morton run (gs_mesh_remove's
+ * rule). */
+int gs_mesh_reorder(gs_mesh* m, uint32_t from, uint32_t count);
+
 /* Per-scene uniforms (SplatMesh.updateUniforms :1263-1276, setupDataTextures :868-878). */
 typedef struct gs_scene_params {
     uint32_t scene_count;                       /* sceneCount                                                  */

@@ -72,6 +72,7 @@ export class SplatMesh {
       matrixWorld: new THREE.Matrix4(),                     // Object3D.matrixWorld (src/Viewer.js:1891 multiplies by it)
       core: null,                                           // the device-side mesh (gs_mesh_*)
       frame: null, shCompressionLevel: 1,
+      foldRunsAtFinalBuild: false,                          // HIP-engine extra: build(..., finalBuild = true) ends a progressive load with reorderScenes()
       _region: new VisibleRegion(this.sceneFadeInRateMultiplier), _sceneCenter: new THREE.Vector3() });
     // The scene reveal's state under the reference's names (:144-149; src/Viewer.js:1585 reads visibleRegionChanging): kept by
     // node/VisibleRegion.mjs, advanced by updateVisibleRegion (every build) and updateVisibleRegionFadeDistance (every frame).
@@ -139,6 +140,7 @@ export class SplatMesh {
     const update = this.refreshGPUDataFromSplatBuffers(appendOnly);
     Object.assign(this, { lastBuildScenes: this.scenes.slice(), lastBuildSplatCount: uploadedUpTo,
                           lastBuildMaxSplatCount: this.getMaxSplatCount(), lastBuildSceneCount: this.scenes.length });
+    if (finalBuild && this.foldRunsAtFinalBuild) this.reorderScenes();
     if (finalBuild && this.scenes.length) {
       const minAlphas = sceneOptions.map((o) => o.splatAlphaRemovalThreshold || 1);
       this.buildSplatTree(minAlphas, onSplatTreeIndexesUpload, onSplatTreeConstruction).then(() => {
@@ -149,6 +151,26 @@ export class SplatMesh {
     }
     this.visible = this.scenes.length > 0;
     return update;
+  }
+
+  // HIP-engine extra: a progressive load uploads every section [lastBuildSplatCount, now) as it arrives, and each upload is a
+  // Morton run of its own whose 256-splat storage blocks span the scene (a trainer writes its rows in no spatial order), so the
+  // vertex stage's block cull rejects nothing.  This folds every scene's getMaxSplatCount() span that holds more than one run into
+  // one run on the device (gs_mesh_reorder): the layout one upload of the finished buffer would have left, no byte across the bus,
+  // the numbering - and with it the sort worker's centres and the splat tree - untouched.  A scene whose buffer is still loading
+  // is skipped (its span is not all uploaded).  Returns the [from, count] spans handed to the device.
+  reorderScenes() {
+    const spans = [];
+    if (!this.core) return spans;
+    let at = 0;
+    for (const sc of this.scenes) {
+      const n = sc.splatBuffer.getMaxSplatCount();
+      if (n > 0 && sc.splatBuffer.getSplatCount() === n && at + n <= this.core.getSplatCount()) {
+        try { this.core.reorder(at, n); spans.push([at, n]); } catch (e) { if (!/Morton run/.test(String(e && e.message))) throw e; }
+      }
+      at += n;
+    }
+    return spans;
   }
 
   // HIP-engine extra, for the body of Viewer.removeSplatScenes (src/Viewer.js:1326-1429) in place of dispose + rebuild: the scenes

@@ -273,6 +273,9 @@ class SplatMeshHIP {
     this.splatCount -= gone;
     this.renderCount = Math.min(this.renderCount, this.splatCount);
   }
+  // the Morton runs (one per fresh upload) inside [from, from + count) become one run on the device: the layout one upload of the
+  // range would have left.  The numbering stays; nothing happens where the range holds at most one run.
+  reorder(from = 0, count = this.splatCount - from) { addon.meshReorder(this.handle, from >>> 0, Math.max(0, count) >>> 0); }
   setSceneIndexes(sceneIndexes, start = 0) { addon.meshUploadSceneIndexes(this.handle, start, sceneIndexes.length, sceneIndexes); }
   setScenes(params) { addon.meshSetScenes(this.handle, params); this.hasScenes = true; }
   // the fade-in of SplatMesh.updateVisibleRegionFadeDistance: visibleRegionFadeStartRadius + sceneCenter; null switches it off

@@ -333,6 +333,30 @@ static napi_value remove_call(napi_env env, napi_callback_info info, int sorter)
 static napi_value MeshRemove(napi_env env, napi_callback_info info) { return remove_call(env, info, 0); }
 static napi_value SorterRemove(napi_env env, napi_callback_info info) { return remove_call(env, info, 1); }
 
+/* meshReorder(mesh, from, count): the Morton runs inside [from, from + count) become one run on the device (gs_mesh_reorder) */
+static napi_value MeshReorder(napi_env env, napi_callback_info info) {
+    ARGS(3)
+    int st;
+
+    LOCKED(st = gs_mesh_reorder((gs_mesh*)get_external(env, argv[0]), get_u32(env, argv[1]), get_u32(env, argv[2])));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+
+/* meshStoragePositions(mesh, out Uint32Array): test hook - the storage position of splats [0, out.length) by original index
+ * (gs_mesh_debug_read 12: the layout uploads and meshReorder leave) */
+static napi_value MeshStoragePositions(napi_env env, napi_callback_info info) {
+    ARGS(2)
+    void* out = NULL;
+    size_t ob = 0;
+    if (!get_bytes(env, argv[1], &out, &ob) || !out || (ob % 4) != 0) { napi_throw_type_error(env, NULL, "meshStoragePositions: out must be a Uint32Array"); return NULL; }
+    int st;
+
+    LOCKED(st = gs_mesh_debug_read((gs_mesh*)get_external(env, argv[0]), 12, out, (uint32_t)(ob / 4)));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+
 /* meshComputeDistances(mesh, flags, uniforms Int32Array|Float32Array, sceneCount, out Int32Array|Float32Array|null, count,
  *                      sorter|null): SplatMesh.computeDistancesOnGPU's pass (gs_mesh_compute_distances).  `count` = the mesh's
  * uploaded splat count (what the pass writes into `out`).  Synchronous under the addon's lock, like every other call here: it
@@ -1079,7 +1103,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"treeSceneLeaves", TreeSceneLeaves}, {"treeGatherScenes", TreeGatherScenes},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
-        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove},
+        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove}, {"meshReorder", MeshReorder}, {"meshStoragePositions", MeshStoragePositions},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
