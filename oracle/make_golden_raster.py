@@ -12,7 +12,8 @@ Runs only where /root/reference exists (with Node and g++).
    the fragment shader; outputs are stored.  tests/test_raster_ref.py compares the C raster oracle (CPU tier) and the HIP
    vertex stage (GPU tier) with them.
 usage: python -m oracle.make_golden_raster            (tests/raster_cases.py       -> tests/golden/raster_ref.npz)
-       python -m oracle.make_golden_raster --combos   (tests/raster_combo_cases.py -> tests/golden/raster_combo_ref.npz)"""
+       python -m oracle.make_golden_raster --combos   (tests/raster_combo_cases.py -> tests/golden/raster_combo_ref.npz)
+       python -m oracle.make_golden_raster --edges    (tests/raster_edge_cases.py  -> tests/golden/raster_edge_ref.npz)"""
 import ctypes as C
 import hashlib
 import json
@@ -219,5 +220,46 @@ def combos():
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "raster_combo_ref.npz"), **out)
 
 
+def edge_census(case, res):
+    """What keeps a designed case (tests/raster_edge_cases.py) from passing vacuously, counted on the reference shader's outputs alone:
+    per group how many splats the shader draws, rejects with gl_Position = (0, 0, 2, 1) and leaves by an early `return` or a NaN; per
+    ladder what it observes along it ('1': drawn, or what raster_edge_cases.observed says for the group); over the drawn splats the least reach of an ellipse's box into the frame and the least
+    half-extent, in px.  tests/test_raster_edge_ref.py asserts the bounds."""
+    import raster_edge_cases as rec
+    drawn, reject, early = shader_verdicts(res)
+    reach, extent = rec.footprints(case, res)
+    groups = {}
+    for name, g in case["groups"].items():
+        i = g["idx"]
+        groups[name] = dict(kind=g["kind"], count=len(i), drawn=int(drawn[i].sum()), rejected=int(reject[i].sum()), early=int(early[i].sum()),
+                            ladders=["".join("1" if v else "0" for v in rec.observed(case, res, name, l)) for l in g["ladders"]])
+    return dict(groups=groups, drawn=int(drawn.sum()), least_reach_px=round(float(reach[drawn].min()), 3),
+                least_half_extent_px=round(float(extent[drawn].min()), 3))
+
+
+def edges():
+    """The designed edge cases (tests/raster_edge_cases.py) -> tests/golden/raster_edge_ref.npz.  Only corner 0's ten outputs and the
+    other three corners' gl_Position.xy are stored per splat (the rest repeats corner 0: z, w and the colour are per splat, vPosition
+    is the corner itself): float32 [n, 16], unpacked by raster_edge_cases.unpack."""
+    import raster_edge_cases as rec
+    builds = {name: b for name, b in rec.shader_builds().items() if name in {rec.make_case(c)["build"] for c in rec.CASES}}
+    libs, meta = build_shaders(builds)
+    out, census = {}, {}
+    for cname in rec.CASES:
+        case = rec.make_case(cname)
+        res = run_vertex(libs[case["build"]], case)
+        assert np.array_equal(rec.unpack(rec.pack(res)), res, equal_nan=True), cname
+        out["vs_" + cname] = rec.pack(res)
+        census[cname] = edge_census(case, res)
+        c = census[cname]
+        print(f"{cname:18s} build={case['build']:9s} splats={res.shape[0]} drawn={c['drawn']} reach={c['least_reach_px']} "
+              f"extent={c['least_half_extent_px']}")
+        for name, g in c["groups"].items():
+            print(f"    {name:16s} {g['kind']:7s} {g['count']:4d} drawn {g['drawn']:4d} rejected {g['rejected']:4d} early {g['early']:4d} "
+                  f"{' '.join(g['ladders'][:3])}")
+    out["meta"] = np.frombuffer(json.dumps(dict(builds=meta, census=census)).encode(), np.uint8)
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "raster_edge_ref.npz"), **out)
+
+
 if __name__ == "__main__":
-    combos() if "--combos" in sys.argv[1:] else main()
+    edges() if "--edges" in sys.argv[1:] else combos() if "--combos" in sys.argv[1:] else main()
