@@ -11,6 +11,7 @@
 #include "../../include/gsplat_hip.h"
 #include "bin_word.hpp"
 #include "draw_plan.hpp"
+#include "gather_plan.hpp"
 #include "sort_plan.hpp"
 #include "upload_plan.hpp"
 
@@ -252,7 +253,6 @@ struct TreeGatherView {
 };
 void gs_tree_view(gs_tree* t, TreeGatherView* v);
 int gs_tree_copy_plain(gs_tree* t, uint32_t* out_dev, hipStream_t st);   // the kept leaves' index lists -> indexesToSort
-void gs_tree_forget_sorter(gs_tree* t, gs_sorter* s);                    // the sorter consumed (or dropped) the pending gather
 
 // An opened asset's bytes as the device decode reads them (asset_decode.hip): the rows of the range being uploaded, the bucket
 // tables of its sections and the section table.  Owned by whatever receives the splats; rewritten by every call.
@@ -290,14 +290,10 @@ struct gs_sorter {
     gs_mesh* result_mesh = nullptr;    // ... as it was when the last sort ran (nullptr = plain splat indexes)
     const uint32_t* result_unmap = nullptr;
     uint32_t result_payload_max = 0;   // largest payload the last sort could emit (clamp of the host-visible un-mapping)
-    uint32_t gathered = 0;             // splatRenderCount of the list gs_tree_gather left in idx_in (an upper bound when
-                                       // gathered_on_device: the asynchronous gather leaves the real count in gathered_dev)
-    bool has_gathered = false;
-    bool gathered_on_device = false;
+    GatherHandover handover;           // what gs_tree_gather left this sorter: nothing, a plan still in the tree (deferred so that a
+                                       // full sort of a static scene can fuse the copy with its key kernel) or a list in idx_in;
+                                       // written by the handover_* transitions alone (gather_plan.hpp)
     DevBuf gathered_dev;               // uint32: splatRenderCount of that list, written by the gather's plan
-    gs_tree* pending_tree = nullptr;   // gs_tree_gather planned a gather whose lists this sorter has still to copy (deferred so
-                                       // that a full sort of a static scene can fuse the copy with its key kernel)
-    bool pending_keep_zeroed = false;  // ... and zeroed this sorter's keep mask for a fused per-splat cull
     uint32_t centers_version = 0;      // bumped by gs_sorter_upload_centers (invalidates the leaf-major caches below)
     DevBuf pay_in;                     // uint32 [max]: the gathered list's payloads (positions in the bound mesh, or the indexes)
     DevBuf leaf_centers, leaf_pos;     // the centres / payloads of the tree's splats in ITS leaf-major order: the fused copy

@@ -1317,6 +1317,7 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     gs_sorter* s = new (std::nothrow) gs_sorter();
     if (!s) return GS_ERR_NOMEM;
     s->ctx = ctx;
+    s->handover.owner = s;
     s->max_count = max_splat_count;
     s->flags = flags;
     s->precision = precision_bits;
@@ -1370,7 +1371,7 @@ void gs_sorter_destroy(gs_sorter* s) {
     if (!s) return;
     std::vector<gs_sorter*>& live = s->ctx->live_sorters;
     live.erase(std::remove(live.begin(), live.end(), s), live.end());
-    if (s->pending_tree) gs_tree_forget_sorter(s->pending_tree, s);
+    handover_dropped(s->handover);
     ScopedDevice sd(s->ctx->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     (void)hipStreamSynchronize(s->ctx->stream);        // a draw may still be reading `sorted`
@@ -1524,14 +1525,11 @@ int gs_sorter_commit_centers(gs_sorter* s, uint32_t from, uint32_t count, const 
 // Every state of a sorter that names splats by their numbering: the resident result, a gathered (or planned) list, the per-tree
 // payload caches, the mask a visibility-culled sort consumed, the stale-key state and device distances.
 static void sorter_forget_numbering(gs_sorter* s) {
-    if (s->pending_tree) gs_tree_forget_sorter(s->pending_tree, s);
-    s->pending_tree = nullptr;
-    s->pending_keep_zeroed = false;
+    handover_dropped(s->handover);
     s->has_result = false;
     s->result_mesh = nullptr; s->result_unmap = nullptr; s->result_frame = nullptr; s->result_payload_max = 0;
     s->last_render = s->last_sort = s->last_passes = 0;
     s->last_in = SortPlanIn(); s->last_plan = SortPlan();
-    s->has_gathered = false; s->gathered_on_device = false; s->gathered = 0;
     s->leaf_cache_tree = 0; s->leaf_cache_mesh = nullptr;
     s->keys_stale = false; s->stale_count = 0;
     s->dev_distances = false; s->dev_distances_count = 0;
@@ -1672,7 +1670,7 @@ static int sort_check(gs_sorter* s, SortCall& c, SortPlanIn& in) {
     in.flags = s->flags; in.precision = s->precision; in.uploaded = s->uploaded;
     in.frustum_cull = s->frustum_cull; in.visibility_cull = s->visibility_cull;
     in.clean_slot = s->clean_slot;
-    in.pending_gather = s->pending_tree != nullptr; in.pending_keep_zeroed = s->pending_keep_zeroed;
+    in.pending_gather = s->handover.state == HANDOVER_PLANNED; in.pending_keep_zeroed = s->handover.keep_zeroed;
     in.extreme_current = s->extreme_ok && s->extreme_version == s->centers_version && !s->extreme.empty();
     in.c16_current = s->c16_ok && s->c16_version == s->centers_version;
     in.sort_count = c.sort_count; in.render_count = c.render_count;
@@ -1758,21 +1756,14 @@ static int sort_stage_inputs(gs_sorter* s, const SortCall& c, const SortPlan& pl
     if (c.device_list) {
         kp.idx_in = s->idx_in.as<uint32_t>();              // written by gs_tree_gather on this stream ...
         if (pl.gather == SORT_GATHER_PLAIN) {              // ... or only planned by it (tree.hip): the copy is ours, here or fused
-            GS_TRY(gs_tree_copy_plain(s->pending_tree, s->idx_in.as<uint32_t>(), st));
-            gs_tree_forget_sorter(s->pending_tree, s);
+            GS_TRY(gs_tree_copy_plain(s->handover.tree->owner, s->idx_in.as<uint32_t>(), st));
+            handover_copied(s->handover);
         }
     } else {
-        // A sort that does not consume the gathered list may destroy what a gather left for a later gs_sorter_sort_gathered
-        // (ADVICE r04): a planned gather's fused copy ORs its keep bits into a mask the GATHER zeroed - a frustum-culled sort in
-        // between rewrites that mask, so the copy falls back to the plain one + the ordinary key kernel; a list that was already
-        // copied into idx_in is gone once a host list or a compaction overwrites it (the compaction: launch_vis_cull_front, where
-        // the front end of a visibility-culled sort is chosen - ADVICE r05: the streaming one writes pay_in and leaves idx_in alone).
-        if (s->pending_tree) {
-            if (pl.cull) s->pending_keep_zeroed = false;
-        } else if (c.indexes_to_sort) {
-            s->has_gathered = false;
-        }
+        // a sort that does not consume the gathered list may destroy what a gather left for a later gs_sorter_sort_gathered
+        if (pl.cull) handover_keep_mask_rewritten(s->handover);
         if (c.indexes_to_sort) {
+            handover_list_overwritten(s->handover);
             GS_TRY(s->idx_in.ensure((size_t)s->max_count * 4));
             if (pl.R) GS_HIP(hipMemcpyAsync(s->idx_in.p, c.indexes_to_sort, (size_t)pl.R * 4, hipMemcpyHostToDevice, st));
             kp.idx_in = s->idx_in.as<uint32_t>();
@@ -1805,7 +1796,7 @@ static int sort_stage_inputs(gs_sorter* s, const SortCall& c, const SortPlan& pl
     kp.im0 = c.im[0]; kp.im1 = c.im[1]; kp.im2 = c.im[2];
     kp.fm0 = mvp[2]; kp.fm1 = mvp[6]; kp.fm2 = mvp[10];
     if (pl.cull) {
-        GS_TRY(s->keep_mask.ensure((((size_t)s->max_count + 63) / 64 + 8) * 8));   // the key kernel writes whole 256-position windows
+        GS_TRY(s->keep_mask.ensure(sorter_keep_mask_bytes(s->max_count)));   // the key kernel writes whole 256-position windows
         kp.keep = s->keep_mask.as<unsigned long long>();
         memcpy(kp.mvp, mvp, sizeof(kp.mvp));
     }
@@ -1818,7 +1809,7 @@ static int launch_tree_front(gs_sorter* s, const SortCall& c, const SortPlan& pl
     gs_context* ctx = s->ctx;
     hipStream_t st = s->stream;
     TreeCopyParams cp;
-    gs_tree_view(s->pending_tree, &cp.v);
+    gs_tree_view(s->handover.tree->owner, &cp.v);
     const void* mesh_key = c.map ? (const void*)s->bound_mesh : nullptr;
     const uint32_t layout = c.map ? s->bound_mesh->layout_version : 0u;
     GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
@@ -1842,7 +1833,7 @@ static int launch_tree_front(gs_sorter* s, const SortCall& c, const SortPlan& pl
     const uint32_t cgrid = grid_for(cp.v.leaves, 4, (uint32_t)ctx->cu_count * 8u);
     if (pl.front == SORT_FRONT_TREE_CULL) hipLaunchKernelGGL(k_tree_copy_keys<true>, dim3(cgrid), dim3(256), 0, st, cp, kp);
     else hipLaunchKernelGGL(k_tree_copy_keys<false>, dim3(cgrid), dim3(256), 0, st, cp, kp);
-    gs_tree_forget_sorter(s->pending_tree, s);
+    handover_copied(s->handover);
     return GS_OK;
 }
 
@@ -1862,7 +1853,7 @@ static int launch_vis_cull_front(gs_sorter* s, const SortCall& c, const SortPlan
     // The projection left the by-original-index mask to us (gs_mesh_project of a full frame for a mesh whose bound sorter
     // culls by visibility): k_mask_derive_count builds it from the storage-order mask through the payload map.
     GS_REQUIRE(!lazy || c.map, "the pending projection expects the sorter to derive its visibility mask, but the sorter has no position map of the mesh");
-    if (!stream && !s->pending_tree) s->has_gathered = false;   // k_mask_compact overwrites a gathered list that was already copied into idx_in
+    if (!stream) handover_list_overwritten(s->handover);    // k_mask_compact writes idx_in
     GS_TRY(s->chunk_counts.ensure((size_t)pl.counts_words * 4));
     if (stream) GS_TRY(s->pay_in.ensure((size_t)s->max_count * 4));
     uint32_t* counts = s->chunk_counts.as<uint32_t>();
@@ -2039,15 +2030,12 @@ int gs_sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_to_so
 int gs_sorter_sort_gathered(gs_sorter* s, const float* mvp, uint32_t sort_count, const void* precomputed,
                             const float* transforms, uint32_t* sorted_out, gs_sort_stats* stats) {
     GS_REQUIRE(s != nullptr, "sorter == NULL");
-    GS_REQUIRE(s->has_gathered, "no gs_tree_gather has filled this sorter's index list");
-    if (s->gathered_on_device) {                                  // s->gathered = the tree's splat count, an upper bound
-        GS_REQUIRE(sort_count >= s->gathered, "after an asynchronous gs_tree_gather only the whole list can be sorted: the "
-                                              "partial-sort schedule needs splatRenderCount on the host (pass render_count)");
-        return sorter_sort(s, mvp, nullptr, true, s->gathered, s->gathered, precomputed, transforms, sorted_out, stats,
-                                s->gathered_dev.as<uint32_t>());
-    }
-    if (sort_count > s->gathered) sort_count = s->gathered;       // Math.min(queuedSorts.shift(), splatRenderCount)
-    return sorter_sort(s, mvp, nullptr, true, sort_count, s->gathered, precomputed, transforms, sorted_out, stats);
+    const HandoverSort r = handover_sort_request(s->handover, sort_count);
+    GS_REQUIRE(r.refused != HANDOVER_SORT_NO_LIST, "no gs_tree_gather has filled this sorter's index list");
+    GS_REQUIRE(r.refused != HANDOVER_SORT_PARTIAL_ASYNC, "after an asynchronous gs_tree_gather only the whole list can be sorted: the "
+                                                         "partial-sort schedule needs splatRenderCount on the host (pass render_count)");
+    return sorter_sort(s, mvp, nullptr, true, r.sort_count, r.render_count, precomputed, transforms, sorted_out, stats,
+                       r.count_on_device ? s->gathered_dev.as<uint32_t>() : nullptr);
 }
 
 // A bound sorter that culls by visibility and holds the mesh's position map derives the by-original-index mask itself

@@ -40,7 +40,7 @@ struct gs_tree {
     uint64_t uid = 0;               // unique per tree of this process (a sorter's leaf-major caches are keyed on it)
     double prev_scale = 1.0;        // bucket scale of the previous gather (its member counters are reset by the next one)
     uint32_t gather_serial = 0;     // gathers planned so far
-    gs_sorter* pending_sorter = nullptr;   // a sorter that has not yet copied the last planned gather's lists (deferred, fused copy)
+    GatherTreeLink link;            // the sorter that has not yet copied the last planned gather's lists (gather_plan.hpp)
     double scene_min[3] = {0, 0, 0}, scene_max[3] = {0, 0, 0};
     std::vector<TreeLeaf> leaves;          // nodesWithIndexes order
     std::vector<uint32_t> indexes;
@@ -474,9 +474,8 @@ __device__ __forceinline__ double tree_leaf_key(const GatherParams& p, double x,
 //                   full fp64 key and the leaf number -> offset(i); totals; the fused cull's keep words go back to zero
 // (the counters are handed back zeroed: hist by k_tree_fill, fill by the NEXT gather's k_tree_test)
 // Deterministic (integer sums; the order of a bucket's members is arbitrary but only their set matters).
-constexpr uint32_t TREE_BUCKET_BITS = 18;
-constexpr uint32_t TREE_BUCKETS = 1u << TREE_BUCKET_BITS;
-constexpr uint32_t PLAN_GRID = 256, PLAN_THREADS = 256;
+// (TREE_BUCKETS and PLAN_THREADS: gather_plan.hpp, which sizes the bucket scale and the leaf grid)
+constexpr uint32_t PLAN_GRID = 256;
 constexpr uint32_t PLAN_CHUNK = TREE_BUCKETS / PLAN_GRID;          // buckets per workgroup of the scan
 constexpr uint32_t PLAN_PER_THREAD = PLAN_CHUNK / PLAN_THREADS;    // ... and per thread: consecutive ones
 static_assert(PLAN_PER_THREAD * PLAN_THREADS * PLAN_GRID == TREE_BUCKETS && PLAN_PER_THREAD % 2 == 0, "plan geometry");
@@ -502,16 +501,28 @@ struct PlanBuffers {
     unsigned long long* keep_zero; uint32_t keep_words;                   // the sorter's keep mask of a fused per-splat cull (nullable)
 };
 
-__global__ __launch_bounds__(PLAN_THREADS) void k_tree_test(GatherParams p, PlanBuffers B, double scale, double prev_scale) {
+// One leaf of k_tree_test / k_tree_test_scenes<SCENES>.  !SCENES: under the modelView p came with.
+template <bool SCENES>
+__device__ __forceinline__ void tree_test_leaf(GatherParams& p, const PlanBuffers& B, double scale, double prev_scale,
+                                               const uint32_t* leaf_scene, const double* scene_mv) {
     const uint32_t i = blockIdx.x * PLAN_THREADS + threadIdx.x;
     if (i >= p.leaves) return;
     // the member counters of the PREVIOUS gather go back to zero first (its keys are still here; +inf before the first gather)
     const unsigned long long old = B.key[i];
     if (old != TREE_INF) B.fill[tree_bucket(__longlong_as_double((long long)old), prev_scale)] = 0u;
+    if (SCENES) {
+        const double* mv = scene_mv + 16 * (size_t)leaf_scene[i];
+#pragma unroll
+        for (int k = 0; k < 16; k++) p.mv[k] = mv[k];
+    }
     const double k = tree_leaf_key(p, B.center[3 * (size_t)i], B.center[3 * (size_t)i + 1], B.center[3 * (size_t)i + 2], B.size[i]);
     const unsigned long long kb = (unsigned long long)__double_as_longlong(k);       // non-negative doubles order like their bits
     B.key[i] = kb;
     if (kb != TREE_INF) atomicAdd(&B.hist[tree_bucket(k, scale)], (1ull << 40) | (unsigned long long)B.count[i]);
+}
+
+__global__ __launch_bounds__(PLAN_THREADS) void k_tree_test(GatherParams p, PlanBuffers B, double scale, double prev_scale) {
+    tree_test_leaf<false>(p, B, scale, prev_scale, nullptr, nullptr);
 }
 
 // k_tree_test for a tree of several sub-trees (dynamic mode, Viewer.js:2005-2011): every leaf is tested under the modelView of
@@ -520,17 +531,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_tree_test(GatherParams p, Plan
 __global__ __launch_bounds__(PLAN_THREADS) void k_tree_test_scenes(GatherParams p, PlanBuffers B, double scale, double prev_scale,
                                                                     const uint32_t* __restrict__ leaf_scene,
                                                                     const double* __restrict__ scene_mv) {
-    const uint32_t i = blockIdx.x * PLAN_THREADS + threadIdx.x;
-    if (i >= p.leaves) return;
-    const unsigned long long old = B.key[i];
-    if (old != TREE_INF) B.fill[tree_bucket(__longlong_as_double((long long)old), prev_scale)] = 0u;
-    const double* mv = scene_mv + 16 * (size_t)leaf_scene[i];
-#pragma unroll
-    for (int k = 0; k < 16; k++) p.mv[k] = mv[k];
-    const double k = tree_leaf_key(p, B.center[3 * (size_t)i], B.center[3 * (size_t)i + 1], B.center[3 * (size_t)i + 2], B.size[i]);
-    const unsigned long long kb = (unsigned long long)__double_as_longlong(k);
-    B.key[i] = kb;
-    if (kb != TREE_INF) atomicAdd(&B.hist[tree_bucket(k, scale)], (1ull << 40) | (unsigned long long)B.count[i]);
+    tree_test_leaf<true>(p, B, scale, prev_scale, leaf_scene, scene_mv);
 }
 
 __global__ __launch_bounds__(PLAN_THREADS) void k_tree_scan(PlanBuffers B) {
@@ -745,11 +746,17 @@ int tree_upload(gs_tree* t) {
     return GS_OK;
 }
 
-// Matrix4.multiplyMatrices (three r160), its expression order, fp64, unfused (this file is built with -ffp-contract=off)
-void mat4_multiply(const double* a, const double* b, double* te) {
-    for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 4; r++)
-            te[r + 4 * c] = a[r] * b[4 * c] + a[r + 4] * b[4 * c + 1] + a[r + 8] * b[4 * c + 2] + a[r + 12] * b[4 * c + 3];
+// a new tree with nothing built yet (nullptr: out of memory)
+gs_tree* tree_new(gs_context* ctx, uint32_t max_depth, uint32_t max_centers, uint32_t scene_count) {
+    gs_tree* t = new (std::nothrow) gs_tree();
+    if (!t) return nullptr;
+    t->ctx = ctx;
+    t->uid = ++g_tree_uid;
+    t->link.owner = t;
+    t->max_depth = max_depth;
+    t->max_centers = max_centers;
+    t->scene_count = scene_count;
+    return t;
 }
 
 }  // namespace
@@ -761,12 +768,8 @@ int gs_tree_create(gs_context* ctx, const float* centers, const uint8_t* keep, u
     GS_REQUIRE(out && (centers || count == 0), "out / centers == NULL");
     *out = nullptr;
     GS_REQUIRE(max_centers_per_node > 0, "max_centers_per_node == 0");
-    gs_tree* t = new (std::nothrow) gs_tree();
+    gs_tree* t = tree_new(ctx, max_depth, max_centers_per_node, 1);
     if (!t) return GS_ERR_NOMEM;
-    t->ctx = ctx;
-    t->uid = ++g_tree_uid;
-    t->max_depth = max_depth;
-    t->max_centers = max_centers_per_node;
     int st = tree_build(t, ctx, centers, keep, count, first_index, nullptr);
     if (st == GS_OK && ctx) st = tree_upload(t);
     if (st != GS_OK) {
@@ -789,13 +792,8 @@ int gs_tree_create_scenes(gs_context* ctx, const float* centers, const uint8_t* 
     if (scene_count == 1)                 // the reference's single sub-tree: the plain tree, leaf for leaf
         return gs_tree_create(ctx, centers, keep, scene_splat_counts[0], 0, max_depth, max_centers_per_node, out);
     GS_REQUIRE(max_centers_per_node > 0, "max_centers_per_node == 0");
-    gs_tree* t = new (std::nothrow) gs_tree();
+    gs_tree* t = tree_new(ctx, max_depth, max_centers_per_node, scene_count);
     if (!t) return GS_ERR_NOMEM;
-    t->ctx = ctx;
-    t->uid = ++g_tree_uid;
-    t->max_depth = max_depth;
-    t->max_centers = max_centers_per_node;
-    t->scene_count = scene_count;
     int st = GS_OK;
     try {
         t->scene_first_leaf.assign(scene_count + 1, 0u);
@@ -881,11 +879,7 @@ int gs_tree_scene_leaves(gs_tree* t, uint32_t* first_leaf) {
 
 void gs_tree_destroy(gs_tree* t) {
     if (!t) return;
-    if (t->pending_sorter) {                               // a sorter still waits to copy this tree's last gather: it has no list
-        t->pending_sorter->pending_tree = nullptr;
-        t->pending_sorter->has_gathered = false;
-        t->pending_sorter = nullptr;
-    }
+    handover_tree_destroyed(t->link);
     if (t->ctx) {
         ScopedDevice sd(t->ctx->device);
         (void)hipDeviceSynchronize();
@@ -939,15 +933,33 @@ static int tree_gather(gs_tree* t, const gs_gather_params* gp, const double* sce
     ScopedDevice sd(ctx->device);
     hipStream_t st = dst ? dst->stream : ctx->stream;      // the list is produced where the sort will consume it
     const uint32_t L = (uint32_t)t->leaves.size();
+    GatherHandover* to = dst ? &dst->handover : nullptr;
+    // everything that is decided (gather_plan.cpp); a plain tree is one scene: its box under the base modelView
+    GatherPlanIn in;
+    memcpy(in.model_view, gp->model_view, sizeof(in.model_view));
+    in.fov_y_deg = gp->fov_y_deg; in.render_width = gp->render_width; in.render_height = gp->render_height;
+    in.gather_all = gp->gather_all ? 1u : 0u;
+    in.leaves = L; in.tree_splats = (uint32_t)t->indexes.size();
+    in.scene_count = scene_mv ? t->scene_count : 1u;
+    in.has_sorter = dst != nullptr; in.sorter_flags = dst ? dst->flags : 0u; in.frustum_cull = dst && dst->frustum_cull;
+    in.max_count = dst ? dst->max_count : 0u;
+    in.host_copy = indexes_out_host != nullptr; in.count_on_device = !render_count;
+    in.no_defer = getenv("GSPLAT_TREE_NO_DEFER") != nullptr; in.pad = 0u;
+    for (uint32_t s = 0; s < in.scene_count; s++) {
+        GatherScene& sc = in.scene[s];
+        memcpy(sc.box, scene_mv ? &t->scene_box[6 * (size_t)s] : t->scene_min, 24);
+        memcpy(sc.box + 3, scene_mv ? &t->scene_box[6 * (size_t)s + 3] : t->scene_max, 24);
+        memcpy(sc.model_view, scene_mv ? scene_mv + 16 * (size_t)s : gp->model_view, sizeof(sc.model_view));
+        sc.empty = scene_mv ? t->scene_empty[s] : 0u; sc.pad = 0u;
+    }
+    const GatherPlan plan = plan_gather(in);
     // another sorter has not yet copied the previous gather, whose offsets are about to be overwritten: it copies now
-    if (t->pending_sorter && t->pending_sorter != dst) {
-        gs_sorter* o = t->pending_sorter;
+    if (const GatherHandover* evicted = handover_gather_begins(t->link, to)) {
+        gs_sorter* o = evicted->owner;
         GS_TRY(o->idx_in.ensure((size_t)o->max_count * 4));
         GS_TRY(gs_tree_copy_plain(t, o->idx_in.as<uint32_t>(), o->stream));
         GS_HIP(hipStreamSynchronize(o->stream));
-        gs_tree_forget_sorter(t, o);
     }
-    if (dst && dst->pending_tree && dst->pending_tree != t) gs_tree_forget_sorter(dst->pending_tree, dst);   // superseded
     uint32_t* out_dev = nullptr;
     if (dst) {
         GS_TRY(dst->idx_in.ensure((size_t)dst->max_count * 4));
@@ -958,49 +970,21 @@ static int tree_gather(gs_tree* t, const gs_gather_params* gp, const double* sce
     }
     if (render_count) *render_count = 0;
     if (L == 0) {
-        if (dst) dst->gathered = 0, dst->gathered_on_device = false, dst->has_gathered = true;
+        handover_gathered(t->link, to, false, false, 0u, false);
         return GS_OK;
     }
     GatherParams p;
     memcpy(p.mv, gp->model_view, sizeof(p.mv));
-    // Viewer.js:1990-1996
-    const double deg2rad = 3.14159265358979323846 / 180.0;              // THREE.MathUtils.DEG2RAD = Math.PI / 180
-    const double focal = (gp->render_height / 2.0) / tan(gp->fov_y_deg / 2.0 * deg2rad);
-    const double fov_x2 = atan(gp->render_width / 2.0 / focal), fov_y2 = atan(gp->render_height / 2.0 / focal);
-    p.thr_x = cos(fov_x2) - .6;
-    p.thr_y = cos(fov_y2) - .6;
-    p.gather_all = gp->gather_all ? 1u : 0u;
+    p.thr_x = plan.thr_x;
+    p.thr_y = plan.thr_y;
+    p.gather_all = in.gather_all;
     p.leaves = L;
-    // bucket scale: the farthest a leaf centre can be from the eye = the farthest corner of the scene box under this modelView
-    // (the distance is convex in the point); the order never depends on it (tree_bucket clamps), only how the leaves spread.
-    // Several sub-trees: the largest over the scenes, each scene's box under its own modelView.
-    double far = 0.0;
-    for (uint32_t sc = 0; sc < (scene_mv ? 8u * t->scene_count : 8u); sc++) {
-        const uint32_t c = sc & 7u, s = sc >> 3;
-        if (scene_mv && t->scene_empty[s]) continue;
-        const double* mn = scene_mv ? &t->scene_box[6 * (size_t)s] : t->scene_min;
-        const double* mx = scene_mv ? &t->scene_box[6 * (size_t)s + 3] : t->scene_max;
-        const double x = (c & 1) ? mx[0] : mn[0], y = (c & 2) ? mx[1] : mn[1], z = (c & 4) ? mx[2] : mn[2];
-        const double* e = scene_mv ? scene_mv + 16 * (size_t)s : p.mv;
-        double w = e[3] * x + e[7] * y + e[11] * z + e[15];
-        w = w != 0.0 ? 1.0 / w : 1.0;
-        const double vx = (e[0] * x + e[4] * y + e[8] * z + e[12]) * w, vy = (e[1] * x + e[5] * y + e[9] * z + e[13]) * w,
-                     vz = (e[2] * x + e[6] * y + e[10] * z + e[14]) * w;
-        const double d = sqrt(vx * vx + vy * vy + vz * vz);
-        if (d > far) far = d;
-    }
-    const double scale = (far > 0.0 && far < 1e300) ? (double)TREE_BUCKETS / (far * 1.0001) : 1.0;
     // the sorter gets the list's length on the device as well
     uint32_t* count_dev = nullptr;
     if (dst) {
         GS_TRY(dst->gathered_dev.ensure(16));
         count_dev = dst->gathered_dev.as<uint32_t>();
     }
-    // The copy is DEFERRED to the sorter when nothing but the sorter will read the list: a full sort of a static scene then
-    // copies the lists, keys them (and tests them against the frustum) in one kernel that streams the centres in leaf order
-    // (sorter.hip, k_tree_copy_keys); any other sort copies first (gs_tree_copy_plain) and goes on as before.
-    // (never for a tree of several sub-trees: the fused copy and its leaf-ordered centre planes know one modelView)
-    const bool deferred = dst && !indexes_out_host && !(dst->flags & GS_SORT_DYNAMIC) && !getenv("GSPLAT_TREE_NO_DEFER") && !scene_mv;
     PlanBuffers pb;
     pb.center = t->d_center.as<double>(); pb.size = t->d_size.as<double>(); pb.count = t->d_count.as<uint32_t>();
     pb.key = t->d_key.as<unsigned long long>();
@@ -1010,14 +994,12 @@ static int tree_gather(gs_tree* t, const gs_gather_params* gp, const double* sce
     pb.fill = reinterpret_cast<uint32_t*>(pb.chunk_sum + PLAN_GRID);
     pb.members = t->d_rank.as<uint32_t>(); pb.offset = t->d_offset.as<uint32_t>();
     pb.totals = t->d_total.as<uint32_t>(); pb.count_out = count_dev;
-    pb.keep_zero = nullptr; pb.keep_words = 0;
-    if (deferred && dst->frustum_cull) {                   // the fused copy ORs its keep bits into a zeroed mask
-        GS_TRY(dst->keep_mask.ensure((((size_t)dst->max_count + 63) / 64 + 8) * 8));
+    pb.keep_zero = nullptr; pb.keep_words = plan.keep_words;
+    if (plan.zero_keep) {
+        GS_TRY(dst->keep_mask.ensure(sorter_keep_mask_bytes(dst->max_count)));
         pb.keep_zero = dst->keep_mask.as<unsigned long long>();
-        pb.keep_words = (uint32_t)(((size_t)t->indexes.size() + 63) / 64 + 2);
     }
-    const uint32_t lgrid = (L + PLAN_THREADS - 1u) / PLAN_THREADS;
-    if (scene_mv) {
+    if (plan.scene_table) {
         // The scenes' modelViews reach the device by a stream-ordered copy out of pinned staging, which the copy engine reads
         // when the stream gets there - possibly after this call has returned (asynchronous gather).  The staging has
         // TREE_STAGE_SLOTS slots used in turn, each with an event recorded behind its copy: a slot is rewritten only after that
@@ -1030,45 +1012,31 @@ static int tree_gather(gs_tree* t, const gs_gather_params* gp, const double* sce
         memcpy(t->mv_stage + slot * mv_count, scene_mv, 8 * mv_count);
         GS_HIP(hipMemcpyAsync(t->d_scene_mv.p, t->mv_stage + slot * mv_count, 8 * mv_count, hipMemcpyHostToDevice, st));
         GS_HIP(hipEventRecord(t->mv_stage_read[slot], st));
-        hipLaunchKernelGGL(k_tree_test_scenes, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale, t->prev_scale,
+        hipLaunchKernelGGL(k_tree_test_scenes, dim3(plan.leaf_grid), dim3(PLAN_THREADS), 0, st, p, pb, plan.scale, t->prev_scale,
                            t->d_scene.as<uint32_t>(), t->d_scene_mv.as<double>());
     } else {
-        hipLaunchKernelGGL(k_tree_test, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale, t->prev_scale);
+        hipLaunchKernelGGL(k_tree_test, dim3(plan.leaf_grid), dim3(PLAN_THREADS), 0, st, p, pb, plan.scale, t->prev_scale);
     }
     hipLaunchKernelGGL(k_tree_scan, dim3(PLAN_GRID), dim3(PLAN_THREADS), 0, st, pb);
-    hipLaunchKernelGGL(k_tree_fill, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale);
-    hipLaunchKernelGGL(k_tree_offsets, dim3(lgrid), dim3(PLAN_THREADS), 0, st, p, pb, scale);
+    hipLaunchKernelGGL(k_tree_fill, dim3(plan.leaf_grid), dim3(PLAN_THREADS), 0, st, p, pb, plan.scale);
+    hipLaunchKernelGGL(k_tree_offsets, dim3(plan.leaf_grid), dim3(PLAN_THREADS), 0, st, p, pb, plan.scale);
     GS_HIP(hipGetLastError());
-    t->prev_scale = scale;
+    t->prev_scale = plan.scale;
     t->gather_serial++;
-    if (deferred) {
-        dst->pending_tree = t;
-        dst->pending_keep_zeroed = pb.keep_zero != nullptr;
-        t->pending_sorter = dst;
-    } else {
-        GS_TRY(gs_tree_copy_plain(t, out_dev, st));
-        if (dst && dst->pending_tree == t) gs_tree_forget_sorter(t, dst);
+    if (!plan.deferred) GS_TRY(gs_tree_copy_plain(t, out_dev, st));
+    // Asynchronous: nothing returns to the host, splatRenderCount stays on the device next to the list; the sorter takes both
+    // from there (gs_sorter_sort_gathered), the draw takes the sorted list's length from the sorter.  The tree's splat count is
+    // an upper bound that sizes grids and buffers.
+    uint32_t total = in.tree_splats;
+    if (render_count) {
+        GS_HIP(hipMemcpyAsync(&total, t->d_total.p, 4, hipMemcpyDeviceToHost, st));
+        GS_HIP(hipStreamSynchronize(st));                  // the Viewer needs splatRenderCount on the host
+        *render_count = total;
     }
-    if (!render_count) {
-        // asynchronous: nothing returns to the host, splatRenderCount stays on the device next to the list; the sorter takes
-        // both from there (gs_sorter_sort_gathered), the draw takes the sorted list's length from the sorter
-        dst->gathered = (uint32_t)t->indexes.size();          // upper bound: sizes grids and buffers
-        dst->gathered_on_device = true;
-        dst->has_gathered = true;
-        return GS_OK;
-    }
-    uint32_t total = 0;
-    GS_HIP(hipMemcpyAsync(&total, t->d_total.p, 4, hipMemcpyDeviceToHost, st));
-    GS_HIP(hipStreamSynchronize(st));                      // the Viewer needs splatRenderCount on the host
-    *render_count = total;
+    handover_gathered(t->link, to, plan.deferred != 0u, plan.zero_keep != 0u, total, !render_count);
     if (indexes_out_host && total) {
         GS_HIP(hipMemcpyAsync(indexes_out_host, out_dev, (size_t)total * 4, hipMemcpyDeviceToHost, st));
         GS_HIP(hipStreamSynchronize(st));
-    }
-    if (dst) {
-        dst->gathered = total;
-        dst->gathered_on_device = false;
-        dst->has_gathered = true;
     }
     return GS_OK;
 }
@@ -1086,7 +1054,7 @@ int gs_tree_gather_scenes(gs_tree* t, const gs_gather_params* gp, const double* 
     // Viewer.js:2007-2011: modelView = baseModelView x sceneTransform(s); no transforms = every scene under the base
     double mv[16 * GS_MAX_SCENES];
     for (uint32_t s = 0; s < t->scene_count; s++) {
-        if (scene_transforms) mat4_multiply(gp->model_view, scene_transforms + 16 * (size_t)s, mv + 16 * (size_t)s);
+        if (scene_transforms) gather_mat4_multiply(gp->model_view, scene_transforms + 16 * (size_t)s, mv + 16 * (size_t)s);
         else memcpy(mv + 16 * (size_t)s, gp->model_view, sizeof(gp->model_view));
     }
     if (t->scene_count == 1) {             // a plain tree: its one modelView rides along with the kernel arguments, as ever
@@ -1124,9 +1092,4 @@ int gs_tree_copy_plain(gs_tree* t, uint32_t* out_dev, hipStream_t st) {
                        t->d_count.as<uint32_t>(), t->d_begin.as<uint32_t>(), t->d_indexes.as<uint32_t>(), out_dev);
     GS_HIP(hipGetLastError());
     return GS_OK;
-}
-
-void gs_tree_forget_sorter(gs_tree* t, gs_sorter* s) {
-    if (t && t->pending_sorter == s) t->pending_sorter = nullptr;
-    if (s && s->pending_tree == t) s->pending_tree = nullptr;
 }
