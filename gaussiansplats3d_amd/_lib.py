@@ -87,6 +87,12 @@ class AssetInfo(C.Structure):
                 ("sh_level", C.c_uint32), ("scene_center", C.c_float * 3), ("sh_min", C.c_float), ("sh_max", C.c_float)]
 
 
+class AssetStreamInfo(C.Structure):
+    """gs_asset_stream_info: where a streamed asset stands."""
+    _fields_ = [("bytes_received", C.c_uint64), ("header_ready", C.c_uint32), ("splats_ready", C.c_uint32),
+                ("complete", C.c_uint32), ("failed", C.c_uint32)]
+
+
 class Bounds(C.Structure):
     """gs_bounds: what gs_mesh_bounds found over a range of splats."""
     _fields_ = [("count", C.c_uint64), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("max_dist_sq", C.c_double)]
@@ -126,6 +132,9 @@ SYMBOLS = {
     "gs_sorter_debug_read": (C.c_int, [_VP, C.c_int, _VP, C.c_uint32]),
     "gs_asset_open": (C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_VP)]),
     "gs_asset_close": (None, [_VP]),
+    "gs_asset_open_stream": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(_VP)]),
+    "gs_asset_append": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int]),
+    "gs_asset_get_stream_info": (C.c_int, [_VP, C.POINTER(AssetStreamInfo)]),
     "gs_asset_get_info": (C.c_int, [_VP, C.POINTER(AssetInfo)]),
     "gs_asset_set_transform": (C.c_int, [_VP, _VP]),
     "gs_asset_fill": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

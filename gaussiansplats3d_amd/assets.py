@@ -128,6 +128,53 @@ class SplatAsset:
             pass
 
 
+class SplatAssetStream(SplatAsset):
+    """An asset handed over as it arrives (gs_asset_open_stream): ``append(data, final)`` takes the next piece, and after
+    every append ``upload_to`` / ``upload_centers_to`` take any range of the first ``stream_info.splats_ready`` splats - a
+    prefix of the whole file's numbering that never shrinks.  Once the final append is accepted it is the ``SplatAsset`` of
+    the concatenated bytes: ``fill`` and ``encode_ksplat`` work from then on (gsplat_hip.h: rules M and P).  ``fmt`` is
+    required (a stream has no bytes to look at); ``"splat"`` needs ``expected_bytes``.  ``info`` is None until the header is in.
+    The appends and uploads of one stream come from one thread."""
+
+    def __init__(self, fmt, spherical_harmonics_degree=2, expected_bytes=0):
+        self.lib = L.load()
+        self.handle = C.c_void_p()
+        self.info = None
+        if fmt not in self.FORMATS:
+            raise ValueError(f"unknown asset format {fmt!r}: one of {sorted(self.FORMATS)}")
+        L.check(self.lib.gs_asset_open_stream(self.FORMATS[fmt], int(spherical_harmonics_degree), int(expected_bytes),
+                                              C.byref(self.handle)))
+        self._refresh()
+
+    def _refresh(self):
+        info = self.stream_info
+        if info.header_ready:
+            self.info = L.AssetInfo()
+            L.check(self.lib.gs_asset_get_info(self.handle, C.byref(self.info)))
+        return info
+
+    @property
+    def stream_info(self):
+        info = L.AssetStreamInfo()
+        L.check(self.lib.gs_asset_get_stream_info(self.handle, C.byref(info)))
+        return info
+
+    def append(self, data, final=False):
+        """The next piece of the file (any length, empty too); ``final`` with the last one.  Returns ``stream_info``.  A
+        refused append raises, consumes nothing and ends the stream; what was ready stays uploadable."""
+        data = bytes(data)
+        L.check(self.lib.gs_asset_append(self.handle, data, len(data), int(bool(final))))
+        return self._refresh()
+
+    def upload_to(self, mesh, frm=0, first=0, count=None, minimum_alpha=1):
+        count = self.stream_info.splats_ready - first if count is None else count
+        super().upload_to(mesh, frm, first, count, minimum_alpha)
+
+    def upload_centers_to(self, sorter, frm=0, first=0, count=None, scene_indexes=None):
+        count = self.stream_info.splats_ready - first if count is None else count
+        super().upload_centers_to(sorter, frm, first, count, scene_indexes)
+
+
 def load(path_or_bytes, spherical_harmonics_degree=2, minimum_alpha=1, half_precision_covariances=False):
     fmt = None
     if isinstance(path_or_bytes, str):

@@ -3,7 +3,7 @@
 // The kernels take a ROW SOURCE (a template parameter, as XF is one): the .ksplat image (also an INRIA-v1 PLY's level-0
 // image; KsplatSource, the reader the host fill uses too), the 32-byte rows of a .splat, the 16-byte vertex rows + chunk rows +
 // SH bytes of a PlayCanvas compressed PLY, the six byte planes of an inflated .spz, or the index rows + decoded codebook of an INRIA-v2
-// PLY.  The last four produce the level-0 tuple in registers through asset_internal.hpp's row arithmetic - the functions the host's image builder calls - so only file rows
+// PLY, or the trainer's own rows of a streamed INRIA-v1 PLY.  The last five produce the level-0 tuple in registers through asset_internal.hpp's row arithmetic - the functions the host's image builder calls - so only file rows
 // cross the bus and the level-0 image is never built on this path.
 // What a thread does with its row is asset_fill_splat (asset_internal.hpp): the one body gs_asset_fill (assets.hip) loops over,
 // compiled for both sides, so the planes are bit-equal to what gs_asset_fill + gs_mesh_upload (+ gs_mesh_upload_sh_u8) leave.
@@ -130,7 +130,8 @@ extern "C" {
 int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first, uint32_t count, uint32_t min_alpha) {
     GS_REQUIRE(m && a, "mesh / asset == NULL");
     GS_REQUIRE((uint64_t)from + count <= m->max_count, "range exceeds max_splat_count");
-    GS_REQUIRE((uint64_t)first + count <= a->splat_count, "range exceeds the asset's splat count");
+    GS_REQUIRE((uint64_t)first + count <= a->ready(), a->stream ? "range exceeds the stream's ready splats (gs_asset_stream_info.splats_ready)"
+                                                                 : "range exceeds the asset's splat count");
     GS_REQUIRE(m->sh_degree == a->sh_degree, "the mesh's SH degree differs from the asset's (gs_asset_info.sh_degree)");
     const bool mesh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
     GS_REQUIRE(m->sh_degree == 0 || mesh_u8 == (a->level == 2),
@@ -147,7 +148,8 @@ int gs_sorter_upload_asset_centers(gs_sorter* s, uint32_t from, gs_asset* a, uin
                                    const uint32_t* scene_indexes) {
     GS_REQUIRE(s && a, "sorter / asset == NULL");
     GS_REQUIRE((uint64_t)from + count <= s->max_count, "range exceeds max_splat_count");
-    GS_REQUIRE((uint64_t)first + count <= a->splat_count, "range exceeds the asset's splat count");
+    GS_REQUIRE((uint64_t)first + count <= a->ready(), a->stream ? "range exceeds the stream's ready splats (gs_asset_stream_info.splats_ready)"
+                                                                 : "range exceeds the asset's splat count");
     GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || scene_indexes, "dynamic sorter needs scene_indexes");
     GS_REQUIRE(!(s->flags & GS_SORT_DYNAMIC) || !a->has_transform,
                "a dynamic sorter takes untransformed centres: dynamic mode applies scene transforms per frame and never bakes them");

@@ -56,6 +56,7 @@ extern "C" int gs_debug_ksplat_layout(uint32_t level, uint32_t sh_degree, uint32
     return GS_OK;
 }
 
+// (its sibling for one row of a stream's ready prefix is gs_debug_asset_row, assets.hip: the readers it needs live there)
 // Debug entry for the tests (not in the public header): the level-0 image the host readers lay an asset's rows out as - what the
 // encoder's result is compared with through a host model.  Valid until the asset is closed.
 extern "C" int gs_debug_asset_level0_image(gs_asset* a, const void** data, uint64_t* bytes) {
@@ -541,6 +542,7 @@ int gs_asset_encode_ksplat(gs_context* ctx, gs_asset* src, const gs_ksplat_param
     GS_REQUIRE(params->flags == 0, "unknown flags");
     GS_REQUIRE(p.block == p.block && p.block > 0.0 && p.block < (double)INFINITY, "block_size is not a finite number above 0");
     GS_REQUIRE(p.bucket_size <= 65535u, "bucket_size above 65535");
+    GS_REQUIRE(!src->incomplete(), "the source is a stream that is not complete");
     if (src->level != 0) {
         gs_set_error("unsupported: the source is a compression level %u .ksplat: its values are quantised already", src->level);
         return GS_ERR_UNSUPPORTED;

@@ -1,10 +1,13 @@
 // asset_internal.hpp — what the host readers (assets.hip) and the device decode (asset_decode.hip) share, each said once as
 // __host__ __device__ code for both sides: the two half-float rules, the scene transform, the per-row arithmetic of the formats
-// whose file rows are decoded on both sides (.splat, PlayCanvas compressed PLY, .spz, INRIA-v2 codebook PLY), the .ksplat row
+// whose file rows are decoded on both sides (.splat, PlayCanvas compressed PLY, .spz, INRIA-v2 codebook PLY, streamed INRIA-v1 PLY), the .ksplat row
 // reader (KsplatSource) and the per-splat fill (asset_fill_splat) that gs_asset_fill loops over and k_asset_decode runs one thread of.
 #pragma once
 #include <math.h>
 
+#include <memory>
+
+#include "asset_stream.hpp"
 #include "gs_internal.hpp"
 #include "spz_container.hpp"
 
@@ -407,6 +410,96 @@ __host__ __device__ inline float inria_v2_row_sh(const uint8_t* row, const Inria
     return inria_v2_entry(codebook, IV2_PAGE_REST + (s < 9u ? s % 3u : 3u + (s - 9u) % 5u), row[L.sh[s]]);
 }
 
+// ---- INRIA-v1 PLY: the trainer's own rows -> the level-0 tuple --------------------------------------------------------------------------
+// Restates, never copies: src/loaders/ply/INRIAV1PlyParser.js:114-209 (parseToUncompressedSplat) + PlyParserUtils.readVertex, then the
+// level-0 store of SplatBuffer.writeSplatDataToSectionBuffer :1056-1113 - the rules parse_ply (assets.hip) applies to a whole file, with
+// row_exp where that calls libm's exp (one implementation for both sides; after the fp32 store and floor(. * 255) the two agree except
+// on rare boundary inputs).  Only streamed assets read their rows through this (gs_asset_open_stream).
+// Where the fields parse_ply maps lie in a file row, from the header: the row stride (< 64 KiB) and per field a present bit, a type
+// and an offset.  A `double` property is never read by the reference (PlyParserUtils.js:281-301): it counts as absent.
+enum : uint8_t { IV1_FLOAT = 0, IV1_INT = 1, IV1_UINT = 2, IV1_SHORT = 3, IV1_USHORT = 4, IV1_UCHAR = 5 };
+struct InriaV1Field { uint16_t offset; uint8_t type, present; };
+struct InriaV1Layout {
+    uint32_t stride;           // bytes per file row: 68 at degree 0, 248 at degree 3, odd with a uchar property
+    uint32_t aligned;          // the stride and the offset of every present 4-byte field are multiples of 4: with row 0 on a 16-byte
+                               // boundary (the staging base) such a field is one aligned dword load on the device
+    InriaV1Field pos[3], scale[3], rot[4], dc[3], rgb[3], opacity, rest0;
+    InriaV1Field sh[24];       // level-0 SH slot s: f_rest_{s%3 + cpc*(s/3)} below 9, f_rest_{3 + (s-9)%5 + cpc*((s-9)/5)} above
+};
+
+// PlyParserUtils.readVertex for one field: false = `undefined`.  Nothing is known of a row's alignment on the host (the header has
+// any length), and on the device only what `aligned` proves: everything else is put together from byte loads.
+__host__ __device__ __forceinline__ bool inria_v1_read(const uint8_t* row, const InriaV1Layout& L, const InriaV1Field f, double* out) {
+    if (!f.present) return false;
+    const uint8_t* p = row + f.offset;
+    if (f.type == IV1_UCHAR) { *out = (double)p[0] / 255.0; return true; }                // normalize = true
+    if (f.type >= IV1_SHORT) {
+        const uint32_t h = (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+        *out = f.type == IV1_SHORT ? (double)(int16_t)h : (double)h;
+        return true;
+    }
+    uint32_t w;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (L.aligned) w = *reinterpret_cast<const uint32_t*>(p);
+    else
+#endif
+        w = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    (void)L;
+    *out = f.type == IV1_FLOAT ? (double)__builtin_bit_cast(float, w) : (f.type == IV1_INT ? (double)(int32_t)w : (double)w);
+    return true;
+}
+
+// the centre alone: x, y, z as stored fp32 (an absent one is NaN)
+__host__ __device__ inline void inria_v1_row_centre(const uint8_t* row, const InriaV1Layout& L, float c[3]) {
+    for (int k = 0; k < 3; k++) {
+        double v = (double)NAN;
+        inria_v1_read(row, L, L.pos[k], &v);
+        c[k] = (float)v;
+    }
+}
+
+__host__ __device__ inline void inria_v1_row_tuple(const uint8_t* row, const InriaV1Layout& L, Level0Tuple& t) {
+#pragma clang fp contract(off)
+    double v, s3[3], r4[4] = {(double)NAN, (double)NAN, (double)NAN, (double)NAN}, col[3], op = 0.0;   // createSplat() starts every field at 0
+    if (inria_v1_read(row, L, L.scale[0], &v)) {                                       // INRIAV1PlyParser.js:148-156
+        for (int k = 0; k < 3; k++) { s3[k] = (double)NAN; if (inria_v1_read(row, L, L.scale[k], &v)) s3[k] = row_exp(v); }
+    } else {
+        s3[0] = s3[1] = s3[2] = 0.01;
+    }
+    if (inria_v1_read(row, L, L.dc[0], &v)) {                                          // :158-172
+        const double SH_C0 = 0.28209479177387814;
+        for (int k = 0; k < 3; k++) { col[k] = (double)NAN; if (inria_v1_read(row, L, L.dc[k], &v)) col[k] = (0.5 + SH_C0 * v) * 255; }
+    } else if (inria_v1_read(row, L, L.rgb[0], &v)) {
+        for (int k = 0; k < 3; k++) { col[k] = (double)NAN; if (inria_v1_read(row, L, L.rgb[k], &v)) col[k] = v * 255; }
+    } else {
+        col[0] = col[1] = col[2] = 0;
+    }
+    if (inria_v1_read(row, L, L.opacity, &v)) op = (1 / (1 + row_exp(-v))) * 255;       // :174-176
+    for (int k = 0; k < 3; k++) col[k] = clampd(floor(col[k]), 0, 255);                // :178-181
+    op = clampd(floor(op), 0, 255);
+    // :196-202 Quaternion.set(rot_0..3).normalize(), then the second normalize of writeSplatDataToSectionBuffer :1084-1086
+    for (int k = 0; k < 4; k++) if (inria_v1_read(row, L, L.rot[k], &v)) r4[k] = v;
+    row_normalize(r4);
+    row_normalize(r4);
+    inria_v1_row_centre(row, L, t.c);
+    for (int k = 0; k < 3; k++) t.s[k] = (float)(s3[k] == s3[k] ? s3[k] : 0.0);        // `|| 0`
+    for (int k = 0; k < 4; k++) t.r[k] = row_f32(r4[k]);                               // an infinite component: inf * (1 / inf) = a generated NaN
+    for (int k = 0; k < 3; k++) t.rgba[k] = col[k] == col[k] ? (uint8_t)col[k] : (uint8_t)0;   // Uint8ClampedArray store of an integer in 0..255, NaN -> 0
+    t.rgba[3] = op == op ? (uint8_t)op : (uint8_t)0;
+}
+
+// Level-0 SH float s of the row (:183-194): read only when the row has an f_rest_0 (inria_v1_row_has_sh: asked once per row); an
+// absent field is 0
+__host__ __device__ inline bool inria_v1_row_has_sh(const uint8_t* row, const InriaV1Layout& L) {
+    double v;
+    return inria_v1_read(row, L, L.rest0, &v);
+}
+__host__ __device__ inline float inria_v1_row_sh(const uint8_t* row, const InriaV1Layout& L, bool has_sh, uint32_t s) {
+    double v, c = 0;
+    if (has_sh && inria_v1_read(row, L, L.sh[s], &v)) c = v;
+    return (float)c;
+}
+
 // ---- .ksplat rows: one reader for the host fill and the kernels ------------------------------------------------------------------
 // Restates, never copies: SplatBuffer.js:108-163 (rows per compression level), :199-219 (bucket of a splat), :221-246 (centre).
 // Bytes of a row's parts per compression level, in row order: centre, scale, rotation, RGBA (4), SH
@@ -623,7 +716,9 @@ __host__ __device__ __forceinline__ void asset_fill_splat(const Row row, const A
     }
 }
 
-enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3, ASSET_ROWS_INRIA_V2 = 4 };
+constexpr uint32_t GS_DEBUG_ASSET_ROW_BYTES = 140;         // what gs_debug_asset_row (assets.hip) writes at most: 44 + 4 * 24
+enum AssetRows : uint32_t { ASSET_ROWS_KSPLAT = 0, ASSET_ROWS_SPLAT = 1, ASSET_ROWS_COMPRESSED_PLY = 2, ASSET_ROWS_SPZ = 3, ASSET_ROWS_INRIA_V2 = 4,
+                            ASSET_ROWS_INRIA_V1 = 5 };
 
 struct gs_asset {
     std::vector<uint8_t> buf;              // a .ksplat image (for an INRIA-v1 PLY: the level-0 section built from it; for the
@@ -637,6 +732,9 @@ struct gs_asset {
     InriaV2Layout iv2 = {};                // INRIA-v2 PLY: the vertex element's layout, where its rows start in `file`, and the
     size_t iv2_vertex_base = 0;            // codebook decoded at open (IV2_PAGES x 256 floats)
     std::vector<float> iv2_codebook;
+    InriaV1Layout iv1 = {};                // a STREAMED INRIA-v1 PLY: the vertex element's layout and where its rows start in `file`
+    size_t iv1_vertex_base = 0;            // (gs_asset_open lays a whole INRIA-v1 file out as a level-0 image instead)
+    std::unique_ptr<AssetStream> stream;   // gs_asset_open_stream: the state of the stream (asset_stream.hpp), else null
     uint32_t level = 0, splat_count = 0, sh_degree = 0;
     float scene_center[3] = {0, 0, 0};
     double sh_min = -1.5, sh_max = 1.5;
@@ -645,6 +743,9 @@ struct gs_asset {
     bool has_transform = false;            // gs_asset_set_transform
     AssetTransform xf = {};
     bool encoded = false;                  // `buf` is a file image gs_asset_encode_ksplat made (gs_asset_bytes hands it out)
+    // the splats an upload may name: all of an opened asset, the ready prefix of a stream
+    uint32_t ready() const { return stream ? stream->splats_ready : splat_count; }
+    bool incomplete() const { return stream && !stream->complete; }
 
     template <class T>
     T rd(size_t off) const {

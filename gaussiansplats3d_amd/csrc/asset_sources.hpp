@@ -177,6 +177,40 @@ struct InriaV2Source {
     }
 };
 
+// A streamed INRIA-v1 PLY: the trainer's own rows at their file stride (68 bytes at degree 0, 248 at degree 3, odd with a uchar
+// property), row 0 at the staging base - the header has any length, so nothing else is known of a row's alignment.  A thread reads
+// its row's fields in place: when the stride and every 4-byte field's offset are multiples of 4 (layout.aligned: every file of
+// floats), each is one aligned dword load, else it is put together from byte loads; no load reaches past the row.  Neighbouring
+// lanes are a stride apart, so a wave's loads of one field touch 64 rows' cache lines, and the lines are used up as the thread walks
+// its fields.  k_asset_centers reads x, y and z alone.
+struct InriaV1Source {
+    const uint8_t* rows;           // row 0 = asset splat `base`
+    uint32_t base;
+    uint32_t level, sh_degree, ncomp;   // 0, the output degree, 0 / 9 / 24
+    InriaV1Layout layout;
+    struct Row : TupleValues {
+        const uint8_t* row;
+        const InriaV1Layout& L;
+        bool has_sh;               // the row has an f_rest_0: read once, not per SH slot
+        __device__ __forceinline__ float value(uint32_t src) const { return inria_v1_row_sh(row, L, has_sh, src); }
+        __device__ __forceinline__ double sh_wide(uint32_t src, double, double) const { return (double)value(src); }
+        __device__ __forceinline__ uint16_t sh_half(uint32_t src) const { return to_half_three((double)value(src)); }
+        __device__ __forceinline__ uint8_t sh_byte(uint32_t) const { return 0; }   // sh_level is 1: never stored as bytes
+    };
+    __device__ __forceinline__ const uint8_t* row_of(uint32_t splat) const { return rows + (size_t)layout.stride * (splat - base); }
+    __device__ __forceinline__ Row row(uint32_t splat) const {
+        Row r = {{}, row_of(splat), layout, false};
+        r.has_sh = ncomp != 0 && inria_v1_row_has_sh(r.row, layout);
+        inria_v1_row_tuple(r.row, layout, r.t);
+        return r;
+    }
+    __device__ __forceinline__ void centre(uint32_t splat, double d[3]) const {    // x, y, z alone
+        float c[3];
+        inria_v1_row_centre(row_of(splat), layout, c);
+        for (int k = 0; k < 3; k++) d[k] = c[k];
+    }
+};
+
 // floats of LDS a source's workgroup fills before its threads decode (Source::load_table): the 13 pages degree 2 reads
 template <class Source> struct LdsTable { static constexpr uint32_t floats = 0; };
 template <> struct LdsTable<InriaV2Source> { static constexpr uint32_t floats = 256u * (IV2_PAGE_REST + 8u); };
@@ -306,6 +340,18 @@ int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceIm
     return GS_OK;
 }
 
+// A streamed INRIA-v1 PLY: rows [first, first + count) at their file stride, one piece at the staging base, padded to 16 bytes.  The
+// caller proved the range ready: every byte of these rows has arrived.
+int asset_stage(const gs_asset* a, uint32_t first, uint32_t count, AssetDeviceImage& dev, hipStream_t st, InriaV1Source* src, bool centres_only) {
+    (void)centres_only;                                      // the centre lies in the row
+    const size_t stride = a->iv1.stride, bytes = stride * count;
+    GS_TRY(dev.bytes.ensure(((bytes + 15) & ~(size_t)15) + 16));
+    if (bytes) GS_HIP(hipMemcpyAsync(dev.bytes.p, a->file.data() + a->iv1_vertex_base + stride * first, bytes, hipMemcpyHostToDevice, st));
+    GS_HIP(hipStreamSynchronize(st));
+    *src = InriaV1Source{dev.bytes.as<uint8_t>(), first, 0u, a->sh_degree, sh_components(a->sh_degree), a->iv1};
+    return GS_OK;
+}
+
 // a->rows -> the source type of its rows: f(SourceOf<Source>())
 template <class Source>
 struct SourceOf { using type = Source; };
@@ -316,6 +362,7 @@ int with_source_of(const gs_asset* a, F f) {
         case ASSET_ROWS_COMPRESSED_PLY: return f(SourceOf<CompressedSource>());
         case ASSET_ROWS_SPZ: return f(SourceOf<SpzSource>());
         case ASSET_ROWS_INRIA_V2: return f(SourceOf<InriaV2Source>());
+        case ASSET_ROWS_INRIA_V1: return f(SourceOf<InriaV1Source>());
         default: return f(SourceOf<KsplatSource>());
     }
 }

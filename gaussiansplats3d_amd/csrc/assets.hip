@@ -53,8 +53,14 @@ uint8_t clamped_u8(double v) {                         // Uint8ClampedArray stor
 
 constexpr size_t KS_HEADER = 4096, KS_SECTION_HEADER = 1024;
 
-int parse_ksplat(gs_asset* a) {
+// whole: `buf` is the file, and what does not fit into it is refused.  Else `buf` is the prefix of a stream (gs_asset_append): what
+// has not arrived is waited for (STREAM_NEED_MORE before the header and every section header are in), `sections` receives the
+// sections whose bucket block has arrived and passed the table checks - in file order, stopping at the first that has not - and
+// `runs` says from which byte on their rows are ready.
+const char KS_DATA_EXCEEDS[] = ".ksplat: section data exceeds the file";
+int parse_ksplat(gs_asset* a, bool whole = true, std::vector<StreamRun>* runs = nullptr, size_t* file_end = nullptr) {
     const size_t n = a->buf.size();
+    if (!whole && n < KS_HEADER) return STREAM_NEED_MORE;
     GS_REQUIRE(n >= KS_HEADER, ".ksplat: shorter than its 4096-byte header");
     const uint32_t max_sections = a->rd<uint32_t>(4), max_splats = a->rd<uint32_t>(12);
     a->level = a->rd<uint16_t>(20);
@@ -63,7 +69,9 @@ int parse_ksplat(gs_asset* a) {
     const float mn = a->rd<float>(36), mx = a->rd<float>(40);
     a->sh_min = mn != 0.0f ? (double)mn : -1.5;            // `|| -DefaultSphericalHarmonics8BitCompressionHalfRange`
     a->sh_max = mx != 0.0f ? (double)mx : 1.5;
+    if (!whole && KS_HEADER + (size_t)max_sections * KS_SECTION_HEADER > n) return STREAM_NEED_MORE;
     GS_REQUIRE(KS_HEADER + (size_t)max_sections * KS_SECTION_HEADER <= n, ".ksplat: section headers exceed the file");
+    bool arrived = true;                                    // (a stream) every bucket block so far is in
     size_t base = KS_HEADER + (size_t)max_sections * KS_SECTION_HEADER;
     uint32_t count_offset = 0;
     uint32_t min_degree = 0;
@@ -90,9 +98,10 @@ int parse_ksplat(gs_asset* a) {
         sec.data_off = (long long)(base + buckets);
         sec.count_offset = count_offset;
         const size_t end = base + buckets + (size_t)sec.bytes_per_splat * sec.count;
-        GS_REQUIRE(end <= n, ".ksplat: section data exceeds the file");
+        GS_REQUIRE(!whole || end <= n, KS_DATA_EXCEEDS);
+        arrived = arrived && base + buckets <= n;
         sec.partial_begin = (uint32_t)a->partial_end.size();
-        if (a->level > 0 && sec.count > 0) {
+        if (arrived && a->level > 0 && sec.count > 0) {
             // Bucket tables are only read for compressed centres (SplatBuffer.js:199-246).  The reference is memory-safe
             // JavaScript; here every index into the tables is proven in range before a row read goes through them.
             GS_REQUIRE(sec.bucket_storage >= 12, ".ksplat: bucket storage below the 12 bytes of a bucket centre");
@@ -112,11 +121,15 @@ int parse_ksplat(gs_asset* a) {
         base = end;
         count_offset += sec.count;
         if (s == 0 || sh_degree < min_degree) min_degree = sh_degree;   // getMinSphericalHarmonicsDegree
-        if (sec.count > 0) a->sections.push_back(sec);      // section_of looks among the ones that hold splats
+        if (sec.count > 0 && arrived) {
+            a->sections.push_back(sec);                     // section_of looks among the ones that hold splats
+            if (runs) runs->push_back({(uint64_t)sec.data_off, (uint64_t)sec.data_off, sec.bytes_per_splat, sec.count_offset, sec.count});
+        }
     }
     GS_REQUIRE(count_offset == max_splats || max_sections == 0 || count_offset >= max_splats, ".ksplat: splat counts disagree");
     a->splat_count = count_offset < max_splats ? count_offset : max_splats;
     a->sh_degree = min_degree;
+    if (file_end) *file_end = base;
     return GS_OK;
 }
 
@@ -189,10 +202,21 @@ std::string trim(const std::string& s) {
     return s.substr(b, e - b);
 }
 
-int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+// What the header of an INRIA-v1 PLY says: where the rows start, their stride and count, the output degree and where the fields
+// the reference reads lie in a row.
+struct PlyV1Header {
+    size_t header_bytes = 0, bytes_per_vertex = 0;
+    uint32_t vertex_count = 0, out_degree = 0;
+    PlyField scale[3], rot[4], pos[3], dc[3], op, rgb[3], rest0, d1[9], d2[15];
+};
+
+// The header work of parse_ply, for the whole-file reader and the stream.  `bytes` of `data` are present; file_bytes is the file's
+// size (what the rows are checked against) or STREAM_SIZE_UNKNOWN.  STREAM_NEED_MORE: no end_header yet, and more may come.
+int ply_v1_header(const uint8_t* data, size_t bytes, size_t file_bytes, uint32_t want_degree, PlyV1Header& h) {
     const std::string token = "end_header";
     const std::string head((const char*)data, bytes < (1u << 20) ? bytes : (1u << 20));
     const size_t tok = head.find(token);
+    if (tok == std::string::npos && bytes < (1u << 20) && bytes < file_bytes) return STREAM_NEED_MORE;
     GS_REQUIRE(tok != std::string::npos, "PLY: end_header not found");
     const size_t header_bytes = tok + token.size() + 1;                                // INRIAV1PlyParser.js:53
     // decodeSectionHeader: first `element` section only
@@ -257,8 +281,10 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
     if (cpc_d >= 3) degree = 1;
     if (cpc_d >= 8) degree = 2;
     const uint32_t out_degree = want_degree < degree ? want_degree : degree;
-    GS_REQUIRE(header_bytes + bytes_per_vertex * (size_t)vertex_count <= bytes, "PLY: vertex data exceeds the file");
-    PlyField F_scale[3], F_rot[4], F_pos[3], F_dc[3], F_op, F_rgb[3], F_rest0, F_d1[9], F_d2[15];
+    GS_REQUIRE(file_bytes == STREAM_SIZE_UNKNOWN || header_bytes + bytes_per_vertex * (size_t)vertex_count <= file_bytes,
+               "PLY: vertex data exceeds the file");
+    PlyField(&F_scale)[3] = h.scale, (&F_rot)[4] = h.rot, (&F_pos)[3] = h.pos, (&F_dc)[3] = h.dc, &F_op = h.op, (&F_rgb)[3] = h.rgb,
+            &F_rest0 = h.rest0, (&F_d1)[9] = h.d1, (&F_d2)[15] = h.d2;
     for (int k = 0; k < 3; k++) F_scale[k] = find("scale_" + std::to_string(k));
     for (int k = 0; k < 4; k++) F_rot[k] = find("rot_" + std::to_string(k));
     F_pos[0] = find("x"); F_pos[1] = find("y"); F_pos[2] = find("z");
@@ -277,7 +303,20 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
         if (degree >= 1) for (int i = 0; i < 3; i++) F_d1[3 * rgb + i] = find(rest_name(i + cpc_d * rgb));
         if (degree >= 2) for (int i = 0; i < 5; i++) F_d2[5 * rgb + i] = find(rest_name(i + cpc_d * rgb + 3));
     }
+    h.header_bytes = header_bytes;
+    h.bytes_per_vertex = bytes_per_vertex;
+    h.vertex_count = vertex_count;
+    h.out_degree = out_degree;
+    return GS_OK;
+}
 
+int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+    PlyV1Header h;
+    GS_TRY(ply_v1_header(data, bytes, bytes, want_degree, h));
+    const size_t header_bytes = h.header_bytes, bytes_per_vertex = h.bytes_per_vertex;
+    const uint32_t vertex_count = h.vertex_count, out_degree = h.out_degree;
+    const PlyField(&F_scale)[3] = h.scale, (&F_rot)[4] = h.rot, (&F_pos)[3] = h.pos, (&F_dc)[3] = h.dc, &F_op = h.op, (&F_rgb)[3] = h.rgb,
+                  &F_rest0 = h.rest0, (&F_d1)[9] = h.d1, (&F_d2)[15] = h.d2;
     const uint32_t ncomp = sh_components(out_degree), bps = 44u + 4u * ncomp;
     level0_header(a->buf, vertex_count, out_degree);
     uint8_t* B = a->buf.data() + KS_HEADER + KS_SECTION_HEADER;
@@ -336,61 +375,75 @@ int parse_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
 
 // What a host fill of a .splat / compressed PLY / .spz / INRIA-v2 PLY asset reads: every file row through the shared row arithmetic
 // (asset_internal.hpp) into the level-0 row the reference stores for it.  Built once, on the first fill.
+// the level-0 row (44 + 4 * ncomp bytes at o) of splat i of an asset that keeps file rows
+void level0_row_of(const gs_asset* a, uint32_t i, uint32_t ncomp, uint8_t* o) {
+    Level0Tuple t;
+    if (a->rows == ASSET_ROWS_SPLAT) {
+        uint32_t w[8];
+        memcpy(w, a->file.data() + 32 * (size_t)i, 32);
+        splat_row_tuple(w, t);
+    } else if (a->rows == ASSET_ROWS_SPZ) {
+        const SpzLayout& L = a->spz;
+        const uint8_t* f = a->file.data();
+        auto three = [&](int plane) {
+            const uint8_t* p = f + L.off[plane] + 3 * (size_t)i;
+            return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+        };
+        SpzRowBytes b;
+        const uint8_t* pp = f + L.off[SPZ_POSITIONS] + (size_t)L.pos_stride * i;
+        for (int k = 0; k < 3; k++)
+            b.pos[k] = L.pos_stride == 9u ? ((uint32_t)pp[3 * k] | ((uint32_t)pp[3 * k + 1] << 8) | ((uint32_t)pp[3 * k + 2] << 16))
+                                          : ((uint32_t)pp[2 * k] | ((uint32_t)pp[2 * k + 1] << 8));
+        b.alpha = f[L.off[SPZ_ALPHAS] + i];
+        b.colour = three(SPZ_COLOURS); b.scale = three(SPZ_SCALES); b.rotation = three(SPZ_ROTATIONS);
+        spz_row_tuple(L, b, t);
+        const uint8_t* sh = f + L.off[SPZ_SH] + 3 * (size_t)L.file_dim * i;
+        for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, spz_sh_value(sh[spz_sh_index(s)]));
+    } else if (a->rows == ASSET_ROWS_INRIA_V1) {
+        const uint8_t* row = a->file.data() + a->iv1_vertex_base + (size_t)a->iv1.stride * i;
+        inria_v1_row_tuple(row, a->iv1, t);
+        const bool has_sh = inria_v1_row_has_sh(row, a->iv1);
+        for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, inria_v1_row_sh(row, a->iv1, has_sh, s));
+    } else if (a->rows == ASSET_ROWS_INRIA_V2) {
+        const uint8_t* row = a->file.data() + a->iv2_vertex_base + (size_t)a->iv2.stride * i;
+        inria_v2_row_tuple(row, a->iv2, a->iv2_codebook.data(), t);
+        for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, inria_v2_row_sh(row, a->iv2, a->iv2_codebook.data(), s));
+    } else {
+        uint32_t w[4];
+        memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
+        pc_row_tuple(w, a->file.data() + a->pc_chunk_base + (size_t)a->pc.chunk_stride * (i / 256u), a->pc, t);
+        const uint8_t* sh = a->file.data() + a->pc_sh_base + (size_t)a->pc.sh_stride * i;
+        for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, pc_row_sh(sh, a->pc.read_coeff, s));
+    }
+    store_level0_row(o, t);
+}
+
 int build_level0_image(gs_asset* a) {
     if (a->rows == ASSET_ROWS_KSPLAT || !a->buf.empty()) return GS_OK;
     const uint32_t n = a->splat_count, degree = a->sh_degree, ncomp = sh_components(degree), bps = 44u + 4u * ncomp;
     level0_header(a->buf, n, degree);
     uint8_t* B = a->buf.data() + KS_HEADER + KS_SECTION_HEADER;
-    for (uint32_t i = 0; i < n; i++) {
-        Level0Tuple t;
-        uint8_t* o = B + (size_t)i * bps;
-        if (a->rows == ASSET_ROWS_SPLAT) {
-            uint32_t w[8];
-            memcpy(w, a->file.data() + 32 * (size_t)i, 32);
-            splat_row_tuple(w, t);
-        } else if (a->rows == ASSET_ROWS_SPZ) {
-            const SpzLayout& L = a->spz;
-            const uint8_t* f = a->file.data();
-            auto three = [&](int plane) {
-                const uint8_t* p = f + L.off[plane] + 3 * (size_t)i;
-                return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-            };
-            SpzRowBytes b;
-            const uint8_t* pp = f + L.off[SPZ_POSITIONS] + (size_t)L.pos_stride * i;
-            for (int k = 0; k < 3; k++)
-                b.pos[k] = L.pos_stride == 9u ? ((uint32_t)pp[3 * k] | ((uint32_t)pp[3 * k + 1] << 8) | ((uint32_t)pp[3 * k + 2] << 16))
-                                              : ((uint32_t)pp[2 * k] | ((uint32_t)pp[2 * k + 1] << 8));
-            b.alpha = f[L.off[SPZ_ALPHAS] + i];
-            b.colour = three(SPZ_COLOURS); b.scale = three(SPZ_SCALES); b.rotation = three(SPZ_ROTATIONS);
-            spz_row_tuple(L, b, t);
-            const uint8_t* sh = f + L.off[SPZ_SH] + 3 * (size_t)L.file_dim * i;
-            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, spz_sh_value(sh[spz_sh_index(s)]));
-        } else if (a->rows == ASSET_ROWS_INRIA_V2) {
-            const uint8_t* row = a->file.data() + a->iv2_vertex_base + (size_t)a->iv2.stride * i;
-            inria_v2_row_tuple(row, a->iv2, a->iv2_codebook.data(), t);
-            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, inria_v2_row_sh(row, a->iv2, a->iv2_codebook.data(), s));
-        } else {
-            uint32_t w[4];
-            memcpy(w, a->file.data() + a->pc_vertex_base + 16 * (size_t)i, 16);
-            pc_row_tuple(w, a->file.data() + a->pc_chunk_base + (size_t)a->pc.chunk_stride * (i / 256u), a->pc, t);
-            const uint8_t* sh = a->file.data() + a->pc_sh_base + (size_t)a->pc.sh_stride * i;
-            for (uint32_t s = 0; s < ncomp; s++) store_level0_sh(o, s, pc_row_sh(sh, a->pc.read_coeff, s));
-        }
-        store_level0_row(o, t);
-    }
+    for (uint32_t i = 0; i < n; i++) level0_row_of(a, i, ncomp, B + (size_t)i * bps);
     const int st = parse_ksplat(a);
     if (st != GS_OK) a->buf.clear();
     return st;
 }
 
-int parse_splat(gs_asset* a, const uint8_t* data, size_t bytes) {
+int check_splat_bytes(size_t bytes) {
     GS_REQUIRE(bytes % 32 == 0, ".splat: the byte count is not a multiple of the 32-byte row");
     GS_REQUIRE(bytes / 32 <= 0xFFFFFFFFull, ".splat: more than 2^32 - 1 rows");
-    a->file.assign(data, data + bytes);
+    return GS_OK;
+}
+void parse_splat_rows(gs_asset* a, size_t bytes) {           // `bytes` passed check_splat_bytes
     a->rows = ASSET_ROWS_SPLAT;
     a->splat_count = (uint32_t)(bytes / 32);
     a->level = 0;
     a->sh_degree = 0;
+}
+int parse_splat(gs_asset* a, const uint8_t* data, size_t bytes) {
+    GS_TRY(check_splat_bytes(bytes));
+    a->file.assign(data, data + bytes);
+    parse_splat_rows(a, bytes);
     return GS_OK;
 }
 
@@ -412,18 +465,25 @@ int parse_spz(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degr
 
 // PlyParserUtils.determineHeaderFormatFromHeaderText: every trimmed header line is looked at, the LAST match decides
 enum PlyFlavour { PLY_INRIA_V1, PLY_COMPRESSED, PLY_INRIA_V2 };
-PlyFlavour ply_flavour(const uint8_t* data, size_t bytes) {
+// settled (a stream asks): no byte that may still follow changes the answer - the end_header line is in, newline included, or the
+// 1 MiB that is looked at is.
+PlyFlavour ply_flavour(const uint8_t* data, size_t bytes, bool* settled = nullptr) {
     const std::string head((const char*)data, bytes < (1u << 20) ? bytes : (1u << 20));
     PlyFlavour f = PLY_INRIA_V1;
     size_t pos = 0;
+    if (settled) *settled = bytes >= (1u << 20);
     while (pos < head.size()) {
         size_t nl = head.find('\n', pos);
+        const bool ended = nl != std::string::npos;
         if (nl == std::string::npos) nl = head.size();
         const std::string line = trim(head.substr(pos, nl - pos));
         pos = nl + 1;
         if (line.rfind("element chunk", 0) == 0 || line.find("packed_") != std::string::npos) f = PLY_COMPRESSED;
         else if (line.rfind("element codebook_centers", 0) == 0) f = PLY_INRIA_V2;
-        else if (line == "end_header") break;
+        else if (line == "end_header") {
+            if (settled && ended) *settled = true;
+            break;
+        }
     }
     return f;
 }
@@ -432,10 +492,20 @@ PlyFlavour ply_flavour(const uint8_t* data, size_t bytes) {
 // the layout the row decode relies on is proven at open: chunk, vertex[, sh] in that order (readPly reads them in that order
 // whatever the header says), sixteen-byte vertex rows of the four packed uints, float extremes, one uchar per SH property,
 // enough chunks, and every element inside the file.
-int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+// What the header says (everything of the asset but the bytes).  `bytes` of `data` are present; file_bytes is the file's size (what
+// the elements are checked against) or STREAM_SIZE_UNKNOWN.  STREAM_NEED_MORE: the header's end is not among the bytes, and more
+// may come.
+struct PcHeader {
+    PcLayout layout;
+    size_t base[3];                // chunk, vertex, sh
+    bool has_sh;
+    uint32_t chunk_count, splat_count, degree;
+};
+int compressed_ply_header(const uint8_t* data, size_t bytes, size_t file_bytes, uint32_t want_degree, PcHeader& out) {
     static const char end_token[] = "\nend_header\n";
     GS_REQUIRE(bytes >= 4 && memcmp(data, "ply\n", 4) == 0, "compressed PLY: the file does not start with 'ply'");
     const uint8_t* e = std::search(data, data + bytes, (const uint8_t*)end_token, (const uint8_t*)end_token + 12);
+    if (e == data + bytes && bytes < file_bytes) return STREAM_NEED_MORE;
     GS_REQUIRE(e != data + bytes, "compressed PLY: end of header not found");
     const std::string text((const char*)data, (size_t)(e - data));
     const size_t header_bytes = (size_t)(e - data) + 12;
@@ -496,7 +566,8 @@ int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_
         if (k < 3) base[k] = off;
         const uint64_t need = elements[k].stride * elements[k].count;                  // < 2^32 * (8 * lines of a 2^40 header): no overflow
         GS_REQUIRE(elements[k].stride < (1ull << 24), "compressed PLY: an element row of 16 MiB or more");
-        GS_REQUIRE(need <= bytes - off, "compressed PLY: element data exceeds the file");
+        GS_REQUIRE(file_bytes == STREAM_SIZE_UNKNOWN || (off <= file_bytes && need <= file_bytes - off),
+                   "compressed PLY: element data exceeds the file");
         off += (size_t)need;
     }
     const uint64_t n = vertex.count;
@@ -546,16 +617,32 @@ int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_
     }
     uint32_t degree = want_degree < file_degree ? want_degree : file_degree;            // Math.min(out, file)
     if (degree > 2) degree = 2;                                                        // the level-0 row holds two bands
-    a->file.assign(data, data + bytes);
+    out.layout = L;
+    for (int k = 0; k < 3; k++) out.base[k] = base[k];
+    out.has_sh = sh != nullptr;
+    out.chunk_count = (uint32_t)chunk.count;
+    out.splat_count = (uint32_t)n;
+    out.degree = degree;
+    return GS_OK;
+}
+
+void adopt_compressed_ply(gs_asset* a, const PcHeader& h) {
     a->rows = ASSET_ROWS_COMPRESSED_PLY;
-    a->pc = L;
-    a->pc_chunk_base = base[0];
-    a->pc_vertex_base = base[1];
-    a->pc_sh_base = sh ? base[2] : 0;
-    a->pc_chunk_count = (uint32_t)chunk.count;
-    a->splat_count = (uint32_t)n;
+    a->pc = h.layout;
+    a->pc_chunk_base = h.base[0];
+    a->pc_vertex_base = h.base[1];
+    a->pc_sh_base = h.has_sh ? h.base[2] : 0;
+    a->pc_chunk_count = h.chunk_count;
+    a->splat_count = h.splat_count;
     a->level = 0;
-    a->sh_degree = degree;
+    a->sh_degree = h.degree;
+}
+
+int parse_compressed_ply(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want_degree) {
+    PcHeader h;
+    GS_TRY(compressed_ply_header(data, bytes, bytes, want_degree, h));
+    a->file.assign(data, data + bytes);
+    adopt_compressed_ply(a, h);
     return GS_OK;
 }
 
@@ -691,13 +778,129 @@ int parse_inria_v2(gs_asset* a, const uint8_t* data, size_t bytes, uint32_t want
         }
     }
     uint32_t degree = want_degree < file_degree ? want_degree : file_degree;           // Math.min(out, file) :203; the level-0 row holds two bands
-    a->file.assign(data, data + bytes);
+    if (data != a->file.data()) a->file.assign(data, data + bytes);                     // (a stream's bytes are there already)
     a->rows = ASSET_ROWS_INRIA_V2;
     a->iv2 = L;
     a->iv2_vertex_base = vertex->base;
     a->splat_count = (uint32_t)vertex->count;
     a->level = 0;
     a->sh_degree = degree;
+    return GS_OK;
+}
+
+// ---- streamed assets: gs_asset_open_stream / gs_asset_append (the byte counting is asset_stream.cpp) ---------------------------------
+// the one copy of the stream's bytes: the vector an opened asset of the format keeps its file in (.spz: the gzip member, apart)
+std::vector<uint8_t>& stream_bytes(gs_asset* a) {
+    const uint32_t format = a->stream->format;
+    return format == GS_ASSET_KSPLAT ? a->buf : (format == GS_ASSET_SPZ ? a->stream->raw : a->file);
+}
+
+// parse_ply's fields as the row arithmetic of both sides reads them (asset_internal.hpp)
+InriaV1Layout inria_v1_layout(const PlyV1Header& h) {
+    InriaV1Layout L = {};
+    L.stride = (uint32_t)h.bytes_per_vertex;
+    bool aligned = L.stride % 4u == 0;
+    auto field = [&](const PlyField& f) {
+        InriaV1Field o = {0, 0, 0};
+        uint8_t type;
+        switch (f.type) {
+            case T_FLOAT: type = IV1_FLOAT; break;
+            case T_INT: type = IV1_INT; break;
+            case T_UINT: type = IV1_UINT; break;
+            case T_SHORT: type = IV1_SHORT; break;
+            case T_USHORT: type = IV1_USHORT; break;
+            case T_UCHAR: type = IV1_UCHAR; break;
+            default: return o;                                                         // doubles are never read: as absent
+        }
+        if (!f.present) return o;
+        o = {(uint16_t)f.offset, type, 1};
+        if (type <= IV1_UINT && f.offset % 4 != 0) aligned = false;
+        return o;
+    };
+    for (int k = 0; k < 3; k++) { L.pos[k] = field(h.pos[k]); L.scale[k] = field(h.scale[k]); L.dc[k] = field(h.dc[k]); L.rgb[k] = field(h.rgb[k]); }
+    for (int k = 0; k < 4; k++) L.rot[k] = field(h.rot[k]);
+    L.opacity = field(h.op);
+    L.rest0 = field(h.rest0);
+    for (int k = 0; k < 9; k++) L.sh[k] = field(h.d1[k]);
+    for (int k = 0; k < 15; k++) L.sh[9 + k] = field(h.d2[k]);
+    L.aligned = aligned ? 1u : 0u;
+    return L;
+}
+
+// The bytes of an append are in: what the format's reader makes of the prefix (final: of the file).  < 0: the append is refused.
+int stream_step(gs_asset* a, bool final) {
+    AssetStream& s = *a->stream;
+    std::vector<uint8_t>& store = stream_bytes(a);
+    const uint8_t* data = store.data();
+    const size_t n = store.size(), file_bytes = final ? n : STREAM_SIZE_UNKNOWN;
+    size_t implied = 0;                                       // the file's size as the header implies it (0: not known)
+    const bool had_header = s.header_ready;
+    if (s.format == GS_ASSET_SPLAT) {
+        GS_REQUIRE(!final || n == s.expected_bytes, ".splat: the stream ended before expected_bytes had arrived");
+    } else if (s.format == GS_ASSET_KSPLAT) {
+        std::vector<StreamRun> runs;
+        const int st = parse_ksplat(a, false, &runs, &implied);
+        if (st < 0) return st;
+        if (st == STREAM_NEED_MORE) {
+            if (final) return parse_ksplat(a);                // too short for its headers: the whole-file reader's refusal
+        } else {
+            if (a->sh_degree > s.max_sh_degree) a->sh_degree = s.max_sh_degree;
+            s.header_ready = true;
+            s.splat_limit = a->splat_count;
+            s.runs.swap(runs);
+            GS_REQUIRE(!final || implied <= n, KS_DATA_EXCEEDS);
+        }
+    } else if (s.format == GS_ASSET_SPZ) {                    // a gzip member with a trailing CRC: nothing before the end
+        if (final) {
+            GS_TRY(parse_spz(a, data, n, s.max_sh_degree));
+            std::vector<uint8_t>().swap(s.raw);
+        }
+    } else if (!s.header_ready || final) {                    // PLY: the header, once it is in; again at the end, against the file's size
+        bool settled = false;
+        const PlyFlavour flavour = ply_flavour(data, n, &settled);
+        if (!settled && !final) {
+        } else if (flavour == PLY_INRIA_V2) {                 // the codebook may follow the rows: nothing before the end
+            if (final) GS_TRY(parse_inria_v2(a, data, n, s.max_sh_degree));
+        } else if (flavour == PLY_COMPRESSED) {
+            PcHeader h;
+            const int st = compressed_ply_header(data, n, file_bytes, s.max_sh_degree, h);
+            if (st < 0) return st;
+            if (st != STREAM_NEED_MORE) {
+                adopt_compressed_ply(a, h);
+                // a splat reads its vertex row, its chunk row and - above degree 0 - its SH row: the chunk element is the gate,
+                // and the SH element, which lies behind every vertex row, arrives last
+                const bool sh = h.degree > 0;
+                s.runs.assign(1, {(uint64_t)h.base[1], (uint64_t)(sh ? h.base[2] : h.base[1]), sh ? h.layout.sh_stride : 16u, 0u, h.splat_count});
+                implied = (h.has_sh ? h.base[2] + (size_t)h.layout.sh_stride * h.splat_count : h.base[1] + 16 * (size_t)h.splat_count);
+                s.header_ready = true;
+            }
+        } else {
+            PlyV1Header h;
+            const int st = ply_v1_header(data, n, file_bytes, s.max_sh_degree, h);
+            if (st < 0) return st;
+            if (st != STREAM_NEED_MORE) {
+                GS_REQUIRE(h.bytes_per_vertex < (1u << 16), "PLY: a vertex row of 64 KiB or more");
+                a->rows = ASSET_ROWS_INRIA_V1;
+                a->iv1 = inria_v1_layout(h);
+                a->iv1_vertex_base = h.header_bytes;
+                a->splat_count = h.vertex_count;
+                a->level = 0;
+                a->sh_degree = h.out_degree;
+                s.runs.assign(1, {(uint64_t)h.header_bytes, (uint64_t)h.header_bytes, (uint32_t)h.bytes_per_vertex, 0u, h.vertex_count});
+                implied = h.header_bytes + h.bytes_per_vertex * (size_t)h.vertex_count;
+                s.header_ready = true;
+            }
+        }
+        s.splat_limit = a->splat_count;
+    }
+    if (s.header_ready && !had_header && implied > store.capacity() && !final) {
+        try {
+            store.reserve(implied);                           // the size the header implies, now that it is known
+        } catch (const std::exception&) {                     // (a header may imply anything: the vector then grows as the bytes come)
+        }
+    }
+    if (final) s.finish(n, a->splat_count);
+    else s.advance(n);
     return GS_OK;
 }
 
@@ -759,8 +962,107 @@ int gs_asset_open(const void* data, uint64_t bytes, uint32_t format, uint32_t ma
 
 void gs_asset_close(gs_asset* a) { delete a; }
 
+int gs_asset_open_stream(uint32_t format, uint32_t max_sh_degree, uint64_t expected_bytes, gs_asset** out) {
+    GS_REQUIRE(out != nullptr, "out == NULL");
+    *out = nullptr;
+    GS_REQUIRE(format == GS_ASSET_PLY || format == GS_ASSET_KSPLAT || format == GS_ASSET_SPLAT || format == GS_ASSET_SPZ, "unknown asset format");
+    if (format == GS_ASSET_SPLAT) {
+        GS_REQUIRE(expected_bytes != 0, ".splat: a stream needs expected_bytes (the splat count comes from it)");
+        GS_TRY(check_splat_bytes((size_t)expected_bytes));
+    }
+    gs_asset* a = new (std::nothrow) gs_asset();
+    if (!a) return GS_ERR_NOMEM;
+    try {
+        a->stream.reset(new AssetStream());
+        AssetStream& s = *a->stream;
+        s.format = format;
+        s.max_sh_degree = max_sh_degree;
+        s.expected_bytes = expected_bytes;
+        stream_bytes(a).reserve((size_t)expected_bytes);
+        if (format == GS_ASSET_SPLAT) {                       // no header: everything is known now
+            s.bounded = true;
+            parse_splat_rows(a, (size_t)expected_bytes);
+            s.header_ready = true;
+            s.splat_limit = a->splat_count;
+            s.runs.push_back({0, 0, 32u, 0u, a->splat_count});
+        }
+    } catch (const std::exception&) {                         // bad_alloc, length_error
+        delete a;
+        gs_set_error("out of host memory while reserving the stream's bytes");
+        return GS_ERR_NOMEM;
+    }
+    *out = a;
+    return GS_OK;
+}
+
+int gs_asset_append(gs_asset* a, const void* data, uint64_t bytes, int final) {
+    GS_REQUIRE(a != nullptr, "asset == NULL");
+    GS_REQUIRE(a->stream != nullptr, "the asset is no stream (gs_asset_open_stream opens one)");
+    GS_REQUIRE(data || bytes == 0, "data == NULL");
+    AssetStream& s = *a->stream;
+    const char* refusal = s.admit(bytes);
+    if (refusal) {
+        s.refuse();
+        GS_REQUIRE(false, refusal);
+    }
+    std::vector<uint8_t>& store = stream_bytes(a);
+    const size_t before = store.size();
+    int st;
+    try {
+        store.insert(store.end(), (const uint8_t*)data, (const uint8_t*)data + bytes);
+        st = stream_step(a, final != 0);
+    } catch (const std::bad_alloc&) {
+        gs_set_error("out of host memory while reading the stream");
+        st = GS_ERR_NOMEM;
+    }
+    if (st < 0) {
+        store.resize(before);                                 // nothing of a refused append is consumed
+        s.refuse();
+        return st;
+    }
+    return GS_OK;
+}
+
+int gs_asset_get_stream_info(gs_asset* a, gs_asset_stream_info* info) {
+    GS_REQUIRE(a && info, "asset / info == NULL");
+    GS_REQUIRE(a->stream != nullptr, "the asset is no stream (gs_asset_open_stream opens one)");
+    const AssetStream& s = *a->stream;
+    info->bytes_received = s.bytes_received;
+    info->header_ready = s.header_ready;
+    info->splats_ready = s.splats_ready;
+    info->complete = s.complete;
+    info->failed = s.failed;
+    return GS_OK;
+}
+
+// Debug entry for the tests (pure host; not in the public header): splat `splat` of the READY prefix as the host reads it out of
+// the bytes that have arrived - the level-0 row (44 + 4 * ncomp bytes) an asset of file rows decodes it to, or, for a .ksplat image,
+// the float centre (through the bucket tables) followed by the rest of the file row.  out holds GS_DEBUG_ASSET_ROW_BYTES (140: a
+// level-0 row of degree 2, the longest of either kind); *bytes says how many were written.
+int gs_debug_asset_row(gs_asset* a, uint32_t splat, void* out, uint32_t* bytes) {
+    GS_REQUIRE(a && out && bytes, "asset / out / bytes == NULL");
+    GS_REQUIRE(splat < a->ready(), "the splat is not ready");
+    uint8_t* o = (uint8_t*)out;
+    if (a->rows != ASSET_ROWS_KSPLAT) {
+        const uint32_t ncomp = sh_components(a->sh_degree);
+        level0_row_of(a, splat, ncomp, o);
+        *bytes = 44u + 4u * ncomp;
+        return GS_OK;
+    }
+    const KsplatSource image = a->image();
+    const KsplatSource::Row row = image.row(splat);
+    double d[3];
+    row.centre(d);
+    for (int k = 0; k < 3; k++) { const float c = (float)d[k]; memcpy(o + 4 * k, &c, 4); }
+    const uint32_t rest = row.sec.bytes_per_splat - asset_center_bytes(a->level);
+    memcpy(o + 12, row.srow(), rest);
+    *bytes = 12u + rest;
+    return GS_OK;
+}
+
 int gs_asset_get_info(gs_asset* a, gs_asset_info* info) {
     GS_REQUIRE(a && info, "asset / info == NULL");
+    GS_REQUIRE(!a->stream || a->stream->header_ready, "the stream's header has not arrived (gs_asset_stream_info.header_ready)");
     info->splat_count = a->splat_count;
     info->sh_degree = a->sh_degree;
     info->compression_level = a->level;
@@ -774,6 +1076,7 @@ int gs_asset_get_info(gs_asset* a, gs_asset_info* info) {
 int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba,
                   uint16_t* sh_f16, uint8_t* sh_u8, float* scales, float* rotations) {
     GS_REQUIRE(a != nullptr, "asset == NULL");
+    GS_REQUIRE(!a->incomplete(), "the stream is not complete: gs_asset_fill reads the whole file (uploads take the ready prefix)");
     GS_REQUIRE(!(sh_f16 && sh_u8), "pass sh_f16 (compression level <= 1) or sh_u8 (level 2), not both");
     GS_REQUIRE(!sh_u8 || a->level == 2, "sh_u8 output needs a compression level 2 file (SplatMesh.js:1064-1066)");
     GS_REQUIRE(!sh_f16 || a->level <= 1, "a level 2 file keeps its SH as uint8: ask for sh_u8");

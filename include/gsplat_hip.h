@@ -335,6 +335,51 @@ int gs_asset_set_transform(gs_asset* a, const double* transform16);
 int gs_asset_fill(gs_asset* a, uint32_t min_alpha, float* centers, float* cov_f32, uint16_t* cov_f16, uint8_t* rgba,
                   uint16_t* sh_f16, uint8_t* sh_u8, float* scales, float* rotations);
 
+/* STREAMED ASSETS: a file handed over as it arrives (the reference's progressive loading: PlyLoader / SplatLoader / KSplatLoader
+ * build the scene section by section while the file downloads).  gs_asset_open_stream opens an asset without bytes,
+ * gs_asset_append hands it the next piece, and after every append gs_mesh_upload_asset / gs_sorter_upload_asset_centers take
+ * any range of the splats that are ready - the file's rows cross to the device and are decoded there, as for an opened asset.
+ *   M (whole file)  once the final append is accepted the stream IS the asset gs_asset_open returns for the concatenated bytes,
+ *                   in gs_asset_get_info, gs_asset_fill, gs_asset_set_transform, gs_mesh_upload_asset,
+ *                   gs_sorter_upload_asset_centers and gs_asset_encode_ksplat.  Where gs_asset_open would refuse the
+ *                   concatenation, the append that makes that certain is refused with gs_asset_open's message: a header fault at
+ *                   the append that completes the header; "data exceeds the file" and the .spz container checks at `final`.
+ *                   (A file with two faults: the stream names the one that is certain first - it cannot know where the file ends
+ *                   before `final` - where gs_asset_open names the one it meets first.)
+ *                   One exception: a streamed INRIA-v1 PLY keeps the file's own rows and decodes them with the e^x of the
+ *                   other row formats (the fdlibm text JavaScript engines run) where gs_asset_open calls the C library's; after
+ *                   the fp32 store of a scale and the floor(. * 255) of an opacity the two agree except on rare boundary inputs.
+ *                   A NaN its quaternion arithmetic generates is stored as the canonical quiet NaN.  A row of 64 KiB or more is
+ *                   refused.
+ *   P (prefix)      at any moment the ready splats are a prefix [0, splats_ready) of the whole file's numbering; splats_ready
+ *                   never decreases; an upload of a range inside the prefix leaves what the same call on the whole-file asset
+ *                   leaves; a range beyond it is GS_ERR_INVALID and nothing changes.
+ * A splat is ready when every byte its decode reads has arrived:
+ *   INRIA-v1 PLY    row by row behind the header (which may arrive split anywhere); no end_header within the first 1 MiB: refused
+ *   compressed PLY  nothing until the chunk element is complete, then vertex row by vertex row; with an output SH degree above 0
+ *                   a splat also needs its SH row, in practice the end of the file - open at degree 0 for early splats
+ *                   (the reference's own rule, PlyLoader.js:120-125)
+ *   .splat          floor(received / 32); expected_bytes is required (the splat count comes from it: the reference needs the
+ *                   content length) and bytes beyond it are refused
+ *   .ksplat         nothing until the header and every section header are in; a section's rows row by row once its bucket
+ *                   block (partial lengths and centres) has arrived and passed the table checks; sections in file order
+ *   .spz, INRIA-v2  0 until the final append, then all (a gzip member ends in its CRC; the codebook may follow the rows)
+ * expected_bytes (0 = not known) is reserved up front; the stream keeps one copy of the bytes.  Until the stream is complete
+ * gs_asset_fill and gs_asset_encode_ksplat are GS_ERR_INVALID, and gs_asset_get_info is until header_ready.  A refused append
+ * consumes nothing and sets `failed`: the ready rows stay uploadable, every later append is refused.  An empty append is fine; an
+ * append after `complete` is refused.  NO LOCK: the appends and uploads of one asset come from one thread, or the caller
+ * serialises them. */
+int gs_asset_open_stream(uint32_t format, uint32_t max_sh_degree, uint64_t expected_bytes, gs_asset** out);
+int gs_asset_append(gs_asset* a, const void* data, uint64_t bytes, int final);
+typedef struct gs_asset_stream_info {
+    uint64_t bytes_received;
+    uint32_t header_ready;   /* gs_asset_get_info answers (splat_count, sh_degree, levels, ...) */
+    uint32_t splats_ready;   /* the rows [0, splats_ready) can be uploaded now */
+    uint32_t complete;       /* the final append was accepted */
+    uint32_t failed;         /* an append was refused: no further append is taken */
+} gs_asset_stream_info;
+int gs_asset_get_stream_info(gs_asset* a, gs_asset_stream_info* info);
+
 /* The reference's offline conversion (util/create-ksplat.js, KSplatLoader.downloadFile) on the device: an opened asset ->
  * a one-section .ksplat at compression level 0, 1 or 2.  The file is byte for byte what
  * SplatBuffer.generateFromUncompressedSplatArrays([rows], min_alpha, compression_level, scene_center, block_size,

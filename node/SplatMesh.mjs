@@ -22,7 +22,7 @@
 import * as THREE from 'three';
 import { createRequire } from 'module';
 const require = createRequire(import.meta.url);
-const { SplatMeshHIP: HipMeshCore, addon } = require('./gsplat.js');
+const { SplatMeshHIP: HipMeshCore, addon, assetAppend } = require('./gsplat.js');
 import { VisibleRegion, SceneRevealMode } from './VisibleRegion.mjs';
 
 export const SplatRenderMode = { ThreeD: 0, TwoD: 1 };
@@ -49,6 +49,39 @@ class HipSplatScene {
   updateTransform() {                                       // :28-36 (a scene has no parent here: matrixWorld == matrix)
     this.matrix.compose(this.position, this.quaternion, this.scale);
     this.transform.copy(this.matrix);
+  }
+}
+
+// The splat-buffer face of a streamed asset (gsplat.js assetStreamOpen) for buildFromStream: the counts and header values build()
+// asks a reference SplatBuffer for.  Its rows never exist on the host while it loads - the mesh and the sort worker take them from
+// the stream on the device; the two fills the splat tree of the final build reads come from gs_asset_fill of the completed stream.
+export class StreamedSplatBuffer {
+  constructor(stream) { this.assetStream = stream; this._filled = null; }
+  getSplatCount() { return this.assetStream.info.splatsReady; }
+  getMaxSplatCount() { return this.assetStream.info.splatCount; }
+  getMinSphericalHarmonicsDegree() { return this.assetStream.info.shDegree; }
+  get compressionLevel() { return this.assetStream.info.compressionLevel; }
+  get sceneCenter() { return new THREE.Vector3().fromArray(this.assetStream.info.sceneCenter); }
+  get minSphericalHarmonicsCoeff() { return this.assetStream.info.shMin; }
+  get maxSphericalHarmonicsCoeff() { return this.assetStream.info.shMax; }
+  _fill() {
+    if (!this.assetStream.info.complete) throw new Error('StreamedSplatBuffer: the host fills need the complete stream');
+    return this._filled || (this._filled = addon.assetLoad(this.assetStream.handle, 0, 0, 0, 0));
+  }
+  fillSplatCenterArray(out, transform, from = 0, to = this.getSplatCount() - 1, dest = 0) {     // SplatBuffer.js:332-345
+    const c = this._fill().centers, v = new THREE.Vector3();
+    for (let i = from; i <= to; i++) {
+      v.set(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+      if (transform) v.applyMatrix4(transform);
+      out[3 * (i - from + dest)] = v.x; out[3 * (i - from + dest) + 1] = v.y; out[3 * (i - from + dest) + 2] = v.z;
+    }
+  }
+  fillSplatColorArray(out, minimumAlpha, from = 0, to = this.getSplatCount() - 1, dest = 0) {    // :551-575
+    const c = this._fill().rgba;
+    for (let i = from; i <= to; i++) {
+      const o = 4 * (i - from + dest);
+      out[o] = c[4 * i]; out[o + 1] = c[4 * i + 1]; out[o + 2] = c[4 * i + 2]; out[o + 3] = c[4 * i + 3] >= minimumAlpha ? c[4 * i + 3] : 0;
+    }
   }
 }
 
@@ -153,6 +186,31 @@ export class SplatMesh {
     return update;
   }
 
+  // HIP-engine extra, next to the progressive path above (which it does not replace): the next piece of a streamed file
+  // (gsplat.js assetStreamOpen) as an update build.  The piece is appended; the splats it made ready, [last ready, ready), go to the
+  // mesh inside build() - the file's rows cross the bus and are decoded on the device (gs_mesh_upload_asset), nothing is filled
+  // on the host - and to `sortWorker` as its `centers` message (gs_sorter_upload_asset_centers).  Before the header is in there
+  // is nothing to build: returns null.  Else build()'s reply without `centers`.  final: the last piece; the build is the final
+  // build (foldRunsAtFinalBuild and the splat tree as ever).
+  buildFromStream(stream, bytes, final = false, sortWorker = null, sceneOptions = [{}]) {
+    assetAppend(stream, bytes, final);
+    if (!stream.info.headerReady) return null;
+    if (!stream.splatBuffer) stream.splatBuffer = new StreamedSplatBuffer(stream);
+    const update = this.build([stream.splatBuffer], sceneOptions, true, final);
+    if (sortWorker && update.count > 0) {
+      sortWorker.uploadAssetCenters(stream.handle, stream.format, stream.maxShDegree, update.from, update.from, update.count,
+                                    this.dynamicMode ? new Uint32Array(update.count) : null, this._streamTransform());
+    }
+    return update;
+  }
+  // what fillSplatDataArrays hands the fills of the one scene: its transform in static mode (the identity too), none in dynamic mode
+  _streamTransform() {
+    if (this.dynamicMode) return null;
+    const matrix = new THREE.Matrix4();
+    this.getSceneTransform(0, matrix);
+    return Array.from(matrix.elements);
+  }
+
   // HIP-engine extra: a progressive load uploads every section [lastBuildSplatCount, now) as it arrives, and each upload is a
   // Morton run of its own whose 256-splat storage blocks span the scene (a trainer writes its rows in no spatial order), so the
   // vertex stage's block cull rejects nothing.  This folds every scene's getMaxSplatCount() span that holds more than one run into
@@ -231,10 +289,14 @@ export class SplatMesh {
   getTargetCovarianceCompressionLevel() { return this.halfPrecisionCovariancesOnGPU ? 1 : 0; }
   getTargetSphericalHarmonicsCompressionLevel() { return Math.max(1, this.getMaximumSplatBufferCompressionLevel()); }
 
+  // the stream behind the mesh's one scene (buildFromStream), or null
+  _stream() { return this.scenes.length === 1 && this.scenes[0].splatBuffer.assetStream ? this.scenes[0].splatBuffer.assetStream : null; }
+
   // what the sort worker needs about the freshly uploaded range (the reply shape of :588-609)
   refreshGPUDataFromSplatBuffers(sinceLastBuildOnly) {
     const last = this.getSplatCount(true) - 1, first = sinceLastBuildOnly ? this.lastBuildSplatCount : 0;
     this.refreshDataTexturesFromSplatBuffers(sinceLastBuildOnly);
+    if (this._stream()) return { from: first, to: last, count: last - first + 1, centers: null, sceneIndexes: this.getSceneIndexes(first, last) };
     return Object.assign({ from: first, to: last, count: last - first + 1 }, this.getDataForDistancesComputation(first, last));
   }
 
@@ -261,6 +323,16 @@ export class SplatMesh {
     }
     const count = toSplat - fromSplat + 1;
     if (count <= 0) { this.updateVisibleRegion(sinceLastBuildOnly); return; }
+    const stream = this._stream();
+    if (stream) {                                           // the rows go up as the file holds them and are decoded on the device
+      addon.meshUploadAsset(this.core.handle, fromSplat, stream.handle, stream.format, stream.maxShDegree, fromSplat, count,
+                            this.scenes[0].minimumAlpha, this._streamTransform());
+      this.core.splatCount = Math.max(this.core.splatCount, fromSplat + count);
+      if (this.dynamicMode || this.enableOptionalEffects) this.core.setSceneIndexes(new Uint32Array(count), fromSplat);
+      this._scenesDirty = true;
+      this.updateVisibleRegion(sinceLastBuildOnly);
+      return;
+    }
     const covLevel = this.getTargetCovarianceCompressionLevel();
     const covariances = covLevel === 1 ? new Uint16Array(count * 6) : new Float32Array(count * 6);
     const centers = new Float32Array(count * 3);

@@ -430,6 +430,22 @@ const assetFormatOf = (fileName, bytes) => {
   if (/\.spz$/i.test(fileName) || (bytes[0] === 0x1f && bytes[1] === 0x8b)) return AssetFormat.spz;
   return bytes[0] === 0x70 && bytes[1] === 0x6c && bytes[2] === 0x79 ? AssetFormat.ply : AssetFormat.ksplat;      // "ply"
 };
+// A file handed over as it arrives (gs_asset_open_stream): the reference's progressive loading without a host decode.
+// assetStreamOpen(format, maxShDegree, expectedBytes) -> stream; assetAppend(stream, bytes, final) hands it the next piece and
+// returns assetStreamInfo(stream) = {bytesReceived, headerReady, splatsReady, complete, failed} plus, once headerReady, the asset's
+// {splatCount, shDegree, compressionLevel, shLevel, shMin, shMax, sceneCenter}.  The ready splats are a prefix of the file's numbering
+// that never shrinks: buildFromAsset / uploadAssetCenters take stream.handle where they take a file's bytes, for any range inside it.
+// AssetFormat.splat needs expectedBytes (the splat count comes from it).  A refused append throws and ends the stream; what was
+// ready stays uploadable.  assetStreamClose(stream) frees it.
+function assetStreamOpen(format, maxShDegree = 2, expectedBytes = 0) {
+  const stream = { handle: addon.assetStreamOpen(format, maxShDegree, expectedBytes), format, maxShDegree };
+  stream.info = addon.assetStreamInfo(stream.handle);
+  return stream;
+}
+function assetAppend(stream, bytes, final = false) { return (stream.info = addon.assetAppend(stream.handle, bytes, final ? 1 : 0)); }
+function assetStreamInfo(stream) { return (stream.info = addon.assetStreamInfo(stream.handle)); }
+function assetStreamClose(stream) { if (stream.handle) { addon.assetStreamClose(stream.handle); stream.handle = null; } }
+
 // util/create-ksplat.js's conversion on the device (gs_asset_encode_ksplat): asset = { bytes, format (AssetFormat; default: from the
 // bytes), sphericalHarmonicsDegree (the degree the file is read at) }; options named as the tool's: compressionLevel (0),
 // splatAlphaRemovalThreshold (1), sceneCenter ([0, 0, 0]), blockSize (5.0), bucketSize (256), outSphericalHarmonicsDegree (the
@@ -445,4 +461,4 @@ function encodeKsplat(asset, options = {}) {
                                  or(options.compressionLevel, 0), or(options.splatAlphaRemovalThreshold, 1), or(options.bucketSize, 256),
                                  or(options.blockSize, 5.0), +centre[0], +centre[1], +centre[2]);
 }
-module.exports = { encodeKsplat, createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon, multiply4, invert4 };
+module.exports = { assetStreamOpen, assetAppend, assetStreamInfo, assetStreamClose, encodeKsplat, createSortWorker, SplatMeshHIP, StripGroup, toHalfFloat, Constants, AssetFormat, assetFormatOf, addon, multiply4, invert4 };

@@ -878,14 +878,18 @@ static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     ARGS(5)
     void* data;
     size_t nb;
-    if (!get_bytes(env, argv[0], &data, &nb) || !data) { napi_throw_type_error(env, NULL, "assetLoad: bytes"); return NULL; }
-    gs_asset* a = NULL;
-    int st;
+    napi_valuetype source = napi_undefined;
+    napi_typeof(env, argv[0], &source);
+    const int streamed = source == napi_external;            /* a COMPLETE assetStreamOpen handle in place of the bytes (it stays open) */
+    if (!streamed && (!get_bytes(env, argv[0], &data, &nb) || !data)) { napi_throw_type_error(env, NULL, "assetLoad: bytes"); return NULL; }
+    gs_asset* a = streamed ? (gs_asset*)get_external(env, argv[0]) : NULL;
+    int st = GS_OK;
 
-    LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[1]), get_u32(env, argv[2]), &a));
+    if (!streamed) LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[1]), get_u32(env, argv[2]), &a));
     if (st < 0) return throw_gs(env, st);
+    if (streamed) LOCKED(gs_asset_set_transform(a, NULL));  /* the arrays of the file, as for bytes (an upload sets its own transform) */
     gs_asset_info ai;
-    gs_asset_get_info(a, &ai);
+    if (gs_asset_get_info(a, &ai) < 0) return throw_gs(env, GS_ERR_INVALID);
     const uint32_t n = ai.splat_count, ncoef = ai.sh_degree == 0 ? 0 : (ai.sh_degree == 1 ? 9 : 24);
     const uint32_t half = get_u32(env, argv[4]);
     napi_value r, ab, ta;
@@ -900,7 +904,7 @@ static napi_value AssetLoad(napi_env env, napi_callback_info info) {
     }
     LOCKED(st = gs_asset_fill(a, get_u32(env, argv[3]), (float*)centers, half ? NULL : (float*)cov, half ? (uint16_t*)cov : NULL, (uint8_t*)rgba,
                        (ncoef && ai.sh_level != 2) ? (uint16_t*)sh : NULL, (ncoef && ai.sh_level == 2) ? (uint8_t*)sh : NULL, NULL, NULL));
-    LOCKED(gs_asset_close(a));
+    if (!streamed) LOCKED(gs_asset_close(a));
     if (st < 0) return throw_gs(env, st);
     set(env, r, "splatCount", n);
     set(env, r, "shDegree", ai.sh_degree);
@@ -944,36 +948,108 @@ static napi_value upload_asset(napi_env env, napi_callback_info info, int to_sor
             have_transform = 1;
         }
     }
-    void *data, *sc = NULL;
-    size_t nb, sb = 0;
-    if (!get_bytes(env, argv[2], &data, &nb) || !data) { napi_throw_type_error(env, NULL, "asset bytes"); return NULL; }
+    void *data = NULL, *sc = NULL;
+    size_t nb = 0, sb = 0;
+    napi_valuetype source = napi_undefined;
+    napi_typeof(env, argv[2], &source);
+    const int streamed = source == napi_external;            /* an assetStreamOpen handle in place of the bytes: format / maxShDegree are its own */
+    if (!streamed && (!get_bytes(env, argv[2], &data, &nb) || !data)) { napi_throw_type_error(env, NULL, "asset bytes"); return NULL; }
     if (to_sorter && !get_bytes(env, argv[7], &sc, &sb)) { napi_throw_type_error(env, NULL, "sceneIndexes"); return NULL; }
-    gs_asset* a = NULL;
-    int st;
-    LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[3]), get_u32(env, argv[4]), &a));
+    gs_asset* a = streamed ? (gs_asset*)get_external(env, argv[2]) : NULL;
+    int st = GS_OK;
+    if (!streamed) LOCKED(st = gs_asset_open(data, nb, get_u32(env, argv[3]), get_u32(env, argv[4]), &a));
     if (st < 0) return throw_gs(env, st);
-    if (have_transform) {
-        LOCKED(st = gs_asset_set_transform(a, transform));
+    if (have_transform || streamed) {                        /* (a stream keeps what it was given: every call says what it wants) */
+        LOCKED(st = gs_asset_set_transform(a, have_transform ? transform : NULL));
         if (st < 0) {
-            LOCKED(gs_asset_close(a));
+            if (!streamed) LOCKED(gs_asset_close(a));
             return throw_gs(env, st);
         }
     }
-    gs_asset_info ai;
-    gs_asset_get_info(a, &ai);
     const uint32_t from = get_u32(env, argv[1]), first = get_u32(env, argv[5]);
-    uint32_t count = get_u32(env, argv[6]);
-    if (count == 0xFFFFFFFFu) count = first <= ai.splat_count ? ai.splat_count - first : 0;
+    uint32_t count = get_u32(env, argv[6]), have = 0;
+    if (streamed) {                                          /* every splat from `first` on: of the ready prefix */
+        gs_asset_stream_info si;
+        if (gs_asset_get_stream_info(a, &si) < 0) return throw_gs(env, GS_ERR_INVALID);
+        have = si.splats_ready;
+    } else {
+        gs_asset_info ai;
+        gs_asset_get_info(a, &ai);
+        have = ai.splat_count;
+    }
+    if (count == 0xFFFFFFFFu) count = first <= have ? have - first : 0;
     if (sc && sb < (size_t)count * 4) {
-        LOCKED(gs_asset_close(a));
+        if (!streamed) LOCKED(gs_asset_close(a));
         napi_throw_range_error(env, NULL, "sceneIndexes shorter than count");
         return NULL;
     }
     if (to_sorter) { LOCKED(st = gs_sorter_upload_asset_centers((gs_sorter*)get_external(env, argv[0]), from, a, first, count, (const uint32_t*)sc)); }
     else { LOCKED(st = gs_mesh_upload_asset((gs_mesh*)get_external(env, argv[0]), from, a, first, count, get_u32(env, argv[7]))); }
-    LOCKED(gs_asset_close(a));
+    if (!streamed) LOCKED(gs_asset_close(a));
     if (st < 0) return throw_gs(env, st);
     return num(env, count);
+}
+
+/* Streamed assets (gs_asset_open_stream / gs_asset_append / gs_asset_get_stream_info): a file handed over as it arrives.
+ * assetStreamOpen(format, maxShDegree, expectedBytes) -> handle; assetAppend(handle, bytes, final) -> assetStreamInfo(handle);
+ * assetStreamInfo(handle) -> {bytesReceived, headerReady, splatsReady, complete, failed} and, once headerReady, the asset's
+ * {splatCount, shDegree, compressionLevel, shLevel, shMin, shMax, sceneCenter}; assetStreamClose(handle).  meshUploadAsset and
+ * sorterUploadAssetCenters take the handle where they take a file's bytes, for any range of the ready prefix. */
+static napi_value stream_info_of(napi_env env, gs_asset* a) {
+    gs_asset_stream_info si;
+    if (gs_asset_get_stream_info(a, &si) < 0) return throw_gs(env, GS_ERR_INVALID);
+    napi_value r;
+    NAPI_OK(napi_create_object(env, &r));
+    set(env, r, "bytesReceived", (double)si.bytes_received);
+    set(env, r, "headerReady", si.header_ready);
+    set(env, r, "splatsReady", si.splats_ready);
+    set(env, r, "complete", si.complete);
+    set(env, r, "failed", si.failed);
+    gs_asset_info ai;
+    if (si.header_ready && gs_asset_get_info(a, &ai) == GS_OK) {
+        set(env, r, "splatCount", ai.splat_count);
+        set(env, r, "shDegree", ai.sh_degree);
+        set(env, r, "compressionLevel", ai.compression_level);
+        set(env, r, "shLevel", ai.sh_level);
+        set(env, r, "shMin", ai.sh_min);
+        set(env, r, "shMax", ai.sh_max);
+        napi_value centre;
+        NAPI_OK(napi_create_array_with_length(env, 3, &centre));
+        for (uint32_t k = 0; k < 3; k++) napi_set_element(env, centre, k, num(env, ai.scene_center[k]));
+        napi_set_named_property(env, r, "sceneCenter", centre);
+    }
+    return r;
+}
+static napi_value AssetStreamOpen(napi_env env, napi_callback_info info) {
+    ARGS(3)
+    gs_asset* a = NULL;
+    int st;
+    LOCKED(st = gs_asset_open_stream(get_u32(env, argv[0]), get_u32(env, argv[1]), (uint64_t)get_f64(env, argv[2]), &a));
+    if (st < 0) return throw_gs(env, st);
+    napi_value r;
+    NAPI_OK(napi_create_external(env, a, NULL, NULL, &r));
+    return r;
+}
+static napi_value AssetAppend(napi_env env, napi_callback_info info) {
+    ARGS(3)
+    void* data;
+    size_t nb;
+    if (!get_bytes(env, argv[1], &data, &nb)) { napi_throw_type_error(env, NULL, "assetAppend: bytes"); return NULL; }
+    gs_asset* a = (gs_asset*)get_external(env, argv[0]);
+    static const char none = 0;
+    int st;
+    LOCKED(st = gs_asset_append(a, data ? data : (const void*)&none, data ? nb : 0, get_u32(env, argv[2]) != 0));
+    if (st < 0) return throw_gs(env, st);
+    return stream_info_of(env, a);
+}
+static napi_value AssetStreamInfo(napi_env env, napi_callback_info info) {
+    ARGS(1)
+    return stream_info_of(env, (gs_asset*)get_external(env, argv[0]));
+}
+static napi_value AssetStreamClose(napi_env env, napi_callback_info info) {
+    ARGS(1)
+    LOCKED(gs_asset_close((gs_asset*)get_external(env, argv[0])));
+    return NULL;
 }
 static napi_value MeshUploadAsset(napi_env env, napi_callback_info info) { return upload_asset(env, info, 0); }
 static napi_value SorterUploadAssetCenters(napi_env env, napi_callback_info info) { return upload_asset(env, info, 1); }
@@ -1108,6 +1184,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
         {"meshUploadAsset", MeshUploadAsset}, {"sorterUploadAssetCenters", SorterUploadAssetCenters},
+        {"assetStreamOpen", AssetStreamOpen}, {"assetAppend", AssetAppend}, {"assetStreamInfo", AssetStreamInfo}, {"assetStreamClose", AssetStreamClose},
         {"meshSurface", MeshSurface},       {"meshBounds", MeshBounds},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

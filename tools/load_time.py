@@ -1,8 +1,14 @@
 """Load time of a scene file, file bytes -> a synchronised device, both paths in one process:
     python tools/load_time.py [--n 5800000] [--file NAME] [--format ksplat|ply|splat|compressed-ply|spz|inria-v2] [--sh-degree 0..3]
-                              [--repeats 5] [--transform identity | 16 numbers] [--out profiles/<tag>_load_time.txt]
+                              [--repeats 5] [--transform identity | 16 numbers] [--stream] [--out profiles/<tag>_load_time.txt]
   host    gs_asset_fill -> gs_mesh_upload (+ gs_mesh_upload_sh_u8) -> util.integer_centers -> gs_sorter_upload_centers
   device  gs_mesh_upload_asset + gs_sorter_upload_asset_centers (the per-splat decode on the card, csrc/asset_decode.hip)
+  --stream adds the streamed reader (gs_asset_open_stream): the file is fed in 256 KiB appends (Constants.ProgressiveLoadSectionSize)
+  and the rows that became ready are uploaded to a fresh mesh and sorter
+    stream/1   after every append          stream/16  after every 16th append (and the last)
+  timed from the first append to a synchronised device: the appends' copies and header work, every upload's staging, decode and
+  Morton run.  The bytes are in memory, so this is the cost the loader adds to a download, not a download.  Printed beside the two
+  whole-file paths, which it leaves as they are.
 The file: $GS_DATA_DIR/<--file> when given (a name ending in .splat is one), else a seeded file of --n splats (the C3 count
 by default) in --format, from the writers of gaussiansplats3d_amd.assets: a level-2 SH-2 .ksplat (the default), an INRIA-v1
 PLY, a .splat, a PlayCanvas compressed PLY, a version-2 .spz or an INRIA-v2 codebook PLY with --sh-degree bands.  For .splat /
@@ -23,6 +29,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gaussiansplats3d_amd import Context, SplatMesh, assets, create_sort_worker, util
 from gaussiansplats3d_amd import _lib as L
+
+
+STREAM_APPEND = 262_144                                    # Constants.ProgressiveLoadSectionSize
 
 
 def seeded_file(n):
@@ -69,6 +78,7 @@ def main():
     ap.add_argument("--file", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--transform", nargs="+", default=None, metavar="M", help="`identity` or the 16 elements, column-major")
+    ap.add_argument("--stream", action="store_true", help="also time the streamed reader: 256 KiB appends, uploads after every append and every 16th")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     transform = None
@@ -121,9 +131,32 @@ def main():
         if file_rows:
             a.close()
 
-    times = {"host": [], "device": []}
+    stream_fmt = fmt or ("ply" if data[:3] == b"ply" else "ksplat")
+    uploads = {}
+
+    def streamed(every):
+        def path(mesh, worker):
+            a = assets.SplatAssetStream(stream_fmt, 2, len(data))
+            a.set_transform(transform)
+            done = calls = 0
+            ends = list(range(STREAM_APPEND, len(data), STREAM_APPEND)) + [len(data)]
+            at = 0
+            for k, end in enumerate(ends):
+                ready = a.append(data[at:end], end == len(data)).splats_ready
+                at = end
+                if ready > done and ((k + 1) % every == 0 or end == len(data)):
+                    a.upload_to(mesh, done, done, ready - done)
+                    a.upload_centers_to(worker, done, done, ready - done)
+                    done, calls = ready, calls + 1
+            assert done == n
+            uploads[every] = (len(ends), calls)
+            a.close()
+        return path
+
+    paths = [("host", host), ("device", device)] + ([("stream/1", streamed(1)), ("stream/16", streamed(16))] if args.stream else [])
+    times = {name: [] for name, _ in paths}
     for _ in range(args.repeats):
-        for name, path in (("host", host), ("device", device)):
+        for name, path in paths:
             mesh, worker = fresh()
             ctx.synchronize()
             t0 = time.perf_counter()
@@ -155,7 +188,11 @@ def main():
     for k in ("host", "device"):
         lines.append(f"{k:6s} median {med[k]:10.2f} ms  spread {spread[k]:8.2f} ms  PCIe {pcie[k]:12d} bytes ({pcie[k] / n:.1f} B/splat)  "
                      f"runs " + " ".join(f"{t:.2f}" for t in times[k]))
-    gap, need = med["host"] - med["device"], max(spread.values())
+    for every in (1, 16) if args.stream else ():
+        k = f"stream/{every}"
+        lines.append(f"{k:9s} median {med[k]:10.2f} ms  spread {spread[k]:8.2f} ms  {uploads[every][0]} appends of {STREAM_APPEND} bytes, "
+                     f"{uploads[every][1]} uploads  runs " + " ".join(f"{t:.2f}" for t in times[k]))
+    gap, need = med["host"] - med["device"], max(spread["host"], spread["device"])
     lines.append(f"gap {gap:.2f} ms (x{med['host'] / med['device']:.1f}), larger spread {need:.2f} ms: " + ("PASS" if gap > need else "FAIL"))
     text = "\n".join(lines)
     print(text)
