@@ -127,6 +127,7 @@ SYMBOLS = {
     "gs_sorter_bind_mesh": (C.c_int, [_VP, _VP]),
     "gs_sorter_set_uploaded_count": (C.c_int, [_VP, C.c_uint32]),
     "gs_sorter_remove": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint32]),
+    "gs_sorter_resize": (C.c_int, [_VP, C.c_uint32]),
     "gs_sorter_set_frustum_cull": (C.c_int, [_VP, C.c_int]),
     "gs_sorter_set_visibility_cull": (C.c_int, [_VP, C.c_int]),
     "gs_sorter_debug_read": (C.c_int, [_VP, C.c_int, _VP, C.c_uint32]),
@@ -158,6 +159,7 @@ SYMBOLS = {
     "gs_mesh_upload_scene_indexes": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
     "gs_mesh_remove": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint32]),
     "gs_mesh_reorder": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "gs_mesh_resize": (C.c_int, [_VP, C.c_uint32]),
     "gs_mesh_set_scenes": (C.c_int, [_VP, C.POINTER(SceneParams)]),
     "gs_mesh_project": (C.c_int, [_VP, C.POINTER(Camera)]),
     "gs_mesh_set_destination": (C.c_int, [_VP, C.POINTER(Destination)]),

@@ -2,6 +2,9 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <mutex>
+#include <string>
+
 #include "gs_internal.hpp"
 
 static thread_local char g_err[512] = "";
@@ -11,6 +14,42 @@ void gs_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+// The bytes every DevBuf of the process holds, and the test hook on top of them: $GSPLAT_ALLOC_HEADROOM=<bytes>[:tag] lets the
+// allocations grow by that many bytes over what was held when the variable took this value (any change of the string, so a tag
+// starts a new budget), then fails them as the device's allocator would (GS_ERR_NOMEM).  Tests hold the out-of-memory paths to
+// it: a recovery that needs more memory than the object held before the call fails under the budget too.
+static std::mutex g_alloc_mutex;
+static size_t g_alloc_live = 0, g_alloc_budget = 0;
+static std::string g_alloc_rule;
+
+// the rule as it stands now; a new value starts its budget from what is held at this moment - looked at by allocations and
+// releases alike, so a call that begins by releasing is measured from what the object held when it was called
+static bool alloc_rule_locked() {
+    const char* rule = getenv("GSPLAT_ALLOC_HEADROOM");
+    if (!rule) {
+        g_alloc_rule.clear();
+        return false;
+    }
+    if (g_alloc_rule != rule) {
+        g_alloc_rule = rule;
+        g_alloc_budget = g_alloc_live + (size_t)strtoull(rule, nullptr, 0);
+    }
+    return true;
+}
+
+bool gs_alloc_admit(size_t bytes) {
+    std::lock_guard<std::mutex> lock(g_alloc_mutex);
+    if (alloc_rule_locked() && g_alloc_live + bytes > g_alloc_budget) return false;
+    g_alloc_live += bytes;
+    return true;
+}
+
+void gs_alloc_released(size_t bytes) {
+    std::lock_guard<std::mutex> lock(g_alloc_mutex);
+    (void)alloc_rule_locked();
+    g_alloc_live -= bytes < g_alloc_live ? bytes : g_alloc_live;
 }
 
 extern "C" {

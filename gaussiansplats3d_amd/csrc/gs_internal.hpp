@@ -46,14 +46,22 @@ void gs_set_error(const char* fmt, ...);
 // ---------------------------------------------------------------------------------------------------
 // device memory
 // ---------------------------------------------------------------------------------------------------
+// (context.hip) the bytes all DevBufs hold, and $GSPLAT_ALLOC_HEADROOM, the tests' out-of-memory hook on top of that count
+bool gs_alloc_admit(size_t bytes);        // false: refused by the hook; true: counted
+void gs_alloc_released(size_t bytes);
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     int alloc(size_t n) {
         release();
         if (n == 0) n = 16;
+        if (!gs_alloc_admit(n)) {
+            gs_set_error("hipMalloc(%zu) refused: over the budget of $GSPLAT_ALLOC_HEADROOM", n);
+            return GS_ERR_NOMEM;
+        }
         hipError_t e = hipMalloc(&p, n);
         if (e != hipSuccess) {
+            gs_alloc_released(n);
             p = nullptr;
             gs_set_error("hipMalloc(%zu) failed: %s", n, hipGetErrorString(e));
             return GS_ERR_NOMEM;
@@ -78,9 +86,16 @@ struct DevBuf {
         return n <= bytes ? GS_OK : alloc(n);
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            gs_alloc_released(bytes);
+        }
         p = nullptr;
         bytes = 0;
+    }
+    void swap(DevBuf& o) {
+        void* tp = p; p = o.p; o.p = tp;
+        const size_t tb = bytes; bytes = o.bytes; o.bytes = tb;
     }
     template <class T>
     T* as() const { return reinterpret_cast<T*>(p); }
@@ -264,6 +279,7 @@ struct gs_sorter {
     gs_context* ctx = nullptr;
     AssetDeviceImage asset_dev;
     uint32_t max_count = 0, flags = 0, precision = 16, uploaded = 0;
+    bool scratch_lost = false;   // a resize ran out of memory and could not even get the old scratch back: sorts are refused
     // SoA planes of the AoS x4 centres the worker receives (int32 or float bit patterns)
     DevBuf cx, cy, cz, cw, scene_idx;
     DevBuf caos;               // the AoS x4 centres as uploaded (16-byte gathers for index-list sorts)
@@ -443,6 +459,7 @@ struct gs_mesh {
     uint64_t centre_n = 0;                          // (draw_plan.cpp: how far a camera moved, in screen heights)
     int forced_list_shift = -1;                    // GSPLAT_LIST_SHIFT (A/B and tests)
     uint32_t max_count = 0, sh_degree = 0, flags = 0, uploaded = 0;
+    bool scratch_lost = false; // a resize ran out of memory and could not even get the old scratch back: draws and uploads are refused
     // SoA planes
     DevBuf px, py, pz;         // float centres
     DevBuf covA, covB;         // fp32: float4 + float2 ; fp16: uint2 + uint
@@ -593,6 +610,36 @@ int gs_mesh_morton_sort(gs_mesh* m, const float* c3, uint32_t count, const float
                         uint32_t** spare);
 int gs_mesh_assign_slots(gs_mesh* m, const uint32_t* sorted_local, uint32_t from, uint32_t count);
 void gs_sorter_mesh_reordered(gs_sorter* s);                     // the bound mesh changed its storage order only (sorter.hip)
+
+// Changing the capacity (mesh_edit.hip: gs_mesh_resize; gs_sorter_resize in sorter.hip).  Which buffers of an
+// object have a size that depends on its capacity is said once per object: gs_mesh_capacity_list (mesh.hip) and
+// gs_sorter_capacity_list (sorter.hip).  The create call allocates from the list, the resize call allocates, copies and releases
+// from it, so a buffer added to the list is known to both.
+//   CAP_PLANE      resident, `elem` bytes per position: a resize copies the uploaded positions and zeroes the rest
+//   CAP_POSITIONS  resident uint32 positions (perm, inv_perm): copied; the rest is the identity (the caller's launch)
+//   CAP_BOXES      resident, `elem` bytes per 256-position storage block: copied up to the last block that holds an uploaded
+//                  position, zero behind it
+//   CAP_SCRATCH    holds nothing that outlives a draw or a sort, allocated at creation
+//   CAP_LAZY       the same, allocated and sized by its first user from max_count (DevBuf::ensure): a resize only releases it,
+//                  the row carries no size
+enum CapRole { CAP_PLANE, CAP_POSITIONS, CAP_BOXES, CAP_SCRATCH, CAP_LAZY };
+struct CapBuf {
+    DevBuf* buf;
+    size_t bytes;                          // at the capacity the list was made for (CAP_LAZY: 0)
+    uint32_t elem;
+    CapRole role;
+};
+std::vector<CapBuf> gs_mesh_capacity_list(gs_mesh* m, uint32_t capacity);
+std::vector<CapBuf> gs_sorter_capacity_list(gs_sorter* s, uint32_t capacity);
+uint32_t gs_mesh_entry_guess(uint32_t capacity);                 // the entry capacity gs_mesh_create starts with (mesh.hip)
+// `now` and `next`: the object's list at its present and at the new capacity (the same buffers in the same order).  Releases the
+// scratch, allocates every buffer of `next` before it releases a resident one of `now`, copies `uploaded` positions on st and waits.
+// GS_ERR_NOMEM: the resident buffers are untouched and the scratch is allocated again at the present capacity - after everything
+// the call allocated has been released, so that needs no more memory than the object held before.  GS_CAPACITY_SCRATCH_LOST (an
+// internal status the two callers turn into GS_ERR_NOMEM + scratch_lost): even that failed, the object has no scratch.
+constexpr int GS_CAPACITY_SCRATCH_LOST = -1000;
+#define GS_REQUIRE_SCRATCH(obj) GS_REQUIRE(!(obj)->scratch_lost, "the object lost its scratch buffers in a resize that ran out of memory: resize it again")
+int gs_capacity_move(hipStream_t st, const std::vector<CapBuf>& now, const std::vector<CapBuf>& next, uint32_t uploaded);
 
 // kernels' host launchers ---------------------------------------------------------------------------
 // (ev_before / ev_after, nullable, recorded on ctx->aux: around the whole vertex stage - block test, mask memset, k_project - when

@@ -237,6 +237,57 @@ static int mesh_alloc_entries(gs_mesh* m, uint32_t capacity) {
     return GS_OK;
 }
 
+// first guess: 8 entries per splat, at least 1M; grown on overflow
+uint32_t gs_mesh_entry_guess(uint32_t capacity) {
+    uint64_t cap = (uint64_t)capacity * 8;
+    if (cap < (1u << 20)) cap = 1u << 20;
+    if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
+    return (uint32_t)cap;
+}
+
+// Every buffer of a mesh whose size depends on its capacity (gs_internal.hpp, CapBuf): gs_mesh_create allocates from this list,
+// gs_mesh_resize (mesh_edit.hip) moves the mesh from the list of one capacity to the list of another.  Needs sh_degree, flags,
+// reorder and two_sets of the mesh.  The scene-index plane is in the list once gs_mesh_upload_scene_indexes has allocated it.
+std::vector<CapBuf> gs_mesh_capacity_list(gs_mesh* m, uint32_t capacity) {
+    const size_t n = capacity, blocks = (n + 255) / 256;
+    const bool half = (m->flags & GS_MESH_COV_HALF) != 0;
+    std::vector<CapBuf> l;
+    auto A = [&](DevBuf& b, size_t bytes, uint32_t elem, CapRole role) { l.push_back(CapBuf{&b, bytes, elem, role}); };
+    A(m->px, n * 4, 4, CAP_PLANE); A(m->py, n * 4, 4, CAP_PLANE); A(m->pz, n * 4, 4, CAP_PLANE);
+    A(m->covA, n * (half ? 8 : 16), half ? 8 : 16, CAP_PLANE); A(m->covB, n * (half ? 4 : 8), half ? 4 : 8, CAP_PLANE);
+    A(m->rgba, n * 4, 4, CAP_PLANE);
+    if (m->flags & GS_MESH_SH_U8) {
+        if (m->sh_degree >= 1) A(m->sh0, n * 16, 16, CAP_PLANE);
+        if (m->sh_degree >= 2) A(m->sh1, n * 8, 8, CAP_PLANE);
+    } else {
+        if (m->sh_degree >= 1) { A(m->sh0, n * 16, 16, CAP_PLANE); A(m->sh1, n * (m->sh_degree == 2 ? 16 : 4), m->sh_degree == 2 ? 16 : 4, CAP_PLANE); }
+        if (m->sh_degree >= 2) A(m->sh2, n * 16, 16, CAP_PLANE);
+    }
+    A(m->cov_bound, n * 4, 4, CAP_PLANE);
+    A(m->block_box, blocks * 32 + 32, 32, CAP_BOXES);
+    if (m->scene_idx.p) A(m->scene_idx, n * 4, 4, CAP_PLANE);             // (gs_mesh_upload_scene_indexes: allocated and zeroed)
+    if (m->reorder) { A(m->perm, n * 4 + 16, 4, CAP_POSITIONS); A(m->inv_perm, n * 4, 4, CAP_POSITIONS); }   // (+16: the sorter's k_cull_front reads perm as 16-byte vectors)
+    A(m->rect_q, n * 8 + 2048, 8, CAP_SCRATCH); A(m->cidx, n * 4 + 1024, 4, CAP_SCRATCH); A(m->coff, n * 4 + 1024, 4, CAP_SCRATCH);
+    for (int k = 0; k < (m->two_sets ? 2 : 1); k++) {
+        ProjSet& ps = m->sets[k];
+        A(ps.recs, n * sizeof(SplatRec), sizeof(SplatRec), CAP_SCRATCH);
+        A(ps.rects, blocks * 256 * 8, 8, CAP_SCRATCH);        // whole blocks: whatever slot a 4-byte look-up word's escape names is inside (bin_word.hpp)
+        A(ps.vis_mask, blocks * 32 + 32, 32, CAP_SCRATCH);    // whole 256-splat blocks: 4 words each
+        A(ps.vis32, blocks * 64 + 64, 64, CAP_SCRATCH);
+        A(ps.prect, blocks * 256 * 8 + 64, 8, CAP_SCRATCH);
+        A(ps.block_any, (blocks + 127) & ~(size_t)63, 1, CAP_SCRATCH);
+        A(ps.zrec, 0, 0, CAP_LAZY);                           // (zrec and vis_orig: sized by the first vertex stage that writes them, project.hip)
+        A(ps.vis_orig, 0, 0, CAP_LAZY);
+    }
+    // the tile entries: a fresh mesh's first guess, or the size they have grown to (they never shrink; gs_mesh_alloc_entries)
+    const size_t entries = std::max(m->entry_capacity, gs_mesh_entry_guess(capacity));
+    A(m->ekeyA, entries * 4, 4, CAP_SCRATCH); A(m->ekeyB, entries * 4, 4, CAP_SCRATCH);
+    A(m->evalA, entries * 4, 4, CAP_SCRATCH); A(m->evalB, entries * 4, 4, CAP_SCRATCH);
+    A(m->order, 0, 0, CAP_LAZY);                              // (sized by a draw from a host list, mesh.hip)
+    A(m->distances, 0, 0, CAP_LAZY);                          // (... by gs_mesh_compute_distances, distances.hip)
+    return l;
+}
+
 // The draw path's switches (gs_internal.hpp: DrawSwitches), read here and nowhere else.  (gs_mesh_create below reads the switches
 // that hold for a mesh's lifetime.)
 DrawSwitches draw_switches() {
@@ -277,23 +328,9 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     m->max_count = max_splat_count;
     m->sh_degree = sh_degree;
     m->flags = flags;
-    const size_t n = max_splat_count;
-    const bool half = (flags & GS_MESH_COV_HALF) != 0;
     int st = GS_OK;
     auto A = [&](DevBuf& b, size_t bytes) { if (st == GS_OK) st = b.alloc(bytes); };
-    A(m->px, n * 4); A(m->py, n * 4); A(m->pz, n * 4);
-    A(m->covA, n * (half ? 8 : 16)); A(m->covB, n * (half ? 4 : 8));
-    A(m->rgba, n * 4);
-    if (flags & GS_MESH_SH_U8) {
-        if (sh_degree >= 1) A(m->sh0, n * 16);
-        if (sh_degree >= 2) A(m->sh1, n * 8);
-    } else {
-        if (sh_degree >= 1) { A(m->sh0, n * 16); A(m->sh1, n * (sh_degree == 2 ? 16 : 4)); }
-        if (sh_degree >= 2) A(m->sh2, n * 16);
-    }
     A(m->scene_dev, sizeof(gs_scene_params));
-    A(m->cov_bound, n * 4);
-    A(m->block_box, ((n + 255) / 256) * 32 + 32);
     m->reorder = !(flags & GS_MESH_KEEP_ORDER) && !getenv("GSPLAT_NO_REORDER");
     m->no_block_cull = getenv("GSPLAT_NO_BLOCK_CULL") != nullptr;
     m->no_block_list = getenv("GSPLAT_NO_BLOCK_LIST") != nullptr;
@@ -302,23 +339,16 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     m->no_deep = getenv("GSPLAT_NO_DEEP") != nullptr;
     if (const char* ls = getenv("GSPLAT_LIST_SHIFT"))
         if (ls[0] >= '1' && ls[0] <= '6' && ls[1] == '\0') m->forced_list_shift = ls[0] - '0';
-    if (m->reorder) { A(m->perm, n * 4 + 16); A(m->inv_perm, n * 4); }   // (+16: the sorter's k_cull_front reads perm as 16-byte vectors)
-    A(m->rect_q, n * 8 + 2048); A(m->cidx, n * 4 + 1024); A(m->coff, n * 4 + 1024);
     // (a context with one stream runs the frames' kernels in order: a second set would never be written early)
     m->two_sets = ctx->aux != ctx->stream && !getenv("GSPLAT_ONE_RECORD_SET");
-    for (int k = 0; k < (m->two_sets ? 2 : 1); k++) {      // (zrec and vis_orig: by the first vertex stage that writes them)
-        ProjSet& ps = m->sets[k];
-        A(ps.recs, n * sizeof(SplatRec));
-        A(ps.rects, ((n + 255) / 256) * 256 * 8);      // whole blocks: whatever slot a 4-byte look-up word's escape names is inside (bin_word.hpp)
-        A(ps.vis_mask, ((n + 255) / 256) * 32 + 32);   // whole 256-splat blocks: 4 words each
-        A(ps.vis32, ((n + 255) / 256) * 64 + 64);
-        A(ps.prect, ((n + 255) / 256) * 256 * 8 + 64);
-        A(ps.block_any, ((n + 255) / 256 + 127) & ~(size_t)63);
-        if (st == GS_OK && hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming) != hipSuccess) {
+    const std::vector<CapBuf> sized = gs_mesh_capacity_list(m, max_splat_count);   // everything the capacity sizes
+    for (const CapBuf& c : sized)
+        if (c.role != CAP_LAZY) A(*c.buf, c.bytes);
+    for (int k = 0; k < (m->two_sets ? 2 : 1); k++)
+        if (st == GS_OK && hipEventCreateWithFlags(&m->sets[k].ev_done, hipEventDisableTiming) != hipSuccess) {
             gs_set_error("hipEventCreate failed");
             st = GS_ERR_HIP;
         }
-    }
     A(m->bin_sums, 4 * 3 * 2048 + 64);               // uint32 [3][BIN_MAX_BLOCKS] + the batches-per-workgroup of the last count
     A(m->frame, sizeof(RenderFrame));
     if (st == GS_OK) st = m->radix.init();
@@ -329,9 +359,9 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
         // (or a stale index list) may name them: the planes must be defined and the storage permutation a bijection from
         // the start (identity until an upload assigns Morton slots).
         hipError_t e = hipSuccess;
-        auto Z = [&](DevBuf& b) { if (e == hipSuccess && b.p) e = hipMemsetAsync(b.p, 0, b.bytes, ctx->stream); };
-        Z(m->px); Z(m->py); Z(m->pz); Z(m->covA); Z(m->covB); Z(m->cov_bound); Z(m->rgba); Z(m->sh0); Z(m->sh1); Z(m->sh2);
-        Z(m->block_box);                                      // boxes of never-uploaded blocks: the origin (their zero centres)
+        // (boxes of never-uploaded blocks: the origin, their zero centres)
+        for (const CapBuf& c : sized)
+            if (e == hipSuccess && (c.role == CAP_PLANE || c.role == CAP_BOXES)) e = hipMemsetAsync(c.buf->p, 0, c.buf->bytes, ctx->stream);
         if (e == hipSuccess && m->reorder) {
             hipLaunchKernelGGL(k_iota2, dim3(up_grid(max_splat_count)), dim3(256), 0, ctx->stream, m->perm.as<uint32_t>(),
                                m->inv_perm.as<uint32_t>(), max_splat_count);
@@ -343,13 +373,7 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
             st = GS_ERR_HIP;
         }
     }
-    if (st == GS_OK) {
-        // first guess: 8 entries per splat, at least 1M; grown on overflow
-        uint64_t cap = (uint64_t)n * 8;
-        if (cap < (1u << 20)) cap = 1u << 20;
-        if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
-        st = mesh_alloc_entries(m, (uint32_t)cap);
-    }
+    if (st == GS_OK) m->entry_capacity = gs_mesh_entry_guess(max_splat_count);   // (the list's ekey / eval buffers)
     for (int i = 0; i < 6 && st == GS_OK; i++)
         if (hipEventCreate(&m->ev[i]) != hipSuccess) {
             gs_set_error("hipEventCreate failed");
@@ -596,6 +620,7 @@ int gs_mesh_block_boxes(gs_mesh* m, uint32_t b0, uint32_t b1) {
 // once for gs_mesh_upload and gs_mesh_upload_asset; the fresh / non-fresh segment cuts and the slotted ranges are upload_plan.hpp's.
 int gs_mesh_upload_from(gs_mesh* m, uint32_t from, uint32_t count, MeshUploadSource& src) {
     if (count == 0) return GS_OK;
+    GS_REQUIRE_SCRATCH(m);                                // (the Morton sort of a segment runs in the entry buffers)
     m->projection_pending = false;                        // the scene changed under a pending gs_mesh_project
     ScopedDevice sd(m->ctx->device);
     // earlier draws may still read the planes / the permutation on either stream
@@ -974,6 +999,7 @@ static int mesh_heal_overflow(gs_mesh* m, const DrawSwitches& sw, bool* healed) 
 
 int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
     GS_REQUIRE(m && cam, "mesh / camera == NULL");
+    GS_REQUIRE_SCRATCH(m);
     ProjectParams pp;
     GS_TRY(mesh_params(m, cam, pp));
     ScopedDevice sd(m->ctx->device);
@@ -992,6 +1018,7 @@ int gs_mesh_project(gs_mesh* m, const gs_camera* cam) {
 int gs_mesh_render(gs_mesh* m, const gs_camera* cam, const uint32_t* sorted_host, gs_sorter* sorter,
                    uint32_t render_count, uint8_t* rgba_out_host, void* rgba_out_dev, gs_render_stats* stats) {
     GS_REQUIRE(m && cam, "mesh / camera == NULL");
+    GS_REQUIRE_SCRATCH(m);
     GS_REQUIRE(render_count <= m->uploaded, "render_count exceeds the uploaded splat count");
     GS_REQUIRE(!(sorted_host && sorter), "pass either host indexes or a sorter, not both");
     GS_REQUIRE(!sorter || (sorter->ctx == m->ctx && sorter->has_result && sorter->last_render >= render_count),

@@ -4,6 +4,7 @@
 // Which spans move where, and which calls are refused, is upload_plan.hpp's (plan_remove); DESIGN.md 8.13.
 // Second half of the file: gs_mesh_reorder, which folds the Morton runs of a range - one per fresh upload, as a progressive load leaves
 // them - into the one run a single upload would have been (plan_reorder).
+// Between the two: gs_mesh_resize and the move both resize calls share (gs_capacity_move).
 #include <algorithm>
 
 #include "gs_internal.hpp"
@@ -228,6 +229,95 @@ extern "C" int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ran
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Changing the capacity (gs_mesh_resize; gs_sorter_resize in sorter.hip).  The object moves from its capacity
+// list at one capacity to the list at another (gs_internal.hpp, CapBuf): the scratch goes first - it holds nothing that outlives a
+// draw or a sort - then every buffer of the new list is allocated before a resident one of the old list is released, so a failed
+// allocation leaves the splats where they are.  Plain device-to-device copies move the uploaded positions.
+// ---------------------------------------------------------------------------------------------------
+int gs_capacity_move(hipStream_t st, const std::vector<CapBuf>& now, const std::vector<CapBuf>& next, uint32_t uploaded) {
+    const size_t count = next.size();
+    auto resident = [](const CapBuf& c) { return c.role == CAP_PLANE || c.role == CAP_POSITIONS || c.role == CAP_BOXES; };
+    for (const CapBuf& c : now)
+        if (!resident(c)) c.buf->release();
+    std::vector<DevBuf> fresh(count);                       // the resident buffers at the new capacity
+    int status = GS_OK;
+    for (size_t k = 0; k < count && status == GS_OK; k++) {
+        if (resident(next[k])) status = fresh[k].alloc(next[k].bytes);
+        else if (next[k].role == CAP_SCRATCH) status = next[k].buf->alloc(next[k].bytes);
+    }
+    if (status != GS_OK) {
+        // Back to the present capacity.  Memory ran out, so first everything this call allocated goes - the new resident planes
+        // and the scratch of the new list - and only then is the scratch allocated as it was sized before: the recovery holds no
+        // more than the object held when it was called.  Should even that fail (somebody else took the memory meanwhile), the
+        // object is left without scratch and the caller marks it (GS_CAPACITY_SCRATCH_LOST -> scratch_lost): draws, sorts and
+        // uploads are refused, never run on null buffers, until a resize succeeds.
+        fresh.clear();
+        for (const CapBuf& c : next)
+            if (c.role == CAP_SCRATCH) c.buf->release();
+        for (const CapBuf& c : now)
+            if (c.role == CAP_SCRATCH && c.buf->alloc(c.bytes) != GS_OK) {
+                for (const CapBuf& d : now)
+                    if (d.role == CAP_SCRATCH) d.buf->release();
+                return GS_CAPACITY_SCRATCH_LOST;
+            }
+        return status;
+    }
+    // (a failing copy below is a sticky HIP error: the context is lost with it, whatever capacity the object then reports)
+    for (size_t k = 0; k < count; k++) {
+        const CapBuf& c = next[k];
+        if (!resident(c)) continue;
+        // positions (CAP_BOXES: storage blocks) that hold something, then what a fresh object holds behind them
+        const size_t keep = (c.role == CAP_BOXES ? ((size_t)uploaded + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK : (size_t)uploaded) * c.elem;
+        if (keep) GS_HIP(hipMemcpyAsync(fresh[k].p, c.buf->p, keep, hipMemcpyDeviceToDevice, st));
+        if (c.role != CAP_POSITIONS && fresh[k].bytes > keep)
+            GS_HIP(hipMemsetAsync(static_cast<char*>(fresh[k].p) + keep, 0, fresh[k].bytes - keep, st));
+    }
+    GS_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < count; k++)
+        if (resident(next[k])) next[k].buf->swap(fresh[k]);   // (the old planes go with `fresh`)
+    return GS_OK;
+}
+
+extern "C" int gs_mesh_resize(gs_mesh* m, uint32_t max_splat_count) {
+    GS_REQUIRE(m != nullptr, "mesh == NULL");
+    if (max_splat_count == m->max_count && !m->scratch_lost) return GS_OK;
+    GS_REQUIRE(max_splat_count > 0, "gs_mesh_resize: max_splat_count == 0");
+    GS_REQUIRE(max_splat_count <= (1u << 28), "gs_mesh_resize: max_splat_count > 2^28");
+    if (max_splat_count < m->uploaded) {
+        gs_set_error("invalid argument: gs_mesh_resize: max_splat_count %u is below the uploaded count %u (remove splats first)", max_splat_count,
+                     m->uploaded);
+        return GS_ERR_INVALID;
+    }
+    gs_context* ctx = m->ctx;
+    ScopedDevice sd(ctx->device);
+    hipStream_t st = ctx->stream;
+    // draws in flight read the planes and the permutation on either stream, a bound sorter's sort reads the permutation on its own
+    GS_HIP(hipStreamSynchronize(st));
+    if (ctx->aux != st) GS_HIP(hipStreamSynchronize(ctx->aux));
+    for (gs_sorter* s : ctx->live_sorters)
+        if ((s->bound_mesh == m || s->result_mesh == m) && s->stream != st) GS_HIP(hipStreamSynchronize(s->stream));
+
+    // whatever comes of it, the per-frame buffers go: nothing that described a draw or a projection is left
+    mesh_forget_layout(m);
+    for (gs_sorter* s : ctx->live_sorters)
+        if (s->bound_mesh == m || s->result_mesh == m) gs_sorter_mesh_edited(s);
+    const int moved = gs_capacity_move(st, gs_mesh_capacity_list(m, m->max_count), gs_mesh_capacity_list(m, max_splat_count), m->uploaded);
+    m->scratch_lost = moved == GS_CAPACITY_SCRATCH_LOST;
+    if (moved != GS_OK) return m->scratch_lost ? GS_ERR_NOMEM : moved;
+    m->max_count = max_splat_count;
+    m->entry_capacity = std::max(m->entry_capacity, gs_mesh_entry_guess(max_splat_count));   // (the list's ekey / eval buffers)
+    if (m->reorder && max_splat_count > m->uploaded) {      // the tail is the identity, as gs_mesh_create leaves it
+        hipLaunchKernelGGL(k_remove_iota, dim3(edit_grid(max_splat_count - m->uploaded)), dim3(256), 0, st, m->perm.as<uint32_t>(),
+                           m->inv_perm.as<uint32_t>(), m->uploaded, max_splat_count);
+        GS_HIP(hipGetLastError());
+    }
+    // the box of the partial block at the end of the uploaded splats: it sees the zeros up to the new capacity, as a fresh mesh's does
+    GS_TRY(gs_mesh_block_boxes(m, m->uploaded / UPLOAD_BLOCK, (m->uploaded + UPLOAD_BLOCK - 1u) / UPLOAD_BLOCK));
+    GS_HIP(hipStreamSynchronize(st));
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Folding the Morton runs of a range into one (gs_mesh_reorder).  The range keeps its storage slots; inside them
 // the splats take the order one upload of the range would have given them.  The order itself is mesh.hip's (gs_mesh_morton_sort),
 // fed with the centres as an upload stages them: in original index order, out of the planes.
@@ -306,6 +396,7 @@ static int reorder_planes_of(hipStream_t st, void* const* planes, const uint32_t
 
 extern "C" int gs_mesh_reorder(gs_mesh* m, uint32_t from, uint32_t count) {
     GS_REQUIRE(m != nullptr, "mesh == NULL");
+    GS_REQUIRE_SCRATCH(m);
     const ReorderPlan plan = plan_reorder(m->runs, m->slotted, m->uploaded, m->reorder, from, count);
     if (plan.refused) {
         gs_set_error("invalid argument: gs_mesh_reorder: %s", plan.refused);

@@ -1303,6 +1303,26 @@ extern "C" int gs_debug_radix_prof(void* dst) {
 }
 #endif
 
+// Every buffer of a sorter whose size depends on its capacity (gs_internal.hpp, CapBuf): gs_sorter_create allocates from this
+// list, gs_sorter_resize moves the sorter from the list of one capacity to the list of another.  Needs the sorter's flags.
+std::vector<CapBuf> gs_sorter_capacity_list(gs_sorter* s, uint32_t capacity) {
+    const size_t n = capacity, b4 = n * 4;
+    std::vector<CapBuf> l;
+    auto A = [&](DevBuf& b, size_t bytes, uint32_t elem, CapRole role) { l.push_back(CapBuf{&b, bytes, elem, role}); };
+    A(s->cx, b4 + 16, 4, CAP_PLANE); A(s->cy, b4 + 16, 4, CAP_PLANE); A(s->cz, b4 + 16, 4, CAP_PLANE);   // (+16: k_cull_front reads whole 16-byte vectors)
+    A(s->caos, n * 16, 16, CAP_PLANE);
+    if (s->flags & GS_SORT_DYNAMIC) { A(s->cw, b4 + 16, 4, CAP_PLANE); A(s->scene_idx, b4 + 16, 4, CAP_PLANE); }   // (+16: as above)
+    A(s->keys, b4, 4, CAP_SCRATCH); A(s->keyA, b4, 4, CAP_SCRATCH); A(s->keyB, b4, 4, CAP_SCRATCH);
+    A(s->valA, b4, 4, CAP_SCRATCH); A(s->valB, b4, 4, CAP_SCRATCH); A(s->sorted, b4, 4, CAP_SCRATCH);
+    A(s->keys16, n * 2 + 16, 2, CAP_SCRATCH);
+    // by their first users: a sort from a list, from distances, under a cull, of a gathered list; the debug reads; the 16-bit
+    // centre planes (sorter_update_compact builds them from the int32 planes)
+    // (they size themselves from max_count where they allocate; the list only says that they go with the capacity)
+    for (DevBuf* b : {&s->idx_in, &s->precomputed, &s->pay_in, &s->debug, &s->keep_mask, &s->mask_copy, &s->cx16, &s->cy16, &s->cz16})
+        A(*b, 0, 0, CAP_LAZY);
+    return l;
+}
+
 extern "C" {
 
 int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, uint32_t precision_bits,
@@ -1321,13 +1341,11 @@ int gs_sorter_create(gs_context* ctx, uint32_t max_splat_count, uint32_t flags, 
     s->max_count = max_splat_count;
     s->flags = flags;
     s->precision = precision_bits;
-    const size_t n = max_splat_count, b4 = n * 4;
     int st = GS_OK;
     auto A = [&](DevBuf& b, size_t bytes) { if (st == GS_OK) st = b.alloc(bytes); };
-    A(s->cx, b4 + 16); A(s->cy, b4 + 16); A(s->cz, b4 + 16); A(s->caos, n * 16);   // (+16: k_cull_front reads whole 16-byte vectors)
-    if (flags & GS_SORT_DYNAMIC) { A(s->cw, b4 + 16); A(s->scene_idx, b4 + 16); A(s->scene_rows, sizeof(SceneRows)); }   // (+16: as above)
-    A(s->keys, b4); A(s->keyA, b4); A(s->keyB, b4); A(s->valA, b4); A(s->valB, b4); A(s->sorted, b4);
-    A(s->keys16, n * 2 + 16);
+    for (const CapBuf& c : gs_sorter_capacity_list(s, max_splat_count))   // everything the capacity sizes
+        if (c.role != CAP_LAZY) A(*c.buf, c.bytes);
+    if (flags & GS_SORT_DYNAMIC) A(s->scene_rows, sizeof(SceneRows));
     A(s->frame, 2 * sizeof(SortFrame));
     if (st == GS_OK) st = s->radix.init();
     if (st == GS_OK && (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess ||
@@ -1597,6 +1615,35 @@ int gs_sorter_remove(gs_sorter* s, const uint32_t* ranges, uint32_t n_ranges, co
     GS_TRY(sorter_update_compact(s, 0, new_end, new_end));
     sorter_tell_mesh(s);
     return GS_OK;
+}
+
+// The sorter's half of gs_mesh_resize (mesh_edit.hip: gs_capacity_move).  The rows as uploaded, the SoA planes and
+// the scene indexes are copied; the extreme set depends on the rows alone and stays; the 16-bit planes are built again from the
+// int32 planes, as an upload builds them for new buffers.
+int gs_sorter_resize(gs_sorter* s, uint32_t max_splat_count) {
+    GS_REQUIRE(s != nullptr, "sorter == NULL");
+    if (max_splat_count == s->max_count && !s->scratch_lost) return GS_OK;
+    GS_REQUIRE(max_splat_count > 0, "gs_sorter_resize: max_splat_count == 0");
+    if (max_splat_count < s->uploaded) {
+        gs_set_error("invalid argument: gs_sorter_resize: max_splat_count %u is below the uploaded splat count %u (remove centres first)",
+                     max_splat_count, s->uploaded);
+        return GS_ERR_INVALID;
+    }
+    ScopedDevice sd(s->ctx->device);
+    hipStream_t st = s->stream;
+    GS_HIP(hipStreamSynchronize(st));                      // the sort in flight
+    if (s->ctx->stream != st) GS_HIP(hipStreamSynchronize(s->ctx->stream));   // a draw may still be reading `sorted`
+    sorter_forget_numbering(s);                            // whatever comes of it, the result and the lists go with their buffers
+    s->consumer_pending = false;                           // (the context's stream is idle: no draw reads `sorted`)
+    int status = gs_capacity_move(st, gs_sorter_capacity_list(s, s->max_count), gs_sorter_capacity_list(s, max_splat_count), s->uploaded);
+    s->scratch_lost = status == GS_CAPACITY_SCRATCH_LOST;  // (not even the old scratch came back: sorts are refused)
+    if (s->scratch_lost) status = GS_ERR_NOMEM;
+    if (status == GS_OK) s->max_count = max_splat_count;
+    s->c16_ok = false;                                     // the 16-bit planes went with the scratch: every uploaded position again
+    const int compact = sorter_update_compact(s, 0, s->uploaded, s->uploaded);
+    if (compact != GS_OK && compact != GS_ERR_NOMEM) return compact;   // (no room for the 16-bit planes: sorts read the int32 ones)
+    sorter_tell_mesh(s);
+    return status;
 }
 
 int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count) {
@@ -2001,6 +2048,7 @@ static int sorter_sort(gs_sorter* s, const float* mvp, const uint32_t* indexes_t
                        uint32_t render_count, const void* precomputed, const float* transforms, uint32_t* sorted_out,
                        gs_sort_stats* stats, const uint32_t* list_count_dev = nullptr) {
     GS_REQUIRE(s && mvp, "sorter / mvp == NULL");
+    GS_REQUIRE_SCRATCH(s);
     SortCall c = {};
     c.mvp = mvp; c.indexes_to_sort = indexes_to_sort; c.device_list = device_list; c.precomputed = precomputed;
     c.transforms = transforms; c.list_count_dev = list_count_dev; c.sort_count = sort_count; c.render_count = render_count;

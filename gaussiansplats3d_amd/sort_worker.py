@@ -48,6 +48,8 @@ class SortWorker:
             return self._on_sort(msg["sort"])
         if "remove" in msg:                              # (not a message of the reference's worker: its Viewer rebuilds the worker)
             return self.remove(msg["remove"]["ranges"], msg["remove"].get("sceneRemap"))
+        if "resize" in msg:                              # (nor this one: its Viewer rebuilds the worker when maxSplatCount changes)
+            return self.resize(msg["resize"]["maxSplatCount"])
         raise ValueError("unknown sort-worker message: " + ", ".join(msg.keys()))
 
     def _reply(self, msg):
@@ -158,6 +160,16 @@ class SortWorker:
         L.check(self.lib.gs_sorter_remove(self.handle, r.ctypes.data if n else None, n, m.ctypes.data if m is not None else None, mc))
         self.uploaded_splat_count -= removed_below(r, self.uploaded_splat_count)
         self.gathered_count = 0
+
+    def resize(self, max_splat_count):
+        """gs_sorter_resize: the capacity (maxSplatCount) becomes max_splat_count (>= uploaded_splat_count), larger or smaller, on
+        the device; the centres stay.  What adding a scene needs: resize, then the `centers` message of the new range only.  The
+        resident result and a gathered list are forgotten unless the capacity is the one the worker has: sort again."""
+        n = int(max_splat_count)
+        L.check(self.lib.gs_sorter_resize(self.handle, n))
+        if n != self.max_splat_count:
+            self.max_splat_count = n
+            self.gathered_count = 0
 
     def set_frustum_cull(self, enable=True):
         """Fuse a per-splat frustum cull into full sorts (gs_sorter_set_frustum_cull): the result is the reference's

@@ -130,6 +130,20 @@ class SplatMesh:
         L.check(self.lib.gs_mesh_reorder(self.handle, int(frm), int(count)))
         return self
 
+    def resize(self, max_splat_count):
+        """gs_mesh_resize: the capacity becomes max_splat_count (>= splat_count), larger or smaller, on the device - the planes
+        are copied there, nothing crosses the bus, and the mesh then behaves as a fresh one of that capacity that received the
+        same uploads.  What adding a scene to a live mesh needs: resize, then build(..., start=splat_count).  The last draw, a
+        pending project() and bound sorters' results are forgotten unless the capacity is the one the mesh has."""
+        n = int(max_splat_count)
+        L.check(self.lib.gs_mesh_resize(self.handle, n))
+        if n != self.max_splat_count:
+            scene_of = np.zeros(n, np.uint32)                  # the host copy of the scene indexes follows
+            keep = min(n, self.max_splat_count)
+            scene_of[:keep] = self._scene_of[:keep]
+            self._scene_of, self.max_splat_count = scene_of, n
+        return self
+
     def set_scenes(self, transforms=None, camera_position=None, opacity=None, visible=None, sh8_range=None):
         """Per-scene uniforms: uniforms.transforms (dynamicMode), sceneOpacity / sceneVisibility
         (enableOptionalEffects), sphericalHarmonics8BitCompressionRangeMin/Max.  transforms: column-major 16-vectors;

@@ -140,6 +140,20 @@ int gs_sorter_set_uploaded_count(gs_sorter* s, uint32_t count);
 int gs_sorter_remove(gs_sorter* s, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* scene_remap,
                      uint32_t scene_remap_count);
 
+/* Change the capacity of a live sorter on the device: the sorter's half of gs_mesh_resize (a Viewer whose maxSplatCount changed
+ * drops its sort worker and sends every centre again, src/Viewer.js:1123-1136).  uploaded splat count <= max_splat_count, larger
+ * or smaller than the current capacity.  Afterwards every sort's list is what a fresh sorter of the new capacity and the same flags
+ * gives that received the same centres by the same uploads: the rows as uploaded, the SoA planes and the scene indexes are copied
+ * on the device, the 16-bit centre planes are derived again, the extreme set stays (it depends on the rows alone), and the
+ * key / value / result buffers are allocated again as gs_sorter_create (or their first user) allocates them.  Flags, precision,
+ * cull switches and the mesh binding stay.  The call waits for the sort in flight; the resident result, a gathered list, the
+ * per-tree caches and device distances are dropped - sort again before the next draw.
+ * GS_OK and nothing happens when max_splat_count is the current capacity.  GS_ERR_INVALID, and nothing changes, for 0 or a value
+ * below the uploaded splat count.  GS_ERR_NOMEM: as for gs_mesh_resize - what the call allocated is released before the key /
+ * value buffers come back at their old size, the sorter keeps its capacity and its centres and stays usable; should even that
+ * fail, sorts are refused (GS_ERR_INVALID) until a gs_sorter_resize succeeds. */
+int gs_sorter_resize(gs_sorter* s, uint32_t max_splat_count);
+
 /* Optional coupling of the two seams: a sorter bound to a mesh leaves its device-resident result as positions in
  * that mesh's internal storage order, so gs_mesh_render(m, ..., sorter = s, ...) needs no per-frame index translation.
  * Host-visible results (sorted_out, gs_sorter_debug_read) are always the caller's splat indexes.  m = NULL unbinds. */
@@ -511,6 +525,27 @@ int gs_mesh_remove(gs_mesh* m, const uint32_t* ranges, uint32_t n_ranges, const 
  * when a position of the range was never uploaded, or when a border of the range falls inside a Morton run (gs_mesh_remove's
  * rule). */
 int gs_mesh_reorder(gs_mesh* m, uint32_t from, uint32_t count);
+
+/* Change the capacity of a live mesh on the device: what adding a scene to a mesh that is already drawing needs
+ * (Viewer.addSplatBuffersToMesh without dispose + rebuild, src/Viewer.js:1081-1141), and what gives memory back after a removal.
+ *   max_splat_count  uploaded count <= max_splat_count <= 2^28 (gs_mesh_create's limit), larger or smaller than the current one.
+ * Afterwards the mesh behaves, in every output, as a fresh mesh of the new capacity and the same flags that received the same
+ * splats by the same uploads.  The caller's numbering, the uploaded count, the Morton runs, the storage positions, destination, draw
+ * mode, deep-pass switch and scene parameters do not change; no splat data crosses the bus.  The first `uploaded` positions of every
+ * resident plane are copied on the device, the positions behind them hold what gs_mesh_create leaves there (zero planes, the
+ * identity permutation, boxes at the origin), and every buffer of the draw path that is sized by the capacity is allocated again
+ * as gs_mesh_create (or its first user) allocates it.  The call waits for the mesh's work in flight and for the sorters bound to
+ * it, and forgets what gs_mesh_remove forgets: a pending gs_mesh_project, the last draw, the statistics, and the resident result of
+ * every sorter bound to it.  Trees are not edited.  Resize the sorter with gs_sorter_resize, in either order; between the two
+ * calls a draw from a host list is safe.
+ * GS_OK and nothing happens - not even the last draw is forgotten - when max_splat_count is the current capacity.
+ * GS_ERR_INVALID, and nothing changes, for 0, a value above 2^28 or a value below the uploaded count (remove first).
+ * GS_ERR_NOMEM when the new buffers cannot be allocated: everything the call allocated is released first, then the draw buffers
+ * come back at the size they had - which needs no more memory than the mesh held before the call - and the mesh keeps its
+ * capacity and its splats and stays usable (the last draw is forgotten).  Should even that fail, because another owner took the
+ * memory meanwhile, the mesh keeps its splats but refuses draws, projections, uploads and gs_mesh_reorder (GS_ERR_INVALID) until
+ * a gs_mesh_resize - to any accepted capacity, the present one included - succeeds. */
+int gs_mesh_resize(gs_mesh* m, uint32_t max_splat_count);
 
 /* Per-scene uniforms (SplatMesh.updateUniforms :1263-1276, setupDataTextures :868-878). */
 typedef struct gs_scene_params {

@@ -22,7 +22,7 @@
 import * as THREE from 'three';
 import { createRequire } from 'module';
 const require = createRequire(import.meta.url);
-const { SplatMeshHIP: HipMeshCore, addon, assetAppend } = require('./gsplat.js');
+const { SplatMeshHIP: HipMeshCore, addon, assetAppend, Constants } = require('./gsplat.js');
 import { VisibleRegion, SceneRevealMode } from './VisibleRegion.mjs';
 
 export const SplatRenderMode = { ThreeD: 0, TwoD: 1 };
@@ -279,6 +279,76 @@ export class SplatMesh {
     if (edited) this.updateVisibleRegion(false);            // (a refresh ends with it)
     this.visible = survivors.length > 0;
     return { edited, ranges, sceneRemap };
+  }
+
+  // HIP-engine extra, for the body of Viewer.addSplatBuffersToMesh (src/Viewer.js:1189-1226) in place of build(allSplatBuffers, ...):
+  // `splatBuffers` become further scenes of a mesh that is already drawing.  Host bookkeeping as a build of all buffers leaves it
+  // (the SplatScene objects that exist stay - and their transforms -, new ones are appended; sceneOptions, the two global index
+  // maps, the lastBuild* fields, the visible region through updateVisibleRegion(false); the splat tree is disposed of: call
+  // buildSplatTree).  The device mesh is resized to the new getMaxSplatCount() in place (gs_mesh_resize: the resident planes are
+  // copied on the device) and only the new scenes are filled and uploaded - each by an upload of its own, one Morton run, so that
+  // removeScenes can take it out again.  Where that cannot be - no device mesh yet, a buffer still loading, a build that would
+  // choose another SH degree or SH format, more than Constants.MaxScenes scenes - the mesh is built afresh from all buffers, as
+  // before.  Returns {edited, from, to, count, centers, sceneIndexes}: refreshGPUDataFromSplatBuffers' reply for the new range when
+  // edited is true - post `{resize: {maxSplatCount}}` to the sort worker, then the ordinary `centers` message for that range -
+  // and build()'s reply for every splat otherwise (the worker is rebuilt, as the reference does).
+  addScenes(splatBuffers, sceneOptions = []) {
+    const before = this.scenes.length;
+    const options = Array.from({ length: before }, (_, k) => (this.sceneOptions || [])[k] || {}).concat(splatBuffers.map((_, k) => sceneOptions[k] || {}));
+    const buffers = this.scenes.map((sc) => sc.splatBuffer).concat(splatBuffers);
+    const degree = buffers.reduce((d, buffer) => Math.min(d, buffer.getMinSphericalHarmonicsDegree()), Math.min(3, this.sphericalHarmonicsDegree));
+    const level = Math.max(1, ...buffers.map((buffer) => buffer.compressionLevel));
+    const inPlace = !!this.core && before > 0 && splatBuffers.length > 0 && !this._stream() && buffers.length <= Constants.MaxScenes &&
+                    buffers.every((buffer) => buffer.getSplatCount() === buffer.getMaxSplatCount()) &&
+                    this.lastBuildSplatCount === this.getSplatCount(true) && degree === this.minSphericalHarmonicsDegree && level === this.shCompressionLevel;
+    if (!inPlace) return Object.assign({ edited: false }, this.build(buffers, options, true, this.finalBuild));
+    const from = this.getSplatCount(true);
+    this.disposeSplatTree();
+    const added = SplatMesh.buildScenes(this, splatBuffers, options.slice(before));
+    this.scenes = this.scenes.concat(added);
+    this.sceneOptions = options;
+    const maps = SplatMesh.buildSplatIndexMaps(buffers);
+    this.globalSplatIndexToLocalSplatIndexMap = maps.localSplatIndexMap;
+    this.globalSplatIndexToSceneIndexMap = maps.sceneIndexMap;
+    this.updateTransforms();                                // the new scenes' matrices exist before their data is filled
+    const maxSplatCount = this.getMaxSplatCount();
+    this.core.resize(maxSplatCount);
+    Object.assign(this.splatDataTextures, { maxSplatCount });
+    const count = this.getSplatCount(true) - from;
+    const covLevel = this.getTargetCovarianceCompressionLevel(), shComponents = [0, 9, 24][this.minSphericalHarmonicsDegree];
+    const xyz = new Float32Array(count * 3);                // the new range's centres, for the sort worker
+    let at = 0;
+    for (let k = before; k < this.scenes.length; k++) {
+      const c = this.scenes[k].splatBuffer.getSplatCount();
+      if (c > 0) {
+        const covariances = covLevel === 1 ? new Uint16Array(c * 6) : new Float32Array(c * 6);
+        const centers = xyz.subarray(at * 3, (at + c) * 3), colors = new Uint8Array(c * 4);
+        let sh = null;
+        if (shComponents) sh = this.shCompressionLevel === 2 ? new Uint8Array(c * shComponents) : new Uint16Array(c * shComponents);
+        this.fillSplatDataArrays(covariances, null, null, centers, colors, sh, undefined, covLevel, 0, this.shCompressionLevel, undefined, undefined, 0, k);
+        addon.meshUpload(this.core.handle, from + at, c, centers, covLevel === 1 ? null : covariances, covLevel === 1 ? covariances : null, colors,
+                         sh && this.shCompressionLevel !== 2 ? sh : null);
+        if (sh && this.shCompressionLevel === 2) addon.meshUploadShU8(this.core.handle, from + at, c, sh);
+      }
+      at += c;
+    }
+    this.core.splatCount = Math.max(this.core.splatCount, from + count);
+    const sceneIndexes = new Uint32Array(count);
+    for (let c = 0; c < count; c++) sceneIndexes[c] = this.globalSplatIndexToSceneIndexMap[from + c];
+    if (count > 0) this.core.setSceneIndexes(sceneIndexes, from);   // (several scenes: the mesh holds scene indexes in every mode)
+    Object.assign(this, { lastBuildScenes: this.scenes.slice(), lastBuildSplatCount: from + count,
+                          lastBuildMaxSplatCount: maxSplatCount, lastBuildSceneCount: this.scenes.length });
+    this._scenesDirty = true;
+    this.updateVisibleRegion(false);
+    this.visible = true;
+    // the centres as getDataForDistancesComputation hands them over (:572-581): x1000 rounded to int32, or float; four per splat
+    const centers = this.integerBasedDistancesComputation ? new Int32Array(count * 4) : new Float32Array(count * 4);
+    for (let k = 0, o = 0; k < xyz.length; k += 3, o += 4) {
+      if (this.integerBasedDistancesComputation) {
+        centers[o] = Math.round(xyz[k] * 1000.0); centers[o + 1] = Math.round(xyz[k + 1] * 1000.0); centers[o + 2] = Math.round(xyz[k + 2] * 1000.0); centers[o + 3] = 1000;
+      } else { centers[o] = xyz[k]; centers[o + 1] = xyz[k + 1]; centers[o + 2] = xyz[k + 2]; centers[o + 3] = 1.0; }
+    }
+    return { edited: true, from, to: from + count - 1, count, centers, sceneIndexes };
   }
 
   // setupDataTextures' decisions (:637-690, 1060-1090) without the textures: covariance as fp16 when asked for, SH as fp16

@@ -139,6 +139,27 @@ class HipSortWorker {
       let gone = 0;
       for (let k = 0; k < ranges.length; k += 2) gone += Math.max(0, Math.min(ranges[k] + ranges[k + 1], this.uploadedSplatCount) - Math.min(ranges[k], this.uploadedSplatCount));
       this.uploadedSplatCount -= gone;
+    } else if (msg.resize) {
+      // HIP-engine extra (the reference's Viewer drops a worker whose maxSplatCount changed and sends every centre again,
+      // src/Viewer.js:1123-1136): the capacity changes on the device, the centres stay; then the `centers` message of the
+      // new range only.  The host-side index, result and distance arrays grow with it (they never shrink: views stay valid).
+      const n = msg.resize.maxSplatCount >>> 0;
+      addon.sorterResize(this.handle, n);
+      this.maxSplatCount = n;                                               // what Viewer.js:1124 compares
+      if (n * 4 > this.sortedIndexesBuffer.byteLength) {
+        const AB = this.sortedIndexesBuffer.constructor;
+        const grown = (old) => { const b = new AB(n * 4); new Uint8Array(b).set(new Uint8Array(old)); return b; };
+        this.indexesToSortBuffer = grown(this.indexesToSortBuffer);
+        this.sortedIndexesBuffer = grown(this.sortedIndexesBuffer);
+        this.precomputedDistancesBuffer = grown(this.precomputedDistancesBuffer);
+      }
+      const reply = { sortResized: true, maxSplatCount: n };
+      if (this.useSharedMemory) {
+        Object.assign(reply, { indexesToSortBuffer: this.indexesToSortBuffer, indexesToSortOffset: 0,
+          sortedIndexesBuffer: this.sortedIndexesBuffer, sortedIndexesOffset: 0,
+          precomputedDistancesBuffer: this.precomputedDistancesBuffer, precomputedDistancesOffset: 0 });
+      }
+      setImmediate(() => this._emit(reply));
     } else if (msg.init) {
       // the reference ships its WASM bytes through an init message (SortWorker.js:116-199); nothing to do here
     }
@@ -276,6 +297,11 @@ class SplatMeshHIP {
   // the Morton runs (one per fresh upload) inside [from, from + count) become one run on the device: the layout one upload of the
   // range would have left.  The numbering stays; nothing happens where the range holds at most one run.
   reorder(from = 0, count = this.splatCount - from) { addon.meshReorder(this.handle, from >>> 0, Math.max(0, count) >>> 0); }
+  // the capacity becomes maxSplatCount (>= splatCount) on the device: the planes are copied there, nothing crosses the bus
+  resize(maxSplatCount) {
+    addon.meshResize(this.handle, maxSplatCount >>> 0);
+    this.maxSplatCount = maxSplatCount >>> 0;
+  }
   setSceneIndexes(sceneIndexes, start = 0) { addon.meshUploadSceneIndexes(this.handle, start, sceneIndexes.length, sceneIndexes); }
   setScenes(params) { addon.meshSetScenes(this.handle, params); this.hasScenes = true; }
   // the fade-in of SplatMesh.updateVisibleRegionFadeDistance: visibleRegionFadeStartRadius + sceneCenter; null switches it off

@@ -343,6 +343,22 @@ static napi_value MeshReorder(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* meshResize(mesh, maxSplatCount) and sorterResize(sorter, maxSplatCount): the capacity changes on the device, the uploaded splats
+ * stay where they are (gs_mesh_resize / gs_sorter_resize) */
+static napi_value resize_call(napi_env env, napi_callback_info info, int sorter) {
+    ARGS(2)
+    void* h = get_external(env, argv[0]);
+    const uint32_t n = get_u32(env, argv[1]);
+    int st;
+
+    if (sorter) { LOCKED(st = gs_sorter_resize((gs_sorter*)h, n)); }
+    else { LOCKED(st = gs_mesh_resize((gs_mesh*)h, n)); }
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+static napi_value MeshResize(napi_env env, napi_callback_info info) { return resize_call(env, info, 0); }
+static napi_value SorterResize(napi_env env, napi_callback_info info) { return resize_call(env, info, 1); }
+
 /* meshStoragePositions(mesh, out Uint32Array): test hook - the storage position of splats [0, out.length) by original index
  * (gs_mesh_debug_read 12: the layout uploads and meshReorder leave) */
 static napi_value MeshStoragePositions(napi_env env, napi_callback_info info) {
@@ -1179,7 +1195,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"treeSceneLeaves", TreeSceneLeaves}, {"treeGatherScenes", TreeGatherScenes},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
-        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove}, {"meshReorder", MeshReorder}, {"meshStoragePositions", MeshStoragePositions},
+        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove}, {"meshReorder", MeshReorder}, {"meshResize", MeshResize}, {"sorterResize", SorterResize},{"meshStoragePositions", MeshStoragePositions},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
