@@ -18,6 +18,8 @@ GS_OK, GS_WARN_KEY_CLAMPED, GS_WARN_FRAME_TRUNCATED = 0, 1, 2
 GS_ERR_INVALID, GS_ERR_HIP, GS_ERR_NOMEM, GS_ERR_CAPACITY, GS_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 GS_SORT_INTEGER, GS_SORT_DYNAMIC = 1, 2
 GS_MESH_COV_HALF, GS_MESH_SH_U8, GS_MESH_KEEP_ORDER = 1, 2, 4
+GS_MESH_SURFEL = 8      # SplatRenderMode.TwoD: the covariance planes hold (scale xyz, rotation xyz)
+GS_DEBUG_RECORDS_2D = 15   # gs_mesh_debug_read: the 80-byte vertex-stage records of a GS_MESH_SURFEL mesh
 GS_CAM_ANTIALIASED, GS_CAM_POINT_CLOUD, GS_CAM_ORTHOGRAPHIC, GS_CAM_FADE_IN, GS_CAM_SCENE_EFFECTS, GS_CAM_DYNAMIC = 1, 2, 4, 8, 16, 32
 GS_CTX_SINGLE_STREAM, GS_CTX_STAGE_TIMING, GS_CTX_FORK_JOIN = 1, 2, 4
 GS_TILE = 16

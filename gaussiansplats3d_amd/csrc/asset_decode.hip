@@ -28,7 +28,8 @@ __device__ __forceinline__ double sh_lo(const NoTransform&) { return 0.0; }
 __device__ __forceinline__ double sh_hi(const NoTransform&) { return 0.0; }
 
 // One thread per splat: asset splat first + i -> element i of the staging arrays (MeshStaging).
-template <class Source, bool XF, class Transform>
+// SURFEL: into a GS_MESH_SURFEL mesh - the covariance slot receives (sx, sy, 1, qx, qy, qz) (asset_fill_splat)
+template <class Source, bool XF, class Transform, bool SURFEL = false>
 __global__ __launch_bounds__(256) void k_asset_decode(Source v, Transform xf, uint32_t first, uint32_t count, uint32_t min_alpha,
                                                       float* __restrict__ centers, float* __restrict__ cov_f32,
                                                       uint16_t* __restrict__ cov_f16, uint32_t* __restrict__ rgba,
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void k_asset_decode(Source v, Transform xf, ui
         v.load_table(table);
     }
     if (i >= count) return;
-    asset_fill_splat<XF, false>(v.row(first + i), transform_of(xf), v.sh_degree, v.ncomp, sh_lo(xf), sh_hi(xf), min_alpha, i, centers,
+    asset_fill_splat<XF, false, SURFEL>(v.row(first + i), transform_of(xf), v.sh_degree, v.ncomp, sh_lo(xf), sh_hi(xf), min_alpha, i, centers,
                                 cov_f32, cov_f16, rgba, sh_f16, sh_u8, nullptr, nullptr);
 }
 
@@ -84,7 +85,10 @@ struct AssetRows : MeshUploadSource {
         uint16_t* cov16 = half ? (uint16_t*)(s.base + s.off_cov) : nullptr;
         uint16_t* sh16 = s.sh_u8 ? nullptr : (uint16_t*)(s.base + s.off_sh);
         uint8_t* sh8 = s.sh_u8 ? (uint8_t*)(s.base + s.off_sh) : nullptr;
-        if (asset->has_transform)
+        if (m->flags & GS_MESH_SURFEL)                     // (never with a transform: gs_mesh_upload_asset refuses that)
+            hipLaunchKernelGGL((k_asset_decode<Source, false, NoTransform, true>), grid, block, 0, st, view, NoTransform{0u}, first + o, count,
+                               min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
+        else if (asset->has_transform)
             hipLaunchKernelGGL((k_asset_decode<Source, true, DevTransform>), grid, block, 0, st, view, dev_transform(asset), first + o, count,
                                min_alpha, (float*)s.base, cov32, cov16, (uint32_t*)(s.base + s.off_rgba), sh16, sh8);
         else
@@ -136,6 +140,8 @@ int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first,
     const bool mesh_u8 = (m->flags & GS_MESH_SH_U8) != 0;
     GS_REQUIRE(m->sh_degree == 0 || mesh_u8 == (a->level == 2),
                "GS_MESH_SH_U8 must be set exactly for a file whose SH are uint8 (gs_asset_info.sh_level == 2)");
+    GS_REQUIRE(!((m->flags & GS_MESH_SURFEL) && a->has_transform),
+               "a GS_MESH_SURFEL mesh takes untransformed scales and rotations: the asset has a scene transform (gs_asset_set_transform)");
     if (count == 0) return GS_OK;
     ScopedDevice sd(m->ctx->device);
     // (an earlier call's decode kernels have finished: every upload synchronises before it returns)

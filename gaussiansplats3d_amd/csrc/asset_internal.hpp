@@ -634,7 +634,10 @@ __host__ __device__ __forceinline__ void store_centre(const AssetTransform& t, c
 // pointer of each pair is set; scales / rotations are never looked at.  The host fill (HOST true) may leave any output out, may
 // ask for both covariance widths, and has scales / rotations on top.  HOST settles that at compile time: the kernels carry none
 // of the host's checks.  Rgba: uint32_t on the device (one aligned word), uint8_t on the host (the C ABI asks for no alignment).
-template <bool XF, bool HOST, class Row, class Rgba>
+// SURFEL (kernels only, never with XF): the mesh is a GS_MESH_SURFEL one and cov_f32 receives, in place of the covariance, the tuple
+// (sx, sy, 1, qx, qy, qz) - the host's `scales` and `rotations` outputs with the scaleOverride.z = 1 of SplatMesh.fillSplatDataArrays
+// in 2D mode (SplatMesh.js:1856-1863), as SplatMesh.updateScaleRotationsPaddedData stores them (:1155-1170).
+template <bool XF, bool HOST, bool SURFEL = false, class Row, class Rgba>
 __host__ __device__ __forceinline__ void asset_fill_splat(const Row row, const AssetTransform& t, uint32_t sh_degree, uint32_t ncomp,
                                                           double sh_lo, double sh_hi, uint32_t min_alpha, uint32_t i, float* centers,
                                                           float* cov_f32, uint16_t* cov_f16, Rgba* rgba, uint16_t* sh_f16, uint8_t* sh_u8,
@@ -662,7 +665,15 @@ __host__ __device__ __forceinline__ void asset_fill_splat(const Row row, const A
                 for (int k = 0; k < 4; k++) rotations[4 * (size_t)i + k] = (float)(q[k] * flip);
             }
         }
-        if (!HOST || cov_f32 || cov_f16) {
+        if constexpr (SURFEL) {
+            static_assert(!HOST && !XF, "the surfel tuple is a device output of the untransformed fill");
+            double q[4] = {x, y, z, w};                // as `rotations` above: Quaternion.normalize, then ensurePositiveW
+            row_normalize(q);
+            const double flip = q[3] < 0 ? -1 : 1;
+            float* o = cov_f32 + 6 * (size_t)i;
+            o[0] = (float)s3[0]; o[1] = (float)s3[1]; o[2] = 1.0f;
+            for (int k = 0; k < 3; k++) o[3 + k] = (float)(q[k] * flip);
+        } else if (!HOST || cov_f32 || cov_f16) {
             // Matrix4.makeRotationFromQuaternion = compose(zero, q, one) (three r160)
             const double x2 = x + x, y2 = y + y, z2 = z + z;
             const double xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2;

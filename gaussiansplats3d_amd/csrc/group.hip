@@ -300,6 +300,10 @@ int gs_group_render_gather(gs_group* g, gs_mesh* m, const gs_camera* cam, const 
     // Argument errors every rank sees alike (same tables, same root) may return early: no rank enters the collective.
     GS_REQUIRE(g && m && cam && row_begin && row_end, "group / mesh / camera / row tables == NULL");
     GS_REQUIRE(m->ctx == g->ctx, "mesh lives on another context");
+    if (m->flags & GS_MESH_SURFEL) {                       // (every rank holds the same kind of mesh: all of them return here)
+        gs_set_error("gs_group_render_gather: a GS_MESH_SURFEL mesh draws full frames only (no tile-row strips)");
+        return GS_ERR_UNSUPPORTED;
+    }
     GS_REQUIRE(root < g->world, "root outside the group");
     for (uint32_t r = 0; r < g->world; r++)
         GS_REQUIRE(row_begin[r] % GS_TILE == 0 && (row_end[r] % GS_TILE == 0 || row_end[r] == cam->height) &&

@@ -374,6 +374,24 @@ struct __attribute__((aligned(32))) SplatRec {
 };
 static_assert(sizeof(SplatRec) == 32, "SplatRec must be one 32-byte sector");
 
+// Vertex-stage record of a GS_MESH_SURFEL mesh (SplatRenderMode.TwoD; project_2d.hip writes it, tile_blend_2d.hip stages it as it
+// is): the varyings of SplatMaterial2D's vertex shader plus the quad as the rasteriser sees it.  80 B, five aligned 16-byte reads.
+//   tu, tv, tw     vT[0], vT[1], vT[2]: the splat-to-pixel homography's rows (SplatMaterial2D.js:125, 231)
+//   qcx, qcy       vQuadCenter (:187 the AABB branch's pointImage in pixels; :232 center.xy - in NDC, as the shader has it)
+//   cx, cy         the quad's centre in pixels (GL window coordinates, row 0 = bottom)
+//   i00 .. i11     inverse of the quad's 2x2 basis in pixels: the pixel centre f is inside the quad iff
+//                  |i00 dx + i01 dy| <= 1 and |i10 dx + i11 dy| <= 1 with d = f - (cx, cy); a diagonal for the square branch
+//   c0, c1         colour and opacity as in SplatRec
+struct __attribute__((aligned(16))) SurfelRec {
+    float tu[3], tv[3], tw[3];
+    float qcx, qcy;
+    float cx, cy;
+    float i00, i01, i10, i11;
+    uint32_t c0, c1, pad;
+};
+static_assert(sizeof(SurfelRec) == 80, "SurfelRec is 20 words");
+constexpr uint32_t GS_PROJECT_INSTANCE_2D = 8u;    // gs_mesh::last_project_instance: the surfel kernel ran (with bits 0..2 as for k_project)
+
 struct RenderFrame {          // device-resident per-draw scalars
     uint32_t visible;         // splats passing the vertex-stage rejects
     uint32_t entries_lo;      // total tile entries D (uint64 split for atomics-free writes)
@@ -430,6 +448,7 @@ DrawSwitches draw_switches();
 // One set of the vertex stage's outputs, with everything that belongs to it (gs_mesh::sets).
 struct ProjSet {
     DevBuf recs;               // SplatRec [n]  survivors compacted inside each 256-splat block (project.hip)
+    DevBuf recs2d;             // SurfelRec [n] the same slots, GS_MESH_SURFEL meshes only (project_2d.hip; `recs` stays unwritten there)
     DevBuf zrec;               // float [n]     the survivor's window-space centre depth, same slots (only while a destination
                                //               depth is set: the blend's depth test, gs_mesh_set_destination)
     DevBuf rects;              // uint2 [n]     tile rect per survivor, same slots
@@ -652,6 +671,8 @@ int gs_launch_project(gs_mesh* m, const ProjectParams& pp, int orig_mask, hipEve
                       bool whole_stage = false);
 int gs_launch_binning(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, const uint32_t* order_dev, gs_sorter* sorter, uint32_t render_count);
 int gs_launch_blend(gs_mesh* m, const DrawSwitches& sw, const DrawFeedback& fb, const ProjectParams& pp, uint8_t* out_dev);
+// the draw of a GS_MESH_SURFEL mesh (tile_blend_2d.hip): k_tile_blend_2d over the same lists, per-bin statistics as gs_launch_blend
+int gs_launch_blend_2d(gs_mesh* m, const ProjectParams& pp, uint8_t* out_dev);
 int gs_launch_rop8_window(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* out_dev);
 int gs_launch_surface(gs_mesh* m, const ProjectParams& pp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float threshold,
                       uint32_t* ids_dev, float* depth_dev);   // either output may be null

@@ -78,13 +78,20 @@ __device__ __forceinline__ float cov_spectral_bound(float c0, float c1, float c2
 
 __global__ __launch_bounds__(256) void k_split_cov_f32(const float* __restrict__ c6, uint32_t count, uint32_t from,
                                                        const uint32_t* __restrict__ perm, float4* __restrict__ a,
-                                                       float2* __restrict__ b, float* __restrict__ bound) {
+                                                       float2* __restrict__ b, float* __restrict__ bound, bool surfel) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
         const float* s = c6 + 6 * (size_t)i;
         const uint32_t d = DST(i);
         a[d] = make_float4(s[0], s[1], s[2], s[3]);
         b[d] = make_float2(s[4], s[5]);
-        bound[d] = cov_spectral_bound(s[0], s[1], s[2], s[3], s[4], s[5]);
+        // a GS_MESH_SURFEL mesh: the six values are (sx, sy, sz, qx, qy, qz), and the covariance R S S R^T they stand for has the
+        // spectral radius max s^2 exactly (NaN stays NaN, as below)
+        if (surfel) {
+            const float q0 = s[0] * s[0], q1 = s[1] * s[1], q2 = s[2] * s[2];
+            bound[d] = (q0 != q0 || q1 != q1 || q2 != q2) ? NAN : fmaxf(q0, fmaxf(q1, q2));
+        } else {
+            bound[d] = cov_spectral_bound(s[0], s[1], s[2], s[3], s[4], s[5]);
+        }
     }
 }
 
@@ -126,7 +133,8 @@ __global__ __launch_bounds__(256) void k_debug_expand(const unsigned long long* 
                                                       const uint32_t* __restrict__ perm, const uint4* __restrict__ recs,
                                                       const uint2* __restrict__ rects, uint4* __restrict__ out_recs,
                                                       uint2* __restrict__ out_rects, unsigned long long* __restrict__ out_mask,
-                                                      uint32_t* __restrict__ out_slots) {
+                                                      uint32_t* __restrict__ out_slots, const uint4* __restrict__ recs2d,
+                                                      uint4* __restrict__ out_recs2d) {
     const uint32_t orig = blockIdx.x * 256u + threadIdx.x;
     const uint32_t i = orig < count ? (perm ? perm[orig] : orig) : 0u;     // internal position of this original splat
     const unsigned long long* mw = vis_mask + ((i >> 8) << 2);
@@ -144,6 +152,8 @@ __global__ __launch_bounds__(256) void k_debug_expand(const unsigned long long* 
         out_recs[2 * (size_t)orig] = vis ? recs[2 * (size_t)slot] : z;
         out_recs[2 * (size_t)orig + 1] = vis ? recs[2 * (size_t)slot + 1] : z;
     }
+    if (out_recs2d)                                                         // (a GS_MESH_SURFEL mesh: SurfelRec, 5 x 16 bytes)
+        for (uint32_t k = 0; k < 5u; k++) out_recs2d[5 * (size_t)orig + k] = vis ? recs2d[5 * (size_t)slot + k] : z;
     if (out_rects) out_rects[orig] = vis ? rects[slot] : make_uint2(0xFFFFu, 0u);
     if (out_slots) out_slots[orig] = vis ? slot : 0xFFFFFFFFu;              // the slot the entry lists name the splat by
 }
@@ -270,13 +280,15 @@ std::vector<CapBuf> gs_mesh_capacity_list(gs_mesh* m, uint32_t capacity) {
     A(m->rect_q, n * 8 + 2048, 8, CAP_SCRATCH); A(m->cidx, n * 4 + 1024, 4, CAP_SCRATCH); A(m->coff, n * 4 + 1024, 4, CAP_SCRATCH);
     for (int k = 0; k < (m->two_sets ? 2 : 1); k++) {
         ProjSet& ps = m->sets[k];
-        A(ps.recs, n * sizeof(SplatRec), sizeof(SplatRec), CAP_SCRATCH);
+        // (a GS_MESH_SURFEL mesh never writes or reads 32-byte records: its 80-byte ones are recs2d below)
+        if (!(m->flags & GS_MESH_SURFEL)) A(ps.recs, n * sizeof(SplatRec), sizeof(SplatRec), CAP_SCRATCH);
         A(ps.rects, blocks * 256 * 8, 8, CAP_SCRATCH);        // whole blocks: whatever slot a 4-byte look-up word's escape names is inside (bin_word.hpp)
         A(ps.vis_mask, blocks * 32 + 32, 32, CAP_SCRATCH);    // whole 256-splat blocks: 4 words each
         A(ps.vis32, blocks * 64 + 64, 64, CAP_SCRATCH);
         A(ps.prect, blocks * 256 * 8 + 64, 8, CAP_SCRATCH);
         A(ps.block_any, (blocks + 127) & ~(size_t)63, 1, CAP_SCRATCH);
         A(ps.zrec, 0, 0, CAP_LAZY);                           // (zrec and vis_orig: sized by the first vertex stage that writes them, project.hip)
+        A(ps.recs2d, 0, 0, CAP_LAZY);                         // (a GS_MESH_SURFEL mesh's records: by its vertex stage, project_2d.hip)
         A(ps.vis_orig, 0, 0, CAP_LAZY);
     }
     // the tile entries: a fresh mesh's first guess, or the size they have grown to (they never shrink; gs_mesh_alloc_entries)
@@ -320,7 +332,9 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     GS_REQUIRE(max_splat_count > 0, "max_splat_count == 0");
     GS_REQUIRE(max_splat_count <= (1u << 28), "max_splat_count > 2^28");
     GS_REQUIRE(sh_degree <= 2, "sh_degree > 2 (the reference renders degrees 0..2, src/Viewer.js:154)");
-    GS_REQUIRE((flags & ~(GS_MESH_COV_HALF | GS_MESH_SH_U8 | GS_MESH_KEEP_ORDER)) == 0, "unknown mesh flags");
+    GS_REQUIRE((flags & ~(GS_MESH_COV_HALF | GS_MESH_SH_U8 | GS_MESH_KEEP_ORDER | GS_MESH_SURFEL)) == 0, "unknown mesh flags");
+    GS_REQUIRE(!((flags & GS_MESH_SURFEL) && (flags & GS_MESH_COV_HALF)),
+               "GS_MESH_SURFEL | GS_MESH_COV_HALF: scales and rotations are stored in fp32 (scaleRotationCompressionLevel 0)");
     ScopedDevice sd(ctx->device);
     gs_mesh* m = new (std::nothrow) gs_mesh();
     if (!m) return GS_ERR_NOMEM;
@@ -336,7 +350,7 @@ int gs_mesh_create(gs_context* ctx, uint32_t max_splat_count, uint32_t sh_degree
     m->no_block_list = getenv("GSPLAT_NO_BLOCK_LIST") != nullptr;
     m->no_coarse_vis = getenv("GSPLAT_NO_COARSE_VIS") != nullptr;
     m->block_test_always = getenv("GSPLAT_BLOCK_TEST_ALWAYS") != nullptr;
-    m->no_deep = getenv("GSPLAT_NO_DEEP") != nullptr;
+    m->no_deep = getenv("GSPLAT_NO_DEEP") != nullptr || (flags & GS_MESH_SURFEL);   // (the surfel blend has no deep pass)
     if (const char* ls = getenv("GSPLAT_LIST_SHIFT"))
         if (ls[0] >= '1' && ls[0] <= '6' && ls[1] == '\0') m->forced_list_shift = ls[0] - '0';
     // (a context with one stream runs the frames' kernels in order: a second set would never be written early)
@@ -590,7 +604,7 @@ static int mesh_commit_segment(gs_mesh* m, const UploadSegment& seg, const MeshS
                            m->covB.as<uint32_t>(), m->cov_bound.as<float>());
     else
         hipLaunchKernelGGL(k_split_cov_f32, g, b, 0, st, (const float*)(stg + s.off_cov), count, from, perm, m->covA.as<float4>(),
-                           m->covB.as<float2>(), m->cov_bound.as<float>());
+                           m->covB.as<float2>(), m->cov_bound.as<float>(), (m->flags & GS_MESH_SURFEL) != 0u);
     if (s.ncoef && s.sh_u8)
         hipLaunchKernelGGL(k_split_sh_u8, g, b, 0, st, (const uint8_t*)(stg + s.off_sh), count, from, perm, s.ncoef, m->sh0.as<uint4>(),
                            m->sh1.as<uint2>());
@@ -855,7 +869,8 @@ static int mesh_draw_once(gs_mesh* m, const DrawSwitches& sw, const ProjectParam
     const DrawFeedback fb = read_feedback(m->mirror_host);
     GS_TRY(gs_launch_binning(m, sw, fb, pp, order_dev, sorter, R));   // records ev[2] between emit and the tile sort
     if (timed) GS_HIP(hipEventRecord(m->ev[3], st));
-    GS_TRY(gs_launch_blend(m, sw, fb, pp, out_dev));
+    if (m->flags & GS_MESH_SURFEL) GS_TRY(gs_launch_blend_2d(m, pp, out_dev));      // SplatRenderMode.TwoD (tile_blend_2d.hip)
+    else GS_TRY(gs_launch_blend(m, sw, fb, pp, out_dev));
     // whose bins, draw mode and view the per-bin blend statistics now describe.  (An empty strip blends nothing: the statistics
     // stay those of the bins before it; a GS_DRAW_ROP8 draw's neither order a later fp32 draw's bins nor pick its deep bins.)
     if (m->plan.blend_bins > 0u) {
@@ -918,6 +933,10 @@ static int mesh_params(gs_mesh* m, const gs_camera* cam, ProjectParams& pp) {
     pp.row_end = cam->tile_row_end;
     if (pp.row_begin == 0 && pp.row_end == 0) pp.row_end = pp.tiles_y;
     GS_REQUIRE(pp.row_begin <= pp.row_end && pp.row_end <= pp.tiles_y, "tile row range outside the viewport");
+    if ((m->flags & GS_MESH_SURFEL) && (cam->tile_row_begin != 0u || cam->tile_row_end != 0u)) {
+        gs_set_error("a GS_MESH_SURFEL mesh draws full frames only: tile_row_begin / tile_row_end must be 0, 0");
+        return GS_ERR_UNSUPPORTED;
+    }
     pp.count = m->uploaded;
     // whole-block tests assume one modelView for every splat of a block: off under per-scene transforms (and GSPLAT_NO_BLOCK_CULL)
     pp.block_cull = (!(cam->flags & GS_CAM_DYNAMIC) && !m->no_block_cull) ? 1u : 0u;
@@ -1145,13 +1164,17 @@ int gs_mesh_kernel_time(gs_mesh* m, int which, int reset, double* sum_ms, uint32
 int gs_mesh_set_draw_mode(gs_mesh* m, uint32_t mode) {
     GS_REQUIRE(m, "mesh == NULL");
     GS_REQUIRE(mode == GS_DRAW_FP32 || mode == GS_DRAW_ROP8 || mode == GS_DRAW_ROP8_FULL, "unknown draw mode");
+    if ((m->flags & GS_MESH_SURFEL) && mode != GS_DRAW_FP32) {
+        gs_set_error("a GS_MESH_SURFEL mesh draws in GS_DRAW_FP32 only: there is no ROP8 composite of surfels");
+        return GS_ERR_UNSUPPORTED;
+    }
     m->draw_mode = mode;
     return GS_OK;
 }
 
 int gs_mesh_set_deep_pass(gs_mesh* m, int enabled) {
     GS_REQUIRE(m, "mesh == NULL");
-    m->no_deep = !enabled;
+    m->no_deep = !enabled || (m->flags & GS_MESH_SURFEL);   // (a surfel mesh has no deep pass to switch on: accepted, ignored)
     return GS_OK;
 }
 
@@ -1177,18 +1200,22 @@ int gs_mesh_debug_read(gs_mesh* m, int what, void* dst, uint32_t count) {
         GS_HIP(hipStreamSynchronize(st));
         return GS_OK;
     }
-    GS_REQUIRE(m->has_draw && ((what >= 2 && what != 9) || count <= m->last_count), "no draw / count too large");
-    if (what == 0 || what == 1 || what == 3 || what == 9) {
+    GS_REQUIRE(m->has_draw && ((what >= 2 && what != 9 && what != 15) || count <= m->last_count), "no draw / count too large");
+    const bool surfel = (m->flags & GS_MESH_SURFEL) != 0u;
+    GS_REQUIRE(!(what == 0 && surfel), "a GS_MESH_SURFEL mesh has no 32-byte records: read its 80-byte ones with what = 15");
+    GS_REQUIRE(!(what == 15 && !surfel), "what = 15 reads the records of a GS_MESH_SURFEL mesh");
+    if (what == 0 || what == 1 || what == 3 || what == 9 || what == 15) {
         if (count == 0) return GS_OK;
         const uint32_t splats = what == 3 ? (count * 64u < m->last_count ? count * 64u : m->last_count) : count;
-        const size_t bytes = what == 3 ? (size_t)count * 8 : (size_t)count * (what == 0 ? sizeof(SplatRec) : what == 9 ? 4 : 8);
+        const size_t bytes = what == 3 ? (size_t)count * 8 : (size_t)count * (what == 0 ? sizeof(SplatRec) : what == 15 ? sizeof(SurfelRec) : what == 9 ? 4 : 8);
         GS_REQUIRE(what != 3 || (size_t)count * 8 <= ps.vis_mask.bytes, "count exceeds the mask length");
         GS_TRY(m->staging.ensure(bytes + 64));
         if (what == 3) GS_HIP(hipMemsetAsync(m->staging.p, 0, bytes, st));
         hipLaunchKernelGGL(k_debug_expand, dim3((splats + 255u) / 256u), dim3(256), 0, st, ps.vis_mask.as<unsigned long long>(), ps.vis32.as<uint2>(), splats,
                            m->reorder ? m->perm.as<uint32_t>() : nullptr, ps.recs.as<uint4>(), ps.rects.as<uint2>(),
                            what == 0 ? m->staging.as<uint4>() : nullptr, what == 1 ? m->staging.as<uint2>() : nullptr,
-                           what == 3 ? m->staging.as<unsigned long long>() : nullptr, what == 9 ? m->staging.as<uint32_t>() : nullptr);
+                           what == 3 ? m->staging.as<unsigned long long>() : nullptr, what == 9 ? m->staging.as<uint32_t>() : nullptr,
+                           ps.recs2d.as<uint4>(), what == 15 ? m->staging.as<uint4>() : nullptr);
         GS_HIP(hipGetLastError());
         GS_HIP(hipMemcpyAsync(dst, m->staging.p, bytes, hipMemcpyDeviceToHost, st));
     } else if (what == 2) {   // [begin,end) of every tile of the last draw's strip; count = number of tiles
@@ -1297,6 +1324,10 @@ int gs_mesh_set_destination(gs_mesh* m, const gs_destination* dest) {
 
 int gs_mesh_debug_rop8(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint8_t* rgba_out_host) {
     GS_REQUIRE(m && rgba_out_host, "mesh / out == NULL");
+    if (m->flags & GS_MESH_SURFEL) {
+        gs_set_error("gs_mesh_debug_rop8: not available for a GS_MESH_SURFEL mesh (there is no ROP8 composite of surfels)");
+        return GS_ERR_UNSUPPORTED;
+    }
     GS_REQUIRE(m->has_draw, "no draw yet");
     //  on a context with two sets of vertex-stage outputs a gs_mesh_project for the NEXT frame has swapped the sets:
     // the last draw's lists would be composited against the other set's records
@@ -1322,6 +1353,10 @@ int gs_mesh_debug_rop8(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uin
 int gs_mesh_surface(gs_mesh* m, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, float threshold, uint32_t* ids_out_host,
                     float* depth_out_host, void* ids_out_dev, void* depth_out_dev) {
     GS_REQUIRE(m, "mesh == NULL");
+    if (m->flags & GS_MESH_SURFEL) {
+        gs_set_error("gs_mesh_surface: not available for a GS_MESH_SURFEL mesh (the surface pass walks 3D records)");
+        return GS_ERR_UNSUPPORTED;
+    }
     GS_REQUIRE(ids_out_host || depth_out_host || ids_out_dev || depth_out_dev, "gs_mesh_surface: all four outputs are NULL");
     GS_REQUIRE(!(ids_out_host && ids_out_dev), "gs_mesh_surface: pass the id plane on the host OR on the device, not both");
     GS_REQUIRE(!(depth_out_host && depth_out_dev), "gs_mesh_surface: pass the depth plane on the host OR on the device, not both");

@@ -20,12 +20,14 @@ class SplatMesh:
     def __init__(self, context, max_splat_count, spherical_harmonics_degree=0, half_precision_covariances=False,
                  antialiased=False, kernel_2d_size=0.3, max_screen_space_splat_size=1024.0, splat_scale=1.0,
                  point_cloud_mode=False, spherical_harmonics_8bit=False, dynamic_mode=False,
-                 enable_optional_effects=False, keep_order=False, scene_fade_in_rate_multiplier=1.0):
+                 enable_optional_effects=False, keep_order=False, scene_fade_in_rate_multiplier=1.0, render_mode_2d=False):
         self.ctx = context
         self.lib = context.lib
         self.max_splat_count = int(max_splat_count)
         self.sh_degree = int(spherical_harmonics_degree)
-        self.half_cov = bool(half_precision_covariances)
+        self.render_mode_2d = bool(render_mode_2d)             # splatRenderMode: SplatRenderMode.TwoD (GS_MESH_SURFEL)
+        # (2D mode stores scales and rotations in fp32 whatever halfPrecisionCovariancesOnGPU says, SplatMesh.js:666-675)
+        self.half_cov = bool(half_precision_covariances) and not self.render_mode_2d
         self.antialiased = bool(antialiased)
         self.kernel_2d_size = float(kernel_2d_size)
         self.max_screen_space_splat_size = float(max_screen_space_splat_size)
@@ -51,19 +53,32 @@ class SplatMesh:
         L.check(self.lib.gs_mesh_create(context.handle, self.max_splat_count, self.sh_degree,
                                         (L.GS_MESH_COV_HALF if self.half_cov else 0) |
                                         (L.GS_MESH_SH_U8 if self.sh_8bit else 0) |
-                                        (L.GS_MESH_KEEP_ORDER if self.keep_order else 0), C.byref(self.handle)))
+                                        (L.GS_MESH_KEEP_ORDER if self.keep_order else 0) |
+                                        (L.GS_MESH_SURFEL if self.render_mode_2d else 0), C.byref(self.handle)))
         context._adopt(self)
 
     # -- build / data upload ------------------------------------------------------------------------
     def build(self, centers, covariances, colors, spherical_harmonics=None, start=0, scene_indexes=None,
-              covariances_are_half_bits=False):
+              covariances_are_half_bits=False, scales=None, rotations=None):
         """fillSplatDataArrays output -> device planes.  covariances: float32 [n,6]; narrowed with
         THREE.DataUtils.toHalfFloat semantics when half_precision_covariances (SplatBuffer.js:469-474).
         covariances_are_half_bits=True (half_precision_covariances meshes only): covariances is uint16 [n,6], half bit patterns
         the caller narrowed, stored as they are - the only way to store an inf or a NaN half, which toHalfFloat clamps away.
-        spherical_harmonics: float16 (or uint16 bit patterns) [n, 9|24], coefficient-major RGB triples."""
+        spherical_harmonics: float16 (or uint16 bit patterns) [n, 9|24], coefficient-major RGB triples.
+        A render_mode_2d mesh takes scales float32 [n,3] and rotations float32 [n,4] (x, y, z, w; normalised, w >= 0) as
+        fillSplatScaleRotationArray returns them, and no covariances: scale z becomes 1 (the scaleOverride of
+        SplatMesh.fillSplatDataArrays in 2D mode, SplatMesh.js:1856-1863) and (sx, sy, 1, qx, qy, qz) is what the device stores
+        (updateScaleRotationsPaddedData, :1155-1170)."""
         c = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 3)
         n = c.shape[0]
+        if self.render_mode_2d:
+            if scales is None or rotations is None or covariances is not None:
+                raise ValueError("a render_mode_2d mesh is built from scales= and rotations=, without covariances")
+            sc = np.array(scales, dtype=np.float32).reshape(n, 3)
+            sc[:, 2] = 1.0
+            covariances = np.concatenate([sc, np.asarray(rotations, dtype=np.float32).reshape(n, 4)[:, :3]], axis=1)
+        elif scales is not None or rotations is not None:
+            raise ValueError("scales= / rotations= belong to a render_mode_2d mesh")
         if covariances_are_half_bits:
             if not self.half_cov or np.asarray(covariances).dtype != np.uint16:
                 raise ValueError("covariances_are_half_bits needs a half_precision_covariances mesh and a uint16 array")
@@ -424,6 +439,21 @@ class SplatMesh:
         words = (n + 63) // 64
         mask = np.empty(words, dtype=np.uint64)
         L.check(self.lib.gs_mesh_debug_read(self.handle, 0, recs.ctypes.data, n))
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 1, rects.ctypes.data, n))
+        L.check(self.lib.gs_mesh_debug_read(self.handle, 3, mask.ctypes.data, words))
+        vis = np.unpackbits(mask.view(np.uint8), bitorder="little")[:n].astype(bool)
+        return recs, rects, vis
+
+    def debug_records_2d(self, count=None):
+        """Vertex-stage outputs of the last draw of a render_mode_2d mesh: (records uint32 [n,20] - as float32: vT rows Tu, Tv, Tw
+        [0:9], vQuadCenter [9:11], the quad's centre in pixels [11:13], the inverse of its 2x2 pixel basis [13:17]; then r|g<<16,
+        b|a<<16 (unorm16) and an unused word -, rects uint32 [n,2], visible bool [n]); defined where `visible` is set."""
+        n = self.splat_count if count is None else count
+        recs = np.empty((n, 20), dtype=np.uint32)
+        rects = np.empty((n, 2), dtype=np.uint32)
+        words = (n + 63) // 64
+        mask = np.empty(words, dtype=np.uint64)
+        L.check(self.lib.gs_mesh_debug_read(self.handle, L.GS_DEBUG_RECORDS_2D, recs.ctypes.data, n))
         L.check(self.lib.gs_mesh_debug_read(self.handle, 1, rects.ctypes.data, n))
         L.check(self.lib.gs_mesh_debug_read(self.handle, 3, mask.ctypes.data, words))
         vis = np.unpackbits(mask.view(np.uint8), bitorder="little")[:n].astype(bool)

@@ -444,6 +444,19 @@ int gs_asset_bytes(gs_asset* a, const void** data, uint64_t* bytes);
 #define GS_MESH_SH_U8 2u      /* SH stored as uint8 (compression level 2, SplatMesh.js:680-684,789,1064-1066):
                                  sphericalHarmonics8BitMode, dequantised per scene as v/255*(max-min)+min      */
 #define GS_SH_F16 0u          /* SH as fp16 (compression level <= 1, SplatMesh.js:1064-1066)                  */
+#define GS_MESH_SURFEL 8u     /* splatRenderMode: SplatRenderMode.TwoD (2D Gaussian splatting; SplatMesh.js:666-675, 763-786,
+                                 SplatMaterial2D.js): per splat the mesh stores scale x, y, z and rotation x, y, z (w is rebuilt in
+                                 the vertex stage) where a 3D mesh stores the six covariance values, always in fp32 - with
+                                 GS_MESH_COV_HALF gs_mesh_create is GS_ERR_INVALID (the reference keeps
+                                 scaleRotationCompressionLevel 0 whatever halfPrecisionCovariancesOnGPU says).  Every SH option
+                                 stays.  Draws restate SplatMaterial2D's vertex and fragment shaders (useRefImplementation =
+                                 false): splat_scale, kernel2d, max_splat_px, GS_CAM_ANTIALIASED, GS_CAM_POINT_CLOUD and the
+                                 per-scene opacity factor do not appear in that material and are ignored as it ignores them.
+                                 Uploads, gs_mesh_project + a visibility-culled sort, gs_mesh_set_destination,
+                                 gs_mesh_compute_distances, gs_mesh_bounds, trees, gs_mesh_remove / _reorder / _resize and the
+                                 statistics work as for a 3D mesh.  GS_ERR_UNSUPPORTED, mesh unchanged: gs_mesh_set_draw_mode
+                                 other than GS_DRAW_FP32, gs_mesh_debug_rop8, gs_mesh_surface, a camera with a tile-row strip,
+                                 gs_group_render_gather.  gs_mesh_set_deep_pass is accepted and ignored (no deep pass) */
 
 /* SplatMesh.build + setupDataTextures (SplatMesh.js:306-405, 637-898): device SoA planes instead of data
  * textures, so none of the 4096^2-texel limits apply. */
@@ -456,7 +469,11 @@ void gs_mesh_destroy(gs_mesh* m);
  *   cov     (m00,m01,m02,m11,m12,m22) per splat (SplatBuffer.js:440-486): cov_f32 float[6*count] for a
  *           full-precision mesh, cov_f16 uint16 (IEEE half bits)[6*count] for a GS_MESH_COV_HALF mesh -
  *           the caller narrows exactly as THREE.DataUtils.toHalfFloat does (SplatBuffer.js:469-474);
- *           exactly one of the two is non-NULL
+ *           exactly one of the two is non-NULL.  A GS_MESH_SURFEL mesh: cov_f32 carries (sx, sy, sz, qx, qy, qz) per splat, the
+ *           tuple SplatMesh.updateScaleRotationsPaddedData stores (SplatMesh.js:1155-1170) - the scale (z already overridden to 1
+ *           by the caller, as fillSplatDataArrays does in 2D mode, :1856-1863) and the x, y, z of the rotation normalised with
+ *           w >= 0; the bound of what = 10 is then the largest squared scale, the spectral radius of the covariance the tuple
+ *           stands for
  *   rgba    uint8[4*count]
  *   sh_f16  uint16 (IEEE half bits)[ncoef*count], coefficient-major RGB triples, ncoef = 0/9/24
  *           (SplatBuffer.js:680-728); NULL when the mesh has sh_degree 0. */
@@ -474,8 +491,10 @@ int gs_mesh_upload_sh_u8(gs_mesh* m, uint32_t from, uint32_t count, const uint8_
  * (SplatBuffer.js:440-486, 517-734) + SplatMesh.updateDataTexturesFromBaseData (SplatMesh.js:900-1062) in one call:
  * the file's rows cross to the device, not the decoded arrays; a scene transform (gs_asset_set_transform) is applied
  * there too.  GS_ERR_INVALID, and nothing changes, when a range is
- * out of bounds, the mesh's SH degree differs from gs_asset_info.sh_degree, or GS_MESH_SH_U8 disagrees with
- * sh_level == 2 for a degree > 0.  GS_MESH_COV_HALF is the mesh's choice; the device narrows with
+ * out of bounds, the mesh's SH degree differs from gs_asset_info.sh_degree, GS_MESH_SH_U8 disagrees with
+ * sh_level == 2 for a degree > 0, or a GS_MESH_SURFEL mesh is handed an asset with a scene transform (as gs_asset_fill refuses
+ * scales and rotations there).  Into a GS_MESH_SURFEL mesh the decode stores (sx, sy, 1, qx, qy, qz) per splat - bit for bit what
+ * gs_asset_fill(..., scales, rotations), the scaleOverride.z = 1 of 2D mode and gs_mesh_upload leave.  GS_MESH_COV_HALF is the mesh's choice; the device narrows with
  * THREE.DataUtils.toHalfFloat's truncating rule (SplatBuffer.js:469-474). */
 int gs_mesh_upload_asset(gs_mesh* m, uint32_t from, gs_asset* a, uint32_t first, uint32_t count, uint32_t min_alpha);
 
@@ -715,7 +734,7 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * host, where the last vertex stage ran its block test (1 = a kernel of its own, 0 = in every workgroup, 2 = not at all), and - with
  * count = 4 - which k_project instance that stage launched: bit 0 = the shader-permutation kernel (orthographic, fade-in, scene
  * effects, per-scene transforms, 8-bit SH, several scenes), bit 1 = it wrote window depths (a destination depth), bit 2 = the 4-byte
- * look-up word;
+ * look-up word, bit 3 = the surfel kernel of a GS_MESH_SURFEL mesh (k_project_2d) instead of k_project;
  * 7 = the blend schedule of the last draw (the one workgroup that orders the blend's bins by the previous draw's per-bin statistics,
  * what = 4, and names the deep pass's members), GS_SCHEDULE_WORDS words: {1 if it ran, blend bins, shift x, shift y (int32: this
  * draw's bin (x, y) reads the statistics of bin (x - sx, y - sy)), 1 if this draw ran the deep pass, deep_min, deep_factor, bit 0:
@@ -733,6 +752,10 @@ int gs_mesh_compute_distances(gs_mesh* m, uint32_t flags, const void* uniforms, 
  * 13 = the window depths the last draw's destination depth test compared, float per RECORD SLOT (what = 9 gives a splat's slot; only
  * the slots of visible splats are defined; count <= max_splat_count): 0.5 * ndc.z + 0.5 as the vertex stage formed it, or that value as
  * a 24-bit integer under GS_DEST_DEPTH_UNORM24; refused when the last draw had no destination depth.
+ * 15 = (GS_MESH_SURFEL meshes only, which in turn refuse what = 0) per splat, in the caller's numbering, the 80-byte vertex-stage
+ * record of a surfel, 20 words: vT as Tu xyz, Tv xyz, Tw xyz (SplatMaterial2D.js:125); vQuadCenter xy; the quad's centre in pixels;
+ * the inverse i00, i01, i10, i11 of the quad's 2x2 basis in pixels (pixel centre f is inside iff |i00 dx + i01 dy| <= 1 and
+ * |i10 dx + i11 dy| <= 1, d = f - centre); r|g<<16, b|a<<16 (unorm16); one unused word.  Zeros where the mask bit is clear.
  * 10 .. 12 read what the uploads left and need no draw.  Like the reads above, 10 and 12 go through the mesh's upload staging
  * buffer: no debug read may run while another thread uploads to the same mesh.
  *

@@ -94,7 +94,7 @@ export class SplatMesh {
                    'logLevel', 'sphericalHarmonicsDegree', 'sceneFadeInRateMultiplier', 'kernel2DSize'];
     const defaults = [SplatRenderMode.ThreeD, false, false, false, 1, true, false, false, 1024, 0, 0, 1.0, 0.3];
     names.forEach((name, k) => { this[name] = args[k] === undefined ? defaults[k] : args[k]; });
-    if (this.splatRenderMode !== SplatRenderMode.ThreeD) throw new Error('SplatMesh (HIP): only SplatRenderMode.ThreeD is implemented');
+    if (this.splatRenderMode !== SplatRenderMode.ThreeD && this.splatRenderMode !== SplatRenderMode.TwoD) throw new Error('SplatMesh (HIP): unknown splatRenderMode');
     Object.assign(this, {
       renderer: undefined, scenes: [], sceneOptions: undefined, minSphericalHarmonicsDegree: 0,
       splatTree: null, baseSplatTree: null, onSplatTreeReadyCallback: null, splatDataTextures: {},
@@ -321,11 +321,10 @@ export class SplatMesh {
     for (let k = before; k < this.scenes.length; k++) {
       const c = this.scenes[k].splatBuffer.getSplatCount();
       if (c > 0) {
-        const covariances = covLevel === 1 ? new Uint16Array(c * 6) : new Float32Array(c * 6);
         const centers = xyz.subarray(at * 3, (at + c) * 3), colors = new Uint8Array(c * 4);
         let sh = null;
         if (shComponents) sh = this.shCompressionLevel === 2 ? new Uint8Array(c * shComponents) : new Uint16Array(c * shComponents);
-        this.fillSplatDataArrays(covariances, null, null, centers, colors, sh, undefined, covLevel, 0, this.shCompressionLevel, undefined, undefined, 0, k);
+        const covariances = this._fillShapes(c, covLevel, centers, colors, sh, undefined, undefined, k);
         addon.meshUpload(this.core.handle, from + at, c, centers, covLevel === 1 ? null : covariances, covLevel === 1 ? covariances : null, colors,
                          sh && this.shCompressionLevel !== 2 ? sh : null);
         if (sh && this.shCompressionLevel === 2) addon.meshUploadShU8(this.core.handle, from + at, c, sh);
@@ -356,7 +355,27 @@ export class SplatMesh {
   _compressionLevels() { return this.scenes.map((sc) => sc.splatBuffer.compressionLevel); }
   getMaximumSplatBufferCompressionLevel() { const l = this._compressionLevels(); return l.length ? Math.max(...l) : undefined; }
   getMinimumSplatBufferCompressionLevel() { const l = this._compressionLevels(); return l.length ? Math.min(...l) : undefined; }
-  getTargetCovarianceCompressionLevel() { return this.halfPrecisionCovariancesOnGPU ? 1 : 0; }
+  // (2D mode keeps scales and rotations in fp32 whatever halfPrecisionCovariancesOnGPU says: scaleRotationCompressionLevel 0, :666-675)
+  getTargetCovarianceCompressionLevel() { return this.halfPrecisionCovariancesOnGPU && this.splatRenderMode === SplatRenderMode.ThreeD ? 1 : 0; }
+
+  // One fillSplatDataArrays call for `count` splats and what the device stores per splat in the covariance's place: the six
+  // covariance values (fp32, or half bits at covLevel 1), or - SplatRenderMode.TwoD - scale x, y, z and rotation x, y, z as
+  // SplatMesh.updateScaleRotationsPaddedData packs them (:1155-1170) from the scales / rotations this pulls through
+  // fillSplatDataArrays, i.e. with the reference's scaleOverride.z = 1 (:1856-1863).
+  _fillShapes(count, covLevel, centers, colors, sh, srcStart, srcEnd, sceneIndex) {
+    if (this.splatRenderMode !== SplatRenderMode.TwoD) {
+      const covariances = covLevel === 1 ? new Uint16Array(count * 6) : new Float32Array(count * 6);
+      this.fillSplatDataArrays(covariances, null, null, centers, colors, sh, undefined, covLevel, 0, this.shCompressionLevel, srcStart, srcEnd, 0, sceneIndex);
+      return covariances;
+    }
+    const scales = new Float32Array(count * 3), rotations = new Float32Array(count * 4), packed = new Float32Array(count * 6);
+    this.fillSplatDataArrays(null, scales, rotations, centers, colors, sh, undefined, 0, 0, this.shCompressionLevel, srcStart, srcEnd, 0, sceneIndex);
+    for (let c = 0; c < count; c++) {
+      packed[6 * c] = scales[3 * c]; packed[6 * c + 1] = scales[3 * c + 1]; packed[6 * c + 2] = scales[3 * c + 2];
+      packed[6 * c + 3] = rotations[4 * c]; packed[6 * c + 4] = rotations[4 * c + 1]; packed[6 * c + 5] = rotations[4 * c + 2];
+    }
+    return packed;
+  }
   getTargetSphericalHarmonicsCompressionLevel() { return Math.max(1, this.getMaximumSplatBufferCompressionLevel()); }
 
   // the stream behind the mesh's one scene (buildFromStream), or null
@@ -382,6 +401,7 @@ export class SplatMesh {
         sphericalHarmonicsDegree: this.minSphericalHarmonicsDegree, halfPrecisionCovariancesOnGPU: this.halfPrecisionCovariancesOnGPU,
         antialiased: this.antialiased, kernel2DSize: this.kernel2DSize, maxScreenSpaceSplatSize: this.maxScreenSpaceSplatSize,
         dynamicMode: this.dynamicMode, enableOptionalEffects: this.enableOptionalEffects,
+        renderMode2D: this.splatRenderMode === SplatRenderMode.TwoD,
         sphericalHarmonics8Bit: this.minSphericalHarmonicsDegree > 0 && this.shCompressionLevel === 2 });
       this.core.setSplatScale(this.splatScale);
       this.core.setPointCloudModeEnabled(this.pointCloudModeEnabled);
@@ -395,6 +415,11 @@ export class SplatMesh {
     if (count <= 0) { this.updateVisibleRegion(sinceLastBuildOnly); return; }
     const stream = this._stream();
     if (stream) {                                           // the rows go up as the file holds them and are decoded on the device
+      // (2D mode: the device decode emits untransformed scales and rotations, so only where fillSplatDataArrays applies no
+      // scene transform either - dynamicMode; a static 2D mesh takes its buffers through the host fills)
+      if (this.splatRenderMode === SplatRenderMode.TwoD && !this.dynamicMode) {
+        throw new Error('SplatMesh (HIP): SplatRenderMode.TwoD decodes a streamed asset on the device in dynamicMode only (no scene transform)');
+      }
       addon.meshUploadAsset(this.core.handle, fromSplat, stream.handle, stream.format, stream.maxShDegree, fromSplat, count,
                             this.scenes[0].minimumAlpha, this._streamTransform());
       this.core.splatCount = Math.max(this.core.splatCount, fromSplat + count);
@@ -404,15 +429,14 @@ export class SplatMesh {
       return;
     }
     const covLevel = this.getTargetCovarianceCompressionLevel();
-    const covariances = covLevel === 1 ? new Uint16Array(count * 6) : new Float32Array(count * 6);
     const centers = new Float32Array(count * 3);
     const colors = new Uint8Array(count * 4);
     const shComponents = [0, 9, 24][this.minSphericalHarmonicsDegree];
     let sh = null;
     if (shComponents) sh = this.shCompressionLevel === 2 ? new Uint8Array(count * shComponents) : new Uint16Array(count * shComponents);
     // updateBaseDataFromSplatBuffers (:900-913): source range [fromSplat, toSplat], written from 0 of these range arrays
-    this.fillSplatDataArrays(covariances, null, null, centers, colors, sh, undefined, covLevel, 0, this.shCompressionLevel,
-                             sinceLastBuildOnly ? fromSplat : undefined, sinceLastBuildOnly ? toSplat : undefined, 0);
+    const covariances = this._fillShapes(count, covLevel, centers, colors, sh, sinceLastBuildOnly ? fromSplat : undefined,
+                                         sinceLastBuildOnly ? toSplat : undefined, undefined);
     // A mesh of several scenes receives every scene by an upload of its own - one Morton run each, so that removeScenes can take
     // whole scenes out on the device (gs_mesh_remove refuses a border inside a run).  One scene, and a progressive load's
     // appended range, go up in one call as ever.
@@ -503,8 +527,9 @@ export class SplatMesh {
   // :1853-1902, argument for argument
   fillSplatDataArrays(covariances, scales, rotations, centers, colors, sphericalHarmonics, applySceneTransform, covarianceCompressionLevel = 0,
                       scaleRotationCompressionLevel = 0, sphericalHarmonicsCompressionLevel = 1, srcStart, srcEnd, destStart = 0, sceneIndex) {
-    const noScaleOverride = new THREE.Vector3();
-    noScaleOverride.x = noScaleOverride.y = noScaleOverride.z = undefined;       // "no override" for fillSplatScaleRotationArray
+    const scaleOverride = new THREE.Vector3();                                    // :1856-1863: none in 3D, z = 1 in 2D (a surfel is flat)
+    scaleOverride.x = scaleOverride.y = undefined;
+    scaleOverride.z = this.splatRenderMode === SplatRenderMode.ThreeD ? undefined : 1;
     const matrix = new THREE.Matrix4();
     const oneScene = Number.isInteger(sceneIndex) && sceneIndex >= 0 && sceneIndex <= this.scenes.length;
     const firstScene = oneScene ? sceneIndex : 0, lastScene = oneScene ? sceneIndex : this.scenes.length - 1;
@@ -516,7 +541,7 @@ export class SplatMesh {
       let transform;                                                         // undefined = none (what the fill methods expect)
       if (applySceneTransform) { this.getSceneTransform(k, matrix); transform = matrix; }
       if (covariances) buffer.fillSplatCovarianceArray(covariances, transform, srcStart, srcEnd, dest, covarianceCompressionLevel);
-      if (scales) buffer.fillSplatScaleRotationArray(scales, rotations, transform, srcStart, srcEnd, dest, scaleRotationCompressionLevel, noScaleOverride);
+      if (scales) buffer.fillSplatScaleRotationArray(scales, rotations, transform, srcStart, srcEnd, dest, scaleRotationCompressionLevel, scaleOverride);
       if (centers) buffer.fillSplatCenterArray(centers, transform, srcStart, srcEnd, dest);
       if (colors) buffer.fillSplatColorArray(colors, scene.minimumAlpha, srcStart, srcEnd, dest);
       if (sphericalHarmonics) {
@@ -569,6 +594,18 @@ export class SplatMesh {
     const sc = this.getScene(sceneIndex);
     sc.updateTransform(this.dynamicMode);
     outTransform.copy(sc.transform);
+  }
+  // :1981-1996 (with getLocalSplatParameters, :1827-1834): the scene's transform applied for a static mesh unless told otherwise;
+  // scale z reads 0 in 2D mode
+  getSplatScaleAndRotation(globalIndex, outScale, outRotation, applySceneTransform) {
+    if (applySceneTransform === undefined || applySceneTransform === null) applySceneTransform = !this.dynamicMode;
+    const sceneIndex = this.getSceneIndexForSplat(globalIndex);
+    let transform = null;
+    if (applySceneTransform) { transform = new THREE.Matrix4(); this.getSceneTransform(sceneIndex, transform); }
+    const scaleOverride = new THREE.Vector3();
+    scaleOverride.x = scaleOverride.y = scaleOverride.z = undefined;
+    if (this.splatRenderMode === SplatRenderMode.TwoD) scaleOverride.z = 0;
+    this.getSplatBufferForSplat(globalIndex).getSplatScaleAndRotation(this.getSplatLocalIndex(globalIndex), outScale, outRotation, transform, scaleOverride);
   }
   getSplatBufferForSplat(globalIndex) { return this.getScene(this.globalSplatIndexToSceneIndexMap[globalIndex]).splatBuffer; }
   getSceneIndexForSplat(globalIndex) { return this.globalSplatIndexToSceneIndexMap[globalIndex]; }

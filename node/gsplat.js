@@ -14,7 +14,7 @@ const path = require('path');
 const addon = require(path.join(__dirname, 'gsplat_addon.node'));
 
 const Constants = { DefaultSplatSortDistanceMapPrecision: 16, BytesPerInt: 4, BytesPerFloat: 4, MaxScenes: 32 };
-const GS_SORT_INTEGER = 1, GS_SORT_DYNAMIC = 2, GS_MESH_COV_HALF = 1, GS_MESH_SH_U8 = 2, GS_DEST_DEPTH_UNORM24 = 1;
+const GS_SORT_INTEGER = 1, GS_SORT_DYNAMIC = 2, GS_MESH_COV_HALF = 1, GS_MESH_SH_U8 = 2, GS_MESH_SURFEL = 8, GS_DEST_DEPTH_UNORM24 = 1;
 const GS_CAM_ANTIALIASED = 1, GS_CAM_POINT_CLOUD = 2, GS_CAM_ORTHOGRAPHIC = 4, GS_CAM_FADE_IN = 8, GS_CAM_SCENE_EFFECTS = 16, GS_CAM_DYNAMIC = 32;
 
 let sharedContext = null;
@@ -232,7 +232,9 @@ class SplatMeshHIP {
     this.ctx = getContext(options.device);
     this.maxSplatCount = maxSplatCount;
     this.shDegree = options.sphericalHarmonicsDegree || 0;
-    this.halfPrecisionCovariancesOnGPU = !!options.halfPrecisionCovariancesOnGPU;
+    this.renderMode2D = !!options.renderMode2D;                             // SplatRenderMode.TwoD: a GS_MESH_SURFEL mesh
+    // (2D mode stores scales and rotations in fp32 whatever halfPrecisionCovariancesOnGPU says, SplatMesh.js:666-675)
+    this.halfPrecisionCovariancesOnGPU = !!options.halfPrecisionCovariancesOnGPU && !this.renderMode2D;
     this.antialiased = !!options.antialiased;
     this.kernel2DSize = options.kernel2DSize === undefined ? 0.3 : options.kernel2DSize;
     this.maxScreenSpaceSplatSize = options.maxScreenSpaceSplatSize || 1024;
@@ -244,7 +246,8 @@ class SplatMeshHIP {
     this.orthographicMode = false;
     this.fadeIn = false;
     this.handle = addon.meshCreate(this.ctx.handle, maxSplatCount, this.shDegree,
-      (this.halfPrecisionCovariancesOnGPU ? GS_MESH_COV_HALF : 0) | (this.sphericalHarmonics8Bit ? GS_MESH_SH_U8 : 0));
+      (this.halfPrecisionCovariancesOnGPU ? GS_MESH_COV_HALF : 0) | (this.sphericalHarmonics8Bit ? GS_MESH_SH_U8 : 0) |
+      (this.renderMode2D ? GS_MESH_SURFEL : 0));
     this.splatCount = 0;
     this.renderCount = 0;
     this.indexes = null;
@@ -301,6 +304,12 @@ class SplatMeshHIP {
   resize(maxSplatCount) {
     addon.meshResize(this.handle, maxSplatCount >>> 0);
     this.maxSplatCount = maxSplatCount >>> 0;
+  }
+  // test hook: the 80-byte records of the last draw of a renderMode2D mesh, Uint32Array [20 * splatCount] (gs_mesh_debug_read 15)
+  debugRecords2D() {
+    const out = new Uint32Array(20 * this.splatCount);
+    addon.meshDebugRecords2D(this.handle, out);
+    return out;
   }
   setSceneIndexes(sceneIndexes, start = 0) { addon.meshUploadSceneIndexes(this.handle, start, sceneIndexes.length, sceneIndexes); }
   setScenes(params) { addon.meshSetScenes(this.handle, params); this.hasScenes = true; }

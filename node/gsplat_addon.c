@@ -373,6 +373,20 @@ static napi_value MeshStoragePositions(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* meshDebugRecords2D(mesh, out Uint32Array): test hook - the 80-byte vertex-stage records (20 words each) the last draw of a
+ * GS_MESH_SURFEL mesh left for splats [0, out.length / 20), by original index (gs_mesh_debug_read 15) */
+static napi_value MeshDebugRecords2D(napi_env env, napi_callback_info info) {
+    ARGS(2)
+    void* out = NULL;
+    size_t ob = 0;
+    if (!get_bytes(env, argv[1], &out, &ob) || !out || (ob % 80) != 0) { napi_throw_type_error(env, NULL, "meshDebugRecords2D: out must be a Uint32Array of 20 words per splat"); return NULL; }
+    int st;
+
+    LOCKED(st = gs_mesh_debug_read((gs_mesh*)get_external(env, argv[0]), 15, out, (uint32_t)(ob / 80)));
+    if (st < 0) return throw_gs(env, st);
+    return NULL;
+}
+
 /* meshComputeDistances(mesh, flags, uniforms Int32Array|Float32Array, sceneCount, out Int32Array|Float32Array|null, count,
  *                      sorter|null): SplatMesh.computeDistancesOnGPU's pass (gs_mesh_compute_distances).  `count` = the mesh's
  * uploaded splat count (what the pass writes into `out`).  Synchronous under the addon's lock, like every other call here: it
@@ -1195,7 +1209,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"treeSceneLeaves", TreeSceneLeaves}, {"treeGatherScenes", TreeGatherScenes},         {"assetLoad", AssetLoad},           {"assetEncodeKsplat", AssetEncodeKsplat},
         {"meshProject", MeshProject},       {"sorterSetVisibilityCull", SorterSetVisibilityCull},
         {"meshComputeDistances", MeshComputeDistances}, {"sorterSetUploadedCount", SorterSetUploadedCount},
-        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove}, {"meshReorder", MeshReorder}, {"meshResize", MeshResize}, {"sorterResize", SorterResize},{"meshStoragePositions", MeshStoragePositions},
+        {"meshRemove", MeshRemove}, {"sorterRemove", SorterRemove}, {"meshReorder", MeshReorder}, {"meshResize", MeshResize}, {"sorterResize", SorterResize},{"meshStoragePositions", MeshStoragePositions}, {"meshDebugRecords2D", MeshDebugRecords2D},
         {"groupUniqueId", GroupUniqueId},   {"groupCreate", GroupCreate},     {"groupDestroy", GroupDestroy},
         {"groupRenderGather", GroupRenderGather}, {"groupSetOverlap", GroupSetOverlap}, {"groupWait", GroupWait},
         {"meshSetDeepPass", MeshSetDeepPass}, {"meshSetDestination", MeshSetDestination}, {"meshSetDrawMode", MeshSetDrawMode},
